@@ -23,6 +23,12 @@ configs (`config.workload` carries BASELINE.json's own wording): config2 = 6-rob
 composed along the horizon, a trajectory = 128 support points), config5 = the 64-robot Conveyor instance -- 8 robots per GPU under
 `--gpus 8`, one 4096-trajectory instance under `--gpus 1`.  All with B = 64 samples, T = 100 + 1 steps.
 
+A plain run sets up, warms up, times the --steps rounds and prints the line; its `roofline` holds only what follows from the timed
+region's own time.  `--full` adds everything that takes runs of its own: the second pass with the launch profiler and the clock /
+power sampler attached, the whole-batch kernel back to back, the rocprofv3 PMC passes, the CPU baseline, the other scaling mode
+under N > 1, and the long-form record written to `--detail-dir`.  `--dump-outputs DIR` writes what the last timed round returned
+(every array a caller of the round receives) as DIR/<name>.npy; the inputs depend on the arguments alone.
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -191,7 +197,20 @@ def parse():
     ap.add_argument("--no-power-probe", action="store_true",
                     help="skip the 1.5 s of whole-batch launches timed with the clock / power sampled (outside the timed region; "
                          "~6000 extra unet_kernel launches that would swamp a rocprofv3 trace of the command)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run what takes runs of its own: profiled second pass, power probe, PMC passes, CPU baseline, the other "
+                         "scaling mode (N > 1), the long-form record; the --no-* options above switch parts of it off")
+    ap.add_argument("--detail-dir", default=os.path.join(ROOT, "bench_out"),
+                    help="--full: where the long-form measurement record bench_detail_<workload>_n<N>.json goes")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed round returned as DIR/<name>.npy (float32 / float64, "
+                         "at most 64 MB in all: a fixed seeded sample of each large array beyond that)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return args
 
 
 def cpu_model_name():
@@ -290,14 +309,41 @@ def cpu_baseline(T, B, workload, budget_s):
 
 
 def self_launch(args):
-    """`python bench.py --gpus N` with N > 1 and no launcher around it: re-exec under torch.distributed.run, one rank per GPU."""
+    """`python bench.py --gpus N` with N > 1 and no launcher around it: run torch.distributed.run as a child process, one rank per
+    GPU, and exit with its status."""
     with socket.socket() as sk:
         sk.bind(("127.0.0.1", 0))
         port = sk.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
-    os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-    os.execvp(sys.executable, cmd)
+    env = dict(os.environ)
+    env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
+    raise SystemExit(subprocess.call(cmd, env=env))
+
+
+DUMP_LIMIT_BYTES = 60_000_000          # the arrays' data; with the .npy headers well under 64 MB
+DUMP_WHOLE_BYTES = 1 << 20             # arrays up to this size are always written whole
+
+
+def dump_outputs(out_dir, arrays, limit=DUMP_LIMIT_BYTES):
+    """Write {name: tensor / array / number} as out_dir/<name>.npy: float64 stays float64, integers and booleans become float64
+    (exact), everything else float32.  Where the arrays would pass `limit` bytes together, every array above DUMP_WHOLE_BYTES
+    is replaced by the same fraction of its elements, in flat order, at indices drawn from a generator seeded by the array's name
+    and size (the same elements in every run)."""
+    import zlib
+    os.makedirs(out_dir, exist_ok=True)
+    conv = {}
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+        conv[name] = a.astype(np.float64 if a.dtype == np.float64 or a.dtype.kind in "iub" else np.float32)
+    whole = sum(a.nbytes for a in conv.values() if a.nbytes <= DUMP_WHOLE_BYTES)
+    large = sum(a.nbytes for a in conv.values() if a.nbytes > DUMP_WHOLE_BYTES)
+    keep = 1.0 if whole + large <= limit else max(limit - whole, 0) / large
+    for name, a in conv.items():
+        if keep < 1.0 and a.nbytes > DUMP_WHOLE_BYTES:
+            rng = np.random.default_rng([zlib.crc32(name.encode()), a.size])
+            a = a.reshape(-1)[np.sort(rng.choice(a.size, int(a.size * keep), replace=False))]
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
 
 
 def union_length(intervals):
@@ -317,7 +363,8 @@ def union_length(intervals):
 def run_mode(args, scaling, rank, world, dev, rehearsal, with_roofline, cpu_job=None):
     """Time args.steps planning rounds of one scaling mode with NOTHING attached (pass 1: `value`); with_roofline: the same
     rounds once more with the launch profiler and the clock / power sampler attached (pass 2: secondary launch statistics) and
-    the whole-batch kernel back to back (power probe).  Returns (value, ms_per_step, config, roofline objects or None)."""
+    the whole-batch kernel back to back (power probe).  Returns (value, ms_per_step, config, roofline, the step kernel's
+    roofline and the CPU result or None, {name: what the last timed round returned} or None without --dump-outputs)."""
     import ctypes as C
     from mmd_amd import _lib, synth
     from mmd_amd.diffusion_model import GaussianDiffusionModel
@@ -352,6 +399,7 @@ def run_mode(args, scaling, rank, world, dev, rehearsal, with_roofline, cpu_job=
         torch.cuda.synchronize()
 
     def timed_rounds(seed0):
+        """(seconds of args.steps rounds, the last round's normalised trajectories)"""
         nonlocal paths_local
         barrier()
         t0 = time.perf_counter()
@@ -364,7 +412,7 @@ def run_mode(args, scaling, rank, world, dev, rehearsal, with_roofline, cpu_job=
             torch.distributed.all_reduce(tt, op=torch.distributed.ReduceOp.MAX)
             dt = float(tt.item())
         assert torch.isfinite(trajs).all()
-        return dt
+        return dt, trajs
 
     lib = _lib.load()
     n_traj_local = RPG * B
@@ -373,7 +421,9 @@ def run_mode(args, scaling, rank, world, dev, rehearsal, with_roofline, cpu_job=
     for w in range(args.warmup):
         _, paths_local = sampler.plan_round(paths_local, seed=1000 + w)
     # ---- pass 1: the timed region.  No profiler, no sampler thread: exactly args.steps rounds between two barriers.
-    dt = timed_rounds(0)
+    dt, trajs = timed_rounds(0)
+    # what the last timed round returned: the local robots' normalised trajectories and their chosen paths (copied before pass 2)
+    outputs = {"trajectories": trajs.cpu(), "best_paths": paths_local.cpu()} if args.dump_outputs else None
     ms_per_step = dt / args.steps * 1e3
     value = args.steps * n_traj_local * world / dt
     detail = (f"{scaling}-scaling over {world} GPU(s): {n_robots}-robot {W['env']} {' '.join(str(v) for v in W['formation'])}, "
@@ -387,8 +437,6 @@ def run_mode(args, scaling, rank, world, dev, rehearsal, with_roofline, cpu_job=
                else f"robots sharded x{world}; no exchange (the workload has no inter-robot term)"),
               "noise": "in-kernel Philox4x32-10 keyed by global trajectory index",
               "weights": "random-init (numpy PCG64 seed 0)"}
-    if not with_roofline:
-        return value, ms_per_step, config, None, None
 
     # ---- roofline of the dominant kernel from the timed region alone: MFMA issue time of one round at the spec clock / the
     # round's wall time.  Every conv runs as f16x2: 3 fp16 MFMA FLOPs per fp32 GEMM FLOP, (T + 1) forwards of every local
@@ -404,6 +452,23 @@ def run_mode(args, scaling, rank, world, dev, rehearsal, with_roofline, cpu_job=
     launches_round = n_fwd * chunks
     n_launch = n_traj_local // chunks                                # trajectories per launch
     busy_s = issue_ms_round * 1e-3 / launches_round                  # MFMA issue time of ONE launch at spec clock
+    # frac = ALGORITHMIC FLOPs / time / peak: the direct-convolution fp32 FLOPs of the (T + 1) forwards of a round over the round's
+    # wall time, against the dense fp16 MFMA peak (the pipe the kernel runs on).  pipe_occupancy is a different question -- how busy
+    # the matrix pipe is, counting the THREE fp16 MFMAs the f16x2 split issues per fp32 product -- reported beside it (with the
+    # hardware counter of the same run under --full).
+    algo_tflops_round = flops_traj * n_traj_local * n_fwd / (ms_per_step * 1e-3) / 1e12
+    roofline = {
+        "bound": "mfma",
+        "kernel": "unet_kernel<4> (<= 512 trajectories per launch: unet_kernel<2>, <= 256: unet_kernel<1>): the whole TemporalUnet forward in one launch, every conv "
+                  "a direct convolution as an fp16 two-piece split of fp32 on the fp16 matrix pipe, fp32 accumulate",
+        "achieved": algo_tflops_round, "peak": PEAK_F16_MFMA_TFLOPS, "unit": "TFLOP/s", "frac": algo_tflops_round / PEAK_F16_MFMA_TFLOPS,
+        "frac_is": "algorithmic fp32 direct-conv FLOPs of the round / round time / dense fp16 MFMA peak (not the issued f16x2 FLOPs: those are pipe_occupancy)",
+        "pipe_occupancy": {"issue_frac": frac, "mfma_busy_pmc": None, "f16_mfma_per_fp32_product": 3},
+        "ms_per_step": ms_per_step, "trajectories_per_launch": n_launch, "stream_chunks": chunks,
+    }
+    if not with_roofline:
+        roofline["scope"] = "the timed region's own time only (--full adds the kernel alone, the in-loop launches, PMC traffic, power)"
+        return value, ms_per_step, config, roofline, None, outputs
 
     # ---- pass 2 (secondary): the same rounds with every UNet launch and step-kernel launch of two consecutive DDPM steps out
     # of every twelve (all stream chunks) bracketed by a HIP event pair on the stream it is launched on, and the shader clock /
@@ -418,7 +483,7 @@ def run_mode(args, scaling, rank, world, dev, rehearsal, with_roofline, cpu_job=
     watch = PowerSampler() if rank == 0 and not rehearsal else None
     if watch:
         watch.start()
-    dt2 = timed_rounds(10_000)
+    dt2, _ = timed_rounds(10_000)
     power_timed = watch.finish() if watch else None
     model.profiler = None
 
@@ -510,11 +575,8 @@ def run_mode(args, scaling, rank, world, dev, rehearsal, with_roofline, cpu_job=
     elif pmc_ref and pmc_ref.get("UNET", {}).get("FETCH_SIZE_KiB") and pmc_ref["UNET"].get("trajectories_per_launch") == n_launch:
         traffic = (2.0 * pmc_ref["UNET"]["FETCH_SIZE_KiB"] + pmc_ref["UNET"]["WRITE_SIZE_KiB"]) * 1024.0
         traffic_src = "NOT this run (the live passes failed: see pmc_log): the last committed passes, profiles/pmc_latest.json"
-    # ---- the roofline object (SURVEY 8d / VERDICT r5 #5).  frac = ALGORITHMIC FLOPs / time / peak: the direct-convolution fp32 FLOPs of
-    # the (T + 1) forwards of a round over the round's wall time, against the dense fp16 MFMA peak (the pipe the kernel runs on).
-    # pipe_occupancy is a different question -- how busy the matrix pipe is, counting the THREE fp16 MFMAs the f16x2 split issues per
-    # fp32 product -- and is reported beside it with the hardware counter of the same run.
-    algo_tflops_round = flops_traj * n_traj_local * n_fwd / (ms_per_step * 1e-3) / 1e12
+    # ---- the rest of the roofline object (SURVEY 8d / VERDICT r5 #5): the hardware counter beside pipe_occupancy, the kernel alone,
+    # the in-loop launches, the traffic
     busy_pmc = None
     if u.get("SQ_VALU_MFMA_BUSY_CYCLES") and u.get("GRBM_GUI_ACTIVE"):
         # per-SIMD MFMA-busy cycles / the launch's cycles (GRBM_GUI_ACTIVE is summed over the 8 XCDs; 1024 SIMDs)
@@ -545,25 +607,19 @@ def run_mode(args, scaling, rank, world, dev, rehearsal, with_roofline, cpu_job=
                     "accumulators: ppt_pwr = package power tracker, *_thrm = thermal) while the whole-batch launch runs back to "
                     "back; frac_at_measured_clock = MFMA issue time at the sampled clock / launch time"},
     }
-    roofline = {
-        "bound": "mfma",
-        "kernel": "unet_kernel<4> (<= 512 trajectories per launch: unet_kernel<2>, <= 256: unet_kernel<1>): the whole TemporalUnet forward in one launch, every conv "
-                  "a direct convolution as an fp16 two-piece split of fp32 on the fp16 matrix pipe, fp32 accumulate",
-        "achieved": algo_tflops_round, "peak": PEAK_F16_MFMA_TFLOPS, "unit": "TFLOP/s", "frac": algo_tflops_round / PEAK_F16_MFMA_TFLOPS,
-        "frac_is": "algorithmic fp32 direct-conv FLOPs of the round / round time / dense fp16 MFMA peak (not the issued f16x2 FLOPs: those are pipe_occupancy)",
-        "pipe_occupancy": {"issue_frac": frac, "mfma_busy_pmc": busy_pmc, "f16_mfma_per_fp32_product": 3},
+    roofline["pipe_occupancy"]["mfma_busy_pmc"] = busy_pmc
+    roofline.update({
         "kernel_alone": {"trajectories": n_traj_local, "launch_ms": solo_s * 1e3, "launches_timed": solo_n,
                          "frac": flops_traj * n_traj_local / solo_s / 1e12 / PEAK_F16_MFMA_TFLOPS, "issue_frac": busy_s * chunks / solo_s,
                          "timed_with": "HIP events around back-to-back launches of the whole local batch, outside the timed region"},
         "in_loop_launch": {"trajectories": n_launch, "stream_chunks": chunks, "avg_launch_ms": mean_ms(iv_unet),
                            "measured_concurrency": bracketed["measured_concurrency"],
                            "timed_with": "HIP event pairs on the launching stream (pass 2: the same rounds with the profiler attached)"},
-        "ms_per_step": ms_per_step, "trajectories_per_launch": n_launch, "stream_chunks": chunks,
         "traffic": traffic, "algorithmic_bytes_per_launch": algo_bytes, "wasted_ratio": None if traffic is None else traffic / algo_bytes,
         "traffic_source": traffic_src,
         "hbm_gbps_in_round": None if traffic is None else traffic * launches_round / (ms_per_step * 1e-3) / 1e9,
         "detail": detail,
-    }
+    })
     # second kernel: the fused DDPM-step + guide kernel.  It moves 3 KiB per trajectory and step (0.4 % of the HBM roof):
     # its bound is the VALU issue port -- a SIMD issues one wave64 VALU instruction per 4 cycles -- so the fraction reported is
     # 4 cycles x wave-level VALU instructions per launch / (1024 SIMDs x launch cycles), alone (the PMC pass's own dispatches) and
@@ -599,7 +655,7 @@ def run_mode(args, scaling, rank, world, dev, rehearsal, with_roofline, cpu_job=
     guide["frac"] = guide["achieved"]
     if not iv_p:
         guide["unguided"] = {"fused": "steps without guidance run inside the tail of the unet_kernel launch that produces their eps (no step-kernel launch)"}
-    return value, ms_per_step, config, roofline, (guide, cpu_result)
+    return value, ms_per_step, config, roofline, (guide, cpu_result), outputs
 
 
 PMC_PASSES = ("FETCH_SIZE", "WRITE_SIZE", "SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE",
@@ -693,28 +749,33 @@ def run_ensemble(args, rank, world, dev, rehearsal=False):
     def rounds(n):
         # the four planner calls of a round are independent.  batched (default): ONE launch sequence for all of them
         # (planners.plan_batched: a 64-trajectory UNet launch costs what a 256-trajectory one does); --concurrent-planners: one host
-        # thread + one stream per call; --sequential-planners: one after the other, the reference's loop
-        out = None
+        # thread + one stream per call; --sequential-planners: one after the other, the reference's loop.  Returns the last round's
+        # PlannerOutputs, one per local robot.
+        outs = None
         for _ in range(n):
             if mode == "sequential":
-                for p, start, goal in planners:
-                    out = p(start, goal)
+                outs = [p(start, goal) for p, start, goal in planners]
             elif mode == "concurrent":
-                out = plan_concurrently(planners)[-1]
+                outs = plan_concurrently(planners)
             else:
-                out = plan_batched(planners)[-1]
-        return out
+                outs = plan_batched(planners)
+        return outs
     rounds(args.warmup)
     barrier()
     t0 = time.perf_counter()
-    out = rounds(args.steps)
+    outs = rounds(args.steps)
     barrier()
     dt = time.perf_counter() - t0
     if world > 1:
         tt = torch.tensor([dt], dtype=torch.float64, device="cpu" if rehearsal else dev)
         torch.distributed.all_reduce(tt, op=torch.distributed.ReduceOp.MAX)
         dt = float(tt.item())
-    assert out.trajs_iters.shape[-2] == 2 * H and torch.isfinite(out.trajs_iters[-1]).all()
+    assert all(o.trajs_iters.shape[-2] == 2 * H and torch.isfinite(o.trajs_iters[-1]).all() for o in outs)
+    outputs = None
+    if args.dump_outputs:
+        # every array / number of each local robot's PlannerOutput (not t_total, a time; not constraints_l, objects)
+        outputs = {f"robot{rank * RPG + k}_{field}": v.cpu() if torch.is_tensor(v) else v for k, o in enumerate(outs) for field, v in vars(o).items()
+                   if field not in ("t_total", "constraints_l") and (torch.is_tensor(v) or isinstance(v, (bool, int, float, np.ndarray, np.number)))}
     ms = dt / args.steps * 1e3
     n_traj = RPG * B * world
     lib = _lib.load()
@@ -741,7 +802,7 @@ def run_ensemble(args, rank, world, dev, rehearsal=False):
                 "ms_per_step": ms, "unet_launches_per_round": (1 if mode == "batched" else RPG) * 2 * (T + 1),
                 "trajectories_per_launch": per_launch, "traffic": None,
                 "traffic_source": "PMC passes are wired for the sharded sampler's launches (tools/pmc_kernels.py); not collected for the planner-call workload"}
-    return n_traj * args.steps / dt, ms, config, roofline
+    return n_traj * args.steps / dt, ms, config, roofline, outputs
 
 
 def throttle_snapshot():
@@ -770,7 +831,7 @@ def main():
         return
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if world == 1 and args.gpus > 1 and "RANK" not in os.environ:
-        self_launch(args)                                   # does not return
+        self_launch(args)                                   # runs the ranks as a child process and exits with its status
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     if world != args.gpus:
@@ -790,7 +851,7 @@ def main():
         else:
             dist.init_process_group("nccl", device_id=dev)
 
-    want_cpu = rank == 0 and world == 1 and not args.no_cpu_baseline
+    want_cpu = args.full and rank == 0 and world == 1 and not args.no_cpu_baseline
 
     def cpu_job():
         """The CPU baseline in a process of its own (host cores only), started when the GPU part's timed region is over."""
@@ -800,10 +861,15 @@ def main():
 
     W = WORKLOADS[args.workload]
     if W.get("ensemble"):
-        value, ms, config, roofline = run_ensemble(args, rank, world, dev, rehearsal)
+        value, ms, config, roofline, outputs = run_ensemble(args, rank, world, dev, rehearsal)
         guide = None
     else:
-        value, ms, config, roofline, (guide, _) = run_mode(args, args.scaling, rank, world, dev, rehearsal, with_roofline=True)
+        value, ms, config, roofline, extra, outputs = run_mode(args, args.scaling, rank, world, dev, rehearsal, with_roofline=args.full)
+        guide = extra[0] if extra else None
+    if args.dump_outputs:
+        # one set per rank under N > 1 (each rank's share of the instance), within the size limit together
+        suffix = f"_rank{rank}" if world > 1 else ""
+        dump_outputs(args.dump_outputs, {name + suffix: a for name, a in outputs.items()}, DUMP_LIMIT_BYTES // world)
     out = {
         "metric": HEADLINE_METRIC if W["label"] is None else f"guided trajectories/sec (H=64, {args.diffusion_steps} denoise steps), {W['label']}",
         "value": value, "unit": "trajectories/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -816,15 +882,15 @@ def main():
     }
     if rehearsal:
         out["rehearsal"] = "all ranks on ONE GPU over gloo (MMD_BENCH_REHEARSAL=1): exercises the N>1 code path, NOT a measurement"
-    if world > 1 and not args.no_second_scaling and not args.robots_per_gpu and not W.get("ensemble"):
+    if args.full and world > 1 and not args.no_second_scaling and not args.robots_per_gpu and not W.get("ensemble"):
         other = "weak" if args.scaling == "strong" else "strong"
-        v2, ms2, cfg2, _, _ = run_mode(args, other, rank, world, dev, rehearsal, with_roofline=False)
+        v2, ms2, cfg2, _, _, _ = run_mode(args, other, rank, world, dev, rehearsal, with_roofline=False)
         out[f"{other}_scaling"] = {"value": v2, "unit": "trajectories/s", "ms_per_step": ms2, "scaling": other, "config": cfg2}
     if want_cpu:
         # the CPU baseline LAST: every GPU measurement above is finished and this process only waits for the subprocess
         torch.cuda.synchronize()
         out["cpu_baseline"] = cpu_job_result(cpu_job())
-    if rank == 0:
+    if rank == 0 and args.full:
         # the long-form measurement record (definitions, per-pass PMC logs, bracketed launches, power / clock samples) goes to a side
         # file; the line keeps the numbers
         detail = {}
@@ -834,13 +900,14 @@ def main():
         if isinstance(out.get("cpu_baseline"), dict) and "thread_sweep" in out["cpu_baseline"]:
             detail["cpu_baseline_thread_sweep"] = out["cpu_baseline"].pop("thread_sweep")
         try:
-            os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
-            path = os.path.join(ROOT, "gpurun_out", f"bench_detail_{args.workload}_n{world}.json")
+            os.makedirs(args.detail_dir, exist_ok=True)
+            path = os.path.abspath(os.path.join(args.detail_dir, f"bench_detail_{args.workload}_n{world}.json"))
             with open(path, "w") as f:
                 json.dump(detail, f, indent=1)
-            out["detail_file"] = os.path.relpath(path, ROOT)
+            out["detail_file"] = os.path.relpath(path, ROOT) if path.startswith(ROOT + os.sep) else path
         except OSError:
             pass
+    if rank == 0:
         print(json.dumps(out), flush=True)
     if world > 1:
         torch.distributed.destroy_process_group()

@@ -174,6 +174,32 @@ def test_bench_power_sampler_reads_sysfs(tmp_path):
     assert bench.PowerSampler(drm_root=str(tmp_path / "card9")).cards == []      # nothing there: rocm-smi fallback
 
 
+def test_bench_dump_outputs(tmp_path):
+    """bench.py --dump-outputs: float64, integers and booleans as float64, the rest float32; past the size limit every large array
+    is replaced by a seeded sample of its elements -- the same in every run -- and the files stay within the limit."""
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    import bench
+    big = torch.from_numpy(np.random.default_rng(3).standard_normal(600_000).astype(np.float32))
+    arrays = {"x": torch.arange(6, dtype=torch.float32).view(2, 3), "idx": torch.tensor([4, 1]), "ok": True, "cost": np.float64(0.5),
+              "big": big, "big64": big.double() * 2}
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), arrays, limit=2_000_000)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["big.npy", "big64.npy", "cost.npy", "idx.npy", "ok.npy", "x.npy"] and sorted(os.listdir(tmp_path / "b")) == names
+    for f in names:
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f))
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in names) <= 2_000_000 + 128 * len(names)
+    load = lambda f: np.load(tmp_path / "a" / f)      # noqa: E731
+    assert load("x.npy").dtype == np.float32 and np.array_equal(load("x.npy"), np.arange(6).reshape(2, 3))
+    assert load("idx.npy").dtype == np.float64 and load("idx.npy").tolist() == [4.0, 1.0]
+    assert load("ok.npy").dtype == np.float64 and float(load("ok.npy")) == 1.0 and float(load("cost.npy")) == 0.5
+    s, s64 = load("big.npy"), load("big64.npy")
+    assert s.dtype == np.float32 and s64.dtype == np.float64 and 0 < s.size < big.numel() and 0 < s64.size < big.numel()
+    assert np.isin(s, big.numpy()).all()                      # a sample of the array's own elements
+    assert s.size * 4 + s64.size * 8 + 48 <= 2_000_000
+
+
 def test_split_cost_constraints_to_tasks_golden_g13():
     """MPDEnsemble.split_cost_constraints_to_tasks + the per-tile range / transform shift of run_constrained_inference
     (mpd_ensemble.py:431-507, 515-518) against the reference's own output (g13): tile order, hard-then-soft order inside a
