@@ -311,6 +311,67 @@ int mmd_rr_collisions(const float* paths_dev, int n_robots, int horizon, float m
 int mmd_count_collisions(const float* trajs_dev, const float* paths_dev, int robot0, int n_local,
                          int samples_per_robot, int n_all, int horizon, float margin, int32_t* counts_dev, void* stream);
 
+/* ---- the search layer of CBS / PrioritizedPlanning (mmd/planners/multi_agent/cbs.py, prioritized_planning.py) ----------------
+ * Agent k of a search state is its chosen sample of a batch, with its own length and start time.  Its position at global time t
+ * is path_k[clamp(t - s_k, 0, L_k - 1)]: global_pad_paths (mmd/common/multi_agent_utils.py:120-143) without the padded tensors.
+ * The global horizon is Tg = max_k (L_k + s_k).  The collision test and the midpoint are the fp32 operations of mmd_rr_collisions:
+ * ||p_a - p_b|| < margin (margin = 2.1 * radius, robot_planar_disk.py:186) and (p_a + p_b) / 2. */
+typedef struct mmd_agent_path {
+  const float* batch_dev;        /* [B_k, L_k, 4] un-normalised (x, y, vx, vy) samples of agent k (only x, y are read) */
+  int32_t index;                 /* the chosen sample (SearchState.ix_best_path_in_batch_l[k]) */
+  int32_t length;                /* L_k: 64 for MPD, K * 64 for a K-tile MPDEnsemble */
+  int32_t start_time;            /* s_k (CBS / PrioritizedPlanning start_time_l) */
+  int32_t reserved;
+} mmd_agent_path;                /* 24 bytes */
+
+typedef struct mmd_conflict {
+  int32_t t, a, b, reserved;     /* global time step, the two agents */
+  float pa[2], pb[2];            /* both agents' positions at t (PointConflict.p_l, VertexConflict.q_l) */
+  float mid[2];                  /* (pa + pb) / 2 (PointConflict.q_l, the midpoint of check_rr_collisions) */
+  float reserved2[2];
+} mmd_conflict;                  /* 48 bytes */
+
+#define MMD_CONFLICTS_ORDERED 0  /* CBS.get_conflicts with PointConflict (cbs.py:193-246): every (t, a, b), a != b, in torch.nonzero
+                                  * row-major order -- each pair twice */
+#define MMD_CONFLICTS_PAIRS 1    /* PrioritizedPlanning.get_conflicts (prioritized_planning.py:249-298): (t, a, b), a < b, loop order */
+#define MMD_SELECT_CBS 0         /* CBS.expand 'least_collisions' (cbs.py:446-456): the first free index with the smallest count */
+#define MMD_SELECT_PP 1          /* PrioritizedPlanning.plan (prioritized_planning.py:172-182): start from idx_best_traj and its count;
+                                  * only a strictly smaller count replaces it */
+
+/* The conflict list of a search state in one launch sequence (CBS.get_conflicts, cbs.py:166-246, densification 1;
+ * PrioritizedPlanning.get_conflicts, prioritized_planning.py:249-298).  agents_dev [n_agents] (device copy of the table),
+ * horizon_global = Tg.  count_dev [1] = the number of conflicts; first_dev (may be NULL) = the first record, or t = a = b = -1
+ * when there is none; list_dev (may be NULL) = the first min(count, list_cap) records in order (count > list_cap: truncated).
+ * row_counts_dev [Tg] int32 scratch (afterwards: the count per time step). */
+int mmd_find_conflicts(const mmd_agent_path* agents_dev, int n_agents, int horizon_global, float margin, int mode,
+                       int32_t* row_counts_dev, int32_t* count_dev, mmd_conflict* first_dev, mmd_conflict* list_dev, int list_cap,
+                       void* stream);
+
+/* The 'least_collisions' choice for re-planned agent `agent` without the per-candidate get_conflicts loop (cbs.py:446-458,
+ * prioritized_planning.py:172-182): for candidate c (sample cand_idx_dev[c] of cand_batch_dev [B, L_agent, 4], in the order of
+ * trajs_final_free_idxs) the conflict count (in `mode`) of the state with that sample swapped in for agent `agent` -- the pairs
+ * without `agent` are one constant, the rest counted per candidate -- then `rule` picks one.  MMD_SELECT_PP reads one more entry,
+ * cand_idx_dev[n_free] = idx_best_traj.  The other agents' entries of agents_dev are fixed; the entry of `agent` gives L and s
+ * (its batch / index are not read).  result_dev [2] = (chosen sample index, its count), (-1, -1) for CBS without candidates;
+ * counts_dev [n_free] (may be NULL) = every candidate's count; scratch_dev: horizon_global + n_free + 1 int32. */
+int mmd_scan_candidates(const mmd_agent_path* agents_dev, int n_agents, int horizon_global, int agent, const float* cand_batch_dev,
+                        const int32_t* cand_idx_dev, int n_free, float margin, int mode, int rule, int32_t* scratch_dev,
+                        int32_t* counts_dev, int32_t* result_dev, void* stream);
+
+/* The constraint group the two searches build from the other agents' chosen paths, as ONE ELL block (the layout of
+ * mmd_pack_constraints, bitwise the table it makes from the equivalent MultiPointConstraint, in the same slot order):
+ *   soft (hard = 0): CBS.create_soft_constraints_from_other_agents_paths (cbs.py:468-508) -- for every agent j != agent of
+ *     agents_dev[0, n_state) and every t_j < L_j: t_i = t_j + s_j - s_i is kept iff 1 <= t_i <= agent_last_t (L_i - 1 when agent i
+ *     has a path in the state; agent_last_t < 0: L_j - 1, the reference's rule when it has none), range (t_i, t_i + 1);
+ *   hard (hard = 1): PrioritizedPlanning.plan (prioritized_planning.py:149-159) -- the same points, the ranges clamped to
+ *     (max(0, min(t0, H - 1)), min(H - 1, t1)).
+ * Every point has radius `radius` (vertex_constraint_radius).  ell_out_dev [n_slots][H][4]; n_slots = the largest number of agents
+ * with a point active at one t (a function of the lengths and start times only: the caller sizes it; the kernel never writes past
+ * it).  grp_slot_off_dev [2], grp_weight_dev [1] (= weight), robot_grp_off_dev [2]: one group for one robot, or all three NULL. */
+int mmd_path_constraints(const mmd_agent_path* agents_dev, int n_state, int agent, int agent_start_time, int agent_last_t, int hard,
+                         int horizon, float radius, float weight, int n_slots, float* ell_out_dev, int32_t* grp_slot_off_dev,
+                         float* grp_weight_dev, int32_t* robot_grp_off_dev, void* stream);
+
 /* ------------------------------------------------------------------------------------------------------------
  * Post-sampling selection: the step right after the sampler in MPD.__call__
  * (mmd/planners/single_agent/mpd.py:344-405)

@@ -70,6 +70,20 @@ class CrossCond(C.Structure):
                 ("rel", C.c_float * 4), ("boundary", C.c_float * 4), ("by_robot_dev", C.c_void_p)]
 
 
+class AgentPath(C.Structure):
+    _fields_ = [("batch_dev", C.c_void_p), ("index", C.c_int32), ("length", C.c_int32), ("start_time", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class Conflict(C.Structure):
+    _fields_ = [("t", C.c_int32), ("a", C.c_int32), ("b", C.c_int32), ("reserved", C.c_int32), ("pa", C.c_float * 2),
+                ("pb", C.c_float * 2), ("mid", C.c_float * 2), ("reserved2", C.c_float * 2)]
+
+
+CONFLICTS_ORDERED, CONFLICTS_PAIRS = 0, 1               # MMD_CONFLICTS_*
+SELECT_CBS, SELECT_PP = 0, 1                            # MMD_SELECT_*
+
+
 _SIGNATURES = {
     "mmd_abi_version": (C.c_int, []),
     "mmd_last_error": (C.c_char_p, []),
@@ -104,6 +118,12 @@ _SIGNATURES = {
     "mmd_rr_collisions": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mmd_count_collisions": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
                                        C.c_void_p, C.c_void_p]),
+    "mmd_find_conflicts": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_int, C.c_void_p]),
+    "mmd_scan_candidates": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_int,
+                                      C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mmd_path_constraints": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float,
+                                       C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mmd_postprocess_trajs": (C.c_int, [C.POINTER(GuideDesc), C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                         C.POINTER(C.c_float), C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int,
                                         C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -83,9 +83,39 @@ class CostConstraint:
         self.is_soft = is_soft
 
 
-def pack_constraints(per_robot_groups: Sequence[Sequence[Tuple[CostConstraint, float]]], device, return_max_slots=False):
+class PathConstraintGroup(CostConstraint):
+    """The group a multi_agent.PathConstraints puts on its agent, in a pack: the host pack reserves its slots (n_slots points, each active at
+    t = 0 only, fill exactly n_slots slots) and mmd_path_constraints then writes the whole block on the device (build_path_groups)."""
+
+    def __init__(self, spec, n_slots):
+        self.spec, self.n_slots = spec, int(n_slots)
+        self.n_support_points = H
+        self.qs = np.zeros((self.n_slots, 2), dtype=np.float32)
+        self.traj_ranges = np.tile(np.array([[0.0, 1.0]], dtype=np.float32), (self.n_slots, 1))
+        self.radii = np.full(self.n_slots, spec.radius, dtype=np.float32)
+        self.is_soft = spec.is_soft
+
+
+def path_constraint_group(spec):
+    """PathConstraintGroup of a multi_agent.PathConstraints, or None when the reference would add no group (no point at all)."""
+    has_points, n_slots = spec.extent()
+    return PathConstraintGroup(spec, n_slots) if has_points else None
+
+
+def build_path_groups(per_robot_groups, cons, host_offsets):
+    """Write every PathConstraintGroup's block into the packed table `cons` (pack_constraints' output) at its slots."""
+    flat = [g for groups in per_robot_groups for g, _ in groups]
+    for k, g in enumerate(flat):
+        if isinstance(g, PathConstraintGroup) and g.n_slots > 0:
+            off = int(host_offsets[k])
+            g.spec.build(0.0, ell_out=cons[0][off:off + g.n_slots], n_slots=g.n_slots)
+
+
+def pack_constraints(per_robot_groups: Sequence[Sequence[Tuple[CostConstraint, float]]], device, return_max_slots=False,
+                     host_offsets=None):
     """per_robot_groups[r] = [(CostConstraint, weight), ...].  Returns device tensors
-    (ell [n_slots,H,4] f32, grp_slot_off [G+1] i32, grp_weight [G] f32, robot_grp_off [R+1] i32) or None if empty."""
+    (ell [n_slots,H,4] f32, grp_slot_off [G+1] i32, grp_weight [G] f32, robot_grp_off [R+1] i32) or None if empty.
+    `host_offsets` (a list): receives grp_slot_off on the host."""
     lib = _lib.load()
     flat = [gw for groups in per_robot_groups for gw in groups]
     if not flat:
@@ -116,6 +146,8 @@ def pack_constraints(per_robot_groups: Sequence[Sequence[Tuple[CostConstraint, f
     words = buf.view(np.int32)
     grp_slot_off = words[n_ell:n_ell + G + 1]
     grp_slot_off[1:] = np.cumsum(np.array(list(slots), dtype=np.int64))
+    if host_offsets is not None:
+        host_offsets.extend(int(v) for v in grp_slot_off)
     buf[n_ell + G + 1:n_ell + 2 * G + 1] = [w for _, w in flat]
     robot_grp_off = words[n_ell + 2 * G + 1:]
     robot_grp_off[1:] = np.cumsum([len(g) for g in per_robot_groups])

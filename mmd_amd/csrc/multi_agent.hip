@@ -4,8 +4,15 @@
 //     (deps/torch_robotics/torch_robotics/robots/robot_planar_disk.py:173-203) as called by CBS.get_conflicts
 //     (mmd/planners/multi_agent/cbs.py:166-246) for equal start times and densification 1;
 //   * the 'least_collisions' batch scan (cbs.py:446-458): for every sample of a robot's batch, how many (t, other robot)
-//     pairs collide with the other robots' best paths.
+//     pairs collide with the other robots' best paths;
+//   * the search layer of CBS / PrioritizedPlanning over agents with their own path lengths and start times
+//     (cbs.py:166-246, :446-508; prioritized_planning.py:149-182, :212-298): the conflict list of a search state, the
+//     'least_collisions' choice of a re-planned agent, and the soft / hard constraint table built from the other agents' paths.
+//     Agent k's position at global time t is path_k[clamp(t - s_k, 0, L_k - 1)] (global_pad_paths, multi_agent_utils.py:120-143,
+//     without the padded tensors).
 #include <hip/hip_runtime.h>
+
+#include <climits>
 
 #include "../../include/mmd_amd.h"
 #include "common.h"
@@ -50,6 +57,219 @@ __global__ __launch_bounds__(256) void count_collisions_kernel(const float4* __r
   if (t == 0) counts[traj] = c;
 }
 
+
+// ---- search layer over mmd_agent_path tables ----------------------------------------------------------------------------------------
+__device__ __forceinline__ float2 sample_pos(const float* batch, int index, int length, int u) {
+  const float* p = batch + ((size_t)index * length + u) * 4;
+  return make_float2(p[0], p[1]);
+}
+
+// global_pad_paths: the start state before s_k, the last state after s_k + L_k - 1
+__device__ __forceinline__ float2 agent_pos(const mmd_agent_path& a, int t) {
+  int u = t - a.start_time;
+  u = u < 0 ? 0 : (u > a.length - 1 ? a.length - 1 : u);
+  return sample_pos(a.batch_dev, a.index, a.length, u);
+}
+
+// the collision test of rr_collisions_kernel, operation for operation
+__device__ __forceinline__ bool rr_hit(float2 a, float2 b, float margin) {
+  const float dx = a.x - b.x, dy = a.y - b.y;
+  return sqrtf(dx * dx + dy * dy) < margin;
+}
+
+// cell c of row t: (a, b) = (c / n, c % n); MMD_CONFLICTS_ORDERED keeps a != b (torch.nonzero order of cbs.py:193-246),
+// MMD_CONFLICTS_PAIRS keeps a < b (the loops of prioritized_planning.py:271-298); `exclude` drops every pair with that agent
+__device__ __forceinline__ bool cell_kept(int a, int b, int mode, int exclude) {
+  if (a == exclude || b == exclude) return false;
+  return mode == MMD_CONFLICTS_PAIRS ? a < b : a != b;
+}
+
+// exclusive prefix of `flag` over a 256-thread block in thread order; returns the block total
+__device__ __forceinline__ int block_prefix(bool flag, int* lds4, int& prefix) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const unsigned long long bal = __ballot(flag);
+  const int in_wave = __popcll(bal & ((1ull << lane) - 1ull));
+  if (lane == 0) lds4[wave] = __popcll(bal);
+  __syncthreads();
+  int before = 0, total = 0;
+#pragma unroll
+  for (int w = 0; w < 4; ++w) {
+    before += w < wave ? lds4[w] : 0;
+    total += lds4[w];
+  }
+  __syncthreads();
+  prefix = before + in_wave;
+  return total;
+}
+
+__device__ __forceinline__ int block_sum(int v, int* lds4) {
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
+  if ((threadIdx.x & 63) == 0) lds4[threadIdx.x >> 6] = v;
+  __syncthreads();
+  const int s = lds4[0] + lds4[1] + lds4[2] + lds4[3];
+  __syncthreads();
+  return s;
+}
+
+// one workgroup per global time step t: the number of conflicts in row t
+__global__ __launch_bounds__(256) void conflict_rows_kernel(const mmd_agent_path* __restrict__ agents, int n, float margin,
+                                                             int mode, int exclude, int* __restrict__ row_counts) {
+  __shared__ int lds4[4];
+  const int t = blockIdx.x;
+  int c = 0;
+  for (int cell = threadIdx.x; cell < n * n; cell += 256) {
+    const int a = cell / n, b = cell % n;
+    if (cell_kept(a, b, mode, exclude)) c += rr_hit(agent_pos(agents[a], t), agent_pos(agents[b], t), margin) ? 1 : 0;
+  }
+  c = block_sum(c, lds4);
+  if (threadIdx.x == 0) row_counts[t] = c;
+}
+
+// one workgroup per t: the records of row t at their place in the (t, a, b) row-major list
+__global__ __launch_bounds__(256) void conflict_emit_kernel(const mmd_agent_path* __restrict__ agents, int n, int Tg, float margin,
+                                                             int mode, const int* __restrict__ row_counts, int* __restrict__ count,
+                                                             mmd_conflict* __restrict__ first, mmd_conflict* __restrict__ list,
+                                                             int list_cap) {
+  __shared__ int lds4[4];
+  const int t = blockIdx.x;
+  int before = 0;
+  for (int k = threadIdx.x; k < t; k += 256) before += row_counts[k];
+  before = block_sum(before, lds4);
+  if (t == Tg - 1 && threadIdx.x == 0) {
+    const int total = before + row_counts[t];
+    *count = total;
+    if (total == 0 && first) {
+      mmd_conflict none{};
+      none.t = none.a = none.b = -1;
+      *first = none;
+    }
+  }
+  if (row_counts[t] == 0) return;
+  const bool want_first = first && before == 0;
+  const bool want_list = list && before < list_cap;
+  if (!want_first && !want_list) return;
+  int base = before;
+  for (int c0 = 0; c0 < n * n; c0 += 256) {
+    const int cell = c0 + threadIdx.x;
+    const int a = cell / n, b = cell % n;
+    bool hit = false;
+    float2 pa = make_float2(0.f, 0.f), pb = pa;
+    if (cell < n * n && cell_kept(a, b, mode, -1)) {
+      pa = agent_pos(agents[a], t);
+      pb = agent_pos(agents[b], t);
+      hit = rr_hit(pa, pb, margin);
+    }
+    int prefix;
+    const int total = block_prefix(hit, lds4, prefix);
+    if (hit) {
+      const int idx = base + prefix;
+      mmd_conflict r;
+      r.t = t; r.a = a; r.b = b; r.reserved = 0;
+      r.pa[0] = pa.x; r.pa[1] = pa.y; r.pb[0] = pb.x; r.pb[1] = pb.y;
+      r.mid[0] = (pa.x + pb.x) / 2.f; r.mid[1] = (pa.y + pb.y) / 2.f;
+      r.reserved2[0] = r.reserved2[1] = 0.f;
+      if (idx == 0 && first) *first = r;
+      if (list && idx < list_cap) list[idx] = r;
+    }
+    base += total;
+  }
+}
+
+// one wave per candidate, lane = global time step: #{(t, j != self) : candidate(t) hits agent j(t)}
+__global__ __launch_bounds__(256) void candidate_pairs_kernel(const mmd_agent_path* __restrict__ agents, int n, int Tg, int self,
+                                                               const float* __restrict__ cand_batch, const int* __restrict__ cand_idx,
+                                                               int n_cand, float margin, int* __restrict__ pair_counts) {
+  const int lane = threadIdx.x & 63;
+  const int c = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (c >= n_cand) return;
+  const mmd_agent_path me = agents[self];
+  const int idx = cand_idx[c];
+  int hits = 0;
+  for (int t = lane; t < Tg; t += 64) {
+    int u = t - me.start_time;
+    u = u < 0 ? 0 : (u > me.length - 1 ? me.length - 1 : u);
+    const float2 p = sample_pos(cand_batch, idx, me.length, u);
+    for (int j = 0; j < n; ++j)
+      if (j != self) hits += rr_hit(p, agent_pos(agents[j], t), margin) ? 1 : 0;
+  }
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) hits += __shfl_xor(hits, m);
+  if (lane == 0) pair_counts[c] = hits;
+}
+
+// the selection rule over the n_free candidates (candidate n_free = the PP rule's starting sample), one workgroup
+__global__ __launch_bounds__(256) void select_candidate_kernel(const int* __restrict__ base_rows, int Tg, const int* __restrict__ pair_counts,
+                                                                const int* __restrict__ cand_idx, int n_free, int mult, int rule,
+                                                                int* __restrict__ counts_out, int* __restrict__ result) {
+  __shared__ int lds4[4];
+  __shared__ long long best_w[4];
+  int b = 0;
+  for (int k = threadIdx.x; k < Tg; k += 256) b += base_rows[k];
+  const int base = block_sum(b, lds4);
+  // (count, position) packed so that the minimum is the FIRST candidate with the smallest count
+  long long best = LLONG_MAX;
+  for (int c = threadIdx.x; c < n_free; c += 256) {
+    const int total = base + mult * pair_counts[c];
+    if (counts_out) counts_out[c] = total;
+    const long long key = ((long long)total << 32) | (unsigned)c;
+    best = key < best ? key : best;
+  }
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) {
+    const long long o = __shfl_xor(best, m);
+    best = o < best ? o : best;
+  }
+  if ((threadIdx.x & 63) == 0) best_w[threadIdx.x >> 6] = best;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < 4; ++w) best = best_w[w] < best ? best_w[w] : best;
+    int pick = -1, count = -1;
+    if (best != LLONG_MAX) {
+      pick = cand_idx[(int)(best & 0xffffffffll)];
+      count = (int)(best >> 32);
+    }
+    if (rule == MMD_SELECT_PP) {                 // start from idx_best_traj; only a strictly smaller count replaces it
+      const int init = base + mult * pair_counts[n_free];
+      if (pick < 0 || count >= init) {
+        pick = cand_idx[n_free];
+        count = init;
+      }
+    }
+    result[0] = pick;
+    result[1] = count;
+  }
+}
+
+// thread t of agent `self`'s horizon: slot s holds the s-th other agent (in agent order) with a point active at t
+__global__ void path_constraints_kernel(const mmd_agent_path* __restrict__ agents, int n_state, int self, int self_start, int self_last,
+                                        int hard, int horizon, float radius, float weight, int n_slots, float4* __restrict__ ell,
+                                        int* __restrict__ grp_slot_off, float* __restrict__ grp_weight, int* __restrict__ robot_grp_off) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t == 0 && grp_slot_off) {                   // one group of n_slots slots for one robot
+    grp_slot_off[0] = 0; grp_slot_off[1] = n_slots;
+    grp_weight[0] = weight;
+    robot_grp_off[0] = 0; robot_grp_off[1] = 1;
+  }
+  if (t >= horizon) return;
+  int fill = 0;
+  // soft: range (t, t + 1); hard: clamped to (max(0, min(t, H-1)), min(H-1, t + 1)), i.e. active only for t <= H - 2
+  const bool active = t >= 1 && (!hard || t <= horizon - 2);
+  if (active) {
+    for (int j = 0; j < n_state && fill < n_slots; ++j) {
+      if (j == self) continue;
+      const mmd_agent_path o = agents[j];
+      const int tj = t + self_start - o.start_time;
+      const int last = self_last >= 0 ? self_last : o.length - 1;
+      if (tj < 0 || tj > o.length - 1 || t > last) continue;
+      const float2 p = sample_pos(o.batch_dev, o.index, o.length, tj);
+      ell[(size_t)fill * horizon + t] = make_float4(p.x, p.y, radius, radius * fabsf(radius));
+      ++fill;
+    }
+  }
+  for (; fill < n_slots; ++fill) ell[(size_t)fill * horizon + t] = make_float4(0.f, 0.f, -1.f, -1.f);
+}
+
 }  // namespace mmd
 
 using namespace mmd;
@@ -77,6 +297,57 @@ int mmd_count_collisions(const float* trajs_dev, const float* paths_dev, int rob
   hipLaunchKernelGGL(count_collisions_kernel, dim3((n_traj + 3) / 4), dim3(256), 0, (hipStream_t)stream,
                      (const float4*)trajs_dev, (const float2*)paths_dev, robot0, samples_per_robot, n_traj, n_all, margin,
                      counts_dev);
+  MMD_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+int mmd_find_conflicts(const mmd_agent_path* agents_dev, int n_agents, int horizon_global, float margin, int mode,
+                       int32_t* row_counts_dev, int32_t* count_dev, mmd_conflict* first_dev, mmd_conflict* list_dev, int list_cap,
+                       void* stream) {
+  MMD_REQUIRE(agents_dev && row_counts_dev && count_dev && n_agents >= 1 && horizon_global >= 1, "mmd_find_conflicts: bad arguments");
+  MMD_REQUIRE(mode == MMD_CONFLICTS_ORDERED || mode == MMD_CONFLICTS_PAIRS, "mmd_find_conflicts: unknown mode %d", mode);
+  MMD_REQUIRE(list_cap >= 0 && (list_cap == 0 || list_dev), "mmd_find_conflicts: list_cap without a list");
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(conflict_rows_kernel, dim3(horizon_global), dim3(256), 0, st, agents_dev, n_agents, margin, mode, -1,
+                     row_counts_dev);
+  hipLaunchKernelGGL(conflict_emit_kernel, dim3(horizon_global), dim3(256), 0, st, agents_dev, n_agents, horizon_global, margin, mode,
+                     row_counts_dev, count_dev, first_dev, list_cap > 0 ? list_dev : nullptr, list_cap);
+  MMD_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+int mmd_scan_candidates(const mmd_agent_path* agents_dev, int n_agents, int horizon_global, int agent, const float* cand_batch_dev,
+                        const int32_t* cand_idx_dev, int n_free, float margin, int mode, int rule, int32_t* scratch_dev,
+                        int32_t* counts_dev, int32_t* result_dev, void* stream) {
+  MMD_REQUIRE(agents_dev && cand_batch_dev && cand_idx_dev && scratch_dev && result_dev, "mmd_scan_candidates: NULL argument");
+  MMD_REQUIRE(n_agents >= 1 && agent >= 0 && agent < n_agents && horizon_global >= 1 && n_free >= 0, "mmd_scan_candidates: bad arguments");
+  MMD_REQUIRE(mode == MMD_CONFLICTS_ORDERED || mode == MMD_CONFLICTS_PAIRS, "mmd_scan_candidates: unknown mode %d", mode);
+  MMD_REQUIRE(rule == MMD_SELECT_CBS || rule == MMD_SELECT_PP, "mmd_scan_candidates: unknown rule %d", rule);
+  const int n_cand = n_free + (rule == MMD_SELECT_PP ? 1 : 0);
+  hipStream_t st = (hipStream_t)stream;
+  int32_t* base_rows = scratch_dev;                    // [horizon_global]
+  int32_t* pairs = scratch_dev + horizon_global;       // [n_cand]
+  hipLaunchKernelGGL(conflict_rows_kernel, dim3(horizon_global), dim3(256), 0, st, agents_dev, n_agents, margin, mode, agent, base_rows);
+  if (n_cand > 0)
+    hipLaunchKernelGGL(candidate_pairs_kernel, dim3((n_cand + 3) / 4), dim3(256), 0, st, agents_dev, n_agents, horizon_global, agent,
+                       cand_batch_dev, (const int*)cand_idx_dev, n_cand, margin, pairs);
+  hipLaunchKernelGGL(select_candidate_kernel, dim3(1), dim3(256), 0, st, base_rows, horizon_global, pairs, (const int*)cand_idx_dev,
+                     n_free, mode == MMD_CONFLICTS_ORDERED ? 2 : 1, rule, counts_dev, result_dev);
+  MMD_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+int mmd_path_constraints(const mmd_agent_path* agents_dev, int n_state, int agent, int agent_start_time, int agent_last_t, int hard,
+                         int horizon, float radius, float weight, int n_slots, float* ell_out_dev, int32_t* grp_slot_off_dev,
+                         float* grp_weight_dev, int32_t* robot_grp_off_dev, void* stream) {
+  MMD_REQUIRE(agents_dev && ell_out_dev && n_state >= 0 && n_slots >= 0, "mmd_path_constraints: bad arguments");
+  MMD_REQUIRE(horizon == H, "mmd_path_constraints: horizon must be %d", H);
+  const bool offsets = grp_slot_off_dev && grp_weight_dev && robot_grp_off_dev;
+  MMD_REQUIRE(offsets || !(grp_slot_off_dev || grp_weight_dev || robot_grp_off_dev), "mmd_path_constraints: all three offset arrays or none");
+  if (n_slots > 0 || offsets)
+    hipLaunchKernelGGL(path_constraints_kernel, dim3(1), dim3(H), 0, (hipStream_t)stream, agents_dev, n_state, agent, agent_start_time,
+                       agent_last_t, hard, H, radius, weight, n_slots, (float4*)ell_out_dev, offsets ? grp_slot_off_dev : nullptr,
+                       grp_weight_dev, robot_grp_off_dev);
   MMD_HIP_CHECK(hipGetLastError());
   return 0;
 }

@@ -10,7 +10,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .constraints import CostConstraint, pack_constraints
+from .constraints import CostConstraint, PathConstraintGroup, build_path_groups, pack_constraints
 from .environments import LIMITS, sdf_grid_texture
 
 ROBOT_RADIUS = 0.05                 # mmd/config/mmd_params.py:30
@@ -126,7 +126,12 @@ class GuideManagerTrajectoriesWithVelocity:
             return self._external_cons
         if self._cons_dirty:
             groups = [list(zip(c, w)) for c, w in zip(self.extra_cost_l, self.extra_costs_grad_weight_l)]
-            self._cons, self._max_slots = pack_constraints(groups, self.device, return_max_slots=True)
+            offsets = []
+            self._cons, self._max_slots = pack_constraints(groups, self.device, return_max_slots=True, host_offsets=offsets)
+            if any(isinstance(c, PathConstraintGroup) for cl in self.extra_cost_l for c in cl):
+                if self._soft_paths is not None:
+                    raise ValueError("soft_paths and path constraints in one call")
+                build_path_groups(groups, self._cons, offsets)      # (the blocks built on the device, in their reserved slots)
             if self._soft_paths is not None and self._soft_paths[0].shape[0] > 1:
                 from .constraints import soft_constraints_from_paths
                 paths_all, idx, radius, weight = self._soft_paths

@@ -412,14 +412,22 @@ class MPD:
         return [CostConstraint(self.robot, self.n_support_points, q_l=c.get_q_l(), traj_range_l=c.get_t_range_l(),
                                radius_l=c.radius_l, is_soft=c.is_soft) for c in (constraints_l or [])]
 
-    def __call__(self, start_state_pos, goal_state_pos, constraints_l=None, experience=None, *args, soft_paths=None, **kwargs):
+    def __call__(self, start_state_pos, goal_state_pos, constraints_l=None, experience=None, *args, soft_paths=None, path_constraints=None,
+                 **kwargs):
         """`soft_paths` (an extension; None = the reference's call): (paths_all [N, 64, 2] device tensor, this agent's index) -- the soft
         constraints from the other agents' current best paths (cbs.py:468-508) as one tensor instead of a MultiPointConstraint of
         (N - 1) x 63 tiny tensors in `constraints_l`; built on the device, placed after the groups of `constraints_l`, weighted with
-        weight_grad_cost_soft_constraints: bitwise the list form's result without its 0.14 ms of host conversion per call."""
+        weight_grad_cost_soft_constraints: bitwise the list form's result without its 0.14 ms of host conversion per call.
+        `path_constraints` (an extension, the general form of soft_paths): a multi_agent.PathConstraints -- the other agents' chosen paths
+        with their own lengths and start times, the agents in the state, soft (ECBS, cbs.py:468-508) or hard (PrioritizedPlanning,
+        prioritized_planning.py:149-159); its group is built on the device after the groups of `constraints_l`, weighted with
+        weight_grad_cost_soft_constraints / weight_grad_cost_constraints: bitwise `constraints_l + path_constraints.constraint_list()`."""
         _check_states(self, start_state_pos, goal_state_pos)
+        if soft_paths is not None and path_constraints is not None:
+            raise ValueError("MPD.__call__: soft_paths or path_constraints, not both")
         cost_constraints_l = self._cost_constraints(constraints_l)
         self._soft_paths = soft_paths
+        self._path_constraints = path_constraints
         with _Timer() as timer:
             if experience is None:
                 chain = self.run_constrained_inference(cost_constraints_l, **kwargs)
@@ -432,10 +440,21 @@ class MPD:
         self.recent_call_data = out
         return out
 
+    def _path_group(self, path_constraints):
+        """[(PathConstraintGroup, weight)] of a PathConstraints (empty when the reference would add no group)."""
+        from .constraints import path_constraint_group
+        g = path_constraint_group(path_constraints) if path_constraints is not None else None
+        if g is None:
+            return []
+        return [(g, self.weight_grad_cost_soft_constraints if g.is_soft else self.weight_grad_cost_constraints)]
+
     def _add_constraints(self, cost_constraints_l):
         self.guide.add_extra_costs(cost_constraints_l,
                                    [self.weight_grad_cost_soft_constraints if c.is_soft else
                                     self.weight_grad_cost_constraints for c in cost_constraints_l])
+        path_group, self._path_constraints = self._path_group(getattr(self, "_path_constraints", None)), None
+        for g, w in path_group:
+            self.guide.add_extra_costs([g], [w])
         soft_paths, self._soft_paths = getattr(self, "_soft_paths", None), None
         if soft_paths is not None:
             self.guide.set_soft_paths(soft_paths[0], soft_paths[1], weight=self.weight_grad_cost_soft_constraints)
@@ -626,8 +645,13 @@ class MPDEnsemble:
         finally:
             self._reset()
 
-    def __call__(self, start_state_pos, goal_state_pos, constraints_l=None, experience=None, *args, **kwargs):
+    def __call__(self, start_state_pos, goal_state_pos, constraints_l=None, experience=None, *args, path_constraints=None, **kwargs):
+        """`path_constraints` (a multi_agent.PathConstraints): appended to constraints_l in its list form (the constraints are split per
+        tile on the host, split_cost_constraints_to_tasks); PlannerOutput.constraints_l stays the caller's list."""
         _check_states(self, start_state_pos, goal_state_pos)
+        given_l = constraints_l
+        if path_constraints is not None:
+            constraints_l = list(constraints_l or []) + path_constraints.constraint_list()
         cl = [CostConstraint(self.robot, HORIZON, q_l=c.get_q_l(), traj_range_l=c.get_t_range_l(), radius_l=c.radius_l,
                              is_soft=c.is_soft) for c in (constraints_l or [])]
         with _Timer() as timer:
@@ -645,7 +669,7 @@ class MPDEnsemble:
         out = PlannerOutput()
         out.t_total = timer.elapsed
         _fill_output_ensemble(out, self.task, tile_final, trajs_iters)
-        out.constraints_l = constraints_l
+        out.constraints_l = given_l
         self.recent_call_data = out
         return out
 
@@ -853,7 +877,8 @@ def _run_mpd_group(calls, seeds):
     per_robot = []
     for p, c in zip(planners, calls):
         cl = p._cost_constraints(c[3] if len(c) > 3 else None)
-        per_robot.append([(cc, p.weight_grad_cost_soft_constraints if cc.is_soft else p.weight_grad_cost_constraints) for cc in cl])
+        per_robot.append([(cc, p.weight_grad_cost_soft_constraints if cc.is_soft else p.weight_grad_cost_constraints) for cc in cl]
+                         + p._path_group(c[5] if len(c) > 5 else None))
     _load_constraints(cg, per_robot)
     hard = {row: torch.stack([p.hard_conds[row] for p in planners]) for row in p0.hard_conds}
     experiences = [c[4] if len(c) > 4 else None for c in calls]                  # (all or none: _batch_key)
@@ -892,8 +917,9 @@ def _run_ensemble_group(calls, seeds):
     cgs = {j: _combined_guide([p.guides[j] for p in planners]) for j in keys}
     per_tile = {j: [[] for _ in range(R)] for j in keys}
     for k, (p, c) in enumerate(zip(planners, calls)):
+        given = list((c[3] if len(c) > 3 else None) or []) + (c[5].constraint_list() if len(c) > 5 and c[5] is not None else [])
         cl = [CostConstraint(p.robot, HORIZON, q_l=cc.get_q_l(), traj_range_l=cc.get_t_range_l(), radius_l=cc.radius_l,
-                             is_soft=cc.is_soft) for cc in ((c[3] if len(c) > 3 else None) or [])]
+                             is_soft=cc.is_soft) for cc in given]
         for task_id, tile_cl in p.split_cost_constraints_to_tasks(cl).items():
             for cc in tile_cl:
                 cc.traj_ranges = cc.traj_ranges - task_id * HORIZON                       # mpd_ensemble.py:517
@@ -936,6 +962,13 @@ def _run_ensemble_group(calls, seeds):
     return _split_outputs(calls, planners, r, summary, trajs_iters, B, timer.elapsed, ensemble_tasks=True)
 
 
+def _call_one(call, seed):
+    """One call of a plan_batched list on its own: the sixth element, if any, is the path_constraints keyword."""
+    if len(call) > 5:
+        return call[0](*call[1:5], path_constraints=call[5], seed=seed)
+    return call[0](*call[1:], seed=seed)
+
+
 def plan_batched(calls, seeds=None):
     """Independent planner calls as ONE launch sequence: the calls that share a device model, schedule and sampler settings (_batch_key)
     are packed robot-major into one [R * n_samples, H, D] batch -- each with its own start / goal, map index, constraint groups, tile
@@ -945,7 +978,9 @@ def plan_batched(calls, seeds=None):
     does.  Same signature and seeds as plan_concurrently, and BITWISE the same results as the calls made one after the other with those
     seeds (mmd_sampler_desc.robot_seeds_dev: one Philox stream per robot).  Re-plans from an experience -- the two children of a CBS
     expansion re-plan two different agents independently (cbs.py:397-432) -- pack with each other.  Calls that cannot be packed
-    (`diffusion_prior_then_guide`, extra objects) run on their own, in list order, with their seed."""
+    (`diffusion_prior_then_guide`, extra objects) run on their own, in list order, with their seed.  A call may carry a sixth element,
+    the `path_constraints` of MPD.__call__ / MPDEnsemble.__call__ (None = none): the soft constraints of an ECBS child, the hard ones
+    of a PrioritizedPlanning agent."""
     calls = [tuple(c) for c in calls]
     if len({id(c[0]) for c in calls}) != len(calls):
         raise ValueError("plan_batched: a planner appears twice (a planner call is not re-entrant)")
@@ -966,7 +1001,7 @@ def plan_batched(calls, seeds=None):
         js = groups[key]
         if key[0] == "single" or len(js) == 1:
             for j in js:
-                outs[j] = calls[j][0](*calls[j][1:], seed=int(seeds[j]))
+                outs[j] = _call_one(calls[j], int(seeds[j]))
             continue
         run = _run_mpd_group if key[0] == "MPD" else _run_ensemble_group
         for j, out in zip(js, run([calls[j] for j in js], [int(seeds[j]) for j in js])):

@@ -28,6 +28,8 @@ Fixtures:
   g22_ensemble3_local.npz    DiffusionsEnsemble.run_local_inference (the re-plan path) on the 3-tile instance: whole-seed q_sample, per-tile split
                              into the tile frames, 3 + 1 guided denoising steps, both directions
   g21_ensemble_task.npz      PlanningTaskEnsemble.compute_collision / infer_task_id_from_q on global positions over the three tiles
+  g23_mapf.npz               the reference CBS / ECBS / XECBS / PrioritizedPlanning driven by a scripted low-level planner
+                             (tests/mapf_stub.py): call log, node choices, get_conflicts / soft constraints on a set of states, results
   g15_distribution_*.npz     guided sampling over 32 noise seeds: final rows of every sample, their position mean / covariance per
                              support point, free / collision split and soft-constraint violation counts (distribution-level parity)
 """
@@ -1189,11 +1191,101 @@ def g22():
     np.savez_compressed(os.path.join(OUT, "g22_ensemble3_local.npz"), **out)
 
 
+def g23():
+    """The search layer (cbs.py, prioritized_planning.py): the GENUINE reference CBS (plain, ECBS, XECBS) and PrioritizedPlanning driven by
+    the scripted low-level planner of tests/mapf_stub.py (staggered start times, a 2-tile agent, a failing child): every low-level call,
+    every node's choices and conflict count, get_conflicts and the soft-constraint builder on a set of states, the final result."""
+    sys.path.insert(0, os.path.join(os.path.dirname(HERE), "tests"))
+    import matplotlib
+    import matplotlib.pyplot as plt
+    if not hasattr(plt.cm, "get_cmap"):                 # (removed from matplotlib 3.9; the reference's constructors still call it)
+        plt.cm.get_cmap = matplotlib.colormaps.get_cmap
+    import mapf_stub as st
+    from mmd.planners.multi_agent.cbs import CBS, SearchState
+    from mmd.planners.multi_agent.prioritized_planning import PrioritizedPlanning
+    from mmd.common.conflicts import PointConflict
+    from mmd.common.constraints import MultiPointConstraint
+    with quiet():
+        env, robot, task = make_task("EnvEmpty2D")
+    out = {}
+    for ci, (name, kind, flags, n, lengths, stagger, fail_at) in enumerate(st.CASES):
+        script = st.make_script(n, lengths, fail_at, seed=2300 + 10 * ci)
+        starts, goals = st.starts_goals(n)
+        start_times = [stagger * k for k in range(n)]
+        log = []
+        planners = [st.ScriptedPlanner(k, script[k], log, robot, task) for k in range(n)]
+        sl, gl = [torch.from_numpy(v) for v in starts], [torch.from_numpy(v) for v in goals]
+        with quiet():
+            if kind == "PP":
+                alg = PrioritizedPlanning(planners, sl, gl, start_time_l=start_times)
+            else:
+                alg = CBS(planners, sl, gl, start_time_l=start_times, conflict_type_to_constraint_types={PointConflict: {MultiPointConstraint}},
+                          **flags)
+                alg.open_l = st.RecordingList()
+            paths, n_exp, status, n_conf = alg.plan(runtime_limit=1e9)
+        calls, cons, pts = st.log_to_arrays(log)
+        pre = f"{name}."
+        out[pre + "meta"] = np.array([n, stagger, -1 if fail_at is None else fail_at[0], -1 if fail_at is None else fail_at[1], 2300 + 10 * ci])
+        out[pre + "lengths"] = np.array(lengths)
+        # (the script itself is regenerated from these seeds by tests/mapf_stub.make_script; a checksum pins it)
+        out[pre + "script_sum"] = np.array([float(np.sum(script[k][e][0], dtype=np.float64)) for k in range(n) for e in range(st.N_ENTRIES)])
+        out[pre + "calls"], out[pre + "cons"], out[pre + "points"] = calls, cons, pts
+        if kind == "CBS":
+            rec = alg.open_l.record
+            out[pre + "nodes_ix"] = np.array([r[0] for r in rec], np.int64)
+            out[pre + "nodes_count"] = np.array([r[1] for r in rec], np.int64)
+        else:
+            # PP: agent i's choice is final once made; its count is that of the state of agents 0 .. i
+            counts, chosen = [], []
+            for k in range(len(paths)):
+                ent = script[k][0]
+                pad = paths[k][start_times[k]:start_times[k] + lengths[k]].numpy()
+                hits = [b for b in range(st.B) if np.array_equal(ent[0][b], pad)]
+                chosen.append(hits[0])
+            for k in range(len(chosen)):
+                stt = SearchState(chosen[:k + 1], [torch.from_numpy(script[j][0][0]) for j in range(k + 1)])
+                counts.append(len(alg.get_conflicts(stt)))
+            out[pre + "nodes_ix"] = np.array([chosen], np.int64)
+            out[pre + "nodes_count"] = np.array(counts, np.int64)
+        out[pre + "result_paths"] = torch.stack(paths).numpy() if len(paths) else np.zeros((0,))
+        out[pre + "result"] = np.array([n_exp, status.value, n_conf])
+        # get_conflicts and the soft-constraint builder on a set of states (entry 0 of every agent, chosen samples from a seed)
+        rng = np.random.Generator(np.random.PCG64(2399 + ci))
+        for si in range(3):
+            ix = [int(v) for v in rng.integers(0, st.B, n)]
+            stt = SearchState(ix, [torch.from_numpy(script[k][si % st.N_ENTRIES][0]) for k in range(n)])
+            confl = alg.get_conflicts(stt)
+            rows = []
+            for c in confl:
+                a, b = c.agent_ids
+                if kind == "CBS":
+                    pa, pb, q = c.agent_id_to_p[a], c.agent_id_to_p[b], c.agent_id_to_q[a]
+                    rows.append([c.t_from, a, b, *[float(v) for v in pa], *[float(v) for v in pb], *[float(v) for v in q]])
+                else:
+                    pa, pb = c.q_map[a], c.q_map[b]
+                    rows.append([c.t, a, b, *[float(v) for v in pa], *[float(v) for v in pb], 0.0, 0.0])
+            out[pre + f"state{si}_ix"] = np.array(ix)
+            out[pre + f"state{si}_conflicts"] = np.array(rows, np.float32).reshape(-1, 9)
+            for agent in range(n):
+                for n_state in (n, agent):                               # agent in the state (expansion) / not yet (root, PP)
+                    sub = SearchState(ix[:n_state], [torch.from_numpy(script[k][si % st.N_ENTRIES][0]) for k in range(n_state)])
+                    cl = alg.create_soft_constraints_from_other_agents_paths(sub, agent)
+                    key = pre + f"state{si}_soft{agent}_{n_state}"
+                    if cl:
+                        c = cl[0]
+                        q = torch.stack(list(c.q_l)).numpy()
+                        out[key] = np.concatenate([q, np.asarray(c.t_range_l, np.float32), np.asarray(c.radius_l, np.float32)[:, None]], 1)
+                    else:
+                        out[key] = np.zeros((0, 5), np.float32)
+        print(f"   g23 {name}: {len(log)} low-level calls, {n_exp} expansions, status {status.name}, {n_conf} conflicts", flush=True)
+    np.savez_compressed(os.path.join(OUT, "g23_mapf.npz"), **out)
+
+
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
     torch.manual_seed(0)
-    todo = sys.argv[1:] or ["g1", "g2", "g3", "g45", "g6", "g7", "g8", "g9", "g10", "g11", "g12", "g13", "g14", "g15", "g16", "g17", "g18", "g19", "g20", "g21", "g22"]
+    todo = sys.argv[1:] or ["g1", "g2", "g3", "g45", "g6", "g7", "g8", "g9", "g10", "g11", "g12", "g13", "g14", "g15", "g16", "g17", "g18", "g19", "g20", "g21", "g22", "g23"]
     for name in todo:
         print("generating", name, flush=True)
-        {"g1": g1, "g2": g2, "g3": g3, "g45": g4_g5, "g6": g6, "g7": g7, "g8": g8, "g9": g9, "g10": g10, "g11": g11, "g12": g12, "g13": g13, "g14": g14, "g6full": g6_full, "g15": g15, "g16": g16, "g17": g17, "g18": g18, "g19": g19, "g20": g20, "g21": g21, "g22": g22}[name]()
+        {"g1": g1, "g2": g2, "g3": g3, "g45": g4_g5, "g6": g6, "g7": g7, "g8": g8, "g9": g9, "g10": g10, "g11": g11, "g12": g12, "g13": g13, "g14": g14, "g6full": g6_full, "g15": g15, "g16": g16, "g17": g17, "g18": g18, "g19": g19, "g20": g20, "g21": g21, "g22": g22, "g23": g23}[name]()
     print("done")
