@@ -31,7 +31,9 @@ struct GuideDev {
 };
 
 // signed distance of the env's extra objects at p and its gradient (torch's sub-gradients: the first minimum / maximum);
-// no object at all: sdf = 1 (an empty MultiSphereField, primitives.py:109-110)
+// no object at all: sdf = 1 (an empty MultiSphereField, primitives.py:109-110).  kTorchNorm: the two norms in torch.norm's fp32 form
+// sqrt(fma(y, y, x * x)), as the occupancy decision sdf < margin needs (postprocess.hip); the guide keeps its own arithmetic.
+template <bool kTorchNorm = false>
 __device__ __forceinline__ float extra_sdf(const float4* __restrict__ xs, int n_xs, const float4* __restrict__ xb, int n_xb,
                                            float px, float py, float& gx, float& gy) {
   float best = n_xs + n_xb > 0 ? 1e30f : 1.f;
@@ -39,7 +41,7 @@ __device__ __forceinline__ float extra_sdf(const float4* __restrict__ xs, int n_
   for (int i = 0; i < n_xs; ++i) {
     const float4 s = xs[i];
     const float dx = px - s.x, dy = py - s.y;
-    const float n = sqrtf(dx * dx + dy * dy), d = n - s.z;
+    const float n = kTorchNorm ? sqrtf(__builtin_fmaf(dy, dy, dx * dx)) : sqrtf(dx * dx + dy * dy), d = n - s.z;
     if (d < best) { best = d; gx = n > 0.f ? dx / n : 0.f; gy = n > 0.f ? dy / n : 0.f; }
   }
   for (int i = 0; i < n_xb; ++i) {
@@ -48,7 +50,8 @@ __device__ __forceinline__ float extra_sdf(const float4* __restrict__ xs, int n_
     const float4 b = xb[i];
     const float rad = 0.3f * fminf(b.z, b.w);
     const float dx = px - b.x, dy = py - b.y, qx = fabsf(dx) - b.z + rad, qy = fabsf(dy) - b.w + rad;
-    const float mq = fmaxf(qx, qy), rx = fmaxf(qx, 0.f), ry = fmaxf(qy, 0.f), n = sqrtf(rx * rx + ry * ry);
+    const float mq = fmaxf(qx, qy), rx = fmaxf(qx, 0.f), ry = fmaxf(qy, 0.f);
+    const float n = kTorchNorm ? sqrtf(__builtin_fmaf(ry, ry, rx * rx)) : sqrtf(rx * rx + ry * ry);
     const float d = fminf(mq, 0.f) + n - rad;
     if (d < best) {
       best = d;

@@ -17,7 +17,14 @@
 #include "../../include/mmd_amd.h"
 #include "common.h"
 
+// Every fp32 operation here is the one written out: the collision decision ||pa - pb|| < margin must be torch.norm's own rounding.
+#pragma clang fp contract(off)
+
 namespace mmd {
+
+// torch.norm(pa - pb, dim=-1) over (dx, dy) in fp32: sqrt(fma(dy, dy, dx * dx)), the form of check_rr_collisions / get_conflicts.
+// Any other order (dx * dx + dy * dy rounded twice, or fma(dx, dx, dy * dy)) moves pairs within an ulp of the margin across it.
+__device__ __forceinline__ float torch_norm2(float dx, float dy) { return sqrtf(__builtin_fmaf(dy, dy, dx * dx)); }
 
 __global__ void rr_collisions_kernel(const float2* __restrict__ paths, int n, int T, float margin,
                                      unsigned char* __restrict__ mask, float2* __restrict__ mid) {
@@ -26,7 +33,7 @@ __global__ void rr_collisions_kernel(const float2* __restrict__ paths, int n, in
     const int j = idx % n, i = (idx / n) % n, t = idx / ((size_t)n * n);
     const float2 a = paths[(size_t)i * T + t], b = paths[(size_t)j * T + t];
     const float dx = a.x - b.x, dy = a.y - b.y;
-    const bool c = sqrtf(dx * dx + dy * dy) < margin && i != j;
+    const bool c = torch_norm2(dx, dy) < margin && i != j;
     mask[idx] = c ? 1 : 0;
     if (mid) {
       const float nanv = __builtin_nanf("");
@@ -50,7 +57,7 @@ __global__ __launch_bounds__(256) void count_collisions_kernel(const float4* __r
     if (j == self) continue;
     const float2 q = paths[(size_t)j * H + t];
     const float dx = p.x - q.x, dy = p.y - q.y;
-    c += sqrtf(dx * dx + dy * dy) < margin ? 1 : 0;
+    c += torch_norm2(dx, dy) < margin ? 1 : 0;
   }
 #pragma unroll
   for (int m = 32; m >= 1; m >>= 1) c += __shfl_xor(c, m);
@@ -74,7 +81,7 @@ __device__ __forceinline__ float2 agent_pos(const mmd_agent_path& a, int t) {
 // the collision test of rr_collisions_kernel, operation for operation
 __device__ __forceinline__ bool rr_hit(float2 a, float2 b, float margin) {
   const float dx = a.x - b.x, dy = a.y - b.y;
-  return sqrtf(dx * dx + dy * dy) < margin;
+  return torch_norm2(dx, dy) < margin;
 }
 
 // cell c of row t: (a, b) = (c / n, c % n); MMD_CONFLICTS_ORDERED keeps a != b (torch.nonzero order of cbs.py:193-246),
@@ -319,11 +326,13 @@ int mmd_find_conflicts(const mmd_agent_path* agents_dev, int n_agents, int horiz
 int mmd_scan_candidates(const mmd_agent_path* agents_dev, int n_agents, int horizon_global, int agent, const float* cand_batch_dev,
                         const int32_t* cand_idx_dev, int n_free, float margin, int mode, int rule, int32_t* scratch_dev,
                         int32_t* counts_dev, int32_t* result_dev, void* stream) {
-  MMD_REQUIRE(agents_dev && cand_batch_dev && cand_idx_dev && scratch_dev && result_dev, "mmd_scan_candidates: NULL argument");
+  MMD_REQUIRE(agents_dev && scratch_dev && result_dev, "mmd_scan_candidates: NULL argument");
   MMD_REQUIRE(n_agents >= 1 && agent >= 0 && agent < n_agents && horizon_global >= 1 && n_free >= 0, "mmd_scan_candidates: bad arguments");
   MMD_REQUIRE(mode == MMD_CONFLICTS_ORDERED || mode == MMD_CONFLICTS_PAIRS, "mmd_scan_candidates: unknown mode %d", mode);
   MMD_REQUIRE(rule == MMD_SELECT_CBS || rule == MMD_SELECT_PP, "mmd_scan_candidates: unknown rule %d", rule);
   const int n_cand = n_free + (rule == MMD_SELECT_PP ? 1 : 0);
+  // CBS without candidates reads neither (an empty index tensor has no storage): the result is (-1, -1)
+  MMD_REQUIRE(n_cand == 0 || (cand_batch_dev && cand_idx_dev), "mmd_scan_candidates: NULL candidates");
   hipStream_t st = (hipStream_t)stream;
   int32_t* base_rows = scratch_dev;                    // [horizon_global]
   int32_t* pairs = scratch_dev + horizon_global;       // [n_cand]

@@ -19,9 +19,11 @@
 
 #include "../../include/mmd_amd.h"
 #include "common.h"
-#include "guide_dev.h"
 
+// before guide_dev.h: its extra_sdf decides occupancy here, operation for operation (guide.hip keeps its own contraction)
 #pragma clang fp contract(off)
+
+#include "guide_dev.h"
 
 namespace mmd {
 
@@ -67,7 +69,7 @@ __device__ __forceinline__ bool point_collides(const EnvDev& e, const float4* __
   }
   if (e.n_xs + e.n_xb > 0) {                                // env.get_df_obj_list(): the fixed grid + obj_extra_list
     float gx, gy;
-    c = c || extra_sdf(e.xs, e.n_xs, e.xb, e.n_xb, px, py, gx, gy) < margin;
+    c = c || extra_sdf<true>(e.xs, e.n_xs, e.xb, e.n_xb, px, py, gx, gy) < margin;
   }
   c = c || (px - e.ws_min[0] < margin) || (py - e.ws_min[1] < margin) || (e.ws_max[0] - px < margin) ||
       (e.ws_max[1] - py < margin);

@@ -9,6 +9,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+import fp32_forms                        # noqa: E402
 import mapf_stub as st                   # noqa: E402
 from mmd_amd import synth                # noqa: E402
 
@@ -261,8 +262,7 @@ def test_search_replays_g23(g23, name):
 
 def _host_conflicts(paths):
     p = torch.stack(paths)[..., :2].cpu().numpy()                # [n, Tg, 2], already padded
-    d = p[:, None] - p[None]
-    hit = np.sqrt((d * d).sum(-1)) < np.float32(2.1 * 0.05)
+    hit = fp32_forms.pos_norm(p[:, None], p[None]) < fp32_forms.MARGIN          # torch.norm's fp32 form
     hit[np.arange(len(p)), np.arange(len(p))] = False
     return int(hit.sum())
 

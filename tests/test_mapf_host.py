@@ -1,11 +1,13 @@
 """CPU: golden g23 (the reference's CBS / ECBS / XECBS / PrioritizedPlanning driven by the scripted planner of mapf_stub) pinned by a NumPy
 restatement of get_conflicts and of the soft-constraint builder, and the pure-host pieces of mmd_amd.multi_agent_planners against it."""
 import os
+from fractions import Fraction
 
 import numpy as np
 import pytest
 import torch
 
+import fp32_forms as F
 import mapf_stub as st
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "g23_mapf.npz")
@@ -27,8 +29,8 @@ def _case(g, name):
 
 
 def np_conflicts(paths, lengths, starts, ordered):
-    """get_conflicts restated: global padding by clamping, ||pa - pb|| < 2.1 r in fp32, (pa + pb) / 2; (t, a, b) row-major, a != b
-    (CBS, PointConflict) or a < b (PP, VertexConflict)."""
+    """get_conflicts restated: global padding by clamping, ||pa - pb|| < 2.1 r in torch.norm's fp32 form, (pa + pb) / 2; (t, a, b)
+    row-major, a != b (CBS, PointConflict) or a < b (PP, VertexConflict)."""
     n = len(paths)
     Tg = max(L + s for L, s in zip(lengths, starts))
     pos = np.stack([paths[k][np.clip(np.arange(Tg) - starts[k], 0, lengths[k] - 1), :2] for k in range(n)])      # [n, Tg, 2]
@@ -39,8 +41,7 @@ def np_conflicts(paths, lengths, starts, ordered):
                 if (a == b) or (not ordered and b < a):
                     continue
                 pa, pb = pos[a, t], pos[b, t]
-                d = pa - pb
-                if np.sqrt(np.float32(d[0] * d[0] + d[1] * d[1])) < MARGIN:
+                if F.pos_norm(pa, pb) < MARGIN:
                     mid = (pa + pb) / np.float32(2) if ordered else np.zeros(2, np.float32)
                     rows.append([t, a, b, *pa, *pb, *mid])
     return np.array(rows, np.float32).reshape(-1, 9)
@@ -161,3 +162,58 @@ def test_g23_results_and_global_pad_paths(g23):
         np.testing.assert_array_equal(torch.stack(got).numpy(), g23[name + ".result_paths"])
         assert TrialSuccessStatus(int(g23[name + ".result"][1])) is TrialSuccessStatus.SUCCESS
     assert TrialSuccessStatus(int(g23["xecbs.result"][1])) is TrialSuccessStatus.FAIL_NO_SOLUTION
+
+
+def _round_f32(x):
+    """A Fraction rounded to the nearest fp32, ties to even."""
+    f = np.float32(float(x))
+    cands = [np.nextafter(f, np.float32(-np.inf)), f, np.nextafter(f, np.float32(np.inf))]
+    key = [(abs(Fraction(float(c)) - x), int(np.array(c, np.float32).view(np.int32)) & 1) for c in cands]
+    return cands[min(range(3), key=lambda i: key[i])]
+
+
+def test_torch_norm_is_sqrt_fma_dy_dy_dx_dx():
+    """The collision kernels pin torch.norm(d, dim=-1) over (dx, dy) in fp32 as sqrt(fma(dy, dy, dx * dx)).  This host's torch must
+    compute that form on near-margin pairs (else the bitwise GPU tests of the decisions have no fixed reference); the fma is exact
+    (Fraction), rounded once to nearest-even fp32, and fp32_forms.fma_f32 agrees with it.  The two other forms differ on these pairs."""
+    pa, pb = F.margin_pairs(5, 20000)
+    d = pa - pb
+    dx, dy = d[:, 0], d[:, 1]
+    tn = torch.norm(torch.from_numpy(d), dim=-1).numpy()
+    ln = torch.linalg.norm(torch.from_numpy(d), dim=-1).numpy()
+    sub = np.random.default_rng(6).choice(len(d), 3000, replace=False)
+    exact = np.array([np.sqrt(_round_f32(Fraction(float(y)) * Fraction(float(y)) + Fraction(float(np.float32(x * x)))))
+                      for x, y in zip(dx[sub], dy[sub])], np.float32)
+    np.testing.assert_array_equal(F.torch_norm2(dx[sub], dy[sub]), exact)
+    np.testing.assert_array_equal(tn[sub], exact)
+    np.testing.assert_array_equal(tn, F.torch_norm2(dx, dy))
+    np.testing.assert_array_equal(ln, tn)
+    # broadcast [T, n, n, 2] as check_rr_collisions forms it
+    q = torch.from_numpy(np.random.default_rng(7).uniform(-1, 1, (64, 33, 2)).astype(np.float32))
+    qn = q.numpy()
+    np.testing.assert_array_equal(torch.norm(q.unsqueeze(-2) - q.unsqueeze(-3), dim=-1).numpy(), F.pos_norm(qn[:, :, None], qn[:, None]))
+    # the forms the guard tells apart: two roundings, and the fma with the operands the other way round
+    assert (np.sqrt(dx * dx + dy * dy) != tn).sum() > 100
+    assert (np.sqrt(F.fma_f32(dx, dx, dy * dy)) != tn).sum() > 100
+    below, above = F.sides(tn)
+    assert below > 5000 and above > 5000
+
+
+def test_host_restatements_decide_as_check_rr_collisions():
+    """np_conflicts and test_gpu_mapf._host_conflicts (the independent recounts of the GPU tests) decide near-margin pairs as
+    O.check_rr_collisions does."""
+    from oracle import mmd_oracle as O
+    import test_gpu_mapf
+    pa, pb = F.margin_pairs(8, 2000)
+    qa, qb = F.margin_pairs(9, 2000)
+    m = min(len(pa), len(qa))
+    paths = np.stack([pa[:m], pb[:m], qa[:m], qb[:m]])                                  # [4, T, 2]
+    coll, mid = O.check_rr_collisions(torch.from_numpy(paths).permute(1, 0, 2))
+    assert F.sides(F.pos_norm(pa, pb))[0] > 500 and F.sides(F.pos_norm(pa, pb))[1] > 500
+    nz = torch.nonzero(coll).numpy()
+    got = np_conflicts(list(paths), [m] * 4, [0] * 4, ordered=True)
+    np.testing.assert_array_equal(got[:, :3].astype(np.int64), nz)
+    np.testing.assert_array_equal(got[:, 7:9], mid.numpy()[nz[:, 0], nz[:, 1], nz[:, 2]])
+    got = np_conflicts(list(paths), [m] * 4, [0] * 4, ordered=False)
+    np.testing.assert_array_equal(got[:, :3].astype(np.int64), nz[nz[:, 1] < nz[:, 2]])
+    assert test_gpu_mapf._host_conflicts([torch.from_numpy(p) for p in paths]) == int(coll.sum())
