@@ -9,7 +9,9 @@ planner_alg).  Differences, all forced by what exists offline:
     model_id before the first '-') and the normaliser limits from `normalizer_limits`;
   * the guide / sampler are the HIP kernels of libmmd_amd.so; there is no CPU fallback.
 """
+import functools
 import os
+from contextlib import contextmanager
 from math import ceil
 from typing import Dict, List, Optional, Tuple
 
@@ -17,7 +19,7 @@ import numpy as np
 import torch
 
 from . import synth
-from .constraints import CostConstraint, MultiPointConstraint   # noqa: F401
+from .constraints import CostConstraint, MultiPointConstraint, path_constraint_group   # noqa: F401
 from .diffusion_ensemble import DiffusionsEnsemble, HORIZON
 from .diffusion_model import GaussianDiffusionModel, ddpm_sample_fn
 from .guides import GuideManagerTrajectoriesWithVelocity
@@ -227,84 +229,98 @@ def _check_states(planner, start_state_pos, goal_state_pos):
         raise ValueError("The goal state is different from the one stored in the planner.")
 
 
-def _fill_output(out, guide, trajs_iters, all_free=False):
-    """mpd.py:344-405 / mpd_ensemble.py:385-429 on the device: ONE fused launch (collision / free split, path length,
-    smoothness, SavGol) + the per-batch argmin + the waypoint variance of the free set."""
+def _planner_alg(planner_alg):
+    """(run_prior_only, run_prior_then_guidance) of a planner_alg (mpd.py:104-113, mpd_ensemble.py:112-121)."""
+    if planner_alg == "mmd":
+        return False, False
+    if planner_alg == "diffusion_prior_then_guide":
+        return False, True
+    if planner_alg == "diffusion_prior":
+        return True, False
+    raise NotImplementedError
+
+
+def _cost_constraints(robot, constraints_l, path_constraints=None):
+    """The caller's constraints as CostConstraints, in order (mpd.py:329-342); `path_constraints` (MPDEnsemble) is appended in its
+    list form."""
+    if path_constraints is not None:
+        constraints_l = list(constraints_l or []) + path_constraints.constraint_list()
+    return [CostConstraint(robot, HORIZON, q_l=c.get_q_l(), traj_range_l=c.get_t_range_l(), radius_l=c.radius_l, is_soft=c.is_soft)
+            for c in (constraints_l or [])]
+
+
+def _weighted(planner, groups):
+    """[(group, weight), ...]: a soft group weighs weight_grad_cost_soft_constraints, a hard one weight_grad_cost_constraints
+    (mpd.py:409-411, mpd_ensemble.py:519-521)."""
+    return [(g, planner.weight_grad_cost_soft_constraints if g.is_soft else planner.weight_grad_cost_constraints) for g in groups]
+
+
+@contextmanager
+def _constraints_loaded(entries, soft_paths=None):
+    """Every (guide, robot, [(group, weight), ...]) entry's groups -- and soft_paths = (guide, paths_all, index, weight), MPD's
+    set_soft_paths -- on the guides for the duration of the block (mpd.py:409-456, mpd_ensemble.py:509-568).  Every guide named is
+    reset on the way out, also when loading itself raises."""
+    guides = {id(g): g for g in [e[0] for e in entries] + ([soft_paths[0]] if soft_paths is not None else [])}
+    try:
+        for guide, robot, pairs in entries:
+            if pairs:
+                guide.add_extra_costs([c for c, _ in pairs], [w for _, w in pairs], robot=robot)
+        if soft_paths is not None:
+            guide, paths_all, index, weight = soft_paths
+            guide.set_soft_paths(paths_all, index, weight=weight)
+        yield
+    finally:
+        for g in guides.values():
+            g.reset_extra_costs()
+
+
+def _joint_guide(guides):
+    """The guide of one call; R > 1 calls sampled together: ONE guide over their R maps (_combined_guide)."""
+    return guides[0] if len(guides) == 1 else _combined_guide(guides)
+
+
+def _planner_outputs(planners, trajs_iters, guides, tile_final, t_total, constraints):
+    """The PlannerOutputs of R = len(planners) calls sampled together (mpd.py:344-405, mpd_ensemble.py:385-429) from their
+    un-normalised global trajs_iters [T', R*B, K*64, 4], call k's samples at rows [k*B, (k+1)*B).  A sample is free iff it is free
+    against the map of guides[0] -- or, with `tile_final` (MPDEnsemble: every tile's final rows in the tile's frame), against every
+    tile's OWN map guides[m] (tasks_ensemble.py:79-88).  ONE fused launch (collision / free split, path length, smoothness, SavGol) +
+    the per-call argmin write one summary buffer, and `.cpu()` on it is the ONE device -> host transfer (boolean-mask indexing,
+    argwhere, .item() would each synchronise: nine round trips = 0.4 ms of a 3.4 ms planner call at T = 25), followed by ONE host ->
+    device copy of all index lists.  The fields each planner kind shapes its own way come from its _set_split / _set_best."""
+    R, dev = len(planners), trajs_iters.device
+    B = trajs_iters.shape[1] // R
     trajs_final = trajs_iters[-1].contiguous()
-    B, dev = trajs_final.shape[0], trajs_final.device
-    summary = post.host_summary(B, 1, dev)
-    r = post.postprocess_batch(guide, trajs_final, all_free=all_free, smooth=True, summary=summary)
-    post.select_best(r.free_mask, 1, cost_a=r.path_length, cost_b=r.smoothness, summary=summary)
-    # the call's ONE device -> host transfer: free mask, index of the cheapest free sample, the two costs, written by the two kernels
-    # into one buffer (boolean-mask indexing, argwhere, .item() would each synchronise: nine round trips = 0.4 ms of a 3.4 ms
-    # planner call at T = 25), and ONE host -> device copy of the two index lists back
+    summary = post.host_summary(R * B, R, dev)
+    r = post.postprocess_batch(guides[0], trajs_final, n_robots=R, all_free=tile_final is not None, smooth=True, summary=summary)
+    free_mask = r.free_mask
+    if tile_final is not None:
+        free_mask = functools.reduce(torch.bitwise_and, [post.postprocess_batch(g, rows, n_robots=R, smooth=False).free_mask
+                                                         for g, rows in zip(guides, tile_final)])
+    post.select_best(free_mask, R, cost_a=r.path_length, cost_b=r.smoothness, summary=summary)
     host = summary.cpu().numpy()
-    fm, ib = host[:B] > 0, int(host[B])
-    free_i, coll_i = np.flatnonzero(fm), np.flatnonzero(~fm)
-    both = torch.from_numpy(np.concatenate((free_i, coll_i))).to(dev)
-    free_idxs = both[:free_i.size].view(-1, 1)                       # [n, 1] int64, as torch.argwhere gives them (tasks.py:258-307)
-    coll_idxs = both[free_i.size:].view(-1, 1)
-    split = trajs_final.index_select(0, both)                        # (free rows first, then the colliding ones: one gather)
-    free = split[:free_i.size] if free_i.size else None
-    coll = split[free_i.size:] if coll_i.size else None
-    out.trajs_iters, out.trajs_final = trajs_iters, r.smoothed
-    out.trajs_final_coll, out.trajs_final_coll_idxs = coll, coll_idxs
-    out.trajs_final_free, out.trajs_final_free_idxs = free, free_idxs
-    out.success_free_trajs = free is not None
-    out.fraction_free_trajs = 0.0 if free is None else free.shape[0] / B
-    if free is not None:
-        costs = summary[B + 1:].view(2, B).index_select(1, free_idxs.view(-1))      # (path lengths | smoothness of the free samples)
-        out.cost_path_length, out.cost_smoothness = costs[0], costs[1]
-        out.cost_all = out.cost_path_length + out.cost_smoothness
-        idx_best_free = int(np.searchsorted(free_i, ib))          # position of the batch index ib among the free samples
-        out.idx_best_traj = free_idxs[idx_best_free]
-        out.idx_best_free_traj = idx_best_free
-        out.traj_final_free_best = free[idx_best_free]
-        out.cost_best_free_traj = float(np.float32(host[B + 1 + ib]) + np.float32(host[2 * B + 1 + ib]))
-        out.variance_waypoint_trajs_final_free = post.compute_variance_waypoints(free)
-    return out
-
-
-def _fill_output_ensemble(out, task, tile_trajs_final, trajs_iters):
-    """mpd_ensemble.py:385-429 + PlanningTaskEnsemble.get_traj_unnormalized / combine_trajs (tasks_ensemble.py:79-88, 162-225) on
-    the device: every tile's final samples [B, 64, 4] (tile frame) are split against the tile's OWN map (one launch per tile), a
-    sample is free iff it is free in every tile; costs, SavGol and the waypoint variance are those of the concatenated global-frame
-    trajectories [B, K*64, 4] (one launch), the best sample the cheapest free one.  Shapes as combine_trajs leaves them: index
-    tensors are int64 [n] (not [n, 1]), an empty free / colliding set is an empty tensor, and trajs_final_coll indexes the HORIZON
-    axis of the final batch with the colliding sample indices (tasks_ensemble.py:190, `trajs_final[:, idxs]`) as the reference does."""
-    trajs_final = trajs_iters[-1].contiguous()
-    B, dev = trajs_final.shape[0], trajs_final.device
-    free_mask = None
-    for m, tf in tile_trajs_final.items():
-        fm = post.postprocess_batch(task.tasks[m].guide, tf.contiguous(), smooth=False).free_mask
-        free_mask = fm if free_mask is None else free_mask & fm
-    summary = post.host_summary(B, 1, dev)
-    r = post.postprocess_batch(task.tasks[next(iter(task.tasks))].guide, trajs_final, all_free=True, smooth=True, summary=summary)
-    post.select_best(free_mask, 1, cost_a=r.path_length, cost_b=r.smoothness, summary=summary)
-    host = summary.cpu().numpy()                                                                        # the call's one transfer
-    fm, ib = host[:B] > 0, int(host[B])
-    free_i, coll_i = np.flatnonzero(fm), np.flatnonzero(~fm)
-    both = torch.from_numpy(np.concatenate((free_i, coll_i))).to(dev)
-    free_idxs, coll_idxs = both[:free_i.size], both[free_i.size:]
-    empty = torch.tensor([], dtype=torch.float32, device=dev)
-    out.trajs_iters, out.trajs_final = trajs_iters, r.smoothed
-    out.trajs_final_coll = trajs_final[:, coll_idxs] if coll_i.size else empty
-    out.trajs_final_coll_idxs = coll_idxs
-    out.trajs_final_free = trajs_final.index_select(0, free_idxs) if free_i.size else empty
-    out.trajs_final_free_idxs = free_idxs
-    out.success_free_trajs = 1 if free_i.size else 0
-    out.fraction_free_trajs = free_i.size / B
-    out.collision_intensity_trajs = 1 - out.fraction_free_trajs
-    if free_i.size:
-        out.cost_smoothness = r.smoothness.index_select(0, free_idxs)
-        out.cost_path_length = r.path_length.index_select(0, free_idxs)
-        out.cost_all = out.cost_smoothness + out.cost_path_length
-        best = int(np.searchsorted(free_i, ib))
-        out.idx_best_traj = free_idxs[best]
-        out.traj_final_free_best = out.trajs_final_free[best]
-        out.cost_best_free_traj = out.cost_all[best]
-        out.variance_waypoint_trajs_final_free = post.compute_variance_waypoints(out.trajs_final_free)
-    return out
+    free = (host[:R * B] > 0).reshape(R, B)
+    # every call's free sample indices, then its colliding ones, each in ascending order (a stable sort of the collision flags)
+    idxs = torch.from_numpy(np.argsort(~free, axis=1, kind="stable")).to(dev)
+    costs = summary[R * B + R:].view(2, R, B)                                            # (path lengths | smoothness)
+    outs = []
+    for k, p in enumerate(planners):
+        sl, n_free, ib = slice(k * B, (k + 1) * B), int(np.count_nonzero(free[k])), int(host[R * B + k])     # ib: the call's pick
+        out = PlannerOutput()
+        out.t_total, out.constraints_l = t_total, constraints[k]
+        out.trajs_iters, out.trajs_final = trajs_iters[:, sl], r.smoothed[sl]
+        out.fraction_free_trajs = n_free / B
+        p._set_split(out, trajs_final[sl], idxs[k], n_free)
+        if n_free:
+            out.cost_path_length, out.cost_smoothness = costs[:, k].index_select(1, idxs[k, :n_free]).unbind()
+            out.cost_all = out.cost_path_length + out.cost_smoothness
+            best = int(np.count_nonzero(free[k, :ib]))          # the cheapest free sample's position among the free ones
+            out.idx_best_traj = out.trajs_final_free_idxs[best]
+            out.traj_final_free_best = out.trajs_final_free[best]
+            p._set_best(out, best, float(host[R * B + R + k * B + ib] + host[2 * R * B + R + k * B + ib]))
+            out.variance_waypoint_trajs_final_free = post.compute_variance_waypoints(out.trajs_final_free)
+        p.recent_call_data = out
+        outs.append(out)
+    return outs
 
 
 def normalizer_limits_from_dataset(dataset_dir):
@@ -358,14 +374,7 @@ class MPD:
         self.constraints = []
         self.weight_grad_cost_constraints = weight_grad_cost_constraints
         self.weight_grad_cost_soft_constraints = weight_grad_cost_soft_constraints
-        if planner_alg == "mmd":
-            self.run_prior_only, self.run_prior_then_guidance = False, False
-        elif planner_alg == "diffusion_prior_then_guide":
-            self.run_prior_only, self.run_prior_then_guidance = False, True
-        elif planner_alg == "diffusion_prior":
-            self.run_prior_only, self.run_prior_then_guidance = True, False
-        else:
-            raise NotImplementedError
+        self.run_prior_only, self.run_prior_then_guidance = _planner_alg(planner_alg)
         self.device = torch.device(device)
         self.tensor_args = {"device": self.device, "dtype": torch.float32}
         self.model, self.model_args = _load_model(model_id, trained_models_dir, model_state_dict, model_args, self.device)
@@ -408,10 +417,6 @@ class MPD:
             noise_std_extra_schedule_fn=lambda x: 0.5)
 
     # ---- planner call -------------------------------------------------------------------------------------------
-    def _cost_constraints(self, constraints_l):
-        return [CostConstraint(self.robot, self.n_support_points, q_l=c.get_q_l(), traj_range_l=c.get_t_range_l(),
-                               radius_l=c.radius_l, is_soft=c.is_soft) for c in (constraints_l or [])]
-
     def __call__(self, start_state_pos, goal_state_pos, constraints_l=None, experience=None, *args, soft_paths=None, path_constraints=None,
                  **kwargs):
         """`soft_paths` (an extension; None = the reference's call): (paths_all [N, 64, 2] device tensor, this agent's index) -- the soft
@@ -425,39 +430,26 @@ class MPD:
         _check_states(self, start_state_pos, goal_state_pos)
         if soft_paths is not None and path_constraints is not None:
             raise ValueError("MPD.__call__: soft_paths or path_constraints, not both")
-        cost_constraints_l = self._cost_constraints(constraints_l)
-        self._soft_paths = soft_paths
-        self._path_constraints = path_constraints
+        cost_constraints_l = _cost_constraints(self.robot, constraints_l)
         with _Timer() as timer:
             if experience is None:
-                chain = self.run_constrained_inference(cost_constraints_l, **kwargs)
+                chain = self.run_constrained_inference(cost_constraints_l, path_constraints=path_constraints, soft_paths=soft_paths,
+                                                       **kwargs)
             else:
-                chain = self.run_constrained_local_inference(cost_constraints_l, experience, **kwargs)
-        out = PlannerOutput()
-        out.t_total = timer.elapsed
-        _fill_output(out, self._task_guide, self.dataset.unnormalize_trajectories(chain))
-        out.constraints_l = constraints_l
-        self.recent_call_data = out
-        return out
+                chain = self.run_constrained_local_inference(cost_constraints_l, experience, path_constraints=path_constraints,
+                                                             soft_paths=soft_paths, **kwargs)
+        return self._outputs([self], chain, timer.elapsed, [constraints_l])[0]
 
-    def _path_group(self, path_constraints):
-        """[(PathConstraintGroup, weight)] of a PathConstraints (empty when the reference would add no group)."""
-        from .constraints import path_constraint_group
+    def _constraint_pairs(self, cost_constraints_l, path_constraints=None):
+        """[(group, weight), ...] of a call: its CostConstraints in order, then the PathConstraintGroup of `path_constraints` when the
+        reference would add one."""
         g = path_constraint_group(path_constraints) if path_constraints is not None else None
-        if g is None:
-            return []
-        return [(g, self.weight_grad_cost_soft_constraints if g.is_soft else self.weight_grad_cost_constraints)]
+        return _weighted(self, list(cost_constraints_l) + ([g] if g is not None else []))
 
-    def _add_constraints(self, cost_constraints_l):
-        self.guide.add_extra_costs(cost_constraints_l,
-                                   [self.weight_grad_cost_soft_constraints if c.is_soft else
-                                    self.weight_grad_cost_constraints for c in cost_constraints_l])
-        path_group, self._path_constraints = self._path_group(getattr(self, "_path_constraints", None)), None
-        for g, w in path_group:
-            self.guide.add_extra_costs([g], [w])
-        soft_paths, self._soft_paths = getattr(self, "_soft_paths", None), None
-        if soft_paths is not None:
-            self.guide.set_soft_paths(soft_paths[0], soft_paths[1], weight=self.weight_grad_cost_soft_constraints)
+    def _loaded(self, cost_constraints_l, path_constraints, soft_paths):
+        """The call's constraint groups and soft paths on self.guide for the duration of a with block."""
+        soft = None if soft_paths is None else (self.guide, soft_paths[0], soft_paths[1], self.weight_grad_cost_soft_constraints)
+        return _constraints_loaded([(self.guide, 0, self._constraint_pairs(cost_constraints_l, path_constraints))], soft)
 
     def _post_guidance(self, chain):
         """planner_alg 'diffusion_prior_then_guide' (mpd.py:429-453): extra guide steps after the prior sample."""
@@ -470,30 +462,45 @@ class MPD:
         self.guide.guide_steps(x, hard, mask, n_post, chain=extra)        # ONE launch; every iteration lands in `extra`
         return torch.cat((chain, extra))
 
-    def run_constrained_inference(self, cost_constraints_l, **kw):
-        try:
-            self._add_constraints(cost_constraints_l)
-            chain = self.model.run_inference(
+    def run_constrained_inference(self, cost_constraints_l, path_constraints=None, soft_paths=None, **kw):
+        with self._loaded(cost_constraints_l, path_constraints, soft_paths):
+            return self._post_guidance(self.model.run_inference(
                 self.context, self.hard_conds, n_samples=self.num_samples, horizon=self.n_support_points,
                 return_chain=True, sample_fn=ddpm_sample_fn, **self.sample_fn_kwargs,
-                n_diffusion_steps_without_noise=self.n_diffusion_steps_without_noise, device=self.device, **kw)
-            chain = self._post_guidance(chain)
-        finally:
-            self.guide.reset_extra_costs()
-        return chain
+                n_diffusion_steps_without_noise=self.n_diffusion_steps_without_noise, device=self.device, **kw))
 
-    def run_constrained_local_inference(self, cost_constraints_l, experience, **kw):
-        try:
-            self._add_constraints(cost_constraints_l)
-            chain = self.model.run_local_inference(
+    def run_constrained_local_inference(self, cost_constraints_l, experience, path_constraints=None, soft_paths=None, **kw):
+        with self._loaded(cost_constraints_l, path_constraints, soft_paths):
+            return self._post_guidance(self.model.run_local_inference(
                 experience.path_b.to(self.device), self.n_local_inference_noising_steps,
                 self.n_local_inference_denoising_steps, self.context, self.hard_conds, n_samples=self.num_samples,
                 horizon=self.n_support_points, return_chain=True, sample_fn=ddpm_sample_fn, **self.sample_fn_kwargs,
-                n_diffusion_steps_without_noise=self.n_diffusion_steps_without_noise, device=self.device, **kw)
-            chain = self._post_guidance(chain)
-        finally:
-            self.guide.reset_extra_costs()
-        return chain
+                n_diffusion_steps_without_noise=self.n_diffusion_steps_without_noise, device=self.device, **kw))
+
+    # ---- post-processing: what MPD's PlannerOutput holds (mpd.py:344-405) ---------------------------------------------
+    @staticmethod
+    def _outputs(planners, chain, t_total, constraints):
+        """The PlannerOutputs of R = len(planners) calls sampled together: chain [T', R*B, 64, 4], every call un-normalised with its own
+        clip decision and split against its task's map (the full map, whatever the guide is restricted to)."""
+        trajs_iters = planners[0].dataset.unnormalize_trajectories(chain, n_tensors=len(planners))
+        return _planner_outputs(planners, trajs_iters, [_joint_guide([p._task_guide for p in planners])], None, t_total, constraints)
+
+    @staticmethod
+    def _set_split(out, trajs_final, idxs, n_free):
+        """idxs: the call's free sample indices, then its colliding ones.  Index tensors [n, 1] as torch.argwhere gives them, the rows
+        of the un-smoothed final samples, None for an empty set (tasks.py:258-307)."""
+        rows, idxs = trajs_final.index_select(0, idxs), idxs.view(-1, 1)        # (free rows first, then the colliding ones: one gather)
+        out.trajs_final_free_idxs, out.trajs_final_coll_idxs = idxs[:n_free], idxs[n_free:]
+        out.trajs_final_free = rows[:n_free] if n_free else None
+        out.trajs_final_coll = rows[n_free:] if n_free < idxs.shape[0] else None
+        out.success_free_trajs = bool(n_free)
+
+    @staticmethod
+    def _set_best(out, best, cost):
+        """mpd.py:377-379: the best sample's position among the free ones and its cost as Python numbers (cost: the fp32 sum of its
+        path length and smoothness, from the host summary)."""
+        out.idx_best_free_traj = best
+        out.cost_best_free_traj = cost
 
 
 class MPDEnsemble:
@@ -511,14 +518,7 @@ class MPDEnsemble:
                  trained_models_dir: str = "", n_samples: int = 64, n_local_inference_noising_steps: int = 3,
                  n_local_inference_denoising_steps: int = 3, model_state_dicts=None, model_args=None, env_ids=None,
                  normalizer_limits=None, **kwargs):
-        if planner_alg == "mmd":
-            self.run_prior_only, self.run_prior_then_guidance = False, False
-        elif planner_alg == "diffusion_prior_then_guide":
-            self.run_prior_only, self.run_prior_then_guidance = False, True
-        elif planner_alg == "diffusion_prior":
-            self.run_prior_only, self.run_prior_then_guidance = True, False
-        else:
-            raise NotImplementedError
+        self.run_prior_only, self.run_prior_then_guidance = _planner_alg(planner_alg)
         self.weight_grad_cost_constraints = weight_grad_cost_constraints
         self.weight_grad_cost_soft_constraints = weight_grad_cost_soft_constraints
         self.device = torch.device(device)
@@ -591,17 +591,20 @@ class MPDEnsemble:
                     is_soft=soft))
         return out
 
-    def _add_constraints(self, cost_constraints_l):
-        for task_id, cl in self.split_cost_constraints_to_tasks(cost_constraints_l).items():
+    def _tile_constraints(self, cost_constraints_l):
+        """{tile: [(CostConstraint, weight), ...]}: the call's constraints routed to the tiles (split_cost_constraints_to_tasks) and
+        shifted to the tile's frame (mpd_ensemble.py:508-522)."""
+        per_tile = self.split_cost_constraints_to_tasks(cost_constraints_l)
+        for task_id, cl in per_tile.items():
             for c in cl:
                 c.traj_ranges = c.traj_ranges - task_id * HORIZON               # mpd_ensemble.py:517
                 c.qs = c.qs - self.transforms[task_id].numpy()                  # :518
-                self.guides[task_id].add_extra_costs(
-                    [c], [self.weight_grad_cost_constraints if not c.is_soft else self.weight_grad_cost_soft_constraints])
+        return {task_id: _weighted(self, cl) for task_id, cl in per_tile.items()}
 
-    def _reset(self):
-        for g in self.guides.values():
-            g.reset_extra_costs()
+    def _loaded(self, cost_constraints_l):
+        """The call's constraints on the tile guides for the duration of a with block."""
+        per_tile = self._tile_constraints(cost_constraints_l)
+        return _constraints_loaded([(g, 0, per_tile.get(j, [])) for j, g in self.guides.items()])
 
     def _post_guidance(self, chains):
         """planner_alg 'diffusion_prior_then_guide' (mpd_ensemble.py:540-564, :603-627): after the prior sample every tile runs
@@ -624,54 +627,63 @@ class MPDEnsemble:
         return out
 
     def run_constrained_inference(self, cost_constraints_l, **kw):
-        self._add_constraints(cost_constraints_l)
-        try:
+        with self._loaded(cost_constraints_l):
             return self._post_guidance(self.model.run_inference(
                 None, self.hard_conds, cross_conds=self.cross_conds, n_samples=self.num_samples, return_chain=True,
                 sample_fn=ddpm_sample_fn, sample_kwargs=self.sample_kwargs,
                 n_diffusion_steps_without_noise=self.n_diffusion_steps_without_noise, device=self.device, **kw))
-        finally:
-            self._reset()
 
     def run_constrained_local_inference(self, cost_constraints_l, experience, **kw):
-        self._add_constraints(cost_constraints_l)
-        try:
+        with self._loaded(cost_constraints_l):
             return self._post_guidance(self.model.run_local_inference(
                 experience.path_b.to(self.device), self.n_local_inference_noising_steps,
                 self.n_local_inference_denoising_steps, None, self.hard_conds, cross_conds=self.cross_conds,
                 n_samples=self.num_samples, return_chain=True, sample_fn=ddpm_sample_fn,
                 sample_kwargs=self.sample_kwargs,
                 n_diffusion_steps_without_noise=self.n_diffusion_steps_without_noise, device=self.device, **kw))
-        finally:
-            self._reset()
 
     def __call__(self, start_state_pos, goal_state_pos, constraints_l=None, experience=None, *args, path_constraints=None, **kwargs):
         """`path_constraints` (a multi_agent.PathConstraints): appended to constraints_l in its list form (the constraints are split per
         tile on the host, split_cost_constraints_to_tasks); PlannerOutput.constraints_l stays the caller's list."""
         _check_states(self, start_state_pos, goal_state_pos)
-        given_l = constraints_l
-        if path_constraints is not None:
-            constraints_l = list(constraints_l or []) + path_constraints.constraint_list()
-        cl = [CostConstraint(self.robot, HORIZON, q_l=c.get_q_l(), traj_range_l=c.get_t_range_l(), radius_l=c.radius_l,
-                             is_soft=c.is_soft) for c in (constraints_l or [])]
+        cost_constraints_l = _cost_constraints(self.robot, constraints_l, path_constraints)
         with _Timer() as timer:
-            chains = (self.run_constrained_inference(cl, **kwargs) if experience is None
-                      else self.run_constrained_local_inference(cl, experience, **kwargs))
-        # un-normalise per tile (the tile-frame final rows go to the tile's own collision check, tasks_ensemble.py:79-88), move to
-        # the global frame, concatenate along the horizon (:162-175)
-        parts, tile_final = [], {}
-        for m in sorted(chains):
-            tr = self.datasets[m].unnormalize_trajectories(chains[m]).clone()
-            tile_final[m] = tr[-1].clone()
-            tr[..., :2] += self.transforms[m].to(tr.device)
-            parts.append(tr)
-        trajs_iters = torch.cat(parts, dim=-2)                     # [T+2, B, K*64, D]
-        out = PlannerOutput()
-        out.t_total = timer.elapsed
-        _fill_output_ensemble(out, self.task, tile_final, trajs_iters)
-        out.constraints_l = given_l
-        self.recent_call_data = out
-        return out
+            chains = (self.run_constrained_inference(cost_constraints_l, **kwargs) if experience is None
+                      else self.run_constrained_local_inference(cost_constraints_l, experience, **kwargs))
+        return self._outputs([self], chains, timer.elapsed, [constraints_l])[0]
+
+    # ---- post-processing: what MPDEnsemble's PlannerOutput holds (mpd_ensemble.py:385-429) -----------------------------
+    @staticmethod
+    def _outputs(planners, chains, t_total, constraints):
+        """The PlannerOutputs of R = len(planners) calls sampled together: chains {tile: [T', R*B, 64, 4]} normalised in the tile frame
+        (PlanningTaskEnsemble.get_traj_unnormalized / combine_trajs, tasks_ensemble.py:79-88, 162-175): every tile un-normalised
+        (every call its own clip decision), its final rows split against the tile's OWN map in the tile frame, then moved to the global
+        frame by each call's tile transform and concatenated along the horizon."""
+        R, tiles = len(planners), sorted(chains)
+        parts = [planners[0].datasets[m].unnormalize_trajectories(chains[m], n_tensors=R) for m in tiles]
+        trajs_iters = torch.cat(parts, dim=-2)                                                   # [T', R*B, K*64, 4]
+        offs = torch.stack([torch.stack([p.transforms[m] for m in tiles]) for p in planners]).to(trajs_iters.device)   # [R, K, 2]
+        trajs_iters.view(trajs_iters.shape[0], R, -1, len(tiles), HORIZON, 4)[..., :2].add_(offs[:, None, :, None, :])
+        guides = [_joint_guide([p.task.tasks[m].guide for p in planners]) for m in tiles]
+        return _planner_outputs(planners, trajs_iters, guides, [tr[-1] for tr in parts], t_total, constraints)
+
+    @staticmethod
+    def _set_split(out, trajs_final, idxs, n_free):
+        """idxs: the call's free sample indices, then its colliding ones.  Shapes as combine_trajs leaves them: index tensors [n], an
+        empty set an empty tensor, and trajs_final_coll indexes the HORIZON axis of the final batch with the colliding sample indices
+        (tasks_ensemble.py:190, `trajs_final[:, idxs]`) as the reference does."""
+        free_idxs, coll_idxs = idxs[:n_free], idxs[n_free:]
+        empty = torch.tensor([], dtype=torch.float32, device=idxs.device)
+        out.trajs_final_free_idxs, out.trajs_final_coll_idxs = free_idxs, coll_idxs
+        out.trajs_final_free = trajs_final.index_select(0, free_idxs) if n_free else empty
+        out.trajs_final_coll = trajs_final[:, coll_idxs] if coll_idxs.shape[0] else empty
+        out.success_free_trajs = 1 if n_free else 0
+        out.collision_intensity_trajs = 1 - out.fraction_free_trajs
+
+    @staticmethod
+    def _set_best(out, best, cost):
+        """tasks_ensemble.py:223: the best free sample's cost, a 0-d device tensor."""
+        out.cost_best_free_traj = out.cost_all[best]
 
 
 def plan_concurrently(calls, seeds=None):
@@ -803,109 +815,31 @@ def _combined_guide(guides):
     return cg
 
 
-def _load_constraints(cg, per_robot):
-    """per_robot[r] = [(CostConstraint, weight), ...] -> the combined guide's extra costs (one host pack for all robots)."""
-    cg.reset_extra_costs()
-    for r, pairs in enumerate(per_robot):
-        if pairs:
-            cg.add_extra_costs([c for c, _ in pairs], [w for _, w in pairs], robot=r)
-
-
-def _split_outputs(calls, planners, r, summary, trajs_iters_all, B, t_total, ensemble_tasks=None):
-    """The PlannerOutputs of a batched group from ONE post-processing launch + ONE device -> host transfer (post.host_summary)."""
-    R, dev = len(planners), trajs_iters_all.device
-    host = summary.cpu().numpy()
-    fm_all, ib_all = host[:R * B] > 0, host[R * B:R * B + R].astype(np.int64)
-    pl_all, sm_all = host[R * B + R:2 * R * B + R], host[2 * R * B + R:]
-    outs = []
-    for k, (call, planner) in enumerate(zip(calls, planners)):
-        sl = slice(k * B, (k + 1) * B)
-        out = PlannerOutput()
-        out.t_total = t_total
-        trajs_iters = trajs_iters_all[:, sl]
-        trajs_final = trajs_iters[-1].contiguous()
-        fm, ib = fm_all[sl], int(ib_all[k])
-        free_i, coll_i = np.flatnonzero(fm), np.flatnonzero(~fm)
-        ens = ensemble_tasks is not None
-        free_idxs = torch.from_numpy(free_i).to(dev) if ens else torch.from_numpy(free_i).to(dev).view(-1, 1)
-        coll_idxs = torch.from_numpy(coll_i).to(dev) if ens else torch.from_numpy(coll_i).to(dev).view(-1, 1)
-        out.trajs_iters, out.trajs_final = trajs_iters, r.smoothed[sl]
-        out.trajs_final_coll_idxs, out.trajs_final_free_idxs = coll_idxs, free_idxs
-        if ens:                                             # shapes of combine_trajs (_fill_output_ensemble)
-            empty = torch.tensor([], dtype=torch.float32, device=dev)
-            out.trajs_final_coll = trajs_final[:, coll_idxs] if coll_i.size else empty
-            out.trajs_final_free = trajs_final.index_select(0, free_idxs) if free_i.size else empty
-            out.success_free_trajs = 1 if free_i.size else 0
-            out.collision_intensity_trajs = 1 - free_i.size / B
-        else:                                               # shapes of MPD.__call__ (_fill_output)
-            out.trajs_final_coll = trajs_final.index_select(0, coll_idxs.view(-1)) if coll_i.size else None
-            out.trajs_final_free = trajs_final.index_select(0, free_idxs.view(-1)) if free_i.size else None
-            out.success_free_trajs = bool(free_i.size)
-        out.fraction_free_trajs = free_i.size / B if ens else (0.0 if not free_i.size else free_i.size / B)
-        if free_i.size:
-            sel = free_idxs.view(-1) + k * B
-            out.cost_smoothness = r.smoothness.index_select(0, sel)
-            out.cost_path_length = r.path_length.index_select(0, sel)
-            best = int(np.searchsorted(free_i, ib))
-            out.idx_best_traj = free_idxs[best]
-            out.traj_final_free_best = out.trajs_final_free[best]
-            if ens:
-                out.cost_all = out.cost_smoothness + out.cost_path_length
-                out.cost_best_free_traj = out.cost_all[best]
-            else:
-                out.cost_all = out.cost_path_length + out.cost_smoothness
-                out.idx_best_free_traj = best
-                out.cost_best_free_traj = float(np.float32(pl_all[k * B + ib]) + np.float32(sm_all[k * B + ib]))
-            out.variance_waypoint_trajs_final_free = post.compute_variance_waypoints(out.trajs_final_free)
-        out.constraints_l = call[3] if len(call) > 3 else None
-        planner.recent_call_data = out
-        outs.append(out)
-    return outs
-
-
-def _check_start_goal(planner, call):
-    _check_states(planner, call[1], call[2])
-
-
 def _run_mpd_group(calls, seeds):
     planners = [c[0] for c in calls]
     p0, R, B = planners[0], len(calls), planners[0].num_samples
     dev = p0.device
     for p, c in zip(planners, calls):
-        _check_start_goal(p, c)
+        _check_states(p, c[1], c[2])
     cg = _combined_guide([p.guide for p in planners])
-    per_robot = []
-    for p, c in zip(planners, calls):
-        cl = p._cost_constraints(c[3] if len(c) > 3 else None)
-        per_robot.append([(cc, p.weight_grad_cost_soft_constraints if cc.is_soft else p.weight_grad_cost_constraints) for cc in cl]
-                         + p._path_group(c[5] if len(c) > 5 else None))
-    _load_constraints(cg, per_robot)
+    entries = [(cg, r, p._constraint_pairs(_cost_constraints(p.robot, c[3]), c[5])) for r, (p, c) in enumerate(zip(planners, calls))]
     hard = {row: torch.stack([p.hard_conds[row] for p in planners]) for row in p0.hard_conds}
-    experiences = [c[4] if len(c) > 4 else None for c in calls]                  # (all or none: _batch_key)
     kw = dict(n_samples=B, n_robots=R, horizon=HORIZON, return_chain=True, sample_fn=ddpm_sample_fn,
               guide=None if p0.run_prior_only else cg, n_guide_steps=p0.n_guide_steps, t_start_guide=p0.t_start_guide,
               noise_std_extra_schedule_fn=p0.sample_fn_kwargs["noise_std_extra_schedule_fn"],
               n_diffusion_steps_without_noise=p0.n_diffusion_steps_without_noise, device=dev, robot_seeds=seeds)
-    with _Timer() as timer:
-        try:
-            if experiences[0] is None:
-                chain = p0.model.run_inference(None, hard, **kw)
-            else:
-                # every call's seed batch forward-noised with the call's own Philox stream (q_sample under `seed`, as its own call does),
-                # then ONE denoising loop over all of them
-                noised = torch.cat([p.model.q_sample(e.path_b.to(dev), p.n_local_inference_noising_steps, seed=s)
-                                    for p, e, s in zip(planners, experiences, seeds)])
-                kw.pop("n_samples"), kw.pop("return_chain")
-                chain = p0.model.conditional_sample(dict(hard), n_diffusion_steps=p0.n_local_inference_denoising_steps, batch_size=R * B,
-                                                    return_chain=True, warm_start_path_b=noised, **kw)[1].transpose(0, 1)
-        finally:
-            cg.reset_extra_costs()
-    trajs_iters = p0.dataset.unnormalize_trajectories(chain, n_tensors=R)        # [T+2, R*B, H, D]; every call's own clip decision
-    tg = cg if all(p._task_guide is p.guide for p in planners) else _combined_guide([p._task_guide for p in planners])
-    summary = post.host_summary(R * B, R, dev)
-    r = post.postprocess_batch(tg, trajs_iters[-1].contiguous(), n_robots=R, smooth=True, summary=summary)
-    post.select_best(r.free_mask, R, cost_a=r.path_length, cost_b=r.smoothness, summary=summary)
-    return _split_outputs(calls, planners, r, summary, trajs_iters, B, timer.elapsed)
+    with _constraints_loaded(entries), _Timer() as timer:
+        if calls[0][4] is None:                                       # (all or none: _batch_key)
+            chain = p0.model.run_inference(None, hard, **kw)
+        else:
+            # every call's seed batch forward-noised with the call's own Philox stream (q_sample under `seed`, as its own call does),
+            # then ONE denoising loop over all of them
+            noised = torch.cat([p.model.q_sample(c[4].path_b.to(dev), p.n_local_inference_noising_steps, seed=s)
+                                for p, c, s in zip(planners, calls, seeds)])
+            kw.pop("n_samples"), kw.pop("return_chain")
+            chain = p0.model.conditional_sample(dict(hard), n_diffusion_steps=p0.n_local_inference_denoising_steps, batch_size=R * B,
+                                                return_chain=True, warm_start_path_b=noised, **kw)[1].transpose(0, 1)
+    return MPD._outputs(planners, chain, timer.elapsed, [c[3] for c in calls])
 
 
 def _run_ensemble_group(calls, seeds):
@@ -913,60 +847,26 @@ def _run_ensemble_group(calls, seeds):
     p0, R, B = planners[0], len(calls), planners[0].num_samples
     dev, keys = p0.device, list(p0.models.keys())
     for p, c in zip(planners, calls):
-        _check_start_goal(p, c)
+        _check_states(p, c[1], c[2])
     cgs = {j: _combined_guide([p.guides[j] for p in planners]) for j in keys}
-    per_tile = {j: [[] for _ in range(R)] for j in keys}
+    entries = []
     for k, (p, c) in enumerate(zip(planners, calls)):
-        given = list((c[3] if len(c) > 3 else None) or []) + (c[5].constraint_list() if len(c) > 5 and c[5] is not None else [])
-        cl = [CostConstraint(p.robot, HORIZON, q_l=cc.get_q_l(), traj_range_l=cc.get_t_range_l(), radius_l=cc.radius_l,
-                             is_soft=cc.is_soft) for cc in given]
-        for task_id, tile_cl in p.split_cost_constraints_to_tasks(cl).items():
-            for cc in tile_cl:
-                cc.traj_ranges = cc.traj_ranges - task_id * HORIZON                       # mpd_ensemble.py:517
-                cc.qs = cc.qs - p.transforms[task_id].numpy()                             # :518
-                per_tile[task_id][k].append((cc, p.weight_grad_cost_constraints if not cc.is_soft else p.weight_grad_cost_soft_constraints))
-    for j in keys:
-        _load_constraints(cgs[j], per_tile[j])
+        per_tile = p._tile_constraints(_cost_constraints(p.robot, c[3], c[5]))
+        entries += [(cgs[j], k, per_tile.get(j, [])) for j in keys]
     hard = {j: {row: torch.stack([p.hard_conds[j][row] for p in planners]) for row in p0.hard_conds.get(j, {})} for j in keys}
     skw = {j: dict(p0.sample_kwargs[j], guide=None if p0.run_prior_only else cgs[j]) for j in keys}
-    experiences = [c[4] if len(c) > 4 else None for c in calls]                  # (all or none: _batch_key)
-    with _Timer() as timer:
-        try:
-            noised, n_steps = None, p0.model.n_diffusion_steps
-            if experiences[0] is not None:                   # DiffusionsEnsemble.run_local_inference per call, then ONE denoising loop
-                noised = torch.cat([p.models[keys[0]].q_sample(e.path_b.to(dev), p.n_local_inference_noising_steps, seed=s)
-                                    for p, e, s in zip(planners, experiences, seeds)])
-                n_steps = p0.n_local_inference_denoising_steps
-            _, chains = p0.model.p_sample_loop(
-                (R * B, HORIZON, p0.models[keys[0]].state_dim), hard, dict(p0.cross_conds), n_diffusion_steps=n_steps,
-                return_chain=True, sample_fn=ddpm_sample_fn, n_diffusion_steps_without_noise=p0.n_diffusion_steps_without_noise,
-                warm_start_path_b=noised, device=dev, n_robots=R, robot_seeds=seeds, robot_transforms=[p.transforms for p in planners],
-                sample_kwargs=skw)
-        finally:
-            for j in keys:
-                cgs[j].reset_extra_costs()
-    # un-normalise per tile, tile-frame final rows to the tile's own collision check, global frame, concatenate (as MPDEnsemble.__call__)
-    parts, free_mask = [], None
-    for j in keys:
-        tr = p0.datasets[j].unnormalize_trajectories(chains[j].transpose(0, 1), n_tensors=R).clone()   # [T+2, R*B, H, D]
-        tgs = _combined_guide([p.task.tasks[j].guide for p in planners])
-        fm = post.postprocess_batch(tgs, tr[-1].contiguous(), n_robots=R, smooth=False).free_mask
-        free_mask = fm if free_mask is None else free_mask & fm
-        offs = torch.stack([p.transforms[j] for p in planners]).to(tr.device).repeat_interleave(B, 0)     # [R*B, 2]
-        tr[..., :2] += offs[None, :, None, :]
-        parts.append(tr)
-    trajs_iters = torch.cat(parts, dim=-2)                                                      # [T+2, R*B, K*64, D]
-    summary = post.host_summary(R * B, R, dev)
-    r = post.postprocess_batch(cgs[keys[0]], trajs_iters[-1].contiguous(), n_robots=R, all_free=True, smooth=True, summary=summary)
-    post.select_best(free_mask, R, cost_a=r.path_length, cost_b=r.smoothness, summary=summary)
-    return _split_outputs(calls, planners, r, summary, trajs_iters, B, timer.elapsed, ensemble_tasks=True)
-
-
-def _call_one(call, seed):
-    """One call of a plan_batched list on its own: the sixth element, if any, is the path_constraints keyword."""
-    if len(call) > 5:
-        return call[0](*call[1:5], path_constraints=call[5], seed=seed)
-    return call[0](*call[1:], seed=seed)
+    with _constraints_loaded(entries), _Timer() as timer:
+        noised, n_steps = None, p0.model.n_diffusion_steps
+        if calls[0][4] is not None:                    # DiffusionsEnsemble.run_local_inference per call, then ONE denoising loop
+            noised = torch.cat([p.models[keys[0]].q_sample(c[4].path_b.to(dev), p.n_local_inference_noising_steps, seed=s)
+                                for p, c, s in zip(planners, calls, seeds)])
+            n_steps = p0.n_local_inference_denoising_steps
+        _, chains = p0.model.p_sample_loop(
+            (R * B, HORIZON, p0.models[keys[0]].state_dim), hard, dict(p0.cross_conds), n_diffusion_steps=n_steps,
+            return_chain=True, sample_fn=ddpm_sample_fn, n_diffusion_steps_without_noise=p0.n_diffusion_steps_without_noise,
+            warm_start_path_b=noised, device=dev, n_robots=R, robot_seeds=seeds, robot_transforms=[p.transforms for p in planners],
+            sample_kwargs=skw)
+    return MPDEnsemble._outputs(planners, {j: c.transpose(0, 1) for j, c in chains.items()}, timer.elapsed, [c[3] for c in calls])
 
 
 def plan_batched(calls, seeds=None):
@@ -981,7 +881,7 @@ def plan_batched(calls, seeds=None):
     (`diffusion_prior_then_guide`, extra objects) run on their own, in list order, with their seed.  A call may carry a sixth element,
     the `path_constraints` of MPD.__call__ / MPDEnsemble.__call__ (None = none): the soft constraints of an ECBS child, the hard ones
     of a PrioritizedPlanning agent."""
-    calls = [tuple(c) for c in calls]
+    calls = [tuple(c) + (None,) * (6 - len(c)) for c in calls]     # (planner, start, goal, constraints_l, experience, path_constraints)
     if len({id(c[0]) for c in calls}) != len(calls):
         raise ValueError("plan_batched: a planner appears twice (a planner call is not re-entrant)")
     if seeds is None:
@@ -1001,7 +901,7 @@ def plan_batched(calls, seeds=None):
         js = groups[key]
         if key[0] == "single" or len(js) == 1:
             for j in js:
-                outs[j] = _call_one(calls[j], int(seeds[j]))
+                outs[j] = calls[j][0](*calls[j][1:5], path_constraints=calls[j][5], seed=int(seeds[j]))
             continue
         run = _run_mpd_group if key[0] == "MPD" else _run_ensemble_group
         for j, out in zip(js, run([calls[j] for j in js], [int(seeds[j]) for j in js])):

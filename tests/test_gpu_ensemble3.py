@@ -132,17 +132,18 @@ def test_ensemble3_teacher_forced_steps_g20(direction):
 
 
 @pytest.mark.parametrize("direction", cases.ENSEMBLE3_DIRECTIONS)
-def test_mpd_ensemble_call_on_the_g20_instance(direction):
+def test_mpd_ensemble_call_and_outputs_on_the_g20_instance(direction):
     """MPDEnsemble.__call__ on the same instance: the planner routes the two MultiPointConstraints itself
     (split_cost_constraints_to_tasks + the tile shift); its chains are BITWISE those of DiffusionsEnsemble.p_sample_loop fed with
     the reference's own per-tile tables (same injected noise) -- the routing produced the same guide tables; the PlannerOutput is
     the oracle's restatement of the reference's post-processing (pinned on the reference's chains by the CPU test of g20) applied
     to the HIP chains: per-tile collision split in the tile frame, free = free in every tile, global concatenation, costs, best
-    sample, SavGol; and on the reference's OWN final rows the split is the reference's."""
+    sample, SavGol; and the output builder (MPDEnsemble._outputs, one call) on the reference's OWN chains gives the reference's
+    PlannerOutput fields."""
     from mmd_amd.constraints import MultiPointConstraint
     from mmd_amd.diffusion_ensemble import DiffusionsEnsemble
     from mmd_amd.diffusion_model import ddpm_sample_fn
-    from mmd_amd.planners import MPDEnsemble, _fill_output_ensemble, PlannerOutput
+    from mmd_amd.planners import MPDEnsemble
     g, T, B, K, case, models, cons, guides, transforms, hard, cross, skw, x0, steps = _setup(direction)
     ens = DiffusionsEnsemble(models, transforms)
     _, chains = ens.p_sample_loop((B, H, D), {m: dict(hard[m]) for m in range(K)}, cross, n_diffusion_steps=T, return_chain=True,
@@ -186,14 +187,8 @@ def test_mpd_ensemble_call_on_the_g20_instance(direction):
             assert out.idx_best_traj is None and out.cost_all is None and out.trajs_final_free.numel() == 0
     same(out, ref_out)
     # the post-processing on the REFERENCE's chains against the reference's own PlannerOutput fields (golden g20)
-    ref_chains = {m: torch.from_numpy(g[f"{direction}.chain{m}"]) for m in range(K)}
-    parts, tile_final = [], {}
-    for m in range(K):
-        tr = p.datasets[m].unnormalize_trajectories(ref_chains[m].cuda()).clone()
-        tile_final[m] = tr[-1].clone()
-        tr[..., :2] += transforms[m].cuda()
-        parts.append(tr)
-    o2 = _fill_output_ensemble(PlannerOutput(), p.task, tile_final, torch.cat(parts, dim=-2))
+    ref_chains = {m: torch.from_numpy(g[f"{direction}.chain{m}"]).cuda() for m in range(K)}
+    o2 = MPDEnsemble._outputs([p], ref_chains, 0.0, [None])[0]
     assert o2.trajs_final_free_idxs.cpu().tolist() == g[f"{direction}.free_idxs"].tolist()
     assert o2.trajs_final_coll_idxs.cpu().tolist() == g[f"{direction}.coll_idxs"].tolist()
     assert np.allclose(o2.trajs_iters[-1].cpu().numpy(), g[f"{direction}.trajs_final_global"], atol=1e-6)

@@ -200,34 +200,58 @@ def test_bench_dump_outputs(tmp_path):
     assert s.size * 4 + s64.size * 8 + 48 <= 2_000_000
 
 
-def test_split_cost_constraints_to_tasks_golden_g13():
-    """MPDEnsemble.split_cost_constraints_to_tasks + the per-tile range / transform shift of run_constrained_inference
-    (mpd_ensemble.py:431-507, 515-518) against the reference's own output (g13): tile order, hard-then-soft order inside a
-    tile, every (q, range, radius, is_soft) table exactly -- a mixed list over 3 tiles with a range that starts on a tile
-    boundary and one that straddles it.  The guides are stand-ins that record what add_extra_costs receives."""
-    import types
-    from mmd_amd.planners import MPDEnsemble
-    g = np.load(os.path.join(GOLDEN, "g13_split_constraints.npz"))
-    received = {k: [] for k in range(3)}
-
-    def recorder(k):
-        return types.SimpleNamespace(add_extra_costs=lambda costs, weights, k=k: received[k].extend(zip(costs, weights)))
-    me = types.SimpleNamespace(robot=None, guides={k: recorder(k) for k in range(3)},
-                               transforms={0: torch.tensor([0.0, 0.0]), 1: torch.tensor([2.0, 0.0]), 2: torch.tensor([4.0, 0.5])},
-                               weight_grad_cost_constraints=2e-1, weight_grad_cost_soft_constraints=2e-2)
-    me.infer_task_id_from_q_idx = types.MethodType(MPDEnsemble.infer_task_id_from_q_idx, me)
-    me.split_cost_constraints_to_tasks = types.MethodType(MPDEnsemble.split_cost_constraints_to_tasks, me)
-
+def _g13_constraints():
+    """The mixed list of golden g13: hard + soft constraints over 3 tiles, a range that starts on a tile boundary, one that straddles it."""
     def cc(qs, ranges, radii, soft):
         return CostConstraint(None, H, q_l=[torch.tensor(q, dtype=torch.float32) for q in qs], traj_range_l=ranges,
                               radius_l=radii, is_soft=soft)
-    cons = [cc(([0.1, 0.2], [2.3, 0.1]), [(10, 14), (70, 75)], [0.12, 0.10], False),
+    return [cc(([0.1, 0.2], [2.3, 0.1]), [(10, 14), (70, 75)], [0.12, 0.10], False),
             cc(([-0.4, 0.3], [1.7, -0.2], [4.4, 0.6]), [(5, 6), (64, 65), (130, 131)], [0.12, 0.12, 0.12], True),
             cc(([3.9, 0.4],), [(128, 140)], [0.2], False),
             cc(([0.9, -0.1], [0.0, 0.0]), [(62, 66), (0, 1)], [0.12, 0.15], True)]
+
+
+def _ensemble_stand_in(transforms, guides):
+    """An MPDEnsemble with only what its constraint routing and loading read (constructing one needs the library and a device)."""
+    from mmd_amd.planners import MPDEnsemble
+    me = object.__new__(MPDEnsemble)
+    me.robot, me.guides, me.transforms = None, guides, transforms
+    me.weight_grad_cost_constraints, me.weight_grad_cost_soft_constraints = 2e-1, 2e-2
+    return me
+
+
+class _TileGuide:
+    """Stand-in tile guide: records what add_extra_costs receives and counts resets; `fail` makes it refuse its constraints."""
+
+    def __init__(self, fail=False):
+        self.fail, self.costs, self.n_resets = fail, [], 0
+
+    def add_extra_costs(self, costs, weights, robot=0):
+        if self.fail:
+            raise RuntimeError("tile guide refused its constraints")
+        self.costs.extend(zip(costs, weights))
+
+    def reset_extra_costs(self):
+        self.costs, self.n_resets = [], self.n_resets + 1
+
+
+def test_tile_constraints_golden_g13():
+    """MPDEnsemble.split_cost_constraints_to_tasks + the per-tile range / transform shift of run_constrained_inference
+    (mpd_ensemble.py:431-507, 515-518) against the reference's own output (g13): tile order, hard-then-soft order inside a
+    tile, every (q, range, radius, is_soft) table exactly -- a mixed list over 3 tiles with a range that starts on a tile
+    boundary and one that straddles it.  The guides are stand-ins that record what add_extra_costs receives while the call's
+    constraints are loaded (MPDEnsemble._tile_constraints through the planners' one loader), and are reset after it."""
+    from mmd_amd.planners import MPDEnsemble
+    g = np.load(os.path.join(GOLDEN, "g13_split_constraints.npz"))
+    guides = {k: _TileGuide() for k in range(3)}
+    me = _ensemble_stand_in({0: torch.tensor([0.0, 0.0]), 1: torch.tensor([2.0, 0.0]), 2: torch.tensor([4.0, 0.5])}, guides)
+    cons = _g13_constraints()
     split = MPDEnsemble.split_cost_constraints_to_tasks(me, cons)
     assert list(split.keys()) == g["task_order"].tolist()
-    MPDEnsemble._add_constraints(me, cons)
+    assert list(MPDEnsemble._tile_constraints(me, cons).keys()) == g["task_order"].tolist()
+    with MPDEnsemble._loaded(me, cons):
+        received = {k: list(guide.costs) for k, guide in guides.items()}
+    assert all(guide.costs == [] and guide.n_resets == 1 for guide in guides.values())
     for k in g["task_order"].tolist():
         assert len(received[k]) == int(g[f"n_{k}"])
         for j, (c, w) in enumerate(received[k]):
@@ -237,6 +261,16 @@ def test_split_cost_constraints_to_tasks_golden_g13():
             assert np.array_equal(np.asarray(c.traj_ranges, dtype=np.float32), g[f"ranges_{k}_{j}"]), (k, j, c.traj_ranges)
             assert np.array_equal(np.asarray(c.radii, dtype=np.float32), g[f"radii_{k}_{j}"]), (k, j)
 
+
+def test_ensemble_constraint_load_failure_resets_every_tile_guide():
+    """A failure while the tile constraints are put on the guides (here the second tile's add_extra_costs) reaches the caller of
+    MPDEnsemble.run_constrained_inference, and no tile guide keeps extra costs from the failed call."""
+    from mmd_amd.planners import MPDEnsemble
+    guides = {k: _TileGuide(fail=k == 1) for k in range(3)}
+    me = _ensemble_stand_in({0: torch.tensor([0.0, 0.0]), 1: torch.tensor([2.0, 0.0]), 2: torch.tensor([4.0, 0.5])}, guides)
+    with pytest.raises(RuntimeError, match="refused"):
+        MPDEnsemble.run_constrained_inference(me, _g13_constraints())
+    assert all(guide.costs == [] and guide.n_resets >= 1 for guide in guides.values())
 
 
 def test_launch_helper_rejects_host_tensors():
@@ -290,34 +324,29 @@ def test_stream_seeds_are_unique_across_host_threads():
 
 
 @pytest.mark.parametrize("direction", ("fwd", "rev"))
-def test_split_cost_constraints_to_tasks_golden_g20(direction):
+def test_tile_constraints_golden_g20(direction):
     """The 3-tile corner-turning instance of golden g20: MPDEnsemble's own routing (split_cost_constraints_to_tasks + the tile shift of
-    _add_constraints, mpd_ensemble.py:431-522) of the instance's hard + soft MultiPointConstraints, built the way __call__ builds them,
+    _tile_constraints, mpd_ensemble.py:431-522) of the instance's hard + soft MultiPointConstraints, built the way __call__ builds them,
     against the tables the genuine MPDEnsemble produced -- tile order, hard-then-soft order inside a tile, the shifted (q, range,
     radius, is_soft) rows (a soft range that straddles a tile boundary stays with the tile of its first index), for x AND y tile
-    offsets in both directions."""
-    import types
+    offsets in both directions; the stand-in tile guides record what add_extra_costs receives while the constraints are loaded."""
     from mmd_amd import synth
     from mmd_amd.constraints import MultiPointConstraint
     from mmd_amd.planners import MPDEnsemble
     g = np.load(os.path.join(GOLDEN, "g20_ensemble3.npz"))
     case = synth.ensemble3_case(direction)
     K = len(case["env_ids"])
-    received = {k: [] for k in range(K)}
-
-    def recorder(k):
-        return types.SimpleNamespace(add_extra_costs=lambda costs, weights, k=k: received[k].extend(zip(costs, weights)))
-    me = types.SimpleNamespace(robot=None, guides={k: recorder(k) for k in range(K)},
-                               transforms={k: torch.from_numpy(case["transforms"][k]) for k in range(K)},
-                               weight_grad_cost_constraints=2e-1, weight_grad_cost_soft_constraints=2e-2)
-    me.infer_task_id_from_q_idx = types.MethodType(MPDEnsemble.infer_task_id_from_q_idx, me)
-    me.split_cost_constraints_to_tasks = types.MethodType(MPDEnsemble.split_cost_constraints_to_tasks, me)
+    guides = {k: _TileGuide() for k in range(K)}
+    me = _ensemble_stand_in({k: torch.from_numpy(case["transforms"][k]) for k in range(K)}, guides)
     cl = [MultiPointConstraint(q_l=[torch.from_numpy(q) for q in qs], t_range_l=[tuple(int(v) for v in t) for t in tr],
                                radius_l=[float(r) for r in rad], is_soft=soft) for (qs, tr, rad, soft) in case["constraints"]]
     cons = [CostConstraint(None, H, q_l=c.get_q_l(), traj_range_l=c.get_t_range_l(), radius_l=c.radius_l, is_soft=c.is_soft) for c in cl]
     split = MPDEnsemble.split_cost_constraints_to_tasks(me, cons)
     assert list(split.keys()) == g[f"{direction}.task_order"].tolist()
-    MPDEnsemble._add_constraints(me, cons)
+    assert list(MPDEnsemble._tile_constraints(me, cons).keys()) == g[f"{direction}.task_order"].tolist()
+    with MPDEnsemble._loaded(me, cons):
+        received = {k: list(guide.costs) for k, guide in guides.items()}
+    assert all(guide.costs == [] and guide.n_resets == 1 for guide in guides.values())
     n_total = 0
     for k in g[f"{direction}.task_order"].tolist():
         assert len(received[k]) == int(g[f"{direction}.n_{k}"])

@@ -19,7 +19,7 @@ for _ in range(5):
     p(s, g)
 torch.cuda.synchronize()
 marks = {}
-orig_run, orig_fill = p.run_constrained_inference, planners._fill_output
+orig_run, orig_fill = p.run_constrained_inference, planners._planner_outputs
 
 
 def run(*a, **k):
@@ -38,7 +38,7 @@ def fill(*a, **k):
     return out
 
 
-p.run_constrained_inference, planners._fill_output = run, fill
+p.run_constrained_inference, planners._planner_outputs = run, fill
 rows = []
 for _ in range(12):
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
