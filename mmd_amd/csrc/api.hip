@@ -1,6 +1,6 @@
-// Sampling-loop orchestration and ABI bookkeeping of libmmd_amd.so.
+// Sampling-loop orchestration, ABI bookkeeping and the event profiler (include/mmd_amd_debug.h) of libmmd_amd.so.
 //
-// p_sample_loop (diffusion_model_base.py:162-211) = per outer step: ONE UNet launch (unet.hip) + ONE fused kernel doing
+// p_sample_loop (diffusion_model_base.py:162-211) = per outer step: ONE UNet launch (unet.hip, unet_kernel.h) + ONE fused kernel doing
 // posterior mean, the n_guide_steps guide iterations, noise and hard conditioning (guide.hip).  Everything is
 // enqueued on the caller's stream with no host synchronisation: the reference's per-step `.item()`-style syncs
 // (sample_functions.py:53,63; normalization.py:161) do not exist here because the branches depend only on the
@@ -12,11 +12,22 @@
 #include <cstdio>
 #include <cstdlib>
 #include <map>
+#include <vector>
 
 #include "../../include/mmd_amd.h"
 #include "../../include/mmd_amd_debug.h"
 #include "common.h"
 #include "guide_dev.h"
+
+// caller-owned event-pair pool (include/mmd_amd_debug.h); the unet handle itself is immutable after creation
+struct mmd_profiler_s {
+  int stride = 1, window = 1, period = 0;   // launch i of a period is bracketed iff (i / window) % stride == 0
+  std::vector<hipEvent_t> ev;               // event pairs, in bracketing order
+  std::vector<int> kind;                    // per pair: MMD_PROF_UNET / _UNET_FUSED / _STEP_GUIDED / _STEP_PLAIN
+  hipEvent_t base = nullptr;                // recorded with the first bracket: origin of the interval clock
+  size_t used = 0;                          // events handed out
+  size_t seen[2] = {0, 0};                  // launches counted: UNet, step kernel (the same steps of both are bracketed)
+};
 
 namespace mmd {
 
@@ -29,12 +40,32 @@ void set_error(const char* fmt, ...) {
   va_end(ap);
 }
 
+// counter 0: UNet launches, 1: step-kernel launches.  Both are issued once per (step, stream chunk) in the same order, so
+// the same steps of both are bracketed.
+bool prof_begin(mmd_profiler_t prof, int counter, int kind, hipStream_t st) {
+  if (!prof) return false;
+  const size_t i = prof->period > 0 ? prof->seen[counter] % (size_t)prof->period : prof->seen[counter];
+  ++prof->seen[counter];
+  if (((i / (size_t)prof->window) % (size_t)prof->stride) != 0 || prof->used + 2 > prof->ev.size()) return false;
+  if (prof->used == 0) (void)hipEventRecord(prof->base, st);
+  (void)hipEventRecord(prof->ev[prof->used], st);
+  prof->kind[prof->used / 2] = kind;
+  return true;
+}
+void prof_end(mmd_profiler_t prof, hipStream_t st) {
+  (void)hipEventRecord(prof->ev[prof->used + 1], st);
+  prof->used += 2;
+}
+void prof_skip(mmd_profiler_t prof, int counter) {
+  if (prof) ++prof->seen[counter];
+}
+
 constexpr int kMaxChunks = 4;
 // Measurement switches travel in the descriptors (mmd_sampler_desc.flags / .n_streams / .guide_coop_max, mmd_unet_options): the
 // library never reads the environment.
 //   MMD_SAMPLER_NO_FUSED_STEP: unguided steps run as step-kernel launches instead of inside the UNet launch's tail (A/B of the
 //     fused step).
-//   MMD_SAMPLER_PERSIST (default OFF): the leading run of unguided steps as persistent launches (unet.hip: unet_persist_kernel).
+//   MMD_SAMPLER_PERSIST (default OFF): the leading run of unguided steps as persistent launches (unet_kernel.h: unet_persist_kernel).
 //     Measured in round 5 and NOT kept as the default (profiles/r05_persist_ab.txt): bitwise-equal results, +1 .. 2 % on the
 //     256 .. 1024-trajectory shards (the launch gaps of 50 steps), -1 .. -4 % on the 2048-trajectory headline (one whole-batch
 //     persistent launch replaces the two interleaved stream chunks, which are worth more there).
@@ -79,9 +110,20 @@ static Streams& streams() {
   return S[dev];
 }
 
+// the fields a step of either sampler takes from the descriptor as they are
+static StepDev step_base(const mmd_sampler_desc* s) {
+  StepDev sd{};
+  sd.do_model = 1;
+  sd.n_guide_steps = s->n_guide_steps;
+  sd.hard_rows = s->hard_rows; sd.n_hard = __builtin_popcountll(s->hard_rows);
+  sd.traj_base = (long long)s->traj_index_base;
+  return sd;
+}
+
 static int make_step(const mmd_sampler_desc* s, int i, bool guided, StepDev& sd) {
   const int t = i < 0 ? 0 : i;                                    // sample_functions.py:53-54
   MMD_REQUIRE(t < s->n_diffusion_steps, "loop index %d outside the %d-step schedule", i, s->n_diffusion_steps);
+  sd = step_base(s);
   sd.a_t = s->sqrt_recip_alphas_cumprod[t];
   sd.b_t = s->sqrt_recipm1_alphas_cumprod[t];
   if (s->model_predicts_x0) { sd.a_t = 0.f; sd.b_t = -1.f; }       // predict_epsilon = False: x_recon = a x - b out = out (diffusion_model_base.py:131-141)
@@ -92,16 +134,48 @@ static int make_step(const mmd_sampler_desc* s, int i, bool guided, StepDev& sd)
   sd.sigma = expf(0.5f * s->posterior_log_variance_clipped[t]);   // model_std, sample_functions.py:60
   // noise_std_extra_schedule_fn(t_single), evaluated per step (sample_functions.py:83-86)
   sd.noise_std_extra = s->noise_std_extra_by_t ? s->noise_std_extra_by_t[t] : s->noise_std_extra;
-  sd.do_model = 1;
   sd.do_guide = guided && i < s->t_start_guide ? 1 : 0;           // sample_functions.py:63
   sd.do_noise = t == 0 ? 0 : 1;                                   // noise[t == 0] = 0, sample_functions.py:76
-  sd.n_guide_steps = s->n_guide_steps;
-  sd.hard_rows = s->hard_rows; sd.n_hard = __builtin_popcountll(s->hard_rows);
-  sd.traj_base = (long long)s->traj_index_base;
   sd.robot_seeds = reinterpret_cast<const unsigned long long*>(s->robot_seeds_dev);
   sd.coop_max = s->guide_coop_max;
   return 0;
 }
+
+// the DDIM step from time t to tn (eta = 0: no noise).  robot_seeds, coop_max and noise_std_extra stay zero.
+static StepDev make_ddim_step(const mmd_sampler_desc* s, const float* alphas_cumprod, int t, int tn, bool guided) {
+  StepDev sd = step_base(s);
+  sd.ddim = s->model_predicts_x0 ? 2 : 1;
+  sd.grad_scale = 1.f;                                              // (ddim_sample passes no scale_grad_by_std on)
+  sd.a_t = s->sqrt_recip_alphas_cumprod[t];
+  // (x0-predicting model: b_t carries 1 / sqrt_recipm1; on the last pair x = x_start and pred_noise is never used -- 0 there, so a
+  // schedule whose sqrt_recipm1[t] is 0 or denormal cannot put 0 * inf into the update)
+  sd.b_t = s->model_predicts_x0 ? (tn < 0 ? 0.f : 1.f / s->sqrt_recipm1_alphas_cumprod[t]) : s->sqrt_recipm1_alphas_cumprod[t];
+  sd.c1 = tn < 0 ? 1.f : sqrtf(alphas_cumprod[tn]);               // x = x_start on the last pair (time_next = -1)
+  sd.c2 = tn < 0 ? 0.f : sqrtf(1.f - alphas_cumprod[tn]);         // sigma = eta * ... = 0
+  sd.do_guide = guided && tn >= 0 && tn < s->t_start_guide ? 1 : 0;  // torch.all(t_next < t_start_guide); none after the break
+  sd.do_noise = 0;
+  return sd;
+}
+
+// The unguided step sd as it rides in the tail of a UNet launch: x / hard = the full arrays, noise / chain = the step's rows of
+// theirs (or null), traj0 = first trajectory of the launch in them, t_row = the step's time-table row (persistent run only).
+static FusedStep fused_step(const StepDev& sd, float* x, const float* hard, const float* noise, float* chain, int traj0, int spr,
+                            int t_row = 0) {
+  FusedStep fs{};
+  fs.enabled = 1;
+  fs.a_t = sd.a_t; fs.b_t = sd.b_t; fs.c1 = sd.c1; fs.c2 = sd.c2; fs.sigma = sd.sigma; fs.noise_std_extra = sd.noise_std_extra;
+  fs.do_noise = sd.do_noise; fs.hard_rows = sd.hard_rows; fs.n_hard = sd.n_hard; fs.seed = sd.seed; fs.draw = sd.draw;
+  fs.robot_seeds = sd.robot_seeds;
+  fs.traj_base = sd.traj_base; fs.traj0 = traj0; fs.spr = spr;
+  fs.x = reinterpret_cast<float4*>(x); fs.noise = reinterpret_cast<const float4*>(noise);
+  fs.chain = reinterpret_cast<float4*>(chain); fs.hard = reinterpret_cast<const float4*>(hard);
+  fs.t_row = t_row;
+  return fs;
+}
+
+// row k of an optional [steps][n][H][D] buffer (step noise, chain): null stays null
+template <class T>
+static inline T* row_of(T* buf, size_t k, size_t traj_floats) { return buf ? buf + k * traj_floats : nullptr; }
 
 static inline float* eps_of(void* workspace_dev, mmd_unet_t unet, int n) {
   return reinterpret_cast<float*>(reinterpret_cast<char*>(workspace_dev) + mmd_unet_workspace_bytes(unet, n));
@@ -193,16 +267,17 @@ int mmd_p_sample_loop(mmd_unet_t unet, const mmd_sampler_desc* s, const mmd_guid
   launch_init(x_dev, chain_dev, hard_dev, s->hard_rows, init_noise, (unsigned long long)seed,
               reinterpret_cast<const unsigned long long*>(s->robot_seeds_dev), (long long)s->traj_index_base, n, samples_per_robot, st);
   const bool persist = (s->flags & MMD_SAMPLER_PERSIST) != 0, no_fused_step = (s->flags & MMD_SAMPLER_NO_FUSED_STEP) != 0;
+  const mmd_profiler_t prof = (mmd_profiler_t)s->profiler;
 
   // OPT-IN (mmd_sampler_desc.flags & MMD_SAMPLER_PERSIST): the leading run of steps WITHOUT guidance (i >= t_start_guide; every step of a
   // prior-only call) as persistent launches on the caller's stream: a workgroup iterates the run's steps on its own trajectories
-  // (unet.hip: unet_persist_kernel), <= 64 steps a launch.  Bitwise the launch-per-step result.  Not with a profiler attached (its
+  // (unet_kernel.h: unet_persist_kernel), <= 64 steps a launch.  Bitwise the launch-per-step result.  Not with a profiler attached (its
   // brackets are per launch).
   int k_start = 0;
   // (its step table travels by hipMemcpyAsync from host memory: not inside a stream capture)
   hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
   if (persist) (void)hipStreamIsCapturing(st, &capturing);
-  if (persist && capturing == hipStreamCaptureStatusNone && !no_fused_step && unet_fused_step_supported(unet) && !s->profiler) {
+  if (persist && capturing == hipStreamCaptureStatusNone && !no_fused_step && unet_fused_step_supported(unet) && !prof) {
     FusedStep run[PERSIST_MAX_STEPS];
     int i = n_steps - 1, k0 = 0;
     while (i >= -n_steps_without_noise) {
@@ -211,18 +286,9 @@ int mmd_p_sample_loop(mmd_unet_t unet, const mmd_sampler_desc* s, const mmd_guid
         StepDev sd{};
         if (int rc = make_step(s, i - m, guide != nullptr, sd)) return rc;
         if (sd.do_guide) break;
-        FusedStep& fs = run[m];
-        fs = FusedStep{};
-        fs.enabled = 1;
-        fs.a_t = sd.a_t; fs.b_t = sd.b_t; fs.c1 = sd.c1; fs.c2 = sd.c2; fs.sigma = sd.sigma; fs.noise_std_extra = sd.noise_std_extra;
-        fs.do_noise = sd.do_noise; fs.hard_rows = sd.hard_rows; fs.n_hard = sd.n_hard; fs.seed = seed; fs.draw = (unsigned int)(k0 + m);
-        fs.robot_seeds = sd.robot_seeds;
-        fs.traj_base = sd.traj_base; fs.traj0 = 0; fs.spr = samples_per_robot;
-        fs.x = reinterpret_cast<float4*>(x_dev);
-        fs.noise = step_noise_dev ? reinterpret_cast<const float4*>(step_noise_dev + (size_t)(k0 + m) * traj_floats) : nullptr;
-        fs.chain = chain_dev ? reinterpret_cast<float4*>(chain_dev + (size_t)(k0 + m + 1) * traj_floats) : nullptr;
-        fs.hard = reinterpret_cast<const float4*>(hard_dev);
-        fs.t_row = i - m < 0 ? 0 : i - m;
+        sd.seed = seed; sd.draw = (unsigned int)(k0 + m);
+        run[m] = fused_step(sd, x_dev, hard_dev, row_of(step_noise_dev, k0 + m, traj_floats), row_of(chain_dev, k0 + m + 1, traj_floats), 0,
+                            samples_per_robot, i - m < 0 ? 0 : i - m);
       }
       if (m == 0 || (m < 2 && k0 == 0)) break;              // (a single step gains nothing over the fused launch)
       if (int rc = unet_persist_steps(unet, n, workspace_dev, mmd_unet_workspace_bytes(unet, n), st, run, m)) return rc;
@@ -255,35 +321,23 @@ int mmd_p_sample_loop(mmd_unet_t unet, const mmd_sampler_desc* s, const mmd_guid
     StepDev sd{};
     if ((rc = make_step(s, i, guide != nullptr, sd))) break;
     sd.seed = seed; sd.draw = (unsigned int)k;
-    // A step without guidance is fused into the tail of the UNet launch (unet.hip: the wave that holds a trajectory's eps applies
+    // A step without guidance is fused into the tail of the UNet launch (unet_kernel.h: the wave that holds a trajectory's eps applies
     // ddpm_sample_fn to it): one launch and one dependent dispatch less per (step, chunk).
     const bool fused = !sd.do_guide && !no_fused_step && unet_fused_step_supported(unet);
-    const float* noise_k = step_noise_dev ? step_noise_dev + (size_t)k * traj_floats : nullptr;
-    float* chain_k = chain_dev ? chain_dev + (size_t)(k + 1) * traj_floats : nullptr;
+    const float* noise_k = row_of(step_noise_dev, k, traj_floats);
+    float* chain_k = row_of(chain_dev, k + 1, traj_floats);
     for (int c = 0; c < nch && rc == 0; ++c) {
       const int t0 = r0[c] * samples_per_robot, nc = (r0[c + 1] - r0[c]) * samples_per_robot;
-      if (fused) {
-        FusedStep fs{};
-        fs.enabled = 1;
-        fs.a_t = sd.a_t; fs.b_t = sd.b_t; fs.c1 = sd.c1; fs.c2 = sd.c2; fs.sigma = sd.sigma; fs.noise_std_extra = sd.noise_std_extra;
-        fs.do_noise = sd.do_noise; fs.hard_rows = sd.hard_rows; fs.n_hard = sd.n_hard; fs.seed = sd.seed; fs.draw = sd.draw; fs.traj_base = sd.traj_base;
-        fs.robot_seeds = sd.robot_seeds;
-        fs.traj0 = t0; fs.spr = samples_per_robot;
-        fs.x = reinterpret_cast<float4*>(x_dev); fs.noise = reinterpret_cast<const float4*>(noise_k);
-        fs.chain = reinterpret_cast<float4*>(chain_k); fs.hard = reinterpret_cast<const float4*>(hard_dev);
-        rc = unet_forward_fused(unet, x_dev + (size_t)t0 * H * D, i < 0 ? 0 : i, eps + (size_t)t0 * H * D, nc, workspace_dev, uws,
-                                (mmd_profiler_t)s->profiler, cs[c], fs);
-        prof_skip((mmd_profiler_t)s->profiler, 1);
-      } else {
-        rc = mmd_unet_forward_profiled(unet, x_dev + (size_t)t0 * H * D, i < 0 ? 0 : i, eps + (size_t)t0 * H * D, nc,
-                                       workspace_dev, uws, (mmd_profiler_t)s->profiler, cs[c]);
-      }
+      // (a disabled FusedStep{} is the plain forward: what mmd_unet_forward_profiled launches)
+      rc = unet_forward_fused(unet, x_dev + (size_t)t0 * H * D, i < 0 ? 0 : i, eps + (size_t)t0 * H * D, nc, workspace_dev, uws, prof, cs[c],
+                              fused ? fused_step(sd, x_dev, hard_dev, noise_k, chain_k, t0, samples_per_robot) : FusedStep{});
+      if (fused) prof_skip(prof, 1);
     }
     for (int c = 0; c < nch && rc == 0 && !fused; ++c) {
       const int t0 = r0[c] * samples_per_robot, nc = (r0[c + 1] - r0[c]) * samples_per_robot;
-      const bool br = prof_begin((mmd_profiler_t)s->profiler, 1, sd.do_guide ? MMD_PROF_STEP_GUIDED : MMD_PROF_STEP_PLAIN, cs[c]);
+      const bool br = prof_begin(prof, 1, sd.do_guide ? MMD_PROF_STEP_GUIDED : MMD_PROF_STEP_PLAIN, cs[c]);
       launch_step(g, sd, x_dev, eps, noise_k, chain_k, hard_dev, t0, nc, samples_per_robot, cs[c]);
-      if (br) prof_end((mmd_profiler_t)s->profiler, cs[c]);
+      if (br) prof_end(prof, cs[c]);
     }
   }
   // join on every exit path: an error above must not leave the caller's stream detached from the side streams
@@ -329,9 +383,7 @@ int mmd_p_sample_loop_ensemble(const mmd_ensemble_tile* tiles, int n_tiles, cons
   auto cross_all = [&](int crow, int stepped) {
     for (int c = 0; c < n_cross; ++c) {
       const mmd_cross_cond& C = cross[c];
-      auto row = [&](int m) -> float* {
-        return tiles[m].chain_dev ? tiles[m].chain_dev + (size_t)(m > stepped ? crow - 1 : crow) * traj_floats : nullptr;
-      };
+      auto row = [&](int m) { return row_of(tiles[m].chain_dev, m > stepped ? crow - 1 : crow, traj_floats); };
       launch_cross(tiles[C.m1].x_dev, tiles[C.m2].x_dev, row(C.m1), row(C.m2), C.ind1, C.ind2, C.rel, C.boundary, C.by_robot_dev,
                    samples_per_robot, n, st);
     }
@@ -352,28 +404,18 @@ int mmd_p_sample_loop_ensemble(const mmd_ensemble_tile* tiles, int n_tiles, cons
       StepDev sd{};
       if (int rc = make_step(T.sampler, i, T.guide != nullptr, sd)) return rc;
       sd.seed = T.seed; sd.draw = (unsigned int)k;
+      const mmd_profiler_t prof = (mmd_profiler_t)T.sampler->profiler;
+      const size_t uws = mmd_unet_workspace_bytes(T.unet, n);
       float* eps = eps_of(workspace_dev, T.unet, n);
-      const float* noise_k = T.step_noise_dev ? T.step_noise_dev + (size_t)k * traj_floats : nullptr;
-      float* chain_k = T.chain_dev ? T.chain_dev + (size_t)(k + 1) * traj_floats : nullptr;
-      if (!sd.do_guide && !(T.sampler->flags & MMD_SAMPLER_NO_FUSED_STEP) && unet_fused_step_supported(T.unet)) {
-        // a step without guidance rides in the tail of the UNet launch, as in mmd_p_sample_loop (one launch and one dependent
-        // dispatch less per tile step; bitwise the two-launch form)
-        FusedStep fs{};
-        fs.enabled = 1;
-        fs.a_t = sd.a_t; fs.b_t = sd.b_t; fs.c1 = sd.c1; fs.c2 = sd.c2; fs.sigma = sd.sigma; fs.noise_std_extra = sd.noise_std_extra;
-        fs.do_noise = sd.do_noise; fs.hard_rows = sd.hard_rows; fs.n_hard = sd.n_hard; fs.seed = sd.seed; fs.draw = sd.draw;
-        fs.traj_base = sd.traj_base; fs.robot_seeds = sd.robot_seeds; fs.traj0 = 0; fs.spr = samples_per_robot;
-        fs.x = reinterpret_cast<float4*>(T.x_dev); fs.noise = reinterpret_cast<const float4*>(noise_k);
-        fs.chain = reinterpret_cast<float4*>(chain_k); fs.hard = reinterpret_cast<const float4*>(T.hard_dev);
-        if (int rc = unet_forward_fused(T.unet, T.x_dev, i < 0 ? 0 : i, eps, n, workspace_dev, mmd_unet_workspace_bytes(T.unet, n),
-                                        (mmd_profiler_t)T.sampler->profiler, st, fs))
-          return rc;
-      } else {
-        if (int rc = mmd_unet_forward_profiled(T.unet, T.x_dev, i < 0 ? 0 : i, eps, n, workspace_dev,
-                                               mmd_unet_workspace_bytes(T.unet, n), (mmd_profiler_t)T.sampler->profiler, st))
-          return rc;
-        launch_step(g[m], sd, T.x_dev, eps, noise_k, chain_k, T.hard_dev, 0, n, samples_per_robot, st);
-      }
+      const float* noise_k = row_of(T.step_noise_dev, k, traj_floats);
+      float* chain_k = row_of(T.chain_dev, k + 1, traj_floats);
+      // a step without guidance rides in the tail of the UNet launch, as in mmd_p_sample_loop (one launch and one dependent
+      // dispatch less per tile step; bitwise the two-launch form)
+      const bool fused = !sd.do_guide && !(T.sampler->flags & MMD_SAMPLER_NO_FUSED_STEP) && unet_fused_step_supported(T.unet);
+      if (int rc = unet_forward_fused(T.unet, T.x_dev, i < 0 ? 0 : i, eps, n, workspace_dev, uws, prof, st,
+                                      fused ? fused_step(sd, T.x_dev, T.hard_dev, noise_k, chain_k, 0, samples_per_robot) : FusedStep{}))
+        return rc;
+      if (!fused) launch_step(g[m], sd, T.x_dev, eps, noise_k, chain_k, T.hard_dev, 0, n, samples_per_robot, st);
       cross_all(k + 1, m);
     }
   }
@@ -393,6 +435,7 @@ int mmd_ddim_sample(mmd_unet_t unet, const mmd_sampler_desc* s, const float* alp
   const size_t traj_floats = (size_t)n * H * D;
   const size_t uws = mmd_unet_workspace_bytes(unet, n);
   float* eps = eps_of(workspace_dev, unet, n);
+  const mmd_profiler_t prof = (mmd_profiler_t)s->profiler;
   GuideDev g{};
   if (guide)
     if (int rc = fill_guide(guide, g)) return rc;
@@ -401,29 +444,86 @@ int mmd_ddim_sample(mmd_unet_t unet, const mmd_sampler_desc* s, const float* alp
   for (int k = 0; k + 1 < n_times; ++k) {
     const int t = times[k], tn = times[k + 1];
     MMD_REQUIRE(t >= 0 && t < s->n_diffusion_steps && tn < t, "mmd_ddim_sample: times must decrease inside the schedule");
-    StepDev sd{};
-    sd.ddim = s->model_predicts_x0 ? 2 : 1;
-    sd.grad_scale = 1.f;                                              // (ddim_sample passes no scale_grad_by_std on)
-    sd.a_t = s->sqrt_recip_alphas_cumprod[t];
-    // (x0-predicting model: b_t carries 1 / sqrt_recipm1; on the last pair x = x_start and pred_noise is never used -- 0 there, so a
-    // schedule whose sqrt_recipm1[t] is 0 or denormal cannot put 0 * inf into the update)
-    sd.b_t = s->model_predicts_x0 ? (tn < 0 ? 0.f : 1.f / s->sqrt_recipm1_alphas_cumprod[t]) : s->sqrt_recipm1_alphas_cumprod[t];
-    sd.c1 = tn < 0 ? 1.f : sqrtf(alphas_cumprod[tn]);               // x = x_start on the last pair (time_next = -1)
-    sd.c2 = tn < 0 ? 0.f : sqrtf(1.f - alphas_cumprod[tn]);         // sigma = eta * ... = 0
-    sd.do_model = 1;
-    sd.do_guide = guide && tn >= 0 && tn < s->t_start_guide ? 1 : 0;  // torch.all(t_next < t_start_guide); none after the break
-    sd.do_noise = 0;
-    sd.n_guide_steps = s->n_guide_steps;
-    sd.hard_rows = s->hard_rows; sd.n_hard = __builtin_popcountll(s->hard_rows);
+    StepDev sd = make_ddim_step(s, alphas_cumprod, t, tn, guide != nullptr);
     sd.seed = seed; sd.draw = (unsigned int)k;
-    sd.traj_base = (long long)s->traj_index_base;
-    if (int rc = mmd_unet_forward_profiled(unet, x_dev, t, eps, n, workspace_dev, uws, (mmd_profiler_t)s->profiler, stream))
-      return rc;
-    launch_step(g, sd, x_dev, eps, nullptr, chain_dev ? chain_dev + (size_t)(k + 1) * traj_floats : nullptr, hard_dev, 0, n,
-                samples_per_robot, st);
+    if (int rc = mmd_unet_forward_profiled(unet, x_dev, t, eps, n, workspace_dev, uws, prof, stream)) return rc;
+    launch_step(g, sd, x_dev, eps, nullptr, row_of(chain_dev, k + 1, traj_floats), hard_dev, 0, n, samples_per_robot, st);
     if (tn < 0) break;
   }
   MMD_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+int mmd_unet_forward_profiled(mmd_unet_t u, const float* x, int t, float* eps, int n, void* ws, size_t ws_bytes,
+                              mmd_profiler_t prof, void* stream) {
+  return unet_forward_fused(u, x, t, eps, n, ws, ws_bytes, prof, (hipStream_t)stream, FusedStep{});
+}
+
+int mmd_profiler_create(mmd_profiler_t* out, int max_launches, int stride) {
+  return mmd_profiler_create_windowed(out, max_launches, stride, 1, 0);
+}
+
+int mmd_profiler_create_windowed(mmd_profiler_t* out, int max_launches, int stride, int window, int period) {
+  MMD_REQUIRE(out && max_launches > 0, "mmd_profiler_create: bad arguments");
+  auto* p = new mmd_profiler_s();
+  p->stride = stride > 0 ? stride : 1;
+  p->window = window > 0 ? window : 1;
+  p->period = period > 0 ? period : 0;
+  if (hipEventCreate(&p->base) != hipSuccess) {
+    set_error("mmd_profiler_create: hipEventCreate failed");
+    delete p;
+    return 1;
+  }
+  p->ev.resize((size_t)2 * max_launches);
+  p->kind.assign((size_t)max_launches, 0);
+  for (auto& e : p->ev)
+    if (hipEventCreate(&e) != hipSuccess) {
+      set_error("mmd_profiler_create: hipEventCreate failed");
+      e = nullptr;
+      mmd_profiler_destroy(p);
+      return 1;
+    }
+  *out = p;
+  return 0;
+}
+
+int mmd_profiler_destroy(mmd_profiler_t p) {
+  if (!p) return 0;
+  for (auto& e : p->ev)
+    if (e) (void)hipEventDestroy(e);
+  if (p->base) (void)hipEventDestroy(p->base);
+  delete p;
+  return 0;
+}
+
+int mmd_profiler_intervals(mmd_profiler_t p, int kind, double* start_ms, double* end_ms, int cap, int* n_out) {
+  MMD_REQUIRE(p && start_ms && end_ms && n_out, "mmd_profiler_intervals: NULL argument");
+  int cnt = 0;
+  for (size_t i = 0; i + 1 < p->used && cnt < cap; i += 2) {
+    if (p->kind[i / 2] != kind) continue;
+    float a = 0.f, b = 0.f;
+    if (hipEventElapsedTime(&a, p->base, p->ev[i]) == hipSuccess && hipEventElapsedTime(&b, p->base, p->ev[i + 1]) == hipSuccess) {
+      start_ms[cnt] = a;
+      end_ms[cnt] = b;
+      ++cnt;
+    }
+  }
+  *n_out = cnt;
+  return 0;
+}
+
+int mmd_profiler_read(mmd_profiler_t p, double* mean_ms, int* n_launches) {
+  MMD_REQUIRE(p && mean_ms && n_launches, "mmd_profiler_read: NULL argument");
+  double tot = 0.0;
+  int cnt = 0;
+  for (size_t i = 0; i + 1 < p->used; i += 2) {
+    float ms = 0.f;
+    if ((p->kind[i / 2] == MMD_PROF_UNET || p->kind[i / 2] == MMD_PROF_UNET_FUSED) && hipEventElapsedTime(&ms, p->ev[i], p->ev[i + 1]) == hipSuccess) { tot += ms; ++cnt; }
+  }
+  *mean_ms = cnt ? tot / cnt : 0.0;
+  *n_launches = cnt;
+  p->used = 0;
+  p->seen[0] = p->seen[1] = 0;
   return 0;
 }
 

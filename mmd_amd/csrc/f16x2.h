@@ -1,4 +1,4 @@
-// fp32 GEMMs on the fp16 matrix pipe ("f16x2") -- the building blocks shared by the fused TemporalUnet kernel (unet.hip) and the
+// fp32 GEMMs on the fp16 matrix pipe ("f16x2") -- the building blocks shared by the fused TemporalUnet kernel (unet_kernel.h) and the
 // layer-by-layer path (unet_layers.hip): the two-piece fp16 split of an fp32 operand, the MFMA triple of one K = 32 chunk, the
 // dynamic per-sample input scale, and the host-side packing of conv weights into MFMA B-fragment order.  gfx950 only.
 #pragma once

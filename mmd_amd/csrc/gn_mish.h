@@ -1,4 +1,4 @@
-// GroupNorm affine + Mish as the fused TemporalUnet kernel (unet.hip) and the layer-by-layer kernels (unet_layers.hip) evaluate it.
+// GroupNorm affine + Mish as the fused TemporalUnet kernel (unet_kernel.h) and the layer-by-layer kernels (unet_layers.hip) evaluate it.
 #pragma once
 #include <hip/hip_runtime.h>
 

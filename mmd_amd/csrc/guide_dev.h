@@ -109,7 +109,7 @@ __device__ __forceinline__ float4 traj_normal4(unsigned long long seed, const un
 }
 
 // p_mean_variance (diffusion_model_base.py:148-160): x0 = a x - b eps; clamp; mean = c1 x0 + c2 x.  Explicit fmas: the step
-// kernel and the UNet kernel's fused unguided step (unet.hip) must round identically.
+// kernel and the UNet kernel's fused unguided step (unet_kernel.h) must round identically.
 __device__ __forceinline__ float ddpm_mean1(float x, float e, float a, float b, float c1, float c2) {
   const float x0 = fminf(fmaxf(__builtin_fmaf(a, x, -(b * e)), -1.f), 1.f);
   return __builtin_fmaf(c1, x0, c2 * x);
@@ -136,7 +136,7 @@ __device__ __forceinline__ float4 add_step_noise(float4 v, float4 z, float sigma
                      __builtin_fmaf(sigma * z.z, noise_std_extra, v.z), __builtin_fmaf(sigma * z.w, noise_std_extra, v.w));
 }
 
-// An UNGUIDED ddpm_sample_fn step fused into the tail of the UNet launch that produces its eps (unet.hip; mmd_p_sample_loop uses
+// An UNGUIDED ddpm_sample_fn step fused into the tail of the UNet launch that produces its eps (unet_kernel.h; mmd_p_sample_loop uses
 // it for every step without guidance: one launch and one dependent-dispatch bubble less per step).  Pointers are those of the full
 // arrays, traj0 = first trajectory of the launch in them.
 struct FusedStep {
@@ -156,7 +156,7 @@ struct FusedStep {
   int t_row;              // persistent run only: the step's row of the time table (t = max(i, 0))
 };
 
-// A persistent run of unguided steps (unet.hip: unet_persist_kernel): one complete FusedStep per step (schedule coefficients, Philox
+// A persistent run of unguided steps (unet_kernel.h: unet_persist_kernel): one complete FusedStep per step (schedule coefficients, Philox
 // draw index, the step's noise / chain rows, row t of the time table) in a table at the start of the sampler workspace, the run's
 // kernel-argument block behind it.
 constexpr int PERSIST_MAX_STEPS = 64;
@@ -200,9 +200,9 @@ struct StepDev {
 };
 
 int fill_guide(const mmd_guide_desc* d, GuideDev& g);
-// the UNet forward with the unguided step fused into its tail (unet.hip); only the fused kernel's configuration has it
+// the UNet forward (unet.hip), with the unguided step fs fused into its tail where fs.enabled; only the fused kernel's configuration has it
 bool unet_fused_step_supported(mmd_unet_t u);
-int unet_forward_fused(mmd_unet_t u, const float* x, int t, float* eps, int n, void* ws, size_t ws_bytes, ::mmd_profiler_s* prof,
+int unet_forward_fused(mmd_unet_t u, const float* x, int t, float* eps, int n, void* ws, size_t ws_bytes, Profiler* prof,
                        hipStream_t st, const FusedStep& fs);
 int unet_persist_steps(mmd_unet_t u, int n, void* ws, size_t ws_bytes, hipStream_t st, const FusedStep* steps, int n_steps);
 int launch_step(const GuideDev& g, StepDev s, float* x, const float* eps, const float* noise, float* chain,

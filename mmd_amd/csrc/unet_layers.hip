@@ -1,4 +1,4 @@
-// TemporalUnet forward, layer by layer, for the configurations the fused kernel (unet.hip) is not instantiated for -- first of all
+// TemporalUnet forward, layer by layer, for the configurations the fused kernel (unet_kernel.h) is not instantiated for -- first of all
 // UNET_DIM_MULTS[1] = (1, 2, 4, 8) (mmd/models/diffusion_models/temporal_unet.py:17-20, selected by a checkpoint's args.yaml at
 // mmd/planners/single_agent/mpd.py:158; the released checkpoints use option 0 and run the fused kernel).  Plain fp32 FMA
 // arithmetic on the vector ALUs, one launch per Conv1dBlock / conv, activations channels-FIRST [n][C][L] in an HBM workspace (the

@@ -1,5 +1,5 @@
 """TemporalUnet: host mirror of reference mmd/models/diffusion_models/temporal_unet.py:23-174 whose forward runs as
-hand-written gfx950 kernels (mmd_amd/csrc/unet.hip) behind the C ABI (include/mmd_amd.h: mmd_unet_*)."""
+hand-written gfx950 kernels (mmd_amd/csrc/unet_kernel.h, packed and launched by mmd_amd/csrc/unet.hip) behind the C ABI (include/mmd_amd.h: mmd_unet_*)."""
 import ctypes as C
 import hashlib
 import os

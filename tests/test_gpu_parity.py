@@ -810,7 +810,7 @@ def test_stream_chunking_is_bit_identical():
 
 
 def test_fused_unguided_steps_equal_the_step_api_bitwise():
-    """mmd_p_sample_loop applies the steps WITHOUT guidance inside the UNet launch (FusedStep, unet.hip); mmd_ddpm_step keeps the
+    """mmd_p_sample_loop applies the steps WITHOUT guidance inside the UNet launch (FusedStep, unet_kernel.h); mmd_ddpm_step keeps the
     UNet launch + ddpm_guide_kernel form.  Both run the same explicit-fma helpers (guide_dev.h), so the whole chain of a guided
     call -- 12 fused steps, then 14 guided ones -- must equal the step-by-step replay BIT FOR BIT (injected noise: the two entry
     points number their Philox draws differently); B = 5 also covers a workgroup with invalid waves.

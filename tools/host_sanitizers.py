@@ -15,8 +15,8 @@ import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = ["mmd_amd/csrc/unet.hip", "mmd_amd/csrc/unet_layers.hip", "mmd_amd/csrc/guide.hip", "mmd_amd/csrc/api.hip",
-       "mmd_amd/csrc/multi_agent.hip", "mmd_amd/csrc/postprocess.hip"]
+sys.path.insert(0, ROOT)
+from __graft_entry__ import SOURCES as SRC  # noqa: E402
 CLANG = "/opt/rocm/lib/llvm/bin/clang"
 
 LEG = r'''

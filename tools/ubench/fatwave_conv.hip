@@ -1,11 +1,11 @@
 // Would ONE 512-register wave per SIMD that interleaves the MFMAs of one 4-sample half with the GroupNorm + Mish epilogue of the
 // other beat TWO 256-register workgroups per CU running in lockstep?  (HISTORY.md section 7, item 1.)  The loop body is downs.2's
-// 128 -> 128 conv exactly as unet_kernel runs it (rd_store2 -> barrier -> rd_taps -> rd_gn_mish, this file includes unet.hip):
+// 128 -> 128 conv exactly as unet_kernel runs it (rd_store2 -> barrier -> rd_taps -> rd_gn_mish, this file includes unet_kernel.h):
 //   base: 512 workgroups of 4 samples, 2 per CU  (hipcc ... -o fat_base)
 //   fat : 256 workgroups of 8 samples = two halves; per phase the taps of one half and the epilogue + slab store of the other sit
 //         in one basic block and a sched_group_barrier pipeline asks for 3 MFMAs : 4 VALU  (hipcc -DFAT ... -o fat_fat)
 // Prints the time per conv of 8 samples per CU.  Build (both): hipcc --offload-arch=gfx950 -O3 -std=c++17 -fno-slp-vectorize [-DFAT]
-//   tools/ubench/fatwave_conv.hip mmd_amd/csrc/{unet_layers,guide,api,multi_agent,postprocess}.hip -o build_tmp/fat_{base,fat}
+//   tools/ubench/fatwave_conv.hip mmd_amd/csrc/{unet,unet_layers,guide,api,multi_agent,postprocess}.hip -o build_tmp/fat_{base,fat}
 #ifdef FAT
 #define MMD_VB3_LOOSE
 #define MMD_NO_PIN
@@ -13,7 +13,7 @@
 #ifndef VPT
 #define VPT 4                 // VALU instructions asked for after each MFMA triple (HOOK variant)
 #endif
-#include "../../mmd_amd/csrc/unet.hip"
+#include "../../mmd_amd/csrc/unet_kernel.h"
 
 #include <cstdio>
 #include <random>

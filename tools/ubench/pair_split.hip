@@ -2,7 +2,7 @@
 // <= 256 trajectories (83 us whatever the batch: one workgroup's 25 dependent convs, each bound by streaming the conv's whole
 // weight pack through ONE CU -- 320 KB for a 128 -> 128 conv at L = 16, where the GEMM is only 32 rows)?
 //
-// The loop body is downs.2 / mid's 128 -> 128 conv exactly as unet_kernel<2> runs it (this file includes unet.hip: rd_store ->
+// The loop body is downs.2 / mid's 128 -> 128 conv exactly as unet_kernel<2> runs it (this file includes unet_kernel.h: rd_store ->
 // barrier -> rd_taps -> rd_gn_mish), 7 distinct weight packs cycled (downs.2's four convs + mid's... the seven 128 -> 128 convs),
 // two samples per workgroup:
 //   base : one workgroup owns the two samples' 128 output channels (wave = 2 interleaved n-tiles): today's kernel.
@@ -17,8 +17,8 @@
 //          flag with a read-modify-write (executes in the L2); the reader polls with device-scope loads and invalidates its L1
 //          (acquire fence) before copying.  The floor of what an exchange through L2 costs.
 // Prints us per conv.  Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -fno-slp-vectorize -w tools/ubench/pair_split.hip
-//   mmd_amd/csrc/{unet_layers,guide,api,multi_agent,postprocess}.hip -o build_tmp/pair_split ; run: build_tmp/pair_split [workgroups of the base arm]
-#include "../../mmd_amd/csrc/unet.hip"
+//   mmd_amd/csrc/{unet,unet_layers,guide,api,multi_agent,postprocess}.hip -o build_tmp/pair_split ; run: build_tmp/pair_split [workgroups of the base arm]
+#include "../../mmd_amd/csrc/unet_kernel.h"
 
 #include <cstdio>
 #include <cstdlib>
