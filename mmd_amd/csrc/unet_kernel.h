@@ -39,9 +39,6 @@
 
 namespace mmd {
 
-
-enum { RES_NONE = 0, RES_IDENT = 1, RES_CONV = 2 };
-
 // final Conv1dBlock(32->32, k5) + Conv1d(32->4, k1) of the network
 struct FinalArgs {
   float* out;             // eps [n, 64, 4]
@@ -105,6 +102,11 @@ __device__ __forceinline__ float row_max16(float v) {      // max over the 16 la
   v = dpp_max<0x140>(v);
   return v;
 }
+__device__ __forceinline__ float wave_max(float v) {       // max over the wave's 64 lanes, in all of them (v >= 0)
+  v = row_max16(v);
+  v = max_xor16(v);
+  return max_xor32(v);
+}
 constexpr int MX_SLOTS = 8;                                  // partial maxima per sample (waves x lane groups sharing a sample)
 constexpr int MX_REGION = 4 * MX_SLOTS;                      // region 0: the conv being prepared; 1 / 2: downs.2's skip2 / the
 constexpr int MX_FLOATS = 3 * MX_REGION;                     // mid blocks' output, kept for ups.0's conv A
@@ -154,7 +156,6 @@ __device__ __forceinline__ float dpp_add(float v) {   // v + v[DPP-permuted lane
   return v + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
 }
 // ----------------------------------------------------------------------------------------------------------------
-enum { TAIL_NONE = 0, TAIL_DOWN = 1, TAIL_UP = 2 };
 constexpr int MAX_IDENT = 3;
 
 struct RtbPtrs {
@@ -180,19 +181,122 @@ struct ChainArgs {
   int n;
 };
 
-// Shape of a stage: RTB (C0 [+ C1 concatenated] -> CM channels, 1x1 residual conv), N_IDENT identity RTBs (the skip tensor is
-// the output of RTB number MID_AFTER), an optional strided / transposed tail conv; L = length of the level.  A workgroup owns
-// SPB = 4 samples in every stage.  XSTR / XSS: row and sample stride (floats) of the one row-form fp32 slab left, the stage's
-// input as the previous stage's tail hands it over (downs.1 -> downs.2): [sample][2 + position][channel], even row stride (two
-// channels per 8-byte access), sample stride padded to 16 (mod 32) floats.
-template <int C0_, int C1_, int CM_, int L_, int RES0_, int N_IDENT_, int MID_AFTER_, int TAIL_>
-struct ChainCfg {
-  static constexpr int C0 = C0_, C1 = C1_, CM = CM_, L = L_, RES0 = RES0_, N_IDENT = N_IDENT_;
-  static constexpr int MID_AFTER = MID_AFTER_, TAIL = TAIL_, SPB = 4;
-  static constexpr int C0P = (C0 + 7) / 8 * 8, XSTR = C0P + 2, SROWS = L + 4;
+// The five stages, each an RTB with a 1x1 residual conv, identity RTBs and an optional strided / transposed tail conv; a workgroup owns
+// the same 4 (2, 1) samples in every stage:
+//   downs.0   4 -> 32 channels at L = 64: RTB, RTB, Downsample1d               (chain_body_d0w / d0s)
+//   downs.1  32 -> 64 at L = 32: RTB, RTB (its output = skip1), Downsample1d   (chain_body_d1d)
+//   downs.2 + mid_block1 / 2  64 -> 128 at L = 16: RTB + D2::N_IDENT RTBs      (chain_body_d2d)
+//   ups.0    cat(x, skip2) 256 -> 64 at L = 16: RTB, RTB, Upsample1d           (chain_body_u0d)
+//   ups.1    cat(x, skip1) 128 -> 32 at L = 32: RTB, RTB, Upsample1d, + the final block at L = 64   (chain_body_u1w / u1s)
+// D2: downs.2 + mid blocks.  N_IDENT identity RTBs follow RTB 0, the skip tensor (skip2) is the output of RTB number MID_AFTER.
+// XSTR / XSS: row and sample stride (floats) of the one row-form fp32 slab left, the stage's input as downs.1's tail hands it
+// over: [sample][2 + position][channel], even row stride (two channels per 8-byte access), sample stride padded to 16 (mod 32)
+// floats.  SLAB_OFF: the stage's Rd slab lies behind the x slab of the four samples.
+struct D2 {
+  static constexpr int N_IDENT = 3, MID_AFTER = 1, C0 = 64, XSTR = C0 + 2, SROWS = 16 + 4;
   static constexpr int XSS = SROWS * XSTR + (16 - (SROWS * XSTR) % 32 + 32) % 32;
-  static_assert(CM % 32 == 0 && L >= 16 && N_IDENT <= MAX_IDENT, "stage shape");
+  static constexpr int SLAB_OFF = (4 * XSS * 4 + 255) / 256 * 256;
+  static_assert(N_IDENT <= MAX_IDENT && MID_AFTER >= 1, "ChainArgs::ri holds the identity RTBs");
 };
+
+constexpr int cmax(int a, int b) { return a > b ? a : b; }
+// LDS of a workgroup: the largest stage is downs.2 / ups.0 -- the row-form fp32 x slab of downs.2's input + the 128-channel Rd
+// slab (2 x 21504 B) behind it; downs.1 (input slab + 64-channel slab) and the four private slabs of the wave-private stages
+// (downs.0, ups.1 + final block) fit below it (static_asserts at the stages: D0, U1, the stage bodies).
+constexpr int MX_OFF = (D2::SLAB_OFF + 43008) / 4 + 8;
+// + the per-sample maxima of the dynamic input scales + the second part of downs.2's lane-private residual parking area (the
+// first part is the stage's dead x slab: 5 + 3 float4 per thread)
+constexpr int PARK2_OFF = MX_OFF + MX_FLOATS;
+constexpr int UNET_LDS_FLOATS = PARK2_OFF + 3 * 256 * 4;
+static_assert(UNET_LDS_FLOATS * 4 == 76960, "LDS of a workgroup");
+
+// GroupNorm-epilogue parameters of an RTB's conv A (with its time bias, tb_off floats into the table) / conv B for channels c0 ..
+template <int NT>
+__device__ __forceinline__ Epi<NT> epi_a(const RtbPtrs& R, int tb_off, int c0) { return epi_load<NT>(R.ba, R.ga, R.bea, R.tb + tb_off, R.isa, c0); }
+template <int NT>
+__device__ __forceinline__ Epi<NT> epi_b(const RtbPtrs& R, int c0) { return epi_load<NT>(R.bb, R.gb, R.beb, nullptr, R.isb, c0); }
+
+// The lane's pointers into a weight pack for the n-tiles tile0 .. tile0 + NT - 1 (`frags` 1 KiB fragments [lane] x 16 B per n-tile)
+template <int NT> struct WTiles { const u32x4* p[NT]; };
+template <int NT>
+__device__ __forceinline__ WTiles<NT> w_tiles(const void* w, int frags, int tile0, int lane) {
+  WTiles<NT> r;
+#pragma unroll
+  for (int t = 0; t < NT; ++t) r.p[t] = reinterpret_cast<const u32x4*>(w) + (size_t)(tile0 + t) * frags * 64 + lane;
+  return r;
+}
+
+// "Request the NEXT conv's first ring steps right behind this conv's taps", for a wave that holds `m_tiles` M tiles per conv.  At <= 2
+// (unet_kernel<2> / <1>: the latency-bound launches of <= 512 trajectories, where nothing else on the CU covers an L2 round trip) they
+// travel during the GroupNorm + Mish epilogue and the slab store instead of in front of the first MFMA (tools/ubench/pair_split.hip, arm
+// basePF: 3 - 10 % of a conv); with four M tiles the ring registers would have to live through the epilogue of a 32-register tile.
+constexpr bool ring_prefetch(int m_tiles) {
+#ifdef MMD_NO_PF
+  return false;                                              // (A/B side build: profiles/r06_prefetch_ab.txt)
+#else
+  return m_tiles <= 2;
+#endif
+}
+
+// ---- tiles: t[M tile][n-tile] of f32x4 (a lane's 4 positions of one channel)
+template <int M, int N>
+__device__ __forceinline__ void tile_scale(f32x4 (&t)[M][N], float s) {
+#pragma unroll
+  for (int m = 0; m < M; ++m)
+#pragma unroll
+    for (int n = 0; n < N; ++n) t[m][n] *= s;
+}
+template <int M, int N>
+__device__ __forceinline__ void tile_copy(f32x4 (&d)[M][N], const f32x4 (&s)[M][N]) {
+#pragma unroll
+  for (int m = 0; m < M; ++m)
+#pragma unroll
+    for (int n = 0; n < N; ++n) d[m][n] = s[m][n];
+}
+// the raw 1x1 residual conv -> the residual: times its weights' inverse scales and the input's inverse dynamic scale (of the S samples
+// the M tiles belong to, M / S tiles each), + bias
+template <int M, int N, int S>
+__device__ __forceinline__ void tile_finish_res(f32x4 (&r)[M][N], const float (&isr)[N], const float (&inv)[S], const float (&br)[N]) {
+#pragma unroll
+  for (int m = 0; m < M; ++m)
+#pragma unroll
+    for (int n = 0; n < N; ++n) r[m][n] = r[m][n] * (isr[n] * inv[m / (M / S)]) + br[n];
+}
+template <int M, int N>
+__device__ __forceinline__ void tile_finish_res(f32x4 (&r)[M][N], const float (&isr)[N], float inv, const float (&br)[N]) {
+  const float inv1[1] = {inv};
+  tile_finish_res(r, isr, inv1, br);
+}
+// tiles m0 .. m0 + MS - 1 of a larger tile
+template <int MS, int M, int N>
+__device__ __forceinline__ f32x4 (&sub_tile(f32x4 (&t)[M][N], int m0))[MS][N] { return reinterpret_cast<f32x4(&)[MS][N]>(t[m0]); }
+template <int MS, int M, int N>
+__device__ __forceinline__ const f32x4 (&sub_tile(const f32x4 (&t)[M][N], int m0))[MS][N] { return reinterpret_cast<const f32x4(&)[MS][N]>(t[m0]); }
+
+// What a GroupNorm + Mish epilogue adds behind Mish.  Conv A of an RTB: the time bias, and the output is carried times act_s, the static
+// f16x2 input scale of conv B (ACT); conv B: the residual tile.
+template <int NT> struct AddTimeBias {
+  static constexpr bool ACT = true;
+  float tb[NT];
+  ActScale as;
+  __device__ __forceinline__ float operator()(int, int t, int) const { return tb[t]; }
+};
+template <int MT, int NT> struct AddResidual {
+  static constexpr bool ACT = false;
+  const f32x4 (&res)[MT][NT];
+  ActScale as;
+  __device__ __forceinline__ float operator()(int mt, int t, int r) const { return res[mt][t][r]; }
+};
+template <int NT>
+__device__ __forceinline__ AddTimeBias<NT> gn_addend(const Epi<NT>& e, float act_s) {
+  AddTimeBias<NT> a;
+#pragma unroll
+  for (int t = 0; t < NT; ++t) a.tb[t] = e.tb[t] * act_s;
+  a.as = act_scale(act_s);
+  return a;
+}
+template <int MT, int NT>
+__device__ __forceinline__ AddResidual<MT, NT> gn_addend(const Epi<NT>&, const f32x4 (&res)[MT][NT]) { return AddResidual<MT, NT>{res, ActScale{}}; }
 
 // sum over the CPG adjacent lanes (channels) of a GroupNorm group, same value in all of them
 template <int CPG>
@@ -204,23 +308,6 @@ __device__ __forceinline__ float group_colsum(float v) {
   return v;
 }
 
-
-//                  C0   C1   CM   L   RES0      N_IDENT MID_AFTER TAIL
-using CH_D0 = ChainCfg<4, 0, 32, 64, RES_CONV, 1, -1, TAIL_DOWN>;     // downs.0: RTB, RTB, Downsample1d
-using CH_D1 = ChainCfg<32, 0, 64, 32, RES_CONV, 1, 1, TAIL_DOWN>;     // downs.1 (skip1 = output of its 2nd RTB)
-using CH_D2 = ChainCfg<64, 0, 128, 16, RES_CONV, 3, 1, TAIL_NONE>;    // downs.2 + mid_block1/2 (skip2 after downs.2)
-using CH_U0 = ChainCfg<128, 128, 64, 16, RES_CONV, 1, -1, TAIL_UP>;   // ups.0: cat(x, skip2) RTB, RTB, Upsample1d
-using CH_U1 = ChainCfg<64, 64, 32, 32, RES_CONV, 1, -1, TAIL_UP>;     // ups.1: cat(x, skip1) RTB, RTB, Upsample1d
-
-constexpr int cmax(int a, int b) { return a > b ? a : b; }
-// LDS of a workgroup: the largest stage is downs.2 / ups.0 -- the row-form fp32 x slab of downs.2's input + the 128-channel Rd
-// slab (2 x 21504 B) behind it; downs.1 (input slab + 64-channel slab) and the four private slabs of the wave-private stages
-// (downs.0, ups.1 + final block) fit below it (static_asserts in the stage bodies).
-constexpr int MX_OFF = ((CH_D2::SPB * CH_D2::XSS * 4 + 255) / 256 * 256 + 43008) / 4 + 8;
-// + the per-sample maxima of the dynamic input scales + the second part of downs.2's lane-private residual parking area (the
-// first part is the stage's dead x slab: 5 + 3 float4 per thread)
-constexpr int PARK2_OFF = MX_OFF + MX_FLOATS;
-constexpr int UNET_LDS_FLOATS = PARK2_OFF + 3 * 256 * 4;
 
 // ----------------------------------------------------------------------------------------------------------------
 // DIRECT f16x2 convolutions on a row-form slab (downs.1, downs.2 + mid blocks, ups.0; the wave-private stages use the same
@@ -424,6 +511,13 @@ __device__ __forceinline__ void rd_gn_mish(f32x4 (&acc)[NS][NT], const float (&b
     }
   }
 }
+// The epilogue of a conv of the workgroup-slab stages.  `addend`: conv A's act_s (+ the time bias, output carried times act_s) or conv
+// B's residual tile (gn_addend)
+template <int NG, int NS, int NT, class ADDEND>
+__device__ __forceinline__ void rd_gn(f32x4 (&acc)[NS][NT], const Epi<NT>& e, const float (&inv)[NS], const ADDEND& addend) {
+  const auto add = gn_addend(e, addend);
+  rd_gn_mish<NT, NG, decltype(add)::ACT>(acc, e.b, e.g, e.be, e.is, inv, add.as, add);
+}
 // per-sample |x| maxima of a direct-layout tile -> mx region 0 (and region2 if > 0): row_max16, one cross-row step,
 // lanes 0 / 32 write the wave's two partials: slots 2 wave + {0, 1} of MX_SLOTS = 8
 template <int NT, int NS>
@@ -446,6 +540,17 @@ __device__ __forceinline__ void rd_dyn_out(const f32x4 (&acc)[NS][NT], float* mx
 __device__ __forceinline__ float mx_read(const float* mx, int sm) {
   const float4 p = *reinterpret_cast<const float4*>(mx + sm * MX_SLOTS), q = *reinterpret_cast<const float4*>(mx + sm * MX_SLOTS + 4);
   return fmaxf(fmaxf(fmaxf(p.x, p.y), fmaxf(p.z, p.w)), fmaxf(fmaxf(q.x, q.y), fmaxf(q.z, q.w)));
+}
+// dynamic input scale of a conv on tile t (samples s0 .. s0 + S - 1, M / S M tiles each) from the samples' maxima in mx: scale in place;
+// inv: the inverse scales
+template <int M, int N, int S>
+__device__ __forceinline__ void mx_scale_tile(const float* mx, int s0, f32x4 (&t)[M][N], float (&inv)[S]) {
+#pragma unroll
+  for (int sl = 0; sl < S; ++sl) {
+    const DynScale ds = dyn_scale(mx_read(mx, s0 + sl));
+    inv[sl] = ds.inv;
+    tile_scale(sub_tile<M / S>(t, M / S * sl), ds.s);
+  }
 }
 // two-interleaved-n-tile tile (lane: channels c0, c0 + 1 = block 4 wave + (n >> 2), dword n & 3; positions 4 g + r) -> slab
 template <class GEO, int NS>
@@ -537,18 +642,19 @@ __device__ __forceinline__ float wave_sum_rows(float v) {   // v + the same lane
   v = add_xor32(v);
   return v;
 }
+template <int GL>
+__device__ __forceinline__ float rw_gsum(float v) {          // sum over the GL lanes of a group and the wave's four 16-lane rows
+  v = dpp_add<0xB1>(v);
+  if constexpr (GL >= 4) v = dpp_add<0x4E>(v);
+  if constexpr (GL >= 8) v = dpp_add<0x141>(v);
+  return wave_sum_rows(v);
+}
 // GroupNorm + Mish of ONE sample's tile acc[M tile][tile] (positions 16 mt + 4 g + r; true value = acc * isc[tile] * inv);
 // GL = lanes per group (the lane's NT channels belong to one group), NG = values per group
 template <int MT, int NT, int GL, int NG, bool ACT, class ADD>
 __device__ __forceinline__ void rw_gn_mish(f32x4 (&acc)[MT][NT], const float (&bias)[NT], const float (&gamma)[NT],
                                            const float (&beta)[NT], const float (&isc)[NT], float inv, const ActScale& as, ADD add) {
   constexpr float inv_n = 1.f / (float)NG;
-  auto gsum = [](float v) {
-    v = dpp_add<0xB1>(v);
-    if constexpr (GL >= 4) v = dpp_add<0x4E>(v);
-    if constexpr (GL >= 8) v = dpp_add<0x141>(v);
-    return wave_sum_rows(v);
-  };
   float k[NT], bsum = 0.f, v = 0.f;
 #pragma unroll
   for (int t = 0; t < NT; ++t) {
@@ -560,7 +666,7 @@ __device__ __forceinline__ void rw_gn_mish(f32x4 (&acc)[MT][NT], const float (&b
     v = fmaf(st, k[t], v);
   }
   // mean over the group of (x + bias): every channel's bias counts at the sample's 16 MT positions, 4 per lane row
-  const float mean = (gsum(v) + gsum(bsum) * (float)(4 * MT)) * inv_n;
+  const float mean = (rw_gsum<GL>(v) + rw_gsum<GL>(bsum) * (float)(4 * MT)) * inv_n;
   float dm[NT], q = 0.f;
 #pragma unroll
   for (int t = 0; t < NT; ++t) {
@@ -573,7 +679,7 @@ __device__ __forceinline__ void rw_gn_mish(f32x4 (&acc)[MT][NT], const float (&b
         q = fmaf(d, d, q);
       }
   }
-  const float rstd = __builtin_amdgcn_rsqf(fmaf(gsum(q), inv_n, 1e-5f));
+  const float rstd = __builtin_amdgcn_rsqf(fmaf(rw_gsum<GL>(q), inv_n, 1e-5f));
 #pragma unroll
   for (int t = 0; t < NT; ++t) {
     GnCoef cf = gn_coef(dm[t], rstd, gamma[t], beta[t]);
@@ -594,13 +700,6 @@ __device__ __forceinline__ void rw_gn_mish(f32x4 (&acc)[MT][NT], const float (&b
 // by the pairwise update mean = (m0 + m1) / 2, M2 = (M2_0 + M2_1) + (m1 - m0)^2 N / 4.  A whole-sample wave evaluates both halves
 // itself; two half-sample waves evaluate one each and swap (mean, M2) through LDS -- the same arithmetic, the same bits.
 struct HalfStat { float mean, m2; };
-template <int GL>
-__device__ __forceinline__ float rw_gsum(float v) {          // sum over the GL lanes of a group and the wave's four 16-lane rows
-  v = dpp_add<0xB1>(v);
-  if constexpr (GL >= 4) v = dpp_add<0x4E>(v);
-  if constexpr (GL >= 8) v = dpp_add<0x141>(v);
-  return wave_sum_rows(v);
-}
 // bsum4 = rw_gsum(sum of the lane's biases) (every channel's bias counts once per position: 4 positions per lane row and M tile)
 template <int HT, int NT, int GL, int NG>
 __device__ __forceinline__ HalfStat rw_half_stat(const f32x4 (&acc)[HT][NT], const float (&bias)[NT], const float (&k)[NT], float bsum4) {
@@ -653,21 +752,27 @@ __device__ __forceinline__ void rw_gn_apply(f32x4 (&acc)[MT][NT], const float (&
       }
   }
 }
+// k[tile] = the factor from acc to the true value; returns bsum4 of rw_half_stat
+template <int GL, int NT>
+__device__ __forceinline__ float rw_gn_prologue(const float (&bias)[NT], const float (&isc)[NT], float inv, float (&k)[NT]) {
+  float bsum = 0.f;
+#pragma unroll
+  for (int t = 0; t < NT; ++t) {
+    k[t] = isc[t] * inv;
+    bsum += bias[t];
+  }
+  return rw_gsum<GL>(bsum);
+}
 // ... of a WHOLE sample held by one wave (MT = 2 HT M tiles)
 template <int MT, int NT, int GL, int NG, bool ACT, class ADD>
 __device__ __forceinline__ void rw_gn_mish_whole(f32x4 (&acc)[MT][NT], const float (&bias)[NT], const float (&gamma)[NT],
                                                  const float (&beta)[NT], const float (&isc)[NT], float inv, const ActScale& as, ADD add) {
   constexpr int HT = MT / 2;
   static_assert(MT == 2 || MT == 4, "two halves of one or two M tiles");
-  float k[NT], bsum = 0.f;
-#pragma unroll
-  for (int t = 0; t < NT; ++t) {
-    k[t] = isc[t] * inv;
-    bsum += bias[t];
-  }
-  const float bsum4 = rw_gsum<GL>(bsum);
-  const HalfStat h0 = rw_half_stat<HT, NT, GL, NG>(reinterpret_cast<const f32x4(&)[HT][NT]>(acc[0]), bias, k, bsum4);
-  const HalfStat h1 = rw_half_stat<HT, NT, GL, NG>(reinterpret_cast<const f32x4(&)[HT][NT]>(acc[HT]), bias, k, bsum4);
+  float k[NT];
+  const float bsum4 = rw_gn_prologue<GL>(bias, isc, inv, k);
+  const HalfStat h0 = rw_half_stat<HT, NT, GL, NG>(sub_tile<HT>(acc, 0), bias, k, bsum4);
+  const HalfStat h1 = rw_half_stat<HT, NT, GL, NG>(sub_tile<HT>(acc, HT), bias, k, bsum4);
   rw_gn_apply<MT, NT, ACT>(acc, bias, gamma, beta, k, gn_combine<NG>(h0, h1), as, add);
 }
 // ... of the HALF sample this wave holds (HT M tiles; half index hf); the partner wave's statistics arrive through xch = the
@@ -677,13 +782,8 @@ template <int HT, int NT, int GL, int NG, bool ACT, class ADD>
 __device__ __forceinline__ void rw_gn_mish_half(f32x4 (&acc)[HT][NT], const float (&bias)[NT], const float (&gamma)[NT],
                                                 const float (&beta)[NT], const float (&isc)[NT], float inv, const ActScale& as, ADD add,
                                                 HalfStat* xch, int hf, int lane) {
-  float k[NT], bsum = 0.f;
-#pragma unroll
-  for (int t = 0; t < NT; ++t) {
-    k[t] = isc[t] * inv;
-    bsum += bias[t];
-  }
-  const float bsum4 = rw_gsum<GL>(bsum);
+  float k[NT];
+  const float bsum4 = rw_gn_prologue<GL>(bias, isc, inv, k);
   const HalfStat own = rw_half_stat<HT, NT, GL, NG>(acc, bias, k, bsum4);
   xch[hf * 64 + lane] = own;
   __syncthreads();
@@ -700,9 +800,7 @@ __device__ __forceinline__ float rw_absmax(const f32x4 (&acc)[MT][NT]) {   // th
     for (int t = 0; t < NT; ++t)
 #pragma unroll
       for (int r = 0; r < 4; ++r) m = fmaxf(m, fabsf(acc[mt][t][r]));
-  m = row_max16(m);
-  m = max_xor16(m);
-  return max_xor32(m);
+  return wave_max(m);
 }
 // two-interleaved-n-tile tile of one sample (lane: channels 2 n, 2 n + 1 (+ 32 per further pair); positions 16 mt + 4 g + r)
 // -> the wave's slab; vs = slab + the lane's (block n >> 2, row 2 + 4 g, dword n & 3) offset
@@ -722,192 +820,86 @@ __device__ __forceinline__ void wave_lds_fence() {           // a wave's own LDS
   __builtin_amdgcn_wave_barrier();
 }
 
-// downs.0 (4 -> 32 -> 32 channels at L = 64, Downsample1d): wave = sample.  The first conv's K is 5 taps x 4 channels = 20
-// of the 32 slots of ONE MFMA chunk (im2col: lane group j holds taps 2 j, 2 j + 1 -- two consecutive 8-byte rows of the
-// [row][4 channel] input slab), its 1x1 residual conv a second chunk with only the centre tap's slots non-zero.  The raw
-// network input has no bounded range: dynamic scale from the sample's own maximum.  The stride-2 tail reads its slab at stride 2
-// (Stride2: 3 taps on two M tiles, 36 MFMAs; the A reads are 2-way bank conflicted, half as many as at every position).
-// The stage's output goes straight into the next stage's input slab (RlGeo<32>) as f16 pieces under the sample's own dynamic
-// scale, behind a workgroup barrier (it aliases the waves' slabs); the sample's maximum goes to mx.
-template <class CF, int NS>
-__device__ __forceinline__ void chain_body_d0w(const ChainArgs& a, float* lds, int n0, int lane, int wave, int trb, int tb_off = 0) {
-  static_assert(CF::L == 64 && CF::CM == 32 && CF::C0 == 4 && CF::C1 == 0 && CF::RES0 == RES_CONV && CF::N_IDENT == 1 &&
-                    CF::TAIL == TAIL_DOWN, "downs.0");
-  using GW = RwGeo<32, 64>;
-  constexpr int XIN = 72 * 8;                                // bytes per piece of the [row][4 channel] input slab (rows -2 .. 69)
-  constexpr int W_BYTES = GW::BYTES + 2 * XIN + 128;
-  static_assert(4 * W_BYTES <= MX_OFF * 4, "four private slabs");
-  char* const slab = reinterpret_cast<char*>(lds) + wave * W_BYTES;
-  char* const xin = slab + GW::BYTES;
-  const int n = lane & 15, g = lane >> 4, c0 = 2 * n;
-  const char* const va = slab + g * GW::G + n * 16;          // A fragment: row lane & 15, lane group lane >> 4 (KC = 1: block j)
-  char* const vs = slab + (n >> 2) * GW::G + (2 + 4 * g) * 16 + (n & 3) * 4;
-  auto wptr = [&](const uint4* w, int frags, int t) { return reinterpret_cast<const u32x4*>(w) + (size_t)t * frags * 64 + lane; };
-  TR(trb + 0);
-  // ---- stage the sample: lane = position; [row = 2 + position][4 channels] x two pieces, zero rows around it
-  float inv_in;
-  {
-    const bool valid = wave < NS && n0 + wave < a.n;           // (NS < 4: the other waves run on zeros, see unet_kernel)
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (valid) v = *reinterpret_cast<const float4*>(a.in0 + ((size_t)(n0 + wave) * 64 + lane) * 4);
-    float m = fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w)));
-    m = row_max16(m);
-    m = max_xor16(m);
-    m = max_xor32(m);
-    const DynScale ds = dyn_scale(m);
-    inv_in = ds.inv;
-    const F16Pair p0 = f16_split2(v.x * ds.s, v.y * ds.s), p1 = f16_split2(v.z * ds.s, v.w * ds.s);
-    *reinterpret_cast<uint2*>(xin + (2 + lane) * 8) = make_uint2(p0.hi, p1.hi);
-    *reinterpret_cast<uint2*>(xin + XIN + (2 + lane) * 8) = make_uint2(p0.lo, p1.lo);
-    if (lane < 16) {                                         // rows 0, 1, 66 .. 71 of both pieces
-      const int row = (lane & 7) < 2 ? (lane & 7) : 64 + (lane & 7);
-      *reinterpret_cast<uint2*>(xin + (lane >> 3) * XIN + row * 8) = make_uint2(0u, 0u);
-    }
-    // zero halo rows of the conv slab (rows 0, 1, 66, 67 of the 4 blocks x 2 pieces)
-    if (lane < 32) *reinterpret_cast<uint4*>(slab + (lane >> 4) * GW::PS + ((lane >> 2) & 3) * GW::G + ((lane & 3) < 2 ? (lane & 3) : 64 + (lane & 3)) * 16) = make_uint4(0u, 0u, 0u, 0u);
+// The epilogue of a conv of the wave-private stages, on the wave's whole sample or (RwHalf) on its half of the sample.  `addend`: as rd_gn
+struct RwHalf { HalfStat* xch; int hf, lane; };              // the partner-wave exchange of rw_gn_mish_half
+template <int GL, int NG, int MT, int NT, class ADDEND>
+__device__ __forceinline__ void rw_gn(f32x4 (&acc)[MT][NT], const Epi<NT>& e, float inv, const ADDEND& addend) {
+  const auto add = gn_addend(e, addend);
+  rw_gn_mish_whole<MT, NT, GL, NG, decltype(add)::ACT>(acc, e.b, e.g, e.be, e.is, inv, add.as, add);
+}
+template <int GL, int NG, int HT, int NT, class ADDEND>
+__device__ __forceinline__ void rw_gn(f32x4 (&acc)[HT][NT], const Epi<NT>& e, float inv, const ADDEND& addend, const RwHalf& h) {
+  const auto add = gn_addend(e, addend);
+  rw_gn_mish_half<HT, NT, GL, NG, decltype(add)::ACT>(acc, e.b, e.g, e.be, e.is, inv, add.as, add, h.xch, h.hf, h.lane);
+}
+// ... on downs.1's tile of S samples x M / S M tiles, sample by sample (a sample's group is wave-internal there: rw_gn_mish)
+template <int TPS>
+__device__ __forceinline__ float sample_of(float act_s, int) { return act_s; }
+template <int TPS, int M, int N>
+__device__ __forceinline__ const f32x4 (&sample_of(const f32x4 (&t)[M][N], int sl))[TPS][N] { return sub_tile<TPS>(t, TPS * sl); }
+template <int GL, int NG, int M, int NT, int S, class ADDEND>
+__device__ __forceinline__ void rw_gn_samples(f32x4 (&acc)[M][NT], const Epi<NT>& e, const float (&inv)[S], const ADDEND& addend) {
+  constexpr int TPS = M / S;
+#pragma unroll
+  for (int sl = 0; sl < S; ++sl) {
+    const auto add = gn_addend(e, sample_of<TPS>(addend, sl));
+    rw_gn_mish<TPS, NT, GL, NG, decltype(add)::ACT>(sub_tile<TPS>(acc, TPS * sl), e.b, e.g, e.be, e.is, inv[sl], add.as, add);
   }
-  wave_lds_fence();
-  f32x4 acc[4][2], res[4][2];
-  const Epi<2> e0a = epi_load<2>(a.r0.ba, a.r0.ga, a.r0.bea, a.r0.tb + tb_off, a.r0.isa, c0);
-  const float br0[2] = {a.br[c0], a.br[c0 + 1]}, isr0[2] = {a.isr[c0], a.isr[c0 + 1]};
-  // ---- RTB 0 conv A (im2col chunk) + the 1x1 residual conv
-  {
-    u32x4 b[2][2], br[2][2];
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-      for (int q = 0; q < 2; ++q) {
-        b[t][q] = wptr(a.r0.wa_bf, 2, t)[q * 64];
-        br[t][q] = wptr(a.wres_bf, 2, t)[q * 64];
-      }
-#pragma unroll
-    for (int mt = 0; mt < 4; ++mt) {
-      u32x4 af[2];
-#pragma unroll
-      for (int q = 0; q < 2; ++q) {
-        const uint2* p = reinterpret_cast<const uint2*>(xin + q * XIN + (mt * 16 + n + 2 * g) * 8);
-        const uint2 lo = p[0], hi = p[1];
-        af[q] = u32x4{lo.x, lo.y, hi.x, hi.y};
-      }
-#pragma unroll
-      for (int t = 0; t < 2; ++t) {
-        vb_three<true>(acc[mt][t], af, b[t]);
-        vb_three<true>(res[mt][t], af, br[t]);
-      }
-    }
+}
+// Zero the four halo rows (0, 1, rows + 2, rows + 3) of a wave-private-geometry slab: 4 KC blocks x 2 pieces, one 16-byte store per
+// lane (KC = 1: lanes 0 .. 31).  base = the slab's first row; `mine`: whether this wave is the one that zeroes (half-sample stages: one
+// wave per sample)
+template <class GEO>
+__device__ __forceinline__ void rw_zero_halo(char* base, int rows, int lane, bool mine) {
+  constexpr int KC = GEO::KC;
+  if (mine && (32 * KC >= 64 || lane < 32 * KC)) {
+    const int hr = lane & 3, blk = (lane >> 2) % (4 * KC), q = lane / (16 * KC);
+    *reinterpret_cast<uint4*>(base + q * GEO::PS + (blk / KC) * GEO::G + (blk % KC) * GEO::BX + (hr < 2 ? hr : rows + hr) * 16) =
+        make_uint4(0u, 0u, 0u, 0u);
   }
-  const float one = 1.f;
-  auto epi = [&](const float* bs, const float* gm, const float* be, const float* tb, const float* isc) {
-    return epi_load<2>(bs, gm, be, tb, isc, c0);
-  };
-  auto gn = [&](auto conv_a, const Epi<2>& e, float inv, float act_s) {
-    if constexpr (decltype(conv_a)::value) {
-      const float t0 = e.tb[0] * act_s, t1 = e.tb[1] * act_s;
-      rw_gn_mish_whole<4, 2, 2, 256, true>(acc, e.b, e.g, e.be, e.is, inv, act_scale(act_s), [&](int, int t, int) { return t ? t1 : t0; });
-    } else {
-      rw_gn_mish_whole<4, 2, 2, 256, false>(acc, e.b, e.g, e.be, e.is, inv, ActScale{}, [&](int mt, int t, int r) { return res[mt][t][r]; });
-    }
-  };
-  // The whole weight set of a conv (5 taps x 2 n-tiles x 2 pieces = 20 KB per wave) is requested BEFORE the epilogue that
-  // produces the conv's input (preload), so the L2 latency hides behind GroupNorm + Mish instead of in front of the MFMAs.
-  u32x4 ring[5][2][2];
-  auto preload = [&](const uint4* w) {
-    const u32x4* wp[2] = {wptr(w, GW::FRAGS5, 0), wptr(w, GW::FRAGS5, 1)};
-    rd_ring_load<GW, 2, 5>(ring, wp);
-  };
-  auto conv = [&](const uint4* w) {                          // one 32 -> 32 conv over the tile in acc (already scaled)
-    const u32x4* wp[2] = {wptr(w, GW::FRAGS5, 0), wptr(w, GW::FRAGS5, 1)};
-    rw_store2<GW, 4>(vs, acc);
-    wave_lds_fence();
-    rd_taps<GW, 2, 0, 5, true, false, 4, 5>(acc, res, va, wp, wp, ring);
-    wave_lds_fence();                                        // (the next store must not overtake these reads)
-  };
+}
+// per-sample |x| maxima of a tile in downs.1's layout (wave = (channel half np = wave & 1, sample pair sp = wave >> 1); M tiles 2 sl,
+// 2 sl + 1 = sample NS / 2 * sp + sl) -> K of the sample's mx slots from SLOT0 on (the two waves of a sample pair fill 2 K slots)
+template <int K, int SLOT0, int NS>
+__device__ __forceinline__ void pair_maxima_out(const f32x4 (&v)[NS][2], float* mx, int wave, int lane) {
+  constexpr int SW = NS / 2;
+  const int np = wave & 1, s0 = SW * (wave >> 1);
+  float m2[2] = {0.f, 0.f};
 #pragma unroll
-  for (int mt = 0; mt < 4; ++mt)
+  for (int sl = 0; sl < SW; ++sl) m2[sl] = rw_absmax(sub_tile<2>(v, 2 * sl));
+  if (lane < K * SW) mx[(s0 + lane / K) * MX_SLOTS + SLOT0 + np + 2 * (lane & (K - 1))] = SW == 2 && lane / K ? m2[1] : m2[0];
+}
+// strided tail: y = y * is + bt in place; returns the wave's |y| maximum
+template <int MT, int NT>
+__device__ __forceinline__ float tail_epilogue(f32x4 (&y)[MT][NT], const float (&is)[NT], const float (&bt)[NT]) {
+  float m = 0.f;
 #pragma unroll
-    for (int t = 0; t < 2; ++t) res[mt][t] = res[mt][t] * (isr0[t] * inv_in) + br0[t];
-  preload(a.r0.wb_bf);
-  gn(std::true_type{}, e0a, inv_in, a.r0.act_a);
-  TR(trb + 1);
-  {
-    const Epi<2> e = epi(a.r0.bb, a.r0.gb, a.r0.beb, nullptr, a.r0.isb);
-    conv(a.r0.wb_bf);
-    preload(a.ri[0].wa_bf);
-    gn(std::false_type{}, e, one, 1.f);
-  }
-  TR(trb + 2);
-  // ---- identity RTB
-  {
-    const RtbPtrs& R = a.ri[0];
+  for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
-    for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-      for (int t = 0; t < 2; ++t) res[mt][t] = acc[mt][t];
-    const DynScale ds = dyn_scale(rw_absmax<4, 2>(acc));
-#pragma unroll
-    for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-      for (int t = 0; t < 2; ++t) acc[mt][t] *= ds.s;
-    const Epi<2> ea = epi(R.ba, R.ga, R.bea, R.tb + tb_off, R.isa);
-    conv(R.wa_bf);
-    preload(R.wb_bf);
-    gn(std::true_type{}, ea, ds.inv, R.act_a);
-    TR(trb + 3);
-    const Epi<2> eb = epi(R.bb, R.gb, R.beb, nullptr, R.isb);
-    conv(R.wb_bf);
-    gn(std::false_type{}, eb, one, 1.f);
-    TR(trb + 4);
-  }
-  // ---- tail: Downsample1d = Conv1d(k3, s2, p1): y[p] = sum_t x[p + t - 1] W_t at the even p
-  {
-    const DynScale ds = dyn_scale(rw_absmax<4, 2>(acc));
-#pragma unroll
-    for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-      for (int t = 0; t < 2; ++t) acc[mt][t] *= ds.s;
-    const u32x4* wt[2] = {wptr(a.wt_bf0, GW::FRAGS3, 0), wptr(a.wt_bf0, GW::FRAGS3, 1)};
-    u32x4 ring3[3][2][2];
-    const float bt[2] = {a.bt[c0], a.bt[c0 + 1]}, ist[2] = {a.ist0[c0] * ds.inv, a.ist0[c0 + 1] * ds.inv};
-    rd_ring_load<GW, 2, 3>(ring3, wt);
-    rw_store2<GW, 4>(vs, acc);
-    wave_lds_fence();
-    // (outputs q = 16 mt + 4 g + r = the even positions 2 q: two M tiles read at stride 2)
-    f32x4 y[2][2];
-    rd_taps<Stride2<GW, 0, 2>, 2, 1, 3, true, false, 2, 3>(y, y, va + n * 16, wt, wt, ring3);
-    float mo = 0.f;
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-      for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          y[mt][t][r] = fmaf(y[mt][t][r], ist[t], bt[t]);
-          mo = fmaxf(mo, fabsf(y[mt][t][r]));
-        }
-    mo = row_max16(mo);
-    mo = max_xor16(mo);
-    mo = max_xor32(mo);
-    __syncthreads();                                         // every wave is done with its slab: the next stage's slab aliases them
-    if (lane < MX_SLOTS) (lds + MX_OFF)[wave * MX_SLOTS + lane] = mo;
-    // -> the next stage's input slab (RlGeo<32>: rows 36 sample + 2 + q), channels 2 n, 2 n + 1 = block n >> 2, dword n & 3, as
-    //    f16 pieces under the sample's own dynamic scale (the next stage reads it from mx)
-    using GN = RlGeo<32>;
-    const float so = dyn_scale(mo).s;
-    char* const lb = reinterpret_cast<char*>(lds);
-    char* xb = lb + (n >> 2) * GN::G + (wave * GN::RPS + 2 + 4 * g) * 16 + (n & 3) * 4;
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
+    for (int t = 0; t < NT; ++t)
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const F16Pair f = f16_split2(y[mt][0][r] * so, y[mt][1][r] * so);
-        *reinterpret_cast<unsigned*>(xb + (16 * mt + r) * 16) = f.hi;
-        *reinterpret_cast<unsigned*>(xb + GN::PS + (16 * mt + r) * 16) = f.lo;
+        y[mt][t][r] = fmaf(y[mt][t][r], is[t], bt[t]);
+        m = fmaxf(m, fabsf(y[mt][t][r]));
       }
-    if (lane < 32)                                           // halo rows 0, 1, 34, 35 of the sample's 4 blocks x 2 pieces
-      *reinterpret_cast<uint4*>(lb + (lane >> 4) * GN::PS + ((lane >> 2) & 3) * GN::G +
-                                (wave * GN::RPS + ((lane & 3) < 2 ? (lane & 3) : 32 + (lane & 3))) * 16) = make_uint4(0u, 0u, 0u, 0u);
-  }
-  TR(trb + 5);
+  return wave_max(m);
+}
+// transposed tail: the same for its two parity passes e / o (even / odd output positions); the maximum over both
+template <int MT, int NT>
+__device__ __forceinline__ float tail_up_epilogue(f32x4 (&e)[MT][NT], f32x4 (&o)[MT][NT], const float (&is0)[NT], const float (&is1)[NT],
+                                                  const float (&bt)[NT]) {
+  float m = 0.f;
+#pragma unroll
+  for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+    for (int t = 0; t < NT; ++t)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        e[mt][t][r] = fmaf(e[mt][t][r], is0[t], bt[t]);
+        o[mt][t][r] = fmaf(o[mt][t][r], is1[t], bt[t]);
+        m = fmaxf(m, fmaxf(fabsf(e[mt][t][r]), fabsf(o[mt][t][r])));
+      }
+  return wave_max(m);
 }
 
 // Cooperative weight staging of the half-sample stages (unet_kernel<2>): there every wave of the workgroup needs ALL B fragments of
@@ -930,6 +922,183 @@ __device__ __forceinline__ void stage_weights(const uint4* w, char* dst, int wav
 }
 __device__ __forceinline__ void staged_weights_landed() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 constexpr int WBUF_BYTES = 20 * 1024;                        // the largest staged conv: 32 -> 32, k = 5, two pieces
+// The half-sample stages (wave = (sample sp = wave >> 1, half hf = wave & 1)): the sample's maximum of a per-wave partial -- both waves
+// publish theirs in the sample's mx slots (4 hf .. 4 hf + 3), barrier
+__device__ __forceinline__ float half_sample_max(float* mx, int sp, int hf, int lane, float own) {
+  if (lane < 4) mx[sp * MX_SLOTS + 4 * hf + lane] = own;
+  __syncthreads();
+  return mx_read(mx, sp);
+}
+
+// downs.0 (4 -> 32 -> 32 channels at L = 64, Downsample1d): wave = sample.  The first conv's K is 5 taps x 4 channels = 20
+// of the 32 slots of ONE MFMA chunk (im2col: lane group j holds taps 2 j, 2 j + 1 -- two consecutive 8-byte rows of the
+// [row][4 channel] input slab), its 1x1 residual conv a second chunk with only the centre tap's slots non-zero.  The raw
+// network input has no bounded range: dynamic scale from the sample's own maximum.  The stride-2 tail reads its slab at stride 2
+// (Stride2: 3 taps on two M tiles, 36 MFMAs; the A reads are 2-way bank conflicted, half as many as at every position).
+// The stage's output goes straight into the next stage's input slab (RlGeo<32>) as f16 pieces under the sample's own dynamic
+// scale, behind a workgroup barrier (it aliases the waves' slabs); the sample's maximum goes to mx.
+//
+// Two schedules: chain_body_d0w (wave = sample: unet_kernel<4>) and chain_body_d0s (wave = half a sample: unet_kernel<2> / <1>).  What
+// defines values or layout is written once below, on MT M tiles from tile m0 of the sample on: a wave of d0w holds tiles 0 .. 3, a wave of
+// d0s tiles 2 hf, 2 hf + 1 -- the same arithmetic, the same bits.
+struct D0 {
+  using GW = RwGeo<32, 64>;
+  static constexpr int XIN = 72 * 8;                          // bytes per piece of the [row][4 channel] input slab (rows -2 .. 69)
+  static constexpr int W_BYTES = GW::BYTES + 2 * XIN + 128;   // a sample's conv slab + input slab
+  static_assert(4 * W_BYTES <= MX_OFF * 4, "four private slabs");
+  static_assert(2 * W_BYTES + 2 * WBUF_BYTES <= MX_OFF * 4, "two samples' slabs + two weight buffers below the maxima");
+  static_assert(GW::FRAGS5 * 2 * 1024 <= WBUF_BYTES, "a staged conv fits its buffer");
+};
+// Sample `smp` (`valid`: it exists, else zeros), lane = position: its dynamic scale from its own maximum, f16 pieces -> rows [2 +
+// position][4 channels] of the input slab's two pieces where `store` (d0s: the wave's half).  Returns the inverse scale.
+__device__ __forceinline__ float d0_stage_input(const float* in0, bool valid, size_t smp, int lane, char* xin, bool store) {
+  float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (valid) v = *reinterpret_cast<const float4*>(in0 + (smp * 64 + lane) * 4);
+  const DynScale ds = dyn_scale(wave_max(fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w)))));
+  const F16Pair p0 = f16_split2(v.x * ds.s, v.y * ds.s), p1 = f16_split2(v.z * ds.s, v.w * ds.s);
+  if (store) {
+    *reinterpret_cast<uint2*>(xin + (2 + lane) * 8) = make_uint2(p0.hi, p1.hi);
+    *reinterpret_cast<uint2*>(xin + D0::XIN + (2 + lane) * 8) = make_uint2(p0.lo, p1.lo);
+  }
+  return ds.inv;
+}
+__device__ __forceinline__ void d0_zero_xin_halo(char* xin, int lane, bool mine) {   // rows 0, 1, 66 .. 71 of both pieces
+  if (mine && lane < 16) {
+    const int row = (lane & 7) < 2 ? (lane & 7) : 64 + (lane & 7);
+    *reinterpret_cast<uint2*>(xin + (lane >> 3) * D0::XIN + row * 8) = make_uint2(0u, 0u);
+  }
+}
+// the B fragments of RTB 0's conv A (im2col chunk) and of the 1x1 residual conv: one chunk x two pieces per n-tile
+__device__ __forceinline__ void d0_load_wa(const ChainArgs& a, int lane, u32x4 (&b)[2][2], u32x4 (&br)[2][2]) {
+  const WTiles<2> wa = w_tiles<2>(a.r0.wa_bf, 2, 0, lane), wr = w_tiles<2>(a.wres_bf, 2, 0, lane);
+#pragma unroll
+  for (int t = 0; t < 2; ++t)
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      b[t][q] = wa.p[t][q * 64];
+      br[t][q] = wr.p[t][q * 64];
+    }
+}
+// RTB 0's conv A + the 1x1 residual conv on M tiles m0 .. m0 + MT - 1
+template <int MT>
+__device__ __forceinline__ void d0_conv_a(f32x4 (&acc)[MT][2], f32x4 (&res)[MT][2], const char* xin, int m0, int n, int g,
+                                          const u32x4 (&b)[2][2], const u32x4 (&br)[2][2]) {
+#pragma unroll
+  for (int mt = 0; mt < MT; ++mt) {
+    u32x4 af[2];
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      const uint2* p = reinterpret_cast<const uint2*>(xin + q * D0::XIN + ((m0 + mt) * 16 + n + 2 * g) * 8);
+      const uint2 lo = p[0], hi = p[1];
+      af[q] = u32x4{lo.x, lo.y, hi.x, hi.y};
+    }
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      vb_three<true>(acc[mt][t], af, b[t]);
+      vb_three<true>(res[mt][t], af, br[t]);
+    }
+  }
+}
+// The tail's output tiles m0 .. m0 + MT - 1 of sample `smp` (outputs q = 16 (m0 + mt) + 4 g + r) -> the next stage's input slab
+// (RlGeo<32>: rows 36 sample + 2 + q), channels 2 n, 2 n + 1 = block n >> 2, dword n & 3, as f16 pieces under the sample's own
+// dynamic scale `so` (the next stage reads it from mx)
+template <int MT>
+__device__ __forceinline__ void d0_tail_store(char* lb, int smp, int m0, int n, int g, const f32x4 (&y)[MT][2], float so) {
+  using GN = RlGeo<32>;
+  char* xb = lb + (n >> 2) * GN::G + (smp * GN::RPS + 2 + 16 * m0 + 4 * g) * 16 + (n & 3) * 4;
+#pragma unroll
+  for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const F16Pair f = f16_split2(y[mt][0][r] * so, y[mt][1][r] * so);
+      *reinterpret_cast<unsigned*>(xb + (16 * mt + r) * 16) = f.hi;
+      *reinterpret_cast<unsigned*>(xb + GN::PS + (16 * mt + r) * 16) = f.lo;
+    }
+}
+
+template <int NS>     // NS: the workgroup's samples (a wave >= NS runs on zeros and stores nothing)
+__device__ __forceinline__ void chain_body_d0w(const ChainArgs& a, float* lds, int n0, int lane, int wave, int trb, int tb_off = 0) {
+  using GW = D0::GW;
+  char* const slab = reinterpret_cast<char*>(lds) + wave * D0::W_BYTES;
+  char* const xin = slab + GW::BYTES;
+  const int n = lane & 15, g = lane >> 4, c0 = 2 * n;
+  const char* const va = slab + g * GW::G + n * 16;          // A fragment: row lane & 15, lane group lane >> 4 (KC = 1: block j)
+  char* const vs = slab + (n >> 2) * GW::G + (2 + 4 * g) * 16 + (n & 3) * 4;
+  TR(trb + 0);
+  // ---- stage the sample, zero rows around it and the halo rows of the conv slab
+  const float inv_in = d0_stage_input(a.in0, wave < NS && n0 + wave < a.n, n0 + wave, lane, xin, true);
+  d0_zero_xin_halo(xin, lane, true);
+  rw_zero_halo<GW>(slab, 64, lane, true);
+  wave_lds_fence();
+  f32x4 acc[4][2], res[4][2];
+  const Epi<2> e0a = epi_a<2>(a.r0, tb_off, c0);
+  const float br0[2] = {a.br[c0], a.br[c0 + 1]}, isr0[2] = {a.isr[c0], a.isr[c0 + 1]};
+  // ---- RTB 0 conv A (im2col chunk) + the 1x1 residual conv
+  {
+    u32x4 b[2][2], br[2][2];
+    d0_load_wa(a, lane, b, br);
+    d0_conv_a<4>(acc, res, xin, 0, n, g, b, br);
+  }
+  // The whole weight set of a conv (5 taps x 2 n-tiles x 2 pieces = 20 KB per wave) is requested BEFORE the epilogue that
+  // produces the conv's input (preload), so the L2 latency hides behind GroupNorm + Mish instead of in front of the MFMAs.
+  u32x4 ring[5][2][2];
+  auto preload = [&](const uint4* w) { rd_ring_load<GW, 2, 5>(ring, w_tiles<2>(w, GW::FRAGS5, 0, lane).p); };
+  auto conv = [&](const uint4* w) {                          // one 32 -> 32 conv over the tile in acc (already scaled)
+    const WTiles<2> wp = w_tiles<2>(w, GW::FRAGS5, 0, lane);
+    rw_store2<GW, 4>(vs, acc);
+    wave_lds_fence();
+    rd_taps<GW, 2, 0, 5, true, false, 4, 5>(acc, res, va, wp.p, wp.p, ring);
+    wave_lds_fence();                                        // (the next store must not overtake these reads)
+  };
+  tile_finish_res(res, isr0, inv_in, br0);
+  preload(a.r0.wb_bf);
+  rw_gn<2, 256>(acc, e0a, inv_in, a.r0.act_a);
+  TR(trb + 1);
+  {
+    const Epi<2> e = epi_b<2>(a.r0, c0);
+    conv(a.r0.wb_bf);
+    preload(a.ri[0].wa_bf);
+    rw_gn<2, 256>(acc, e, 1.f, res);
+  }
+  TR(trb + 2);
+  // ---- identity RTB
+  {
+    const RtbPtrs& R = a.ri[0];
+    tile_copy(res, acc);
+    const DynScale ds = dyn_scale(rw_absmax(acc));
+    tile_scale(acc, ds.s);
+    const Epi<2> ea = epi_a<2>(R, tb_off, c0);
+    conv(R.wa_bf);
+    preload(R.wb_bf);
+    rw_gn<2, 256>(acc, ea, ds.inv, R.act_a);
+    TR(trb + 3);
+    const Epi<2> eb = epi_b<2>(R, c0);
+    conv(R.wb_bf);
+    rw_gn<2, 256>(acc, eb, 1.f, res);
+    TR(trb + 4);
+  }
+  // ---- tail: Downsample1d = Conv1d(k3, s2, p1): y[p] = sum_t x[p + t - 1] W_t at the even p
+  {
+    const DynScale ds = dyn_scale(rw_absmax(acc));
+    tile_scale(acc, ds.s);
+    const WTiles<2> wt = w_tiles<2>(a.wt_bf0, GW::FRAGS3, 0, lane);
+    u32x4 ring3[3][2][2];
+    const float bt[2] = {a.bt[c0], a.bt[c0 + 1]}, ist[2] = {a.ist0[c0] * ds.inv, a.ist0[c0 + 1] * ds.inv};
+    rd_ring_load<GW, 2, 3>(ring3, wt.p);
+    rw_store2<GW, 4>(vs, acc);
+    wave_lds_fence();
+    // (outputs q = 16 mt + 4 g + r = the even positions 2 q: two M tiles read at stride 2)
+    f32x4 y[2][2];
+    rd_taps<Stride2<GW, 0, 2>, 2, 1, 3, true, false, 2, 3>(y, y, va + n * 16, wt.p, wt.p, ring3);
+    const float mo = tail_epilogue(y, ist, bt);
+    __syncthreads();                                         // every wave is done with its slab: the next stage's slab aliases them
+    if (lane < MX_SLOTS) (lds + MX_OFF)[wave * MX_SLOTS + lane] = mo;
+    char* const lb = reinterpret_cast<char*>(lds);
+    d0_tail_store<2>(lb, wave, 0, n, g, y, dyn_scale(mo).s);
+    rw_zero_halo<RlGeo<32>>(lb + wave * RlGeo<32>::RPS * 16, 32, lane, true);   // (the sample's rows 0, 1, 34, 35)
+  }
+  TR(trb + 5);
+}
 
 // downs.0 for unet_kernel<2> (two trajectories per workgroup): a sample is split between two waves by POSITION -- wave = (sample sp =
 // wave >> 1, half hf = wave & 1: positions 32 hf .. 32 hf + 31 = M tiles 2 hf, 2 hf + 1 of the sample's four), so all four waves
@@ -937,106 +1106,40 @@ constexpr int WBUF_BYTES = 20 * 1024;                        // the largest stag
 // two waves share the sample's slab (a conv's taps reach two rows into the other half: one workgroup barrier between the slab
 // store and the taps), GroupNorm statistics are the two-half combination of rw_half_stat (one exchange through LDS per conv,
 // whose barrier also orders the next slab store behind the partner's taps), dynamic scales take the sample's maximum from the
-// two waves' partials in mx.  Per-sample arithmetic is that of chain_body_d0w: bitwise equal results.
-template <class CF, int NV = 2>     // NV: the workgroup's REAL samples (unet_kernel<1>: sample 1 is fed zeros and never stored)
+// two waves' partials in mx.  Weights come through LDS (stage_weights), one conv ahead, into two buffers behind the two samples' slabs.
+template <int NV>     // NV: the workgroup's REAL samples (unet_kernel<1>: sample 1 is fed zeros and never stored)
 __device__ __forceinline__ void chain_body_d0s(const ChainArgs& a, float* lds, int n0, int lane, int wave, int trb, int tb_off = 0) {
-  static_assert(CF::L == 64 && CF::CM == 32 && CF::C0 == 4 && CF::C1 == 0 && CF::RES0 == RES_CONV && CF::N_IDENT == 1 &&
-                    CF::TAIL == TAIL_DOWN, "downs.0");
-  using GW = RwGeo<32, 64>;
-  constexpr int XIN = 72 * 8;
-  constexpr int W_BYTES = GW::BYTES + 2 * XIN + 128;          // (per SAMPLE here)
+  using GW = D0::GW;
   const int sp = wave >> 1, hf = wave & 1;
-  char* const slab = reinterpret_cast<char*>(lds) + sp * W_BYTES;
+  char* const slab = reinterpret_cast<char*>(lds) + sp * D0::W_BYTES;
   char* const xin = slab + GW::BYTES;
   float* const mx = lds + MX_OFF;
-  HalfStat* const xch = reinterpret_cast<HalfStat*>(lds + PARK2_OFF) + sp * 128;   // (downs.2's parking area is idle in this stage)
+  const RwHalf half{reinterpret_cast<HalfStat*>(lds + PARK2_OFF) + sp * 128, hf, lane};   // (downs.2's parking area is idle in this stage)
   static_assert(2 * 128 * sizeof(HalfStat) <= 3 * 256 * 16, "exchange area inside the parking area");
-  char* const wb0 = reinterpret_cast<char*>(lds) + 2 * W_BYTES;   // two weight buffers behind the two samples' slabs
+  char* const wb0 = reinterpret_cast<char*>(lds) + 2 * D0::W_BYTES;
   char* const wb1 = wb0 + WBUF_BYTES;
-  static_assert(2 * W_BYTES + 2 * WBUF_BYTES <= MX_OFF * 4, "slabs + weight buffers below the maxima");
-  static_assert(GW::FRAGS5 * 2 * 1024 <= WBUF_BYTES, "a staged conv fits its buffer");
   stage_weights<2 * GW::FRAGS5>(a.r0.wb_bf, wb0, wave, lane);     // RTB 0's conv B: lands while the sample is staged and conv A runs
   const int n = lane & 15, g = lane >> 4, c0 = 2 * n;
   const char* const va = slab + g * GW::G + (n + 32 * hf) * 16;
   char* const vs = slab + (n >> 2) * GW::G + (2 + 4 * g + 32 * hf) * 16 + (n & 3) * 4;
-  auto wptr = [&](const uint4* w, int frags, int t) { return reinterpret_cast<const u32x4*>(w) + (size_t)t * frags * 64 + lane; };
-  // the sample's maximum of a per-wave partial: both waves publish theirs in the sample's mx slots (4 hf .. 4 hf + 3), barrier
-  auto sample_max = [&](float own) {
-    if (lane < 4) mx[sp * MX_SLOTS + 4 * hf + lane] = own;
-    __syncthreads();
-    return mx_read(mx, sp);
-  };
   TR(trb + 0);
   // ---- stage the sample: every wave loads all of it (lane = position: the exact maximum without an exchange) and writes its half
-  float inv_in;
-  {
-    const bool valid = sp < NV && n0 + sp < a.n;
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (valid) v = *reinterpret_cast<const float4*>(a.in0 + ((size_t)(n0 + sp) * 64 + lane) * 4);
-    float m = fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w)));
-    m = row_max16(m);
-    m = max_xor16(m);
-    m = max_xor32(m);
-    const DynScale ds = dyn_scale(m);
-    inv_in = ds.inv;
-    const F16Pair p0 = f16_split2(v.x * ds.s, v.y * ds.s), p1 = f16_split2(v.z * ds.s, v.w * ds.s);
-    if ((lane >> 5) == hf) {
-      *reinterpret_cast<uint2*>(xin + (2 + lane) * 8) = make_uint2(p0.hi, p1.hi);
-      *reinterpret_cast<uint2*>(xin + XIN + (2 + lane) * 8) = make_uint2(p0.lo, p1.lo);
-    }
-    if (hf == 0) {
-      if (lane < 16) {                                         // rows 0, 1, 66 .. 71 of both pieces
-        const int row = (lane & 7) < 2 ? (lane & 7) : 64 + (lane & 7);
-        *reinterpret_cast<uint2*>(xin + (lane >> 3) * XIN + row * 8) = make_uint2(0u, 0u);
-      }
-      if (lane < 32) *reinterpret_cast<uint4*>(slab + (lane >> 4) * GW::PS + ((lane >> 2) & 3) * GW::G + ((lane & 3) < 2 ? (lane & 3) : 64 + (lane & 3)) * 16) = make_uint4(0u, 0u, 0u, 0u);
-    }
-  }
+  const float inv_in = d0_stage_input(a.in0, sp < NV && n0 + sp < a.n, n0 + sp, lane, xin, (lane >> 5) == hf);
+  d0_zero_xin_halo(xin, lane, hf == 0);
+  rw_zero_halo<GW>(slab, 64, lane, hf == 0);
   f32x4 acc[2][2], res[2][2];
-  const Epi<2> e0a = epi_load<2>(a.r0.ba, a.r0.ga, a.r0.bea, a.r0.tb + tb_off, a.r0.isa, c0);
+  const Epi<2> e0a = epi_a<2>(a.r0, tb_off, c0);
   const float br0[2] = {a.br[c0], a.br[c0 + 1]}, isr0[2] = {a.isr[c0], a.isr[c0 + 1]};
   u32x4 b0[2][2], br[2][2];
-#pragma unroll
-  for (int t = 0; t < 2; ++t)
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-      b0[t][q] = wptr(a.r0.wa_bf, 2, t)[q * 64];
-      br[t][q] = wptr(a.wres_bf, 2, t)[q * 64];
-    }
+  d0_load_wa(a, lane, b0, br);
   __syncthreads();
   // ---- RTB 0 conv A (im2col chunk) + the 1x1 residual conv on the half's two M tiles
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    u32x4 af[2];
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-      const uint2* p = reinterpret_cast<const uint2*>(xin + q * XIN + ((2 * hf + i) * 16 + n + 2 * g) * 8);
-      const uint2 lo = p[0], hi = p[1];
-      af[q] = u32x4{lo.x, lo.y, hi.x, hi.y};
-    }
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      vb_three<true>(acc[i][t], af, b0[t]);
-      vb_three<true>(res[i][t], af, br[t]);
-    }
-  }
-  const float one = 1.f;
-  auto epi = [&](const float* bs, const float* gm, const float* be, const float* tb, const float* isc) {
-    return epi_load<2>(bs, gm, be, tb, isc, c0);
-  };
-  auto gn = [&](auto conv_a, const Epi<2>& e, float inv, float act_s) {
-    if constexpr (decltype(conv_a)::value) {
-      const float t0 = e.tb[0] * act_s, t1 = e.tb[1] * act_s;
-      rw_gn_mish_half<2, 2, 2, 256, true>(acc, e.b, e.g, e.be, e.is, inv, act_scale(act_s), [&](int, int t, int) { return t ? t1 : t0; }, xch, hf, lane);
-    } else {
-      rw_gn_mish_half<2, 2, 2, 256, false>(acc, e.b, e.g, e.be, e.is, inv, ActScale{}, [&](int mt, int t, int r) { return res[mt][t][r]; }, xch, hf, lane);
-    }
-  };
+  d0_conv_a<2>(acc, res, xin, 2 * hf, n, g, b0, br);
   u32x4 ring[2][2][2];
   // one 32 -> 32 conv over the half tile in acc (already scaled), its weights staged in wb; behind the barrier the NEXT conv's
   // NEXT_FRAGS fragments start on their way into the other buffer (every wave is past the conv that read it)
   auto conv = [&](char* wb, auto next_frags, const uint4* w_next, char* wb_next, int tr = -1) {
-    const u32x4* wp[2] = {reinterpret_cast<const u32x4*>(wb) + lane, reinterpret_cast<const u32x4*>(wb) + GW::FRAGS5 * 64 + lane};
+    const WTiles<2> wp = w_tiles<2>(wb, GW::FRAGS5, 0, lane);
     if (tr >= 0) TR(tr);
     rw_store2<GW, 2>(vs, acc);
     if (tr >= 0) TR(tr + 1);
@@ -1044,87 +1147,56 @@ __device__ __forceinline__ void chain_body_d0s(const ChainArgs& a, float* lds, i
     __syncthreads();                                         // both halves of the sample and the conv's weights are in LDS
     if (tr >= 0) TR(tr + 2);
     if constexpr (decltype(next_frags)::value > 0) stage_weights<decltype(next_frags)::value>(w_next, wb_next, wave, lane);
-    rd_ring_load<GW, 2, 2>(ring, wp);
-    rd_taps<GW, 2, 0, 5, true, false, 2, 2>(acc, res, va, wp, wp, ring);
+    rd_ring_load<GW, 2, 2>(ring, wp.p);
+    rd_taps<GW, 2, 0, 5, true, false, 2, 2>(acc, res, va, wp.p, wp.p, ring);
     if (tr >= 0) TR(tr + 3);
   };
   using F5 = std::integral_constant<int, 2 * GW::FRAGS5>;
   using F3 = std::integral_constant<int, 2 * GW::FRAGS3>;
-#pragma unroll
-  for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-    for (int t = 0; t < 2; ++t) res[mt][t] = res[mt][t] * (isr0[t] * inv_in) + br0[t];
-  gn(std::true_type{}, e0a, inv_in, a.r0.act_a);
+  tile_finish_res(res, isr0, inv_in, br0);
+  rw_gn<2, 256>(acc, e0a, inv_in, a.r0.act_a, half);
   TR(trb + 1);
   {
-    const Epi<2> e = epi(a.r0.bb, a.r0.gb, a.r0.beb, nullptr, a.r0.isb);
+    const Epi<2> e = epi_b<2>(a.r0, c0);
     conv(wb0, F5{}, a.ri[0].wa_bf, wb1);
-    gn(std::false_type{}, e, one, 1.f);
+    rw_gn<2, 256>(acc, e, 1.f, res, half);
   }
   TR(trb + 2);
   // ---- identity RTB
   {
     const RtbPtrs& R = a.ri[0];
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-      for (int t = 0; t < 2; ++t) res[mt][t] = acc[mt][t];
-    const DynScale ds = dyn_scale(sample_max(rw_absmax<2, 2>(acc)));
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-      for (int t = 0; t < 2; ++t) acc[mt][t] *= ds.s;
-    const Epi<2> ea = epi(R.ba, R.ga, R.bea, R.tb + tb_off, R.isa);
+    tile_copy(res, acc);
+    const DynScale ds = dyn_scale(half_sample_max(mx, sp, hf, lane, rw_absmax(acc)));
+    tile_scale(acc, ds.s);
+    const Epi<2> ea = epi_a<2>(R, tb_off, c0);
     conv(wb1, F5{}, R.wb_bf, wb0, trb + 6);
     TR(trb + 10);
-    gn(std::true_type{}, ea, ds.inv, R.act_a);
+    rw_gn<2, 256>(acc, ea, ds.inv, R.act_a, half);
     TR(trb + 3);
-    const Epi<2> eb = epi(R.bb, R.gb, R.beb, nullptr, R.isb);
+    const Epi<2> eb = epi_b<2>(R, c0);
     conv(wb0, F3{}, a.wt_bf0, wb1);
-    gn(std::false_type{}, eb, one, 1.f);
+    rw_gn<2, 256>(acc, eb, 1.f, res, half);
     TR(trb + 4);
   }
   // ---- tail: Downsample1d = Conv1d(k3, s2, p1) at the even positions: the half's 16 outputs = ONE M tile read at stride 2
   {
-    const DynScale ds = dyn_scale(sample_max(rw_absmax<2, 2>(acc)));
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-      for (int t = 0; t < 2; ++t) acc[mt][t] *= ds.s;
-    const u32x4* wt[2] = {reinterpret_cast<const u32x4*>(wb1) + lane, reinterpret_cast<const u32x4*>(wb1) + GW::FRAGS3 * 64 + lane};
+    const DynScale ds = dyn_scale(half_sample_max(mx, sp, hf, lane, rw_absmax(acc)));
+    tile_scale(acc, ds.s);
+    const WTiles<2> wt = w_tiles<2>(wb1, GW::FRAGS3, 0, lane);
     const float bt[2] = {a.bt[c0], a.bt[c0 + 1]}, ist[2] = {a.ist0[c0] * ds.inv, a.ist0[c0 + 1] * ds.inv};
     rw_store2<GW, 2>(vs, acc);
     staged_weights_landed();
     __syncthreads();
     f32x4 y[1][2];
-    rd_ring_load<GW, 2, 2>(ring, wt);
-    rd_taps<Stride2<GW, 0, 2>, 2, 1, 3, true, false, 1, 2>(y, y, va + n * 16, wt, wt, ring);
-    float mo = 0.f;
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        y[0][t][r] = fmaf(y[0][t][r], ist[t], bt[t]);
-        mo = fmaxf(mo, fabsf(y[0][t][r]));
-      }
-    mo = row_max16(mo);
-    mo = max_xor16(mo);
-    mo = max_xor32(mo);
+    rd_ring_load<GW, 2, 2>(ring, wt.p);
+    rd_taps<Stride2<GW, 0, 2>, 2, 1, 3, true, false, 1, 2>(y, y, va + n * 16, wt.p, wt.p, ring);
+    const float mo = tail_epilogue(y, ist, bt);
     // (the barrier inside: every wave is done with its slab -- the next stage's slab aliases them -- and the sample's maxima
     // are published for the next stage's dynamic scale)
-    const float so = dyn_scale(sample_max(mo)).s;
-    using GN = RlGeo<32>;
+    const float so = dyn_scale(half_sample_max(mx, sp, hf, lane, mo)).s;
     char* const lb = reinterpret_cast<char*>(lds);
-    char* xb = lb + (n >> 2) * GN::G + (sp * GN::RPS + 2 + 16 * hf + 4 * g) * 16 + (n & 3) * 4;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const F16Pair f = f16_split2(y[0][0][r] * so, y[0][1][r] * so);
-      *reinterpret_cast<unsigned*>(xb + r * 16) = f.hi;
-      *reinterpret_cast<unsigned*>(xb + GN::PS + r * 16) = f.lo;
-    }
-    if (hf == 0 && lane < 32)                                // halo rows 0, 1, 34, 35 of the sample's 4 blocks x 2 pieces
-      *reinterpret_cast<uint4*>(lb + (lane >> 4) * GN::PS + ((lane >> 2) & 3) * GN::G +
-                                (sp * GN::RPS + ((lane & 3) < 2 ? (lane & 3) : 32 + (lane & 3))) * 16) = make_uint4(0u, 0u, 0u, 0u);
+    d0_tail_store<1>(lb, sp, hf, n, g, y, so);
+    rw_zero_halo<RlGeo<32>>(lb + sp * RlGeo<32>::RPS * 16, 32, lane, hf == 0);   // (the sample's rows 0, 1, 34, 35)
   }
   TR(trb + 5);
 }
@@ -1134,12 +1206,10 @@ __device__ __forceinline__ void chain_body_d0s(const ChainArgs& a, float* lds, i
 // used on four M tiles and fetched by two waves; acc[m][t]: M tile m = sample 2 sp + (m >> 1), positions 16 (m & 1) + 4 g + r.
 // A GroupNorm group (8 channels x 32 positions of a sample) is 4 lanes x 2 tiles x the sample's 2 M tiles: wave-internal.
 // The input slab arrives from downs.0's tail (f16 pieces, per-sample scales in mx); the strided tail reads its slab at stride 2
-// (Stride2) and writes downs.2's row-form fp32 x slab (CFN geometry) + the per-sample maxima to mx.
+// (Stride2) and writes downs.2's row-form fp32 x slab (D2 geometry) + the per-sample maxima to mx.
 // skip: the stage's skip tensor (output of its second RTB) in the acc layout.
-template <class CF, class CFN, int NS>
+template <int NS>
 __device__ __forceinline__ void chain_body_d1d(const ChainArgs& a, float* lds, int lane, int wave, f32x4 (&skip)[NS][2], int trb, int tb_off = 0) {
-  static_assert(CF::L == 32 && CF::CM == 64 && CF::C0 == 32 && CF::C1 == 0 && CF::RES0 == RES_CONV && CF::N_IDENT == 1 &&
-                    CF::MID_AFTER == 1 && CF::TAIL == TAIL_DOWN, "downs.1");
   using GI = RlGeo<32>;
   using GH = RlGeo<64>;
   constexpr int H_OFF = GI::BYTES;                           // the 64-channel slab lies behind the input slab
@@ -1156,10 +1226,7 @@ __device__ __forceinline__ void chain_body_d1d(const ChainArgs& a, float* lds, i
   const char* const vaH = slabH + g * GH::G + (s0 * GH::RPS + n) * 16;
   // the lane's channel pair (c0, c0 + 1) = block 4 np + (n >> 2) = (chunk (n >> 2) & 1, lane group 2 np + (n >> 3)), dword n & 3
   char* const vsH = slabH + (2 * np + (n >> 3)) * GH::G + ((n >> 2) & 1) * GH::BX + (s0 * GH::RPS + 2 + 4 * g) * 16 + (n & 3) * 4;
-  auto wptr = [&](const uint4* w, int frags, int h) { return reinterpret_cast<const u32x4*>(w) + (size_t)(2 * np + h) * frags * 64 + lane; };
-  auto epi = [&](const float* b, const float* gm, const float* be, const float* tb, const float* isc) {
-    return epi_load<2>(b, gm, be, tb, isc, c0);
-  };
+  auto wt2 = [&](const uint4* w, int frags) { return w_tiles<2>(w, frags, 2 * np, lane); };
   f32x4 acc[NS][2], res[NS][2];
   constexpr int RD1 = MMD_D1_RD;                               // weight ring depth of the 64 -> 64 convs
   u32x4 ring[RD1][2][2];
@@ -1173,69 +1240,19 @@ __device__ __forceinline__ void chain_body_d1d(const ChainArgs& a, float* lds, i
         *reinterpret_cast<unsigned*>(vsH + GH::PS + (GH::tile_row(m) + r) * 16) = f.lo;
       }
   };
-  // GroupNorm + Mish of acc, sample by sample (M tiles 2 s, 2 s + 1)
-  auto gn = [&](auto conv_a, const Epi<2>& e, const float (&inv)[SW], float act_s) {
-#pragma unroll
-    for (int sl = 0; sl < SW; ++sl) {
-      f32x4(&t)[2][2] = reinterpret_cast<f32x4(&)[2][2]>(acc[2 * sl]);
-      if constexpr (decltype(conv_a)::value) {
-        const float t0 = e.tb[0] * act_s, t1 = e.tb[1] * act_s;
-        rw_gn_mish<2, 2, 4, 256, true>(t, e.b, e.g, e.be, e.is, inv[sl], act_scale(act_s), [&](int, int tt, int) { return tt ? t1 : t0; });
-      } else {
-        rw_gn_mish<2, 2, 4, 256, false>(t, e.b, e.g, e.be, e.is, inv[sl], ActScale{}, [&](int mt, int tt, int r) { return res[2 * sl + mt][tt][r]; });
-      }
-    }
-  };
-  // per-sample |x| maxima of the tile in v -> all eight slots of the two samples (the two waves of a sample pair fill them)
-  auto maxima_out = [&](const f32x4 (&v)[NS][2]) {
-    float m2[2] = {0.f, 0.f};
-#pragma unroll
-    for (int sl = 0; sl < SW; ++sl) {
-      float m = 0.f;
-#pragma unroll
-      for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) m = fmaxf(m, fabsf(v[2 * sl + mt][t][r]));
-      m = row_max16(m);
-      m = max_xor16(m);
-      m2[sl] = max_xor32(m);
-    }
-    if (lane < 4 * SW) mx[(s0 + (lane >> 2)) * MX_SLOTS + np + 2 * (lane & 3)] = (lane >> 2) ? m2[1] : m2[0];
-  };
-  // dynamic input scale of the tile in acc from the maxima in mx: scale in place, the inverse scales per sample of the pair
-  auto scale_in = [&](float (&inv)[SW]) {
-#pragma unroll
-    for (int sl = 0; sl < SW; ++sl) {
-      const DynScale ds = dyn_scale(mx_read(mx, s0 + sl));
-      inv[sl] = ds.inv;
-#pragma unroll
-      for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-        for (int t = 0; t < 2; ++t) acc[2 * sl + mt][t] *= ds.s;
-    }
-  };
-  // one 64 -> 64 conv over the tile in acc (already scaled); on entry every wave is past its reads of the slab.  PF (one sample per
-  // wave = unet_kernel<2>, the latency-bound launches): the NEXT conv's first ring steps are requested right behind this conv's taps
-  // and travel during the epilogue (chain_body_d2d has the measurement); `frags_next`: the next pack's fragments per n-tile.
-#ifdef MMD_NO_PF
-  constexpr bool PF = false;
-#else
-  constexpr bool PF = SW == 1;
-#endif
+  // one 64 -> 64 conv over the tile in acc (already scaled); on entry every wave is past its reads of the slab.  PF (ring_prefetch: one
+  // sample per wave = unet_kernel<2>): the NEXT conv's first ring steps are requested right behind this conv's taps and travel during
+  // the epilogue; `frags_next`: the next pack's fragments per n-tile.
+  constexpr bool PF = ring_prefetch(NS);
   auto prefetch = [&](const uint4* w, int frags) {
-    if constexpr (PF) {
-      const u32x4* wp[2] = {wptr(w, frags, 0), wptr(w, frags, 1)};
-      rd_ring_load<GH, 2, RD1>(ring, wp);
-    }
+    if constexpr (PF) rd_ring_load<GH, 2, RD1>(ring, wt2(w, frags).p);
   };
   auto conv = [&](const uint4* w, const uint4* w_next, int frags_next) {
-    const u32x4* wp[2] = {wptr(w, GH::FRAGS5, 0), wptr(w, GH::FRAGS5, 1)};
-    if constexpr (!PF) rd_ring_load<GH, 2, RD1>(ring, wp);
+    const WTiles<2> wp = wt2(w, GH::FRAGS5);
+    if constexpr (!PF) rd_ring_load<GH, 2, RD1>(ring, wp.p);
     store_tile();
     __syncthreads();
-    rd_taps<GH, 2, 0, 5, true, false, NS, RD1>(acc, acc, vaH, wp, wp, ring);
+    rd_taps<GH, 2, 0, 5, true, false, NS, RD1>(acc, acc, vaH, wp.p, wp.p, ring);
     prefetch(w_next, frags_next);
   };
   float one2[SW];
@@ -1245,10 +1262,9 @@ __device__ __forceinline__ void chain_body_d1d(const ChainArgs& a, float* lds, i
   // =================== RTB 0 (32 -> 64): conv A + the 1x1 residual conv on the centre tap ===================
   {
     u32x4 ring5[5][2][2];
-    const u32x4* wpa[2] = {wptr(a.r0.wa_bf, GI::FRAGS5, 0), wptr(a.r0.wa_bf, GI::FRAGS5, 1)};
-    const u32x4* wpr[2] = {wptr(a.wres_bf, 2 * GI::KC, 0), wptr(a.wres_bf, 2 * GI::KC, 1)};
-    rd_ring_load<GI, 2, 5>(ring5, wpa);
-    const Epi<2> e0a = epi(a.r0.ba, a.r0.ga, a.r0.bea, a.r0.tb + tb_off, a.r0.isa);
+    const WTiles<2> wpa = wt2(a.r0.wa_bf, GI::FRAGS5), wpr = wt2(a.wres_bf, 2 * GI::KC);
+    rd_ring_load<GI, 2, 5>(ring5, wpa.p);
+    const Epi<2> e0a = epi_a<2>(a.r0, tb_off, c0);
     const float br[2] = {a.br[c0], a.br[c0 + 1]}, isr[2] = {a.isr[c0], a.isr[c0 + 1]};
     __syncthreads();                                         // downs.0's tail has written the input slab and its maxima
     TR(trb + 0);
@@ -1256,92 +1272,74 @@ __device__ __forceinline__ void chain_body_d1d(const ChainArgs& a, float* lds, i
 #pragma unroll
     for (int sl = 0; sl < SW; ++sl) inv_in[sl] = dyn_scale(mx_read(mx, s0 + sl)).inv;
     rd_zero_halo<GH>(slabH);
-    rd_taps<GI, 2, 0, 5, true, true, NS, 5>(acc, res, vaI, wpa, wpr, ring5);
-#pragma unroll
-    for (int m = 0; m < NS; ++m)
-#pragma unroll
-      for (int t = 0; t < 2; ++t) res[m][t] = res[m][t] * (isr[t] * inv_in[m >> 1]) + br[t];
+    rd_taps<GI, 2, 0, 5, true, true, NS, 5>(acc, res, vaI, wpa.p, wpr.p, ring5);
+    tile_finish_res(res, isr, inv_in, br);
     prefetch(a.r0.wb_bf, GH::FRAGS5);
-    gn(std::true_type{}, e0a, inv_in, a.r0.act_a);
+    rw_gn_samples<4, 256>(acc, e0a, inv_in, a.r0.act_a);
   }
   TR(trb + 1);
   {
-    const Epi<2> e = epi(a.r0.bb, a.r0.gb, a.r0.beb, nullptr, a.r0.isb);
+    const Epi<2> e = epi_b<2>(a.r0, c0);
     conv(a.r0.wb_bf, a.ri[0].wa_bf, GH::FRAGS5);             // (its slab is not the one conv A reads: no barrier before the store)
-    gn(std::false_type{}, e, one2, 1.f);
+    rw_gn_samples<4, 256>(acc, e, one2, res);
   }
   TR(trb + 2);
   // =================== identity RTB ===================
   {
     const RtbPtrs& R = a.ri[0];
-#pragma unroll
-    for (int m = 0; m < NS; ++m)
-#pragma unroll
-      for (int t = 0; t < 2; ++t) res[m][t] = acc[m][t];
-    maxima_out(acc);
+    tile_copy(res, acc);
+    pair_maxima_out<4, 0>(acc, mx, wave, lane);              // (all eight slots of the wave's samples)
     __syncthreads();                                         // the previous conv is done reading the slab
     float inv[SW];
-    scale_in(inv);
-    const Epi<2> ea = epi(R.ba, R.ga, R.bea, R.tb + tb_off, R.isa);
+    mx_scale_tile(mx, s0, acc, inv);
+    const Epi<2> ea = epi_a<2>(R, tb_off, c0);
     conv(R.wa_bf, R.wb_bf, GH::FRAGS5);
-    gn(std::true_type{}, ea, inv, R.act_a);
+    rw_gn_samples<4, 256>(acc, ea, inv, R.act_a);
     TR(trb + 3);
     __syncthreads();
-    const Epi<2> eb = epi(R.bb, R.gb, R.beb, nullptr, R.isb);
+    const Epi<2> eb = epi_b<2>(R, c0);
     conv(R.wb_bf, a.wt_bf0, GH::FRAGS3);                     // (next: the strided tail's 3-tap pack)
-    gn(std::false_type{}, eb, one2, 1.f);
+    rw_gn_samples<4, 256>(acc, eb, one2, res);
     TR(trb + 4);
-#pragma unroll
-    for (int m = 0; m < NS; ++m)
-#pragma unroll
-      for (int t = 0; t < 2; ++t) skip[m][t] = acc[m][t];
+    tile_copy(skip, acc);
   }
   // =================== tail: Downsample1d = Conv1d(k3, s2, p1): y[p] = sum_t x[p + t - 1] W_t at the even p ===================
   {
-    maxima_out(acc);
+    pair_maxima_out<4, 0>(acc, mx, wave, lane);
     __syncthreads();
     float inv[SW];
-    scale_in(inv);
-    const u32x4* wt[2] = {wptr(a.wt_bf0, GH::FRAGS3, 0), wptr(a.wt_bf0, GH::FRAGS3, 1)};
+    mx_scale_tile(mx, s0, acc, inv);
+    const WTiles<2> wt = wt2(a.wt_bf0, GH::FRAGS3);
     const float bt[2] = {a.bt[c0], a.bt[c0 + 1]}, ist[2] = {a.ist0[c0], a.ist0[c0 + 1]};
-    if constexpr (!PF) rd_ring_load<GH, 2, RD1>(ring, wt);
+    if constexpr (!PF) rd_ring_load<GH, 2, RD1>(ring, wt.p);
     store_tile();
     __syncthreads();
     // (outputs q = 4 g + r = the even positions 2 q of the wave's samples: one M tile each, read at stride 2; the GEMM loop takes
     // M tiles in pairs: a one-sample wave computes its tile twice)
     f32x4 y[2][2];
-    rd_taps<Stride2<GH, SW == 2 ? GH::RPS : 0, 1>, 2, 1, 3, true, false, 2, RD1>(y, y, vaH + n * 16, wt, wt, ring);
+    rd_taps<Stride2<GH, SW == 2 ? GH::RPS : 0, 1>, 2, 1, 3, true, false, 2, RD1>(y, y, vaH + n * 16, wt.p, wt.p, ring);
     float m2[2] = {0.f, 0.f};
 #pragma unroll
     for (int sl = 0; sl < SW; ++sl) {
-      float m = 0.f;
-#pragma unroll
-      for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          y[sl][t][r] = fmaf(y[sl][t][r], ist[t] * inv[sl], bt[t]);
-          m = fmaxf(m, fabsf(y[sl][t][r]));
-        }
-      m = row_max16(m);
-      m = max_xor16(m);
-      m2[sl] = max_xor32(m);
+      const float is[2] = {ist[0] * inv[sl], ist[1] * inv[sl]};
+      m2[sl] = tail_epilogue(sub_tile<1>(y, sl), is, bt);
     }
     __syncthreads();                                         // every wave is done reading the slab the next stage's x slab aliases
     if (lane < 4 * SW) mx[(s0 + (lane >> 2)) * MX_SLOTS + np + 2 * (lane & 3)] = (lane >> 2) ? m2[1] : m2[0];
-    // -> the next stage's row-form fp32 x slab [sample][2 + q][CFN::XSTR]
-    float* xb = lds + s0 * CFN::XSS + (2 + 4 * g) * CFN::XSTR + c0;
+    // -> the next stage's row-form fp32 x slab [sample][2 + q][D2::XSTR]
+    float* xb = lds + s0 * D2::XSS + (2 + 4 * g) * D2::XSTR + c0;
 #pragma unroll
     for (int sl = 0; sl < SW; ++sl)
 #pragma unroll
       for (int r = 0; r < 4; ++r)
-        *reinterpret_cast<float2*>(xb + sl * CFN::XSS + r * CFN::XSTR) = make_float2(y[sl][0][r], y[sl][1][r]);
+        *reinterpret_cast<float2*>(xb + sl * D2::XSS + r * D2::XSTR) = make_float2(y[sl][0][r], y[sl][1][r]);
   }
   TR(trb + 5);
 }
 
 // downs.2 + mid blocks in the direct form.  Wave w owns the n-tiles 2 w, 2 w + 1 with INTERLEAVED columns (column n of tile h =
 // channel 32 w + 2 n + h: adjacent channels per lane, dword slab stores) x all four samples; acc[sample][h][r] = position
-// 4 (lane >> 4) + r.  acc: the stage's output; mid: the skip tensor (after RTB MID_AFTER).
+// 4 (lane >> 4) + r.  acc: the stage's output; mid: the skip tensor (after RTB D2::MID_AFTER).
 // Lane-private parking of a 32-register tile in LDS ([i][thread] x 16 B: conflict-free b128, no synchronisation -- a thread
 // reads back only what it wrote): the residual tile of an RTB waits there instead of in 32 VGPRs while the block's two convs
 // run (the kernel sits at the 256-register limit of two waves per SIMD; a compiler spill to scratch costs a vmcnt(0) wait
@@ -1360,78 +1358,54 @@ __device__ __forceinline__ void unpark_tile(float* lds, f32x4 (&t)[NS][2]) {
   for (int i = 0; i < 2 * NS; ++i) t[i >> 1][i & 1] = *reinterpret_cast<const f32x4*>(park_slot(lds, i));
 }
 
-template <class CF, int NS>
+template <int NS>
 __device__ __forceinline__ void chain_body_d2d(const ChainArgs& a, float* lds, int lane, int wave, f32x4 (&acc)[NS][2],
                                                f32x4 (&mid)[NS][2], int trb, int tb_off = 0) {
-  static_assert(CF::L == 16 && CF::CM == 128 && CF::C0 == 64 && CF::C1 == 0 && CF::RES0 == RES_CONV && CF::TAIL == TAIL_NONE &&
-                    CF::MID_AFTER >= 1, "downs.2 + mid blocks");
   using G128 = RdGeo<128>;
   using G64 = RdGeo<64>;
   const int n = lane & 15, g = lane >> 4;
   const int c0 = 32 * wave + 2 * n;                          // the lane's channels c0 (tile 0), c0 + 1 (tile 1)
   // LDS: the row-form fp32 x slab (previous stage's tail tile) at the start, the Rd slab behind it (conv A's 64-channel
   // input uses its first bytes in the 64-channel geometry)
-  constexpr int S_OFF = (CF::SPB * CF::XSS * 4 + 255) / 256 * 256;
-  static_assert(S_OFF + G128::BYTES <= MX_OFF * 4, "x slab + Rd slab must fit below the maxima");
-  static_assert(S_OFF >= 5 * 1024 * 4, "the dead x slab holds 5 of the 8 parked float4 per thread");
-  char* const slab = reinterpret_cast<char*>(lds) + S_OFF;
+  static_assert(D2::SLAB_OFF + G128::BYTES <= MX_OFF * 4, "x slab + Rd slab must fit below the maxima");
+  static_assert(D2::SLAB_OFF >= 5 * 1024 * 4, "the dead x slab holds 5 of the 8 parked float4 per thread");
+  char* const slab = reinterpret_cast<char*>(lds) + D2::SLAB_OFF;
   float* const mx = lds + MX_OFF;
   const char* const va128 = slab + g * G128::G + n * 16;     // A fragment: row lane & 15 = position, lane group lane >> 4
   const char* const va64 = slab + g * G64::G + n * 16;
   char* const vs = slab + wave * G128::G + (n >> 2) * G128::BX + (2 + 4 * g) * 16 + (n & 3) * 4;
-  auto wptr = [&](const uint4* w, int frags, int h) { return reinterpret_cast<const u32x4*>(w) + (size_t)(2 * wave + h) * frags * 64 + lane; };
+  auto wt2 = [&](const uint4* w, int frags) { return w_tiles<2>(w, frags, 2 * wave, lane); };
   constexpr int RDD = MMD_D2_RD;                               // weight ring depth of the 128 -> 128 convs
   u32x4 ring[RDD][2][2];
-  const u32x4* wpa[2] = {wptr(a.r0.wa_bf, G64::FRAGS5, 0), wptr(a.r0.wa_bf, G64::FRAGS5, 1)};
-  const u32x4* wpr[2] = {wptr(a.wres_bf, 2 * G64::KC, 0), wptr(a.wres_bf, 2 * G64::KC, 1)};
-  rd_ring_load<G64, 2, 2>(reinterpret_cast<u32x4(&)[2][2][2]>(ring), wpa);   // (conv A + residual streams: depth 2, or it spills)
+  const WTiles<2> wpa = wt2(a.r0.wa_bf, G64::FRAGS5), wpr = wt2(a.wres_bf, 2 * G64::KC);
+  rd_ring_load<G64, 2, 2>(reinterpret_cast<u32x4(&)[2][2][2]>(ring), wpa.p);   // (conv A + residual streams: depth 2, or it spills)
   __syncthreads();                                           // the x slab (previous stage's tail tile) and its maxima are staged
   TR(trb + 0);
 
   float one4[NS];
 #pragma unroll
   for (int sm = 0; sm < NS; ++sm) one4[sm] = 1.f;
-  // GroupNorm + Mish of acc.  Conv A (tb != nullptr): + the time bias, output carried times act_s (conv B's static f16x2
-  // input scale); conv B: + the residual tile, which comes back from its parking area.  isc: the conv's inverse weight scales,
-  // inv: inverse dynamic input scales
-  auto epi = [&](const float* b, const float* gm, const float* be, const float* tb, const float* isc) {
-    return epi_load<2>(b, gm, be, tb, isc, c0);
-  };
-  auto gn = [&](auto conv_a, const Epi<2>& e, const float (&inv)[NS], float act_s) {
-    if constexpr (decltype(conv_a)::value) {
-      const float t0 = e.tb[0] * act_s, t1 = e.tb[1] * act_s;
-      rd_gn_mish<2, 256, true>(acc, e.b, e.g, e.be, e.is, inv, act_scale(act_s), [&](int, int t, int) { return t ? t1 : t0; });
-    } else {
-      f32x4 res[NS][2];
-      unpark_tile(lds, res);
-      rd_gn_mish<2, 256, false>(acc, e.b, e.g, e.be, e.is, inv, ActScale{}, [&](int sm, int t, int r) { return res[sm][t][r]; });
-    }
+  // conv B's epilogue: the residual tile comes back from its parking area
+  auto gn_unparked = [&](const Epi<2>& e) {
+    f32x4 res[NS][2];
+    unpark_tile(lds, res);
+    rd_gn<256>(acc, e, one4, res);
   };
   // one 128 -> 128 conv over the tile in acc (already scaled for f16x2); on entry every wave is past its reads of the slab.
-  // PF (two trajectories per workgroup: the latency-bound launches of <= 512 trajectories, where nothing else on the CU covers an L2
-  // round trip): the first RDD weight steps of the NEXT conv are requested right behind this conv's taps, so they travel during the
-  // GroupNorm + Mish epilogue and the slab store instead of in front of the first MFMA (tools/ubench/pair_split.hip, arm basePF: 3 - 10 %
-  // of a conv); with four trajectories per workgroup the 48 ring registers would have to live through the epilogue of a 32-register tile.
-#ifdef MMD_NO_PF
-  constexpr bool PF = false;                                  // (A/B side build: profiles/r06_prefetch_ab.txt)
-#else
-  constexpr bool PF = NS <= 2;
-#endif
+  // PF (ring_prefetch): the first RDD weight steps of the NEXT conv are requested right behind this conv's taps.
+  constexpr bool PF = ring_prefetch(NS);
   auto prefetch = [&](const uint4* w) {
-    if constexpr (PF) {
-      const u32x4* wp[2] = {wptr(w, G128::FRAGS5, 0), wptr(w, G128::FRAGS5, 1)};
-      rd_ring_load<G128, 2, RDD>(ring, wp);
-    }
+    if constexpr (PF) rd_ring_load<G128, 2, RDD>(ring, wt2(w, G128::FRAGS5).p);
   };
   auto conv = [&](const uint4* w, const uint4* w_next) {
-    const u32x4* wp[2] = {wptr(w, G128::FRAGS5, 0), wptr(w, G128::FRAGS5, 1)};
+    const WTiles<2> wp = wt2(w, G128::FRAGS5);
     TR(trb + 10);
-    if constexpr (!PF) rd_ring_load<G128, 2, RDD>(ring, wp);
+    if constexpr (!PF) rd_ring_load<G128, 2, RDD>(ring, wp.p);
     rd_store2<G128>(vs, acc);
     TR(trb + 11);
     __syncthreads();
     TR(trb + 12);
-    rd_taps<G128, 2, 0, 5, true, false, NS, RDD>(acc, acc, va128, wp, wp, ring);
+    rd_taps<G128, 2, 0, 5, true, false, NS, RDD>(acc, acc, va128, wp.p, wp.p, ring);
     if (w_next) prefetch(w_next);
     TR(trb + 13);
   };
@@ -1441,59 +1415,45 @@ __device__ __forceinline__ void chain_body_d2d(const ChainArgs& a, float* lds, i
 #pragma unroll
   for (int sm = 0; sm < NS; ++sm) inv_in[sm] = dyn_scale(mx_read(mx, sm)).inv;
   rd_zero_halo<G64>(slab);
-  const Epi<2> e0a = epi(a.r0.ba, a.r0.ga, a.r0.bea, a.r0.tb + tb_off, a.r0.isa);
+  const Epi<2> e0a = epi_a<2>(a.r0, tb_off, c0);
   const float br[2] = {a.br[c0], a.br[c0 + 1]}, isr[2] = {a.isr[c0], a.isr[c0 + 1]};
-  rowform_to_rd<CF::C0P, CF::XSS, CF::XSTR, NS>(lds, slab, mx);
+  rowform_to_rd<D2::C0, D2::XSS, D2::XSTR, NS>(lds, slab, mx);
   __syncthreads();
   {
     f32x4 res[NS][2];
-    rd_taps<G64, 2, 0, 5, true, true, NS, 2>(acc, res, va64, wpa, wpr, reinterpret_cast<u32x4(&)[2][2][2]>(ring));
-#pragma unroll
-    for (int sm = 0; sm < NS; ++sm)
-#pragma unroll
-      for (int t = 0; t < 2; ++t) res[sm][t] = res[sm][t] * (isr[t] * inv_in[sm]) + br[t];
+    rd_taps<G64, 2, 0, 5, true, true, NS, 2>(acc, res, va64, wpa.p, wpr.p, reinterpret_cast<u32x4(&)[2][2][2]>(ring));
+    tile_finish_res(res, isr, inv_in, br);
     park_tile(lds, res);                                     // (every wave is past the barrier behind the x slab's last read)
   }
   prefetch(a.r0.wb_bf);                                      // (the 64 -> 128 conv's depth-2 ring is consumed: RTB 0's conv B travels now)
-  gn(std::true_type{}, e0a, inv_in, a.r0.act_a);
+  rd_gn<256>(acc, e0a, inv_in, a.r0.act_a);
   TR(trb + 1);
   __syncthreads();                                           // conv A is done reading the 64-channel slab
   rd_zero_halo<G128>(slab);
   {
-    const Epi<2> e = epi(a.r0.bb, a.r0.gb, a.r0.beb, nullptr, a.r0.isb);
-    conv(a.r0.wb_bf, CF::N_IDENT > 0 ? a.ri[0].wa_bf : nullptr);
-    gn(std::false_type{}, e, one4, 1.f);
+    const Epi<2> e = epi_b<2>(a.r0, c0);
+    conv(a.r0.wb_bf, D2::N_IDENT > 0 ? a.ri[0].wa_bf : nullptr);
+    gn_unparked(e);
   }
 
   // =================== identity RTBs ===================
 #pragma unroll 1
-  for (int k = 0; k < CF::N_IDENT; ++k) {
+  for (int k = 0; k < D2::N_IDENT; ++k) {
     const RtbPtrs& R = a.ri[k];
     park_tile(lds, acc);                                     // the block's input = its residual
-    rd_dyn_out<2>(acc, mx, wave, lane, k == CF::MID_AFTER ? 1 : 0);   // (the input of the RTB after MID_AFTER is the skip tensor)
+    rd_dyn_out<2>(acc, mx, wave, lane, k == D2::MID_AFTER ? 1 : 0);   // (the input of the RTB after MID_AFTER is the skip tensor)
     __syncthreads();                                         // the previous conv is done reading the slab
     float inv[NS];
-#pragma unroll
-    for (int sm = 0; sm < NS; ++sm) {
-      const DynScale ds = dyn_scale(mx_read(mx, sm));
-      inv[sm] = ds.inv;
-#pragma unroll
-      for (int t = 0; t < 2; ++t) acc[sm][t] *= ds.s;
-    }
-    const Epi<2> ea = epi(R.ba, R.ga, R.bea, R.tb + tb_off, R.isa);
+    mx_scale_tile(mx, 0, acc, inv);
+    const Epi<2> ea = epi_a<2>(R, tb_off, c0);
     conv(R.wa_bf, R.wb_bf);
-    gn(std::true_type{}, ea, inv, R.act_a);
+    rd_gn<256>(acc, ea, inv, R.act_a);
     __syncthreads();
-    const Epi<2> eb = epi(R.bb, R.gb, R.beb, nullptr, R.isb);
-    conv(R.wb_bf, k + 1 < CF::N_IDENT ? a.ri[k + 1].wa_bf : nullptr);
-    gn(std::false_type{}, eb, one4, 1.f);
+    const Epi<2> eb = epi_b<2>(R, c0);
+    conv(R.wb_bf, k + 1 < D2::N_IDENT ? a.ri[k + 1].wa_bf : nullptr);
+    gn_unparked(eb);
     TR(trb + 18);
-    if (CF::MID_AFTER == k + 1) {
-#pragma unroll
-      for (int sm = 0; sm < NS; ++sm)
-#pragma unroll
-        for (int t = 0; t < 2; ++t) mid[sm][t] = acc[sm][t];
-    }
+    if (D2::MID_AFTER == k + 1) tile_copy(mid, acc);
   }
   rd_dyn_out<2>(acc, mx, wave, lane, 2);                     // the stage's output: ups.0's conv A takes its maximum from region 2
 }
@@ -1502,12 +1462,10 @@ __device__ __forceinline__ void chain_body_d2d(const ChainArgs& a, float* lds, i
 // Upsample1d = ConvTranspose1d(k4, s2, p1) as two 2-tap parity passes, all f16x2 on Rd slabs.  Wave w owns the n-tile of
 // channels 16 w + (lane & 15) x all four samples.  x0 / x1: the two 128-channel chunks of the input (downs.2's tiles, in
 // ITS layout: store2(tile) writes one into the 128-channel slab); xe / xo: the stage's output (even / odd positions).
-template <class CF, int NS, class STORE2>
+template <int NS, class STORE2>
 __device__ __forceinline__ void chain_body_u0d(const ChainArgs& a, float* lds, int lane, int wave, f32x4 (&x0)[NS][2],
                                                f32x4 (&x1)[NS][2], STORE2 store2, char* slab128, f32x4 (&xe)[NS][1],
                                                f32x4 (&xo)[NS][1], int trb, int tb_off = 0) {
-  static_assert(CF::L == 16 && CF::CM == 64 && CF::C0 == 128 && CF::C1 == 128 && CF::RES0 == RES_CONV && CF::TAIL == TAIL_UP &&
-                    CF::N_IDENT == 1, "ups.0");
   using G128 = RdGeo<128>;
   using G64 = RdGeo<64>;
   const int n = lane & 15, g = lane >> 4, col = 16 * wave + n;
@@ -1517,16 +1475,14 @@ __device__ __forceinline__ void chain_body_u0d(const ChainArgs& a, float* lds, i
   const char* const va128 = slab128 + g * G128::G + n * 16;
   const char* const va64 = slab64 + g * G64::G + n * 16;
   char* const vs64 = slab64 + wave * G64::G + (n >> 3) * G64::BX + (2 + 4 * g) * 16 + ((n & 7) >> 1) * 4;
-  auto wptr = [&](const uint4* w, int frags) { return reinterpret_cast<const u32x4*>(w) + (size_t)wave * frags * 64 + lane; };
+  auto wt1 = [&](const uint4* w, int frags) { return w_tiles<1>(w, frags, wave, lane); };
   constexpr int RDU = MMD_U0_RD;                               // weight ring depth of conv A's two 128-channel chunks
   u32x4 ringa[RDU][1][2];
   constexpr int RDC = MMD_U0C_RD;                              // ... of the 64 -> 64 convs and the tail's parity passes
   u32x4 ring[RDC][1][2];
-  const u32x4* wp0[1] = {wptr(a.r0.wa_bf, G128::FRAGS5)};
-  const u32x4* wp1[1] = {wptr(a.wa0_c1_bf, G128::FRAGS5)};
-  const u32x4* wr0[1] = {wptr(a.wres_bf, 2 * G128::KC)};
-  const u32x4* wr1[1] = {wptr(a.wres_c1_bf, 2 * G128::KC)};
-  rd_ring_load<G128, 1, RDU>(ringa, wp0);
+  const WTiles<1> wp0 = wt1(a.r0.wa_bf, G128::FRAGS5), wp1 = wt1(a.wa0_c1_bf, G128::FRAGS5);
+  const WTiles<1> wr0 = wt1(a.wres_bf, 2 * G128::KC), wr1 = wt1(a.wres_c1_bf, 2 * G128::KC);
+  rd_ring_load<G128, 1, RDU>(ringa, wp0.p);
   __syncthreads();                                           // the previous stage is done with the slab; its maxima are in mx
   TR(trb + 0);
 
@@ -1534,46 +1490,18 @@ __device__ __forceinline__ void chain_body_u0d(const ChainArgs& a, float* lds, i
   float one4[NS];
 #pragma unroll
   for (int sm = 0; sm < NS; ++sm) one4[sm] = 1.f;
-  auto epi = [&](const float* b, const float* gm, const float* be, const float* tb, const float* isc) {
-    return epi_load<1>(b, gm, be, tb, isc, col);
-  };
-  auto gn = [&](auto conv_a, const Epi<1>& e, const float (&inv)[NS], float act_s) {
-    if constexpr (decltype(conv_a)::value) {
-      const float t0 = e.tb[0] * act_s;
-      rd_gn_mish<1, 128, true>(acc, e.b, e.g, e.be, e.is, inv, act_scale(act_s), [&](int, int, int) { return t0; });
-    } else {
-      rd_gn_mish<1, 128, false>(acc, e.b, e.g, e.be, e.is, inv, ActScale{}, [&](int sm, int, int r) { return res[sm][0][r]; });
-    }
-  };
-  // dynamic input scale of a conv on the tile in acc: (maxima -> mx, barrier, then) scale in place; the inverse scales
-  auto dyn_scale_acc = [&](float (&inv)[NS]) {
-#pragma unroll
-    for (int sm = 0; sm < NS; ++sm) {
-      const DynScale ds = dyn_scale(mx_read(mx, sm));
-      inv[sm] = ds.inv;
-      acc[sm][0] *= ds.s;
-    }
-  };
-  // one 64 -> 64 conv over the tile in acc (already scaled); on entry every wave is past its reads of the slab.  PF (two trajectories
-  // per workgroup = unet_kernel<2>): the NEXT pack's first ring steps are requested right behind this conv's taps and travel during the
-  // epilogue (chain_body_d2d has the measurement); `frags_next`: the next pack's fragments per n-tile.
-#ifdef MMD_NO_PF
-  constexpr bool PF = false;
-#else
-  constexpr bool PF = NS <= 2;
-#endif
+  // one 64 -> 64 conv over the tile in acc (already scaled); on entry every wave is past its reads of the slab.  PF (ring_prefetch): the
+  // NEXT pack's first ring steps are requested right behind this conv's taps; `frags_next`: the next pack's fragments per n-tile.
+  constexpr bool PF = ring_prefetch(NS);
   auto prefetch64 = [&](const uint4* w, int frags) {
-    if constexpr (PF) {
-      const u32x4* wp[1] = {wptr(w, frags)};
-      rd_ring_load<G64, 1, RDC>(ring, wp);
-    }
+    if constexpr (PF) rd_ring_load<G64, 1, RDC>(ring, wt1(w, frags).p);
   };
   auto conv64 = [&](const uint4* w, const uint4* w_next, int frags_next) {
-    const u32x4* wp[1] = {wptr(w, G64::FRAGS5)};
-    if constexpr (!PF) rd_ring_load<G64, 1, RDC>(ring, wp);
+    const WTiles<1> wp = wt1(w, G64::FRAGS5);
+    if constexpr (!PF) rd_ring_load<G64, 1, RDC>(ring, wp.p);
     rd_store1<G64>(vs64, acc, lane);
     __syncthreads();
-    rd_taps<G64, 1, 0, 5, true, false, NS, RDC>(acc, res, va64, wp, wp, ring);
+    rd_taps<G64, 1, 0, 5, true, false, NS, RDC>(acc, res, va64, wp.p, wp.p, ring);
     prefetch64(w_next, frags_next);
   };
 
@@ -1584,58 +1512,53 @@ __device__ __forceinline__ void chain_body_u0d(const ChainArgs& a, float* lds, i
     // residual-stream input: dynamic scale from the maxima downs.2 left in regions 1 (skip2) and 2 (mid output) of mx
     const DynScale ds = dyn_scale(fmaxf(mx_read(mx + MX_REGION, sm), mx_read(mx + 2 * MX_REGION, sm)));
     inv_in[sm] = ds.inv;
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      x0[sm][t] *= ds.s;
-      x1[sm][t] *= ds.s;
-    }
+    tile_scale(sub_tile<1>(x0, sm), ds.s);
+    tile_scale(sub_tile<1>(x1, sm), ds.s);
   }
-  const Epi<1> e0a = epi(a.r0.ba, a.r0.ga, a.r0.bea, a.r0.tb + tb_off, a.r0.isa);
-  const float br = a.br[col], isr = a.isr[col];
+  const Epi<1> e0a = epi_a<1>(a.r0, tb_off, col);
+  const float br[1] = {a.br[col]}, isr[1] = {a.isr[col]};
   store2(x0);
   TR(160);
   __syncthreads();
   TR(161);
-  rd_taps<G128, 1, 0, 5, true, true, NS, RDU>(acc, res, va128, wp0, wr0, ringa);
-  rd_ring_load<G128, 1, RDU>(ringa, wp1);
+  rd_taps<G128, 1, 0, 5, true, true, NS, RDU>(acc, res, va128, wp0.p, wr0.p, ringa);
+  rd_ring_load<G128, 1, RDU>(ringa, wp1.p);
   TR(162);
   __syncthreads();                                           // every wave is done reading chunk 0
   store2(x1);
   TR(163);
   __syncthreads();
   TR(164);
-  rd_taps<G128, 1, 0, 5, false, true, NS, RDU>(acc, res, va128, wp1, wr1, ringa);
+  rd_taps<G128, 1, 0, 5, false, true, NS, RDU>(acc, res, va128, wp1.p, wr1.p, ringa);
   TR(165);
-#pragma unroll
-  for (int sm = 0; sm < NS; ++sm) res[sm][0] = res[sm][0] * (isr * inv_in[sm]) + br;
+  tile_finish_res(res, isr, inv_in, br);
   prefetch64(a.r0.wb_bf, G64::FRAGS5);
-  gn(std::true_type{}, e0a, inv_in, a.r0.act_a);
+  rd_gn<128>(acc, e0a, inv_in, a.r0.act_a);
   TR(trb + 1);
   __syncthreads();                                           // chunk 1 is consumed
   rd_zero_halo<G64>(slab64);
   {
-    const Epi<1> e = epi(a.r0.bb, a.r0.gb, a.r0.beb, nullptr, a.r0.isb);
+    const Epi<1> e = epi_b<1>(a.r0, col);
     conv64(a.r0.wb_bf, a.ri[0].wa_bf, G64::FRAGS5);
-    gn(std::false_type{}, e, one4, 1.f);
+    rd_gn<128>(acc, e, one4, res);
   }
   TR(trb + 4);
   // =================== identity RTB ===================
   {
     const RtbPtrs& R = a.ri[0];
-#pragma unroll
-    for (int sm = 0; sm < NS; ++sm) res[sm][0] = acc[sm][0];
+    tile_copy(res, acc);
     rd_dyn_out<1>(acc, mx, wave, lane, 0);
     __syncthreads();                                         // the previous conv is done reading the slab
     float inv[NS];
-    dyn_scale_acc(inv);
-    const Epi<1> ea = epi(R.ba, R.ga, R.bea, R.tb + tb_off, R.isa);
+    mx_scale_tile(mx, 0, acc, inv);
+    const Epi<1> ea = epi_a<1>(R, tb_off, col);
     conv64(R.wa_bf, R.wb_bf, G64::FRAGS5);
-    gn(std::true_type{}, ea, inv, R.act_a);
+    rd_gn<128>(acc, ea, inv, R.act_a);
     TR(trb + 5);
     __syncthreads();
-    const Epi<1> eb = epi(R.bb, R.gb, R.beb, nullptr, R.isb);
+    const Epi<1> eb = epi_b<1>(R, col);
     conv64(R.wb_bf, a.wt_bf0, 2 * G64::KC * 2);              // (next: the transposed tail's first parity pack)
-    gn(std::false_type{}, eb, one4, 1.f);
+    rd_gn<128>(acc, eb, one4, res);
     TR(trb + 6);
   }
   // =================== tail: out[2 m] = in[m - 1] W3 + in[m] W1, out[2 m + 1] = in[m] W2 + in[m + 1] W0 ===================
@@ -1643,31 +1566,22 @@ __device__ __forceinline__ void chain_body_u0d(const ChainArgs& a, float* lds, i
     rd_dyn_out<1>(acc, mx, wave, lane, 0);
     __syncthreads();
     float inv[NS];
-    dyn_scale_acc(inv);
-    const u32x4* wt0[1] = {wptr(a.wt_bf0, 2 * G64::KC * 2)};
-    const u32x4* wt1[1] = {wptr(a.wt_bf1, 2 * G64::KC * 2)};
-    const float bt = a.bt[col], is0 = a.ist0[col], is1 = a.ist1[col];
-    if constexpr (!PF) rd_ring_load<G64, 1, RDC>(ring, wt0);
+    mx_scale_tile(mx, 0, acc, inv);
+    const WTiles<1> wt0 = wt1(a.wt_bf0, 2 * G64::KC * 2), wt1p = wt1(a.wt_bf1, 2 * G64::KC * 2);
+    const float bt[1] = {a.bt[col]}, is0 = a.ist0[col], is1 = a.ist1[col];
+    if constexpr (!PF) rd_ring_load<G64, 1, RDC>(ring, wt0.p);
     rd_store1<G64>(vs64, acc, lane);
     __syncthreads();
     TR(trb + 7);
-    rd_taps<G64, 1, 1, 2, true, false, NS, RDC>(xe, res, va64, wt0, wt0, ring);
-    rd_ring_load<G64, 1, RDC>(ring, wt1);
-    rd_taps<G64, 1, 2, 2, true, false, NS, RDC>(xo, res, va64, wt1, wt1, ring);
+    rd_taps<G64, 1, 1, 2, true, false, NS, RDC>(xe, res, va64, wt0.p, wt0.p, ring);
+    rd_ring_load<G64, 1, RDC>(ring, wt1p.p);
+    rd_taps<G64, 1, 2, 2, true, false, NS, RDC>(xo, res, va64, wt1p.p, wt1p.p, ring);
     // the stage's output stays in registers: xe / xo[sample][0][r] = positions 2 m, 2 m + 1 (m = 4 g + r) of channel col; the
     // per-sample maxima of the wave's 16 channels go to slot `wave` of mx region 0 (the caller's barrier publishes them)
 #pragma unroll
     for (int sm = 0; sm < NS; ++sm) {
-      float m = 0.f;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        xe[sm][0][r] = fmaf(xe[sm][0][r], is0 * inv[sm], bt);
-        xo[sm][0][r] = fmaf(xo[sm][0][r], is1 * inv[sm], bt);
-        m = fmaxf(m, fmaxf(fabsf(xe[sm][0][r]), fabsf(xo[sm][0][r])));
-      }
-      m = row_max16(m);
-      m = max_xor16(m);
-      m = max_xor32(m);
+      const float s0[1] = {is0 * inv[sm]}, s1[1] = {is1 * inv[sm]};
+      const float m = tail_up_epilogue(sub_tile<1>(xe, sm), sub_tile<1>(xo, sm), s0, s1, bt);
       if (lane == 0) mx[sm * MX_SLOTS + wave] = m;
     }
   }
@@ -1680,7 +1594,128 @@ __device__ __forceinline__ void chain_body_u0d(const ChainArgs& a, float* lds, i
 // the four samples' slabs across waves, one after the other through the same 10 KB slab (4 workgroup barriers); everything
 // after it -- 3 convs, the transposed tail as two parity passes, the final block and the output store -- reads only what the
 // same wave wrote (wave_lds_fence).  Slabs: RwGeo<64, 32> (conv A chunks), RwGeo<32, 32>, RwGeo<32, 64> (final block).
-template <class CF, int NS>
+//
+// Two schedules, as for downs.0: chain_body_u1w (wave = sample) and chain_body_u1s (wave = half a sample); the fragments below define
+// values and layout for both, on MT M tiles from tile m0 of the sample on.
+struct U1 {
+  using GA = RwGeo<64, 32>;
+  using GB = RwGeo<32, 32>;
+  using GF = RwGeo<32, 64>;
+  static constexpr int W_BYTES = cmax(GA::BYTES, cmax(GB::BYTES, GF::BYTES)) + 128;   // a sample's slab
+  static constexpr int RDA = 5;                               // conv A's weight ring: half a chunk ahead
+  static constexpr int TF = 2 * (2 * GB::KC * 2);             // fragments of one parity pass of the transposed tail (both n-tiles)
+  static_assert(4 * W_BYTES <= MX_OFF * 4, "four private slabs");
+  static_assert(2 * W_BYTES + 2 * WBUF_BYTES <= MX_OFF * 4, "two samples' slabs + two weight buffers below the maxima");
+  static_assert(GB::FRAGS5 * 2 * 1024 <= WBUF_BYTES && GF::FRAGS5 * 2 * 1024 <= WBUF_BYTES, "a staged conv fits its buffer");
+};
+__device__ __forceinline__ float lane_swap1(float v) {       // the value of the partner lane (n ^ 1)
+  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xf, 0xf, true));
+}
+// The dynamic input scales of conv A from the maxima in mx region 0 (slots 0 .. 3: ups.0's output, 4 .. 7: the skip tensor): sc[sample]
+// of the workgroup's NS samples for chunk 0, skip[sl] of the samples whose skip tiles this wave holds (downs.1's layout) for chunk 1
+template <int NS> struct U1Scales { float sc[NS]; DynScale skip[NS / 2]; };
+template <int NS>
+__device__ __forceinline__ U1Scales<NS> u1_input_scales(const float* mx, int wave) {
+  U1Scales<NS> s;
+#pragma unroll
+  for (int sm = 0; sm < NS; ++sm) s.sc[sm] = dyn_scale(mx_read(mx, sm)).s;
+#pragma unroll
+  for (int sl = 0; sl < NS / 2; ++sl) s.skip[sl] = dyn_scale(mx_read(mx, NS / 2 * (wave >> 1) + sl));
+  return s;
+}
+// chunk 0 = ups.0's output (wave w holds channels col = 16 w + n of all NS samples) -> the samples' slabs: block 2 wave + (n >> 3) = (lane
+// group wave, chunk n >> 3), the pair (n & ~1, n | 1) one dword; the lanes of a pair swap halves so that each stores whole dwords -- the
+// even lane the even positions 2 (4 g + r) of channels (col, col + 1), the odd lane the odd positions of (col - 1, col)
+template <int NS>
+__device__ __forceinline__ void u1_store_chunk0(char* lb, int wave, int n, int g, const f32x4 (&xe)[NS][1], const f32x4 (&xo)[NS][1],
+                                                const float (&sc)[NS]) {
+  using GA = U1::GA;
+  const bool odd = n & 1;
+  char* const d0 = lb + wave * GA::G + (n >> 3) * GA::BX + ((n & 7) >> 1) * 4 + 2 * 16 + (8 * g + (odd ? 1 : 0)) * 16;
+#pragma unroll
+  for (int sm = 0; sm < NS; ++sm)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const float own = (odd ? xo[sm][0][r] : xe[sm][0][r]) * sc[sm];
+      const float recv = lane_swap1((odd ? xe[sm][0][r] : xo[sm][0][r]) * sc[sm]);
+      const F16Pair p = f16_split2(odd ? recv : own, odd ? own : recv);
+      char* d = d0 + sm * U1::W_BYTES + 2 * r * 16;
+      *reinterpret_cast<unsigned*>(d) = p.hi;
+      *reinterpret_cast<unsigned*>(d + GA::PS) = p.lo;
+    }
+}
+// chunk 1 = skip (downs.1's layout: wave = (channel half np, sample pair sp); skip[m][t][r]: sample s0 + (m >> 1), channel 32 np + 2 n + t,
+// position 16 (m & 1) + 4 g + r): the lane's channel pair of the 64-channel chunk = block 4 np + (n >> 2) = (chunk (n >> 2) & 1, lane
+// group 2 np + (n >> 3)), dword n & 3, in the slabs of the wave's samples
+template <int NS>
+__device__ __forceinline__ void u1_store_chunk1(char* lb, int wave, int n, int g, const f32x4 (&skip)[NS][2], const DynScale (&sc)[NS / 2]) {
+  using GA = U1::GA;
+  const int np = wave & 1, s0 = NS / 2 * (wave >> 1);
+  char* const sdst = lb + (2 * np + (n >> 3)) * GA::G + ((n >> 2) & 1) * GA::BX + (n & 3) * 4 + (2 + 4 * g) * 16;
+#pragma unroll
+  for (int m = 0; m < NS; ++m)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const F16Pair p = f16_split2(skip[m][0][r] * sc[m >> 1].s, skip[m][1][r] * sc[m >> 1].s);
+      char* d = sdst + (s0 + (m >> 1)) * U1::W_BYTES + (16 * (m & 1) + r) * 16;
+      *reinterpret_cast<unsigned*>(d) = p.hi;
+      *reinterpret_cast<unsigned*>(d + GA::PS) = p.lo;
+    }
+}
+// The transposed tail's output of input tiles m0 .. m0 + MT - 1 (positions 2 m + parity, m = 16 (m0 + mt) + 4 g + r: rows 2 + 32 (m0 + mt)
+// + 8 g + 2 r + parity) times s -> the 64-row slab; vsF = slab + the lane's (block n >> 2, row 0, dword n & 3)
+template <int MT>
+__device__ __forceinline__ void u1_tail_store(char* vsF, int m0, int g, const f32x4 (&e)[MT][2], const f32x4 (&o)[MT][2], float s) {
+  using GF = U1::GF;
+#pragma unroll
+  for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const F16Pair pe = f16_split2(e[mt][0][r] * s, e[mt][1][r] * s), po = f16_split2(o[mt][0][r] * s, o[mt][1][r] * s);
+      char* d = vsF + (2 + 32 * (m0 + mt) + 8 * g + 2 * r) * 16;
+      *reinterpret_cast<unsigned*>(d) = pe.hi;
+      *reinterpret_cast<unsigned*>(d + GF::PS) = pe.lo;
+      *reinterpret_cast<unsigned*>(d + 16) = po.hi;
+      *reinterpret_cast<unsigned*>(d + 16 + GF::PS) = po.lo;
+    }
+}
+// eps = the 1x1 conv's output times its scale + bias (columns n < 4 of the tile are real), M tiles m0 .. m0 + MT - 1 of a sample:
+// ... -> rows [position][4] of et (the sample's slab, for the fused step)
+template <int MT>
+__device__ __forceinline__ void u1_eps_to_slab(float* et, int m0, int n, int g, const f32x4 (&out)[MT][1], float s1, float b1) {
+  if (n < 4) {
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) et[(16 * (m0 + mt) + 4 * g + r) * 4 + n] = fmaf(out[mt][0][r], s1, b1);
+  }
+}
+// ... -> eps [n, 64, 4] in HBM (the unfused path), sample smp
+template <int MT>
+__device__ __forceinline__ void u1_store_out(float* eps, size_t smp, int m0, int n, int g, const f32x4 (&out)[MT][1], float s1, float b1) {
+  float* dst = eps + (smp * 64 + 16 * m0 + 4 * g) * 4 + n;
+#pragma unroll
+  for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) dst[(16 * mt + r) * 4] = fmaf(out[mt][0][r], s1, b1);
+}
+// The unguided ddpm_sample_fn step (sample_functions.py:40-86; ddpm_guide_kernel's arithmetic, guide_dev.h) on trajectory `smp` of the
+// launch, in place, lane = support point; et = its eps rows [64][4] in LDS
+__device__ __forceinline__ void fused_ddpm_row(const FusedStep& fs, const float* et, int smp, int lane) {
+  const float4 e = *reinterpret_cast<const float4*>(et + lane * 4);
+  const int traj = fs.traj0 + smp, robot = traj / fs.spr;
+  const size_t idx = (size_t)traj * H + lane;
+  float4 v = ddpm_posterior_mean(fs.x[idx], e, fs.a_t, fs.b_t, fs.c1, fs.c2);
+  if (fs.do_noise)
+    v = add_step_noise(v, fs.noise ? fs.noise[idx] : traj_normal4(fs.seed, fs.robot_seeds, fs.draw, fs.traj_base, idx, robot, fs.spr), fs.sigma,
+                       fs.noise_std_extra);
+  float4 hv;
+  if (hard_row(fs.hard_rows, fs.n_hard, fs.hard, robot, lane, hv)) v = hv;
+  fs.x[idx] = v;
+  if (fs.chain) fs.chain[idx] = v;
+}
+
+template <int NS>
 __device__ __forceinline__ void chain_body_u1w(const ChainArgs& a, const FinalArgs& f, const FusedStep& fs, float* lds, int n0, int lane_in, int wave,
                                                const f32x4 (&xe)[NS][1], const f32x4 (&xo)[NS][1], const f32x4 (&skip)[NS][2],
                                                int trb, int tb_off = 0) {
@@ -1688,176 +1723,83 @@ __device__ __forceinline__ void chain_body_u1w(const ChainArgs& a, const FinalAr
   // of being kept alive, i.e. spilled, since the stages that happen to use the same products)
   int lane = lane_in;
   asm volatile("" : "+v"(lane));
-  static_assert(CF::L == 32 && CF::CM == 32 && CF::C0 == 64 && CF::C1 == 64 && CF::RES0 == RES_CONV && CF::N_IDENT == 1 &&
-                    CF::TAIL == TAIL_UP, "ups.1");
-  using GA = RwGeo<64, 32>;
-  using GB = RwGeo<32, 32>;
-  using GF = RwGeo<32, 64>;
-  constexpr int W_BYTES = cmax(GA::BYTES, cmax(GB::BYTES, GF::BYTES)) + 128;
-  static_assert(4 * W_BYTES <= MX_OFF * 4, "four private slabs");
+  using GA = U1::GA;
+  using GB = U1::GB;
+  using GF = U1::GF;
+  constexpr int RDA = U1::RDA;
   char* const lb = reinterpret_cast<char*>(lds);
-  char* const slab = lb + wave * W_BYTES;
+  char* const slab = lb + wave * U1::W_BYTES;
   float* const mx = lds + MX_OFF;
   const int n = lane & 15, g = lane >> 4, c0 = 2 * n;
-  const bool odd = n & 1;
-  auto wptr = [&](const uint4* w, int frags, int t) { return reinterpret_cast<const u32x4*>(w) + (size_t)t * frags * 64 + lane; };
-  auto swap1 = [](float v) {                                  // the value of the partner lane (n ^ 1)
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xf, 0xf, true));
-  };
-  const u32x4* wp0[2] = {wptr(a.r0.wa_bf, GA::FRAGS5, 0), wptr(a.r0.wa_bf, GA::FRAGS5, 1)};
-  const u32x4* wp1[2] = {wptr(a.wa0_c1_bf, GA::FRAGS5, 0), wptr(a.wa0_c1_bf, GA::FRAGS5, 1)};
-  const u32x4* wr0[2] = {wptr(a.wres_bf, 2 * GA::KC, 0), wptr(a.wres_bf, 2 * GA::KC, 1)};
-  const u32x4* wr1[2] = {wptr(a.wres_c1_bf, 2 * GA::KC, 0), wptr(a.wres_c1_bf, 2 * GA::KC, 1)};
-  constexpr int RDA = 5;                                      // conv A's weight ring: half a chunk ahead
+  auto wt2 = [&](const uint4* w, int frags) { return w_tiles<2>(w, frags, 0, lane); };
+  const WTiles<2> wp0 = wt2(a.r0.wa_bf, GA::FRAGS5), wp1 = wt2(a.wa0_c1_bf, GA::FRAGS5);
+  const WTiles<2> wr0 = wt2(a.wres_bf, 2 * GA::KC), wr1 = wt2(a.wres_c1_bf, 2 * GA::KC);
   u32x4 ring[RDA][2][2];
-  rd_ring_load<GA, 2, RDA>(ring, wp0);
-  // ---- the skip tensor's per-sample maxima (downs.1's layout: wave = (channel half np, sample pair sp); skip[m][t][r]: sample 2 sp
-  //      + (m >> 1), channel 32 np + 2 n + t, position 16 (m & 1) + 4 g + r) -> slots 4 .. 7 of mx region 0 (the two waves of a
-  //      sample pair fill them); ups.0 left its output's maxima in slots 0 .. 3
-  //      (two trajectories per workgroup: sp = the wave's one sample, NS = 2 M tiles)
-  constexpr int SW = NS / 2;
-  const int np = wave & 1, sp = wave >> 1, s0 = SW * sp;
-  {
-    float m2[2] = {0.f, 0.f};
-#pragma unroll
-    for (int sl = 0; sl < SW; ++sl) {
-      float m = 0.f;
-#pragma unroll
-      for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) m = fmaxf(m, fabsf(skip[2 * sl + mt][t][r]));
-      m = row_max16(m);
-      m = max_xor16(m);
-      m2[sl] = max_xor32(m);
-    }
-    if (lane < 2 * SW) mx[(s0 + (lane >> 1)) * MX_SLOTS + 4 + np + 2 * (lane & 1)] = (lane >> 1) ? m2[1] : m2[0];
-  }
+  rd_ring_load<GA, 2, RDA>(ring, wp0.p);
+  // ---- the skip tensor's per-sample maxima -> slots 4 .. 7 of mx region 0 (the two waves of a sample pair fill them); ups.0 left its
+  //      output's maxima in slots 0 .. 3
+  pair_maxima_out<2, 4>(skip, mx, wave, lane);
   __syncthreads();                                           // ups.0 is done with its slabs; the maxima are in mx
   TR(trb + 0);
-  float sc[4];
-#pragma unroll
-  for (int sm = 0; sm < 4; ++sm) sc[sm] = dyn_scale(mx_read(mx, sm)).s;
+  const U1Scales<NS> sc = u1_input_scales<NS>(mx, wave);
   const float inv_in = dyn_scale(mx_read(mx, wave)).inv;
-  const float sc_lo = dyn_scale(mx_read(mx, s0)).s, sc_hi = dyn_scale(mx_read(mx, s0 + SW - 1)).s;
-  // channel col = 16 wave + n of a 64-channel chunk: block 2 wave + (n >> 3) = (lane group wave, chunk n >> 3), the pair (n & ~1,
-  // n | 1) one dword; the lanes of a pair swap halves so that each stores whole dwords
-  char* const cdst = lb + wave * GA::G + (n >> 3) * GA::BX + ((n & 7) >> 1) * 4 + 2 * 16;
-  {
-    // zero halo rows 0, 1, 34, 35 of the own slab's 8 blocks x 2 pieces
-    const int hr = lane & 3;
-    *reinterpret_cast<uint4*>(slab + (lane >> 5) * GA::PS + ((lane >> 3) & 3) * GA::G + ((lane >> 2) & 1) * GA::BX +
-                              (hr < 2 ? hr : 32 + hr) * 16) = make_uint4(0u, 0u, 0u, 0u);
-    // chunk 0 = ups.0's output: the even lane stores the even positions 2 (4 g + r) of channels (col, col + 1), the odd lane
-    // the odd positions of (col - 1, col)
-    char* const d0 = cdst + (8 * g + (odd ? 1 : 0)) * 16;
-#pragma unroll
-    for (int sm = 0; sm < NS; ++sm)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const float own = (odd ? xo[sm][0][r] : xe[sm][0][r]) * sc[sm];
-        const float recv = swap1((odd ? xe[sm][0][r] : xo[sm][0][r]) * sc[sm]);
-        const F16Pair p = f16_split2(odd ? recv : own, odd ? own : recv);
-        char* d = d0 + sm * W_BYTES + 2 * r * 16;
-        *reinterpret_cast<unsigned*>(d) = p.hi;
-        *reinterpret_cast<unsigned*>(d + GA::PS) = p.lo;
-      }
-  }
+  rw_zero_halo<GA>(slab, 32, lane, true);                    // (rows 0, 1, 34, 35 of the own slab's 8 blocks x 2 pieces)
+  u1_store_chunk0(lb, wave, n, g, xe, xo, sc.sc);
   TR(trb + 6);
   __syncthreads();
   TR(trb + 7);
   const char* const vaA = slab + g * GA::G + n * 16;
   f32x4 acc[2][2], res[2][2];
-  rd_taps<GA, 2, 0, 5, true, true, 2, RDA>(acc, res, vaA, wp0, wr0, ring);
-  rd_ring_load<GA, 2, RDA>(ring, wp1);
+  rd_taps<GA, 2, 0, 5, true, true, 2, RDA>(acc, res, vaA, wp0.p, wr0.p, ring);
+  rd_ring_load<GA, 2, RDA>(ring, wp1.p);
   TR(trb + 8);
   __syncthreads();                                           // every wave has consumed chunk 0
-  {
-    // chunk 1 = skip: the lane's channel pair (32 np + 2 n, + 1) of the 64-channel chunk = block 4 np + (n >> 2) = (chunk (n >> 2) &
-    // 1, lane group 2 np + (n >> 3)), dword n & 3, in the slabs of samples 2 sp, 2 sp + 1
-    char* const sdst = lb + (2 * np + (n >> 3)) * GA::G + ((n >> 2) & 1) * GA::BX + (n & 3) * 4 + (2 + 4 * g) * 16;
-#pragma unroll
-    for (int m = 0; m < NS; ++m) {
-      const float sm_s = (m >> 1) ? sc_hi : sc_lo;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const F16Pair p = f16_split2(skip[m][0][r] * sm_s, skip[m][1][r] * sm_s);
-        char* d = sdst + (s0 + (m >> 1)) * W_BYTES + (16 * (m & 1) + r) * 16;
-        *reinterpret_cast<unsigned*>(d) = p.hi;
-        *reinterpret_cast<unsigned*>(d + GA::PS) = p.lo;
-      }
-    }
-  }
+  u1_store_chunk1(lb, wave, n, g, skip, sc.skip);
   __syncthreads();
   TR(trb + 10);
-  const Epi<2> e0a = epi_load<2>(a.r0.ba, a.r0.ga, a.r0.bea, a.r0.tb + tb_off, a.r0.isa, c0);
+  const Epi<2> e0a = epi_a<2>(a.r0, tb_off, c0);
   const float br[2] = {a.br[c0], a.br[c0 + 1]}, isr[2] = {a.isr[c0], a.isr[c0 + 1]};
-  rd_taps<GA, 2, 0, 5, false, true, 2, RDA>(acc, res, vaA, wp1, wr1, ring);
+  rd_taps<GA, 2, 0, 5, false, true, 2, RDA>(acc, res, vaA, wp1.p, wr1.p, ring);
   TR(trb + 11);
   // ---- from here on the wave is on its own: 32-channel slab
   const char* const vaB = slab + g * GB::G + n * 16;
   char* const vsB = slab + (n >> 2) * GB::G + (2 + 4 * g) * 16 + (n & 3) * 4;
   u32x4 ring5[5][2][2];
-  auto preload = [&](const uint4* w) {
-    const u32x4* wp[2] = {wptr(w, GB::FRAGS5, 0), wptr(w, GB::FRAGS5, 1)};
-    rd_ring_load<GB, 2, 5>(ring5, wp);
-  };
+  auto preload = [&](const uint4* w) { rd_ring_load<GB, 2, 5>(ring5, wt2(w, GB::FRAGS5).p); };
   preload(a.r0.wb_bf);
-  const float one = 1.f;
-  auto epi = [&](const float* bs, const float* gm, const float* be, const float* tb, const float* isc) {
-    return epi_load<2>(bs, gm, be, tb, isc, c0);
-  };
-  auto gn = [&](auto conv_a, const Epi<2>& e, float inv, float act_s) {
-    if constexpr (decltype(conv_a)::value) {
-      const float t0 = e.tb[0] * act_s, t1 = e.tb[1] * act_s;
-      rw_gn_mish_whole<2, 2, 2, 128, true>(acc, e.b, e.g, e.be, e.is, inv, act_scale(act_s), [&](int, int t, int) { return t ? t1 : t0; });
-    } else {
-      rw_gn_mish_whole<2, 2, 2, 128, false>(acc, e.b, e.g, e.be, e.is, inv, ActScale{}, [&](int mt, int t, int r) { return res[mt][t][r]; });
-    }
-  };
   auto conv = [&](const uint4* w) {                          // one 32 -> 32 conv over the tile in acc (already scaled)
-    const u32x4* wp[2] = {wptr(w, GB::FRAGS5, 0), wptr(w, GB::FRAGS5, 1)};
+    const WTiles<2> wp = wt2(w, GB::FRAGS5);
     rw_store2<GB, 2>(vsB, acc);
     wave_lds_fence();
-    rd_taps<GB, 2, 0, 5, true, false, 2, 5>(acc, res, vaB, wp, wp, ring5);
+    rd_taps<GB, 2, 0, 5, true, false, 2, 5>(acc, res, vaB, wp.p, wp.p, ring5);
     wave_lds_fence();                                        // (the next store must not overtake these reads)
   };
-#pragma unroll
-  for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-    for (int t = 0; t < 2; ++t) res[mt][t] = res[mt][t] * (isr[t] * inv_in) + br[t];
-  gn(std::true_type{}, e0a, inv_in, a.r0.act_a);
+  tile_finish_res(res, isr, inv_in, br);
+  rw_gn<2, 128>(acc, e0a, inv_in, a.r0.act_a);
   TR(trb + 1);
   wave_lds_fence();                                          // conv A's reads are done: the slab changes its geometry
-  if (lane < 32) *reinterpret_cast<uint4*>(slab + (lane >> 4) * GB::PS + ((lane >> 2) & 3) * GB::G + ((lane & 3) < 2 ? (lane & 3) : 32 + (lane & 3)) * 16) = make_uint4(0u, 0u, 0u, 0u);
+  rw_zero_halo<GB>(slab, 32, lane, true);
   {
-    const Epi<2> e = epi(a.r0.bb, a.r0.gb, a.r0.beb, nullptr, a.r0.isb);
+    const Epi<2> e = epi_b<2>(a.r0, c0);
     conv(a.r0.wb_bf);
     preload(a.ri[0].wa_bf);
-    gn(std::false_type{}, e, one, 1.f);
+    rw_gn<2, 128>(acc, e, 1.f, res);
   }
   TR(trb + 2);
   // ---- identity RTB
   {
     const RtbPtrs& R = a.ri[0];
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-      for (int t = 0; t < 2; ++t) res[mt][t] = acc[mt][t];
-    const DynScale ds = dyn_scale(rw_absmax<2, 2>(acc));
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-      for (int t = 0; t < 2; ++t) acc[mt][t] *= ds.s;
-    const Epi<2> ea = epi(R.ba, R.ga, R.bea, R.tb + tb_off, R.isa);
+    tile_copy(res, acc);
+    const DynScale ds = dyn_scale(rw_absmax(acc));
+    tile_scale(acc, ds.s);
+    const Epi<2> ea = epi_a<2>(R, tb_off, c0);
     conv(R.wa_bf);
     preload(R.wb_bf);
-    gn(std::true_type{}, ea, ds.inv, R.act_a);
+    rw_gn<2, 128>(acc, ea, ds.inv, R.act_a);
     TR(trb + 3);
-    const Epi<2> eb = epi(R.bb, R.gb, R.beb, nullptr, R.isb);
+    const Epi<2> eb = epi_b<2>(R, c0);
     conv(R.wb_bf);
-    gn(std::false_type{}, eb, one, 1.f);
+    rw_gn<2, 128>(acc, eb, 1.f, res);
     TR(trb + 4);
   }
   // ---- tail: Upsample1d = ConvTranspose1d(k4, s2, p1): out[2 m] = in[m - 1] W3 + in[m] W1, out[2 m + 1] = in[m] W2 + in[m + 1] W0
@@ -1867,281 +1809,150 @@ __device__ __forceinline__ void chain_body_u1w(const ChainArgs& a, const FinalAr
   f32x4 y[4][2];
   float inv_f;
   {
-    const DynScale ds = dyn_scale(rw_absmax<2, 2>(acc));
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-      for (int t = 0; t < 2; ++t) acc[mt][t] *= ds.s;
-    const u32x4* wt0[2] = {wptr(a.wt_bf0, 2 * GB::KC * 2, 0), wptr(a.wt_bf0, 2 * GB::KC * 2, 1)};
-    const u32x4* wt1[2] = {wptr(a.wt_bf1, 2 * GB::KC * 2, 0), wptr(a.wt_bf1, 2 * GB::KC * 2, 1)};
+    const DynScale ds = dyn_scale(rw_absmax(acc));
+    tile_scale(acc, ds.s);
+    const WTiles<2> wt0 = wt2(a.wt_bf0, 2 * GB::KC * 2), wt1 = wt2(a.wt_bf1, 2 * GB::KC * 2);
     u32x4 ring2[2][2][2];
     const float bt[2] = {a.bt[c0], a.bt[c0 + 1]};
     const float is0[2] = {a.ist0[c0] * ds.inv, a.ist0[c0 + 1] * ds.inv}, is1[2] = {a.ist1[c0] * ds.inv, a.ist1[c0 + 1] * ds.inv};
-    rd_ring_load<GB, 2, 2>(ring2, wt0);
+    rd_ring_load<GB, 2, 2>(ring2, wt0.p);
     rw_store2<GB, 2>(vsB, acc);
     wave_lds_fence();
     f32x4 e[2][2], o[2][2];
-    rd_taps<GB, 2, 1, 2, true, false, 2, 2>(e, res, vaB, wt0, wt0, ring2);
-    rd_ring_load<GB, 2, 2>(ring2, wt1);
-    rd_taps<GB, 2, 2, 2, true, false, 2, 2>(o, res, vaB, wt1, wt1, ring2);
-    float m = 0.f;
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-      for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          e[mt][t][r] = fmaf(e[mt][t][r], is0[t], bt[t]);
-          o[mt][t][r] = fmaf(o[mt][t][r], is1[t], bt[t]);
-          m = fmaxf(m, fmaxf(fabsf(e[mt][t][r]), fabsf(o[mt][t][r])));
-        }
-    m = row_max16(m);
-    m = max_xor16(m);
-    m = max_xor32(m);
-    const DynScale df = dyn_scale(m);
+    rd_taps<GB, 2, 1, 2, true, false, 2, 2>(e, res, vaB, wt0.p, wt0.p, ring2);
+    rd_ring_load<GB, 2, 2>(ring2, wt1.p);
+    rd_taps<GB, 2, 2, 2, true, false, 2, 2>(o, res, vaB, wt1.p, wt1.p, ring2);
+    const DynScale df = dyn_scale(tail_up_epilogue(e, o, is0, is1, bt));
     inv_f = df.inv;
     wave_lds_fence();                                        // the tail's reads are done: 64-row geometry
-    if (lane < 32) *reinterpret_cast<uint4*>(slab + (lane >> 4) * GF::PS + ((lane >> 2) & 3) * GF::G + ((lane & 3) < 2 ? (lane & 3) : 64 + (lane & 3)) * 16) = make_uint4(0u, 0u, 0u, 0u);
-    // positions 2 m + parity, m = 16 mt + 4 g + r: rows 2 + 32 mt + 8 g + 2 r + parity
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const F16Pair pe = f16_split2(e[mt][0][r] * df.s, e[mt][1][r] * df.s), po = f16_split2(o[mt][0][r] * df.s, o[mt][1][r] * df.s);
-        char* d = vsF + (2 + 32 * mt + 8 * g + 2 * r) * 16;
-        *reinterpret_cast<unsigned*>(d) = pe.hi;
-        *reinterpret_cast<unsigned*>(d + GF::PS) = pe.lo;
-        *reinterpret_cast<unsigned*>(d + 16) = po.hi;
-        *reinterpret_cast<unsigned*>(d + 16 + GF::PS) = po.lo;
-      }
+    rw_zero_halo<GF>(slab, 64, lane, true);
+    u1_tail_store<2>(vsF, 0, g, e, o, df.s);
   }
   TR(trb + 5);
   // ---- final block: Conv1dBlock(32 -> 32, k5) + GroupNorm + Mish, then the 1x1 conv 32 -> 4 (N padded to one n-tile)
   {
-    const u32x4* wf[2] = {wptr(f.w5, GF::FRAGS5, 0), wptr(f.w5, GF::FRAGS5, 1)};
-    rd_ring_load<GF, 2, 5>(ring5, wf);
-    const u32x4* w1[1] = {reinterpret_cast<const u32x4*>(f.w1_bf) + lane};
+    const WTiles<2> wf = wt2(f.w5, GF::FRAGS5);
+    rd_ring_load<GF, 2, 5>(ring5, wf.p);
+    const WTiles<1> w1 = w_tiles<1>(f.w1_bf, 2 * GF::KC, 0, lane);
     u32x4 ring1[1][1][2];
-    rd_ring_load<GF, 1, 1>(ring1, w1);
+    rd_ring_load<GF, 1, 1>(ring1, w1.p);
     const Epi<2> ef = epi_load<2>(f.bias, f.gamma, f.beta, nullptr, f.isc, c0);
     const float b1 = f.w1_bias[n & 3], s1 = f.is1[n & 3];
     wave_lds_fence();
-    rd_taps<GF, 2, 0, 5, true, false, 4, 5>(y, y, vaF, wf, wf, ring5);
+    rd_taps<GF, 2, 0, 5, true, false, 4, 5>(y, y, vaF, wf.p, wf.p, ring5);
     rw_gn_mish_whole<4, 2, 2, 256, true>(y, ef.b, ef.g, ef.be, ef.is, inv_f, act_scale(f.act), [](int, int, int) { return 0.f; });
     wave_lds_fence();
     rw_store2<GF, 4>(vsF + (2 + 4 * g) * 16, y);
     wave_lds_fence();
     f32x4 out[4][1];
-    rd_taps<GF, 1, 2, 1, true, false, 4, 1>(out, out, vaF, w1, w1, ring1);
+    rd_taps<GF, 1, 2, 1, true, false, 4, 1>(out, out, vaF, w1.p, w1.p, ring1);
+    auto valid = [&] { return wave < NS && n0 + wave < a.n; };   // (a.n is read inside the branch that needs it)
     if (fs.enabled) {
-      // eps[64][4] -> the wave's slab as float4 rows, lane = support point: the unguided ddpm_sample_fn step (sample_functions.py:
-      // 40-86; ddpm_guide_kernel's arithmetic, guide_dev.h) on the wave's trajectory, in place
+      // eps[64][4] -> the wave's slab as float4 rows, then the fused step on the wave's trajectory
       float* const et = reinterpret_cast<float*>(slab);
       wave_lds_fence();                                      // (the 1x1 conv's reads of the slab are done)
-      if (n < 4) {
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) et[(16 * mt + 4 * g + r) * 4 + n] = fmaf(out[mt][0][r], s1, b1);
-      }
+      u1_eps_to_slab<4>(et, 0, n, g, out, s1, b1);
       wave_lds_fence();
-      if (wave < NS && n0 + wave < a.n) {
-        const float4 e = *reinterpret_cast<const float4*>(et + lane * 4);
-        const int traj = fs.traj0 + n0 + wave, robot = traj / fs.spr;
-        const size_t idx = (size_t)traj * H + lane;
-        float4 v = ddpm_posterior_mean(fs.x[idx], e, fs.a_t, fs.b_t, fs.c1, fs.c2);
-        if (fs.do_noise)
-          v = add_step_noise(v, fs.noise ? fs.noise[idx] : traj_normal4(fs.seed, fs.robot_seeds, fs.draw, fs.traj_base, idx, robot, fs.spr), fs.sigma,
-                             fs.noise_std_extra);
-        float4 hv;
-        if (hard_row(fs.hard_rows, fs.n_hard, fs.hard, robot, lane, hv)) v = hv;
-        fs.x[idx] = v;
-        if (fs.chain) fs.chain[idx] = v;
-      }
-    } else if (n < 4 && wave < NS && n0 + wave < a.n) {
-      float* dst = f.out + ((size_t)(n0 + wave) * 64 + 4 * g) * 4 + n;
-#pragma unroll
-      for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) dst[(16 * mt + r) * 4] = fmaf(out[mt][0][r], s1, b1);
+      if (valid()) fused_ddpm_row(fs, et, n0 + wave, lane);
+    } else if (n < 4 && valid()) {
+      u1_store_out<4>(f.out, n0 + wave, 0, n, g, out, s1, b1);
     }
   }
 }
 
 // ups.1 + final block for unet_kernel<2>: like chain_body_d0s a sample is split between two waves by position (wave = (sample sp =
 // wave >> 1, half hf = wave & 1): ONE M tile of the L = 32 convs, two of the final block's L = 64), the sample's slab is shared,
-// GroupNorm statistics / dynamic scales are exchanged through LDS.  The two input chunks arrive across waves as in
-// chain_body_u1w.  Bitwise equal results.
-template <class CF, int NV = 2>
+// GroupNorm statistics / dynamic scales are exchanged through LDS, weights are staged through LDS one conv ahead (stage_weights: two
+// buffers behind the two samples' slabs).  The two input chunks arrive across waves as in chain_body_u1w (downs.1's skip layout for
+// two trajectories has the same sample index sp, and np = hf).
+template <int NV>
 __device__ __forceinline__ void chain_body_u1s(const ChainArgs& a, const FinalArgs& f, const FusedStep& fs, float* lds, int n0, int lane_in, int wave,
                                                const f32x4 (&xe)[2][1], const f32x4 (&xo)[2][1], const f32x4 (&skip)[2][2], int trb, int tb_off = 0) {
   int lane = lane_in;
   asm volatile("" : "+v"(lane));
-  static_assert(CF::L == 32 && CF::CM == 32 && CF::C0 == 64 && CF::C1 == 64 && CF::RES0 == RES_CONV && CF::N_IDENT == 1 &&
-                    CF::TAIL == TAIL_UP, "ups.1");
-  using GA = RwGeo<64, 32>;
-  using GB = RwGeo<32, 32>;
-  using GF = RwGeo<32, 64>;
-  constexpr int W_BYTES = cmax(GA::BYTES, cmax(GB::BYTES, GF::BYTES)) + 128;   // (the geometry of chain_body_u1w: per SAMPLE here)
+  using GA = U1::GA;
+  using GB = U1::GB;
+  using GF = U1::GF;
+  constexpr int RDA = U1::RDA, TF = U1::TF;
   char* const lb = reinterpret_cast<char*>(lds);
-  const int sp = wave >> 1, hf = wave & 1;                   // (downs.1's skip layout has the same sample index: np = wave & 1 there)
-  char* const slab = lb + sp * W_BYTES;
+  const int sp = wave >> 1, hf = wave & 1;
+  char* const slab = lb + sp * U1::W_BYTES;
   float* const mx = lds + MX_OFF;
-  HalfStat* const xch = reinterpret_cast<HalfStat*>(lds + PARK2_OFF) + sp * 128;
+  const RwHalf half{reinterpret_cast<HalfStat*>(lds + PARK2_OFF) + sp * 128, hf, lane};
   const int n = lane & 15, g = lane >> 4, c0 = 2 * n;
-  const bool odd = n & 1;
-  auto wptr = [&](const uint4* w, int frags, int t) { return reinterpret_cast<const u32x4*>(w) + (size_t)t * frags * 64 + lane; };
-  auto swap1 = [](float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xf, 0xf, true));
-  };
-  auto sample_max = [&](float own) {
-    if (lane < 4) mx[sp * MX_SLOTS + 4 * hf + lane] = own;
-    __syncthreads();
-    return mx_read(mx, sp);
-  };
-  const u32x4* wp0[2] = {wptr(a.r0.wa_bf, GA::FRAGS5, 0), wptr(a.r0.wa_bf, GA::FRAGS5, 1)};
-  const u32x4* wp1[2] = {wptr(a.wa0_c1_bf, GA::FRAGS5, 0), wptr(a.wa0_c1_bf, GA::FRAGS5, 1)};
-  const u32x4* wr0[2] = {wptr(a.wres_bf, 2 * GA::KC, 0), wptr(a.wres_bf, 2 * GA::KC, 1)};
-  const u32x4* wr1[2] = {wptr(a.wres_c1_bf, 2 * GA::KC, 0), wptr(a.wres_c1_bf, 2 * GA::KC, 1)};
-  constexpr int RDA = 5;
+  auto wt2 = [&](const void* w, int frags) { return w_tiles<2>(w, frags, 0, lane); };
+  const WTiles<2> wp0 = wt2(a.r0.wa_bf, GA::FRAGS5), wp1 = wt2(a.wa0_c1_bf, GA::FRAGS5);
+  const WTiles<2> wr0 = wt2(a.wres_bf, 2 * GA::KC), wr1 = wt2(a.wres_c1_bf, 2 * GA::KC);
   u32x4 ring[RDA][2][2];
-  rd_ring_load<GA, 2, RDA>(ring, wp0);
-  // ---- the skip tensor's per-sample maxima (downs.1's layout for two trajectories: wave = (channel half np = wave & 1, sample wave >> 1),
-  //      skip[m][t][r]: M tile m of the sample) -> slots 4 .. 7 of mx region 0; ups.0 left its output's maxima in slots 0 .. 3
-  {
-    float m = 0.f;
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-      for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) m = fmaxf(m, fabsf(skip[mt][t][r]));
-    m = row_max16(m);
-    m = max_xor16(m);
-    m = max_xor32(m);
-    if (lane < 2) mx[sp * MX_SLOTS + 4 + hf + 2 * lane] = m;
-  }
+  rd_ring_load<GA, 2, RDA>(ring, wp0.p);
+  // ---- the skip tensor's per-sample maxima -> slots 4 .. 7 of mx region 0; ups.0 left its output's maxima in slots 0 .. 3
+  pair_maxima_out<2, 4>(skip, mx, wave, lane);
   __syncthreads();                                           // ups.0 is done with its slabs; the maxima are in mx
   TR(trb + 0);
-  // staged weights (stage_weights above): two buffers behind the two samples' slabs; RTB 0's conv B lands while conv A runs
-  char* const wb0 = lb + 2 * W_BYTES;
+  char* const wb0 = lb + 2 * U1::W_BYTES;
   char* const wb1 = wb0 + WBUF_BYTES;
-  static_assert(2 * W_BYTES + 2 * WBUF_BYTES <= MX_OFF * 4, "slabs + weight buffers below the maxima");
-  static_assert(GB::FRAGS5 * 2 * 1024 <= WBUF_BYTES && GF::FRAGS5 * 2 * 1024 <= WBUF_BYTES, "a staged conv fits its buffer");
-  stage_weights<2 * GB::FRAGS5>(a.r0.wb_bf, wb0, wave, lane);
-  float sc[2];
-#pragma unroll
-  for (int sm = 0; sm < 2; ++sm) sc[sm] = dyn_scale(mx_read(mx, sm)).s;
-  const float inv_in = dyn_scale(mx_read(mx, sp)).inv;
-  const float sc_own = dyn_scale(mx_read(mx, sp)).s;
-  char* const cdst = lb + wave * GA::G + (n >> 3) * GA::BX + ((n & 7) >> 1) * 4 + 2 * 16;
-  {
-    // zero halo rows 0, 1, 34, 35 of the sample's slab (8 blocks x 2 pieces): one wave per sample
-    if (hf == 0) {
-      const int hr = lane & 3;
-      *reinterpret_cast<uint4*>(slab + (lane >> 5) * GA::PS + ((lane >> 3) & 3) * GA::G + ((lane >> 2) & 1) * GA::BX +
-                                (hr < 2 ? hr : 32 + hr) * 16) = make_uint4(0u, 0u, 0u, 0u);
-    }
-    // chunk 0 = ups.0's output (wave w holds channels 16 w + n of both samples): as in chain_body_u1w
-    char* const d0 = cdst + (8 * g + (odd ? 1 : 0)) * 16;
-#pragma unroll
-    for (int sm = 0; sm < 2; ++sm)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const float own = (odd ? xo[sm][0][r] : xe[sm][0][r]) * sc[sm];
-        const float recv = swap1((odd ? xe[sm][0][r] : xo[sm][0][r]) * sc[sm]);
-        const F16Pair p = f16_split2(odd ? recv : own, odd ? own : recv);
-        char* d = d0 + sm * W_BYTES + 2 * r * 16;
-        *reinterpret_cast<unsigned*>(d) = p.hi;
-        *reinterpret_cast<unsigned*>(d + GA::PS) = p.lo;
-      }
-  }
+  stage_weights<2 * GB::FRAGS5>(a.r0.wb_bf, wb0, wave, lane);     // RTB 0's conv B lands while conv A runs
+  const U1Scales<2> sc = u1_input_scales<2>(mx, wave);
+  const float inv_in = sc.skip[0].inv;                       // (the wave's sample is the one whose skip tiles it holds)
+  rw_zero_halo<GA>(slab, 32, lane, hf == 0);                 // (the sample's slab, 8 blocks x 2 pieces: one wave per sample)
+  u1_store_chunk0(lb, wave, n, g, xe, xo, sc.sc);
   TR(trb + 6);
   __syncthreads();
   TR(trb + 7);
   const char* const vaA = slab + g * GA::G + (n + 16 * hf) * 16;
   f32x4 acc[1][2], res[1][2];
-  rd_taps<GA, 2, 0, 5, true, true, 1, RDA>(acc, res, vaA, wp0, wr0, ring);
-  rd_ring_load<GA, 2, RDA>(ring, wp1);
+  rd_taps<GA, 2, 0, 5, true, true, 1, RDA>(acc, res, vaA, wp0.p, wr0.p, ring);
+  rd_ring_load<GA, 2, RDA>(ring, wp1.p);
   TR(trb + 8);
   __syncthreads();                                           // every wave has consumed chunk 0
-  {
-    // chunk 1 = skip (downs.1's layout: this wave holds channel pair (32 np + 2 n, + 1), np = wave & 1, of sample sp, both M tiles)
-    const int np = hf;
-    char* const sdst = lb + (2 * np + (n >> 3)) * GA::G + ((n >> 2) & 1) * GA::BX + (n & 3) * 4 + (2 + 4 * g) * 16 + sp * W_BYTES;
-#pragma unroll
-    for (int m = 0; m < 2; ++m)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const F16Pair p = f16_split2(skip[m][0][r] * sc_own, skip[m][1][r] * sc_own);
-        char* d = sdst + (16 * m + r) * 16;
-        *reinterpret_cast<unsigned*>(d) = p.hi;
-        *reinterpret_cast<unsigned*>(d + GA::PS) = p.lo;
-      }
-  }
+  u1_store_chunk1(lb, wave, n, g, skip, sc.skip);
   __syncthreads();
   TR(trb + 10);
-  const Epi<2> e0a = epi_load<2>(a.r0.ba, a.r0.ga, a.r0.bea, a.r0.tb + tb_off, a.r0.isa, c0);
+  const Epi<2> e0a = epi_a<2>(a.r0, tb_off, c0);
   const float br[2] = {a.br[c0], a.br[c0 + 1]}, isr[2] = {a.isr[c0], a.isr[c0 + 1]};
-  rd_taps<GA, 2, 0, 5, false, true, 1, RDA>(acc, res, vaA, wp1, wr1, ring);
+  rd_taps<GA, 2, 0, 5, false, true, 1, RDA>(acc, res, vaA, wp1.p, wr1.p, ring);
   TR(trb + 11);
   // ---- 32-channel slab of the sample, shared by its two waves
   const char* const vaB = slab + g * GB::G + (n + 16 * hf) * 16;
   char* const vsB = slab + (n >> 2) * GB::G + (2 + 4 * g + 16 * hf) * 16 + (n & 3) * 4;
   u32x4 ring2[2][2][2];
-  const float one = 1.f;
-  auto epi = [&](const float* bs, const float* gm, const float* be, const float* tb, const float* isc) {
-    return epi_load<2>(bs, gm, be, tb, isc, c0);
-  };
-  auto gn = [&](auto conv_a, const Epi<2>& e, float inv, float act_s) {
-    if constexpr (decltype(conv_a)::value) {
-      const float t0 = e.tb[0] * act_s, t1 = e.tb[1] * act_s;
-      rw_gn_mish_half<1, 2, 2, 128, true>(acc, e.b, e.g, e.be, e.is, inv, act_scale(act_s), [&](int, int t, int) { return t ? t1 : t0; }, xch, hf, lane);
-    } else {
-      rw_gn_mish_half<1, 2, 2, 128, false>(acc, e.b, e.g, e.be, e.is, inv, ActScale{}, [&](int mt, int t, int r) { return res[mt][t][r]; }, xch, hf, lane);
-    }
-  };
   // one 32 -> 32 conv over the half tile in acc (already scaled), its weights staged in wb; `stage_next` puts the next conv's on
   // their way behind the barrier (every wave is past the conv that read the other buffer)
   auto conv = [&](char* wb, auto stage_next) {
-    const u32x4* wp[2] = {reinterpret_cast<const u32x4*>(wb) + lane, reinterpret_cast<const u32x4*>(wb) + GB::FRAGS5 * 64 + lane};
+    const WTiles<2> wp = wt2(wb, GB::FRAGS5);
     rw_store2<GB, 1>(vsB, acc);
     staged_weights_landed();
     __syncthreads();
     stage_next();
-    rd_ring_load<GB, 2, 2>(ring2, wp);
-    rd_taps<GB, 2, 0, 5, true, false, 1, 2>(acc, res, vaB, wp, wp, ring2);
+    rd_ring_load<GB, 2, 2>(ring2, wp.p);
+    rd_taps<GB, 2, 0, 5, true, false, 1, 2>(acc, res, vaB, wp.p, wp.p, ring2);
   };
-  constexpr int TF = 2 * (2 * GB::KC * 2);                   // fragments of one parity pass of the transposed tail (both n-tiles)
-#pragma unroll
-  for (int t = 0; t < 2; ++t) res[0][t] = res[0][t] * (isr[t] * inv_in) + br[t];
-  gn(std::true_type{}, e0a, inv_in, a.r0.act_a);             // (its barrier: conv A's reads are done, the slab changes its geometry)
+  tile_finish_res(res, isr, inv_in, br);
+  rw_gn<2, 128>(acc, e0a, inv_in, a.r0.act_a, half);         // (its barrier: conv A's reads are done, the slab changes its geometry)
   TR(trb + 1);
-  if (hf == 0 && lane < 32) *reinterpret_cast<uint4*>(slab + (lane >> 4) * GB::PS + ((lane >> 2) & 3) * GB::G + ((lane & 3) < 2 ? (lane & 3) : 32 + (lane & 3)) * 16) = make_uint4(0u, 0u, 0u, 0u);
+  rw_zero_halo<GB>(slab, 32, lane, hf == 0);
   {
-    const Epi<2> e = epi(a.r0.bb, a.r0.gb, a.r0.beb, nullptr, a.r0.isb);
+    const Epi<2> e = epi_b<2>(a.r0, c0);
     conv(wb0, [&] { stage_weights<2 * GB::FRAGS5>(a.ri[0].wa_bf, wb1, wave, lane); });
-    gn(std::false_type{}, e, one, 1.f);
+    rw_gn<2, 128>(acc, e, 1.f, res, half);
   }
   TR(trb + 2);
   // ---- identity RTB
   {
     const RtbPtrs& R = a.ri[0];
-#pragma unroll
-    for (int t = 0; t < 2; ++t) res[0][t] = acc[0][t];
-    const DynScale ds = dyn_scale(sample_max(rw_absmax<1, 2>(acc)));
-#pragma unroll
-    for (int t = 0; t < 2; ++t) acc[0][t] *= ds.s;
-    const Epi<2> ea = epi(R.ba, R.ga, R.bea, R.tb + tb_off, R.isa);
+    tile_copy(res, acc);
+    const DynScale ds = dyn_scale(half_sample_max(mx, sp, hf, lane, rw_absmax(acc)));
+    tile_scale(acc, ds.s);
+    const Epi<2> ea = epi_a<2>(R, tb_off, c0);
     conv(wb1, [&] { stage_weights<2 * GB::FRAGS5>(R.wb_bf, wb0, wave, lane); });
-    gn(std::true_type{}, ea, ds.inv, R.act_a);
+    rw_gn<2, 128>(acc, ea, ds.inv, R.act_a, half);
     TR(trb + 3);
-    const Epi<2> eb = epi(R.bb, R.gb, R.beb, nullptr, R.isb);
+    const Epi<2> eb = epi_b<2>(R, c0);
     conv(wb0, [&] {                                          // the tail's two parity passes
       stage_weights<TF>(a.wt_bf0, wb1, wave, lane);
       stage_weights<TF>(a.wt_bf1, wb1 + TF * 1024, wave, lane);
     });
-    gn(std::false_type{}, eb, one, 1.f);
+    rw_gn<2, 128>(acc, eb, 1.f, res, half);
     TR(trb + 4);
   }
   // ---- tail: Upsample1d as two parity passes -> the final block's input (L = 64), the half's rows of the 64-row slab
@@ -2150,13 +1961,9 @@ __device__ __forceinline__ void chain_body_u1s(const ChainArgs& a, const FinalAr
   f32x4 y[2][2];
   float inv_f;
   {
-    const DynScale ds = dyn_scale(sample_max(rw_absmax<1, 2>(acc)));
-#pragma unroll
-    for (int t = 0; t < 2; ++t) acc[0][t] *= ds.s;
-    const u32x4* const t0 = reinterpret_cast<const u32x4*>(wb1) + lane;
-    const u32x4* const t1 = reinterpret_cast<const u32x4*>(wb1 + TF * 1024) + lane;
-    const u32x4* wt0[2] = {t0, t0 + (TF / 2) * 64};
-    const u32x4* wt1[2] = {t1, t1 + (TF / 2) * 64};
+    const DynScale ds = dyn_scale(half_sample_max(mx, sp, hf, lane, rw_absmax(acc)));
+    tile_scale(acc, ds.s);
+    const WTiles<2> wt0 = wt2(wb1, TF / 2), wt1 = wt2(wb1 + TF * 1024, TF / 2);
     const float bt[2] = {a.bt[c0], a.bt[c0 + 1]};
     const float is0[2] = {a.ist0[c0] * ds.inv, a.ist0[c0 + 1] * ds.inv}, is1[2] = {a.ist1[c0] * ds.inv, a.ist1[c0 + 1] * ds.inv};
     rw_store2<GB, 1>(vsB, acc);
@@ -2164,87 +1971,47 @@ __device__ __forceinline__ void chain_body_u1s(const ChainArgs& a, const FinalAr
     __syncthreads();
     stage_weights<2 * GF::FRAGS5>(f.w5, wb0, wave, lane);    // the final block's k5 conv
     f32x4 e[1][2], o[1][2];
-    rd_ring_load<GB, 2, 2>(ring2, wt0);
-    rd_taps<GB, 2, 1, 2, true, false, 1, 2>(e, res, vaB, wt0, wt0, ring2);
-    rd_ring_load<GB, 2, 2>(ring2, wt1);
-    rd_taps<GB, 2, 2, 2, true, false, 1, 2>(o, res, vaB, wt1, wt1, ring2);
-    float m = 0.f;
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        e[0][t][r] = fmaf(e[0][t][r], is0[t], bt[t]);
-        o[0][t][r] = fmaf(o[0][t][r], is1[t], bt[t]);
-        m = fmaxf(m, fmaxf(fabsf(e[0][t][r]), fabsf(o[0][t][r])));
-      }
-    m = row_max16(m);
-    m = max_xor16(m);
-    m = max_xor32(m);
-    const DynScale df = dyn_scale(sample_max(m));            // (its barrier: the tail's reads are done, 64-row geometry)
+    rd_ring_load<GB, 2, 2>(ring2, wt0.p);
+    rd_taps<GB, 2, 1, 2, true, false, 1, 2>(e, res, vaB, wt0.p, wt0.p, ring2);
+    rd_ring_load<GB, 2, 2>(ring2, wt1.p);
+    rd_taps<GB, 2, 2, 2, true, false, 1, 2>(o, res, vaB, wt1.p, wt1.p, ring2);
+    const float m = tail_up_epilogue(e, o, is0, is1, bt);
+    const DynScale df = dyn_scale(half_sample_max(mx, sp, hf, lane, m));   // (its barrier: the tail's reads are done, 64-row geometry)
     inv_f = df.inv;
-    if (hf == 0 && lane < 32) *reinterpret_cast<uint4*>(slab + (lane >> 4) * GF::PS + ((lane >> 2) & 3) * GF::G + ((lane & 3) < 2 ? (lane & 3) : 64 + (lane & 3)) * 16) = make_uint4(0u, 0u, 0u, 0u);
-    // positions 2 m + parity, m = 16 hf + 4 g + r: rows 2 + 32 hf + 8 g + 2 r + parity
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const F16Pair pe = f16_split2(e[0][0][r] * df.s, e[0][1][r] * df.s), po = f16_split2(o[0][0][r] * df.s, o[0][1][r] * df.s);
-      char* d = vsF + (2 + 32 * hf + 8 * g + 2 * r) * 16;
-      *reinterpret_cast<unsigned*>(d) = pe.hi;
-      *reinterpret_cast<unsigned*>(d + GF::PS) = pe.lo;
-      *reinterpret_cast<unsigned*>(d + 16) = po.hi;
-      *reinterpret_cast<unsigned*>(d + 16 + GF::PS) = po.lo;
-    }
+    rw_zero_halo<GF>(slab, 64, lane, hf == 0);
+    u1_tail_store<1>(vsF, hf, g, e, o, df.s);
   }
   TR(trb + 5);
   // ---- final block: Conv1dBlock(32 -> 32, k5) + GroupNorm + Mish, then the 1x1 conv 32 -> 4, on the half's two M tiles
   {
-    const u32x4* wf[2] = {reinterpret_cast<const u32x4*>(wb0) + lane, reinterpret_cast<const u32x4*>(wb0) + GF::FRAGS5 * 64 + lane};
-    const u32x4* w1[1] = {reinterpret_cast<const u32x4*>(f.w1_bf) + lane};
+    const WTiles<2> wf = wt2(wb0, GF::FRAGS5);
+    const WTiles<1> w1 = w_tiles<1>(f.w1_bf, 2 * GF::KC, 0, lane);
     u32x4 ring1[1][1][2];
-    rd_ring_load<GF, 1, 1>(ring1, w1);
+    rd_ring_load<GF, 1, 1>(ring1, w1.p);
     const Epi<2> ef = epi_load<2>(f.bias, f.gamma, f.beta, nullptr, f.isc, c0);
     const float b1 = f.w1_bias[n & 3], s1 = f.is1[n & 3];
     staged_weights_landed();
     __syncthreads();                                         // the final block's input and weights are complete
-    rd_ring_load<GF, 2, 2>(ring2, wf);
-    rd_taps<GF, 2, 0, 5, true, false, 2, 2>(y, y, vaF, wf, wf, ring2);
-    rw_gn_mish_half<2, 2, 2, 256, true>(y, ef.b, ef.g, ef.be, ef.is, inv_f, act_scale(f.act), [](int, int, int) { return 0.f; }, xch, hf, lane);
+    rd_ring_load<GF, 2, 2>(ring2, wf.p);
+    rd_taps<GF, 2, 0, 5, true, false, 2, 2>(y, y, vaF, wf.p, wf.p, ring2);
+    rw_gn_mish_half<2, 2, 2, 256, true>(y, ef.b, ef.g, ef.be, ef.is, inv_f, act_scale(f.act), [](int, int, int) { return 0.f; }, half.xch, hf, lane);
     // (the exchange's barrier: the partner is past its taps, the slab may be overwritten; the 1x1 conv reads only the centre
     // tap = the wave's own rows)
     rw_store2<GF, 2>(vsF + (2 + 4 * g + 32 * hf) * 16, y);
     wave_lds_fence();
     f32x4 out[2][1];
-    rd_taps<GF, 1, 2, 1, true, false, 2, 1>(out, out, vaF, w1, w1, ring1);
+    rd_taps<GF, 1, 2, 1, true, false, 2, 1>(out, out, vaF, w1.p, w1.p, ring1);
+    auto valid = [&] { return sp < NV && n0 + sp < a.n; };
     if (fs.enabled) {
-      // eps[64][4] -> the sample's slab as float4 rows (both waves their halves), then the unguided ddpm_sample_fn step on the
-      // trajectory by the sample's first wave, lane = support point (chain_body_u1w)
+      // eps[64][4] -> the sample's slab as float4 rows (both waves their halves), then the fused step on the trajectory by the sample's
+      // first wave
       float* const et = reinterpret_cast<float*>(slab);
       __syncthreads();                                       // (both waves' 1x1 reads of the slab are done)
-      if (n < 4) {
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) et[(32 * hf + 16 * mt + 4 * g + r) * 4 + n] = fmaf(out[mt][0][r], s1, b1);
-      }
+      u1_eps_to_slab<2>(et, 2 * hf, n, g, out, s1, b1);
       __syncthreads();
-      if (hf == 0 && sp < NV && n0 + sp < a.n) {
-        const float4 e = *reinterpret_cast<const float4*>(et + lane * 4);
-        const int traj = fs.traj0 + n0 + sp, robot = traj / fs.spr;
-        const size_t idx = (size_t)traj * H + lane;
-        float4 v = ddpm_posterior_mean(fs.x[idx], e, fs.a_t, fs.b_t, fs.c1, fs.c2);
-        if (fs.do_noise)
-          v = add_step_noise(v, fs.noise ? fs.noise[idx] : traj_normal4(fs.seed, fs.robot_seeds, fs.draw, fs.traj_base, idx, robot, fs.spr), fs.sigma,
-                             fs.noise_std_extra);
-        float4 hv;
-        if (hard_row(fs.hard_rows, fs.n_hard, fs.hard, robot, lane, hv)) v = hv;
-        fs.x[idx] = v;
-        if (fs.chain) fs.chain[idx] = v;
-      }
-    } else if (n < 4 && sp < NV && n0 + sp < a.n) {
-      float* dst = f.out + ((size_t)(n0 + sp) * 64 + 32 * hf + 4 * g) * 4 + n;
-#pragma unroll
-      for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) dst[(16 * mt + r) * 4] = fmaf(out[mt][0][r], s1, b1);
+      if (hf == 0 && valid()) fused_ddpm_row(fs, et, n0 + sp, lane);
+    } else if (n < 4 && valid()) {
+      u1_store_out<2>(f.out, n0 + sp, 2 * hf, n, g, out, s1, b1);
     }
   }
 }
@@ -2261,82 +2028,52 @@ struct UnetArgs {
   FusedStep fs;           // enabled: the unguided DDPM step on the launch's trajectories follows in the same kernel
 };
 
-static_assert(CH_D0::SPB == 4 && CH_D1::SPB == 4 && CH_D2::SPB == 4 && CH_U0::SPB == 4 && CH_U1::SPB == 4,
-              "every stage must own the same 4 samples");
-
 // NS = trajectories per workgroup.  4: the form everything above is written for.  2 (launched for small batches, which leave
 // most CUs without a workgroup otherwise: twice the workgroups): only samples 0, 1 exist -- the L = 16 stages (downs.2 + mid,
 // ups.0: 3/4 of the matrix work, waves = channel slices x ALL samples) run over two samples, i.e. half the MFMAs, A reads,
-// epilogue and parking per wave for the same weight stream, and downs.1's waves (n-tile pair x sample PAIR) take one sample each,
-// while the stages whose waves ARE samples (downs.0, ups.1 + final block) keep their form with samples 2, 3 fed zeros and
-// never stored.  Per-sample arithmetic is the same
-// instruction sequence either way: the results are bitwise equal.
+// epilogue and parking per wave for the same weight stream, downs.1's waves (n-tile pair x sample PAIR) take one sample each,
+// and the stages whose waves ARE samples at NS = 4 (downs.0, ups.1 + final block) split a sample between two waves (chain_body_d0s /
+// u1s).  Per-sample arithmetic is the same instruction sequence either way: the results are bitwise equal.
 // tb_off: added to every RTB's time-bias pointer (floats) -- 0 in unet_kernel, whose host side bakes the step's row of the time
 // table into the pointers; t * tb_total in the persistent kernel, whose pointers are those of row 0
-// One trajectory per workgroup (unet_kernel<1>, launches of <= ns1_max = 256 trajectories -- one workgroup per CU at most; ONE planner
-// call has 64): the L = 16 stages
-// (downs.2 + mid, ups.0: their waves are channel slices x all samples) run ONE M tile per conv -- the conv's time there is the weight
+// 1 (unet_kernel<1>, launches of <= ns1_max = 256 trajectories -- one workgroup per CU at most; ONE planner call has 64): the L = 16 stages
+// run ONE M tile per conv -- the conv's time there is the weight
 // stream plus what the samples' MFMAs, A-fragment reads and epilogues add to it: 3.15 -> 2.7 us per 128 -> 128 conv at <= 64 workgroups
 // (tools/ubench/pair_split.hip, arms basePF / base1PF) -- while the stages whose waves are sample halves or n-tile pairs x samples
-// (downs.0, downs.1, ups.1 + final block) keep the two-trajectory form with sample 1 fed zeros and never stored.  A sample's
-// arithmetic is the same instruction sequence: bitwise the results of unet_kernel<2> / <4>.
-__device__ __forceinline__ void unet_forward_body1(const UnetArgs& a, const FusedStep& fs, int tb_off, float* lds, int n0, int lane, int wave) {
-  f32x4 skip1[2][2], skip2[1][2], mid_out[1][2], xe[2][1], xo[2][1];
-#pragma unroll
-  for (int r = 0; r < 4; ++r) xe[1][0][r] = xo[1][0][r] = 0.f;
-  chain_body_d0s<CH_D0, 1>(a.c[0], lds, n0, lane, wave, 0, tb_off);
-  chain_body_d1d<CH_D1, CH_D2, 2>(a.c[1], lds, lane, wave, skip1, 40, tb_off);
-  chain_body_d2d<CH_D2, 1>(a.c[2], lds, lane, wave, mid_out, skip2, 80, tb_off);
-  TR(130);
-  {
-    using G128 = RdGeo<128>;
-    constexpr int S_OFF = (CH_D2::SPB * CH_D2::XSS * 4 + 255) / 256 * 256;
-    char* const slab128 = reinterpret_cast<char*>(lds) + S_OFF;
-    char* const vs = slab128 + wave * G128::G + ((lane & 15) >> 2) * G128::BX + (2 + 4 * (lane >> 4)) * 16 + (lane & 3) * 4;
-    chain_body_u0d<CH_U0, 1>(a.c[3], lds, lane, wave, mid_out, skip2, [&](const f32x4 (&t)[1][2]) { rd_store2<G128>(vs, t); }, slab128,
-                             reinterpret_cast<f32x4(&)[1][1]>(xe), reinterpret_cast<f32x4(&)[1][1]>(xo), 136, tb_off);
-  }
-  TR(131);
-  chain_body_u1s<CH_U1, 1>(a.c[4], a.fin, fs, lds, n0, lane, wave, xe, xo, skip1, 146, tb_off);
-  TR(133);
-}
-
+// (downs.0, downs.1, ups.1 + final block) keep the two-trajectory form (NP = 2 below) with sample 1 fed zeros and never stored.  A
+// sample's arithmetic is the same instruction sequence: bitwise the results of unet_kernel<2> / <4>.
 template <int NS>
 __device__ __forceinline__ void unet_forward_body(const UnetArgs& a, const FusedStep& fs, int tb_off, float* lds, int n0, int lane, int wave) {
-  f32x4 skip1[NS][2], skip2[NS][2];
-  // ---- downs.0 @ L=64 -> [4][32][32]: wave = sample, direct f16x2 convs on the wave's own slab (chain_body_d0w)
-  if constexpr (NS == 2) chain_body_d0s<CH_D0>(a.c[0], lds, n0, lane, wave, 0, tb_off);
-  else chain_body_d0w<CH_D0, NS>(a.c[0], lds, n0, lane, wave, 0, tb_off);
+  constexpr int NP = NS == 1 ? 2 : NS;                       // samples of downs.0, downs.1 and ups.1 + final block
+  f32x4 skip1[NP][2], skip2[NS][2], xe[NP][1], xo[NP][1];
+  if constexpr (NS == 1) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) xe[1][0][r] = xo[1][0][r] = 0.f;
+  }
+  // ---- downs.0 @ L=64 -> [4][32][32]: direct f16x2 convs on per-sample slabs, wave = sample or half a sample
+  if constexpr (NS <= 2) chain_body_d0s<NS>(a.c[0], lds, n0, lane, wave, 0, tb_off);
+  else chain_body_d0w<NS>(a.c[0], lds, n0, lane, wave, 0, tb_off);
   // ---- downs.1 @ L=32 -> [4][16][64], skip1: direct f16x2 convs, wave = (n-tile pair, sample pair) (chain_body_d1d)
-  chain_body_d1d<CH_D1, CH_D2, NS>(a.c[1], lds, lane, wave, skip1, 40, tb_off);
+  chain_body_d1d<NP>(a.c[1], lds, lane, wave, skip1, 40, tb_off);
   // ---- downs.2 + mid blocks @ L=16 -> [NS][16][128], skip2: direct f16x2 convs (chain_body_d2d; lane = channels 32 wave + 2
   //      (lane & 15) + h, positions 4 (lane >> 4) + r of all NS samples)
   f32x4 mid_out[NS][2];
-  chain_body_d2d<CH_D2, NS>(a.c[2], lds, lane, wave, mid_out, skip2, 80, tb_off);
+  chain_body_d2d<NS>(a.c[2], lds, lane, wave, mid_out, skip2, 80, tb_off);
   TR(130);
   // ---- ups.0 @ L=16: cat(x, skip2) -> [NS][32][64] (chain_body_u0d; the chunks are stored from downs.2's tiles); its output
   //      stays in registers (even / odd positions of channel 16 wave + (lane & 15))
-  f32x4 xe[NS][1], xo[NS][1];
   {
     using G128 = RdGeo<128>;
-    constexpr int S_OFF = (CH_D2::SPB * CH_D2::XSS * 4 + 255) / 256 * 256;
-    char* const slab128 = reinterpret_cast<char*>(lds) + S_OFF;
+    char* const slab128 = reinterpret_cast<char*>(lds) + D2::SLAB_OFF;
     char* const vs = slab128 + wave * G128::G + ((lane & 15) >> 2) * G128::BX + (2 + 4 * (lane >> 4)) * 16 + (lane & 3) * 4;
-    chain_body_u0d<CH_U0, NS>(a.c[3], lds, lane, wave, mid_out, skip2, [&](const f32x4 (&t)[NS][2]) { rd_store2<G128>(vs, t); },
-                              slab128, xe, xo, 136, tb_off);
+    chain_body_u0d<NS>(a.c[3], lds, lane, wave, mid_out, skip2, [&](const f32x4 (&t)[NS][2]) { rd_store2<G128>(vs, t); }, slab128,
+                       sub_tile<NS>(xe, 0), sub_tile<NS>(xo, 0), 136, tb_off);
   }
   TR(131);
-  // ---- ups.1 @ L=32: cat(x, skip1) -> [4][64][32], final_conv: Conv1dBlock(32->32) -> 1x1 conv (32->4) -> eps[n,64,4]:
-  //      wave = sample (chain_body_u1w)
-  if constexpr (NS == 2) chain_body_u1s<CH_U1>(a.c[4], a.fin, fs, lds, n0, lane, wave, xe, xo, skip1, 146, tb_off);
-  else chain_body_u1w<CH_U1, NS>(a.c[4], a.fin, fs, lds, n0, lane, wave, xe, xo, skip1, 146, tb_off);
+  // ---- ups.1 @ L=32: cat(x, skip1) -> [4][64][32], final_conv: Conv1dBlock(32->32) -> 1x1 conv (32->4) -> eps[n,64,4]
+  if constexpr (NS <= 2) chain_body_u1s<NS>(a.c[4], a.fin, fs, lds, n0, lane, wave, xe, xo, skip1, 146, tb_off);
+  else chain_body_u1w<NS>(a.c[4], a.fin, fs, lds, n0, lane, wave, xe, xo, skip1, 146, tb_off);
   TR(133);
-}
-
-template <int NS>
-__device__ __forceinline__ void unet_forward_any(const UnetArgs& a, const FusedStep& fs, int tb_off, float* lds, int n0, int lane, int wave) {
-  if constexpr (NS == 1) unet_forward_body1(a, fs, tb_off, lds, n0, lane, wave);
-  else unet_forward_body<NS>(a, fs, tb_off, lds, n0, lane, wave);
 }
 
 template <int NS>
@@ -2344,7 +2081,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   __shared__ __attribute__((aligned(16))) float lds[UNET_LDS_FLOATS];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  unet_forward_any<NS>(a, a.fs, 0, lds, blockIdx.x * NS, lane, wave);
+  unet_forward_body<NS>(a, a.fs, 0, lds, blockIdx.x * NS, lane, wave);
 }
 
 // A RUN of consecutive unguided DDPM steps in ONE launch (mmd_p_sample_loop: the steps before guidance starts, or every step of a

@@ -3,10 +3,17 @@
 
     python tools/device_asm.py OUT_DIR [TREE]     # TREE: the checkout to compile, default this one
     diff -r OUT_DIR_OF_ONE_TREE OUT_DIR_OF_THE_OTHER
+    python tools/device_asm.py --compare DIR_A DIR_B
 
 Each of __graft_entry__.SOURCES is compiled with the library build's flags plus --offload-device-only -S into OUT_DIR/<name>.s.  The
 compilation-unit id (__hip_cuid_<16 hex digits>) is the only text in the output that depends on the file's path and content hash; it is
-replaced by a constant, so a refactor that moves no device code leaves every file identical."""
+replaced by a constant, so a refactor that moves no device code leaves every file identical.
+
+--compare is for a refactor of the device code itself, where inlining order moves the scheduler and the register allocator and the files
+cannot stay identical.  It reads the .s files of two earlier runs and prints, per kernel, the resources of both sides and every mnemonic
+whose count differs.  Exit status 1 if side B, for any kernel, has more VGPRs, any scratch, a different LDS size or occupancy, or a
+different count of a work-defining mnemonic (WORK below: matrix, LDS, memory, scalar loads, barriers, lane permutes, transcendentals).  Other
+VALU / SALU counts (address arithmetic, register copies, s_nop, s_waitcnt) are printed only: time on the GPU judges those."""
 import os
 import re
 import subprocess
@@ -25,7 +32,65 @@ def device_asm(tree, src):
     return re.sub(r"__hip_cuid_[0-9a-f]{16}", "__hip_cuid_0", r.stdout)
 
 
+RESOURCES = ("NumVgprs", "TotalNumSgprs", "ScratchSize", "LDSByteSize", "Occupancy", "codeLenInByte")
+WORK = re.compile(r"v_mfma_|ds_|global_|buffer_|flat_|s_load_|s_barrier$|v_permlane|v_exp_|v_log_|v_rcp_|v_rsq_")
+
+
+def kernels(path):
+    """{kernel: (resources, mnemonic counts)} of one .s file: the instructions between a function's label and its .Lfunc_end, the
+    figures from the '; Kernel info:' comments behind it"""
+    out, name, counts = {}, None, None
+    for line in open(path):
+        m = re.match(r"\s+\.type\s+(\S+),@function", line)
+        if m:
+            name, counts = m.group(1), {}
+            out[name] = ({}, counts)
+        elif name and line.startswith(".Lfunc_end"):
+            counts = None
+        elif name and counts is not None and re.match(r"\t[a-z]\w*(\s|$)", line):
+            op = line.split()[0]
+            counts[op] = counts.get(op, 0) + 1
+        elif name and line.startswith("; "):
+            m = re.match(r"; (\w+)(?::| =) (\d+)", line)
+            if m and m.group(1) in RESOURCES:
+                out[name][0].setdefault(m.group(1), int(m.group(2)))
+    return {k: v for k, v in out.items() if "NumVgprs" in v[0]}
+
+
+def compare(dir_a, dir_b):
+    bad = []
+    for f in sorted(set(os.listdir(dir_a)) | set(os.listdir(dir_b))):
+        if not f.endswith(".s"):
+            continue
+        if not (os.path.exists(os.path.join(dir_a, f)) and os.path.exists(os.path.join(dir_b, f))):
+            bad.append(f"{f}: on one side only")
+            continue
+        if open(os.path.join(dir_a, f)).read() == open(os.path.join(dir_b, f)).read():
+            print(f"{f}: identical")
+            continue
+        ka, kb = kernels(os.path.join(dir_a, f)), kernels(os.path.join(dir_b, f))
+        for k in sorted(set(ka) | set(kb)):
+            if k not in ka or k not in kb:
+                bad.append(f"{f} {k}: on one side only")
+                continue
+            (ra, ca), (rb, cb) = ka[k], kb[k]
+            print(f"{f} {k}\n    " + "  ".join(f"{r} {ra.get(r)} -> {rb.get(r)}" for r in RESOURCES))
+            if rb["NumVgprs"] > ra["NumVgprs"] or rb["ScratchSize"] or any(ra[r] != rb[r] for r in ("LDSByteSize", "Occupancy")):
+                bad.append(f"{f} {k}: resources")
+            for op in sorted(set(ca) | set(cb)):
+                if ca.get(op, 0) != cb.get(op, 0):
+                    work = bool(WORK.match(op))
+                    print(f"    {op} {ca.get(op, 0)} -> {cb.get(op, 0)}" + ("   WORK-DEFINING" if work else ""))
+                    if work:
+                        bad.append(f"{f} {k}: {op} {ca.get(op, 0)} -> {cb.get(op, 0)}")
+    for b in bad:
+        print("FAIL", b)
+    return 1 if bad else 0
+
+
 def main():
+    if len(sys.argv) == 4 and sys.argv[1] == "--compare":
+        sys.exit(compare(sys.argv[2], sys.argv[3]))
     if len(sys.argv) not in (2, 3):
         sys.exit(__doc__)
     out, tree = os.path.abspath(sys.argv[1]), os.path.abspath(sys.argv[2] if len(sys.argv) == 3 else ROOT)
