@@ -373,6 +373,44 @@ int mmd_path_constraints(const mmd_agent_path* agents_dev, int n_state, int agen
                          float* grp_weight_dev, int32_t* robot_grp_off_dev, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * The statistics of a returned solution (scripts/inference/inference_multi_agent.py:285-342, run_multi_agent_trial)
+ * ---------------------------------------------------------------------------------------------------------- */
+
+/* The data-adherence rule of a tile's environment (compute_traj_data_adherence of deps/torch_robotics/torch_robotics/environments/):
+ * every rule reads the tile's 64 positions after its offset was subtracted and gives a score in [0, 1]. */
+#define MMD_ADHERENCE_LINE 0        /* EnvEmpty2D, EnvEmptyNoWait2D (env_empty_2d.py:132-146): the fraction of points closer than 0.1
+                                     * (mmd_params.py:57) times the first-to-last distance to that line; first == last: 0 */
+#define MMD_ADHERENCE_HIGHWAYS 1    /* EnvHighways2D (env_highways_2d.py:255-273): 1 iff the cross products of consecutive normalised
+                                     * position vectors sum to > 0 (counter-clockwise); a point at the origin: 0 */
+#define MMD_ADHERENCE_CONVEYOR 2    /* EnvConveyor2D (env_conveyor_2d.py:161-185): 1 iff the three waypoints of the top corridor (right
+                                     * to left) or of the bottom one (left to right) are visited in order (radius 0.2) */
+#define MMD_ADHERENCE_DROP_REGION 3 /* EnvDropRegion2D (env_drop_region_2d.py:183-196): 1 iff 16 consecutive points among rows 0 .. 62 lie
+                                     * within 0.15 of one of the 16 drop-region centres */
+
+typedef struct mmd_tile_ref {    /* one (agent, skeleton step) of a solution */
+  int32_t agent;                 /* row of paths_dev */
+  int32_t t0;                    /* first of the tile's 64 rows in the agent's padded path: start_time + skeleton_step * 64 */
+  float offset[2];               /* the tile's transform, subtracted before scoring (inference_multi_agent.py:310-313) */
+  int32_t rule;                  /* MMD_ADHERENCE_* */
+  int32_t reserved;
+} mmd_tile_ref;                  /* 24 bytes */
+
+/* paths_dev [n_agents, horizon_global, 4]: the solution as CBS.plan / PrioritizedPlanning.plan return it -- un-normalised (x, y, vx, vy),
+ * global frame, globally padded (global_pad_paths); horizon_global = Tg >= 1 is arbitrary (K * 64 + stagger).  The tile table is passed twice,
+ * as agents_dev tables are built by their caller: tiles [n_tiles] on the HOST, checked here (a rule other than MMD_ADHERENCE_*, an agent
+ * outside [0, n_agents) or 64 rows that do not fit in Tg are error returns), and tiles_dev, the same table on the device, which the kernel
+ * reads.
+ * stats_dev: ONE buffer of 1 + 2 * n_agents + n_tiles 4-byte words, so that a trial needs one device -> host copy:
+ *   [0]                       int32  #{(t, i < j) : ||p_i(t) - p_j(t)|| < collision_dist} over all Tg rows (inference_multi_agent.py:288-294;
+ *                                    the fp32 form of mmd_rr_collisions; collision_dist = 2.0 * radius there)
+ *   [1, 1 + n)                fp32   path_length[a] = sum_t ||p_{t+1} - p_t|| (trajectory/metrics.py:13-16)
+ *   [1 + n, 1 + 2n)           fp32   mean_accel[a] = mean_t ||v_{t+1} - v_t|| over Tg - 1 terms (trajectory/metrics.py:52-65)
+ *   [1 + 2n, 1 + 2n + tiles)  fp32   adherence[tile]
+ * The count and the adherence scores are exact; the two sums are fixed-order (no floating-point atomics). */
+int mmd_solution_stats(const float* paths_dev, int n_agents, int horizon_global, float collision_dist, const mmd_tile_ref* tiles,
+                       int n_tiles, const mmd_tile_ref* tiles_dev, float* stats_dev, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Post-sampling selection: the step right after the sampler in MPD.__call__
  * (mmd/planners/single_agent/mpd.py:344-405)
  * ---------------------------------------------------------------------------------------------------------- */

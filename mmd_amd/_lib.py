@@ -80,6 +80,11 @@ class Conflict(C.Structure):
                 ("pb", C.c_float * 2), ("mid", C.c_float * 2), ("reserved2", C.c_float * 2)]
 
 
+class TileRef(C.Structure):
+    _fields_ = [("agent", C.c_int32), ("t0", C.c_int32), ("offset", C.c_float * 2), ("rule", C.c_int32), ("reserved", C.c_int32)]
+
+
+ADHERENCE_LINE, ADHERENCE_HIGHWAYS, ADHERENCE_CONVEYOR, ADHERENCE_DROP_REGION = 0, 1, 2, 3      # MMD_ADHERENCE_*
 CONFLICTS_ORDERED, CONFLICTS_PAIRS = 0, 1               # MMD_CONFLICTS_*
 SELECT_CBS, SELECT_PP = 0, 1                            # MMD_SELECT_*
 
@@ -124,6 +129,7 @@ _SIGNATURES = {
                                       C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mmd_path_constraints": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float,
                                        C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mmd_solution_stats": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mmd_postprocess_trajs": (C.c_int, [C.POINTER(GuideDesc), C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                         C.POINTER(C.c_float), C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int,
                                         C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

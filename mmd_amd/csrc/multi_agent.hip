@@ -15,16 +15,10 @@
 #include <climits>
 
 #include "../../include/mmd_amd.h"
+#include "collision_dev.h"        // torch_norm2 / rr_hit: the pinned fp32 form of the collision decision (sets fp contract(off))
 #include "common.h"
 
-// Every fp32 operation here is the one written out: the collision decision ||pa - pb|| < margin must be torch.norm's own rounding.
-#pragma clang fp contract(off)
-
 namespace mmd {
-
-// torch.norm(pa - pb, dim=-1) over (dx, dy) in fp32: sqrt(fma(dy, dy, dx * dx)), the form of check_rr_collisions / get_conflicts.
-// Any other order (dx * dx + dy * dy rounded twice, or fma(dx, dx, dy * dy)) moves pairs within an ulp of the margin across it.
-__device__ __forceinline__ float torch_norm2(float dx, float dy) { return sqrtf(__builtin_fmaf(dy, dy, dx * dx)); }
 
 __global__ void rr_collisions_kernel(const float2* __restrict__ paths, int n, int T, float margin,
                                      unsigned char* __restrict__ mask, float2* __restrict__ mid) {
@@ -76,12 +70,6 @@ __device__ __forceinline__ float2 agent_pos(const mmd_agent_path& a, int t) {
   int u = t - a.start_time;
   u = u < 0 ? 0 : (u > a.length - 1 ? a.length - 1 : u);
   return sample_pos(a.batch_dev, a.index, a.length, u);
-}
-
-// the collision test of rr_collisions_kernel, operation for operation
-__device__ __forceinline__ bool rr_hit(float2 a, float2 b, float margin) {
-  const float dx = a.x - b.x, dy = a.y - b.y;
-  return torch_norm2(dx, dy) < margin;
 }
 
 // cell c of row t: (a, b) = (c / n, c % n); MMD_CONFLICTS_ORDERED keeps a != b (torch.nonzero order of cbs.py:193-246),

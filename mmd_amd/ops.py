@@ -1,5 +1,5 @@
 """PyTorch-ROCm custom ops over the C ABI (include/mmd_amd.h): `torch.ops.mmd_amd.{unet_forward, guide_steps,
-p_sample_loop, ddim_sample}`.  They take tensors instead of raw pointers, run on torch's CURRENT HIP stream
+p_sample_loop, ddim_sample, solution_stats}`.  They take tensors instead of raw pointers, run on torch's CURRENT HIP stream
 without any host synchronisation (so they can be captured into a hipGraph with torch.cuda.graph) and register fake
 (meta) implementations so that torch.compile / FakeTensor tracing sees their output shapes.  The C header stays the ABI
 of record: every op is a thin wrapper over the same entry point the host mirror classes call through ctypes.
@@ -141,3 +141,22 @@ def _(x, hard, hard_rows, model, guide, n_robots, n_diffusion_steps, init_noise,
       return_chain):
     n_times = n_diffusion_steps // 5 + 2
     return x.new_empty((n_times,) + tuple(x.shape)) if return_chain else x.new_empty(0)
+
+
+# ---- solution_stats ------------------------------------------------------------------------------------------------
+@torch.library.custom_op("mmd_amd::solution_stats", mutates_args=(), device_types="cuda")
+def solution_stats(paths: torch.Tensor, tiles: torch.Tensor, collision_dist: float) -> torch.Tensor:
+    """The statistics of a multi-agent solution (inference_multi_agent.py:285-342; mmd_solution_stats): paths [n_agents, Tg, 4] globally
+    padded, tiles a HOST float64 tensor [n_tiles, 5] of (agent, t0, offset_x, offset_y, rule) -> float32 [1 + 2 n_agents + n_tiles]: the
+    pair-collision count (an int32 in word 0), path length and mean acceleration per agent, adherence per tile."""
+    from . import trials
+    if not (paths.is_cuda and paths.dtype == torch.float32 and paths.is_contiguous() and paths.ndim == 3 and paths.shape[2] == 4):
+        raise RuntimeError("mmd_amd op: paths must be a contiguous float32 CUDA(HIP) tensor [n_agents, Tg, 4]")
+    if tiles.is_cuda or tiles.ndim != 2 or tiles.shape[1] != 5:
+        raise RuntimeError("mmd_amd op: tiles must be a host tensor [n_tiles, 5]")
+    return trials.solution_stats_dev(paths, [tuple(row) for row in tiles.tolist()], collision_dist)
+
+
+@solution_stats.register_fake
+def _(paths, tiles, collision_dist):
+    return paths.new_empty(1 + 2 * paths.shape[0] + tiles.shape[0])
