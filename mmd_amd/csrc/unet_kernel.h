@@ -88,12 +88,22 @@ __device__ __forceinline__ RowPair rows_xor32(float v) {
 }
 __device__ __forceinline__ float add_xor16(float v) { const RowPair r = rows_xor16(v); return r.a + r.b; }
 __device__ __forceinline__ float add_xor32(float v) { const RowPair r = rows_xor32(v); return r.a + r.b; }
-__device__ __forceinline__ float max_xor16(float v) { const RowPair r = rows_xor16(v); return fmaxf(r.a, r.b); }
-__device__ __forceinline__ float max_xor32(float v) { const RowPair r = rows_xor32(v); return fmaxf(r.a, r.b); }
+// The maximum of two floats whose SIGN BIT IS CLEAR (+0, positive denormal / normal, +inf, a NaN behind fabsf) as the unsigned maximum of
+// their bit patterns: on such floats the integer order is the float order, and +inf / NaN (biased exponent 255) stay on top, which is all
+// dyn_scale reads.  fmaxf on operands that arrive through a bit cast (DPP, permlane, LDS) costs a NaN-quieting v_max_f32 x, x, x per operand
+// and keeps a DPP step from folding into the max; this is one v_max_u32 (v_max_u32_dpp, v_max3_u32).  NOT for an operand that may carry a sign
+// bit, -0.0 included: 0x80000000 is the largest unsigned value but the smallest float magnitude.
+__device__ __forceinline__ float max_nn(float a, float b) {
+  const unsigned ua = __builtin_bit_cast(unsigned, a), ub = __builtin_bit_cast(unsigned, b);
+  return __builtin_bit_cast(float, __builtin_elementwise_max(ua, ub));   // (the intrinsic: a compare + select written out stays one)
+}
+// (v >= 0 in all of the reductions below: they only ever see maxima of absolute values)
+__device__ __forceinline__ float max_xor16(float v) { const RowPair r = rows_xor16(v); return max_nn(r.a, r.b); }   // (both rows' v >= 0)
+__device__ __forceinline__ float max_xor32(float v) { const RowPair r = rows_xor32(v); return max_nn(r.a, r.b); }   // (both halves' v >= 0)
 
 template <int CTRL>
-__device__ __forceinline__ float dpp_max(float v) {
-  return fmaxf(v, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true)));
+__device__ __forceinline__ float dpp_max(float v) {   // max(v, v[DPP-permuted lane]) in one VALU op (v >= 0 in every lane)
+  return max_nn(v, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true)));
 }
 __device__ __forceinline__ float row_max16(float v) {      // max over the 16 lanes of a DPP row, in all of them (v >= 0)
   v = dpp_max<0xB1>(v);
@@ -216,15 +226,71 @@ __device__ __forceinline__ Epi<NT> epi_a(const RtbPtrs& R, int tb_off, int c0) {
 template <int NT>
 __device__ __forceinline__ Epi<NT> epi_b(const RtbPtrs& R, int c0) { return epi_load<NT>(R.bb, R.gb, R.beb, nullptr, R.isb, c0); }
 
-// The lane's pointers into a weight pack for the n-tiles tile0 .. tile0 + NT - 1 (`frags` 1 KiB fragments [lane] x 16 B per n-tile)
-template <int NT> struct WTiles { const u32x4* p[NT]; };
+// A weight pack in global memory as a wave reads it, n-tiles tile0 .. tile0 + NT - 1 (`frags` 1 KiB fragments [lane] x 16 B per n-tile): per
+// n-tile a WAVE-UNIFORM base (pack + tile offset: tile0 comes from the wave index, so the whole address is the same in every lane and lives in
+// a scalar register pair) + ONE 32-bit byte offset per lane, lane * 16, shared by all tiles and packs.  A fragment load is then
+// global_load_dwordx4 v, vOff, s[base] offset:K; past the immediate's range the base moves on the scalar unit, which issues beside VALU and
+// MFMA.  (As one 64-bit pointer per lane and tile the same loads cost two VGPRs per live pointer and a v_add_co / v_addc pair, with an s_nop
+// for the VCC hazard between them, every two ring steps.)
+typedef const __attribute__((address_space(1))) char* WBase;
+__device__ __forceinline__ WBase wave_uniform_base(const void* p, unsigned byte_off) {
+  const unsigned long long a = reinterpret_cast<unsigned long long>(p) + byte_off;
+  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)a), hi = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32));
+  return (WBase)(((unsigned long long)hi << 32) | lo);
+}
+template <int NT> struct WTiles {
+  WBase base[NT];
+  unsigned off;
+  // Fragment i of n-tile t (i is a constant wherever this is unrolled).  The load's immediate reaches -4 KiB .. +4 KiB - 1, i.e. eight
+  // fragments around a base: the base moves in steps of 8 KiB (s_add_u32 / s_addc_u32), through an opaque copy -- left to itself the
+  // compiler folds the constant behind the lane offset again, and then the whole address is a 64-bit VALU sum per lane.
+  __device__ __forceinline__ u32x4 frag(int t, int i) const {
+    const int adv = (i + 4) / 8 * 8192;
+    unsigned long long b = reinterpret_cast<unsigned long long>(base[t]) + adv;
+    if (adv) asm("" : "+s"(b));
+    return *reinterpret_cast<const __attribute__((address_space(1))) u32x4*>((WBase)b + (i * 1024 - adv) + off);
+  }
+};
 template <int NT>
 __device__ __forceinline__ WTiles<NT> w_tiles(const void* w, int frags, int tile0, int lane) {
   WTiles<NT> r;
 #pragma unroll
-  for (int t = 0; t < NT; ++t) r.p[t] = reinterpret_cast<const u32x4*>(w) + (size_t)(tile0 + t) * frags * 64 + lane;
+  for (int t = 0; t < NT; ++t) r.base[t] = wave_uniform_base(w, (unsigned)(tile0 + t) * (unsigned)frags * 1024u);
+  r.off = (unsigned)lane * 16u;
   return r;
 }
+// The same view of a conv's pack staged in LDS (stage_weights: the half-sample stages), n-tiles 0 .. NT - 1: the lane's LDS pointers
+template <int NT> struct WStaged {
+  const u32x4* p[NT];
+  __device__ __forceinline__ u32x4 frag(int t, int i) const { return p[t][i * 64]; }
+};
+template <int NT>
+__device__ __forceinline__ WStaged<NT> w_staged(const char* wb, int frags, int lane) {
+  WStaged<NT> r;
+#pragma unroll
+  for (int t = 0; t < NT; ++t) r.p[t] = reinterpret_cast<const u32x4*>(wb) + t * frags * 64 + lane;
+  return r;
+}
+// fragment i of n-tile t of either view, or of plain per-tile lane pointers (tools/ubench)
+template <int NT> __device__ __forceinline__ u32x4 w_frag(const WTiles<NT>& w, int t, int i) { return w.frag(t, i); }
+template <int NT> __device__ __forceinline__ u32x4 w_frag(const WStaged<NT>& w, int t, int i) { return w.frag(t, i); }
+__device__ __forceinline__ u32x4 w_frag(const u32x4* const* w, int t, int i) { return w[t][i * 64]; }
+// A straight-line consumer's own copy of a view.  The scalar-base form of a load is selected only where the instruction selector sees the
+// lane offset's zero-extension in the SAME basic block as the load; a lane offset that arrives from another block (a view built at the top
+// of a stage, used behind a loop or a branch) has been widened there, and the address falls back to a 64-bit VALU sum per lane.  An opaque
+// copy of the 32-bit offset at the consumer's entry (at most one v_mov_b32) pins the widening to the consumer's block.
+template <int NT> __device__ __forceinline__ WTiles<NT> w_local(WTiles<NT> w) {
+  asm volatile("" : "+v"(w.off));
+  return w;
+}
+template <int NT> __device__ __forceinline__ WStaged<NT> w_local(const WStaged<NT>& w) { return w; }
+__device__ __forceinline__ const u32x4* const* w_local(const u32x4* const* w) { return w; }
+// ... of a second view read next to the first one (the residual conv's weights): it shares the first one's lane offset
+template <int NT> __device__ __forceinline__ WTiles<NT> w_local(WTiles<NT> w, const WTiles<NT>& first) {
+  w.off = first.off;
+  return w;
+}
+template <class W, class F> __device__ __forceinline__ auto w_local(const W& w, const F&) { return w_local(w); }
 
 // "Request the NEXT conv's first ring steps right behind this conv's taps", for a wave that holds `m_tiles` M tiles per conv.  At <= 2
 // (unet_kernel<2> / <1>: the latency-bound launches of <= 512 trajectories, where nothing else on the CU covers an L2 round trip) they
@@ -343,12 +409,12 @@ __device__ __forceinline__ void rd_zero_halo(char* slab) {
                               (sm * GEO::RPS + (hr < 2 ? hr : GEO::RPS - 4 + hr)) * 16) = make_uint4(0u, 0u, 0u, 0u);
   }
 }
-template <class GEO, int NT>
-__device__ __forceinline__ void rd_load_b(u32x4 (&b)[NT][2], const u32x4* const (&w)[NT], int step) {
+template <class GEO, int NT, class W>
+__device__ __forceinline__ void rd_load_b(u32x4 (&b)[NT][2], const W& w, int step) {   // W: anything w_frag reads
 #pragma unroll
   for (int t = 0; t < NT; ++t)
 #pragma unroll
-    for (int q = 0; q < 2; ++q) b[t][q] = w[t][(step * 2 + q) * 64];
+    for (int q = 0; q < 2; ++q) b[t][q] = w_frag(w, t, step * 2 + q);
 }
 // A fragments of one sample PAIR (M tiles 2 hp, 2 hp + 1; SM = 1: of the single M tile) at slab-row offset rowoff, chunk kc
 template <class GEO, int SM = 2>
@@ -372,19 +438,22 @@ constexpr int RD_RD = 2;                    // weight ring depth in steps
 #ifndef MMD_U0_RD
 #define MMD_U0_RD 3
 #endif
-template <class GEO, int NT, int RD = RD_RD>
-__device__ __forceinline__ void rd_ring_load(u32x4 (&b)[RD][NT][2], const u32x4* const (&w)[NT]) {
+template <class GEO, int NT, int RD = RD_RD, class W>
+__device__ __forceinline__ void rd_ring_load(u32x4 (&b)[RD][NT][2], const W& w_in) {
+  const auto w = w_local(w_in);
 #pragma unroll
   for (int i = 0; i < RD; ++i) rd_load_b<GEO, NT>(b[i], w, i);
   MMD_PIN_LOADS();
 }
 // acc[sample][tile] (+)= conv over TAPS taps (slab rows TAP0 .. TAP0 + TAPS - 1 relative to the output position) x the C
-// channels of the slab; va = slab + the lane's A offset (lane group lane >> 4, row lane & 15); w[tile] = the tile's pack +
-// lane; b = ring pre-loaded with the first RD_RD steps.  RES: the stage's 1x1 residual conv rides on the centre tap's A
-// fragments (res[sample][tile] (+)=, weights wr[tile] = [chunk kc][piece] + lane).  FRESH: start from zero.
-template <class GEO, int NT, int TAP0, int TAPS, bool FRESH, bool RES, int MT = 4, int RD = RD_RD>
-__device__ __forceinline__ void rd_taps(f32x4 (&acc)[MT][NT], f32x4 (&res)[MT][NT], const char* va, const u32x4* const (&w)[NT],
-                                        const u32x4* const (&wr)[NT], u32x4 (&b)[RD][NT][2]) {
+// channels of the slab; va = slab + the lane's A offset (lane group lane >> 4, row lane & 15); w = the NT tiles' packs (WTiles /
+// WStaged); b = ring pre-loaded with the first RD_RD steps.  RES: the stage's 1x1 residual conv rides on the centre tap's A
+// fragments (res[sample][tile] (+)=, weights wr: per tile [chunk kc][piece]).  FRESH: start from zero.
+template <class GEO, int NT, int TAP0, int TAPS, bool FRESH, bool RES, int MT = 4, int RD = RD_RD, class W, class WR>
+__device__ __forceinline__ void rd_taps(f32x4 (&acc)[MT][NT], f32x4 (&res)[MT][NT], const char* va, const W& w_in, const WR& wr_in,
+                                        u32x4 (&b)[RD][NT][2]) {
+  const auto w = w_local(w_in);
+  [[maybe_unused]] const auto wr = w_local(wr_in, w);
   // M tiles are processed in pairs (SM = 2), or a single one (MT = 1: the half-sample waves of unet_kernel<2> at L = 32)
   constexpr int KC = GEO::KC, STEPS = TAPS * KC, SM = MT >= 2 ? 2 : 1, HP = MT / SM;
   static_assert(MT == 1 || MT % 2 == 0, "M tiles are processed in pairs");
@@ -400,7 +469,7 @@ __device__ __forceinline__ void rd_taps(f32x4 (&acc)[MT][NT], f32x4 (&res)[MT][N
 #pragma unroll
     for (int t = 0; t < NT; ++t)
 #pragma unroll
-      for (int q = 0; q < 2; ++q) brp[kc][t][q] = wr[t][(kc * 2 + q) * 64];
+      for (int q = 0; q < 2; ++q) brp[kc][t][q] = w_frag(wr, t, kc * 2 + q);
   };
   // Every step (tap, chunk kc) is unrolled: the ring slot step % RD and the A buffer parity are static for any depth, the
   // loop has no branches, and the scheduler sees the whole conv (rolled over the taps, downs.2's convs ran 5 % slower at <= 512
@@ -539,7 +608,8 @@ __device__ __forceinline__ void rd_dyn_out(const f32x4 (&acc)[NS][NT], float* mx
 }
 __device__ __forceinline__ float mx_read(const float* mx, int sm) {
   const float4 p = *reinterpret_cast<const float4*>(mx + sm * MX_SLOTS), q = *reinterpret_cast<const float4*>(mx + sm * MX_SLOTS + 4);
-  return fmaxf(fmaxf(fmaxf(p.x, p.y), fmaxf(p.z, p.w)), fmaxf(fmaxf(q.x, q.y), fmaxf(q.z, q.w)));
+  // (every slot holds a maximum of absolute values, written by rd_dyn_out / pair_maxima_out / half_sample_max / the tails: >= 0)
+  return max_nn(max_nn(max_nn(p.x, p.y), max_nn(p.z, p.w)), max_nn(max_nn(q.x, q.y), max_nn(q.z, q.w)));
 }
 // dynamic input scale of a conv on tile t (samples s0 .. s0 + S - 1, M / S M tiles each) from the samples' maxima in mx: scale in place;
 // inv: the inverse scales
@@ -970,13 +1040,13 @@ __device__ __forceinline__ void d0_zero_xin_halo(char* xin, int lane, bool mine)
 }
 // the B fragments of RTB 0's conv A (im2col chunk) and of the 1x1 residual conv: one chunk x two pieces per n-tile
 __device__ __forceinline__ void d0_load_wa(const ChainArgs& a, int lane, u32x4 (&b)[2][2], u32x4 (&br)[2][2]) {
-  const WTiles<2> wa = w_tiles<2>(a.r0.wa_bf, 2, 0, lane), wr = w_tiles<2>(a.wres_bf, 2, 0, lane);
+  const WTiles<2> wa = w_local(w_tiles<2>(a.r0.wa_bf, 2, 0, lane)), wr = w_local(w_tiles<2>(a.wres_bf, 2, 0, lane), wa);
 #pragma unroll
   for (int t = 0; t < 2; ++t)
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
-      b[t][q] = wa.p[t][q * 64];
-      br[t][q] = wr.p[t][q * 64];
+      b[t][q] = wa.frag(t, q);
+      br[t][q] = wr.frag(t, q);
     }
 }
 // RTB 0's conv A + the 1x1 residual conv on M tiles m0 .. m0 + MT - 1
@@ -1042,12 +1112,12 @@ __device__ __forceinline__ void chain_body_d0w(const ChainArgs& a, float* lds, i
   // The whole weight set of a conv (5 taps x 2 n-tiles x 2 pieces = 20 KB per wave) is requested BEFORE the epilogue that
   // produces the conv's input (preload), so the L2 latency hides behind GroupNorm + Mish instead of in front of the MFMAs.
   u32x4 ring[5][2][2];
-  auto preload = [&](const uint4* w) { rd_ring_load<GW, 2, 5>(ring, w_tiles<2>(w, GW::FRAGS5, 0, lane).p); };
+  auto preload = [&](const uint4* w) { rd_ring_load<GW, 2, 5>(ring, w_tiles<2>(w, GW::FRAGS5, 0, lane)); };
   auto conv = [&](const uint4* w) {                          // one 32 -> 32 conv over the tile in acc (already scaled)
     const WTiles<2> wp = w_tiles<2>(w, GW::FRAGS5, 0, lane);
     rw_store2<GW, 4>(vs, acc);
     wave_lds_fence();
-    rd_taps<GW, 2, 0, 5, true, false, 4, 5>(acc, res, va, wp.p, wp.p, ring);
+    rd_taps<GW, 2, 0, 5, true, false, 4, 5>(acc, res, va, wp, wp, ring);
     wave_lds_fence();                                        // (the next store must not overtake these reads)
   };
   tile_finish_res(res, isr0, inv_in, br0);
@@ -1084,12 +1154,12 @@ __device__ __forceinline__ void chain_body_d0w(const ChainArgs& a, float* lds, i
     const WTiles<2> wt = w_tiles<2>(a.wt_bf0, GW::FRAGS3, 0, lane);
     u32x4 ring3[3][2][2];
     const float bt[2] = {a.bt[c0], a.bt[c0 + 1]}, ist[2] = {a.ist0[c0] * ds.inv, a.ist0[c0 + 1] * ds.inv};
-    rd_ring_load<GW, 2, 3>(ring3, wt.p);
+    rd_ring_load<GW, 2, 3>(ring3, wt);
     rw_store2<GW, 4>(vs, acc);
     wave_lds_fence();
     // (outputs q = 16 mt + 4 g + r = the even positions 2 q: two M tiles read at stride 2)
     f32x4 y[2][2];
-    rd_taps<Stride2<GW, 0, 2>, 2, 1, 3, true, false, 2, 3>(y, y, va + n * 16, wt.p, wt.p, ring3);
+    rd_taps<Stride2<GW, 0, 2>, 2, 1, 3, true, false, 2, 3>(y, y, va + n * 16, wt, wt, ring3);
     const float mo = tail_epilogue(y, ist, bt);
     __syncthreads();                                         // every wave is done with its slab: the next stage's slab aliases them
     if (lane < MX_SLOTS) (lds + MX_OFF)[wave * MX_SLOTS + lane] = mo;
@@ -1139,7 +1209,7 @@ __device__ __forceinline__ void chain_body_d0s(const ChainArgs& a, float* lds, i
   // one 32 -> 32 conv over the half tile in acc (already scaled), its weights staged in wb; behind the barrier the NEXT conv's
   // NEXT_FRAGS fragments start on their way into the other buffer (every wave is past the conv that read it)
   auto conv = [&](char* wb, auto next_frags, const uint4* w_next, char* wb_next, int tr = -1) {
-    const WTiles<2> wp = w_tiles<2>(wb, GW::FRAGS5, 0, lane);
+    const WStaged<2> wp = w_staged<2>(wb, GW::FRAGS5, lane);
     if (tr >= 0) TR(tr);
     rw_store2<GW, 2>(vs, acc);
     if (tr >= 0) TR(tr + 1);
@@ -1147,8 +1217,8 @@ __device__ __forceinline__ void chain_body_d0s(const ChainArgs& a, float* lds, i
     __syncthreads();                                         // both halves of the sample and the conv's weights are in LDS
     if (tr >= 0) TR(tr + 2);
     if constexpr (decltype(next_frags)::value > 0) stage_weights<decltype(next_frags)::value>(w_next, wb_next, wave, lane);
-    rd_ring_load<GW, 2, 2>(ring, wp.p);
-    rd_taps<GW, 2, 0, 5, true, false, 2, 2>(acc, res, va, wp.p, wp.p, ring);
+    rd_ring_load<GW, 2, 2>(ring, wp);
+    rd_taps<GW, 2, 0, 5, true, false, 2, 2>(acc, res, va, wp, wp, ring);
     if (tr >= 0) TR(tr + 3);
   };
   using F5 = std::integral_constant<int, 2 * GW::FRAGS5>;
@@ -1182,14 +1252,14 @@ __device__ __forceinline__ void chain_body_d0s(const ChainArgs& a, float* lds, i
   {
     const DynScale ds = dyn_scale(half_sample_max(mx, sp, hf, lane, rw_absmax(acc)));
     tile_scale(acc, ds.s);
-    const WTiles<2> wt = w_tiles<2>(wb1, GW::FRAGS3, 0, lane);
+    const WStaged<2> wt = w_staged<2>(wb1, GW::FRAGS3, lane);
     const float bt[2] = {a.bt[c0], a.bt[c0 + 1]}, ist[2] = {a.ist0[c0] * ds.inv, a.ist0[c0 + 1] * ds.inv};
     rw_store2<GW, 2>(vs, acc);
     staged_weights_landed();
     __syncthreads();
     f32x4 y[1][2];
-    rd_ring_load<GW, 2, 2>(ring, wt.p);
-    rd_taps<Stride2<GW, 0, 2>, 2, 1, 3, true, false, 1, 2>(y, y, va + n * 16, wt.p, wt.p, ring);
+    rd_ring_load<GW, 2, 2>(ring, wt);
+    rd_taps<Stride2<GW, 0, 2>, 2, 1, 3, true, false, 1, 2>(y, y, va + n * 16, wt, wt, ring);
     const float mo = tail_epilogue(y, ist, bt);
     // (the barrier inside: every wave is done with its slab -- the next stage's slab aliases them -- and the sample's maxima
     // are published for the next stage's dynamic scale)
@@ -1245,14 +1315,14 @@ __device__ __forceinline__ void chain_body_d1d(const ChainArgs& a, float* lds, i
   // the epilogue; `frags_next`: the next pack's fragments per n-tile.
   constexpr bool PF = ring_prefetch(NS);
   auto prefetch = [&](const uint4* w, int frags) {
-    if constexpr (PF) rd_ring_load<GH, 2, RD1>(ring, wt2(w, frags).p);
+    if constexpr (PF) rd_ring_load<GH, 2, RD1>(ring, wt2(w, frags));
   };
   auto conv = [&](const uint4* w, const uint4* w_next, int frags_next) {
     const WTiles<2> wp = wt2(w, GH::FRAGS5);
-    if constexpr (!PF) rd_ring_load<GH, 2, RD1>(ring, wp.p);
+    if constexpr (!PF) rd_ring_load<GH, 2, RD1>(ring, wp);
     store_tile();
     __syncthreads();
-    rd_taps<GH, 2, 0, 5, true, false, NS, RD1>(acc, acc, vaH, wp.p, wp.p, ring);
+    rd_taps<GH, 2, 0, 5, true, false, NS, RD1>(acc, acc, vaH, wp, wp, ring);
     prefetch(w_next, frags_next);
   };
   float one2[SW];
@@ -1263,7 +1333,7 @@ __device__ __forceinline__ void chain_body_d1d(const ChainArgs& a, float* lds, i
   {
     u32x4 ring5[5][2][2];
     const WTiles<2> wpa = wt2(a.r0.wa_bf, GI::FRAGS5), wpr = wt2(a.wres_bf, 2 * GI::KC);
-    rd_ring_load<GI, 2, 5>(ring5, wpa.p);
+    rd_ring_load<GI, 2, 5>(ring5, wpa);
     const Epi<2> e0a = epi_a<2>(a.r0, tb_off, c0);
     const float br[2] = {a.br[c0], a.br[c0 + 1]}, isr[2] = {a.isr[c0], a.isr[c0 + 1]};
     __syncthreads();                                         // downs.0's tail has written the input slab and its maxima
@@ -1272,7 +1342,7 @@ __device__ __forceinline__ void chain_body_d1d(const ChainArgs& a, float* lds, i
 #pragma unroll
     for (int sl = 0; sl < SW; ++sl) inv_in[sl] = dyn_scale(mx_read(mx, s0 + sl)).inv;
     rd_zero_halo<GH>(slabH);
-    rd_taps<GI, 2, 0, 5, true, true, NS, 5>(acc, res, vaI, wpa.p, wpr.p, ring5);
+    rd_taps<GI, 2, 0, 5, true, true, NS, 5>(acc, res, vaI, wpa, wpr, ring5);
     tile_finish_res(res, isr, inv_in, br);
     prefetch(a.r0.wb_bf, GH::FRAGS5);
     rw_gn_samples<4, 256>(acc, e0a, inv_in, a.r0.act_a);
@@ -1311,13 +1381,13 @@ __device__ __forceinline__ void chain_body_d1d(const ChainArgs& a, float* lds, i
     mx_scale_tile(mx, s0, acc, inv);
     const WTiles<2> wt = wt2(a.wt_bf0, GH::FRAGS3);
     const float bt[2] = {a.bt[c0], a.bt[c0 + 1]}, ist[2] = {a.ist0[c0], a.ist0[c0 + 1]};
-    if constexpr (!PF) rd_ring_load<GH, 2, RD1>(ring, wt.p);
+    if constexpr (!PF) rd_ring_load<GH, 2, RD1>(ring, wt);
     store_tile();
     __syncthreads();
     // (outputs q = 4 g + r = the even positions 2 q of the wave's samples: one M tile each, read at stride 2; the GEMM loop takes
     // M tiles in pairs: a one-sample wave computes its tile twice)
     f32x4 y[2][2];
-    rd_taps<Stride2<GH, SW == 2 ? GH::RPS : 0, 1>, 2, 1, 3, true, false, 2, RD1>(y, y, vaH + n * 16, wt.p, wt.p, ring);
+    rd_taps<Stride2<GH, SW == 2 ? GH::RPS : 0, 1>, 2, 1, 3, true, false, 2, RD1>(y, y, vaH + n * 16, wt, wt, ring);
     float m2[2] = {0.f, 0.f};
 #pragma unroll
     for (int sl = 0; sl < SW; ++sl) {
@@ -1378,7 +1448,7 @@ __device__ __forceinline__ void chain_body_d2d(const ChainArgs& a, float* lds, i
   constexpr int RDD = MMD_D2_RD;                               // weight ring depth of the 128 -> 128 convs
   u32x4 ring[RDD][2][2];
   const WTiles<2> wpa = wt2(a.r0.wa_bf, G64::FRAGS5), wpr = wt2(a.wres_bf, 2 * G64::KC);
-  rd_ring_load<G64, 2, 2>(reinterpret_cast<u32x4(&)[2][2][2]>(ring), wpa.p);   // (conv A + residual streams: depth 2, or it spills)
+  rd_ring_load<G64, 2, 2>(reinterpret_cast<u32x4(&)[2][2][2]>(ring), wpa);   // (conv A + residual streams: depth 2, or it spills)
   __syncthreads();                                           // the x slab (previous stage's tail tile) and its maxima are staged
   TR(trb + 0);
 
@@ -1395,17 +1465,17 @@ __device__ __forceinline__ void chain_body_d2d(const ChainArgs& a, float* lds, i
   // PF (ring_prefetch): the first RDD weight steps of the NEXT conv are requested right behind this conv's taps.
   constexpr bool PF = ring_prefetch(NS);
   auto prefetch = [&](const uint4* w) {
-    if constexpr (PF) rd_ring_load<G128, 2, RDD>(ring, wt2(w, G128::FRAGS5).p);
+    if constexpr (PF) rd_ring_load<G128, 2, RDD>(ring, wt2(w, G128::FRAGS5));
   };
   auto conv = [&](const uint4* w, const uint4* w_next) {
     const WTiles<2> wp = wt2(w, G128::FRAGS5);
     TR(trb + 10);
-    if constexpr (!PF) rd_ring_load<G128, 2, RDD>(ring, wp.p);
+    if constexpr (!PF) rd_ring_load<G128, 2, RDD>(ring, wp);
     rd_store2<G128>(vs, acc);
     TR(trb + 11);
     __syncthreads();
     TR(trb + 12);
-    rd_taps<G128, 2, 0, 5, true, false, NS, RDD>(acc, acc, va128, wp.p, wp.p, ring);
+    rd_taps<G128, 2, 0, 5, true, false, NS, RDD>(acc, acc, va128, wp, wp, ring);
     if (w_next) prefetch(w_next);
     TR(trb + 13);
   };
@@ -1421,7 +1491,7 @@ __device__ __forceinline__ void chain_body_d2d(const ChainArgs& a, float* lds, i
   __syncthreads();
   {
     f32x4 res[NS][2];
-    rd_taps<G64, 2, 0, 5, true, true, NS, 2>(acc, res, va64, wpa.p, wpr.p, reinterpret_cast<u32x4(&)[2][2][2]>(ring));
+    rd_taps<G64, 2, 0, 5, true, true, NS, 2>(acc, res, va64, wpa, wpr, reinterpret_cast<u32x4(&)[2][2][2]>(ring));
     tile_finish_res(res, isr, inv_in, br);
     park_tile(lds, res);                                     // (every wave is past the barrier behind the x slab's last read)
   }
@@ -1482,7 +1552,7 @@ __device__ __forceinline__ void chain_body_u0d(const ChainArgs& a, float* lds, i
   u32x4 ring[RDC][1][2];
   const WTiles<1> wp0 = wt1(a.r0.wa_bf, G128::FRAGS5), wp1 = wt1(a.wa0_c1_bf, G128::FRAGS5);
   const WTiles<1> wr0 = wt1(a.wres_bf, 2 * G128::KC), wr1 = wt1(a.wres_c1_bf, 2 * G128::KC);
-  rd_ring_load<G128, 1, RDU>(ringa, wp0.p);
+  rd_ring_load<G128, 1, RDU>(ringa, wp0);
   __syncthreads();                                           // the previous stage is done with the slab; its maxima are in mx
   TR(trb + 0);
 
@@ -1494,14 +1564,14 @@ __device__ __forceinline__ void chain_body_u0d(const ChainArgs& a, float* lds, i
   // NEXT pack's first ring steps are requested right behind this conv's taps; `frags_next`: the next pack's fragments per n-tile.
   constexpr bool PF = ring_prefetch(NS);
   auto prefetch64 = [&](const uint4* w, int frags) {
-    if constexpr (PF) rd_ring_load<G64, 1, RDC>(ring, wt1(w, frags).p);
+    if constexpr (PF) rd_ring_load<G64, 1, RDC>(ring, wt1(w, frags));
   };
   auto conv64 = [&](const uint4* w, const uint4* w_next, int frags_next) {
     const WTiles<1> wp = wt1(w, G64::FRAGS5);
-    if constexpr (!PF) rd_ring_load<G64, 1, RDC>(ring, wp.p);
+    if constexpr (!PF) rd_ring_load<G64, 1, RDC>(ring, wp);
     rd_store1<G64>(vs64, acc, lane);
     __syncthreads();
-    rd_taps<G64, 1, 0, 5, true, false, NS, RDC>(acc, res, va64, wp.p, wp.p, ring);
+    rd_taps<G64, 1, 0, 5, true, false, NS, RDC>(acc, res, va64, wp, wp, ring);
     prefetch64(w_next, frags_next);
   };
 
@@ -1510,7 +1580,8 @@ __device__ __forceinline__ void chain_body_u0d(const ChainArgs& a, float* lds, i
 #pragma unroll
   for (int sm = 0; sm < NS; ++sm) {
     // residual-stream input: dynamic scale from the maxima downs.2 left in regions 1 (skip2) and 2 (mid output) of mx
-    const DynScale ds = dyn_scale(fmaxf(mx_read(mx + MX_REGION, sm), mx_read(mx + 2 * MX_REGION, sm)));
+    // (mx_read returns a maximum of absolute values: >= 0)
+    const DynScale ds = dyn_scale(max_nn(mx_read(mx + MX_REGION, sm), mx_read(mx + 2 * MX_REGION, sm)));
     inv_in[sm] = ds.inv;
     tile_scale(sub_tile<1>(x0, sm), ds.s);
     tile_scale(sub_tile<1>(x1, sm), ds.s);
@@ -1521,15 +1592,15 @@ __device__ __forceinline__ void chain_body_u0d(const ChainArgs& a, float* lds, i
   TR(160);
   __syncthreads();
   TR(161);
-  rd_taps<G128, 1, 0, 5, true, true, NS, RDU>(acc, res, va128, wp0.p, wr0.p, ringa);
-  rd_ring_load<G128, 1, RDU>(ringa, wp1.p);
+  rd_taps<G128, 1, 0, 5, true, true, NS, RDU>(acc, res, va128, wp0, wr0, ringa);
+  rd_ring_load<G128, 1, RDU>(ringa, wp1);
   TR(162);
   __syncthreads();                                           // every wave is done reading chunk 0
   store2(x1);
   TR(163);
   __syncthreads();
   TR(164);
-  rd_taps<G128, 1, 0, 5, false, true, NS, RDU>(acc, res, va128, wp1.p, wr1.p, ringa);
+  rd_taps<G128, 1, 0, 5, false, true, NS, RDU>(acc, res, va128, wp1, wr1, ringa);
   TR(165);
   tile_finish_res(res, isr, inv_in, br);
   prefetch64(a.r0.wb_bf, G64::FRAGS5);
@@ -1569,13 +1640,13 @@ __device__ __forceinline__ void chain_body_u0d(const ChainArgs& a, float* lds, i
     mx_scale_tile(mx, 0, acc, inv);
     const WTiles<1> wt0 = wt1(a.wt_bf0, 2 * G64::KC * 2), wt1p = wt1(a.wt_bf1, 2 * G64::KC * 2);
     const float bt[1] = {a.bt[col]}, is0 = a.ist0[col], is1 = a.ist1[col];
-    if constexpr (!PF) rd_ring_load<G64, 1, RDC>(ring, wt0.p);
+    if constexpr (!PF) rd_ring_load<G64, 1, RDC>(ring, wt0);
     rd_store1<G64>(vs64, acc, lane);
     __syncthreads();
     TR(trb + 7);
-    rd_taps<G64, 1, 1, 2, true, false, NS, RDC>(xe, res, va64, wt0.p, wt0.p, ring);
-    rd_ring_load<G64, 1, RDC>(ring, wt1p.p);
-    rd_taps<G64, 1, 2, 2, true, false, NS, RDC>(xo, res, va64, wt1p.p, wt1p.p, ring);
+    rd_taps<G64, 1, 1, 2, true, false, NS, RDC>(xe, res, va64, wt0, wt0, ring);
+    rd_ring_load<G64, 1, RDC>(ring, wt1p);
+    rd_taps<G64, 1, 2, 2, true, false, NS, RDC>(xo, res, va64, wt1p, wt1p, ring);
     // the stage's output stays in registers: xe / xo[sample][0][r] = positions 2 m, 2 m + 1 (m = 4 g + r) of channel col; the
     // per-sample maxima of the wave's 16 channels go to slot `wave` of mx region 0 (the caller's barrier publishes them)
 #pragma unroll
@@ -1735,7 +1806,7 @@ __device__ __forceinline__ void chain_body_u1w(const ChainArgs& a, const FinalAr
   const WTiles<2> wp0 = wt2(a.r0.wa_bf, GA::FRAGS5), wp1 = wt2(a.wa0_c1_bf, GA::FRAGS5);
   const WTiles<2> wr0 = wt2(a.wres_bf, 2 * GA::KC), wr1 = wt2(a.wres_c1_bf, 2 * GA::KC);
   u32x4 ring[RDA][2][2];
-  rd_ring_load<GA, 2, RDA>(ring, wp0.p);
+  rd_ring_load<GA, 2, RDA>(ring, wp0);
   // ---- the skip tensor's per-sample maxima -> slots 4 .. 7 of mx region 0 (the two waves of a sample pair fill them); ups.0 left its
   //      output's maxima in slots 0 .. 3
   pair_maxima_out<2, 4>(skip, mx, wave, lane);
@@ -1750,8 +1821,8 @@ __device__ __forceinline__ void chain_body_u1w(const ChainArgs& a, const FinalAr
   TR(trb + 7);
   const char* const vaA = slab + g * GA::G + n * 16;
   f32x4 acc[2][2], res[2][2];
-  rd_taps<GA, 2, 0, 5, true, true, 2, RDA>(acc, res, vaA, wp0.p, wr0.p, ring);
-  rd_ring_load<GA, 2, RDA>(ring, wp1.p);
+  rd_taps<GA, 2, 0, 5, true, true, 2, RDA>(acc, res, vaA, wp0, wr0, ring);
+  rd_ring_load<GA, 2, RDA>(ring, wp1);
   TR(trb + 8);
   __syncthreads();                                           // every wave has consumed chunk 0
   u1_store_chunk1(lb, wave, n, g, skip, sc.skip);
@@ -1759,19 +1830,19 @@ __device__ __forceinline__ void chain_body_u1w(const ChainArgs& a, const FinalAr
   TR(trb + 10);
   const Epi<2> e0a = epi_a<2>(a.r0, tb_off, c0);
   const float br[2] = {a.br[c0], a.br[c0 + 1]}, isr[2] = {a.isr[c0], a.isr[c0 + 1]};
-  rd_taps<GA, 2, 0, 5, false, true, 2, RDA>(acc, res, vaA, wp1.p, wr1.p, ring);
+  rd_taps<GA, 2, 0, 5, false, true, 2, RDA>(acc, res, vaA, wp1, wr1, ring);
   TR(trb + 11);
   // ---- from here on the wave is on its own: 32-channel slab
   const char* const vaB = slab + g * GB::G + n * 16;
   char* const vsB = slab + (n >> 2) * GB::G + (2 + 4 * g) * 16 + (n & 3) * 4;
   u32x4 ring5[5][2][2];
-  auto preload = [&](const uint4* w) { rd_ring_load<GB, 2, 5>(ring5, wt2(w, GB::FRAGS5).p); };
+  auto preload = [&](const uint4* w) { rd_ring_load<GB, 2, 5>(ring5, wt2(w, GB::FRAGS5)); };
   preload(a.r0.wb_bf);
   auto conv = [&](const uint4* w) {                          // one 32 -> 32 conv over the tile in acc (already scaled)
     const WTiles<2> wp = wt2(w, GB::FRAGS5);
     rw_store2<GB, 2>(vsB, acc);
     wave_lds_fence();
-    rd_taps<GB, 2, 0, 5, true, false, 2, 5>(acc, res, vaB, wp.p, wp.p, ring5);
+    rd_taps<GB, 2, 0, 5, true, false, 2, 5>(acc, res, vaB, wp, wp, ring5);
     wave_lds_fence();                                        // (the next store must not overtake these reads)
   };
   tile_finish_res(res, isr, inv_in, br);
@@ -1815,13 +1886,13 @@ __device__ __forceinline__ void chain_body_u1w(const ChainArgs& a, const FinalAr
     u32x4 ring2[2][2][2];
     const float bt[2] = {a.bt[c0], a.bt[c0 + 1]};
     const float is0[2] = {a.ist0[c0] * ds.inv, a.ist0[c0 + 1] * ds.inv}, is1[2] = {a.ist1[c0] * ds.inv, a.ist1[c0 + 1] * ds.inv};
-    rd_ring_load<GB, 2, 2>(ring2, wt0.p);
+    rd_ring_load<GB, 2, 2>(ring2, wt0);
     rw_store2<GB, 2>(vsB, acc);
     wave_lds_fence();
     f32x4 e[2][2], o[2][2];
-    rd_taps<GB, 2, 1, 2, true, false, 2, 2>(e, res, vaB, wt0.p, wt0.p, ring2);
-    rd_ring_load<GB, 2, 2>(ring2, wt1.p);
-    rd_taps<GB, 2, 2, 2, true, false, 2, 2>(o, res, vaB, wt1.p, wt1.p, ring2);
+    rd_taps<GB, 2, 1, 2, true, false, 2, 2>(e, res, vaB, wt0, wt0, ring2);
+    rd_ring_load<GB, 2, 2>(ring2, wt1);
+    rd_taps<GB, 2, 2, 2, true, false, 2, 2>(o, res, vaB, wt1, wt1, ring2);
     const DynScale df = dyn_scale(tail_up_epilogue(e, o, is0, is1, bt));
     inv_f = df.inv;
     wave_lds_fence();                                        // the tail's reads are done: 64-row geometry
@@ -1832,20 +1903,20 @@ __device__ __forceinline__ void chain_body_u1w(const ChainArgs& a, const FinalAr
   // ---- final block: Conv1dBlock(32 -> 32, k5) + GroupNorm + Mish, then the 1x1 conv 32 -> 4 (N padded to one n-tile)
   {
     const WTiles<2> wf = wt2(f.w5, GF::FRAGS5);
-    rd_ring_load<GF, 2, 5>(ring5, wf.p);
+    rd_ring_load<GF, 2, 5>(ring5, wf);
     const WTiles<1> w1 = w_tiles<1>(f.w1_bf, 2 * GF::KC, 0, lane);
     u32x4 ring1[1][1][2];
-    rd_ring_load<GF, 1, 1>(ring1, w1.p);
+    rd_ring_load<GF, 1, 1>(ring1, w1);
     const Epi<2> ef = epi_load<2>(f.bias, f.gamma, f.beta, nullptr, f.isc, c0);
     const float b1 = f.w1_bias[n & 3], s1 = f.is1[n & 3];
     wave_lds_fence();
-    rd_taps<GF, 2, 0, 5, true, false, 4, 5>(y, y, vaF, wf.p, wf.p, ring5);
+    rd_taps<GF, 2, 0, 5, true, false, 4, 5>(y, y, vaF, wf, wf, ring5);
     rw_gn_mish_whole<4, 2, 2, 256, true>(y, ef.b, ef.g, ef.be, ef.is, inv_f, act_scale(f.act), [](int, int, int) { return 0.f; });
     wave_lds_fence();
     rw_store2<GF, 4>(vsF + (2 + 4 * g) * 16, y);
     wave_lds_fence();
     f32x4 out[4][1];
-    rd_taps<GF, 1, 2, 1, true, false, 4, 1>(out, out, vaF, w1.p, w1.p, ring1);
+    rd_taps<GF, 1, 2, 1, true, false, 4, 1>(out, out, vaF, w1, w1, ring1);
     auto valid = [&] { return wave < NS && n0 + wave < a.n; };   // (a.n is read inside the branch that needs it)
     if (fs.enabled) {
       // eps[64][4] -> the wave's slab as float4 rows, then the fused step on the wave's trajectory
@@ -1880,11 +1951,11 @@ __device__ __forceinline__ void chain_body_u1s(const ChainArgs& a, const FinalAr
   float* const mx = lds + MX_OFF;
   const RwHalf half{reinterpret_cast<HalfStat*>(lds + PARK2_OFF) + sp * 128, hf, lane};
   const int n = lane & 15, g = lane >> 4, c0 = 2 * n;
-  auto wt2 = [&](const void* w, int frags) { return w_tiles<2>(w, frags, 0, lane); };
+  auto wt2 = [&](const uint4* w, int frags) { return w_tiles<2>(w, frags, 0, lane); };
   const WTiles<2> wp0 = wt2(a.r0.wa_bf, GA::FRAGS5), wp1 = wt2(a.wa0_c1_bf, GA::FRAGS5);
   const WTiles<2> wr0 = wt2(a.wres_bf, 2 * GA::KC), wr1 = wt2(a.wres_c1_bf, 2 * GA::KC);
   u32x4 ring[RDA][2][2];
-  rd_ring_load<GA, 2, RDA>(ring, wp0.p);
+  rd_ring_load<GA, 2, RDA>(ring, wp0);
   // ---- the skip tensor's per-sample maxima -> slots 4 .. 7 of mx region 0; ups.0 left its output's maxima in slots 0 .. 3
   pair_maxima_out<2, 4>(skip, mx, wave, lane);
   __syncthreads();                                           // ups.0 is done with its slabs; the maxima are in mx
@@ -1901,8 +1972,8 @@ __device__ __forceinline__ void chain_body_u1s(const ChainArgs& a, const FinalAr
   TR(trb + 7);
   const char* const vaA = slab + g * GA::G + (n + 16 * hf) * 16;
   f32x4 acc[1][2], res[1][2];
-  rd_taps<GA, 2, 0, 5, true, true, 1, RDA>(acc, res, vaA, wp0.p, wr0.p, ring);
-  rd_ring_load<GA, 2, RDA>(ring, wp1.p);
+  rd_taps<GA, 2, 0, 5, true, true, 1, RDA>(acc, res, vaA, wp0, wr0, ring);
+  rd_ring_load<GA, 2, RDA>(ring, wp1);
   TR(trb + 8);
   __syncthreads();                                           // every wave has consumed chunk 0
   u1_store_chunk1(lb, wave, n, g, skip, sc.skip);
@@ -1910,7 +1981,7 @@ __device__ __forceinline__ void chain_body_u1s(const ChainArgs& a, const FinalAr
   TR(trb + 10);
   const Epi<2> e0a = epi_a<2>(a.r0, tb_off, c0);
   const float br[2] = {a.br[c0], a.br[c0 + 1]}, isr[2] = {a.isr[c0], a.isr[c0 + 1]};
-  rd_taps<GA, 2, 0, 5, false, true, 1, RDA>(acc, res, vaA, wp1.p, wr1.p, ring);
+  rd_taps<GA, 2, 0, 5, false, true, 1, RDA>(acc, res, vaA, wp1, wr1, ring);
   TR(trb + 11);
   // ---- 32-channel slab of the sample, shared by its two waves
   const char* const vaB = slab + g * GB::G + (n + 16 * hf) * 16;
@@ -1919,13 +1990,13 @@ __device__ __forceinline__ void chain_body_u1s(const ChainArgs& a, const FinalAr
   // one 32 -> 32 conv over the half tile in acc (already scaled), its weights staged in wb; `stage_next` puts the next conv's on
   // their way behind the barrier (every wave is past the conv that read the other buffer)
   auto conv = [&](char* wb, auto stage_next) {
-    const WTiles<2> wp = wt2(wb, GB::FRAGS5);
+    const WStaged<2> wp = w_staged<2>(wb, GB::FRAGS5, lane);
     rw_store2<GB, 1>(vsB, acc);
     staged_weights_landed();
     __syncthreads();
     stage_next();
-    rd_ring_load<GB, 2, 2>(ring2, wp.p);
-    rd_taps<GB, 2, 0, 5, true, false, 1, 2>(acc, res, vaB, wp.p, wp.p, ring2);
+    rd_ring_load<GB, 2, 2>(ring2, wp);
+    rd_taps<GB, 2, 0, 5, true, false, 1, 2>(acc, res, vaB, wp, wp, ring2);
   };
   tile_finish_res(res, isr, inv_in, br);
   rw_gn<2, 128>(acc, e0a, inv_in, a.r0.act_a, half);         // (its barrier: conv A's reads are done, the slab changes its geometry)
@@ -1963,7 +2034,7 @@ __device__ __forceinline__ void chain_body_u1s(const ChainArgs& a, const FinalAr
   {
     const DynScale ds = dyn_scale(half_sample_max(mx, sp, hf, lane, rw_absmax(acc)));
     tile_scale(acc, ds.s);
-    const WTiles<2> wt0 = wt2(wb1, TF / 2), wt1 = wt2(wb1 + TF * 1024, TF / 2);
+    const WStaged<2> wt0 = w_staged<2>(wb1, TF / 2, lane), wt1 = w_staged<2>(wb1 + TF * 1024, TF / 2, lane);
     const float bt[2] = {a.bt[c0], a.bt[c0 + 1]};
     const float is0[2] = {a.ist0[c0] * ds.inv, a.ist0[c0 + 1] * ds.inv}, is1[2] = {a.ist1[c0] * ds.inv, a.ist1[c0 + 1] * ds.inv};
     rw_store2<GB, 1>(vsB, acc);
@@ -1971,10 +2042,10 @@ __device__ __forceinline__ void chain_body_u1s(const ChainArgs& a, const FinalAr
     __syncthreads();
     stage_weights<2 * GF::FRAGS5>(f.w5, wb0, wave, lane);    // the final block's k5 conv
     f32x4 e[1][2], o[1][2];
-    rd_ring_load<GB, 2, 2>(ring2, wt0.p);
-    rd_taps<GB, 2, 1, 2, true, false, 1, 2>(e, res, vaB, wt0.p, wt0.p, ring2);
-    rd_ring_load<GB, 2, 2>(ring2, wt1.p);
-    rd_taps<GB, 2, 2, 2, true, false, 1, 2>(o, res, vaB, wt1.p, wt1.p, ring2);
+    rd_ring_load<GB, 2, 2>(ring2, wt0);
+    rd_taps<GB, 2, 1, 2, true, false, 1, 2>(e, res, vaB, wt0, wt0, ring2);
+    rd_ring_load<GB, 2, 2>(ring2, wt1);
+    rd_taps<GB, 2, 2, 2, true, false, 1, 2>(o, res, vaB, wt1, wt1, ring2);
     const float m = tail_up_epilogue(e, o, is0, is1, bt);
     const DynScale df = dyn_scale(half_sample_max(mx, sp, hf, lane, m));   // (its barrier: the tail's reads are done, 64-row geometry)
     inv_f = df.inv;
@@ -1984,23 +2055,23 @@ __device__ __forceinline__ void chain_body_u1s(const ChainArgs& a, const FinalAr
   TR(trb + 5);
   // ---- final block: Conv1dBlock(32 -> 32, k5) + GroupNorm + Mish, then the 1x1 conv 32 -> 4, on the half's two M tiles
   {
-    const WTiles<2> wf = wt2(wb0, GF::FRAGS5);
+    const WStaged<2> wf = w_staged<2>(wb0, GF::FRAGS5, lane);
     const WTiles<1> w1 = w_tiles<1>(f.w1_bf, 2 * GF::KC, 0, lane);
     u32x4 ring1[1][1][2];
-    rd_ring_load<GF, 1, 1>(ring1, w1.p);
+    rd_ring_load<GF, 1, 1>(ring1, w1);
     const Epi<2> ef = epi_load<2>(f.bias, f.gamma, f.beta, nullptr, f.isc, c0);
     const float b1 = f.w1_bias[n & 3], s1 = f.is1[n & 3];
     staged_weights_landed();
     __syncthreads();                                         // the final block's input and weights are complete
-    rd_ring_load<GF, 2, 2>(ring2, wf.p);
-    rd_taps<GF, 2, 0, 5, true, false, 2, 2>(y, y, vaF, wf.p, wf.p, ring2);
+    rd_ring_load<GF, 2, 2>(ring2, wf);
+    rd_taps<GF, 2, 0, 5, true, false, 2, 2>(y, y, vaF, wf, wf, ring2);
     rw_gn_mish_half<2, 2, 2, 256, true>(y, ef.b, ef.g, ef.be, ef.is, inv_f, act_scale(f.act), [](int, int, int) { return 0.f; }, half.xch, hf, lane);
     // (the exchange's barrier: the partner is past its taps, the slab may be overwritten; the 1x1 conv reads only the centre
     // tap = the wave's own rows)
     rw_store2<GF, 2>(vsF + (2 + 4 * g + 32 * hf) * 16, y);
     wave_lds_fence();
     f32x4 out[2][1];
-    rd_taps<GF, 1, 2, 1, true, false, 2, 1>(out, out, vaF, w1.p, w1.p, ring1);
+    rd_taps<GF, 1, 2, 1, true, false, 2, 1>(out, out, vaF, w1, w1, ring1);
     auto valid = [&] { return sp < NV && n0 + sp < a.n; };
     if (fs.enabled) {
       // eps[64][4] -> the sample's slab as float4 rows (both waves their halves), then the fused step on the trajectory by the sample's
