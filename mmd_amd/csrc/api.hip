@@ -181,6 +181,32 @@ static inline float* eps_of(void* workspace_dev, mmd_unet_t unet, int n) {
   return reinterpret_cast<float*>(reinterpret_cast<char*>(workspace_dev) + mmd_unet_workspace_bytes(unet, n));
 }
 
+// One ddpm_sample_fn step of n trajectories through the UNet launch + step kernel pair: the body of mmd_ddpm_step and, with trace_dev (the
+// decision dump, its guide chain and the optional posterior mean: include/mmd_amd_debug.h), of mmd_debug_ddpm_step_trace.
+static int ddpm_step(mmd_unet_t unet, const mmd_sampler_desc* s, const mmd_guide_desc* guide, float* x_dev, const float* hard_dev, int n,
+                     int samples_per_robot, int i, const float* noise_dev, uint64_t seed, uint32_t draw_index, void* workspace_dev,
+                     mmd_profiler_t prof, float* mu_dev, float* guide_chain_dev, uint32_t* trace_dev, void* stream) {
+  StepDev sd{};
+  if (int rc = make_step(s, i, guide != nullptr, sd)) return rc;
+  sd.seed = seed; sd.draw = draw_index;
+  if (trace_dev) {
+    MMD_REQUIRE(sd.do_guide, "mmd_debug_ddpm_step_trace: step %d is not a guided one (t_start_guide %d)", i, s->t_start_guide);
+    sd.guide_chain = reinterpret_cast<float4*>(guide_chain_dev);
+    sd.guide_chain_stride = (long long)n * H;
+    sd.trace = trace_dev;
+    sd.mu_out = reinterpret_cast<float4*>(mu_dev);
+  }
+  GuideDev g{};
+  if (sd.do_guide)
+    if (int rc = fill_guide(guide, g)) return rc;
+  float* eps = eps_of(workspace_dev, unet, n);
+  if (int rc = mmd_unet_forward_profiled(unet, x_dev, i < 0 ? 0 : i, eps, n, workspace_dev, mmd_unet_workspace_bytes(unet, n), prof, stream))
+    return rc;
+  launch_step(g, sd, x_dev, eps, noise_dev, nullptr, hard_dev, 0, n, samples_per_robot, (hipStream_t)stream);
+  MMD_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
 }  // namespace mmd
 
 using namespace mmd;
@@ -205,21 +231,8 @@ int mmd_ddpm_step(mmd_unet_t unet, const mmd_sampler_desc* s, const mmd_guide_de
   const int n = n_robots * samples_per_robot;
   MMD_REQUIRE(n >= 1, "mmd_ddpm_step: empty batch");
   MMD_REQUIRE(workspace_bytes >= mmd_sampler_workspace_bytes(unet, n), "mmd_ddpm_step: workspace too small");
-  hipStream_t st = (hipStream_t)stream;
-  const size_t uws = mmd_unet_workspace_bytes(unet, n);
-  float* eps = eps_of(workspace_dev, unet, n);
-  StepDev sd{};
-  if (int rc = make_step(s, i, guide != nullptr, sd)) return rc;
-  sd.seed = seed; sd.draw = draw_index;
-  GuideDev g{};
-  if (sd.do_guide)
-    if (int rc = fill_guide(guide, g)) return rc;
-  if (int rc = mmd_unet_forward_profiled(unet, x_dev, i < 0 ? 0 : i, eps, n, workspace_dev, uws,
-                                         (mmd_profiler_t)s->profiler, stream))
-    return rc;
-  launch_step(g, sd, x_dev, eps, noise_dev, nullptr, hard_dev, 0, n, samples_per_robot, st);
-  MMD_HIP_CHECK(hipGetLastError());
-  return 0;
+  return ddpm_step(unet, s, guide, x_dev, hard_dev, n, samples_per_robot, i, noise_dev, seed, draw_index, workspace_dev,
+                   (mmd_profiler_t)s->profiler, nullptr, nullptr, nullptr, stream);
 }
 
 int mmd_debug_ddpm_step_trace(mmd_unet_t unet, const mmd_sampler_desc* s, const mmd_guide_desc* guide, float* x_dev,
@@ -231,23 +244,8 @@ int mmd_debug_ddpm_step_trace(mmd_unet_t unet, const mmd_sampler_desc* s, const 
   const int n = n_robots * samples_per_robot;
   MMD_REQUIRE(n >= 1, "mmd_debug_ddpm_step_trace: empty batch");
   MMD_REQUIRE(workspace_bytes >= mmd_sampler_workspace_bytes(unet, n), "mmd_debug_ddpm_step_trace: workspace too small");
-  hipStream_t st = (hipStream_t)stream;
-  float* eps = eps_of(workspace_dev, unet, n);
-  StepDev sd{};
-  if (int rc = make_step(s, i, true, sd)) return rc;
-  MMD_REQUIRE(sd.do_guide, "mmd_debug_ddpm_step_trace: step %d is not a guided one (t_start_guide %d)", i, s->t_start_guide);
-  sd.seed = seed; sd.draw = draw_index;
-  sd.guide_chain = reinterpret_cast<float4*>(guide_chain_dev);
-  sd.guide_chain_stride = (long long)n * H;
-  sd.trace = trace_dev;
-  sd.mu_out = reinterpret_cast<float4*>(mu_dev);
-  GuideDev g{};
-  if (int rc = fill_guide(guide, g)) return rc;
-  if (int rc = mmd_unet_forward(unet, x_dev, i < 0 ? 0 : i, eps, n, workspace_dev, mmd_unet_workspace_bytes(unet, n), stream))
-    return rc;
-  launch_step(g, sd, x_dev, eps, noise_dev, nullptr, hard_dev, 0, n, samples_per_robot, st);
-  MMD_HIP_CHECK(hipGetLastError());
-  return 0;
+  return ddpm_step(unet, s, guide, x_dev, hard_dev, n, samples_per_robot, i, noise_dev, seed, draw_index, workspace_dev, nullptr,
+                   mu_dev, guide_chain_dev, trace_dev, stream);
 }
 
 int mmd_p_sample_loop(mmd_unet_t unet, const mmd_sampler_desc* s, const mmd_guide_desc* guide, float* x_dev,

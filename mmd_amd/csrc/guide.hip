@@ -100,22 +100,15 @@ __device__ __forceinline__ f32x2g acc4_total(const Acc4& r) {
 }
 // a <- a - d m,  d = p - q,  m = [||d||^2 <= R|R|] / ||d||   (one slot, one lane).  Plain fp32 VALU ops with explicit fmas (the same
 // instruction sequence in both kernels).  The packed form (v_pk_add / v_pk_mul / v_pk_fma on the (x, y) pair: 8 instead of 12
-// instructions per slot, -DMMD_GUIDE_PK) was measured and is NOT used: next to another wave's MFMA stream a v_pk_* issues once
+// instructions per slot) was measured and is NOT used: next to another wave's MFMA stream a v_pk_* issues once
 // per MFMA where a plain VALU op issues every ~10 cycles (tools/ubench/mfma_valu_overlap.hip), and the guided step of one stream
 // chunk runs beside the other chunk's UNet launch -- 108 instead of 83 us per launch in the loop, 86.2 k instead of 92.3 k
 // trajectories/s (profiles/r04_guide_packed_ab.txt).
 __device__ __forceinline__ f32x2g cons_term(f32x2g a, f32x2g p, f32x2g q, float r2) {
-#ifdef MMD_GUIDE_PK
-  const f32x2g d = p - q, sq = d * d;
-  const float d2 = sq.x + sq.y;
-  const float m = (d2 > r2) ? 0.f : rsq_pos(d2);
-  return __builtin_elementwise_fma(-d, f32x2g{m, m}, a);
-#else
   const float dx = p.x - q.x, dy = p.y - q.y;
   const float d2 = __builtin_fmaf(dx, dx, dy * dy);
   const float m = (d2 > r2) ? 0.f : rsq_pos(d2);
   return f32x2g{__builtin_fmaf(-dx, m, a.x), __builtin_fmaf(-dy, m, a.y)};
-#endif
 }
 // one table entry as (q, R|R|): the general table holds (qx, qy, R, R|R|) (R < 0: empty, R|R| < 0 <= d2), the compact on-chip
 // table (qx, qy) with one radius for every active point and "no point" stored as (1e30, 1e30): dist^2 = inf > R^2
@@ -332,6 +325,93 @@ __device__ __forceinline__ float4 guide_grad(const GuideDev& g, float4 xn, int t
   return make_float4(-tx, -ty, -tz, -tw);
 }
 
+// ---- What the two step kernels below share, each fragment written once: the kernels are required to produce the same bits, so they
+// ---- run the same text.  They keep only how a trajectory maps to waves and how a group's slot sum is split over them.
+
+// Up to lds_slots slots of `robot`'s constraint table -> LDS, by the NT threads of the workgroup (the caller's barrier follows)
+template <bool COMPACT, int NT>
+__device__ __forceinline__ void stage_cons(const GuideDev& g, int robot, int lds_slots, float4* lds_cons, int& lds_slot0, int& lds_n) {
+  lds_slot0 = __builtin_amdgcn_readfirstlane(g.grp_slot_off[g.robot_grp_off[robot]]);
+  lds_n = min(__builtin_amdgcn_readfirstlane(g.grp_slot_off[g.robot_grp_off[robot + 1]]) - lds_slot0, lds_slots);
+  const float4* src = g.cons + (size_t)lds_slot0 * H;
+  if constexpr (COMPACT) {
+    float2* dst = reinterpret_cast<float2*>(lds_cons);
+    for (int i = threadIdx.x; i < lds_n * H; i += NT) {
+      const float4 c = src[i];
+      dst[i] = c.z < 0.f ? make_float2(1e30f, 1e30f) : make_float2(c.x, c.y);
+    }
+  } else {
+    for (int i = threadIdx.x; i < lds_n * H; i += NT) lds_cons[i] = src[i];
+  }
+}
+
+// The slots of group grp in order: the LDS-resident ones (the lds_n slots of the table from lds_slot0 on, staged by stage_cons<COMPACT>)
+// first, any overflow straight from the L2-resident table.  acc(table, first slot in it, slot count, first slot's index in the group)
+// is the kernel's accumulation.  (Group bounds are the same for the whole wave: scalar registers, scalar loop control.)
+template <bool COMPACT, class ACC>
+__device__ __forceinline__ void group_slots(const GuideDev& g, const GroupMeta& gm, int grp, const float4* lds_cons, int lds_slot0, int lds_n,
+                                            ACC acc) {
+  int s0, s1;
+  gm.bounds(g, grp, s0, s1);
+  const int l0 = min(max(s0 - lds_slot0, 0), lds_n), l1 = min(max(s1 - lds_slot0, 0), lds_n);   // LDS part
+  if (l1 > l0) {
+    if constexpr (COMPACT) acc(ConsTab<true>{reinterpret_cast<const float2*>(lds_cons), g.uniform_r2}, l0, l1 - l0, lds_slot0 + l0 - s0);
+    else acc(ConsTab<false>{lds_cons, 0.f}, l0, l1 - l0, lds_slot0 + l0 - s0);
+  }
+  const int g0 = lds_n > 0 ? max(s0, lds_slot0 + lds_n) : s0;                                    // global part
+  if (s1 > g0) acc(ConsTab<false>{g.cons, 0.f}, g0, s1 - g0, g0 - s0);
+}
+
+// The lane's support point after the step's model update (as it is in a guide-only launch: eps is not read then).  (s and v by value:
+// through references the compiler merges the three updates' code differently from the statements written out in a kernel.)
+__device__ __forceinline__ float4 model_update(StepDev s, float4 v, const float4* eps, size_t idx) {
+  if (s.do_model)
+    v = s.ddim == 2 ? ddim_update_x0(v, eps[idx], s.a_t, s.b_t, s.c1, s.c2)
+        : s.ddim ? ddim_update(v, eps[idx], s.a_t, s.b_t, s.c1, s.c2) : ddpm_posterior_mean(v, eps[idx], s.a_t, s.b_t, s.c1, s.c2);
+  return v;
+}
+
+// The guide iterations (guide_gradient_steps, sample_functions.py:89-107) on the lane's point of a trajectory of `robot`: its map's grids
+// and its constraint groups, then per iteration v += grad_scale * guide_grad(v), pinned rows pinned again, the state -> guide_chain where
+// `store`.  group_sum(gm, grp, p) is the kernel's evaluation of the canonical slot sum of group grp at p.
+template <bool DUMP, class GROUPSUM>
+__device__ __forceinline__ void guide_iterations(const GuideDev& g, const StepDev& s, int robot, int t, size_t idx, float4& v, bool is_hard,
+                                                 float4 hv, bool store, GROUPSUM group_sum) {
+  const int map = g.robot_map ? g.robot_map[robot] : 0;
+  const float4* grid = g.grids + (size_t)map * g.n_grids * g.nx * g.ny;
+  int grp0 = 0, grp1 = 0;
+  if (g.robot_grp_off) {
+    grp0 = __builtin_amdgcn_readfirstlane(g.robot_grp_off[robot]);
+    grp1 = __builtin_amdgcn_readfirstlane(g.robot_grp_off[robot + 1]);
+  }
+  GroupMeta gm;
+  gm.load(g, grp0, grp1);
+  for (int it = 0; it < s.n_guide_steps; ++it) {
+    unsigned int* tr = nullptr;
+    if constexpr (DUMP) {
+      tr = s.trace + ((size_t)it * s.guide_chain_stride + idx) * MMD_TRACE_WORDS;
+      for (int w = 0; w < MMD_TRACE_WORDS; ++w) tr[w] = 0u;
+    }
+    const float4 gr = guide_grad<DUMP>(g, v, t, grid, grp0, grp1, [&](int grp, f32x2g p) { return group_sum(gm, grp, p); },
+                                       [&](int grp) { return gm.weight(g, grp); }, tr);
+    // (x + model_var * grad with scale_grad_by_std, sample_functions.py:100-104; grad_scale = 1 otherwise: the fma is then the add)
+    v.x = __builtin_fmaf(s.grad_scale, gr.x, v.x); v.y = __builtin_fmaf(s.grad_scale, gr.y, v.y);
+    v.z = __builtin_fmaf(s.grad_scale, gr.z, v.z); v.w = __builtin_fmaf(s.grad_scale, gr.w, v.w);
+    if (is_hard) v = hv;
+    if (s.guide_chain && store) s.guide_chain[(size_t)it * s.guide_chain_stride + idx] = v;
+  }
+}
+
+// The step's noise, hard conditioning, the stores to x and the chain row.  (v and hv by reference: by value the compiler turns the
+// branches into selects.)
+__device__ __forceinline__ void step_finish(const StepDev& s, float4* x, const float4* noise, float4* chain, size_t idx, int robot,
+                                            int samples_per_robot, float4& v, bool is_hard, const float4& hv) {
+  if (s.do_noise) v = add_step_noise(v, noise ? noise[idx] : traj_normal4(s.seed, s.robot_seeds, s.draw, s.traj_base, idx, robot, samples_per_robot), s.sigma, s.noise_std_extra);
+  if (is_hard) v = hv;
+  x[idx] = v;
+  if (chain) chain[idx] = v;
+}
+
 // One ddpm_sample_fn (sample_functions.py:40-86) + the apply_hard_conditioning after it, for one trajectory per wave.
 template <int WPB, bool COMPACT, bool DUMP = false>
 __global__ __launch_bounds__(WPB * 64) void ddpm_guide_kernel(GuideDev g, StepDev s, int lds_slots, float4* __restrict__ x,
@@ -340,12 +420,6 @@ __global__ __launch_bounds__(WPB * 64) void ddpm_guide_kernel(GuideDev g, StepDe
                                                          const float4* __restrict__ hard,
                                                          int samples_per_robot) {
   extern __shared__ __attribute__((aligned(16))) float4 lds_cons[];
-#ifdef MMD_GUIDE_PRIO   // (A/B build: the step kernel is on the critical chain of its stream chunk while the other chunk's UNet launch shares the SIMDs)
-  __builtin_amdgcn_s_setprio(MMD_GUIDE_PRIO);
-#endif
-#ifdef MMD_GUIDE_PLAIN   // (A/B side build: the configuration every planner runs -- clip by norm, no extra objects, at most one grid -- folded in)
-  g.clip_rule = 0; g.n_xs = 0; g.n_xb = 0; g.n_grids = g.n_grids > 0 ? 1 : 0;
-#endif
   const int t = threadIdx.x & 63;
   const int traj_b = s.traj0 + blockIdx.x * WPB;
   const int traj = traj_b + (threadIdx.x >> 6);
@@ -357,32 +431,14 @@ __global__ __launch_bounds__(WPB * 64) void ddpm_guide_kernel(GuideDev g, StepDe
   if (s.do_guide && g.robot_grp_off) {
     const int rb0 = traj_b / samples_per_robot;
     const int rb1 = min(traj_b + WPB - 1, s.traj_end - 1) / samples_per_robot;
-    if (rb0 == rb1) {
-      lds_slot0 = __builtin_amdgcn_readfirstlane(g.grp_slot_off[g.robot_grp_off[rb0]]);
-      lds_n = min(__builtin_amdgcn_readfirstlane(g.grp_slot_off[g.robot_grp_off[rb0 + 1]]) - lds_slot0, lds_slots);
-      const float4* src = g.cons + (size_t)lds_slot0 * H;
-      if constexpr (COMPACT) {
-        float2* dst = reinterpret_cast<float2*>(lds_cons);
-        for (int i = threadIdx.x; i < lds_n * H; i += WPB * 64) {
-          const float4 c = src[i];
-          dst[i] = c.z < 0.f ? make_float2(1e30f, 1e30f) : make_float2(c.x, c.y);
-        }
-      } else {
-        for (int i = threadIdx.x; i < lds_n * H; i += WPB * 64) lds_cons[i] = src[i];
-      }
-    }
+    if (rb0 == rb1) stage_cons<COMPACT, WPB * 64>(g, rb0, lds_slots, lds_cons, lds_slot0, lds_n);
   }
   __syncthreads();
   if (!valid) return;
 
   const int robot = traj / samples_per_robot;
   const size_t idx = (size_t)traj * H + t;
-  float4 v = x[idx];
-
-  if (s.do_model)
-    v = s.ddim == 2 ? ddim_update_x0(v, eps[idx], s.a_t, s.b_t, s.c1, s.c2)
-        : s.ddim ? ddim_update(v, eps[idx], s.a_t, s.b_t, s.c1, s.c2) : ddpm_posterior_mean(v, eps[idx], s.a_t, s.b_t, s.c1, s.c2);
-
+  float4 v = model_update(s, x[idx], eps, idx);
   float4 hv = v;
   const bool is_hard = hard_row(s.hard_rows, s.n_hard, hard, robot, t, hv);
   if constexpr (DUMP) {
@@ -390,55 +446,14 @@ __global__ __launch_bounds__(WPB * 64) void ddpm_guide_kernel(GuideDev g, StepDe
     // first one -- guide_gradient_steps, sample_functions.py:89-107)
     if (s.mu_out) s.mu_out[idx] = v;
   }
-
-  if (s.do_guide) {
-    const int map = g.robot_map ? g.robot_map[robot] : 0;
-    const float4* grid = g.grids + (size_t)map * g.n_grids * g.nx * g.ny;
-    int grp0 = 0, grp1 = 0;
-    if (g.robot_grp_off) {
-      grp0 = __builtin_amdgcn_readfirstlane(g.robot_grp_off[robot]);
-      grp1 = __builtin_amdgcn_readfirstlane(g.robot_grp_off[robot + 1]);
-    }
-    GroupMeta gm;
-    gm.load(g, grp0, grp1);
-    auto group_weight = [&](int grp) { return gm.weight(g, grp); };
-    // the group's slots: LDS-resident ones first, any overflow straight from the L2-resident table
-    auto group_sum = [&](int grp, f32x2g p) {
-      // (group bounds are the same for the whole wave: scalar registers, scalar loop control)
-      int s0, s1;
-      gm.bounds(g, grp, s0, s1);
-      const int l0 = min(max(s0 - lds_slot0, 0), lds_n), l1 = min(max(s1 - lds_slot0, 0), lds_n);   // LDS part
+  if (s.do_guide)
+    guide_iterations<DUMP>(g, s, robot, t, idx, v, is_hard, hv, true, [&](const GroupMeta& gm, int grp, f32x2g p) {
       Acc4 acc = acc4_zero();
-      if (l1 > l0) {
-        if constexpr (COMPACT)
-          cons_accumulate4(acc, ConsTab<true>{reinterpret_cast<const float2*>(lds_cons), g.uniform_r2}, l0, l1 - l0,
-                           lds_slot0 + l0 - s0, t, p);
-        else
-          cons_accumulate4(acc, ConsTab<false>{lds_cons, 0.f}, l0, l1 - l0, lds_slot0 + l0 - s0, t, p);
-      }
-      const int g0 = lds_n > 0 ? max(s0, lds_slot0 + lds_n) : s0;                                    // global part
-      if (s1 > g0) cons_accumulate4(acc, ConsTab<false>{g.cons, 0.f}, g0, s1 - g0, g0 - s0, t, p);
+      group_slots<COMPACT>(g, gm, grp, lds_cons, lds_slot0, lds_n,
+                           [&](const auto& tab, int first, int n, int rel) { cons_accumulate4(acc, tab, first, n, rel, t, p); });
       return acc4_total(acc);
-    };
-    for (int it = 0; it < s.n_guide_steps; ++it) {
-      unsigned int* tr = nullptr;
-      if constexpr (DUMP) {
-        tr = s.trace + ((size_t)it * s.guide_chain_stride + idx) * MMD_TRACE_WORDS;
-        for (int w = 0; w < MMD_TRACE_WORDS; ++w) tr[w] = 0u;
-      }
-      const float4 gr = guide_grad<DUMP>(g, v, t, grid, grp0, grp1, group_sum, group_weight, tr);
-      // (x + model_var * grad with scale_grad_by_std, sample_functions.py:100-104; grad_scale = 1 otherwise: the fma is then the add)
-      v.x = __builtin_fmaf(s.grad_scale, gr.x, v.x); v.y = __builtin_fmaf(s.grad_scale, gr.y, v.y);
-      v.z = __builtin_fmaf(s.grad_scale, gr.z, v.z); v.w = __builtin_fmaf(s.grad_scale, gr.w, v.w);
-      if (is_hard) v = hv;
-      if (s.guide_chain) s.guide_chain[(size_t)it * s.guide_chain_stride + idx] = v;
-    }
-  }
-
-  if (s.do_noise) v = add_step_noise(v, noise ? noise[idx] : traj_normal4(s.seed, s.robot_seeds, s.draw, s.traj_base, idx, robot, samples_per_robot), s.sigma, s.noise_std_extra);
-  if (is_hard) v = hv;
-  x[idx] = v;
-  if (chain) chain[idx] = v;
+    });
+  step_finish(s, x, noise, chain, idx, robot, samples_per_robot, v, is_hard, hv);
 }
 
 // The same step with FOUR waves per trajectory (small launches: <= 512 trajectories leave most SIMDs without a wave, and a
@@ -454,83 +469,33 @@ __global__ __launch_bounds__(256) void ddpm_guide_coop_kernel(GuideDev g, StepDe
                                                               float4* __restrict__ chain, const float4* __restrict__ hard,
                                                               int samples_per_robot) {
   extern __shared__ __attribute__((aligned(16))) float4 lds_cons[];
-#ifdef MMD_GUIDE_PLAIN   // (A/B side build: the configuration every planner runs -- clip by norm, no extra objects, at most one grid -- folded in)
-  g.clip_rule = 0; g.n_xs = 0; g.n_xb = 0; g.n_grids = g.n_grids > 0 ? 1 : 0;
-#endif
   const int t = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int traj = s.traj0 + blockIdx.x;                   // (the grid is exactly the launch's trajectories)
   const int robot = traj / samples_per_robot;
   float2* const xch = reinterpret_cast<float2*>(reinterpret_cast<char*>(lds_cons) + (size_t)lds_slots * H * (COMPACT ? 8 : 16));
   int lds_slot0 = 0, lds_n = 0;
-  if (s.do_guide && g.robot_grp_off) {
-    lds_slot0 = __builtin_amdgcn_readfirstlane(g.grp_slot_off[g.robot_grp_off[robot]]);
-    lds_n = min(__builtin_amdgcn_readfirstlane(g.grp_slot_off[g.robot_grp_off[robot + 1]]) - lds_slot0, lds_slots);
-    const float4* src = g.cons + (size_t)lds_slot0 * H;
-    if constexpr (COMPACT) {
-      float2* dst = reinterpret_cast<float2*>(lds_cons);
-      for (int i = threadIdx.x; i < lds_n * H; i += 256) {
-        const float4 c = src[i];
-        dst[i] = c.z < 0.f ? make_float2(1e30f, 1e30f) : make_float2(c.x, c.y);
-      }
-    } else {
-      for (int i = threadIdx.x; i < lds_n * H; i += 256) lds_cons[i] = src[i];
-    }
-  }
+  if (s.do_guide && g.robot_grp_off) stage_cons<COMPACT, 256>(g, robot, lds_slots, lds_cons, lds_slot0, lds_n);
   __syncthreads();
   const size_t idx = (size_t)traj * H + t;
-  float4 v = x[idx];
-  if (s.do_model)
-    v = s.ddim == 2 ? ddim_update_x0(v, eps[idx], s.a_t, s.b_t, s.c1, s.c2)
-        : s.ddim ? ddim_update(v, eps[idx], s.a_t, s.b_t, s.c1, s.c2) : ddpm_posterior_mean(v, eps[idx], s.a_t, s.b_t, s.c1, s.c2);
+  float4 v = model_update(s, x[idx], eps, idx);
   float4 hv = v;
   const bool is_hard = hard_row(s.hard_rows, s.n_hard, hard, robot, t, hv);
   if (s.do_guide) {
-    const int map = g.robot_map ? g.robot_map[robot] : 0;
-    const float4* grid = g.grids + (size_t)map * g.n_grids * g.nx * g.ny;
-    int grp0 = 0, grp1 = 0;
-    if (g.robot_grp_off) {
-      grp0 = __builtin_amdgcn_readfirstlane(g.robot_grp_off[robot]);
-      grp1 = __builtin_amdgcn_readfirstlane(g.robot_grp_off[robot + 1]);
-    }
     int parity = 0;
-    GroupMeta gm;
-    gm.load(g, grp0, grp1);
-    auto group_weight = [&](int grp) { return gm.weight(g, grp); };
-    auto group_sum = [&](int grp, f32x2g p) {
-      int s0, s1;
-      gm.bounds(g, grp, s0, s1);
-      const int l0 = min(max(s0 - lds_slot0, 0), lds_n), l1 = min(max(s1 - lds_slot0, 0), lds_n);
+    guide_iterations<false>(g, s, robot, t, idx, v, is_hard, hv, wave == 0, [&](const GroupMeta& gm, int grp, f32x2g p) {
       f32x2g a = {0.f, 0.f};
-      if (l1 > l0) {
-        if constexpr (COMPACT)
-          a = cons_accumulate1(a, ConsTab<true>{reinterpret_cast<const float2*>(lds_cons), g.uniform_r2}, l0, l1 - l0,
-                               lds_slot0 + l0 - s0, wave, t, p);
-        else
-          a = cons_accumulate1(a, ConsTab<false>{lds_cons, 0.f}, l0, l1 - l0, lds_slot0 + l0 - s0, wave, t, p);
-      }
-      const int g0 = lds_n > 0 ? max(s0, lds_slot0 + lds_n) : s0;
-      if (s1 > g0) a = cons_accumulate1(a, ConsTab<false>{g.cons, 0.f}, g0, s1 - g0, g0 - s0, wave, t, p);
+      group_slots<COMPACT>(g, gm, grp, lds_cons, lds_slot0, lds_n,
+                           [&](const auto& tab, int first, int n, int rel) { a = cons_accumulate1(a, tab, first, n, rel, wave, t, p); });
       float2* const slot = xch + parity * 4 * H;
       slot[wave * H + t] = make_float2(a.x, a.y);
       __syncthreads();                                       // (the buffer of the other parity is free again: every wave has
       parity ^= 1;                                           //  passed the barrier after reading it)
       const float2 q0 = slot[t], q1 = slot[H + t], q2 = slot[2 * H + t], q3 = slot[3 * H + t];
       return acc4_total(Acc4{f32x2g{q0.x, q0.y}, f32x2g{q1.x, q1.y}, f32x2g{q2.x, q2.y}, f32x2g{q3.x, q3.y}});
-    };
-    for (int it = 0; it < s.n_guide_steps; ++it) {
-      const float4 gr = guide_grad(g, v, t, grid, grp0, grp1, group_sum, group_weight);
-      // (x + model_var * grad with scale_grad_by_std, sample_functions.py:100-104; grad_scale = 1 otherwise: the fma is then the add)
-      v.x = __builtin_fmaf(s.grad_scale, gr.x, v.x); v.y = __builtin_fmaf(s.grad_scale, gr.y, v.y);
-      v.z = __builtin_fmaf(s.grad_scale, gr.z, v.z); v.w = __builtin_fmaf(s.grad_scale, gr.w, v.w);
-      if (is_hard) v = hv;
-      if (s.guide_chain && wave == 0) s.guide_chain[(size_t)it * s.guide_chain_stride + idx] = v;
-    }
+    });
   }
   if (wave != 0) return;
-  if (s.do_noise) v = add_step_noise(v, noise ? noise[idx] : traj_normal4(s.seed, s.robot_seeds, s.draw, s.traj_base, idx, robot, samples_per_robot), s.sigma, s.noise_std_extra);
-  if (is_hard) v = hv;
-  x[idx] = v;
-  if (chain) chain[idx] = v;
+  step_finish(s, x, noise, chain, idx, robot, samples_per_robot, v, is_hard, hv);
 }
 
 // x <- conditioned init: optional Philox draw of x_T, apply_hard_conditioning, optional chain[0] write
@@ -611,7 +576,6 @@ int fill_guide(const mmd_guide_desc* d, GuideDev& g) {
   for (int k = 0; k < 2; ++k) {
     g.lo[k] = d->limits_lo[k];
     g.dim[k] = fabsf(d->limits_hi[k] - d->limits_lo[k]);
-    g.inv_dim[k] = 1.f / g.dim[k];
     g.ws_min[k] = d->ws_min[k]; g.ws_max[k] = d->ws_max[k];
   }
   g.nx = d->grid_nx; g.ny = d->grid_ny; g.n_grids = d->n_grids;
@@ -648,23 +612,21 @@ int launch_step(const GuideDev& g, StepDev s, float* x, const float* eps, const 
   const bool compact = guided && g.uniform_r2 > 0.f;
   const int bytes_per_slot = H * (compact ? 8 : 16);
   const int small = LDS_SLOTS_SMALL * (compact ? 2 : 1), big = LDS_SLOTS_MAX * (compact ? 2 : 1);
-  auto launch = [&](auto kern, int wpb, int slots) {
-    hipLaunchKernelGGL(kern, dim3((n_traj + wpb - 1) / wpb), dim3(wpb * 64), (size_t)slots * bytes_per_slot, st, g, s, slots,
-                       (float4*)x, (const float4*)eps, (const float4*)noise, (float4*)chain, (const float4*)hard, spr);
+  auto launch = [&](auto kern, int grid, int block, size_t lds_bytes, int slots) {
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(block), lds_bytes, st, g, s, slots, (float4*)x, (const float4*)eps, (const float4*)noise,
+                       (float4*)chain, (const float4*)hard, spr);
   };
   if (s.trace) {
     // measurement hook: the one-wave kernel, every slot from the L2-resident table (the slot sums are canonical: same bits as any
     // production launch shape), with the decision dump compiled in
-    hipLaunchKernelGGL((ddpm_guide_kernel<4, false, true>), dim3((n_traj + 3) / 4), dim3(256), 0, st, g, s, 0, (float4*)x,
-                       (const float4*)eps, (const float4*)noise, (float4*)chain, (const float4*)hard, spr);
+    launch(ddpm_guide_kernel<4, false, true>, (n_traj + 3) / 4, 256, 0, 0);
   } else if (guided && n_traj <= (s.coop_max > 0 ? s.coop_max : s.coop_max < 0 ? 0 : kCoopMaxTrajDefault)) {
     // four waves per trajectory (ddpm_guide_coop_kernel): the whole table of the trajectory's robot in LDS up to 60 KiB (+ the
     // exchange buffer: inside the 64 KiB a launch gets without an opt-in), the rest from L2
     const int fit = 60 * 1024 / bytes_per_slot;
     const int slots = g.max_slots < fit ? g.max_slots : fit;
-    auto kern = compact ? ddpm_guide_coop_kernel<true> : ddpm_guide_coop_kernel<false>;
-    hipLaunchKernelGGL(kern, dim3(n_traj), dim3(256), (size_t)slots * bytes_per_slot + COOP_XCH_BYTES, st, g, s, slots, (float4*)x,
-                       (const float4*)eps, (const float4*)noise, (float4*)chain, (const float4*)hard, spr);
+    launch(compact ? ddpm_guide_coop_kernel<true> : ddpm_guide_coop_kernel<false>, n_traj, 256,
+           (size_t)slots * bytes_per_slot + COOP_XCH_BYTES, slots);
   } else if (guided && g.max_slots > small && spr % 8 == 0 && traj0 % 8 == 0) {
     // 8 trajectories of one robot per workgroup (2048 trajectories = 256 workgroups = one per CU); LDS sized to the
     // largest table any robot can have (g.max_slots), the rest of a larger table is read from L2
@@ -682,12 +644,10 @@ int launch_step(const GuideDev& g, StepDev s, float* x, const float* eps, const 
                                 hipFuncAttributeMaxDynamicSharedMemorySize, LDS_SLOTS_MAX * H * 16);
       attr_devices.fetch_or(bit, std::memory_order_release);
     }
-    if (compact) launch(ddpm_guide_kernel<8, true>, 8, slots);
-    else launch(ddpm_guide_kernel<8, false>, 8, slots);
+    launch(compact ? ddpm_guide_kernel<8, true> : ddpm_guide_kernel<8, false>, (n_traj + 7) / 8, 512, (size_t)slots * bytes_per_slot, slots);
   } else {
     const int slots = guided ? small : 0;
-    if (compact) launch(ddpm_guide_kernel<4, true>, 4, slots);
-    else launch(ddpm_guide_kernel<4, false>, 4, slots);
+    launch(compact ? ddpm_guide_kernel<4, true> : ddpm_guide_kernel<4, false>, (n_traj + 3) / 4, 256, (size_t)slots * bytes_per_slot, slots);
   }
   return 0;
 }

@@ -9,8 +9,7 @@ namespace mmd {
 
 struct GuideDev {
   float nmin[4], nscale[4];          // x_u = ((clip(x)+1)/2) * nscale + nmin,  nscale = max - min
-  float lo[2], inv_dim[2];           // grid index = floor((p - lo) * inv_dim?  -- see sdf_cell: kept as division
-  float dim[2];
+  float lo[2], dim[2];               // grid index = floor((p - lo) / dim * n): a division, as the reference computes it
   int nx, ny, n_grids;
   const float4* grids;               // [n_maps][n_grids][nx][ny]
   const int* robot_map;

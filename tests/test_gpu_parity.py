@@ -852,8 +852,10 @@ def test_philox_noise_statistics():
 
 @pytest.mark.parametrize("n_robots,B", [(48, 4), (48, 8), (160, 16)])
 def test_guide_large_constraint_tables(n_robots, B):
-    """More constraint slots than the LDS staging holds (4-wave workgroups: 40; 16-wave workgroups: 144): the overflow
-    is read from the L2-resident table.  47 / 159 other robots + a hard group, both workgroup shapes, vs the oracle."""
+    """More constraint slots than the LDS staging holds: the overflow is read from the L2-resident table.  47 / 159 other robots
+    + a hard group vs the oracle.  Launches of 4, 8 and 16 trajectories: all three run the cooperative kernel (launches of <= 512
+    trajectories do), whose staging holds 60 slots of this table, so the 48-slot cases fit and the 160-slot case overflows; the
+    one-wave kernels' staging (40 / 144 slots) is covered by tests/test_gpu_guide_shapes.py."""
     starts, goals = synth.start_goal_circle(n_robots, 0.8)
     paths = synth.straight_line_paths(starts, goals, H)
     soft = cases.soft_group(paths, 1)
