@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define MMD_AMD_ABI_VERSION 7
+#define MMD_AMD_ABI_VERSION 8
 #define MMD_STATE_DIM 4
 #define MMD_HORIZON 64
 
@@ -87,6 +87,26 @@ int mmd_unet_forward(mmd_unet_t unet, const float* x_dev, int t, float* eps_dev,
  * environments/grid_map_sdf.py:84-114)
  * ---------------------------------------------------------------------------------------------------------- */
 
+/* The inter-robot soft constraints of a many-robot round as a CELL table (the alternative to the all-pairs ELL table of
+ * mmd_soft_constraints_from_paths, whose N - 1 slots per robot make a round's constraint work and memory grow with N^2): for every time
+ * step t and cell c of an nx x ny grid over the map, the robots whose best-path point at t lies in the 3 x 3 cells around c, in ascending
+ * robot id.  A point acts on a trajectory point only within `radius`, and a cell is at least (1 + 1/16) x radius wide, so the list of a
+ * trajectory point's own cell holds every robot that can act on it -- 10 to 20 candidates where the all-pairs table has N - 1 slots -- and
+ * the guided step on this table returns the SAME BITS as on the all-pairs table of the same paths.  One table serves every robot of a
+ * GPU: the step skips the entry of the trajectory's own robot, robot0 + its index in the call.  Fill the two arrays with
+ * mmd_bin_constraints_from_paths and hand the struct over in mmd_guide_desc.cons_bins. */
+typedef struct mmd_cons_bins {
+  float lo[2], inv_cell[2];          /* cell index = clamp((int)floorf((p - lo) * inv_cell), 0, n - 1), per axis, in fp32; cell =
+                                      * ix * ny + iy.  lo = the limits mmd_bin_constraints_from_paths was given, inv_cell[k] = the fp32
+                                      * quotient (float)n[k] / (hi[k] - lo[k]) */
+  int32_t nx, ny, n_all, robot0;     /* the grid, the number of robots in the table, the GLOBAL id of the call's first robot */
+  float radius, weight;              /* one radius for every point (as tables from mmd_soft_constraints_from_paths have), and the
+                                      * weight of the one constraint group every robot has */
+  const int32_t* cell_off_dev;       /* [H][nx * ny + 1]: list of (t, c) = entries [off[t][c], off[t][c + 1]) of time step t's segment */
+  const float* entries_dev;          /* [H][9 * n_all][4]: (qx, qy, bit pattern of the GLOBAL robot id, 0); a point is in at most 9
+                                      * lists, so a segment of 9 * n_all entries always fits */
+} mmd_cons_bins;
+
 typedef struct mmd_guide_desc {
   /* LimitsNormalizer (mmd/datasets/normalization.py:145-168): x_u = (clip(x,-1,1)+1)/2*(max-min)+min.
    * The clip is applied unconditionally (the reference clips only if the batch leaves [-1-1e-4, 1+1e-4]). */
@@ -136,6 +156,11 @@ typedef struct mmd_guide_desc {
    * max_grad_value) (the class default 0.1), 2 = clip_grad = False */
   int32_t clip_grad_rule;
   float max_grad_value;
+  /* The inter-robot constraints as a cell table (above) instead of the ELL table, or NULL: every guided step of mmd_guide_steps,
+   * mmd_ddpm_step, mmd_p_sample_loop, mmd_ddim_sample and mmd_p_sample_loop_ensemble then runs the binned step kernel, at every launch
+   * size.  Each robot has exactly one constraint group, of weight cons_bins->weight.  Errors: together with cons_ell_dev, with
+   * mmd_sampler_desc.robot_seeds_dev, or in a call of mmd_debug_ddpm_step_trace. */
+  const mmd_cons_bins* cons_bins;
 } mmd_guide_desc;
 
 /* Host helper: time-bucket one robot's constraint groups.  For group g (n_pts[g] points): q [n,2], t_range [n,2]
@@ -154,6 +179,15 @@ int mmd_pack_constraints(int n_groups, const int32_t* n_pts, const float* const*
 int mmd_soft_constraints_from_paths(const float* paths_dev, int n_all, int robot0, int n_local, int horizon,
                                     float radius, float weight, float* ell_out_dev, int32_t* grp_slot_off_dev,
                                     float* grp_weight_dev, int32_t* robot_grp_off_dev, void* stream);
+
+/* Device helper: the cell table of mmd_cons_bins from the same paths_dev [n_all, H, 2] (equal start times; time step 0 carries no
+ * constraint: empty lists, as the all-pairs table has no active point there).  lo / hi: the map's limits (host, [2]); points outside them
+ * go to the border cells.  nx, ny in [1, 64] with (hi - lo) / n >= (1 + 1/16) * radius on both axes (smaller cells are an error: a list
+ * could then miss an acting robot); n_all in [2, 4096].  mmd_cons_bins_bytes gives the sizes of the two arrays (and returns their sum).
+ * One launch on `stream`, one workgroup per time step, no atomics and no host synchronisation: the lists are deterministic. */
+size_t mmd_cons_bins_bytes(int n_all, int nx, int ny, size_t* off_bytes, size_t* entry_bytes);
+int mmd_bin_constraints_from_paths(const float* paths_dev, int n_all, int horizon, float radius, const float lo[2], const float hi[2],
+                                   int nx, int ny, int32_t* cell_off_dev, float* entries_dev, void* stream);
 
 /* n_steps x { x += guide(x); apply_hard_conditioning }  (guide_gradient_steps,
  * mmd/models/diffusion_models/sample_functions.py:89-107).  Hard conditions (apply_hard_conditioning,

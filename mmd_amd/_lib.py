@@ -5,7 +5,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libmmd_amd.so")
-ABI_VERSION = 7
+ABI_VERSION = 8
 HARD_ROWS_START_GOAL = (1 << 63) | 1     # hard_rows of MPD's {0: start, H-1: goal} (include/mmd_amd.h: bit t = support point t pinned)
 
 
@@ -14,6 +14,15 @@ def signed64(mask):
     mask = int(mask) & 0xFFFFFFFFFFFFFFFF
     return mask - (1 << 64) if mask >> 63 else mask
 
+
+
+class ConsBins(C.Structure):              # mmd_cons_bins
+    _fields_ = [
+        ("lo", C.c_float * 2), ("inv_cell", C.c_float * 2),
+        ("nx", C.c_int32), ("ny", C.c_int32), ("n_all", C.c_int32), ("robot0", C.c_int32),
+        ("radius", C.c_float), ("weight", C.c_float),
+        ("cell_off_dev", C.c_void_p), ("entries_dev", C.c_void_p),
+    ]
 
 
 class GuideDesc(C.Structure):
@@ -30,6 +39,7 @@ class GuideDesc(C.Structure):
         ("extra_spheres_dev", C.c_void_p), ("extra_boxes_dev", C.c_void_p),
         ("n_extra_spheres", C.c_int32), ("n_extra_boxes", C.c_int32),
         ("clip_grad_rule", C.c_int32), ("max_grad_value", C.c_float),
+        ("cons_bins", C.POINTER(ConsBins)),
     ]
 
 
@@ -104,6 +114,9 @@ _SIGNATURES = {
                                        C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int32)]),
     "mmd_soft_constraints_from_paths": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float,
                                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mmd_cons_bins_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    "mmd_bin_constraints_from_paths": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                                 C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mmd_guide_steps": (C.c_int, [C.POINTER(GuideDesc), C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_int,
                                   C.c_void_p, C.c_void_p]),
     "mmd_sampler_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int]),

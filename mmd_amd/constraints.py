@@ -177,3 +177,94 @@ def soft_constraints_from_paths(paths: torch.Tensor, robot0: int, n_local: int, 
                                                    float(radius), float(weight), ell.data_ptr(), gso.data_ptr(),
                                                    gw.data_ptr(), rgo.data_ptr())
     return ell, gso, gw, rgo, float(radius)
+
+
+BIN_CELL_SLACK = 1.0625          # a cell side is at least (1 + 1/16) x the radius (csrc/guide.hip: the cover argument above bin_cell)
+BIN_MAX_CELLS = 32               # per axis, of the default grid
+
+
+def bin_grid(limits, radius):
+    """(nx, ny) of the default cell grid of a cell-binned constraint table over `limits` = (lo [2], hi [2]): the finest grid, up to 32
+    cells per axis, whose cells are at least (1 + 1/16) x radius wide -- 15 x 15 on the [-1, 1]^2 maps at the vertex-constraint radius
+    0.12.  Raises if even one cell per axis would be too small."""
+    lo, hi = limits
+    if not radius > 0:
+        raise ValueError(f"bin_grid: radius must be positive, got {radius}")
+    n = []
+    for k in range(2):
+        extent = float(hi[k]) - float(lo[k])
+        cells = min(BIN_MAX_CELLS, int(np.floor(extent / (BIN_CELL_SLACK * float(radius)))))
+        if cells < 1:
+            raise ValueError(f"bin_grid: axis {k} of extent {extent} cannot hold a cell of {BIN_CELL_SLACK} x radius = "
+                             f"{BIN_CELL_SLACK * float(radius)}")
+        n.append(cells)
+    return tuple(n)
+
+
+def check_bin_grid(limits, radius, grid):
+    """Raise unless every cell of the nx x ny `grid` over `limits` is at least (1 + 1/16) x radius wide (the library's own rule)."""
+    lo, hi = limits
+    for k in range(2):
+        if int(grid[k]) < 1 or (float(hi[k]) - float(lo[k])) / int(grid[k]) < BIN_CELL_SLACK * float(radius):
+            raise ValueError(f"cell grid {tuple(grid)}: cells of axis {k} are smaller than {BIN_CELL_SLACK} x radius")
+
+
+class BinnedConstraints:
+    """A cell-binned inter-robot constraint table on the device (include/mmd_amd.h: mmd_cons_bins): owns the two device tensors and the
+    filled struct that GuideManagerTrajectoriesWithVelocity.set_binned_constraints hands to the guided step."""
+
+    def __init__(self, cell_off, entries, limits, grid, n_all, robot0, n_local, radius, weight):
+        self.cell_off, self.entries = cell_off, entries
+        self.grid, self.n_all, self.robot0, self.n_local = tuple(grid), int(n_all), int(robot0), int(n_local)
+        self.radius, self.weight = float(radius), float(weight)
+        b = _lib.ConsBins()
+        lo, hi = limits
+        for k in range(2):
+            b.lo[k] = float(lo[k])
+            # the fp32 quotient mmd_bin_constraints_from_paths built the table with
+            b.inv_cell[k] = float(np.float32(self.grid[k]) / (np.float32(hi[k]) - np.float32(lo[k])))
+        b.nx, b.ny, b.n_all, b.robot0 = self.grid[0], self.grid[1], self.n_all, self.robot0
+        b.radius, b.weight = self.radius, self.weight
+        b.cell_off_dev, b.entries_dev = cell_off.data_ptr(), entries.data_ptr()
+        self.struct = b
+
+    def lists(self):
+        """Host copy for tests and tools: (offsets [H, nx * ny + 1] int32, entries [H, 9 * n_all, 4] float32, ids [H, 9 * n_all] int32)."""
+        ent = self.entries.cpu().numpy()
+        return self.cell_off.cpu().numpy(), ent, np.ascontiguousarray(ent[..., 2]).view(np.int32)
+
+
+def bin_constraints_table(paths: torch.Tensor, radius, limits, grid):
+    """mmd_bin_constraints_from_paths: the (cell_off [H, nx * ny + 1] int32, entries [H, 9 * n_all, 4] float32) device tensors of the
+    cell table of `paths` [N, H, 2].  One launch on the current stream, no host synchronisation."""
+    lib = _lib.load()
+    n_all, (nx, ny) = paths.shape[0], (int(grid[0]), int(grid[1]))
+    cell_off = torch.empty((H, nx * ny + 1), dtype=torch.int32, device=paths.device)
+    entries = torch.empty((H, 9 * n_all, 4), dtype=torch.float32, device=paths.device)
+    ob, eb = C.c_size_t(), C.c_size_t()
+    lib.mmd_cons_bins_bytes(n_all, nx, ny, C.byref(ob), C.byref(eb))
+    assert ob.value == cell_off.numel() * 4 and eb.value == entries.numel() * 4
+    lo, hi = (C.c_float * 2)(*[float(v) for v in limits[0]]), (C.c_float * 2)(*[float(v) for v in limits[1]])
+    _lib.launch("mmd_bin_constraints_from_paths", paths, _lib.require_gpu(paths, "paths"), n_all, H, float(radius), lo, hi, nx, ny,
+                cell_off.data_ptr(), entries.data_ptr())
+    return cell_off, entries
+
+
+def binned_constraints_from_paths(paths: torch.Tensor, robot0: int, n_local: int, radius=VERTEX_CONSTRAINT_RADIUS, weight=2e-2,
+                                  limits=None, grid=None):
+    """The soft constraints of soft_constraints_from_paths as a cell table: per time step and map cell the robots near that cell
+    instead of N - 1 slots per robot, O(N) instead of O(N^2) work and memory per round, and the same bits out of the guided step.
+    paths [N, H, 2] un-normalised best-path positions of ALL robots on this device; the table serves the local robots
+    [robot0, robot0 + n_local).  limits = (lo, hi) of the map (default: environments.LIMITS), grid = (nx, ny) (default: bin_grid)."""
+    if limits is None:
+        from .environments import LIMITS
+        limits = LIMITS
+    n_all = paths.shape[0]
+    if paths.dim() != 3 or paths.shape[1] != H or paths.shape[2] != 2:
+        raise ValueError(f"binned_constraints_from_paths: paths [N, {H}, 2], got {tuple(paths.shape)}")
+    if not (n_all >= 2 and n_local >= 1 and robot0 >= 0 and robot0 + n_local <= n_all):
+        raise ValueError("binned_constraints_from_paths: bad robot range")
+    grid = bin_grid(limits, radius) if grid is None else tuple(int(v) for v in grid)
+    check_bin_grid(limits, radius, grid)
+    cell_off, entries = bin_constraints_table(paths, radius, limits, grid)
+    return BinnedConstraints(cell_off, entries, limits, grid, n_all, robot0, n_local, radius, weight)

@@ -173,6 +173,14 @@ static FusedStep fused_step(const StepDev& sd, float* x, const float* hard, cons
   return fs;
 }
 
+// The guide's cell table (mmd_guide_desc.cons_bins) for the steps of a sampling call, or NULL.  One table serves the robots
+// [robot0, robot0 + n_robots) of ONE instance: R planner calls batched through robot_seeds_dev are R instances, which it cannot describe.
+static int bins_of(const mmd_guide_desc* guide, const mmd_sampler_desc* s, const mmd_cons_bins** out) {
+  *out = guide ? guide->cons_bins : nullptr;
+  MMD_REQUIRE(!(*out && s->robot_seeds_dev), "cons_bins with per-robot seeds (robot_seeds_dev: batched planner calls) is not supported");
+  return 0;
+}
+
 // row k of an optional [steps][n][H][D] buffer (step noise, chain): null stays null
 template <class T>
 static inline T* row_of(T* buf, size_t k, size_t traj_floats) { return buf ? buf + k * traj_floats : nullptr; }
@@ -189,7 +197,10 @@ static int ddpm_step(mmd_unet_t unet, const mmd_sampler_desc* s, const mmd_guide
   StepDev sd{};
   if (int rc = make_step(s, i, guide != nullptr, sd)) return rc;
   sd.seed = seed; sd.draw = draw_index;
+  const mmd_cons_bins* bins = nullptr;
+  if (int rc = bins_of(guide, s, &bins)) return rc;
   if (trace_dev) {
+    MMD_REQUIRE(!bins, "mmd_debug_ddpm_step_trace: the decision dump reads the ELL table, not a cell table (cons_bins)");
     MMD_REQUIRE(sd.do_guide, "mmd_debug_ddpm_step_trace: step %d is not a guided one (t_start_guide %d)", i, s->t_start_guide);
     sd.guide_chain = reinterpret_cast<float4*>(guide_chain_dev);
     sd.guide_chain_stride = (long long)n * H;
@@ -202,7 +213,7 @@ static int ddpm_step(mmd_unet_t unet, const mmd_sampler_desc* s, const mmd_guide
   float* eps = eps_of(workspace_dev, unet, n);
   if (int rc = mmd_unet_forward_profiled(unet, x_dev, i < 0 ? 0 : i, eps, n, workspace_dev, mmd_unet_workspace_bytes(unet, n), prof, stream))
     return rc;
-  launch_step(g, sd, x_dev, eps, noise_dev, nullptr, hard_dev, 0, n, samples_per_robot, (hipStream_t)stream);
+  launch_step(g, sd, x_dev, eps, noise_dev, nullptr, hard_dev, 0, n, samples_per_robot, (hipStream_t)stream, bins);
   MMD_HIP_CHECK(hipGetLastError());
   return 0;
 }
@@ -262,6 +273,8 @@ int mmd_p_sample_loop(mmd_unet_t unet, const mmd_sampler_desc* s, const mmd_guid
   GuideDev g{};
   if (guide)
     if (int rc = fill_guide(guide, g)) return rc;
+  const mmd_cons_bins* bins = nullptr;
+  if (int rc = bins_of(guide, s, &bins)) return rc;
   launch_init(x_dev, chain_dev, hard_dev, s->hard_rows, init_noise, (unsigned long long)seed,
               reinterpret_cast<const unsigned long long*>(s->robot_seeds_dev), (long long)s->traj_index_base, n, samples_per_robot, st);
   const bool persist = (s->flags & MMD_SAMPLER_PERSIST) != 0, no_fused_step = (s->flags & MMD_SAMPLER_NO_FUSED_STEP) != 0;
@@ -334,7 +347,7 @@ int mmd_p_sample_loop(mmd_unet_t unet, const mmd_sampler_desc* s, const mmd_guid
     for (int c = 0; c < nch && rc == 0 && !fused; ++c) {
       const int t0 = r0[c] * samples_per_robot, nc = (r0[c + 1] - r0[c]) * samples_per_robot;
       const bool br = prof_begin(prof, 1, sd.do_guide ? MMD_PROF_STEP_GUIDED : MMD_PROF_STEP_PLAIN, cs[c]);
-      launch_step(g, sd, x_dev, eps, noise_k, chain_k, hard_dev, t0, nc, samples_per_robot, cs[c]);
+      launch_step(g, sd, x_dev, eps, noise_k, chain_k, hard_dev, t0, nc, samples_per_robot, cs[c], bins);
       if (br) prof_end(prof, cs[c]);
     }
   }
@@ -359,6 +372,7 @@ int mmd_p_sample_loop_ensemble(const mmd_ensemble_tile* tiles, int n_tiles, cons
   hipStream_t st = (hipStream_t)stream;
   const size_t traj_floats = (size_t)n * H * D;
   GuideDev g[8];
+  const mmd_cons_bins* bins[8];
   MMD_REQUIRE(n_tiles <= 8, "mmd_p_sample_loop_ensemble: at most 8 tiles");
   for (int m = 0; m < n_tiles; ++m) {
     const mmd_ensemble_tile& T = tiles[m];
@@ -368,6 +382,7 @@ int mmd_p_sample_loop_ensemble(const mmd_ensemble_tile* tiles, int n_tiles, cons
     g[m] = GuideDev{};
     if (T.guide)
       if (int rc = fill_guide(T.guide, g[m])) return rc;
+    if (int rc = bins_of(T.guide, T.sampler, &bins[m])) return rc;
   }
   for (int c = 0; c < n_cross; ++c)
     MMD_REQUIRE(cross[c].m1 >= 0 && cross[c].m1 < n_tiles && cross[c].m2 >= 0 && cross[c].m2 < n_tiles &&
@@ -413,7 +428,7 @@ int mmd_p_sample_loop_ensemble(const mmd_ensemble_tile* tiles, int n_tiles, cons
       if (int rc = unet_forward_fused(T.unet, T.x_dev, i < 0 ? 0 : i, eps, n, workspace_dev, uws, prof, st,
                                       fused ? fused_step(sd, T.x_dev, T.hard_dev, noise_k, chain_k, 0, samples_per_robot) : FusedStep{}))
         return rc;
-      if (!fused) launch_step(g[m], sd, T.x_dev, eps, noise_k, chain_k, T.hard_dev, 0, n, samples_per_robot, st);
+      if (!fused) launch_step(g[m], sd, T.x_dev, eps, noise_k, chain_k, T.hard_dev, 0, n, samples_per_robot, st, bins[m]);
       cross_all(k + 1, m);
     }
   }
@@ -437,6 +452,8 @@ int mmd_ddim_sample(mmd_unet_t unet, const mmd_sampler_desc* s, const float* alp
   GuideDev g{};
   if (guide)
     if (int rc = fill_guide(guide, g)) return rc;
+  const mmd_cons_bins* bins = nullptr;
+  if (int rc = bins_of(guide, s, &bins)) return rc;
   launch_init(x_dev, chain_dev, hard_dev, s->hard_rows, init_noise, (unsigned long long)seed,
               reinterpret_cast<const unsigned long long*>(s->robot_seeds_dev), (long long)s->traj_index_base, n, samples_per_robot, st);
   for (int k = 0; k + 1 < n_times; ++k) {
@@ -445,7 +462,7 @@ int mmd_ddim_sample(mmd_unet_t unet, const mmd_sampler_desc* s, const float* alp
     StepDev sd = make_ddim_step(s, alphas_cumprod, t, tn, guide != nullptr);
     sd.seed = seed; sd.draw = (unsigned int)k;
     if (int rc = mmd_unet_forward_profiled(unet, x_dev, t, eps, n, workspace_dev, uws, prof, stream)) return rc;
-    launch_step(g, sd, x_dev, eps, nullptr, row_of(chain_dev, k + 1, traj_floats), hard_dev, 0, n, samples_per_robot, st);
+    launch_step(g, sd, x_dev, eps, nullptr, row_of(chain_dev, k + 1, traj_floats), hard_dev, 0, n, samples_per_robot, st, bins);
     if (tn < 0) break;
   }
   MMD_HIP_CHECK(hipGetLastError());

@@ -162,6 +162,7 @@ __device__ __forceinline__ f32x2g cons_accumulate1(f32x2g a, const TAB& tab, int
 // cannot keep them -- in front of its first slot (a robot has one or two groups: soft constraints from the other robots, hard ones from a
 // conflict).  Wave-uniform values, selected by wave-uniform branches.
 struct GroupMeta {
+  static constexpr bool kOneGroup = false;
   int s0[2], s1[2];
   float w[2];
   int grp0, n;
@@ -374,17 +375,20 @@ __device__ __forceinline__ float4 model_update(StepDev s, float4 v, const float4
 // The guide iterations (guide_gradient_steps, sample_functions.py:89-107) on the lane's point of a trajectory of `robot`: its map's grids
 // and its constraint groups, then per iteration v += grad_scale * guide_grad(v), pinned rows pinned again, the state -> guide_chain where
 // `store`.  group_sum(gm, grp, p) is the kernel's evaluation of the canonical slot sum of group grp at p.
-template <bool DUMP, class GROUPSUM>
+template <bool DUMP, class META = GroupMeta, class GROUPSUM>
 __device__ __forceinline__ void guide_iterations(const GuideDev& g, const StepDev& s, int robot, int t, size_t idx, float4& v, bool is_hard,
                                                  float4 hv, bool store, GROUPSUM group_sum) {
   const int map = g.robot_map ? g.robot_map[robot] : 0;
   const float4* grid = g.grids + (size_t)map * g.n_grids * g.nx * g.ny;
   int grp0 = 0, grp1 = 0;
-  if (g.robot_grp_off) {
+  if constexpr (META::kOneGroup) {
+    grp1 = 1;
+  } else if (g.robot_grp_off) {
     grp0 = __builtin_amdgcn_readfirstlane(g.robot_grp_off[robot]);
     grp1 = __builtin_amdgcn_readfirstlane(g.robot_grp_off[robot + 1]);
   }
-  GroupMeta gm;
+  META gm;
+  if constexpr (META::kOneGroup) gm.w = group_sum.weight;
   gm.load(g, grp0, grp1);
   for (int it = 0; it < s.n_guide_steps; ++it) {
     unsigned int* tr = nullptr;
@@ -498,6 +502,101 @@ __global__ __launch_bounds__(256) void ddpm_guide_coop_kernel(GuideDev g, StepDe
   step_finish(s, x, noise, chain, idx, robot, samples_per_robot, v, is_hard, hv);
 }
 
+// ---- The cell-binned inter-robot table (include/mmd_amd.h: mmd_cons_bins): per time step and map cell the robots whose point lies in
+// ---- the cell's 3 x 3 neighbourhood, instead of the all-pairs table's N - 1 slots per robot.
+//
+// Cell index of a coordinate, per axis, in fp32: clamp(floor((p - lo) * inv_cell), 0, n - 1).  (Clamped as a float and then converted:
+// the same integer as clamp((int)floorf(..), 0, n - 1) wherever that conversion is defined, and defined for every p.)  Not contracted:
+// there is no add behind the product.  The build kernel and the step kernel run this one function.
+//
+// COVER: a lane at p needs every table point q that cons_term accepts, i.e. with fma(dx, dx, dy * dy) <= R|R| in fp32, and it reads the
+// list of its own cell, which holds the points of the 3 x 3 cells around it: so |cell(p) - cell(q)| <= 1 per axis must hold for every
+// accepted pair.  dx * dx <= fma(dx, dx, dy * dy) (1 + 2^-23) and R|R| = R^2 (1 +- 2^-24) give |dx| <= R (1 + 2^-22): at most a few ulp
+// over R.  u(p) = fl((p - lo) * inv_cell) is monotone in p (two correctly rounded monotone operations) and differs from the exact
+// (p - lo) / cell by at most a few ulp of a value <= n <= 64, i.e. by < 1e-5, whereas cell >= (1 + 1/16) R puts the exact coordinates of
+// p and q at most (1 + 2^-22) / (1 + 1/16) < 0.9412 apart: |u(p) - u(q)| < 0.95 < 1, so the floors differ by at most 1.  The slack of
+// 1/16 is four orders of magnitude above both error terms.  Outside [lo, hi] the clamp maps an index to the nearest valid one: clamping is
+// monotone and 1-Lipschitz on the integers, so "differ by at most 1" survives it (mmd_bin_constraints_from_paths rejects smaller cells).
+//
+// SAME BITS as the all-pairs table: the dense slot sum of robot `self` is four fma chains, accumulator k over the slots rel = k, k + 4,
+// ... in increasing order (Acc4 above), slot rel = robot id - (id > self).  A chain starts at +0 and a slot that does not act contributes
+// a <- fma(-d, 0, a) = a + (-+0): that is a itself when a != 0, and +0 when a = +0 (round to nearest: +0 + -0 = +0); a chain never holds
+// -0, because an fma whose exact result is zero rounds to +0 unless both addends are -0, the chain's addend a is never -0 by induction,
+// and a nonzero exact result cannot round to zero (an acting slot has m >= (1 - 2^-22) / R > 1/2 on these maps, so |d m| > 2^-150 for
+// every d != 0, subnormal ones included).  So a chain's value is fixed by its ACTING slots in increasing rel.  Every acting slot is in the lane's list (cover), a list
+// is in ascending robot id, hence ascending rel, and an entry goes to accumulator rel & 3 through cons_term itself: entry for entry the
+// acting fmas of the dense chain in the dense order.  Entries that do not act -- too far, the robot itself (one table serves every robot
+// of the GPU), the padding of a lane whose list has ended -- run cons_term with m = 0 and leave their accumulator's bits alone.  (p is
+// finite: the unnormaliser clips.  Time step 0 has empty lists where the dense table has R = -1.)
+__device__ __forceinline__ int bin_cell(float p, float lo, float inv_cell, int n) {
+  return (int)fminf(fmaxf(floorf((p - lo) * inv_cell), 0.f), (float)(n - 1));
+}
+
+// the one constraint group a robot has under a cell table: no group tables to read, its weight is the table's
+struct OneGroup {
+  static constexpr bool kOneGroup = true;
+  float w;
+  __device__ __forceinline__ void load(const GuideDev&, int, int) {}
+  __device__ __forceinline__ float weight(const GuideDev&, int) const { return w; }
+};
+
+// group_sum of the cell table at the lane's point p (time step t, the lane's robot = global id `self`).  The wave walks the lists four
+// entries a trip -- the loads of a trip are issued together -- while any lane has entries left.
+struct BinnedSum {
+  const mmd_cons_bins& b;
+  int t, self;
+  float r2, weight;
+  __device__ __forceinline__ f32x2g operator()(const OneGroup&, int, f32x2g p) const {
+    const int cell = bin_cell(p.x, b.lo[0], b.inv_cell[0], b.nx) * b.ny + bin_cell(p.y, b.lo[1], b.inv_cell[1], b.ny);
+    const int* off = b.cell_off_dev + (size_t)t * (b.nx * b.ny + 1) + cell;
+    const int e0 = off[0], e1 = off[1];
+    const float4* ent = reinterpret_cast<const float4*>(b.entries_dev) + (size_t)t * 9 * b.n_all;
+    const float4 none = make_float4(0.f, 0.f, __builtin_bit_cast(float, self), 0.f);     // (carries the lane's own id: skipped)
+    Acc4 acc = acc4_zero();
+    const int last = max(e1 - 1, 0);                                                     // (a lane past its list re-reads an entry of
+    for (int e = e0; __builtin_amdgcn_ballot_w64(e < e1) != 0; e += 4) {                 //  the segment and drops it: no branch, no stray read)
+      float4 c[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const float4 l = ent[min(e + j, last)];
+        c[j] = e + j < e1 ? l : none;
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int id = __builtin_bit_cast(int, c[j].z);
+        const int k = (id - (id > self ? 1 : 0)) & 3;
+        f32x2g a = k == 0 ? acc.a0 : k == 1 ? acc.a1 : k == 2 ? acc.a2 : acc.a3;
+        a = cons_term(a, p, f32x2g{c[j].x, c[j].y}, id != self ? r2 : -1.f);            // (-1 < 0 <= d2: m = 0)
+        acc.a0 = k == 0 ? a : acc.a0;
+        acc.a1 = k == 1 ? a : acc.a1;
+        acc.a2 = k == 2 ? a : acc.a2;
+        acc.a3 = k == 3 ? a : acc.a3;
+      }
+    }
+    return acc4_total(acc);
+  }
+};
+
+// The step of ddpm_guide_kernel<4, ..> with the inter-robot term from a cell table: one wave per trajectory, lane = support point, four
+// trajectories a workgroup; no LDS.  The robot's only group is the table's.  Bitwise the step on the all-pairs table of the same paths.
+__global__ __launch_bounds__(256) void ddpm_guide_binned_kernel(GuideDev g, StepDev s, mmd_cons_bins b, float4* __restrict__ x,
+                                                                const float4* __restrict__ eps, const float4* __restrict__ noise,
+                                                                float4* __restrict__ chain, const float4* __restrict__ hard,
+                                                                int samples_per_robot) {
+  const int t = threadIdx.x & 63;
+  const int traj = s.traj0 + blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (traj >= s.traj_end) return;
+  const int robot = traj / samples_per_robot;
+  const size_t idx = (size_t)traj * H + t;
+  float4 v = model_update(s, x[idx], eps, idx);
+  float4 hv = v;
+  const bool is_hard = hard_row(s.hard_rows, s.n_hard, hard, robot, t, hv);
+  if (s.do_guide)
+    guide_iterations<false, OneGroup>(g, s, robot, t, idx, v, is_hard, hv, true,
+                                      BinnedSum{b, t, b.robot0 + robot, b.radius * fabsf(b.radius), b.weight});
+  step_finish(s, x, noise, chain, idx, robot, samples_per_robot, v, is_hard, hv);
+}
+
 // x <- conditioned init: optional Philox draw of x_T, apply_hard_conditioning, optional chain[0] write
 __global__ void init_kernel(float4* __restrict__ x, float4* __restrict__ chain, const float4* __restrict__ hard,
                             unsigned long long hard_rows, int draw_noise, unsigned long long seed,
@@ -570,8 +669,82 @@ __global__ void soft_cons_kernel(const float2* __restrict__ paths, int n_all, in
   }
 }
 
+// The cell table of mmd_cons_bins from the best paths: ONE workgroup per time step t, no atomics, so a list is in ascending robot id by
+// construction.  The step's n_all points and cell indices (ix << 16 | iy) are staged in LDS; thread i owns the cells [i cpt, (i + 1) cpt)
+// (cell = ix * ny + iy) and walks the robots 0 .. n_all - 1 in order twice: to count its cells' entries and, after the block's prefix
+// sum, to write them.  A robot is in the lists of the (at most nine) cells within one index of its own, so a time step's lists fit its
+// segment of 9 n_all entries.  Time step 0 has no constraint (soft_cons_kernel: t in [1, H - 1]): empty lists.
+constexpr int BIN_THREADS = 256;
+__global__ __launch_bounds__(BIN_THREADS) void bin_cons_kernel(const float2* __restrict__ paths, int n_all, float lo0, float lo1, float inv0,
+                                                               float inv1, int nx, int ny, int* __restrict__ cell_off,
+                                                               float4* __restrict__ entries) {
+  extern __shared__ __attribute__((aligned(16))) float2 lds_pts[];       // [n_all] points, [n_all] cells, [BIN_THREADS] scan
+  int* const lds_cell = reinterpret_cast<int*>(lds_pts + n_all);
+  int* const scan = lds_cell + n_all;
+  const int t = blockIdx.x, tid = threadIdx.x, ncell = nx * ny;
+  int* const off = cell_off + (size_t)t * (ncell + 1);
+  if (t == 0) {
+    for (int c = tid; c <= ncell; c += BIN_THREADS) off[c] = 0;
+    return;
+  }
+  for (int r = tid; r < n_all; r += BIN_THREADS) {
+    const float2 p = paths[(size_t)r * H + t];
+    lds_pts[r] = p;
+    lds_cell[r] = bin_cell(p.x, lo0, inv0, nx) << 16 | bin_cell(p.y, lo1, inv1, ny);
+  }
+  __syncthreads();
+  const int cpt = (ncell + BIN_THREADS - 1) / BIN_THREADS;
+  const int c0 = min(tid * cpt, ncell), c1 = min(c0 + cpt, ncell);
+  auto near = [&](int rc, int ix, int iy) { return abs((rc >> 16) - ix) <= 1 && abs((rc & 0xffff) - iy) <= 1; };
+  int cnt = 0;
+  for (int c = c0; c < c1; ++c) {
+    const int ix = c / ny, iy = c - ix * ny;
+    for (int r = 0; r < n_all; ++r) cnt += near(lds_cell[r], ix, iy) ? 1 : 0;
+  }
+  scan[tid] = cnt;
+  __syncthreads();
+  for (int d = 1; d < BIN_THREADS; d <<= 1) {                            // inclusive prefix sum over the threads
+    const int add = tid >= d ? scan[tid - d] : 0;
+    __syncthreads();
+    scan[tid] += add;
+    __syncthreads();
+  }
+  int pos = scan[tid] - cnt;
+  float4* const seg = entries + (size_t)t * 9 * n_all;
+  for (int c = c0; c < c1; ++c) {
+    const int ix = c / ny, iy = c - ix * ny;
+    off[c] = pos;
+    for (int r = 0; r < n_all; ++r)
+      if (near(lds_cell[r], ix, iy)) {
+        const float2 p = lds_pts[r];
+        seg[pos++] = make_float4(p.x, p.y, __builtin_bit_cast(float, r), 0.f);
+      }
+  }
+  if (tid == BIN_THREADS - 1) off[ncell] = scan[tid];
+}
+
+constexpr int BIN_MAX_ROBOTS = 4096;     // 12 B of LDS per robot in bin_cons_kernel
+constexpr int BIN_MAX_CELLS = 64;        // per axis
+
+// a cell table as a guided step may use it (every field but the two device arrays' contents)
+static int check_cons_bins(const mmd_cons_bins* b) {
+  MMD_REQUIRE(b->cell_off_dev && b->entries_dev, "cons_bins: NULL table");
+  MMD_REQUIRE(b->nx >= 1 && b->nx <= BIN_MAX_CELLS && b->ny >= 1 && b->ny <= BIN_MAX_CELLS, "cons_bins: grid %d x %d outside [1, %d]", b->nx,
+              b->ny, BIN_MAX_CELLS);
+  MMD_REQUIRE(b->n_all >= 2 && b->robot0 >= 0 && b->robot0 < b->n_all, "cons_bins: bad robot range");
+  MMD_REQUIRE(b->radius > 0.f, "cons_bins: radius must be positive");
+  for (int k = 0; k < 2; ++k)
+    MMD_REQUIRE(b->inv_cell[k] > 0.f && 1.0 / (double)b->inv_cell[k] >= 1.0625 * (double)b->radius * (1.0 - 1e-6),
+                "cons_bins: cells smaller than (1 + 1/16) x the radius");
+  return 0;
+}
+
 int fill_guide(const mmd_guide_desc* d, GuideDev& g) {
   MMD_REQUIRE(d->n_grids == 0 || (d->sdf_grids_dev && d->grid_nx >= 1 && d->grid_ny >= 1), "guide: SDF grid missing");
+  if (d->cons_bins) {
+    MMD_REQUIRE(!d->cons_ell_dev, "guide: cons_bins together with an ELL table (cons_ell_dev) is not supported");
+    if (int rc = check_cons_bins(d->cons_bins)) return rc;
+  }
   for (int k = 0; k < 4; ++k) { g.nmin[k] = d->norm_min[k]; g.nscale[k] = d->norm_max[k] - d->norm_min[k]; }
   for (int k = 0; k < 2; ++k) {
     g.lo[k] = d->limits_lo[k];
@@ -604,9 +777,15 @@ int fill_guide(const mmd_guide_desc* d, GuideDev& g) {
 constexpr int kCoopMaxTrajDefault = 512;
 
 int launch_step(const GuideDev& g, StepDev s, float* x, const float* eps, const float* noise, float* chain,
-                const float* hard, int traj0, int n_traj, int spr, hipStream_t st) {
+                const float* hard, int traj0, int n_traj, int spr, hipStream_t st, const mmd_cons_bins* bins) {
   s.traj0 = traj0;
   s.traj_end = traj0 + n_traj;
+  if (bins && s.do_guide) {
+    // the inter-robot term from a cell table (checked by fill_guide; its callers have refused a trace): one kernel at every launch size
+    hipLaunchKernelGGL(ddpm_guide_binned_kernel, dim3((n_traj + 3) / 4), dim3(256), 0, st, g, s, *bins, (float4*)x, (const float4*)eps,
+                       (const float4*)noise, (float4*)chain, (const float4*)hard, spr);
+    return 0;
+  }
   const bool guided = s.do_guide && g.robot_grp_off;
   // LDS staging of the workgroup's robot's table: 16 B per (slot, t), or 8 B when every active point has the same radius
   const bool compact = guided && g.uniform_r2 > 0.f;
@@ -725,6 +904,39 @@ int mmd_soft_constraints_from_paths(const float* paths_dev, int n_all, int robot
   return 0;
 }
 
+size_t mmd_cons_bins_bytes(int n_all, int nx, int ny, size_t* off_bytes, size_t* entry_bytes) {
+  const bool ok = n_all >= 0 && nx >= 1 && ny >= 1;
+  const size_t ob = ok ? (size_t)H * ((size_t)nx * ny + 1) * sizeof(int32_t) : 0;
+  const size_t eb = ok ? (size_t)H * 9 * n_all * 4 * sizeof(float) : 0;
+  if (off_bytes) *off_bytes = ob;
+  if (entry_bytes) *entry_bytes = eb;
+  return ob + eb;
+}
+
+int mmd_bin_constraints_from_paths(const float* paths_dev, int n_all, int horizon, float radius, const float lo[2], const float hi[2],
+                                   int nx, int ny, int32_t* cell_off_dev, float* entries_dev, void* stream) {
+  MMD_REQUIRE(paths_dev && lo && hi && cell_off_dev && entries_dev, "mmd_bin_constraints_from_paths: NULL argument");
+  MMD_REQUIRE(horizon == H, "horizon must be %d", H);
+  MMD_REQUIRE(n_all >= 2 && n_all <= BIN_MAX_ROBOTS, "mmd_bin_constraints_from_paths: n_all must be in [2, %d]", BIN_MAX_ROBOTS);
+  MMD_REQUIRE(radius > 0.f, "mmd_bin_constraints_from_paths: radius must be positive");
+  MMD_REQUIRE(nx >= 1 && nx <= BIN_MAX_CELLS && ny >= 1 && ny <= BIN_MAX_CELLS, "mmd_bin_constraints_from_paths: grid %d x %d outside [1, %d]",
+              nx, ny, BIN_MAX_CELLS);
+  const int n[2] = {nx, ny};
+  float inv[2];
+  for (int k = 0; k < 2; ++k) {
+    MMD_REQUIRE(hi[k] > lo[k], "mmd_bin_constraints_from_paths: empty limits");
+    // the cover argument above bin_cell needs (1 + 1/16) R <= the cell side
+    MMD_REQUIRE(((double)hi[k] - (double)lo[k]) / n[k] >= 1.0625 * (double)radius,
+                "mmd_bin_constraints_from_paths: cells smaller than (1 + 1/16) x the radius (axis %d: %g < %g)", k,
+                ((double)hi[k] - (double)lo[k]) / n[k], 1.0625 * (double)radius);
+    inv[k] = (float)n[k] / (hi[k] - lo[k]);                  // mmd_cons_bins.inv_cell: this fp32 quotient
+  }
+  hipLaunchKernelGGL(bin_cons_kernel, dim3(H), dim3(BIN_THREADS), (size_t)n_all * 12 + BIN_THREADS * sizeof(int), (hipStream_t)stream,
+                     (const float2*)paths_dev, n_all, lo[0], lo[1], inv[0], inv[1], nx, ny, cell_off_dev, (float4*)entries_dev);
+  MMD_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
 int mmd_guide_steps(const mmd_guide_desc* d, float* x_dev, const float* hard_dev, uint64_t hard_rows, int n_robots,
                     int samples_per_robot, int n_steps, float* chain_dev, void* stream) {
   MMD_REQUIRE(d && x_dev && hard_dev, "mmd_guide_steps: NULL argument");
@@ -735,7 +947,7 @@ int mmd_guide_steps(const mmd_guide_desc* d, float* x_dev, const float* hard_dev
   s.guide_chain = reinterpret_cast<float4*>(chain_dev);
   s.guide_chain_stride = (long long)n_robots * samples_per_robot * H;
   launch_step(g, s, x_dev, nullptr, nullptr, nullptr, hard_dev, 0, n_robots * samples_per_robot, samples_per_robot,
-              (hipStream_t)stream);
+              (hipStream_t)stream, d->cons_bins);
   MMD_HIP_CHECK(hipGetLastError());
   return 0;
 }

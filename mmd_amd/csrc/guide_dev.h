@@ -204,8 +204,9 @@ bool unet_fused_step_supported(mmd_unet_t u);
 int unet_forward_fused(mmd_unet_t u, const float* x, int t, float* eps, int n, void* ws, size_t ws_bytes, Profiler* prof,
                        hipStream_t st, const FusedStep& fs);
 int unet_persist_steps(mmd_unet_t u, int n, void* ws, size_t ws_bytes, hipStream_t st, const FusedStep* steps, int n_steps);
+// bins: the guide's cell table (mmd_guide_desc.cons_bins, checked by fill_guide) or NULL: a guided step then runs the binned kernel
 int launch_step(const GuideDev& g, StepDev s, float* x, const float* eps, const float* noise, float* chain,
-                const float* hard, int traj0, int n_traj, int spr, hipStream_t st);
+                const float* hard, int traj0, int n_traj, int spr, hipStream_t st, const mmd_cons_bins* bins);
 int launch_init(float* x, float* chain, const float* hard, unsigned long long hard_rows, int draw, unsigned long long seed,
                 const unsigned long long* robot_seeds, long long traj_base, int n_traj, int spr, hipStream_t st);
 

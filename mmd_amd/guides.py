@@ -84,6 +84,7 @@ class GuideManagerTrajectoriesWithVelocity:
         self._cons_dirty = True
         self._external_cons = None
         self._soft_paths = None
+        self._binned = None
         self._max_slots = 0
         self._norm_limits = None
 
@@ -99,6 +100,7 @@ class GuideManagerTrajectoriesWithVelocity:
         self._cons_dirty = True
         self._external_cons = None
         self._soft_paths = None
+        self._binned = None
 
     def set_soft_paths(self, paths_all, self_index, radius=None, weight=2e-2):
         """The soft constraints from the OTHER agents' current best paths (cbs.py:468-508 for equal start times: every point t >= 1 of
@@ -120,6 +122,15 @@ class GuideManagerTrajectoriesWithVelocity:
         """Use device-built constraint tensors (constraints.soft_constraints_from_paths) instead of host-packed ones."""
         self._external_cons = cons
         self._max_slots = 0
+
+    def set_binned_constraints(self, binned):
+        """The inter-robot soft constraints as a cell table (constraints.binned_constraints_from_paths) instead of the all-pairs table of
+        set_packed_constraints: every guided step then runs the binned kernel, with the same bits out.  The table is the robots' ONLY
+        constraint group: it does not combine with add_extra_costs / set_soft_paths / set_packed_constraints (the library refuses the
+        mix); reset_extra_costs clears it."""
+        if binned is not None and binned.n_local != self.n_robots:
+            raise ValueError(f"set_binned_constraints: a table for {binned.n_local} local robots on a guide of {self.n_robots}")
+        self._binned = binned
 
     def _constraints(self):
         if self._external_cons is not None:
@@ -183,6 +194,8 @@ class GuideManagerTrajectoriesWithVelocity:
             # upper bound of the slots any one robot owns (exact when robots own equal shares, as the all-pairs table)
             d.max_slots_per_robot = int(self._max_slots) if self._max_slots else -(-ell.shape[0] // max(self.n_robots, 1))
             self._keep = cons
+        if self._binned is not None:
+            d.cons_bins = C.pointer(self._binned.struct)          # (the object outlives the call: the guide holds it)
         return d
 
     # ---- guide_gradient_steps / forward -----------------------------------------------------------------------

@@ -5,14 +5,16 @@ per planning round, sharded over GPUs by robot.
 Robots are independent inside a sampling call (other robots enter only as frozen constraint points), so
 rank g owns robots [g*n_local, (g+1)*n_local) and the only exchange is ONE all-gather per round of the chosen best
 paths [n_local, H, 2] -> [N, H, 2] (RCCL over xGMI on GPUs, gloo in the CPU tests), after which every rank rebuilds
-its robots' soft-constraint table on device (mmd_soft_constraints_from_paths).
+its robots' soft-constraint table on device (mmd_soft_constraints_from_paths: N - 1 slots per robot; or, with
+constraint_table="binned", mmd_bin_constraints_from_paths: per time step and map cell the robots near the cell -- O(N) work and
+memory per round instead of O(N^2), the same bits).
 """
 from math import ceil
 
 import torch
 
 from . import synth
-from .constraints import VERTEX_CONSTRAINT_RADIUS, soft_constraints_from_paths
+from .constraints import VERTEX_CONSTRAINT_RADIUS, binned_constraints_from_paths, soft_constraints_from_paths
 from .diffusion_model import ddpm_sample_fn
 from .guides import GuideManagerTrajectoriesWithVelocity
 from .normalization import TrajectoryDatasetFacade
@@ -56,7 +58,11 @@ class MultiRobotSampler:
                  norm_mins=synth.NORM_MINS, norm_maxs=synth.NORM_MAXS, n_guide_steps=20,
                  start_guide_steps_fraction=0.5, n_diffusion_steps_without_noise=1,
                  weight_grad_cost_soft_constraints=2e-2, radius=VERTEX_CONSTRAINT_RADIUS, device="cuda", group=None,
-                 n_streams=0, inter_robot=True):
+                 n_streams=0, inter_robot=True, constraint_table="dense"):
+        if constraint_table not in ("dense", "binned"):
+            raise ValueError(f"constraint_table must be 'dense' or 'binned', got {constraint_table!r}")
+        # "dense": the all-pairs table; "binned": the cell table (constraints.binned_constraints_from_paths), for rounds of hundreds of robots
+        self.constraint_table = constraint_table
         self.model = model
         self.n_robots = starts.shape[0]
         self.rank, self.world_size, self.group = rank, world_size, group
@@ -86,6 +92,10 @@ class MultiRobotSampler:
         """paths_all [N,H,2] un-normalised best paths of ALL robots (this device) or None (no inter-robot term)."""
         if paths_all is None or self.n_robots < 2:
             self.guide.reset_extra_costs()
+        elif self.constraint_table == "binned":
+            self.guide.reset_extra_costs()
+            self.guide.set_binned_constraints(binned_constraints_from_paths(
+                paths_all.contiguous(), self.robot0, self.n_local, self.radius, self.w_soft))
         else:
             self.guide.set_packed_constraints(soft_constraints_from_paths(
                 paths_all.contiguous(), self.robot0, self.n_local, self.radius, self.w_soft))

@@ -1,5 +1,5 @@
 """PyTorch-ROCm custom ops over the C ABI (include/mmd_amd.h): `torch.ops.mmd_amd.{unet_forward, guide_steps,
-p_sample_loop, ddim_sample, solution_stats}`.  They take tensors instead of raw pointers, run on torch's CURRENT HIP stream
+p_sample_loop, ddim_sample, solution_stats, bin_constraints_from_paths}`.  They take tensors instead of raw pointers, run on torch's CURRENT HIP stream
 without any host synchronisation (so they can be captured into a hipGraph with torch.cuda.graph) and register fake
 (meta) implementations so that torch.compile / FakeTensor tracing sees their output shapes.  The C header stays the ABI
 of record: every op is a thin wrapper over the same entry point the host mirror classes call through ctypes.
@@ -11,6 +11,7 @@ holds weak references, so a token dies with its object.
 import ctypes as C
 import itertools
 import weakref
+from typing import Tuple
 
 import torch
 
@@ -160,3 +161,21 @@ def solution_stats(paths: torch.Tensor, tiles: torch.Tensor, collision_dist: flo
 @solution_stats.register_fake
 def _(paths, tiles, collision_dist):
     return paths.new_empty(1 + 2 * paths.shape[0] + tiles.shape[0])
+
+
+# ---- bin_constraints_from_paths ------------------------------------------------------------------------------------
+@torch.library.custom_op("mmd_amd::bin_constraints_from_paths", mutates_args=(), device_types="cuda")
+def bin_constraints_from_paths(paths: torch.Tensor, radius: float, lo_x: float, lo_y: float, hi_x: float, hi_y: float, nx: int,
+                               ny: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The cell-binned inter-robot constraint table of the best paths [n_all, 64, 2] (mmd_bin_constraints_from_paths; include/mmd_amd.h:
+    mmd_cons_bins): (cell_off int32 [64, nx ny + 1], entries float32 [64, 9 n_all, 4] of (qx, qy, bit pattern of the robot id, 0))."""
+    from . import constraints
+    if not (paths.is_cuda and paths.dtype == torch.float32 and paths.is_contiguous() and paths.ndim == 3 and paths.shape[1] == 64
+            and paths.shape[2] == 2):
+        raise RuntimeError("mmd_amd op: paths must be a contiguous float32 CUDA(HIP) tensor [n_all, 64, 2]")
+    return constraints.bin_constraints_table(paths, radius, ((lo_x, lo_y), (hi_x, hi_y)), (nx, ny))
+
+
+@bin_constraints_from_paths.register_fake
+def _(paths, radius, lo_x, lo_y, hi_x, hi_y, nx, ny):
+    return (paths.new_empty((64, nx * ny + 1), dtype=torch.int32), paths.new_empty((64, 9 * paths.shape[0], 4)))
