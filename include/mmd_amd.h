@@ -224,7 +224,14 @@ typedef struct mmd_sampler_desc {
                                              * robot).  The in-kernel Philox4x32-10 draws are keyed by (seed, draw, global
                                              * trajectory * H + t), so a rank that samples robots [r0, r1) of an N-robot
                                              * instance draws exactly the noise those rows get in the unsharded call
-                                             * (per-robot outputs bitwise identical for G = 1, 2, 4, 8) */
+                                             * (per-robot outputs bitwise identical for G = 1, 2, 4, 8).
+                                             * Counter layout: with point = global trajectory * H + t, the 128-bit counter is
+                                             * (point & 0xFFFFFFFF, draw, point >> 32, 0) and the key (seed & 0xFFFFFFFF, seed >> 32);
+                                             * the four output words give four N(0,1) values by Box-Muller (words 0, 1 -> radius,
+                                             * angle of the first pair, words 2, 3 of the second).  Draws: mmd_p_sample_loop numbers
+                                             * its steps k = 0, 1, ... in loop order, mmd_ddpm_step uses the caller's draw_index;
+                                             * 0xFFFFFFFF is RESERVED for x_T and 0xFFFFFFFE for mmd_q_sample (the Python layer
+                                             * passes it): a step must not draw under either */
   const float* noise_std_extra_by_t;        /* optional [T] host table: noise_std_extra_schedule_fn(t) evaluated for every
                                              * t (sample_functions.py:83-86 calls it per step); NULL = the constant above */
   void* profiler;                           /* optional mmd_profiler_t (include/mmd_amd_debug.h) that brackets UNet launches
