@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define MMD_AMD_ABI_VERSION 8
+#define MMD_AMD_ABI_VERSION 9
 #define MMD_STATE_DIM 4
 #define MMD_HORIZON 64
 
@@ -60,7 +60,14 @@ typedef struct mmd_unet_options {     /* creation-time choices, fixed for the li
   int32_t mconv_max_cs;               /* layer-by-layer path, A/B: the widest column slice of its matrix-pipe kernel; 0 = default (128) */
   int32_t two_per_workgroup_max;      /* fused kernel, A/B: batches up to this size run two trajectories per workgroup; 0 = default
                                        * (512), < 0 = never */
+  int32_t precision;                  /* MMD_UNET_PRECISION_* below; anything else is an error, and so is F16 on the layer-by-layer path
+                                       * (a non-fused shape, MMD_UNET_LAYERED) */
 } mmd_unet_options;
+#define MMD_UNET_PRECISION_F32 0      /* the default: fp32-accurate convs (two fp16 pieces per operand, three MFMAs per product) */
+#define MMD_UNET_PRECISION_F16 1      /* opt-in mixed precision of the fused kernel: conv inputs and weights rounded to ONE fp16 piece under
+                                       * the same power-of-two scales, fp32 accumulation, GroupNorm / Mish / the sampler step in fp32.
+                                       * ~1e-3 relative to the fp32 forward (outside the 1e-3-per-step parity bar).  Fixed for the life of
+                                       * the handle: every entry point that takes the handle follows it */
 #define MMD_UNET_LAYERED 1u           /* the layer-by-layer kernels for the fused kernel's own configuration too (the two
                                        * implementations share no device code: tests hold one against the other) */
 #define MMD_UNET_LAYERED_VALU 2u      /* layer-by-layer path: every layer on the vector-ALU kernels (A/B of its matrix-pipe kernel) */

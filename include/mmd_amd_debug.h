@@ -58,6 +58,9 @@ int mmd_unet_forward_profiled(mmd_unet_t unet, const float* x_dev, int t, float*
  * launch, the denominator of bench.py's roofline.traffic / wasted ratio. */
 size_t mmd_unet_weight_bytes(mmd_unet_t unet);
 
+/* The handle's mmd_unet_options.precision (MMD_UNET_PRECISION_*); -1 for NULL. */
+int mmd_unet_precision(mmd_unet_t unet);
+
 /* Decision trace of ONE guided ddpm_sample_fn step (sample_functions.py:40-107): mmd_ddpm_step on the one-wave step kernel with
  * the dump compiled in -- the same arithmetic, bit for bit, as every production launch shape -- which additionally writes
  *   mu_dev          [n_traj][64][4]  (optional) the posterior mean as the first guide iteration sees it (hard rows are pinned after an iteration, not before the first)

@@ -5,7 +5,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libmmd_amd.so")
-ABI_VERSION = 8
+ABI_VERSION = 9
 HARD_ROWS_START_GOAL = (1 << 63) | 1     # hard_rows of MPD's {0: start, H-1: goal} (include/mmd_amd.h: bit t = support point t pinned)
 
 
@@ -61,10 +61,13 @@ class SamplerDesc(C.Structure):
 
 SAMPLER_NO_FUSED_STEP, SAMPLER_PERSIST = 1, 2          # mmd_sampler_desc.flags
 UNET_LAYERED, UNET_LAYERED_VALU = 1, 2                 # mmd_unet_options.flags
+UNET_PRECISION_F32, UNET_PRECISION_F16 = 0, 1          # mmd_unet_options.precision
+UNET_PRECISIONS = {"f32": UNET_PRECISION_F32, "f16": UNET_PRECISION_F16}
 
 
 class UnetOptions(C.Structure):
-    _fields_ = [("flags", C.c_uint32), ("rtb_fused", C.c_int32), ("mconv_max_cs", C.c_int32), ("two_per_workgroup_max", C.c_int32)]
+    _fields_ = [("flags", C.c_uint32), ("rtb_fused", C.c_int32), ("mconv_max_cs", C.c_int32), ("two_per_workgroup_max", C.c_int32),
+                ("precision", C.c_int32)]
 
 
 class EnsembleTile(C.Structure):
@@ -173,6 +176,7 @@ _DEBUG_SIGNATURES = {
     "mmd_unet_forward_profiled": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t,
                                             C.c_void_p, C.c_void_p]),
     "mmd_unet_weight_bytes": (C.c_size_t, [C.c_void_p]),
+    "mmd_unet_precision": (C.c_int, [C.c_void_p]),
     "mmd_debug_ddpm_step_trace": (C.c_int, [C.c_void_p, C.POINTER(SamplerDesc), C.POINTER(GuideDesc), C.c_void_p, C.c_void_p,
                                             C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_size_t,
                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -204,6 +204,10 @@ bool unet_fused_step_supported(mmd_unet_t u);
 int unet_forward_fused(mmd_unet_t u, const float* x, int t, float* eps, int n, void* ws, size_t ws_bytes, Profiler* prof,
                        hipStream_t st, const FusedStep& fs);
 int unet_persist_steps(mmd_unet_t u, int n, void* ws, size_t ws_bytes, hipStream_t st, const FusedStep* steps, int n_steps);
+// the fp16-precision kernels (unet_f16.hip): ns trajectories per workgroup; args = unet.hip's UnetArgs as bytes (host / device memory)
+int launch_unet_f16(int ns, int blocks, hipStream_t st, const void* args, size_t args_bytes);
+int launch_unet_persist_f16(int ns, int blocks, hipStream_t st, const void* args_dev, size_t args_bytes, const FusedStep* steps_dev,
+                            int n_steps, int tb_total);
 // bins: the guide's cell table (mmd_guide_desc.cons_bins, checked by fill_guide) or NULL: a guided step then runs the binned kernel
 int launch_step(const GuideDev& g, StepDev s, float* x, const float* eps, const float* noise, float* chain,
                 const float* hard, int traj0, int n_traj, int spr, hipStream_t st, const mmd_cons_bins* bins);

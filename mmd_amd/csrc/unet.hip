@@ -155,6 +155,7 @@ using namespace mmd;
 struct mmd_unet_s {
   mmd::LayeredUnet* layered = nullptr;   // set: a configuration other than the fused kernel's; everything below is unused
   int T = 0;
+  int precision = MMD_UNET_PRECISION_F32;   // mmd_unet_options.precision: F16 launches unet_f16.hip's kernels on the same blob
   int ns2_max = 512;         // unet_kernel<2> (two trajectories per workgroup) up to this batch size (mmd_unet_options.two_per_workgroup_max)
 #ifndef MMD_NS1_MAX
 #define MMD_NS1_MAX 256
@@ -376,10 +377,15 @@ int unet_forward_fused(mmd_unet_t u, const float* x, int t, float* eps, int n, v
   a.fs = fs;
   const bool bracket = prof_begin(prof, 0, fs.enabled ? MMD_PROF_UNET_FUSED : MMD_PROF_UNET, st);
   // two trajectories per workgroup while that still leaves at most one workgroup per CU (256 CUs): see unet_kernel
-  if (n <= u->ns1_max && n <= u->ns2_max) hipLaunchKernelGGL(unet_kernel<1>, dim3(n), dim3(256), 0, st, a);
+  int rc = 0;
+  if (u->precision == MMD_UNET_PRECISION_F16) {
+    const int ns = n <= u->ns1_max && n <= u->ns2_max ? 1 : n <= u->ns2_max ? 2 : 4;
+    rc = launch_unet_f16(ns, (n + ns - 1) / ns, st, &a, sizeof(a));
+  } else if (n <= u->ns1_max && n <= u->ns2_max) hipLaunchKernelGGL(unet_kernel<1>, dim3(n), dim3(256), 0, st, a);
   else if (n <= u->ns2_max) hipLaunchKernelGGL(unet_kernel<2>, dim3((n + 1) / 2), dim3(256), 0, st, a);
   else hipLaunchKernelGGL(unet_kernel<4>, dim3((n + 3) / 4), dim3(256), 0, st, a);
   if (bracket) prof_end(prof, st);
+  if (rc) return rc;
   MMD_HIP_CHECK(hipGetLastError());
   return 0;
 }
@@ -402,7 +408,10 @@ int unet_persist_steps(mmd_unet_t u, int n, void* ws, size_t ws_bytes, hipStream
   MMD_HIP_CHECK(hipMemcpyAsync(args_dev, &a, sizeof(a), hipMemcpyHostToDevice, st));   // (pageable source: staged before the call returns)
   const FusedStep* sd = reinterpret_cast<const FusedStep*>(ws);
   const UnetArgs* ap = reinterpret_cast<const UnetArgs*>(args_dev);
-  if (n <= u->ns2_max) hipLaunchKernelGGL(unet_persist_kernel<2>, dim3((n + 1) / 2), dim3(256), 0, st, ap, sd, n_steps, u->w.tb_total);
+  if (u->precision == MMD_UNET_PRECISION_F16) {
+    const int ns = n <= u->ns2_max ? 2 : 4;
+    if (int rc = launch_unet_persist_f16(ns, (n + ns - 1) / ns, st, args_dev, sizeof(a), sd, n_steps, u->w.tb_total)) return rc;
+  } else if (n <= u->ns2_max) hipLaunchKernelGGL(unet_persist_kernel<2>, dim3((n + 1) / 2), dim3(256), 0, st, ap, sd, n_steps, u->w.tb_total);
   else hipLaunchKernelGGL(unet_persist_kernel<4>, dim3((n + 3) / 4), dim3(256), 0, st, ap, sd, n_steps, u->w.tb_total);
   MMD_HIP_CHECK(hipGetLastError());
   return 0;
@@ -462,16 +471,24 @@ int mmd_unet_create(mmd_unet_t* out, int unet_input_dim, int n_levels, int n_dif
     MMD_REQUIRE(numels[i] == s.numel[i] && tensors[i] != nullptr, "parameter tensor %d has %lld elements, expected %lld",
                 i, (long long)numels[i], (long long)s.numel[i]);
   MMD_REQUIRE(n_diffusion_steps >= 1, "n_diffusion_steps must be >= 1");
+  const int precision = options ? options->precision : MMD_UNET_PRECISION_F32;
+  const bool layered_path = !fused_config(unet_input_dim, n_levels) || (options && (options->flags & MMD_UNET_LAYERED));
+  MMD_REQUIRE(precision == MMD_UNET_PRECISION_F32 || precision == MMD_UNET_PRECISION_F16,
+              "mmd_unet_options.precision = %d: MMD_UNET_PRECISION_F32 (0) or MMD_UNET_PRECISION_F16 (1)", precision);
+  MMD_REQUIRE(precision == MMD_UNET_PRECISION_F32 || !layered_path,
+              "mmd_unet_options.precision = MMD_UNET_PRECISION_F16 exists in the fused kernel only (unet_input_dim 32, 3 levels, "
+              "without MMD_UNET_LAYERED): unet_input_dim=%d, n_levels=%d, flags=%u", unet_input_dim, n_levels, options->flags);
   hipStream_t st = (hipStream_t)stream;
 
   // owned until *out takes it: every early return below destroys the handle and what it has allocated by then
   struct Destroy { void operator()(mmd_unet_s* p) const { (void)mmd_unet_destroy(p); } };
   std::unique_ptr<mmd_unet_s, Destroy> u(new mmd_unet_s());
   u->T = n_diffusion_steps;
+  u->precision = precision;
   if (options && options->two_per_workgroup_max != 0) u->ns2_max = options->two_per_workgroup_max < 0 ? 0 : options->two_per_workgroup_max;
   // MMD_UNET_LAYERED: the layer-by-layer path for the fused kernel's own configuration too -- the two implementations share no
   // device code, tests/test_gpu_dim_mults.py holds one against the other
-  if (!fused_config(unet_input_dim, n_levels) || (options && (options->flags & MMD_UNET_LAYERED))) {
+  if (layered_path) {
     // e.g. UNET_DIM_MULTS[1] = (1, 2, 4, 8): layer by layer (unet_layers.hip)
     if (int rc = layered_create(&u->layered, s, n_diffusion_steps, tensors, options, st)) return rc;
   } else {
@@ -516,6 +533,8 @@ int mmd_debug_set_trace(void* dev_ptr) {
   return hipMemcpyToSymbol(HIP_SYMBOL(g_trace), &dev_ptr, sizeof(dev_ptr)) == hipSuccess ? 0 : 1;
 }
 #endif
+
+int mmd_unet_precision(mmd_unet_t u) { return u ? u->precision : -1; }
 
 size_t mmd_unet_weight_bytes(mmd_unet_t u) {
   if (!u) return 0;

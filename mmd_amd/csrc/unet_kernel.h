@@ -37,7 +37,32 @@
 #include "guide_dev.h"
 #include "unet_spec.h"
 
+// Two precisions from this one source.  As included by unet.hip everything below is the f16x2 arithmetic described above (namespace mmd,
+// N_PIECES = 2).  unet_f16.hip includes it under MMD_UNET_F16 (mmd_unet_options.precision = MMD_UNET_PRECISION_F16): the same stages,
+// slabs, weight packs, scales and epilogues in namespace mmd::f16 -- kernels with symbols of their own -- with ONE fp16 piece per
+// operand: f16_split2 / vb_three are shadowed by one-piece forms, the low pieces are neither stored (MMD_LO) nor zeroed nor staged, and
+// what still reads them (rd_load_a / rd_load_b, piece q = 1) is dead code to the compiler.
+#ifdef MMD_UNET_F16
+#define MMD_LO(...)
 namespace mmd {
+namespace f16 {
+constexpr int N_PIECES = 1;
+struct F16Pair { unsigned hi; };
+__device__ __forceinline__ F16Pair f16_split2(float v0, float v1) {
+  return F16Pair{__builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{v0, v1}, f16x2))};   // v_cvt_pk_f16_f32 (round to nearest even)
+}
+// one K = 32 chunk of one accumulator stream: a0 b0 (program order kept, as the triple's is)
+template <bool ZERO>
+__device__ __forceinline__ void vb_three(f32x4& x, const u32x4 (&a)[2], const u32x4 (&b)[2]) {
+  const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+  x = mfma_h(a[0], b[0], ZERO ? z : x);
+  __builtin_amdgcn_sched_barrier(0);
+}
+#else
+#define MMD_LO(...) __VA_ARGS__
+namespace mmd {
+constexpr int N_PIECES = 2;
+#endif
 
 // final Conv1dBlock(32->32, k5) + Conv1d(32->4, k1) of the network
 struct FinalArgs {
@@ -402,7 +427,7 @@ template <int C> struct RlGeo {
 };
 template <class GEO>
 __device__ __forceinline__ void rd_zero_halo(char* slab) {
-  constexpr int TOT = 2 * 4 * GEO::KC * 4 * 4;               // pieces x lane groups x chunks x samples x halo rows, 16 B each
+  constexpr int TOT = N_PIECES * 4 * GEO::KC * 4 * 4;        // pieces x lane groups x chunks x samples x halo rows, 16 B each
   for (int idx = opaque_tid(); idx < TOT; idx += 256) {
     const int hr = idx & 3, sm = (idx >> 2) & 3, blk = (idx >> 4) % (4 * GEO::KC), q = idx / (64 * GEO::KC);
     *reinterpret_cast<uint4*>(slab + q * GEO::PS + (blk / GEO::KC) * GEO::G + (blk % GEO::KC) * GEO::BX +
@@ -631,7 +656,7 @@ __device__ __forceinline__ void rd_store2(char* vs, const f32x4 (&acc)[NS][2]) {
     for (int r = 0; r < 4; ++r) {
       const F16Pair f = f16_split2(acc[sm][0][r], acc[sm][1][r]);
       *reinterpret_cast<unsigned*>(vs + (sm * GEO::RPS + r) * 16) = f.hi;
-      *reinterpret_cast<unsigned*>(vs + GEO::PS + (sm * GEO::RPS + r) * 16) = f.lo;
+      MMD_LO(*reinterpret_cast<unsigned*>(vs + GEO::PS + (sm * GEO::RPS + r) * 16) = f.lo;)
     }
 }
 // one-n-tile tile (lane: channel c, positions 4 g + r of the NS samples): the lanes of a pair (n, n ^ 1) swap half the samples,
@@ -651,7 +676,7 @@ __device__ __forceinline__ void rd_store1(char* vs, const f32x4 (&acc)[NS][1], i
       const float recv = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, own), 0xB1, 0xf, 0xf, true));
       const F16Pair f = f16_split2(odd ? recv : own, odd ? own : recv);        // (low channel, high channel)
       *reinterpret_cast<unsigned*>(vs + r * 16) = f.hi;
-      *reinterpret_cast<unsigned*>(vs + GEO::PS + r * 16) = f.lo;
+      MMD_LO(*reinterpret_cast<unsigned*>(vs + GEO::PS + r * 16) = f.lo;)
     }
   }
 #pragma unroll
@@ -664,7 +689,7 @@ __device__ __forceinline__ void rd_store1(char* vs, const f32x4 (&acc)[NS][1], i
       const F16Pair f = f16_split2(odd ? recv : own, odd ? own : recv);        // (low channel, high channel)
       char* p = vs + ((odd ? HS + h : h) * GEO::RPS + r) * 16;
       *reinterpret_cast<unsigned*>(p) = f.hi;
-      *reinterpret_cast<unsigned*>(p + GEO::PS) = f.lo;
+      MMD_LO(*reinterpret_cast<unsigned*>(p + GEO::PS) = f.lo;)
     }
 }
 // row-form fp32 slab [sample][20][XSTR] (2-row halo) of C channels -> the Rd slab, times the sample's dynamic scale
@@ -684,7 +709,7 @@ __device__ __forceinline__ void rowform_to_rd(const float* xslab, char* slab, co
     const int blk = cp >> 2;
     char* dst = slab + (blk / GEO::KC) * GEO::G + (blk % GEO::KC) * GEO::BX + (sm * GEO::RPS + 2 + pos) * 16 + (cp & 3) * 4;
     *reinterpret_cast<unsigned*>(dst) = f.hi;
-    *reinterpret_cast<unsigned*>(dst + GEO::PS) = f.lo;
+    MMD_LO(*reinterpret_cast<unsigned*>(dst + GEO::PS) = f.lo;)
   }
 }
 
@@ -882,7 +907,7 @@ __device__ __forceinline__ void rw_store2(char* vs, const f32x4 (&acc)[MT][2]) {
     for (int r = 0; r < 4; ++r) {
       const F16Pair f = f16_split2(acc[mt][0][r], acc[mt][1][r]);
       *reinterpret_cast<unsigned*>(vs + (mt * 16 + r) * 16) = f.hi;
-      *reinterpret_cast<unsigned*>(vs + GEO::PS + (mt * 16 + r) * 16) = f.lo;
+      MMD_LO(*reinterpret_cast<unsigned*>(vs + GEO::PS + (mt * 16 + r) * 16) = f.lo;)
     }
 }
 __device__ __forceinline__ void wave_lds_fence() {           // a wave's own LDS writes before its own later reads
@@ -916,13 +941,13 @@ __device__ __forceinline__ void rw_gn_samples(f32x4 (&acc)[M][NT], const Epi<NT>
     rw_gn_mish<TPS, NT, GL, NG, decltype(add)::ACT>(sub_tile<TPS>(acc, TPS * sl), e.b, e.g, e.be, e.is, inv[sl], add.as, add);
   }
 }
-// Zero the four halo rows (0, 1, rows + 2, rows + 3) of a wave-private-geometry slab: 4 KC blocks x 2 pieces, one 16-byte store per
-// lane (KC = 1: lanes 0 .. 31).  base = the slab's first row; `mine`: whether this wave is the one that zeroes (half-sample stages: one
+// Zero the four halo rows (0, 1, rows + 2, rows + 3) of a wave-private-geometry slab: 4 KC blocks x N_PIECES pieces, one 16-byte store
+// per lane (KC = 1, two pieces: lanes 0 .. 31).  base = the slab's first row; `mine`: whether this wave is the one that zeroes (half-sample stages: one
 // wave per sample)
 template <class GEO>
 __device__ __forceinline__ void rw_zero_halo(char* base, int rows, int lane, bool mine) {
   constexpr int KC = GEO::KC;
-  if (mine && (32 * KC >= 64 || lane < 32 * KC)) {
+  if (mine && (16 * N_PIECES * KC >= 64 || lane < 16 * N_PIECES * KC)) {
     const int hr = lane & 3, blk = (lane >> 2) % (4 * KC), q = lane / (16 * KC);
     *reinterpret_cast<uint4*>(base + q * GEO::PS + (blk / KC) * GEO::G + (blk % KC) * GEO::BX + (hr < 2 ? hr : rows + hr) * 16) =
         make_uint4(0u, 0u, 0u, 0u);
@@ -983,11 +1008,24 @@ template <int NFRAG>
 __device__ __forceinline__ void stage_weights(const uint4* w, char* dst, int wave, int lane) {
   static_assert(NFRAG % 4 == 0, "fragments are dealt to the four waves");
   const uint4* src = w + lane;
+  if constexpr (N_PIECES == 2) {
 #pragma unroll
-  for (int i = 0; i < NFRAG / 4; ++i) {
-    const int f = wave + 4 * i;
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + f * 64),
-                                     (__attribute__((address_space(3))) void*)(dst + f * 1024), 16, 0, 0);
+    for (int i = 0; i < NFRAG / 4; ++i) {
+      const int f = wave + 4 * i;
+      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + f * 64),
+                                       (__attribute__((address_space(3))) void*)(dst + f * 1024), 16, 0, 0);
+    }
+  } else {
+    // one piece: the fragments alternate piece 0 / piece 1 ([tap][chunk][piece], an even count per n-tile), only the even ones are
+    // moved, dealt to the four waves (the wave index is uniform: a scalar branch on the ragged last round)
+    constexpr int NF0 = NFRAG / 2;
+#pragma unroll
+    for (int i = 0; i < (NF0 + 3) / 4; ++i) {
+      const int f = 2 * (wave + 4 * i);
+      if (4 * i + 3 < NF0 || wave + 4 * i < NF0)
+        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + f * 64),
+                                         (__attribute__((address_space(3))) void*)(dst + f * 1024), 16, 0, 0);
+    }
   }
 }
 __device__ __forceinline__ void staged_weights_landed() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
@@ -1028,12 +1066,12 @@ __device__ __forceinline__ float d0_stage_input(const float* in0, bool valid, si
   const F16Pair p0 = f16_split2(v.x * ds.s, v.y * ds.s), p1 = f16_split2(v.z * ds.s, v.w * ds.s);
   if (store) {
     *reinterpret_cast<uint2*>(xin + (2 + lane) * 8) = make_uint2(p0.hi, p1.hi);
-    *reinterpret_cast<uint2*>(xin + D0::XIN + (2 + lane) * 8) = make_uint2(p0.lo, p1.lo);
+    MMD_LO(*reinterpret_cast<uint2*>(xin + D0::XIN + (2 + lane) * 8) = make_uint2(p0.lo, p1.lo);)
   }
   return ds.inv;
 }
 __device__ __forceinline__ void d0_zero_xin_halo(char* xin, int lane, bool mine) {   // rows 0, 1, 66 .. 71 of both pieces
-  if (mine && lane < 16) {
+  if (mine && lane < 8 * N_PIECES) {
     const int row = (lane & 7) < 2 ? (lane & 7) : 64 + (lane & 7);
     *reinterpret_cast<uint2*>(xin + (lane >> 3) * D0::XIN + row * 8) = make_uint2(0u, 0u);
   }
@@ -1082,7 +1120,7 @@ __device__ __forceinline__ void d0_tail_store(char* lb, int smp, int m0, int n, 
     for (int r = 0; r < 4; ++r) {
       const F16Pair f = f16_split2(y[mt][0][r] * so, y[mt][1][r] * so);
       *reinterpret_cast<unsigned*>(xb + (16 * mt + r) * 16) = f.hi;
-      *reinterpret_cast<unsigned*>(xb + GN::PS + (16 * mt + r) * 16) = f.lo;
+      MMD_LO(*reinterpret_cast<unsigned*>(xb + GN::PS + (16 * mt + r) * 16) = f.lo;)
     }
 }
 
@@ -1307,7 +1345,7 @@ __device__ __forceinline__ void chain_body_d1d(const ChainArgs& a, float* lds, i
       for (int r = 0; r < 4; ++r) {
         const F16Pair f = f16_split2(acc[m][0][r], acc[m][1][r]);
         *reinterpret_cast<unsigned*>(vsH + (GH::tile_row(m) + r) * 16) = f.hi;
-        *reinterpret_cast<unsigned*>(vsH + GH::PS + (GH::tile_row(m) + r) * 16) = f.lo;
+        MMD_LO(*reinterpret_cast<unsigned*>(vsH + GH::PS + (GH::tile_row(m) + r) * 16) = f.lo;)
       }
   };
   // one 64 -> 64 conv over the tile in acc (already scaled); on entry every wave is past its reads of the slab.  PF (ring_prefetch: one
@@ -1712,7 +1750,7 @@ __device__ __forceinline__ void u1_store_chunk0(char* lb, int wave, int n, int g
       const F16Pair p = f16_split2(odd ? recv : own, odd ? own : recv);
       char* d = d0 + sm * U1::W_BYTES + 2 * r * 16;
       *reinterpret_cast<unsigned*>(d) = p.hi;
-      *reinterpret_cast<unsigned*>(d + GA::PS) = p.lo;
+      MMD_LO(*reinterpret_cast<unsigned*>(d + GA::PS) = p.lo;)
     }
 }
 // chunk 1 = skip (downs.1's layout: wave = (channel half np, sample pair sp); skip[m][t][r]: sample s0 + (m >> 1), channel 32 np + 2 n + t,
@@ -1730,14 +1768,14 @@ __device__ __forceinline__ void u1_store_chunk1(char* lb, int wave, int n, int g
       const F16Pair p = f16_split2(skip[m][0][r] * sc[m >> 1].s, skip[m][1][r] * sc[m >> 1].s);
       char* d = sdst + (s0 + (m >> 1)) * U1::W_BYTES + (16 * (m & 1) + r) * 16;
       *reinterpret_cast<unsigned*>(d) = p.hi;
-      *reinterpret_cast<unsigned*>(d + GA::PS) = p.lo;
+      MMD_LO(*reinterpret_cast<unsigned*>(d + GA::PS) = p.lo;)
     }
 }
 // The transposed tail's output of input tiles m0 .. m0 + MT - 1 (positions 2 m + parity, m = 16 (m0 + mt) + 4 g + r: rows 2 + 32 (m0 + mt)
 // + 8 g + 2 r + parity) times s -> the 64-row slab; vsF = slab + the lane's (block n >> 2, row 0, dword n & 3)
 template <int MT>
 __device__ __forceinline__ void u1_tail_store(char* vsF, int m0, int g, const f32x4 (&e)[MT][2], const f32x4 (&o)[MT][2], float s) {
-  using GF = U1::GF;
+  using GF [[maybe_unused]] = U1::GF;
 #pragma unroll
   for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
@@ -1745,9 +1783,9 @@ __device__ __forceinline__ void u1_tail_store(char* vsF, int m0, int g, const f3
       const F16Pair pe = f16_split2(e[mt][0][r] * s, e[mt][1][r] * s), po = f16_split2(o[mt][0][r] * s, o[mt][1][r] * s);
       char* d = vsF + (2 + 32 * (m0 + mt) + 8 * g + 2 * r) * 16;
       *reinterpret_cast<unsigned*>(d) = pe.hi;
-      *reinterpret_cast<unsigned*>(d + GF::PS) = pe.lo;
+      MMD_LO(*reinterpret_cast<unsigned*>(d + GF::PS) = pe.lo;)
       *reinterpret_cast<unsigned*>(d + 16) = po.hi;
-      *reinterpret_cast<unsigned*>(d + 16 + GF::PS) = po.lo;
+      MMD_LO(*reinterpret_cast<unsigned*>(d + 16 + GF::PS) = po.lo;)
     }
 }
 // eps = the 1x1 conv's output times its scale + bias (columns n < 4 of the tile are real), M tiles m0 .. m0 + MT - 1 of a sample:
@@ -2190,4 +2228,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   }
 }
 
+#ifdef MMD_UNET_F16
+}  // namespace f16
+#endif
 }  // namespace mmd

@@ -336,10 +336,11 @@ def normalizer_limits_from_dataset(dataset_dir):
     return flat.min(dim=0).values.numpy(), flat.max(dim=0).values.numpy()
 
 
-def _load_model(model_id, trained_models_dir, model_state_dict, model_args, device):
-    """mpd.py:117-177: args.yaml + checkpoint if present on disk, else the in-memory state dict."""
+def _load_model(model_id, trained_models_dir, model_state_dict, model_args, device, unet_precision="f32"):
+    """mpd.py:117-177: args.yaml + checkpoint if present on disk, else the in-memory state dict.  unet_precision ("f32" | "f16", also
+    honoured as model_args["unet_precision"]): TemporalUnet's opt-in mixed-precision forward."""
     args = dict(variance_schedule="exponential", n_diffusion_steps=25, predict_epsilon=True, unet_input_dim=32,
-                unet_dim_mults_option=0, use_ema=True)
+                unet_dim_mults_option=0, use_ema=True, unet_precision=unet_precision)
     model_dir = os.path.join(os.path.expanduser(trained_models_dir or ""), model_id or "")
     yaml_path = os.path.join(model_dir, "args.yaml")
     if model_state_dict is None and os.path.exists(yaml_path):
@@ -353,7 +354,7 @@ def _load_model(model_id, trained_models_dir, model_state_dict, model_args, devi
     if model_state_dict is None:
         raise FileNotFoundError(f"no checkpoint under {model_dir} and no model_state_dict given")
     unet = TemporalUnet(state_dim=4, n_support_points=HORIZON, unet_input_dim=args["unet_input_dim"],
-                        dim_mults=UNET_DIM_MULTS[args["unet_dim_mults_option"]])
+                        dim_mults=UNET_DIM_MULTS[args["unet_dim_mults_option"]], precision=args["unet_precision"])
     unet.load_state_dict(model_state_dict)
     model = GaussianDiffusionModel(model=unet, variance_schedule=args["variance_schedule"],
                                    n_diffusion_steps=args["n_diffusion_steps"], predict_epsilon=args["predict_epsilon"])
@@ -370,14 +371,14 @@ class MPD:
                  device: str = "cuda", debug: bool = False, seed: int = 18, results_dir: str = "logs",
                  trained_models_dir: str = "", n_samples: int = 64, n_local_inference_noising_steps: int = 3,
                  n_local_inference_denoising_steps: int = 3, model_state_dict=None, model_args=None, env_id=None,
-                 normalizer_limits=None, obstacle_cutoff_margin=0.05, env_extra_objects=None, **kwargs):
+                 normalizer_limits=None, obstacle_cutoff_margin=0.05, env_extra_objects=None, unet_precision="f32", **kwargs):
         self.constraints = []
         self.weight_grad_cost_constraints = weight_grad_cost_constraints
         self.weight_grad_cost_soft_constraints = weight_grad_cost_soft_constraints
         self.run_prior_only, self.run_prior_then_guidance = _planner_alg(planner_alg)
         self.device = torch.device(device)
         self.tensor_args = {"device": self.device, "dtype": torch.float32}
-        self.model, self.model_args = _load_model(model_id, trained_models_dir, model_state_dict, model_args, self.device)
+        self.model, self.model_args = _load_model(model_id, trained_models_dir, model_state_dict, model_args, self.device, unet_precision)
         self.model.seed = seed
         self.env_id = env_id or (model_id.split("-")[0] if model_id else "EnvEmpty2D")
         if normalizer_limits is None and kwargs.get("dataset_dir"):
@@ -517,7 +518,7 @@ class MPDEnsemble:
                  device: str = "cuda", debug: bool = False, seed: int = 18, results_dir: str = "logs",
                  trained_models_dir: str = "", n_samples: int = 64, n_local_inference_noising_steps: int = 3,
                  n_local_inference_denoising_steps: int = 3, model_state_dicts=None, model_args=None, env_ids=None,
-                 normalizer_limits=None, **kwargs):
+                 normalizer_limits=None, unet_precision="f32", **kwargs):
         self.run_prior_only, self.run_prior_then_guidance = _planner_alg(planner_alg)
         self.weight_grad_cost_constraints = weight_grad_cost_constraints
         self.weight_grad_cost_soft_constraints = weight_grad_cost_soft_constraints
@@ -529,7 +530,7 @@ class MPDEnsemble:
         task_guides = {}
         for j, model_id in enumerate(model_ids):
             sd = None if model_state_dicts is None else model_state_dicts[j]
-            model, _ = _load_model(model_id, trained_models_dir, sd, model_args, self.device)
+            model, _ = _load_model(model_id, trained_models_dir, sd, model_args, self.device, unet_precision)
             model.seed = seed + j
             self.models[j] = model
             self.env_ids[j] = (env_ids[j] if env_ids is not None else model_id.split("-")[0])
@@ -763,7 +764,8 @@ def _guide_key(g):
 
 def _batch_key(call):
     """Calls with equal keys can share one launch sequence: same planner class and algorithm, the same device model(s) (weights are
-    content-hashed: equal state dicts share one handle), schedule, batch size, sampler settings and guide parameters.  Maps,
+    content-hashed: equal state dicts share one handle; a handle is one set of mmd_unet_options, so an f32 and an f16 model of the same
+    weights have different handles and never pack together), schedule, batch size, sampler settings and guide parameters.  Maps,
     start / goal, constraints, tile transforms, seeds and the experience's seed batch may differ per call.  None: the call is run on
     its own (`diffusion_prior_then_guide`, a map with extra objects)."""
     planner = call[0]

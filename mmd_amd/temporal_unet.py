@@ -41,7 +41,7 @@ class _DeviceModel:
 class TemporalUnet:
     def __init__(self, n_support_points=64, state_dim=4, unet_input_dim=32, dim_mults=(1, 2, 4), time_emb_dim=32,
                  self_attention=False, conditioning_type=None, max_timesteps=1000, layered=False, layered_valu=False,
-                 rtb_fused=-1, mconv_max_cs=0, two_per_workgroup_max=0, **kwargs):
+                 rtb_fused=-1, mconv_max_cs=0, two_per_workgroup_max=0, precision="f32", **kwargs):
         if self_attention or conditioning_type not in (None, "None"):
             raise NotImplementedError("only the configuration MPD/MPDEnsemble instantiate is supported "
                                       "(no self-attention, no context conditioning)")
@@ -61,8 +61,13 @@ class TemporalUnet:
         # tests/test_gpu_dim_mults.py).  These choices are fixed for the life of the object and travel to mmd_unet_create as its
         # mmd_unet_options argument (include/mmd_amd.h) -- nothing is read from, or written to, the process environment.
         self.layered = bool(layered)
+        # precision="f16": the opt-in mixed-precision kernels of the fused forward (one fp16 piece per operand, fp32 accumulation; ~1e-3 from
+        # the fp32 forward) -- never the default; with the layer-by-layer path mmd_unet_create refuses it
+        if precision not in _lib.UNET_PRECISIONS:
+            raise ValueError(f"TemporalUnet: precision {precision!r}: one of {sorted(_lib.UNET_PRECISIONS)}")
+        self.precision = precision
         self.options = (int(bool(layered)) * _lib.UNET_LAYERED | int(bool(layered_valu)) * _lib.UNET_LAYERED_VALU, int(rtb_fused),
-                        int(mconv_max_cs), int(two_per_workgroup_max))
+                        int(mconv_max_cs), int(two_per_workgroup_max), _lib.UNET_PRECISIONS[precision])
         self._sd = None
         self._sd_hash = None
         self._models = {}               # (n_timesteps, device index) -> _DeviceModel (shared through _DEVICE_MODELS)

@@ -1,6 +1,7 @@
 """N back-to-back TemporalUnet forwards of n trajectories (the body of the PMC / A-B passes).  MMD_AMD_LIB selects the
 .so.  Usage: python tools/unet_forward_loop.py [n_traj ...]   -> per n: mean unet_kernel time by HIP events.  REPS=<n>: launches
-per size (30); SECS=<s>: keep launching for about s seconds instead (power / throttle sampling sessions)."""
+per size (30); SECS=<s>: keep launching for about s seconds instead (power / throttle sampling sessions); PRECISION=f32|f16: the
+forward's precision (TemporalUnet(precision=...) -> mmd_unet_options.precision; default f32)."""
 import os
 import sys
 import time
@@ -12,7 +13,8 @@ if os.environ.get("MMD_AMD_LIB"):
 from mmd_amd.temporal_unet import TemporalUnet
 
 lib = _lib.load()
-unet = TemporalUnet(two_per_workgroup_max=int(os.environ.get('MMD_AMD_UNET_NS2_MAX', '0')))   # (this TOOL's knob, passed on as mmd_unet_options: the library reads no environment)
+precision = os.environ.get('PRECISION', 'f32')
+unet = TemporalUnet(two_per_workgroup_max=int(os.environ.get('MMD_AMD_UNET_NS2_MAX', '0')), precision=precision)   # (this TOOL's knobs, passed on as mmd_unet_options: the library reads no environment)
 unet.load_state_dict(synth.synth_unet_state_dict(0))
 reps = int(os.environ.get("REPS", "30"))
 for n in [int(a) for a in sys.argv[1:]] or [2048]:
@@ -38,6 +40,7 @@ for n in [int(a) for a in sys.argv[1:]] or [2048]:
     us = e0.elapsed_time(e1) / done * 1e3
     fl, mf = lib.mmd_unet_flops_per_trajectory() * n, lib.mmd_unet_mfma_flops_per_trajectory() * n
     hf = lib.mmd_unet_f16x2_flops_per_trajectory() * n
-    busy_us = ((mf - hf) / 157.3e12 + 3.0 * hf / 2516.6e12) * 1e6      # MFMA issue time at the spec clock (bench.py's accounting)
+    per_product = 1.0 if precision == 'f16' else 3.0                    # MFMAs per product: one piece per operand, or the f16x2 triple
+    busy_us = ((mf - hf) / 157.3e12 + per_product * hf / 2516.6e12) * 1e6   # MFMA issue time at the spec clock (bench.py's accounting)
     print(f"n={n:5d}: unet forward {us:8.1f} us  algorithmic {fl / us / 1e6:6.1f} TF  fp32-equivalent GEMM {mf / us / 1e6:6.1f} TF  "
-          f"matrix pipe busy {busy_us / us:.3f}  [{os.environ.get('MMD_AMD_LIB', 'default lib')}]", flush=True)
+          f"matrix pipe busy {busy_us / us:.3f}  [{precision}, {os.environ.get('MMD_AMD_LIB', 'default lib')}]", flush=True)
