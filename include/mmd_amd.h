@@ -196,6 +196,16 @@ size_t mmd_cons_bins_bytes(int n_all, int nx, int ny, size_t* off_bytes, size_t*
 int mmd_bin_constraints_from_paths(const float* paths_dev, int n_all, int horizon, float radius, const float lo[2], const float hi[2],
                                    int nx, int ny, int32_t* cell_off_dev, float* entries_dev, void* stream);
 
+/* The same table with a choice of the first listed time step: mmd_bin_constraints_from_paths is the first_step = 1 call (bit for bit).
+ * first_step = 0 also lists time step 0 -- a COLLISION table, for mmd_count_collisions_binned and mmd_path_conflicts_binned below, which
+ * count collisions at t = 0 as the all-pairs kernels do; `reach` = the largest distance at which the table's walkers may need a point
+ * (mmd_cons_bins.radius; a collision table of reach = the constraint radius shares the constraint table's grid).  Time steps below
+ * first_step get empty lists; first_step outside {0, 1} is an error.  Same checks, sizes (mmd_cons_bins_bytes), cell rule
+ * ((hi - lo) / n >= (1 + 1/16) * reach) and kernel.  The struct does not record first_step: hand a guided step only tables of
+ * first_step = 1 (its bits are promised on those), the two collision calls only tables of first_step = 0. */
+int mmd_bin_paths(const float* paths_dev, int n_all, int horizon, float reach, const float lo[2], const float hi[2], int nx, int ny,
+                  int first_step, int32_t* cell_off_dev, float* entries_dev, void* stream);
+
 /* n_steps x { x += guide(x); apply_hard_conditioning }  (guide_gradient_steps,
  * mmd/models/diffusion_models/sample_functions.py:89-107).  Hard conditions (apply_hard_conditioning,
  * sample_functions.py:8-14: the dict {support point: state}): bit t of hard_rows set = support point t of every trajectory
@@ -359,6 +369,14 @@ int mmd_rr_collisions(const float* paths_dev, int n_robots, int horizon, float m
 int mmd_count_collisions(const float* trajs_dev, const float* paths_dev, int robot0, int n_local,
                          int samples_per_robot, int n_all, int horizon, float margin, int32_t* counts_dev, void* stream);
 
+/* mmd_count_collisions on a cell table of the best paths (mmd_bin_paths, first_step = 0) instead of the paths: every (sample, t) point
+ * meets only the robots in the list of its own cell instead of all n_all, and the counts are the SAME INTEGERS.  trajs_dev
+ * [n_local * B, H, 4] as above; the local robots are [bins->robot0, bins->robot0 + n_local) and a trajectory skips the entry of its own
+ * robot.  margin <= bins->radius is what makes a cell's list complete (csrc/multi_agent.hip, COVER); a larger margin, a NULL table, or a
+ * grid / robot range a guided step would refuse are error returns before any launch.  bins->weight is not read.  One launch. */
+int mmd_count_collisions_binned(const float* trajs_dev, const mmd_cons_bins* bins, int n_local, int samples_per_robot, float margin,
+                                int32_t* counts_dev, void* stream);
+
 /* ---- the search layer of CBS / PrioritizedPlanning (mmd/planners/multi_agent/cbs.py, prioritized_planning.py) ----------------
  * Agent k of a search state is its chosen sample of a batch, with its own length and start time.  Its position at global time t
  * is path_k[clamp(t - s_k, 0, L_k - 1)]: global_pad_paths (mmd/common/multi_agent_utils.py:120-143) without the padded tensors.
@@ -394,6 +412,17 @@ typedef struct mmd_conflict {
 int mmd_find_conflicts(const mmd_agent_path* agents_dev, int n_agents, int horizon_global, float margin, int mode,
                        int32_t* row_counts_dev, int32_t* count_dev, mmd_conflict* first_dev, mmd_conflict* list_dev, int list_cap,
                        void* stream);
+
+/* The conflict report of a round's best paths on a cell table of those paths (mmd_bin_paths, first_step = 0): paths_dev [n_all, H, 2] with
+ * n_all = bins->n_all, horizon = H, equal start times.  count_dev, first_dev, list_dev / list_cap and row_counts_dev [H] are exactly what
+ * mmd_find_conflicts(..., MMD_CONFLICTS_PAIRS, ...) gives for an agent table of the same paths with start_time 0 and length 64 -- the
+ * records (t, a, b), a < b, in row-major order, pa / pb / mid the same bits -- and robot_counts_dev [n_all] (may be NULL) =
+ * #{(t, j != r) : ||p_r(t) - p_j(t)|| < margin}: every pair counts once for each of its two robots (the row sums of mmd_rr_collisions'
+ * mask).  Work and memory are O(n_all x list length): robot a walks the list of its own cell and keeps the ids above its own.  Three
+ * launches, no atomics, no host synchronisation; the list is the same on every run.  Errors as mmd_count_collisions_binned. */
+int mmd_path_conflicts_binned(const float* paths_dev, const mmd_cons_bins* bins, int horizon, float margin, int32_t* row_counts_dev,
+                              int32_t* robot_counts_dev, int32_t* count_dev, mmd_conflict* first_dev, mmd_conflict* list_dev, int list_cap,
+                              void* stream);
 
 /* The 'least_collisions' choice for re-planned agent `agent` without the per-candidate get_conflicts loop (cbs.py:446-458,
  * prioritized_planning.py:172-182): for candidate c (sample cand_idx_dev[c] of cand_batch_dev [B, L_agent, 4], in the order of

@@ -120,6 +120,8 @@ _SIGNATURES = {
     "mmd_cons_bins_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "mmd_bin_constraints_from_paths": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float),
                                                  C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mmd_bin_paths": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int, C.c_int,
+                                C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mmd_guide_steps": (C.c_int, [C.POINTER(GuideDesc), C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_int,
                                   C.c_void_p, C.c_void_p]),
     "mmd_sampler_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int]),
@@ -139,6 +141,9 @@ _SIGNATURES = {
     "mmd_rr_collisions": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mmd_count_collisions": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
                                        C.c_void_p, C.c_void_p]),
+    "mmd_count_collisions_binned": (C.c_int, [C.c_void_p, C.POINTER(ConsBins), C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p]),
+    "mmd_path_conflicts_binned": (C.c_int, [C.c_void_p, C.POINTER(ConsBins), C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "mmd_find_conflicts": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_int, C.c_void_p]),
     "mmd_scan_candidates": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_int,

@@ -213,8 +213,11 @@ class BinnedConstraints:
     """A cell-binned inter-robot constraint table on the device (include/mmd_amd.h: mmd_cons_bins): owns the two device tensors and the
     filled struct that GuideManagerTrajectoriesWithVelocity.set_binned_constraints hands to the guided step."""
 
-    def __init__(self, cell_off, entries, limits, grid, n_all, robot0, n_local, radius, weight):
+    def __init__(self, cell_off, entries, limits, grid, n_all, robot0, n_local, radius, weight, first_step=1):
         self.cell_off, self.entries = cell_off, entries
+        # 1: a constraint table (no entries at time step 0; the guided step's bits are promised on it), 0: a collision table, which also
+        # lists time step 0 (multi_agent.count_collisions_binned / path_conflicts).  The C struct does not carry it.
+        self.first_step = int(first_step)
         self.grid, self.n_all, self.robot0, self.n_local = tuple(grid), int(n_all), int(robot0), int(n_local)
         self.radius, self.weight = float(radius), float(weight)
         b = _lib.ConsBins()
@@ -234,9 +237,10 @@ class BinnedConstraints:
         return self.cell_off.cpu().numpy(), ent, np.ascontiguousarray(ent[..., 2]).view(np.int32)
 
 
-def bin_constraints_table(paths: torch.Tensor, radius, limits, grid):
-    """mmd_bin_constraints_from_paths: the (cell_off [H, nx * ny + 1] int32, entries [H, 9 * n_all, 4] float32) device tensors of the
-    cell table of `paths` [N, H, 2].  One launch on the current stream, no host synchronisation."""
+def bin_constraints_table(paths: torch.Tensor, radius, limits, grid, first_step=1):
+    """mmd_bin_constraints_from_paths (first_step = 1) / mmd_bin_paths: the (cell_off [H, nx * ny + 1] int32, entries [H, 9 * n_all, 4]
+    float32) device tensors of the cell table of `paths` [N, H, 2]; time steps below first_step (0 or 1) get empty lists.  One launch on
+    the current stream, no host synchronisation."""
     lib = _lib.load()
     n_all, (nx, ny) = paths.shape[0], (int(grid[0]), int(grid[1]))
     cell_off = torch.empty((H, nx * ny + 1), dtype=torch.int32, device=paths.device)
@@ -245,17 +249,22 @@ def bin_constraints_table(paths: torch.Tensor, radius, limits, grid):
     lib.mmd_cons_bins_bytes(n_all, nx, ny, C.byref(ob), C.byref(eb))
     assert ob.value == cell_off.numel() * 4 and eb.value == entries.numel() * 4
     lo, hi = (C.c_float * 2)(*[float(v) for v in limits[0]]), (C.c_float * 2)(*[float(v) for v in limits[1]])
-    _lib.launch("mmd_bin_constraints_from_paths", paths, _lib.require_gpu(paths, "paths"), n_all, H, float(radius), lo, hi, nx, ny,
-                cell_off.data_ptr(), entries.data_ptr())
+    if int(first_step) == 1:
+        _lib.launch("mmd_bin_constraints_from_paths", paths, _lib.require_gpu(paths, "paths"), n_all, H, float(radius), lo, hi, nx, ny,
+                    cell_off.data_ptr(), entries.data_ptr())
+    else:
+        _lib.launch("mmd_bin_paths", paths, _lib.require_gpu(paths, "paths"), n_all, H, float(radius), lo, hi, nx, ny, int(first_step),
+                    cell_off.data_ptr(), entries.data_ptr())
     return cell_off, entries
 
 
 def binned_constraints_from_paths(paths: torch.Tensor, robot0: int, n_local: int, radius=VERTEX_CONSTRAINT_RADIUS, weight=2e-2,
-                                  limits=None, grid=None):
+                                  limits=None, grid=None, first_step=1):
     """The soft constraints of soft_constraints_from_paths as a cell table: per time step and map cell the robots near that cell
     instead of N - 1 slots per robot, O(N) instead of O(N^2) work and memory per round, and the same bits out of the guided step.
     paths [N, H, 2] un-normalised best-path positions of ALL robots on this device; the table serves the local robots
-    [robot0, robot0 + n_local).  limits = (lo, hi) of the map (default: environments.LIMITS), grid = (nx, ny) (default: bin_grid)."""
+    [robot0, robot0 + n_local).  limits = (lo, hi) of the map (default: environments.LIMITS), grid = (nx, ny) (default: bin_grid).
+    first_step = 0 also lists time step 0: a collision table (binned_collision_table), which the guide refuses."""
     if limits is None:
         from .environments import LIMITS
         limits = LIMITS
@@ -266,5 +275,17 @@ def binned_constraints_from_paths(paths: torch.Tensor, robot0: int, n_local: int
         raise ValueError("binned_constraints_from_paths: bad robot range")
     grid = bin_grid(limits, radius) if grid is None else tuple(int(v) for v in grid)
     check_bin_grid(limits, radius, grid)
-    cell_off, entries = bin_constraints_table(paths, radius, limits, grid)
-    return BinnedConstraints(cell_off, entries, limits, grid, n_all, robot0, n_local, radius, weight)
+    if int(first_step) not in (0, 1):
+        raise ValueError(f"binned_constraints_from_paths: first_step must be 0 or 1, got {first_step}")
+    cell_off, entries = bin_constraints_table(paths, radius, limits, grid, first_step)
+    return BinnedConstraints(cell_off, entries, limits, grid, n_all, robot0, n_local, radius, weight, first_step)
+
+
+def binned_collision_table(paths: torch.Tensor, robot0: int = 0, n_local: int = None, reach=VERTEX_CONSTRAINT_RADIUS, limits=None,
+                           grid=None):
+    """The cell table of the best paths [N, H, 2] for the collision kernels (multi_agent.count_collisions_binned / path_conflicts): every
+    time step listed, t = 0 included, since collisions count there.  reach: the largest collision margin the table can serve; the default,
+    the constraint radius (0.12 >= the 0.105 robot-robot margin), reuses the constraint table's 15 x 15 grid.  n_local defaults to all
+    robots from robot0 on.  The weight field is not read by those kernels."""
+    n_local = paths.shape[0] - int(robot0) if n_local is None else n_local
+    return binned_constraints_from_paths(paths, robot0, n_local, radius=reach, weight=0.0, limits=limits, grid=grid, first_step=0)

@@ -22,6 +22,7 @@
 
 #include "../../include/mmd_amd.h"
 #include "../../include/mmd_amd_debug.h"
+#include "bins_dev.h"
 #include "common.h"
 #include "guide_dev.h"
 
@@ -528,9 +529,7 @@ __global__ __launch_bounds__(256) void ddpm_guide_coop_kernel(GuideDev g, StepDe
 // acting fmas of the dense chain in the dense order.  Entries that do not act -- too far, the robot itself (one table serves every robot
 // of the GPU), the padding of a lane whose list has ended -- run cons_term with m = 0 and leave their accumulator's bits alone.  (p is
 // finite: the unnormaliser clips.  Time step 0 has empty lists where the dense table has R = -1.)
-__device__ __forceinline__ int bin_cell(float p, float lo, float inv_cell, int n) {
-  return (int)fminf(fmaxf(floorf((p - lo) * inv_cell), 0.f), (float)(n - 1));
-}
+// (bin_cell itself is in bins_dev.h: the collision kernels of multi_agent.hip walk the same lists.)
 
 // the one constraint group a robot has under a cell table: no group tables to read, its weight is the table's
 struct OneGroup {
@@ -673,17 +672,18 @@ __global__ void soft_cons_kernel(const float2* __restrict__ paths, int n_all, in
 // construction.  The step's n_all points and cell indices (ix << 16 | iy) are staged in LDS; thread i owns the cells [i cpt, (i + 1) cpt)
 // (cell = ix * ny + iy) and walks the robots 0 .. n_all - 1 in order twice: to count its cells' entries and, after the block's prefix
 // sum, to write them.  A robot is in the lists of the (at most nine) cells within one index of its own, so a time step's lists fit its
-// segment of 9 n_all entries.  Time step 0 has no constraint (soft_cons_kernel: t in [1, H - 1]): empty lists.
+// segment of 9 n_all entries.  Time steps below first_step get empty lists: a constraint table starts at 1 (time step 0 has no
+// constraint, soft_cons_kernel: t in [1, H - 1]), a collision table (mmd_bin_paths) at 0.
 constexpr int BIN_THREADS = 256;
 __global__ __launch_bounds__(BIN_THREADS) void bin_cons_kernel(const float2* __restrict__ paths, int n_all, float lo0, float lo1, float inv0,
-                                                               float inv1, int nx, int ny, int* __restrict__ cell_off,
+                                                               float inv1, int nx, int ny, int first_step, int* __restrict__ cell_off,
                                                                float4* __restrict__ entries) {
   extern __shared__ __attribute__((aligned(16))) float2 lds_pts[];       // [n_all] points, [n_all] cells, [BIN_THREADS] scan
   int* const lds_cell = reinterpret_cast<int*>(lds_pts + n_all);
   int* const scan = lds_cell + n_all;
   const int t = blockIdx.x, tid = threadIdx.x, ncell = nx * ny;
   int* const off = cell_off + (size_t)t * (ncell + 1);
-  if (t == 0) {
+  if (t < first_step) {
     for (int c = tid; c <= ncell; c += BIN_THREADS) off[c] = 0;
     return;
   }
@@ -726,8 +726,8 @@ __global__ __launch_bounds__(BIN_THREADS) void bin_cons_kernel(const float2* __r
 constexpr int BIN_MAX_ROBOTS = 4096;     // 12 B of LDS per robot in bin_cons_kernel
 constexpr int BIN_MAX_CELLS = 64;        // per axis
 
-// a cell table as a guided step may use it (every field but the two device arrays' contents)
-static int check_cons_bins(const mmd_cons_bins* b) {
+// a cell table as a guided step or a collision kernel may use it (every field but the two device arrays' contents)
+int check_cons_bins(const mmd_cons_bins* b) {
   MMD_REQUIRE(b->cell_off_dev && b->entries_dev, "cons_bins: NULL table");
   MMD_REQUIRE(b->nx >= 1 && b->nx <= BIN_MAX_CELLS && b->ny >= 1 && b->ny <= BIN_MAX_CELLS, "cons_bins: grid %d x %d outside [1, %d]", b->nx,
               b->ny, BIN_MAX_CELLS);
@@ -913,28 +913,40 @@ size_t mmd_cons_bins_bytes(int n_all, int nx, int ny, size_t* off_bytes, size_t*
   return ob + eb;
 }
 
-int mmd_bin_constraints_from_paths(const float* paths_dev, int n_all, int horizon, float radius, const float lo[2], const float hi[2],
-                                   int nx, int ny, int32_t* cell_off_dev, float* entries_dev, void* stream) {
-  MMD_REQUIRE(paths_dev && lo && hi && cell_off_dev && entries_dev, "mmd_bin_constraints_from_paths: NULL argument");
-  MMD_REQUIRE(horizon == H, "horizon must be %d", H);
-  MMD_REQUIRE(n_all >= 2 && n_all <= BIN_MAX_ROBOTS, "mmd_bin_constraints_from_paths: n_all must be in [2, %d]", BIN_MAX_ROBOTS);
-  MMD_REQUIRE(radius > 0.f, "mmd_bin_constraints_from_paths: radius must be positive");
-  MMD_REQUIRE(nx >= 1 && nx <= BIN_MAX_CELLS && ny >= 1 && ny <= BIN_MAX_CELLS, "mmd_bin_constraints_from_paths: grid %d x %d outside [1, %d]",
-              nx, ny, BIN_MAX_CELLS);
+// the table build behind mmd_bin_constraints_from_paths (first_step = 1) and mmd_bin_paths; `who` names the entry point in the error text
+static int bin_paths(const char* who, const float* paths_dev, int n_all, int horizon, float radius, const float lo[2], const float hi[2],
+                     int nx, int ny, int first_step, int32_t* cell_off_dev, float* entries_dev, void* stream) {
+  MMD_REQUIRE(paths_dev && lo && hi && cell_off_dev && entries_dev, "%s: NULL argument", who);
+  MMD_REQUIRE(horizon == H, "%s: horizon must be %d", who, H);
+  MMD_REQUIRE(first_step == 0 || first_step == 1, "%s: first_step must be 0 or 1, got %d", who, first_step);
+  MMD_REQUIRE(n_all >= 2 && n_all <= BIN_MAX_ROBOTS, "%s: n_all must be in [2, %d]", who, BIN_MAX_ROBOTS);
+  MMD_REQUIRE(radius > 0.f, "%s: radius must be positive", who);
+  MMD_REQUIRE(nx >= 1 && nx <= BIN_MAX_CELLS && ny >= 1 && ny <= BIN_MAX_CELLS, "%s: grid %d x %d outside [1, %d]", who, nx, ny,
+              BIN_MAX_CELLS);
   const int n[2] = {nx, ny};
   float inv[2];
   for (int k = 0; k < 2; ++k) {
-    MMD_REQUIRE(hi[k] > lo[k], "mmd_bin_constraints_from_paths: empty limits");
+    MMD_REQUIRE(hi[k] > lo[k], "%s: empty limits", who);
     // the cover argument above bin_cell needs (1 + 1/16) R <= the cell side
     MMD_REQUIRE(((double)hi[k] - (double)lo[k]) / n[k] >= 1.0625 * (double)radius,
-                "mmd_bin_constraints_from_paths: cells smaller than (1 + 1/16) x the radius (axis %d: %g < %g)", k,
-                ((double)hi[k] - (double)lo[k]) / n[k], 1.0625 * (double)radius);
+                "%s: cells smaller than (1 + 1/16) x the radius (axis %d: %g < %g)", who, k, ((double)hi[k] - (double)lo[k]) / n[k],
+                1.0625 * (double)radius);
     inv[k] = (float)n[k] / (hi[k] - lo[k]);                  // mmd_cons_bins.inv_cell: this fp32 quotient
   }
   hipLaunchKernelGGL(bin_cons_kernel, dim3(H), dim3(BIN_THREADS), (size_t)n_all * 12 + BIN_THREADS * sizeof(int), (hipStream_t)stream,
-                     (const float2*)paths_dev, n_all, lo[0], lo[1], inv[0], inv[1], nx, ny, cell_off_dev, (float4*)entries_dev);
+                     (const float2*)paths_dev, n_all, lo[0], lo[1], inv[0], inv[1], nx, ny, first_step, cell_off_dev, (float4*)entries_dev);
   MMD_HIP_CHECK(hipGetLastError());
   return 0;
+}
+
+int mmd_bin_constraints_from_paths(const float* paths_dev, int n_all, int horizon, float radius, const float lo[2], const float hi[2],
+                                   int nx, int ny, int32_t* cell_off_dev, float* entries_dev, void* stream) {
+  return bin_paths("mmd_bin_constraints_from_paths", paths_dev, n_all, horizon, radius, lo, hi, nx, ny, 1, cell_off_dev, entries_dev, stream);
+}
+
+int mmd_bin_paths(const float* paths_dev, int n_all, int horizon, float reach, const float lo[2], const float hi[2], int nx, int ny,
+                  int first_step, int32_t* cell_off_dev, float* entries_dev, void* stream) {
+  return bin_paths("mmd_bin_paths", paths_dev, n_all, horizon, reach, lo, hi, nx, ny, first_step, cell_off_dev, entries_dev, stream);
 }
 
 int mmd_guide_steps(const mmd_guide_desc* d, float* x_dev, const float* hard_dev, uint64_t hard_rows, int n_robots,

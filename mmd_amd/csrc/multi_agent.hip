@@ -9,12 +9,16 @@
 //     (cbs.py:166-246, :446-508; prioritized_planning.py:149-182, :212-298): the conflict list of a search state, the
 //     'least_collisions' choice of a re-planned agent, and the soft / hard constraint table built from the other agents' paths.
 //     Agent k's position at global time t is path_k[clamp(t - s_k, 0, L_k - 1)] (global_pad_paths, multi_agent_utils.py:120-143,
-//     without the padded tensors).
+//     without the padded tensors);
+//   * the same pick and the conflict report of a round's best paths on a CELL table of those paths (include/mmd_amd.h: mmd_cons_bins,
+//     built by mmd_bin_paths with first_step = 0): a point meets only the robots in the list of its own cell, so a round of N robots
+//     costs O(N x list length) where the kernels above walk all N (or all N^2 pairs).
 #include <hip/hip_runtime.h>
 
 #include <climits>
 
 #include "../../include/mmd_amd.h"
+#include "bins_dev.h"             // bin_cell / check_cons_bins: the cell table of guide.hip
 #include "collision_dev.h"        // torch_norm2 / rr_hit: the pinned fp32 form of the collision decision (sets fp contract(off))
 #include "common.h"
 
@@ -171,6 +175,165 @@ __global__ __launch_bounds__(256) void conflict_emit_kernel(const mmd_agent_path
   }
 }
 
+// ---- the pick and the conflict report on a cell table of the best paths -------------------------------------------------------------
+//
+// COVER (the argument of guide.hip's comment on bin_cell, for the collision decision): a point p meets a table point q iff rr_hit, i.e.
+// sqrtf(s) < margin with s = fma(dy, dy, dx * dx) in fp32.  sqrtf is correctly rounded and monotone, so s < margin^2 (1 + 2^-22).  The
+// exact radicand dy^2 + fl(dx * dx) is at least fl(dx * dx) and at least dy^2, and rounding is monotone: s >= fl(dx * dx) >=
+// dx^2 (1 - 2^-24) and s >= fl(dy^2) >= dy^2 (1 - 2^-24).  Hence |dx|, |dy| < margin (1 + 2^-22): a few ulp over margin.  With
+// margin <= bins->radius that is the bound the cell rule (cells >= (1 + 1/16) x radius) was made for: the cell indices of p and q
+// differ by at most 1 per axis, so q is in the list of p's own cell, and the entry points refuse margin > radius.
+// A count is an integer: the order of a list does not matter to it, only that every hit is in the list exactly once (a robot has one
+// entry per time step and list) and that the robot's own entry is skipped by id.  The table must list time step 0 (mmd_bin_paths with
+// first_step = 0): the dense kernels count collisions there.
+
+// the list of the cell of p at time step t: entries [e0, e1) of `ent`
+struct CellList {
+  const float4* ent;
+  int e0, e1;
+};
+__device__ __forceinline__ CellList own_cell_list(const mmd_cons_bins& b, int t, float px, float py) {
+  const int cell = bin_cell(px, b.lo[0], b.inv_cell[0], b.nx) * b.ny + bin_cell(py, b.lo[1], b.inv_cell[1], b.ny);
+  const int* off = b.cell_off_dev + (size_t)t * (b.nx * b.ny + 1) + cell;
+  return CellList{reinterpret_cast<const float4*>(b.entries_dev) + (size_t)t * 9 * b.n_all, off[0], off[1]};
+}
+
+// count_collisions_kernel on the table: one wave per trajectory, lane = time step, four trajectories a workgroup, no LDS.  The wave
+// walks the lanes' lists four entries a trip -- the loads of a trip are issued together -- while any lane has entries left; a lane past
+// its list re-reads an entry of the segment and drops it.  P = float4 (sample trajectories) or float2 (the best paths themselves: the
+// per-robot counts of the conflict report).
+template <typename P>
+__global__ __launch_bounds__(256) void count_collisions_binned_kernel(const P* __restrict__ pts, mmd_cons_bins b, int robot0,
+                                                                      int samples_per_robot, int n_traj, float margin,
+                                                                      int* __restrict__ counts) {
+  const int t = threadIdx.x & 63;
+  const int traj = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (traj >= n_traj) return;
+  const int self = robot0 + traj / samples_per_robot;
+  const P pt = pts[(size_t)traj * H + t];
+  const float2 p = make_float2(pt.x, pt.y);
+  const CellList l = own_cell_list(b, t, p.x, p.y);
+  const int last = max(l.e1 - 1, 0);
+  int c = 0;
+  for (int e = l.e0; __builtin_amdgcn_ballot_w64(e < l.e1) != 0; e += 4) {
+    float4 q[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) q[j] = l.ent[min(e + j, last)];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const bool other = e + j < l.e1 && __builtin_bit_cast(int, q[j].z) != self;
+      c += other && rr_hit(p, make_float2(q[j].x, q[j].y), margin) ? 1 : 0;
+    }
+  }
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) c += __shfl_xor(c, m);
+  if (t == 0) counts[traj] = c;
+}
+
+// exclusive prefix of `v` over a 256-thread block in thread order; returns the block total
+__device__ __forceinline__ int block_prefix_count(int v, int* lds4, int& prefix) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int inc = v;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const int o = __shfl_up(inc, d);
+    inc += lane >= d ? o : 0;
+  }
+  if (lane == 63) lds4[wave] = inc;
+  __syncthreads();
+  int before = 0, total = 0;
+#pragma unroll
+  for (int w = 0; w < 4; ++w) {
+    before += w < wave ? lds4[w] : 0;
+    total += lds4[w];
+  }
+  __syncthreads();
+  prefix = before + inc - v;
+  return total;
+}
+
+// the number of robots b > a that robot a (at pa, time step t) collides with: the entries of its own list above its id
+__device__ __forceinline__ int pairs_above(const CellList& l, int a, float2 pa, float margin) {
+  int c = 0;
+  for (int e = l.e0; e < l.e1; ++e) {
+    const float4 q = l.ent[e];
+    c += __builtin_bit_cast(int, q.z) > a && rr_hit(pa, make_float2(q.x, q.y), margin) ? 1 : 0;
+  }
+  return c;
+}
+
+// conflict_rows_kernel (MMD_CONFLICTS_PAIRS, equal start times) on the table: one workgroup per time step, a thread per robot
+__global__ __launch_bounds__(256) void path_conflict_rows_binned_kernel(const float2* __restrict__ paths, mmd_cons_bins b, float margin,
+                                                                         int* __restrict__ row_counts) {
+  __shared__ int lds4[4];
+  const int t = blockIdx.x;
+  int c = 0;
+  for (int a = threadIdx.x; a < b.n_all; a += 256) {
+    const float2 pa = paths[(size_t)a * H + t];
+    c += pairs_above(own_cell_list(b, t, pa.x, pa.y), a, pa, margin);
+  }
+  c = block_sum(c, lds4);
+  if (threadIdx.x == 0) row_counts[t] = c;
+}
+
+// conflict_emit_kernel on the table: the records of row t at their place in the (t, a, b) list, a < b.  Robots in blocks of 256 in
+// ascending id; robot a's records are the entries of its own list above its id, which a list holds in ascending id: a first pass counts
+// them, the block's prefix places them, a second pass writes them.  No atomics: the list is the same on every run.
+__global__ __launch_bounds__(256) void path_conflict_emit_binned_kernel(const float2* __restrict__ paths, mmd_cons_bins b, float margin,
+                                                                         const int* __restrict__ row_counts, int* __restrict__ count,
+                                                                         mmd_conflict* __restrict__ first, mmd_conflict* __restrict__ list,
+                                                                         int list_cap) {
+  __shared__ int lds4[4];
+  const int t = blockIdx.x;
+  int before = 0;
+  for (int k = threadIdx.x; k < t; k += 256) before += row_counts[k];
+  before = block_sum(before, lds4);
+  if (t == H - 1 && threadIdx.x == 0) {
+    const int total = before + row_counts[t];
+    *count = total;
+    if (total == 0 && first) {
+      mmd_conflict none{};
+      none.t = none.a = none.b = -1;
+      *first = none;
+    }
+  }
+  if (row_counts[t] == 0) return;
+  const bool want_first = first && before == 0;
+  if (!want_first && !(list && before < list_cap)) return;
+  int base = before;
+  for (int a0 = 0; a0 < b.n_all; a0 += 256) {
+    if (base > 0 && base >= list_cap) return;               // (the rest of the row lies past the list; uniform over the block)
+    const int a = a0 + threadIdx.x;
+    float2 pa = make_float2(0.f, 0.f);
+    CellList l{nullptr, 0, 0};
+    int mine = 0;
+    if (a < b.n_all) {
+      pa = paths[(size_t)a * H + t];
+      l = own_cell_list(b, t, pa.x, pa.y);
+      mine = pairs_above(l, a, pa, margin);
+    }
+    int idx;
+    const int total = block_prefix_count(mine, lds4, idx);
+    idx += base;
+    for (int e = l.e0; mine > 0 && e < l.e1; ++e) {
+      const float4 q = l.ent[e];
+      const int ob = __builtin_bit_cast(int, q.z);
+      const float2 pb = make_float2(q.x, q.y);
+      if (!(ob > a && rr_hit(pa, pb, margin))) continue;
+      mmd_conflict r;
+      r.t = t; r.a = a; r.b = ob; r.reserved = 0;
+      r.pa[0] = pa.x; r.pa[1] = pa.y; r.pb[0] = pb.x; r.pb[1] = pb.y;
+      r.mid[0] = (pa.x + pb.x) / 2.f; r.mid[1] = (pa.y + pb.y) / 2.f;
+      r.reserved2[0] = r.reserved2[1] = 0.f;
+      if (idx == 0 && first) *first = r;
+      if (list && idx < list_cap) list[idx] = r;
+      ++idx;
+      --mine;
+    }
+    base += total;
+  }
+}
+
 // one wave per candidate, lane = global time step: #{(t, j != self) : candidate(t) hits agent j(t)}
 __global__ __launch_bounds__(256) void candidate_pairs_kernel(const mmd_agent_path* __restrict__ agents, int n, int Tg, int self,
                                                                const float* __restrict__ cand_batch, const int* __restrict__ cand_idx,
@@ -292,6 +455,46 @@ int mmd_count_collisions(const float* trajs_dev, const float* paths_dev, int rob
   hipLaunchKernelGGL(count_collisions_kernel, dim3((n_traj + 3) / 4), dim3(256), 0, (hipStream_t)stream,
                      (const float4*)trajs_dev, (const float2*)paths_dev, robot0, samples_per_robot, n_traj, n_all, margin,
                      counts_dev);
+  MMD_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+// what the two collision entry points on a cell table share: the table's own checks, and margin <= radius (COVER above)
+static int check_collision_bins(const char* who, const mmd_cons_bins* bins, float margin) {
+  MMD_REQUIRE(bins, "%s: NULL table", who);
+  if (int rc = check_cons_bins(bins)) return rc;
+  MMD_REQUIRE(margin <= bins->radius, "%s: margin %g above the table's radius %g (a list could miss a colliding robot)", who, margin,
+              bins->radius);
+  return 0;
+}
+
+int mmd_count_collisions_binned(const float* trajs_dev, const mmd_cons_bins* bins, int n_local, int samples_per_robot, float margin,
+                                int32_t* counts_dev, void* stream) {
+  MMD_REQUIRE(trajs_dev && counts_dev, "mmd_count_collisions_binned: NULL argument");
+  if (int rc = check_collision_bins("mmd_count_collisions_binned", bins, margin)) return rc;
+  MMD_REQUIRE(n_local >= 1 && samples_per_robot >= 1 && bins->robot0 + n_local <= bins->n_all, "mmd_count_collisions_binned: bad robot range");
+  const int n_traj = n_local * samples_per_robot;
+  hipLaunchKernelGGL(count_collisions_binned_kernel<float4>, dim3((n_traj + 3) / 4), dim3(256), 0, (hipStream_t)stream,
+                     (const float4*)trajs_dev, *bins, bins->robot0, samples_per_robot, n_traj, margin, counts_dev);
+  MMD_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+int mmd_path_conflicts_binned(const float* paths_dev, const mmd_cons_bins* bins, int horizon, float margin, int32_t* row_counts_dev,
+                              int32_t* robot_counts_dev, int32_t* count_dev, mmd_conflict* first_dev, mmd_conflict* list_dev, int list_cap,
+                              void* stream) {
+  MMD_REQUIRE(paths_dev && row_counts_dev && count_dev, "mmd_path_conflicts_binned: NULL argument");
+  MMD_REQUIRE(horizon == H, "mmd_path_conflicts_binned: horizon must be %d", H);
+  MMD_REQUIRE(list_cap >= 0 && (list_cap == 0 || list_dev), "mmd_path_conflicts_binned: list_cap without a list");
+  if (int rc = check_collision_bins("mmd_path_conflicts_binned", bins, margin)) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  const float2* paths = (const float2*)paths_dev;
+  hipLaunchKernelGGL(path_conflict_rows_binned_kernel, dim3(H), dim3(256), 0, st, paths, *bins, margin, row_counts_dev);
+  hipLaunchKernelGGL(path_conflict_emit_binned_kernel, dim3(H), dim3(256), 0, st, paths, *bins, margin, row_counts_dev, count_dev, first_dev,
+                     list_cap > 0 ? list_dev : nullptr, list_cap);
+  if (robot_counts_dev)                                  // every robot's own path as a "sample" of one: each pair counts for both robots
+    hipLaunchKernelGGL(count_collisions_binned_kernel<float2>, dim3((bins->n_all + 3) / 4), dim3(256), 0, st, paths, *bins, 0, 1,
+                       bins->n_all, margin, robot_counts_dev);
   MMD_HIP_CHECK(hipGetLastError());
   return 0;
 }

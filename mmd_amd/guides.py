@@ -130,6 +130,9 @@ class GuideManagerTrajectoriesWithVelocity:
         mix); reset_extra_costs clears it."""
         if binned is not None and binned.n_local != self.n_robots:
             raise ValueError(f"set_binned_constraints: a table for {binned.n_local} local robots on a guide of {self.n_robots}")
+        if binned is not None and getattr(binned, "first_step", 1) != 1:
+            # a table that lists time step 0 is a collision table: the guided step is promised bitwise only on tables without t = 0
+            raise ValueError(f"set_binned_constraints: a constraint table starts at time step 1, this one at {binned.first_step}")
         self._binned = binned
 
     def _constraints(self):

@@ -1,6 +1,9 @@
 """Device-side multi-agent helpers next to the sampler: robot-robot collisions of the best paths
 (RobotPlanarDisk.check_rr_collisions as CBS.get_conflicts uses it, cbs.py:166-246) and the 'least_collisions' batch scan
-(cbs.py:446-458).  Thin wrappers over the C ABI (mmd_rr_collisions, mmd_count_collisions)."""
+(cbs.py:446-458), both also on a cell table of the best paths (count_collisions_binned, path_conflicts: O(N) work per round instead of
+O(N^2)).  Thin wrappers over the C ABI (mmd_rr_collisions, mmd_count_collisions, mmd_count_collisions_binned, mmd_path_conflicts_binned)."""
+import ctypes as C
+
 import numpy as np
 import torch
 
@@ -29,6 +32,24 @@ def count_collisions(trajs, paths_all, robot0, n_local, margin=RR_MARGIN):
     _lib.launch("mmd_count_collisions", trajs, _lib.require_gpu(trajs.contiguous(), "trajs"),
                                                 _lib.require_gpu(paths_all.contiguous(), "paths_all"), robot0, n_local,
                                                 B, paths_all.shape[0], H, float(margin), counts.data_ptr())
+    return counts.view(n_local, B)
+
+
+def _collision_table(table, what):
+    if getattr(table, "first_step", None) != 0:
+        raise ValueError(f"{what}: a collision table lists time step 0 (constraints.binned_collision_table), this one starts at "
+                         f"{getattr(table, 'first_step', None)}")
+    return table
+
+
+def count_collisions_binned(trajs, table, n_local, margin=RR_MARGIN):
+    """count_collisions on a cell table of the best paths (constraints.binned_collision_table(paths_all, robot0, n_local)) instead of
+    the paths: a sample point meets only the robots near its cell.  -> int32 [n_local, B], the same integers."""
+    _collision_table(table, "count_collisions_binned")
+    B = trajs.shape[0] // n_local
+    counts = torch.empty(n_local * B, dtype=torch.int32, device=trajs.device)
+    _lib.launch("mmd_count_collisions_binned", trajs, _lib.require_gpu(trajs.contiguous(), "trajs"), C.byref(table.struct), n_local, B,
+                float(margin), counts.data_ptr())
     return counts.view(n_local, B)
 
 
@@ -70,6 +91,40 @@ def find_conflicts(table, n, Tg, mode, list_cap=0, margin=RR_MARGIN):
     _lib.launch("mmd_find_conflicts", table, table.data_ptr(), int(n), int(Tg), float(margin), int(mode), rows.data_ptr(),
                 summ.data_ptr(), summ.data_ptr() + 16, lst.data_ptr() if lst is not None else None, int(list_cap))
     return summ, lst
+
+
+def path_conflicts(paths_all, margin=RR_MARGIN, list_cap=0, table=None, row_counts=None):
+    """The conflict report of a round's best paths [N, 64, 2] (equal start times) on a cell table (mmd_path_conflicts_binned), built here
+    when none is passed (constraints.binned_collision_table) -> (summary, robot_counts, list): the summary has find_conflicts' 16-word
+    layout ([0] = count, [4:16] = the first record; `read_summary` / `decode_records` read it) and is what find_conflicts(..., PAIRS)
+    gives for these paths; robot_counts int32 [N] = the (t, other robot) collisions of every robot; list [list_cap, 12] words or None.
+    row_counts: an optional int32 [64] device tensor that receives the count per time step.  No N^2 buffer, no host synchronisation."""
+    paths_all = paths_all.contiguous()
+    if paths_all.shape[0] < 2 and table is None:               # one robot: nothing to collide with (and no table of fewer than two)
+        summ = torch.zeros(16, dtype=torch.int32, device=paths_all.device)
+        summ[4:7] = -1
+        if row_counts is not None:
+            row_counts.zero_()
+        lst = torch.empty((list_cap, _CONFLICT_WORDS), dtype=torch.int32, device=paths_all.device) if list_cap > 0 else None
+        return summ, torch.zeros(paths_all.shape[0], dtype=torch.int32, device=paths_all.device), lst
+    if table is None:
+        from .constraints import binned_collision_table
+        table = binned_collision_table(paths_all)
+    _collision_table(table, "path_conflicts")
+    n = paths_all.shape[0]
+    if table.n_all != n or paths_all.shape[1] != H:
+        raise ValueError(f"path_conflicts: paths {tuple(paths_all.shape)} and a table of {table.n_all} robots")
+    dev = paths_all.device
+    summ = torch.empty(16, dtype=torch.int32, device=dev)
+    rows = torch.empty(H, dtype=torch.int32, device=dev) if row_counts is None else row_counts
+    if not (rows.is_cuda and rows.dtype == torch.int32 and rows.is_contiguous() and rows.numel() == H):
+        raise ValueError(f"path_conflicts: row_counts must be a contiguous int32 device tensor of {H} words")
+    robots = torch.empty(n, dtype=torch.int32, device=dev)
+    lst = torch.empty((list_cap, _CONFLICT_WORDS), dtype=torch.int32, device=dev) if list_cap > 0 else None
+    _lib.launch("mmd_path_conflicts_binned", paths_all, _lib.require_gpu(paths_all, "paths_all"), C.byref(table.struct), H, float(margin),
+                rows.data_ptr(), robots.data_ptr(), summ.data_ptr(), summ.data_ptr() + 16, lst.data_ptr() if lst is not None else None,
+                int(list_cap))
+    return summ, robots, lst
 
 
 def decode_records(words):

@@ -7,14 +7,17 @@ rank g owns robots [g*n_local, (g+1)*n_local) and the only exchange is ONE all-g
 paths [n_local, H, 2] -> [N, H, 2] (RCCL over xGMI on GPUs, gloo in the CPU tests), after which every rank rebuilds
 its robots' soft-constraint table on device (mmd_soft_constraints_from_paths: N - 1 slots per robot; or, with
 constraint_table="binned", mmd_bin_constraints_from_paths: per time step and map cell the robots near the cell -- O(N) work and
-memory per round instead of O(N^2), the same bits).
+memory per round instead of O(N^2), the same bits).  With the cell table the rest of the round is O(N) too: the best-path pick counts
+on a cell table of the gathered paths (mmd_count_collisions_binned), and MultiRobotSampler.plan -- rounds until the paths stop
+colliding -- reads a device-side conflict report of them (mmd_path_conflicts_binned) at the start of every round.
 """
+from dataclasses import dataclass
 from math import ceil
 
 import torch
 
 from . import synth
-from .constraints import VERTEX_CONSTRAINT_RADIUS, binned_constraints_from_paths, soft_constraints_from_paths
+from .constraints import VERTEX_CONSTRAINT_RADIUS, binned_collision_table, binned_constraints_from_paths, soft_constraints_from_paths
 from .diffusion_model import ddpm_sample_fn
 from .guides import GuideManagerTrajectoriesWithVelocity
 from .normalization import TrajectoryDatasetFacade
@@ -53,6 +56,18 @@ def all_gather_paths(paths_local, world_size, group=None, force_collective=False
     return out
 
 
+@dataclass
+class PlanResult:
+    """What MultiRobotSampler.plan returns."""
+    paths_local: torch.Tensor        # [n_local, H, 2] un-normalised best paths of this rank's robots
+    trajs: torch.Tensor              # [n_local * B, H, D] normalised samples of the last round run (None: no round was run)
+    n_rounds: int                    # sampling rounds run
+    conflict_counts: list            # one int per conflict report: at the start of every round run, then of the returned paths
+    robot_counts: torch.Tensor       # int32 [N] on the device: (t, other robot) collisions of every robot, of the returned paths
+    conflict_free: bool              # conflict_counts[-1] == 0
+    first_conflict: tuple            # (t, a, b, pa, pb, mid) of the returned paths' first conflict, or None
+
+
 class MultiRobotSampler:
     def __init__(self, model, starts, goals, env_id="EnvEmpty2D", n_samples=64, rank=0, world_size=1,
                  norm_mins=synth.NORM_MINS, norm_maxs=synth.NORM_MAXS, n_guide_steps=20,
@@ -73,6 +88,7 @@ class MultiRobotSampler:
         self.guide = GuideManagerTrajectoriesWithVelocity(self.dataset, env_id=env_id, n_robots=self.n_local,
                                                           device=device)
         sl = slice(self.robot0, self.robot0 + self.n_local)
+        self._ends = (starts[sl], goals[sl])      # plan(): the straight lines the first round starts from
         st = torch.as_tensor(starts[sl], dtype=torch.float32)
         go = torch.as_tensor(goals[sl], dtype=torch.float32)
         z = torch.zeros_like(st)
@@ -87,15 +103,27 @@ class MultiRobotSampler:
         # False: no inter-robot term (BASELINE config 2: every robot guided by the map, the workspace and the GP prior alone) --
         # plan_round then needs no exchange step either
         self.inter_robot = inter_robot
+        self._collision = None          # "binned": (paths_all, its collision table), kept from set_other_paths for best_paths
+
+    def _collision_table(self, paths_all):
+        """The collision cell table of paths_all (every time step listed): built once per round, by set_other_paths or by the first
+        best_paths that needs it."""
+        if self._collision is None or self._collision[0] is not paths_all:
+            self._collision = (paths_all, binned_collision_table(paths_all.contiguous(), self.robot0, self.n_local, self.radius))
+        return self._collision[1]
 
     def set_other_paths(self, paths_all):
-        """paths_all [N,H,2] un-normalised best paths of ALL robots (this device) or None (no inter-robot term)."""
+        """paths_all [N,H,2] un-normalised best paths of ALL robots (this device) or None (no inter-robot term).  With the cell table
+        the collision table of the same paths is built here too and kept for best_paths (which rebuilds it for another tensor: do not
+        modify paths_all in place in between)."""
+        self._collision = None
         if paths_all is None or self.n_robots < 2:
             self.guide.reset_extra_costs()
         elif self.constraint_table == "binned":
             self.guide.reset_extra_costs()
             self.guide.set_binned_constraints(binned_constraints_from_paths(
                 paths_all.contiguous(), self.robot0, self.n_local, self.radius, self.w_soft))
+            self._collision_table(paths_all)
         else:
             self.guide.set_packed_constraints(soft_constraints_from_paths(
                 paths_all.contiguous(), self.robot0, self.n_local, self.radius, self.w_soft))
@@ -120,7 +148,8 @@ class MultiRobotSampler:
         """Selection for the exchange step, on the device: samples that collide with the map or leave the joint limits
         are dropped first (PlanningTask.get_trajs_collision_and_free, tasks.py:236-311, as MPD.__call__ does at
         mpd.py:357-382); among the free ones the pick is the first sample with the fewest robot-robot collisions against
-        the other robots' current best paths (CBS 'least_collisions', cbs.py:446-458), or the cheapest one (path length +
+        the other robots' current best paths (CBS 'least_collisions', cbs.py:446-458; with constraint_table="binned" counted on a cell
+        table of paths_all, the same counts), or the cheapest one (path length +
         smoothness, mpd.py:366-370) when no paths are known yet.  A robot without any free sample falls back to the same
         criterion over all its samples (`self.last_n_free` tells).  Returns un-normalised positions [n_local,H,2]."""
         from . import postprocess as post
@@ -129,8 +158,11 @@ class MultiRobotSampler:
         if paths_all is None or self.n_robots < 2:
             idx, n_free = post.select_best(r.free_mask, self.n_local, cost_a=r.path_length, cost_b=r.smoothness)
         else:
-            from .multi_agent import count_collisions
-            counts = count_collisions(t, paths_all, self.robot0, self.n_local)
+            from .multi_agent import count_collisions, count_collisions_binned
+            if self.constraint_table == "binned":       # the same integers from the cell lists instead of all N robots
+                counts = count_collisions_binned(t, self._collision_table(paths_all), self.n_local)
+            else:
+                counts = count_collisions(t, paths_all, self.robot0, self.n_local)
             idx, n_free = post.select_best(r.free_mask, self.n_local, counts=counts.view(-1))
         self.last_n_free, self.last_idx = n_free, idx
         tv = t.view(self.n_local, self.n_samples, H, D)
@@ -142,3 +174,34 @@ class MultiRobotSampler:
         self.set_other_paths(paths_all)
         trajs = self.sample(seed=seed)
         return trajs, self.best_paths(trajs, paths_all)
+
+    def plan(self, paths_local=None, max_rounds=8, seed=0, list_cap=0):
+        """Rounds of plan_round until the gathered best paths are free of robot-robot conflicts, at most max_rounds of them.  Round k
+        (seed + k): all-gather the paths, report their conflicts on the device (multi_agent.path_conflicts; the count crosses in one
+        device -> host copy, the only synchronisation the loop adds), stop if k > 0 and there are none or if k == max_rounds, else
+        build the table(s), sample and pick.  After the last round run, the returned paths are gathered once more for the final report:
+        conflict_free, robot_counts and first_conflict describe what is returned.  Every rank computes the same report from the same
+        gathered paths, so the ranks stop together without another collective.  paths_local defaults to this rank's straight lines
+        start -> goal.  list_cap > 0 also keeps the first records of the final report (`self.last_conflict_list`, [list_cap, 12] words).
+        -> PlanResult."""
+        from .multi_agent import path_conflicts, read_summary
+        if paths_local is None:
+            import numpy as np
+            st, go = (np.asarray(torch.as_tensor(v).cpu().numpy(), dtype=np.float32) for v in self._ends)
+            paths_local = torch.from_numpy(synth.straight_line_paths(st, go, H)).to(self.device)
+        trajs, counts, k = None, [], 0
+        while True:
+            paths_all = all_gather_paths(paths_local, self.world_size, self.group).contiguous()
+            last = k == max_rounds
+            summ, robots, lst = path_conflicts(paths_all, list_cap=list_cap)
+            count, first = read_summary(summ)
+            counts.append(count)
+            if last or (k > 0 and count == 0):
+                break
+            others = paths_all if self.inter_robot else None
+            self.set_other_paths(others)
+            trajs = self.sample(seed=seed + k)
+            paths_local = self.best_paths(trajs, others)
+            k += 1
+        self.last_conflict_list = lst
+        return PlanResult(paths_local, trajs, k, counts, robots, count == 0, first)

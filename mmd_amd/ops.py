@@ -1,5 +1,5 @@
 """PyTorch-ROCm custom ops over the C ABI (include/mmd_amd.h): `torch.ops.mmd_amd.{unet_forward, guide_steps,
-p_sample_loop, ddim_sample, solution_stats, bin_constraints_from_paths}`.  They take tensors instead of raw pointers, run on torch's CURRENT HIP stream
+p_sample_loop, ddim_sample, solution_stats, bin_constraints_from_paths, count_collisions_binned, path_conflicts}`.  They take tensors instead of raw pointers, run on torch's CURRENT HIP stream
 without any host synchronisation (so they can be captured into a hipGraph with torch.cuda.graph) and register fake
 (meta) implementations so that torch.compile / FakeTensor tracing sees their output shapes.  The C header stays the ABI
 of record: every op is a thin wrapper over the same entry point the host mirror classes call through ctypes.
@@ -179,3 +179,42 @@ def bin_constraints_from_paths(paths: torch.Tensor, radius: float, lo_x: float, 
 @bin_constraints_from_paths.register_fake
 def _(paths, radius, lo_x, lo_y, hi_x, hi_y, nx, ny):
     return (paths.new_empty((64, nx * ny + 1), dtype=torch.int32), paths.new_empty((64, 9 * paths.shape[0], 4)))
+
+
+# ---- count_collisions_binned / path_conflicts ----------------------------------------------------------------------
+def _collision_table(paths, robot0, n_local):
+    from . import constraints
+    if not (paths.is_cuda and paths.dtype == torch.float32 and paths.is_contiguous() and paths.ndim == 3 and paths.shape[1] == 64
+            and paths.shape[2] == 2):
+        raise RuntimeError("mmd_amd op: paths must be a contiguous float32 CUDA(HIP) tensor [n_all, 64, 2]")
+    return constraints.binned_collision_table(paths, robot0, n_local)
+
+
+@torch.library.custom_op("mmd_amd::count_collisions_binned", mutates_args=(), device_types="cuda")
+def count_collisions_binned(trajs: torch.Tensor, paths: torch.Tensor, robot0: int, n_local: int, margin: float) -> torch.Tensor:
+    """The 'least_collisions' counts int32 [n_local, B] of the local robots' un-normalised samples trajs [n_local * B, 64, 4] against the
+    best paths [n_all, 64, 2], on a cell table of the paths built here (mmd_bin_paths + mmd_count_collisions_binned): the integers of
+    mmd_count_collisions."""
+    from . import multi_agent
+    _check_traj(trajs, "trajs")
+    return multi_agent.count_collisions_binned(trajs, _collision_table(paths, robot0, n_local), n_local, margin)
+
+
+@count_collisions_binned.register_fake
+def _(trajs, paths, robot0, n_local, margin):
+    return trajs.new_empty((n_local, trajs.shape[0] // n_local), dtype=torch.int32)
+
+
+@torch.library.custom_op("mmd_amd::path_conflicts", mutates_args=(), device_types="cuda")
+def path_conflicts(paths: torch.Tensor, margin: float, list_cap: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The conflict report of the best paths [n_all, 64, 2] (mmd_bin_paths + mmd_path_conflicts_binned): (summary int32 [16]: word 0 the
+    count, words 4 .. 15 the first mmd_conflict record; robot_counts int32 [n_all]; list int32 [list_cap, 12], the first records)."""
+    from . import multi_agent
+    summ, robots, lst = multi_agent.path_conflicts(paths, margin, list_cap, _collision_table(paths, 0, paths.shape[0]))
+    return summ, robots, lst if lst is not None else paths.new_empty((0, 12), dtype=torch.int32)
+
+
+@path_conflicts.register_fake
+def _(paths, margin, list_cap):
+    return (paths.new_empty(16, dtype=torch.int32), paths.new_empty(paths.shape[0], dtype=torch.int32),
+            paths.new_empty((list_cap, 12), dtype=torch.int32))
