@@ -529,7 +529,7 @@ __global__ __launch_bounds__(256) void ddpm_guide_coop_kernel(GuideDev g, StepDe
 // acting fmas of the dense chain in the dense order.  Entries that do not act -- too far, the robot itself (one table serves every robot
 // of the GPU), the padding of a lane whose list has ended -- run cons_term with m = 0 and leave their accumulator's bits alone.  (p is
 // finite: the unnormaliser clips.  Time step 0 has empty lists where the dense table has R = -1.)
-// (bin_cell itself is in bins_dev.h: the collision kernels of multi_agent.hip walk the same lists.)
+// (bin_cell and the lookup of a point's own list, own_cell_list, are in bins_dev.h: the collision kernels of multi_agent.hip walk the same lists.)
 
 // the one constraint group a robot has under a cell table: no group tables to read, its weight is the table's
 struct OneGroup {
@@ -546,19 +546,16 @@ struct BinnedSum {
   int t, self;
   float r2, weight;
   __device__ __forceinline__ f32x2g operator()(const OneGroup&, int, f32x2g p) const {
-    const int cell = bin_cell(p.x, b.lo[0], b.inv_cell[0], b.nx) * b.ny + bin_cell(p.y, b.lo[1], b.inv_cell[1], b.ny);
-    const int* off = b.cell_off_dev + (size_t)t * (b.nx * b.ny + 1) + cell;
-    const int e0 = off[0], e1 = off[1];
-    const float4* ent = reinterpret_cast<const float4*>(b.entries_dev) + (size_t)t * 9 * b.n_all;
+    const CellList cl = own_cell_list(b, t, p.x, p.y);
     const float4 none = make_float4(0.f, 0.f, __builtin_bit_cast(float, self), 0.f);     // (carries the lane's own id: skipped)
     Acc4 acc = acc4_zero();
-    const int last = max(e1 - 1, 0);                                                     // (a lane past its list re-reads an entry of
-    for (int e = e0; __builtin_amdgcn_ballot_w64(e < e1) != 0; e += 4) {                 //  the segment and drops it: no branch, no stray read)
+    const int last = max(cl.e1 - 1, 0);                                                  // (a lane past its list re-reads an entry of
+    for (int e = cl.e0; __builtin_amdgcn_ballot_w64(e < cl.e1) != 0; e += 4) {           //  the segment and drops it: no branch, no stray read)
       float4 c[4];
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        const float4 l = ent[min(e + j, last)];
-        c[j] = e + j < e1 ? l : none;
+        const float4 l = cl.ent[min(e + j, last)];
+        c[j] = e + j < cl.e1 ? l : none;
       }
 #pragma unroll
       for (int j = 0; j < 4; ++j) {

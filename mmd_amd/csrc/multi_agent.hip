@@ -18,9 +18,10 @@
 #include <climits>
 
 #include "../../include/mmd_amd.h"
-#include "bins_dev.h"             // bin_cell / check_cons_bins: the cell table of guide.hip
+#include "bins_dev.h"             // own_cell_list / check_cons_bins: the cell table of guide.hip
 #include "collision_dev.h"        // torch_norm2 / rr_hit: the pinned fp32 form of the collision decision (sets fp contract(off))
 #include "common.h"
+#include "wave_dev.h"             // wave_sum / block_sum / block_prefix / block_prefix_count
 
 namespace mmd {
 
@@ -57,11 +58,9 @@ __global__ __launch_bounds__(256) void count_collisions_kernel(const float4* __r
     const float dx = p.x - q.x, dy = p.y - q.y;
     c += torch_norm2(dx, dy) < margin ? 1 : 0;
   }
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) c += __shfl_xor(c, m);
+  c = wave_sum(c);
   if (t == 0) counts[traj] = c;
 }
-
 
 // ---- search layer over mmd_agent_path tables ----------------------------------------------------------------------------------------
 __device__ __forceinline__ float2 sample_pos(const float* batch, int index, int length, int u) {
@@ -83,32 +82,35 @@ __device__ __forceinline__ bool cell_kept(int a, int b, int mode, int exclude) {
   return mode == MMD_CONFLICTS_PAIRS ? a < b : a != b;
 }
 
-// exclusive prefix of `flag` over a 256-thread block in thread order; returns the block total
-__device__ __forceinline__ int block_prefix(bool flag, int* lds4, int& prefix) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const unsigned long long bal = __ballot(flag);
-  const int in_wave = __popcll(bal & ((1ull << lane) - 1ull));
-  if (lane == 0) lds4[wave] = __popcll(bal);
-  __syncthreads();
-  int before = 0, total = 0;
-#pragma unroll
-  for (int w = 0; w < 4; ++w) {
-    before += w < wave ? lds4[w] : 0;
-    total += lds4[w];
+// what the two emit kernels do before they walk row t of `n_rows`: the number of records before the row (returned), and in the last row the
+// total and, when it is 0, the first record that says "none"
+__device__ __forceinline__ int records_before(const int* __restrict__ row_counts, int t, int n_rows, int* lds4, int* __restrict__ count,
+                                              mmd_conflict* __restrict__ first) {
+  int before = 0;
+  for (int k = threadIdx.x; k < t; k += 256) before += row_counts[k];
+  before = block_sum(before, lds4);
+  if (t == n_rows - 1 && threadIdx.x == 0) {
+    const int total = before + row_counts[t];
+    *count = total;
+    if (total == 0 && first) {
+      mmd_conflict none{};
+      none.t = none.a = none.b = -1;
+      *first = none;
+    }
   }
-  __syncthreads();
-  prefix = before + in_wave;
-  return total;
+  return before;
 }
 
-__device__ __forceinline__ int block_sum(int v, int* lds4) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-  if ((threadIdx.x & 63) == 0) lds4[threadIdx.x >> 6] = v;
-  __syncthreads();
-  const int s = lds4[0] + lds4[1] + lds4[2] + lds4[3];
-  __syncthreads();
-  return s;
+// record idx of the (t, a, b) list: robots a at pa and b at pb at time step t
+__device__ __forceinline__ void write_conflict(int idx, int t, int a, int b, float2 pa, float2 pb, mmd_conflict* __restrict__ first,
+                                               mmd_conflict* __restrict__ list, int list_cap) {
+  mmd_conflict r;
+  r.t = t; r.a = a; r.b = b; r.reserved = 0;
+  r.pa[0] = pa.x; r.pa[1] = pa.y; r.pb[0] = pb.x; r.pb[1] = pb.y;
+  r.mid[0] = (pa.x + pb.x) / 2.f; r.mid[1] = (pa.y + pb.y) / 2.f;
+  r.reserved2[0] = r.reserved2[1] = 0.f;
+  if (idx == 0 && first) *first = r;
+  if (list && idx < list_cap) list[idx] = r;
 }
 
 // one workgroup per global time step t: the number of conflicts in row t
@@ -132,18 +134,7 @@ __global__ __launch_bounds__(256) void conflict_emit_kernel(const mmd_agent_path
                                                              int list_cap) {
   __shared__ int lds4[4];
   const int t = blockIdx.x;
-  int before = 0;
-  for (int k = threadIdx.x; k < t; k += 256) before += row_counts[k];
-  before = block_sum(before, lds4);
-  if (t == Tg - 1 && threadIdx.x == 0) {
-    const int total = before + row_counts[t];
-    *count = total;
-    if (total == 0 && first) {
-      mmd_conflict none{};
-      none.t = none.a = none.b = -1;
-      *first = none;
-    }
-  }
+  const int before = records_before(row_counts, t, Tg, lds4, count, first);
   if (row_counts[t] == 0) return;
   const bool want_first = first && before == 0;
   const bool want_list = list && before < list_cap;
@@ -161,16 +152,7 @@ __global__ __launch_bounds__(256) void conflict_emit_kernel(const mmd_agent_path
     }
     int prefix;
     const int total = block_prefix(hit, lds4, prefix);
-    if (hit) {
-      const int idx = base + prefix;
-      mmd_conflict r;
-      r.t = t; r.a = a; r.b = b; r.reserved = 0;
-      r.pa[0] = pa.x; r.pa[1] = pa.y; r.pb[0] = pb.x; r.pb[1] = pb.y;
-      r.mid[0] = (pa.x + pb.x) / 2.f; r.mid[1] = (pa.y + pb.y) / 2.f;
-      r.reserved2[0] = r.reserved2[1] = 0.f;
-      if (idx == 0 && first) *first = r;
-      if (list && idx < list_cap) list[idx] = r;
-    }
+    if (hit) write_conflict(base + prefix, t, a, b, pa, pb, first, list, list_cap);
     base += total;
   }
 }
@@ -186,17 +168,6 @@ __global__ __launch_bounds__(256) void conflict_emit_kernel(const mmd_agent_path
 // A count is an integer: the order of a list does not matter to it, only that every hit is in the list exactly once (a robot has one
 // entry per time step and list) and that the robot's own entry is skipped by id.  The table must list time step 0 (mmd_bin_paths with
 // first_step = 0): the dense kernels count collisions there.
-
-// the list of the cell of p at time step t: entries [e0, e1) of `ent`
-struct CellList {
-  const float4* ent;
-  int e0, e1;
-};
-__device__ __forceinline__ CellList own_cell_list(const mmd_cons_bins& b, int t, float px, float py) {
-  const int cell = bin_cell(px, b.lo[0], b.inv_cell[0], b.nx) * b.ny + bin_cell(py, b.lo[1], b.inv_cell[1], b.ny);
-  const int* off = b.cell_off_dev + (size_t)t * (b.nx * b.ny + 1) + cell;
-  return CellList{reinterpret_cast<const float4*>(b.entries_dev) + (size_t)t * 9 * b.n_all, off[0], off[1]};
-}
 
 // count_collisions_kernel on the table: one wave per trajectory, lane = time step, four trajectories a workgroup, no LDS.  The wave
 // walks the lanes' lists four entries a trip -- the loads of a trip are issued together -- while any lane has entries left; a lane past
@@ -225,31 +196,8 @@ __global__ __launch_bounds__(256) void count_collisions_binned_kernel(const P* _
       c += other && rr_hit(p, make_float2(q[j].x, q[j].y), margin) ? 1 : 0;
     }
   }
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) c += __shfl_xor(c, m);
+  c = wave_sum(c);
   if (t == 0) counts[traj] = c;
-}
-
-// exclusive prefix of `v` over a 256-thread block in thread order; returns the block total
-__device__ __forceinline__ int block_prefix_count(int v, int* lds4, int& prefix) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int inc = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int o = __shfl_up(inc, d);
-    inc += lane >= d ? o : 0;
-  }
-  if (lane == 63) lds4[wave] = inc;
-  __syncthreads();
-  int before = 0, total = 0;
-#pragma unroll
-  for (int w = 0; w < 4; ++w) {
-    before += w < wave ? lds4[w] : 0;
-    total += lds4[w];
-  }
-  __syncthreads();
-  prefix = before + inc - v;
-  return total;
 }
 
 // the number of robots b > a that robot a (at pa, time step t) collides with: the entries of its own list above its id
@@ -285,18 +233,7 @@ __global__ __launch_bounds__(256) void path_conflict_emit_binned_kernel(const fl
                                                                          int list_cap) {
   __shared__ int lds4[4];
   const int t = blockIdx.x;
-  int before = 0;
-  for (int k = threadIdx.x; k < t; k += 256) before += row_counts[k];
-  before = block_sum(before, lds4);
-  if (t == H - 1 && threadIdx.x == 0) {
-    const int total = before + row_counts[t];
-    *count = total;
-    if (total == 0 && first) {
-      mmd_conflict none{};
-      none.t = none.a = none.b = -1;
-      *first = none;
-    }
-  }
+  const int before = records_before(row_counts, t, H, lds4, count, first);
   if (row_counts[t] == 0) return;
   const bool want_first = first && before == 0;
   if (!want_first && !(list && before < list_cap)) return;
@@ -320,14 +257,7 @@ __global__ __launch_bounds__(256) void path_conflict_emit_binned_kernel(const fl
       const int ob = __builtin_bit_cast(int, q.z);
       const float2 pb = make_float2(q.x, q.y);
       if (!(ob > a && rr_hit(pa, pb, margin))) continue;
-      mmd_conflict r;
-      r.t = t; r.a = a; r.b = ob; r.reserved = 0;
-      r.pa[0] = pa.x; r.pa[1] = pa.y; r.pb[0] = pb.x; r.pb[1] = pb.y;
-      r.mid[0] = (pa.x + pb.x) / 2.f; r.mid[1] = (pa.y + pb.y) / 2.f;
-      r.reserved2[0] = r.reserved2[1] = 0.f;
-      if (idx == 0 && first) *first = r;
-      if (list && idx < list_cap) list[idx] = r;
-      ++idx;
+      write_conflict(idx++, t, a, ob, pa, pb, first, list, list_cap);
       --mine;
     }
     base += total;
@@ -351,8 +281,7 @@ __global__ __launch_bounds__(256) void candidate_pairs_kernel(const mmd_agent_pa
     for (int j = 0; j < n; ++j)
       if (j != self) hits += rr_hit(p, agent_pos(agents[j], t), margin) ? 1 : 0;
   }
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) hits += __shfl_xor(hits, m);
+  hits = wave_sum(hits);
   if (lane == 0) pair_counts[c] = hits;
 }
 
@@ -459,6 +388,13 @@ int mmd_count_collisions(const float* trajs_dev, const float* paths_dev, int rob
   return 0;
 }
 
+// what the two report entry points require of the list: a capacity, and a pointer where it is positive; a list of 0 records is none
+static int check_conflict_list(const char* who, mmd_conflict*& list_dev, int list_cap) {
+  MMD_REQUIRE(list_cap >= 0 && (list_cap == 0 || list_dev), "%s: list_cap without a list", who);
+  if (list_cap == 0) list_dev = nullptr;
+  return 0;
+}
+
 // what the two collision entry points on a cell table share: the table's own checks, and margin <= radius (COVER above)
 static int check_collision_bins(const char* who, const mmd_cons_bins* bins, float margin) {
   MMD_REQUIRE(bins, "%s: NULL table", who);
@@ -485,13 +421,13 @@ int mmd_path_conflicts_binned(const float* paths_dev, const mmd_cons_bins* bins,
                               void* stream) {
   MMD_REQUIRE(paths_dev && row_counts_dev && count_dev, "mmd_path_conflicts_binned: NULL argument");
   MMD_REQUIRE(horizon == H, "mmd_path_conflicts_binned: horizon must be %d", H);
-  MMD_REQUIRE(list_cap >= 0 && (list_cap == 0 || list_dev), "mmd_path_conflicts_binned: list_cap without a list");
+  if (int rc = check_conflict_list("mmd_path_conflicts_binned", list_dev, list_cap)) return rc;
   if (int rc = check_collision_bins("mmd_path_conflicts_binned", bins, margin)) return rc;
   hipStream_t st = (hipStream_t)stream;
   const float2* paths = (const float2*)paths_dev;
   hipLaunchKernelGGL(path_conflict_rows_binned_kernel, dim3(H), dim3(256), 0, st, paths, *bins, margin, row_counts_dev);
   hipLaunchKernelGGL(path_conflict_emit_binned_kernel, dim3(H), dim3(256), 0, st, paths, *bins, margin, row_counts_dev, count_dev, first_dev,
-                     list_cap > 0 ? list_dev : nullptr, list_cap);
+                     list_dev, list_cap);
   if (robot_counts_dev)                                  // every robot's own path as a "sample" of one: each pair counts for both robots
     hipLaunchKernelGGL(count_collisions_binned_kernel<float2>, dim3((bins->n_all + 3) / 4), dim3(256), 0, st, paths, *bins, 0, 1,
                        bins->n_all, margin, robot_counts_dev);
@@ -504,12 +440,12 @@ int mmd_find_conflicts(const mmd_agent_path* agents_dev, int n_agents, int horiz
                        void* stream) {
   MMD_REQUIRE(agents_dev && row_counts_dev && count_dev && n_agents >= 1 && horizon_global >= 1, "mmd_find_conflicts: bad arguments");
   MMD_REQUIRE(mode == MMD_CONFLICTS_ORDERED || mode == MMD_CONFLICTS_PAIRS, "mmd_find_conflicts: unknown mode %d", mode);
-  MMD_REQUIRE(list_cap >= 0 && (list_cap == 0 || list_dev), "mmd_find_conflicts: list_cap without a list");
+  if (int rc = check_conflict_list("mmd_find_conflicts", list_dev, list_cap)) return rc;
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(conflict_rows_kernel, dim3(horizon_global), dim3(256), 0, st, agents_dev, n_agents, margin, mode, -1,
                      row_counts_dev);
   hipLaunchKernelGGL(conflict_emit_kernel, dim3(horizon_global), dim3(256), 0, st, agents_dev, n_agents, horizon_global, margin, mode,
-                     row_counts_dev, count_dev, first_dev, list_cap > 0 ? list_dev : nullptr, list_cap);
+                     row_counts_dev, count_dev, first_dev, list_dev, list_cap);
   MMD_HIP_CHECK(hipGetLastError());
   return 0;
 }

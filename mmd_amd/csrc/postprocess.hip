@@ -24,6 +24,7 @@
 #pragma clang fp contract(off)
 
 #include "guide_dev.h"
+#include "wave_dev.h"             // wave_sum
 
 namespace mmd {
 
@@ -78,11 +79,6 @@ __device__ __forceinline__ bool point_collides(const EnvDev& e, const float4* __
 
 __device__ __forceinline__ float lane_next_f(float v) {   // lane t reads lane t + 1 (wave_shl:1)
   return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x130, 0xf, 0xf, true));
-}
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-  return v;
 }
 
 struct PostArgs {
@@ -185,8 +181,7 @@ __global__ __launch_bounds__(64) void select_best_kernel(const unsigned char* __
   for (int b = lane; b < B; b += 64) nf += free_mask[(size_t)r * B + b] ? 1 : 0;
   if (summary)                                                // the host's one transfer: free flags as floats, then the picks
     for (int b = lane; b < B; b += 64) summary[(size_t)r * B + b] = free_mask[(size_t)r * B + b] ? 1.f : 0.f;
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) nf += __shfl_xor(nf, m);
+  nf = wave_sum(nf);
   float best = INFINITY;
   int best_i = 0x7fffffff;
   for (int b = lane; b < B; b += 64) {

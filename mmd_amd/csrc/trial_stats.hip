@@ -12,14 +12,9 @@
 #include "../../include/mmd_amd.h"
 #include "collision_dev.h"        // torch_norm2 / rr_hit; sets fp contract(off): every fp32 operation below is the one written out
 #include "common.h"
+#include "wave_dev.h"             // wave_sum (fixed order: a float sum does not depend on scheduling) / block_sum
 
 namespace mmd {
-
-__device__ __forceinline__ float wave_sum(float v) {          // fixed order: the result does not depend on scheduling
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-  return v;
-}
 
 // first set bit of `mask` strictly above bit `prev` (prev = -1: any bit), or 64
 __device__ __forceinline__ int first_above(unsigned long long mask, int prev) {
@@ -149,14 +144,8 @@ __global__ __launch_bounds__(256) void pair_collisions_kernel(const float4* __re
       c += rr_hit(make_float2(a.x, a.y), make_float2(b.x, b.y), dist) ? 1 : 0;
     }
   }
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) c += __shfl_xor(c, m);
-  if ((threadIdx.x & 63) == 0) lds4[threadIdx.x >> 6] = c;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const int s = lds4[0] + lds4[1] + lds4[2] + lds4[3];
-    if (s) atomicAdd(count, s);
-  }
+  c = block_sum<true>(c, lds4);                               // (the last use of lds4: no barrier behind the read)
+  if (threadIdx.x == 0 && c) atomicAdd(count, c);
 }
 
 }  // namespace mmd

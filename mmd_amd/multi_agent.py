@@ -24,15 +24,19 @@ def check_rr_collisions(paths, margin=RR_MARGIN, with_midpoints=True):
     return mask.bool(), mid
 
 
+def _count_launch(name, trajs, n_local, before, after):
+    """An entry point (trajs, *before, n_local, B, *after, counts) on trajs [n_local * B, H, 4] -> its counts, int32 [n_local, B]."""
+    B = trajs.shape[0] // n_local
+    counts = torch.empty(n_local * B, dtype=torch.int32, device=trajs.device)
+    _lib.launch(name, trajs, _lib.require_gpu(trajs.contiguous(), "trajs"), *before, n_local, B, *after, counts.data_ptr())
+    return counts.view(n_local, B)
+
+
 def count_collisions(trajs, paths_all, robot0, n_local, margin=RR_MARGIN):
     """trajs [n_local*B,H,4] un-normalised sample batches of the local robots, paths_all [N,H,2] best paths of all
     robots -> int32 [n_local, B] number of (t, other robot) collision pairs per sample."""
-    B = trajs.shape[0] // n_local
-    counts = torch.empty(n_local * B, dtype=torch.int32, device=trajs.device)
-    _lib.launch("mmd_count_collisions", trajs, _lib.require_gpu(trajs.contiguous(), "trajs"),
-                                                _lib.require_gpu(paths_all.contiguous(), "paths_all"), robot0, n_local,
-                                                B, paths_all.shape[0], H, float(margin), counts.data_ptr())
-    return counts.view(n_local, B)
+    return _count_launch("mmd_count_collisions", trajs, n_local, (_lib.require_gpu(paths_all.contiguous(), "paths_all"), robot0),
+                         (paths_all.shape[0], H, float(margin)))
 
 
 def _collision_table(table, what):
@@ -46,11 +50,7 @@ def count_collisions_binned(trajs, table, n_local, margin=RR_MARGIN):
     """count_collisions on a cell table of the best paths (constraints.binned_collision_table(paths_all, robot0, n_local)) instead of
     the paths: a sample point meets only the robots near its cell.  -> int32 [n_local, B], the same integers."""
     _collision_table(table, "count_collisions_binned")
-    B = trajs.shape[0] // n_local
-    counts = torch.empty(n_local * B, dtype=torch.int32, device=trajs.device)
-    _lib.launch("mmd_count_collisions_binned", trajs, _lib.require_gpu(trajs.contiguous(), "trajs"), C.byref(table.struct), n_local, B,
-                float(margin), counts.data_ptr())
-    return counts.view(n_local, B)
+    return _count_launch("mmd_count_collisions_binned", trajs, n_local, (C.byref(table.struct),), (float(margin),))
 
 
 def least_collision_samples(trajs, paths_all, robot0, n_local):
@@ -82,14 +82,20 @@ def agent_table(batches, indices, starts, device=None):
     return torch.frombuffer(bytearray(arr), dtype=torch.uint8).to(dev)
 
 
+def _new_report(device, list_cap):
+    """A report for an entry point to fill: (summary int32 [16], list [list_cap, 12] words or None, the entry point's four arguments
+    for them: count, first record, list, list_cap)."""
+    summ = torch.empty(16, dtype=torch.int32, device=device)
+    lst = torch.empty((list_cap, _CONFLICT_WORDS), dtype=torch.int32, device=device) if list_cap > 0 else None
+    return summ, lst, (summ.data_ptr(), summ.data_ptr() + 16, lst.data_ptr() if lst is not None else None, int(list_cap))
+
+
 def find_conflicts(table, n, Tg, mode, list_cap=0, margin=RR_MARGIN):
     """mmd_find_conflicts -> (summary int32 [1 + 3 + 12] on the device: [0] = count, [4:16] = the first mmd_conflict record,
     list [list_cap, 12] words or None).  Read the summary with `read_summary` (one device -> host copy)."""
-    summ = torch.empty(16, dtype=torch.int32, device=table.device)
+    summ, lst, report_args = _new_report(table.device, list_cap)
     rows = torch.empty(max(int(Tg), 1), dtype=torch.int32, device=table.device)
-    lst = torch.empty((list_cap, _CONFLICT_WORDS), dtype=torch.int32, device=table.device) if list_cap > 0 else None
-    _lib.launch("mmd_find_conflicts", table, table.data_ptr(), int(n), int(Tg), float(margin), int(mode), rows.data_ptr(),
-                summ.data_ptr(), summ.data_ptr() + 16, lst.data_ptr() if lst is not None else None, int(list_cap))
+    _lib.launch("mmd_find_conflicts", table, table.data_ptr(), int(n), int(Tg), float(margin), int(mode), rows.data_ptr(), *report_args)
     return summ, lst
 
 
@@ -101,11 +107,11 @@ def path_conflicts(paths_all, margin=RR_MARGIN, list_cap=0, table=None, row_coun
     row_counts: an optional int32 [64] device tensor that receives the count per time step.  No N^2 buffer, no host synchronisation."""
     paths_all = paths_all.contiguous()
     if paths_all.shape[0] < 2 and table is None:               # one robot: nothing to collide with (and no table of fewer than two)
-        summ = torch.zeros(16, dtype=torch.int32, device=paths_all.device)
+        summ, lst, _ = _new_report(paths_all.device, list_cap)
+        summ.zero_()
         summ[4:7] = -1
         if row_counts is not None:
             row_counts.zero_()
-        lst = torch.empty((list_cap, _CONFLICT_WORDS), dtype=torch.int32, device=paths_all.device) if list_cap > 0 else None
         return summ, torch.zeros(paths_all.shape[0], dtype=torch.int32, device=paths_all.device), lst
     if table is None:
         from .constraints import binned_collision_table
@@ -115,15 +121,13 @@ def path_conflicts(paths_all, margin=RR_MARGIN, list_cap=0, table=None, row_coun
     if table.n_all != n or paths_all.shape[1] != H:
         raise ValueError(f"path_conflicts: paths {tuple(paths_all.shape)} and a table of {table.n_all} robots")
     dev = paths_all.device
-    summ = torch.empty(16, dtype=torch.int32, device=dev)
+    summ, lst, report_args = _new_report(dev, list_cap)
     rows = torch.empty(H, dtype=torch.int32, device=dev) if row_counts is None else row_counts
     if not (rows.is_cuda and rows.dtype == torch.int32 and rows.is_contiguous() and rows.numel() == H):
         raise ValueError(f"path_conflicts: row_counts must be a contiguous int32 device tensor of {H} words")
     robots = torch.empty(n, dtype=torch.int32, device=dev)
-    lst = torch.empty((list_cap, _CONFLICT_WORDS), dtype=torch.int32, device=dev) if list_cap > 0 else None
     _lib.launch("mmd_path_conflicts_binned", paths_all, _lib.require_gpu(paths_all, "paths_all"), C.byref(table.struct), H, float(margin),
-                rows.data_ptr(), robots.data_ptr(), summ.data_ptr(), summ.data_ptr() + 16, lst.data_ptr() if lst is not None else None,
-                int(list_cap))
+                rows.data_ptr(), robots.data_ptr(), *report_args)
     return summ, robots, lst
 
 

@@ -41,10 +41,11 @@ def _get(token, what):
     return obj
 
 
-def _check_traj(x, name="x"):
+def _check_traj(x, name="x", rows="n_traj", width=4):
+    """x [rows, 64, width]: trajectories [n_traj, 64, 4] or, for _check_traj(paths, "paths", "n_all", 2), best paths [n_all, 64, 2]"""
     if not (x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.ndim == 3 and x.shape[1] == 64
-            and x.shape[2] == 4):
-        raise RuntimeError(f"mmd_amd op: {name} must be a contiguous float32 CUDA(HIP) tensor [n_traj, 64, 4]")
+            and x.shape[2] == width):
+        raise RuntimeError(f"mmd_amd op: {name} must be a contiguous float32 CUDA(HIP) tensor [{rows}, 64, {width}]")
 
 
 # ---- unet_forward --------------------------------------------------------------------------------------------------
@@ -170,9 +171,7 @@ def bin_constraints_from_paths(paths: torch.Tensor, radius: float, lo_x: float, 
     """The cell-binned inter-robot constraint table of the best paths [n_all, 64, 2] (mmd_bin_constraints_from_paths; include/mmd_amd.h:
     mmd_cons_bins): (cell_off int32 [64, nx ny + 1], entries float32 [64, 9 n_all, 4] of (qx, qy, bit pattern of the robot id, 0))."""
     from . import constraints
-    if not (paths.is_cuda and paths.dtype == torch.float32 and paths.is_contiguous() and paths.ndim == 3 and paths.shape[1] == 64
-            and paths.shape[2] == 2):
-        raise RuntimeError("mmd_amd op: paths must be a contiguous float32 CUDA(HIP) tensor [n_all, 64, 2]")
+    _check_traj(paths, "paths", "n_all", 2)
     return constraints.bin_constraints_table(paths, radius, ((lo_x, lo_y), (hi_x, hi_y)), (nx, ny))
 
 
@@ -184,9 +183,7 @@ def _(paths, radius, lo_x, lo_y, hi_x, hi_y, nx, ny):
 # ---- count_collisions_binned / path_conflicts ----------------------------------------------------------------------
 def _collision_table(paths, robot0, n_local):
     from . import constraints
-    if not (paths.is_cuda and paths.dtype == torch.float32 and paths.is_contiguous() and paths.ndim == 3 and paths.shape[1] == 64
-            and paths.shape[2] == 2):
-        raise RuntimeError("mmd_amd op: paths must be a contiguous float32 CUDA(HIP) tensor [n_all, 64, 2]")
+    _check_traj(paths, "paths", "n_all", 2)
     return constraints.binned_collision_table(paths, robot0, n_local)
 
 

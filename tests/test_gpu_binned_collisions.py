@@ -164,8 +164,12 @@ def test_binned_counts_at_the_margin_and_outside_the_limits():
 
 
 # ---- 3. the conflict report ----------------------------------------------------------------------------------------------------------
+PAST = 4                                                                          # rows behind a list's capacity that must stay untouched
+
+
 def _dense_report(paths, cap):
-    """mmd_find_conflicts(PAIRS) on an agent table of the same paths, start_time 0, length 64: (summary [16], rows [H], list [cap, 12])"""
+    """mmd_find_conflicts(PAIRS) on an agent table of the same paths, start_time 0, length 64, into buffers filled with SENTINEL:
+    (summary [16], rows [H], list [cap + PAST, 12])"""
     from mmd_amd import _lib, multi_agent as ma
     n = paths.shape[0]
     p4 = torch.zeros((n, 1, H, 4), dtype=torch.float32, device="cuda")
@@ -173,10 +177,33 @@ def _dense_report(paths, cap):
     table = ma.agent_table([p4[k] for k in range(n)], [0] * n, [0] * n)
     summ = torch.full((16,), SENTINEL, dtype=torch.int32, device="cuda")
     rows = torch.empty(H, dtype=torch.int32, device="cuda")
-    lst = torch.full((max(cap, 1), 12), SENTINEL, dtype=torch.int32, device="cuda")
+    lst = torch.full((cap + PAST, 12), SENTINEL, dtype=torch.int32, device="cuda")
     _lib.launch("mmd_find_conflicts", table, table.data_ptr(), n, H, float(F.MARGIN), ma.PAIRS, rows.data_ptr(), summ.data_ptr(),
                 summ.data_ptr() + 16, lst.data_ptr() if cap else None, cap)
-    return summ.cpu().numpy(), rows.cpu().numpy(), lst.cpu().numpy()[:cap]
+    return summ.cpu().numpy(), rows.cpu().numpy(), lst.cpu().numpy()
+
+
+def _binned_report(paths, cap):
+    """mmd_path_conflicts_binned on a table of the paths, into buffers filled with SENTINEL: (summary [16], rows [H], robots [N],
+    list [cap + PAST, 12])"""
+    from mmd_amd import _lib
+    tab = binned_collision_table(paths)
+    summ = torch.full((16,), SENTINEL, dtype=torch.int32, device="cuda")
+    rows = torch.empty(H, dtype=torch.int32, device="cuda")
+    robots = torch.empty(paths.shape[0], dtype=torch.int32, device="cuda")
+    lst = torch.full((cap + PAST, 12), SENTINEL, dtype=torch.int32, device="cuda")
+    _lib.launch("mmd_path_conflicts_binned", paths, paths.data_ptr(), C.byref(tab.struct), H, float(F.MARGIN), rows.data_ptr(),
+                robots.data_ptr(), summ.data_ptr(), summ.data_ptr() + 16, lst.data_ptr(), cap)
+    return summ.cpu().numpy(), rows.cpu().numpy(), robots.cpu().numpy(), lst.cpu().numpy()
+
+
+def _check_words(summ, lst, count, cap):
+    """a report written over SENTINEL: the reserved words of every written record (words 3, 10, 11: reserved, reserved2[0..1]) are 0, of
+    the summary's first record too when there is one, and no row behind the last record was touched"""
+    k = min(count, cap)
+    assert lst.shape[0] > k and (lst[:k][:, [3, 10, 11]] == 0).all() and (lst[k:] == SENTINEL).all()
+    if count > 0:
+        assert (summ[4:16][[3, 10, 11]] == 0).all()
 
 
 def _check_report(paths_np, cap=None, want_count=None):
@@ -192,7 +219,12 @@ def _check_report(paths_np, cap=None, want_count=None):
     summ, robots, lst = ma.path_conflicts(paths, list_cap=cap, row_counts=rows)
     s, r, l = summ.cpu().numpy(), rows.cpu().numpy(), lst.cpu().numpy()
     ds, dr, dl = _dense_report(paths, cap)
+    bs, br, brob, bl = _binned_report(paths, cap)                                 # the same call as path_conflicts', over SENTINEL
     k = min(m, cap)
+    assert np.array_equal(bs[[0] + list(range(4, 16))], s[[0] + list(range(4, 16))]) and np.array_equal(br, r)
+    assert np.array_equal(brob, robots.cpu().numpy()) and np.array_equal(bl[:k], l[:k])
+    _check_words(ds, dl, m, cap)
+    _check_words(bs, bl, m, cap)
     print(f"n = {paths_np.shape[0]}: {m} pairs, {int(dr[0])} at t = 0, list of {k}")
     assert s[0] == ds[0] == m
     assert np.array_equal(s[4:16], ds[4:16])                                      # the first record (t = a = b = -1 when there is none)
@@ -226,20 +258,17 @@ def test_path_conflicts_truncated_list_of_300_robots():
     paths_np = _circle(300)[2]
     paths = torch.from_numpy(paths_np).cuda()
     cap = 1000
-    tab = binned_collision_table(paths)
-    summ = torch.full((16,), SENTINEL, dtype=torch.int32, device="cuda")
-    rows = torch.empty(H, dtype=torch.int32, device="cuda")
-    robots = torch.empty(300, dtype=torch.int32, device="cuda")
-    lst = torch.full((cap + 4, 12), SENTINEL, dtype=torch.int32, device="cuda")
-    _lib.launch("mmd_path_conflicts_binned", paths, paths.data_ptr(), C.byref(tab.struct), H, float(F.MARGIN), rows.data_ptr(),
-                robots.data_ptr(), summ.data_ptr(), summ.data_ptr() + 16, lst.data_ptr(), cap)
+    s, r, robots, l = _binned_report(paths, cap)
     ds, dr, dl = _dense_report(paths, cap)
-    s, l = summ.cpu().numpy(), lst.cpu().numpy()
-    assert s[0] == ds[0] == 806400 and np.array_equal(s[4:16], ds[4:16]) and np.array_equal(rows.cpu().numpy(), dr)
-    assert np.array_equal(l[:cap], dl) and (l[cap:] == SENTINEL).all()
+    assert s[0] == ds[0] == 806400 and np.array_equal(s[4:16], ds[4:16]) and np.array_equal(r, dr)
+    assert np.array_equal(l[:cap], dl[:cap])
+    _check_words(ds, dl, 806400, cap)                                             # (and nothing behind record 1000, on both sides)
+    _check_words(s, l, 806400, cap)
     hits = _hits(paths_np)
-    assert np.array_equal(robots.cpu().numpy(), hits.sum((0, 2))) and int(hits.sum()) == 2 * 806400
+    assert np.array_equal(robots, hits.sum((0, 2))) and int(hits.sum()) == 2 * 806400
     # without a list and without per-robot counts
+    tab = binned_collision_table(paths)
+    rows = torch.empty(H, dtype=torch.int32, device="cuda")
     summ2 = torch.full((16,), SENTINEL, dtype=torch.int32, device="cuda")
     _lib.launch("mmd_path_conflicts_binned", paths, paths.data_ptr(), C.byref(tab.struct), H, float(F.MARGIN), rows.data_ptr(), None,
                 summ2.data_ptr(), summ2.data_ptr() + 16, None, 0)
