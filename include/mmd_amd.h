@@ -449,6 +449,40 @@ int mmd_path_constraints(const mmd_agent_path* agents_dev, int n_state, int agen
                          int horizon, float radius, float weight, int n_slots, float* ell_out_dev, int32_t* grp_slot_off_dev,
                          float* grp_weight_dev, int32_t* robot_grp_off_dev, void* stream);
 
+/* ---- the round table: conflict-driven hard constraints next to the soft all-pairs group, for many-robot rounds -----------------
+ * A dense constraint table in the layout mmd_guide_desc reads, for the local robots [robot0, robot0 + n_local) of n_all.  With
+ * S_h = hard_slots (the caller's cap) and S = S_h + n_all - 1, local robot r owns the slots [r S, (r + 1) S) and two groups, hard
+ * first (the order CBS passes them in, cbs.py:407-413):
+ *   group 2 r     = slots [r S, r S + S_h), weight_hard: the points of the robot's conflicts (convert_conflicts_to_constraints,
+ *                   mmd/common/conflict_conversion.py:41-55, weight_grad_cost_constraints = 2e-1);
+ *   group 2 r + 1 = slots [r S + S_h, (r + 1) S), weight_soft: the words mmd_soft_constraints_from_paths writes for the robot.
+ * ell_dev [n_local S][H][4], grp_slot_off_dev [2 n_local + 1], grp_weight_dev [2 n_local], robot_grp_off_dev [n_local + 1] (= 2 r),
+ * max_slots_per_robot = S; fill_dev int32 [n_local][H] (the hard slots in use per time step) and dropped_dev int32 [n_local] belong to
+ * the table and persist between calls.  No offset depends on data: no sizing pass, no host synchronisation, one launch each.
+ * horizon = H.  NULL pointers, hard_slots < 1, a robot range outside [0, n_all) or n_all < 2 are error returns before any launch.
+ *
+ * mmd_round_constraints_init: offsets and weights, every hard slot inactive ((0, 0, -1, -1), as mmd_pack_constraints leaves an unused
+ * slot), fill and dropped zeroed.  The soft blocks are not written. */
+int mmd_round_constraints_init(int n_all, int n_local, int horizon, int hard_slots, float weight_hard, float weight_soft, float* ell_dev,
+                               int32_t* grp_slot_off_dev, float* grp_weight_dev, int32_t* robot_grp_off_dev, int32_t* fill_dev,
+                               int32_t* dropped_dev, void* stream);
+
+/* The soft blocks of a round from the best paths paths_dev [n_all, H, 2]: slot j of robot r's block = the j-th other robot in ascending
+ * id, every time step t >= 1 active with `radius`, t = 0 inactive -- bit for bit mmd_soft_constraints_from_paths' block of that robot. */
+int mmd_round_soft_from_paths(const float* paths_dev, int n_all, int robot0, int n_local, int horizon, int hard_slots, float radius,
+                              float* ell_dev, void* stream);
+
+/* Appends the hard points of the conflicts of paths_dev [n_all, H, 2] (n_all = bins->n_all, local robots from bins->robot0) to the hard
+ * blocks, read off the round's collision cell table `bins` (mmd_bin_paths of the same paths, first_step = 0).  Every record (tc, a, b,
+ * mid) of mmd_path_conflicts_binned's report gives both a and b the point (mid.x, mid.y, radius, radius |radius|) -- the report's bits
+ * -- with range (tc - t_pad, tc + t_pad), i.e. active at the time steps tc - t_pad <= t < tc + t_pad of [0, H).  The slots are
+ * mmd_pack_constraints' for the list of the robot's records in report order, behind the lists of earlier calls: a point's slot at t is
+ * fill[r][t] when it arrives, which it then increments (CBS accumulates constraints down a branch the same way).  A point whose slot
+ * would reach hard_slots is not written and counts into dropped_dev[r]; everything before it in order is kept.  The collision test is
+ * mmd_rr_collisions'.  t_pad < 1, margin > bins->radius, or a table mmd_count_collisions_binned would refuse are error returns. */
+int mmd_conflict_constraints_append(const float* paths_dev, const mmd_cons_bins* bins, int n_local, int horizon, int hard_slots, int t_pad,
+                                    float margin, float radius, float* ell_dev, int32_t* fill_dev, int32_t* dropped_dev, void* stream);
+
 /* ------------------------------------------------------------------------------------------------------------
  * The statistics of a returned solution (scripts/inference/inference_multi_agent.py:285-342, run_multi_agent_trial)
  * ---------------------------------------------------------------------------------------------------------- */

@@ -150,6 +150,11 @@ _SIGNATURES = {
                                       C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mmd_path_constraints": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float,
                                        C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mmd_round_constraints_init": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mmd_round_soft_from_paths": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p]),
+    "mmd_conflict_constraints_append": (C.c_int, [C.c_void_p, C.POINTER(ConsBins), C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float,
+                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mmd_solution_stats": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mmd_postprocess_trajs": (C.c_int, [C.POINTER(GuideDesc), C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                         C.POINTER(C.c_float), C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int,

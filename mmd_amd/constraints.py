@@ -8,6 +8,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .multi_agent import RR_MARGIN
 
 VERTEX_CONSTRAINT_RADIUS = 0.05 * 2.4        # mmd/config/mmd_params.py:52
 H = 64
@@ -289,3 +290,68 @@ def binned_collision_table(paths: torch.Tensor, robot0: int = 0, n_local: int = 
     robots from robot0 on.  The weight field is not read by those kernels."""
     n_local = paths.shape[0] - int(robot0) if n_local is None else n_local
     return binned_constraints_from_paths(paths, robot0, n_local, radius=reach, weight=0.0, limits=limits, grid=grid, first_step=0)
+
+
+class RoundConstraints:
+    """The round table of a many-robot round on the device (include/mmd_amd.h: mmd_round_constraints_init): per local robot a hard group
+    of up to `hard_slots` points per time step -- the midpoints of the conflicts seen so far, as CBS gives both agents of a conflict a
+    hard constraint (convert_conflicts_to_constraints, mmd/common/conflict_conversion.py:41-55) -- in front of the soft all-pairs group
+    of soft_constraints_from_paths.  Owns the tensors; `fill` int32 [n_local, H] (hard slots in use per time step) and `dropped` int32
+    [n_local] (points that found the hard block full) stay on the device.  Every call is launches on the current stream, no host
+    synchronisation.  reset() -> set_soft(paths) / append_conflicts(paths, table) per round -> tensors() for
+    GuideManagerTrajectoriesWithVelocity.set_packed_constraints."""
+
+    def __init__(self, n_all, robot0, n_local, hard_slots=32, radius=VERTEX_CONSTRAINT_RADIUS, w_hard=2e-1, w_soft=2e-2,
+                 hard_radius=None, device="cuda"):
+        self.n_all, self.robot0, self.n_local, self.hard_slots = int(n_all), int(robot0), int(n_local), int(hard_slots)
+        if not (self.n_all >= 2 and self.n_local >= 1 and self.robot0 >= 0 and self.robot0 + self.n_local <= self.n_all):
+            raise ValueError("RoundConstraints: bad robot range")
+        if self.hard_slots < 1:
+            raise ValueError(f"RoundConstraints: hard_slots must be at least 1, got {hard_slots}")
+        self.radius = float(radius)
+        self.hard_radius = self.radius if hard_radius is None else float(hard_radius)
+        self.w_hard, self.w_soft = float(w_hard), float(w_soft)
+        self.slots_per_robot = self.hard_slots + self.n_all - 1
+        dev = torch.device(device)
+        self.ell = torch.empty((self.n_local * self.slots_per_robot, H, 4), dtype=torch.float32, device=dev)
+        self.gso = torch.empty(2 * self.n_local + 1, dtype=torch.int32, device=dev)
+        self.gw = torch.empty(2 * self.n_local, dtype=torch.float32, device=dev)
+        self.rgo = torch.empty(self.n_local + 1, dtype=torch.int32, device=dev)
+        self.fill = torch.empty((self.n_local, H), dtype=torch.int32, device=dev)
+        self.dropped = torch.empty(self.n_local, dtype=torch.int32, device=dev)
+        self.reset()
+
+    def reset(self):
+        """Offsets and weights, an empty hard block for every robot, fill and dropped zeroed.  The soft blocks are set_soft's."""
+        _lib.launch("mmd_round_constraints_init", self.ell, self.n_all, self.n_local, H, self.hard_slots, self.w_hard, self.w_soft,
+                    self.ell.data_ptr(), self.gso.data_ptr(), self.gw.data_ptr(), self.rgo.data_ptr(), self.fill.data_ptr(),
+                    self.dropped.data_ptr())
+
+    def _paths(self, paths_all, what):
+        if paths_all.dim() != 3 or tuple(paths_all.shape) != (self.n_all, H, 2):
+            raise ValueError(f"RoundConstraints.{what}: paths [{self.n_all}, {H}, 2], got {tuple(paths_all.shape)}")
+        return _lib.require_gpu(paths_all.contiguous(), "paths_all")
+
+    def set_soft(self, paths_all):
+        """The soft blocks from the best paths [N, H, 2] of all robots: soft_constraints_from_paths' rows of the local robots."""
+        _lib.launch("mmd_round_soft_from_paths", self.ell, self._paths(paths_all, "set_soft"), self.n_all, self.robot0, self.n_local, H,
+                    self.hard_slots, self.radius, self.ell.data_ptr())
+
+    def append_conflicts(self, paths_all, collision_table, margin=RR_MARGIN, t_pad=2):
+        """Append the hard points of the conflicts of paths_all [N, H, 2], read off their collision cell table
+        (binned_collision_table(paths_all, robot0, n_local)): every record (tc, a, b, mid) of multi_agent.path_conflicts gives a and b the
+        point mid with range (tc - t_pad, tc + t_pad), in report order behind the earlier calls' points."""
+        tb = collision_table
+        if getattr(tb, "first_step", None) != 0:
+            raise ValueError("RoundConstraints.append_conflicts: a collision table lists time step 0 (binned_collision_table)")
+        if (tb.n_all, tb.robot0) != (self.n_all, self.robot0) or tb.n_local < self.n_local:
+            raise ValueError(f"RoundConstraints.append_conflicts: a table of robots [{tb.robot0}, {tb.robot0 + tb.n_local}) of {tb.n_all}")
+        _lib.launch("mmd_conflict_constraints_append", self.ell, self._paths(paths_all, "append_conflicts"), C.byref(tb.struct),
+                    self.n_local, H, self.hard_slots, int(t_pad), float(margin), self.hard_radius, self.ell.data_ptr(),
+                    self.fill.data_ptr(), self.dropped.data_ptr())
+
+    def tensors(self):
+        """(ell, grp_slot_off, grp_weight, robot_grp_off, uniform_radius) for set_packed_constraints.  uniform_radius: the one radius of
+        every active point when the hard and the soft radius are equal (the reference: both vertex_constraint_radius), else 0.0, the
+        guided step's general path."""
+        return self.ell, self.gso, self.gw, self.rgo, self.radius if self.hard_radius == self.radius else 0.0

@@ -12,7 +12,10 @@
 //     without the padded tensors);
 //   * the same pick and the conflict report of a round's best paths on a CELL table of those paths (include/mmd_amd.h: mmd_cons_bins,
 //     built by mmd_bin_paths with first_step = 0): a point meets only the robots in the list of its own cell, so a round of N robots
-//     costs O(N x list length) where the kernels above walk all N (or all N^2 pairs).
+//     costs O(N x list length) where the kernels above walk all N (or all N^2 pairs);
+//   * the round table of a many-robot round that repairs its conflicts: per local robot the hard points of the conflicts seen so far
+//     (convert_conflicts_to_constraints, mmd/common/conflict_conversion.py:41-55; CBS passes them in front of the soft group,
+//     cbs.py:407-413), appended round after round from the same cell table, and behind them the soft all-pairs group.
 #include <hip/hip_runtime.h>
 
 #include <climits>
@@ -357,6 +360,88 @@ __global__ void path_constraints_kernel(const mmd_agent_path* __restrict__ agent
   for (; fill < n_slots; ++fill) ell[(size_t)fill * horizon + t] = make_float4(0.f, 0.f, -1.f, -1.f);
 }
 
+// ---- the round table of a many-robot round: per local robot a hard group (conflict points), then the soft all-pairs group ------------
+//
+// Local robot r owns S = S_h + n_all - 1 slots from r S on: [r S, r S + S_h) is group 2 r (hard), the rest group 2 r + 1 (soft).  The
+// offsets depend on no data, so the three kernels below need no sizing pass and no synchronisation between them.
+
+// offsets, weights, every hard slot inactive, fill and dropped zeroed
+__global__ void round_init_kernel(int n_local, int S_h, int S, float w_hard, float w_soft, float4* __restrict__ ell,
+                                  int* __restrict__ grp_slot_off, float* __restrict__ grp_weight, int* __restrict__ robot_grp_off,
+                                  int* __restrict__ fill, int* __restrict__ dropped) {
+  const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, step = (size_t)gridDim.x * blockDim.x;
+  const size_t per = (size_t)S_h * H;
+  for (size_t idx = tid; idx < (size_t)n_local * per; idx += step) {
+    const size_t r = idx / per;
+    ell[r * S * H + (idx - r * per)] = make_float4(0.f, 0.f, -1.f, -1.f);
+  }
+  for (size_t idx = tid; idx < (size_t)n_local * H; idx += step) fill[idx] = 0;
+  for (size_t r = tid; r <= (size_t)n_local; r += step) {
+    robot_grp_off[r] = 2 * (int)r;
+    grp_slot_off[2 * r] = (int)r * S;
+    if (r == (size_t)n_local) break;
+    grp_slot_off[2 * r + 1] = (int)r * S + S_h;
+    grp_weight[2 * r] = w_hard;
+    grp_weight[2 * r + 1] = w_soft;
+    dropped[r] = 0;
+  }
+}
+
+// the soft block of every local robot: the words soft_cons_kernel (guide.hip) writes for that robot, behind its hard block
+__global__ void round_soft_kernel(const float2* __restrict__ paths, int n_all, int robot0, int n_local, int S_h, float radius,
+                                  float4* __restrict__ ell) {
+  const int slots = n_all - 1, S = S_h + slots;
+  const size_t tot = (size_t)n_local * slots * H;
+  for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < tot; idx += (size_t)gridDim.x * blockDim.x) {
+    const int t = idx % H;
+    const int j = (idx / H) % slots;
+    const int i = idx / ((size_t)H * slots);
+    const int other = j + (j >= robot0 + i ? 1 : 0);
+    const float2 p = paths[(size_t)other * H + t];
+    const float r = t >= 1 ? radius : -1.f;                               // constraints cover t in [1, H-1]
+    ell[((size_t)i * S + S_h + j) * H + t] = make_float4(p.x, p.y, r, r * fabsf(r));
+  }
+}
+
+// The hard points of a round's conflicts (convert_conflicts_to_constraints, mmd/common/conflict_conversion.py:41-55: both agents of a
+// conflict at tc get the midpoint with range (tc - t_pad, tc + t_pad)), appended behind what earlier rounds left.  One wave per local
+// robot, lane = time step t, four robots a workgroup, no atomics, no LDS.  mmd_pack_constraints' rule -- a point's slot at t is the
+// number of earlier points of the list active at t -- needs no list here: the robot's records in report order are tc ascending, then
+// the other robot ascending (a record (tc, a, b) has a < b: the partners below the robot's id come first), a list of the cell table is
+// in ascending id (COVER above: every partner is in the list of the robot's own cell), and the points active at t are those of
+// tc in [t - t_pad + 1, t + t_pad].  So lane t walks exactly its own points in list order and counts its own slots.  The midpoint is
+// write_conflict's expression (the sum commutes: the same bits whichever robot of the pair the lane serves).  A point past slot
+// S_h - 1 is dropped and counted; the lane's fill stays at S_h, so everything later is dropped too and what was written is a prefix.
+__global__ __launch_bounds__(256) void conflict_constraints_kernel(const float2* __restrict__ paths, mmd_cons_bins b, int n_local, int S_h,
+                                                                    int S, int t_pad, float margin, float radius, float4* __restrict__ ell,
+                                                                    int* __restrict__ fill, int* __restrict__ dropped) {
+  const int t = threadIdx.x & 63;
+  const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= n_local) return;
+  const int a = b.robot0 + r;
+  float4* const col = ell + (size_t)r * S * H + t;                        // the robot's hard block, column t
+  const float r2 = radius * fabsf(radius);
+  int f = fill[(size_t)r * H + t], drop = 0;
+  const int tc1 = min(t + t_pad, H - 1);
+  for (int tc = max(t - t_pad + 1, 0); tc <= tc1; ++tc) {
+    const float2 pa = paths[(size_t)a * H + tc];
+    const CellList l = own_cell_list(b, tc, pa.x, pa.y);
+    for (int e = l.e0; e < l.e1; ++e) {
+      const float4 q = l.ent[e];
+      if (__builtin_bit_cast(int, q.z) == a || !rr_hit(pa, make_float2(q.x, q.y), margin)) continue;
+      if (f < S_h) {
+        col[(size_t)f * H] = make_float4((pa.x + q.x) / 2.f, (pa.y + q.y) / 2.f, radius, r2);
+        ++f;
+      } else {
+        ++drop;
+      }
+    }
+  }
+  fill[(size_t)r * H + t] = f;
+  drop = wave_sum(drop);
+  if (t == 0) dropped[r] += drop;
+}
+
 }  // namespace mmd
 
 using namespace mmd;
@@ -484,6 +569,56 @@ int mmd_path_constraints(const mmd_agent_path* agents_dev, int n_state, int agen
     hipLaunchKernelGGL(path_constraints_kernel, dim3(1), dim3(H), 0, (hipStream_t)stream, agents_dev, n_state, agent, agent_start_time,
                        agent_last_t, hard, H, radius, weight, n_slots, (float4*)ell_out_dev, offsets ? grp_slot_off_dev : nullptr,
                        grp_weight_dev, robot_grp_off_dev);
+  MMD_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+// what the three round-table entry points require of the shape: the guided step indexes the table's (slot, t) words with an int
+static int check_round_table(const char* who, int n_all, int robot0, int n_local, int horizon, int hard_slots) {
+  MMD_REQUIRE(horizon == H, "%s: horizon must be %d", who, H);
+  MMD_REQUIRE(hard_slots >= 1, "%s: hard_slots must be at least 1, got %d", who, hard_slots);
+  MMD_REQUIRE(n_all >= 2 && n_local >= 1 && robot0 >= 0 && robot0 < n_all && n_local <= n_all - robot0, "%s: bad robot range", who);
+  MMD_REQUIRE((long long)n_local * ((long long)hard_slots + n_all - 1) * H <= INT_MAX, "%s: a table of more than 2^31 - 1 points", who);
+  return 0;
+}
+
+static int grid_for(size_t items) {
+  const size_t g = (items + 255) / 256;
+  return g > 2048 ? 2048 : (g < 1 ? 1 : (int)g);
+}
+
+int mmd_round_constraints_init(int n_all, int n_local, int horizon, int hard_slots, float weight_hard, float weight_soft, float* ell_dev,
+                               int32_t* grp_slot_off_dev, float* grp_weight_dev, int32_t* robot_grp_off_dev, int32_t* fill_dev,
+                               int32_t* dropped_dev, void* stream) {
+  MMD_REQUIRE(ell_dev && grp_slot_off_dev && grp_weight_dev && robot_grp_off_dev && fill_dev && dropped_dev,
+              "mmd_round_constraints_init: NULL argument");
+  if (int rc = check_round_table("mmd_round_constraints_init", n_all, 0, n_local, horizon, hard_slots)) return rc;
+  hipLaunchKernelGGL(round_init_kernel, dim3(grid_for((size_t)n_local * hard_slots * H)), dim3(256), 0, (hipStream_t)stream, n_local,
+                     hard_slots, hard_slots + n_all - 1, weight_hard, weight_soft, (float4*)ell_dev, grp_slot_off_dev, grp_weight_dev,
+                     robot_grp_off_dev, fill_dev, dropped_dev);
+  MMD_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+int mmd_round_soft_from_paths(const float* paths_dev, int n_all, int robot0, int n_local, int horizon, int hard_slots, float radius,
+                              float* ell_dev, void* stream) {
+  MMD_REQUIRE(paths_dev && ell_dev, "mmd_round_soft_from_paths: NULL argument");
+  if (int rc = check_round_table("mmd_round_soft_from_paths", n_all, robot0, n_local, horizon, hard_slots)) return rc;
+  hipLaunchKernelGGL(round_soft_kernel, dim3(grid_for((size_t)n_local * (n_all - 1) * H)), dim3(256), 0, (hipStream_t)stream,
+                     (const float2*)paths_dev, n_all, robot0, n_local, hard_slots, radius, (float4*)ell_dev);
+  MMD_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+int mmd_conflict_constraints_append(const float* paths_dev, const mmd_cons_bins* bins, int n_local, int horizon, int hard_slots, int t_pad,
+                                    float margin, float radius, float* ell_dev, int32_t* fill_dev, int32_t* dropped_dev, void* stream) {
+  MMD_REQUIRE(paths_dev && ell_dev && fill_dev && dropped_dev, "mmd_conflict_constraints_append: NULL argument");
+  MMD_REQUIRE(t_pad >= 1, "mmd_conflict_constraints_append: t_pad must be at least 1, got %d", t_pad);
+  if (int rc = check_collision_bins("mmd_conflict_constraints_append", bins, margin)) return rc;
+  if (int rc = check_round_table("mmd_conflict_constraints_append", bins->n_all, bins->robot0, n_local, horizon, hard_slots)) return rc;
+  hipLaunchKernelGGL(conflict_constraints_kernel, dim3((n_local + 3) / 4), dim3(256), 0, (hipStream_t)stream, (const float2*)paths_dev,
+                     *bins, n_local, hard_slots, hard_slots + bins->n_all - 1, t_pad < H ? t_pad : H, margin, radius, (float4*)ell_dev,
+                     fill_dev, dropped_dev);
   MMD_HIP_CHECK(hipGetLastError());
   return 0;
 }

@@ -313,7 +313,9 @@ class GaussianDiffusionModel:
         if n_noising_steps is None:
             noised = None
         else:
-            noised = self.q_sample(seed_trajectory_b, n_noising_steps, noise=q_noise, seed=diffusion_kwargs.get("seed"))
+            # (a rank that samples robots [r0, r1) of a bigger instance noises its rows with the unsharded call's draws)
+            noised = self.q_sample(seed_trajectory_b, n_noising_steps, noise=q_noise, seed=diffusion_kwargs.get("seed"),
+                                   traj_index_base=diffusion_kwargs.get("traj_index_base", 0))
         samples, chain = self.conditional_sample(copy(hard_conds), n_diffusion_steps=n_denoising_steps, context=context,
                                                  batch_size=n_samples * n_robots, return_chain=True,
                                                  warm_start_path_b=noised, n_robots=n_robots, **diffusion_kwargs)

@@ -9,7 +9,10 @@ its robots' soft-constraint table on device (mmd_soft_constraints_from_paths: N 
 constraint_table="binned", mmd_bin_constraints_from_paths: per time step and map cell the robots near the cell -- O(N) work and
 memory per round instead of O(N^2), the same bits).  With the cell table the rest of the round is O(N) too: the best-path pick counts
 on a cell table of the gathered paths (mmd_count_collisions_binned), and MultiRobotSampler.plan -- rounds until the paths stop
-colliding -- reads a device-side conflict report of them (mmd_path_conflicts_binned) at the start of every round.
+colliding -- reads a device-side conflict report of them (mmd_path_conflicts_binned) at the start of every round.  plan_rounds(repair=True)
+also acts on the report: every conflict becomes a hard constraint point of both its robots (constraints.RoundConstraints, built on the
+device from the round's collision table), kept over the rounds of the call in front of the soft group, as CBS does down a branch;
+plan_rounds(local_rounds=True) re-plans from the previous round's samples with a few noising and denoising steps instead of from noise.
 """
 from dataclasses import dataclass
 from math import ceil
@@ -17,7 +20,8 @@ from math import ceil
 import torch
 
 from . import synth
-from .constraints import VERTEX_CONSTRAINT_RADIUS, binned_collision_table, binned_constraints_from_paths, soft_constraints_from_paths
+from .constraints import (VERTEX_CONSTRAINT_RADIUS, RoundConstraints, binned_collision_table, binned_constraints_from_paths,
+                          soft_constraints_from_paths)
 from .diffusion_model import ddpm_sample_fn
 from .guides import GuideManagerTrajectoriesWithVelocity
 from .normalization import TrajectoryDatasetFacade
@@ -58,7 +62,7 @@ def all_gather_paths(paths_local, world_size, group=None, force_collective=False
 
 @dataclass
 class PlanResult:
-    """What MultiRobotSampler.plan returns."""
+    """What MultiRobotSampler.plan / plan_rounds return."""
     paths_local: torch.Tensor        # [n_local, H, 2] un-normalised best paths of this rank's robots
     trajs: torch.Tensor              # [n_local * B, H, D] normalised samples of the last round run (None: no round was run)
     n_rounds: int                    # sampling rounds run
@@ -66,6 +70,7 @@ class PlanResult:
     robot_counts: torch.Tensor       # int32 [N] on the device: (t, other robot) collisions of every robot, of the returned paths
     conflict_free: bool              # conflict_counts[-1] == 0
     first_conflict: tuple            # (t, a, b, pa, pb, mid) of the returned paths' first conflict, or None
+    dropped_constraints: torch.Tensor = None   # plan_rounds(repair=True): int32 [n_local] on the device, hard points that found their block full
 
 
 class MultiRobotSampler:
@@ -104,6 +109,7 @@ class MultiRobotSampler:
         # plan_round then needs no exchange step either
         self.inter_robot = inter_robot
         self._collision = None          # "binned": (paths_all, its collision table), kept from set_other_paths for best_paths
+        self.round_constraints = None   # plan_rounds(repair=True): the call's constraints.RoundConstraints
 
     def _collision_table(self, paths_all):
         """The collision cell table of paths_all (every time step listed): built once per round, by set_other_paths or by the first
@@ -139,19 +145,31 @@ class MultiRobotSampler:
             n_diffusion_steps_without_noise=self.n_extra, warm_start_path_b=x_init, step_noise=step_noise, seed=seed,
             traj_index_base=self.robot0 * self.n_samples, device=self.device, n_streams=self.n_streams)
 
+    def sample_local(self, prev_trajs, n_noising_steps=3, n_denoising_steps=3, seed=None):
+        """A local re-plan round (the X-variants of CBS, cbs.py:424-430, mpd.py:460-517): forward-noise the previous round's normalised
+        samples prev_trajs [n_local*B, H, D] n_noising_steps, then n_denoising_steps guided steps (+ the steps without noise) instead
+        of the whole loop from noise.  Both draws are keyed by (seed, global trajectory index), as in `sample`."""
+        return self.model.run_local_inference(
+            prev_trajs, n_noising_steps, n_denoising_steps, None, self.hard_conds, n_samples=self.n_samples, n_robots=self.n_local,
+            horizon=H, sample_fn=ddpm_sample_fn, guide=self.guide, n_guide_steps=self.n_guide_steps,
+            t_start_guide=self.t_start_guide, noise_std_extra_schedule_fn=lambda t: 0.5,
+            n_diffusion_steps_without_noise=self.n_extra, seed=seed, traj_index_base=self.robot0 * self.n_samples, device=self.device,
+            n_streams=self.n_streams)
+
     def unnormalize(self, trajs_normalized):
         nz = self.dataset.normalizer
         mins, maxs = nz.mins.to(trajs_normalized.device), nz.maxs.to(trajs_normalized.device)
         return (torch.clip(trajs_normalized, -1, 1) + 1) / 2.0 * (maxs - mins) + mins
 
-    def best_paths(self, trajs_normalized, paths_all=None):
+    def best_paths(self, trajs_normalized, paths_all=None, collision_table=None):
         """Selection for the exchange step, on the device: samples that collide with the map or leave the joint limits
         are dropped first (PlanningTask.get_trajs_collision_and_free, tasks.py:236-311, as MPD.__call__ does at
         mpd.py:357-382); among the free ones the pick is the first sample with the fewest robot-robot collisions against
         the other robots' current best paths (CBS 'least_collisions', cbs.py:446-458; with constraint_table="binned" counted on a cell
         table of paths_all, the same counts), or the cheapest one (path length +
         smoothness, mpd.py:366-370) when no paths are known yet.  A robot without any free sample falls back to the same
-        criterion over all its samples (`self.last_n_free` tells).  Returns un-normalised positions [n_local,H,2]."""
+        criterion over all its samples (`self.last_n_free` tells).  collision_table: a collision cell table of paths_all the caller
+        already has (plan_rounds(repair=True)): the counts are read from it.  Returns un-normalised positions [n_local,H,2]."""
         from . import postprocess as post
         t = self.unnormalize(trajs_normalized).contiguous()
         r = post.postprocess_batch(self.guide, t, n_robots=self.n_local, smooth=False)
@@ -159,7 +177,9 @@ class MultiRobotSampler:
             idx, n_free = post.select_best(r.free_mask, self.n_local, cost_a=r.path_length, cost_b=r.smoothness)
         else:
             from .multi_agent import count_collisions, count_collisions_binned
-            if self.constraint_table == "binned":       # the same integers from the cell lists instead of all N robots
+            if collision_table is not None:
+                counts = count_collisions_binned(t, collision_table, self.n_local)
+            elif self.constraint_table == "binned":     # the same integers from the cell lists instead of all N robots
                 counts = count_collisions_binned(t, self._collision_table(paths_all), self.n_local)
             else:
                 counts = count_collisions(t, paths_all, self.robot0, self.n_local)
@@ -183,25 +203,55 @@ class MultiRobotSampler:
         conflict_free, robot_counts and first_conflict describe what is returned.  Every rank computes the same report from the same
         gathered paths, so the ranks stop together without another collective.  paths_local defaults to this rank's straight lines
         start -> goal.  list_cap > 0 also keeps the first records of the final report (`self.last_conflict_list`, [list_cap, 12] words).
-        -> PlanResult."""
+        plan_rounds is the same loop with the opt-in ways to act on the report.  -> PlanResult."""
+        return self.plan_rounds(paths_local, max_rounds, seed, list_cap)
+
+    def plan_rounds(self, paths_local=None, max_rounds=8, seed=0, list_cap=0, repair=False, hard_slots=32,
+                    weight_grad_cost_constraints=2e-1, t_pad=2, local_rounds=False, n_noising_steps=3, n_denoising_steps=3):
+        """plan()'s loop -- with repair and local_rounds off, exactly plan() -- and two independent ways to act on the report.
+
+        repair=True (convert_conflicts_to_constraints, mmd/common/conflict_conversion.py:41-55; cbs.py:407-413): the round's collision
+        cell table is built once and serves the report, the pick and the hard points -- every record (t, a, b, mid) gives a and b the
+        point mid, the constraint radius, range (t - t_pad, t + t_pad), in a hard group of weight weight_grad_cost_constraints and at
+        most hard_slots points per time step, in front of the soft group.  The hard group accumulates over the rounds of this call
+        (`self.round_constraints`; PlanResult.dropped_constraints counts the points that found it full).  It needs the dense table with
+        the inter-robot term: constraint_table="binned" or inter_robot=False raise.
+        local_rounds=True: rounds k >= 1 re-plan from round k - 1's samples (sample_local: n_noising_steps forward, n_denoising_steps
+        back) instead of from noise.  -> PlanResult."""
         from .multi_agent import path_conflicts, read_summary
+        if repair and (self.constraint_table == "binned" or not self.inter_robot):
+            raise ValueError("plan_rounds(repair=True) needs constraint_table='dense' and inter_robot=True: the library takes hard groups only in "
+                             "the dense table, not next to a cell table")
         if paths_local is None:
             import numpy as np
             st, go = (np.asarray(torch.as_tensor(v).cpu().numpy(), dtype=np.float32) for v in self._ends)
             paths_local = torch.from_numpy(synth.straight_line_paths(st, go, H)).to(self.device)
+        rc = None
+        if repair and self.n_robots >= 2:
+            rc = self.round_constraints = RoundConstraints(self.n_robots, self.robot0, self.n_local, hard_slots, self.radius,
+                                                           weight_grad_cost_constraints, self.w_soft, device=self.device)
         trajs, counts, k = None, [], 0
         while True:
             paths_all = all_gather_paths(paths_local, self.world_size, self.group).contiguous()
             last = k == max_rounds
-            summ, robots, lst = path_conflicts(paths_all, list_cap=list_cap)
+            table = self._collision_table(paths_all) if rc is not None else None       # one table a round: report, hard points, pick
+            summ, robots, lst = path_conflicts(paths_all, list_cap=list_cap, table=table)
             count, first = read_summary(summ)
             counts.append(count)
             if last or (k > 0 and count == 0):
                 break
             others = paths_all if self.inter_robot else None
-            self.set_other_paths(others)
-            trajs = self.sample(seed=seed + k)
-            paths_local = self.best_paths(trajs, others)
+            if rc is not None:
+                rc.append_conflicts(paths_all, table, t_pad=t_pad)
+                rc.set_soft(paths_all)
+                self.guide.set_packed_constraints(rc.tensors())
+            else:
+                self.set_other_paths(others)
+            if local_rounds and k > 0:
+                trajs = self.sample_local(trajs, n_noising_steps, n_denoising_steps, seed=seed + k)
+            else:
+                trajs = self.sample(seed=seed + k)
+            paths_local = self.best_paths(trajs, others, collision_table=table)
             k += 1
         self.last_conflict_list = lst
-        return PlanResult(paths_local, trajs, k, counts, robots, count == 0, first)
+        return PlanResult(paths_local, trajs, k, counts, robots, count == 0, first, rc.dropped if rc is not None else None)

@@ -1,5 +1,6 @@
 """PyTorch-ROCm custom ops over the C ABI (include/mmd_amd.h): `torch.ops.mmd_amd.{unet_forward, guide_steps,
-p_sample_loop, ddim_sample, solution_stats, bin_constraints_from_paths, count_collisions_binned, path_conflicts}`.  They take tensors instead of raw pointers, run on torch's CURRENT HIP stream
+p_sample_loop, ddim_sample, solution_stats, bin_constraints_from_paths, count_collisions_binned, path_conflicts,
+round_constraints_init, round_soft_from_paths, conflict_constraints_append}`.  They take tensors instead of raw pointers, run on torch's CURRENT HIP stream
 without any host synchronisation (so they can be captured into a hipGraph with torch.cuda.graph) and register fake
 (meta) implementations so that torch.compile / FakeTensor tracing sees their output shapes.  The C header stays the ABI
 of record: every op is a thin wrapper over the same entry point the host mirror classes call through ctypes.
@@ -215,3 +216,63 @@ def path_conflicts(paths: torch.Tensor, margin: float, list_cap: int) -> Tuple[t
 def _(paths, margin, list_cap):
     return (paths.new_empty(16, dtype=torch.int32), paths.new_empty(paths.shape[0], dtype=torch.int32),
             paths.new_empty((list_cap, 12), dtype=torch.int32))
+
+
+# ---- the round table: round_constraints_init / round_soft_from_paths / conflict_constraints_append -------------------------------
+def _check_round(ell, n_all, n_local, hard_slots):
+    S = int(hard_slots) + int(n_all) - 1
+    if not (ell.is_cuda and ell.dtype == torch.float32 and ell.is_contiguous() and tuple(ell.shape) == (int(n_local) * S, 64, 4)):
+        raise RuntimeError(f"mmd_amd op: ell must be a contiguous float32 CUDA(HIP) tensor [{int(n_local) * S}, 64, 4]")
+
+
+def _check_words(t, name, shape):
+    if not (t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and tuple(t.shape) == tuple(shape)):
+        raise RuntimeError(f"mmd_amd op: {name} must be a contiguous int32 CUDA(HIP) tensor {list(shape)}")
+
+
+@torch.library.custom_op("mmd_amd::round_constraints_init", mutates_args=(), device_types="cuda")
+def round_constraints_init(like: torch.Tensor, n_all: int, n_local: int, hard_slots: int, weight_hard: float,
+                           weight_soft: float) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """A fresh round table on the device of `like` (mmd_round_constraints_init): (ell float32 [n_local S, 64, 4] with S = hard_slots +
+    n_all - 1 -- the hard blocks inactive, the soft blocks unwritten --, grp_slot_off int32 [2 n_local + 1], grp_weight float32
+    [2 n_local], robot_grp_off int32 [n_local + 1], fill int32 [n_local, 64] = 0, dropped int32 [n_local] = 0)."""
+    S = int(hard_slots) + int(n_all) - 1
+    ell = like.new_empty((max(n_local, 0) * max(S, 0), 64, 4), dtype=torch.float32)
+    gso = like.new_empty(2 * n_local + 1, dtype=torch.int32)
+    gw = like.new_empty(2 * n_local, dtype=torch.float32)
+    rgo = like.new_empty(n_local + 1, dtype=torch.int32)
+    fill = like.new_empty((n_local, 64), dtype=torch.int32)
+    dropped = like.new_empty(n_local, dtype=torch.int32)
+    _lib.launch("mmd_round_constraints_init", like, int(n_all), int(n_local), 64, int(hard_slots), float(weight_hard), float(weight_soft),
+                ell.data_ptr(), gso.data_ptr(), gw.data_ptr(), rgo.data_ptr(), fill.data_ptr(), dropped.data_ptr())
+    return ell, gso, gw, rgo, fill, dropped
+
+
+@round_constraints_init.register_fake
+def _(like, n_all, n_local, hard_slots, weight_hard, weight_soft):
+    S = hard_slots + n_all - 1
+    return (like.new_empty((n_local * S, 64, 4), dtype=torch.float32), like.new_empty(2 * n_local + 1, dtype=torch.int32),
+            like.new_empty(2 * n_local, dtype=torch.float32), like.new_empty(n_local + 1, dtype=torch.int32),
+            like.new_empty((n_local, 64), dtype=torch.int32), like.new_empty(n_local, dtype=torch.int32))
+
+
+@torch.library.custom_op("mmd_amd::round_soft_from_paths", mutates_args=("ell",), device_types="cuda")
+def round_soft_from_paths(ell: torch.Tensor, paths: torch.Tensor, robot0: int, n_local: int, hard_slots: int, radius: float) -> None:
+    """In place: the soft blocks of the round table `ell` from the best paths [n_all, 64, 2] (mmd_round_soft_from_paths)."""
+    _check_traj(paths, "paths", "n_all", 2)
+    _check_round(ell, paths.shape[0], n_local, hard_slots)
+    _lib.launch("mmd_round_soft_from_paths", ell, paths.data_ptr(), paths.shape[0], int(robot0), int(n_local), 64, int(hard_slots),
+                float(radius), ell.data_ptr())
+
+
+@torch.library.custom_op("mmd_amd::conflict_constraints_append", mutates_args=("ell", "fill", "dropped"), device_types="cuda")
+def conflict_constraints_append(ell: torch.Tensor, fill: torch.Tensor, dropped: torch.Tensor, paths: torch.Tensor, robot0: int,
+                                n_local: int, hard_slots: int, t_pad: int, margin: float, radius: float) -> None:
+    """In place: the hard points of the conflicts of the best paths [n_all, 64, 2] appended to the round table (mmd_bin_paths +
+    mmd_conflict_constraints_append; the collision cell table of the paths is built here)."""
+    table = _collision_table(paths, robot0, n_local)
+    _check_round(ell, paths.shape[0], n_local, hard_slots)
+    _check_words(fill, "fill", (n_local, 64))
+    _check_words(dropped, "dropped", (n_local,))
+    _lib.launch("mmd_conflict_constraints_append", ell, paths.data_ptr(), C.byref(table.struct), int(n_local), 64, int(hard_slots),
+                int(t_pad), float(margin), float(radius), ell.data_ptr(), fill.data_ptr(), dropped.data_ptr())
