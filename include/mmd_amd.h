@@ -483,6 +483,34 @@ int mmd_round_soft_from_paths(const float* paths_dev, int n_all, int robot0, int
 int mmd_conflict_constraints_append(const float* paths_dev, const mmd_cons_bins* bins, int n_local, int horizon, int hard_slots, int t_pad,
                                     float margin, float radius, float* ell_dev, int32_t* fill_dev, int32_t* dropped_dev, void* stream);
 
+/* ---- which robots a round re-plans -----------------------------------------------------------------------------------------------
+ * A round that re-samples every robot moves every path at once: each robot is guided away from paths that no longer hold.  A robot that
+ * keeps its path is a constraint that stays true, so a round may re-plan a SUBSET: `selected_dev` int32 [n_all], 0 / 1, from the conflicts
+ * of paths_dev [n_all, H, 2] (n_all = bins->n_all), read off the round's collision cell table `bins` (mmd_bin_paths of the same paths,
+ * first_step = 0) and robot_counts_dev [n_all], mmd_path_conflicts_binned's per-robot counts of these paths.  Robots r != j are
+ * neighbours iff ||p_r(t) - p_j(t)|| < margin at some t (mmd_rr_collisions' test, symmetric in the two robots). */
+#define MMD_REPLAN_CONFLICTED 0  /* selected[r] = counts[r] > 0: every robot of a conflict.  iters is ignored */
+#define MMD_REPLAN_INDEPENDENT 1 /* an independent set of the conflict graph, by iters >= 1 Jacobi iterations of priority propagation:
+                                  * r beats j iff counts[r] > counts[j], or the counts are equal and r < j.  A robot starts OUT if its
+                                  * count is 0, else UNDECIDED; an iteration reads the old states and writes the new ones: an UNDECIDED
+                                  * robot becomes OUT if a neighbour is IN, else IN if every neighbour that beats it is OUT, else stays.
+                                  * selected = IN after the last iteration.  For every iters: no two selected robots are neighbours (every
+                                  * re-planned robot's neighbours keep their paths), and a robot is selected whenever there is a conflict.
+                                  * iters = 1 selects the strict local maxima of the priority; the limit is the lexicographically first
+                                  * maximal independent set */
+/* perm_dev int32 [n_all]: the stable partition of 0 .. n_all - 1, the selected ids ascending, then the others ascending.  The instance
+ * paths[perm] has the selected robots as a prefix, and since a rank owns a block of ascending ids, its selected robots are the block
+ * [header[1], header[1] + header[2]) of that prefix: a subset round of the rank is an ordinary round of the permuted instance with
+ * robot0 = header[1], n_local = header[2] (mmd_soft_constraints_from_paths / mmd_bin_constraints_from_paths, the sampler with
+ * traj_index_base = header[1] * B, mmd_count_collisions), with the rows that round gives those robots.
+ * header_dev int32 [4] = (robots selected, of them below bins->robot0, of them in the shard [bins->robot0, bins->robot0 + n_local),
+ * robots left UNDECIDED: 0 in mode CONFLICTED).  state_dev int32 [2][n_all]: scratch.  iters + 1 launches in mode INDEPENDENT, 2 in
+ * mode CONFLICTED, no atomics, no host synchronisation.  NULL pointers, an unknown mode, iters < 1 in mode INDEPENDENT, margin >
+ * bins->radius, a shard outside [0, n_all), or a table mmd_count_collisions_binned would refuse are error returns before any launch. */
+int mmd_round_select(const float* paths_dev, const mmd_cons_bins* bins, const int32_t* robot_counts_dev, int n_local, int horizon,
+                     float margin, int mode, int iters, int32_t* state_dev, int32_t* selected_dev, int32_t* perm_dev, int32_t* header_dev,
+                     void* stream);
+
 /* ------------------------------------------------------------------------------------------------------------
  * The statistics of a returned solution (scripts/inference/inference_multi_agent.py:285-342, run_multi_agent_trial)
  * ---------------------------------------------------------------------------------------------------------- */

@@ -100,6 +100,7 @@ class TileRef(C.Structure):
 ADHERENCE_LINE, ADHERENCE_HIGHWAYS, ADHERENCE_CONVEYOR, ADHERENCE_DROP_REGION = 0, 1, 2, 3      # MMD_ADHERENCE_*
 CONFLICTS_ORDERED, CONFLICTS_PAIRS = 0, 1               # MMD_CONFLICTS_*
 SELECT_CBS, SELECT_PP = 0, 1                            # MMD_SELECT_*
+REPLAN_CONFLICTED, REPLAN_INDEPENDENT = 0, 1            # MMD_REPLAN_*
 
 
 _SIGNATURES = {
@@ -155,6 +156,8 @@ _SIGNATURES = {
     "mmd_round_soft_from_paths": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p]),
     "mmd_conflict_constraints_append": (C.c_int, [C.c_void_p, C.POINTER(ConsBins), C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float,
                                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mmd_round_select": (C.c_int, [C.c_void_p, C.POINTER(ConsBins), C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_void_p,
+                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mmd_solution_stats": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mmd_postprocess_trajs": (C.c_int, [C.POINTER(GuideDesc), C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                         C.POINTER(C.c_float), C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int,

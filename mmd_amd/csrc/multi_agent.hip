@@ -15,7 +15,10 @@
 //     costs O(N x list length) where the kernels above walk all N (or all N^2 pairs);
 //   * the round table of a many-robot round that repairs its conflicts: per local robot the hard points of the conflicts seen so far
 //     (convert_conflicts_to_constraints, mmd/common/conflict_conversion.py:41-55; CBS passes them in front of the soft group,
-//     cbs.py:407-413), appended round after round from the same cell table, and behind them the soft all-pairs group.
+//     cbs.py:407-413), appended round after round from the same cell table, and behind them the soft all-pairs group;
+//   * which robots a round re-plans (mmd_round_select): the robots in conflict, or an independent set of the conflict graph found by
+//     priority propagation on the same cell table -- CBS re-plans one agent of a conflict against the others' fixed paths (cbs.py:316-324);
+//     a round does that for every robot of the set at once -- and the stable partition that makes the selected robots a prefix.
 #include <hip/hip_runtime.h>
 
 #include <climits>
@@ -442,6 +445,113 @@ __global__ __launch_bounds__(256) void conflict_constraints_kernel(const float2*
   if (t == 0) dropped[r] += drop;
 }
 
+// ---- which robots a round re-plans: the robots in conflict, or an independent set of the conflict graph -----------------------------
+//
+// The conflict graph: robots r != j are neighbours iff rr_hit(p_r(t), p_j(t), margin) at some t in [0, H).  rr_hit is symmetric in its two
+// points (dx and dy change sign, dx * dx and dy * dy do not), so the graph is undirected: whatever robot r's wave sees of j, j's wave sees
+// of r.  COVER above applies to the walk (margin <= bins->radius is enforced): a robot's neighbours at t are all in the list of its own cell
+// at t.  A robot with a neighbour has a count above 0, its neighbour too.  Priority is a total order: r beats j iff counts[r] > counts[j],
+// or the counts are equal and r < j.
+//
+// Every robot has a state; at the start OUT if its count is 0, else UNDECIDED.  One Jacobi iteration reads only the old array and writes
+// the new one: an UNDECIDED r becomes OUT if a neighbour is IN, else IN if every neighbour that beats it is OUT, else it stays.  IN and
+// OUT are final.  For every number of iterations:
+//   INDEPENDENT -- no two neighbours are IN.  Say neighbours r and j both are, and r beats j.  If they turned IN in the same iteration, j
+//     needed r OUT in the old array, where r was UNDECIDED.  If j turned later, r was IN in the old array and j became OUT; if r turned
+//     later, j (a neighbour, whether it beats r or not) was IN in the old array and r became OUT.
+//   NON-EMPTY -- where there is a conflict, the robot that beats every other robot of a count above 0 has no neighbour that beats it:
+//     the first iteration makes it IN (nothing is IN before), and it stays.
+//   NEIGHBOURS STAY -- every neighbour of a selected robot is not selected: that is INDEPENDENT read from one robot.  So a re-planned robot
+//     is guided against neighbours that keep their paths this round.
+// Iteration 1 selects the strict local maxima of the priority; the limit is the lexicographically first maximal independent set in
+// priority order.
+#define MMD_SEL_UNDECIDED 0
+#define MMD_SEL_IN 1
+#define MMD_SEL_OUT 2
+
+// MMD_REPLAN_CONFLICTED as a state array: IN where the count is above 0, else OUT
+__global__ void round_select_conflicted_kernel(const int* __restrict__ counts, int n_all, int* __restrict__ state) {
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r < n_all) state[r] = counts[r] > 0 ? MMD_SEL_IN : MMD_SEL_OUT;
+}
+
+// One iteration, in the shape of count_collisions_binned_kernel<float2>: one wave per robot, lane = time step, four robots a workgroup,
+// the lane's own cell list four entries a trip, no LDS, no atomics.  `old_state` NULL: the first iteration, whose old array is the
+// start state, read off the counts.  A robot that is decided copies its state without a walk (uniform over the wave).  The two
+// predicates of the rule are reduced over the wave's lanes with one ballot each.
+__global__ __launch_bounds__(256) void round_select_iter_kernel(const float2* __restrict__ paths, mmd_cons_bins b, float margin,
+                                                                const int* __restrict__ counts, const int* __restrict__ old_state,
+                                                                int* __restrict__ new_state) {
+  const int t = threadIdx.x & 63;
+  const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= b.n_all) return;
+  const int mine = counts[r];
+  const int st = old_state ? old_state[r] : (mine == 0 ? MMD_SEL_OUT : MMD_SEL_UNDECIDED);
+  if (st != MMD_SEL_UNDECIDED) {
+    if (t == 0) new_state[r] = st;
+    return;
+  }
+  const float2 p = paths[(size_t)r * H + t];
+  const CellList l = own_cell_list(b, t, p.x, p.y);
+  const int last = max(l.e1 - 1, 0);
+  bool near_in = false, held = false;                       // a neighbour is IN; a neighbour that beats r is not OUT
+  for (int e = l.e0; __builtin_amdgcn_ballot_w64(e < l.e1) != 0; e += 4) {
+    float4 q[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) q[j] = l.ent[min(e + j, last)];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int o = __builtin_bit_cast(int, q[j].z);
+      if (!(e + j < l.e1 && o != r && rr_hit(p, make_float2(q[j].x, q[j].y), margin))) continue;
+      const int oc = counts[o];
+      const int os = old_state ? old_state[o] : MMD_SEL_UNDECIDED;      // (a neighbour has a count above 0)
+      near_in |= os == MMD_SEL_IN;
+      held |= os != MMD_SEL_OUT && (oc > mine || (oc == mine && o < r));
+    }
+  }
+  const bool any_in = __builtin_amdgcn_ballot_w64(near_in) != 0;
+  const bool any_held = __builtin_amdgcn_ballot_w64(held) != 0;
+  if (t == 0) new_state[r] = any_in ? MMD_SEL_OUT : (any_held ? MMD_SEL_UNDECIDED : MMD_SEL_IN);
+}
+
+// selected, the stable partition and the header from the final states: one workgroup, the robots in chunks of 256 in ascending id, no
+// atomics.  A first pass counts; in the second the block's prefix places a selected robot behind the selected robots below it and any
+// other robot behind all n_sel selected ones, at its rank among the robots not selected.
+__global__ __launch_bounds__(256) void round_select_partition_kernel(const int* __restrict__ state, int n_all, int robot0, int n_local,
+                                                                     int* __restrict__ selected, int* __restrict__ perm,
+                                                                     int* __restrict__ header) {
+  __shared__ int lds4[4];
+  int n_sel = 0, below = 0, inside = 0, undecided = 0;
+  for (int r = threadIdx.x; r < n_all; r += 256) {
+    const int st = state[r];
+    const int in = st == MMD_SEL_IN ? 1 : 0;
+    n_sel += in;
+    below += r < robot0 ? in : 0;
+    inside += r >= robot0 && r < robot0 + n_local ? in : 0;
+    undecided += st == MMD_SEL_UNDECIDED ? 1 : 0;
+  }
+  n_sel = block_sum(n_sel, lds4);
+  below = block_sum(below, lds4);
+  inside = block_sum(inside, lds4);
+  undecided = block_sum(undecided, lds4);
+  if (threadIdx.x == 0) {
+    header[0] = n_sel; header[1] = below; header[2] = inside; header[3] = undecided;
+  }
+  int base = 0;                                              // selected robots below the chunk
+  for (int r0 = 0; r0 < n_all; r0 += 256) {
+    const int r = r0 + threadIdx.x;
+    const bool in = r < n_all && state[r] == MMD_SEL_IN;
+    int prefix;
+    const int total = block_prefix(in, lds4, prefix);
+    if (r < n_all) {
+      const int sel_below = base + prefix;
+      selected[r] = in ? 1 : 0;
+      perm[in ? sel_below : n_sel + (r - sel_below)] = r;
+    }
+    base += total;
+  }
+}
+
 }  // namespace mmd
 
 using namespace mmd;
@@ -619,6 +729,36 @@ int mmd_conflict_constraints_append(const float* paths_dev, const mmd_cons_bins*
   hipLaunchKernelGGL(conflict_constraints_kernel, dim3((n_local + 3) / 4), dim3(256), 0, (hipStream_t)stream, (const float2*)paths_dev,
                      *bins, n_local, hard_slots, hard_slots + bins->n_all - 1, t_pad < H ? t_pad : H, margin, radius, (float4*)ell_dev,
                      fill_dev, dropped_dev);
+  MMD_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+int mmd_round_select(const float* paths_dev, const mmd_cons_bins* bins, const int32_t* robot_counts_dev, int n_local, int horizon,
+                     float margin, int mode, int iters, int32_t* state_dev, int32_t* selected_dev, int32_t* perm_dev, int32_t* header_dev,
+                     void* stream) {
+  MMD_REQUIRE(paths_dev && robot_counts_dev && state_dev && selected_dev && perm_dev && header_dev, "mmd_round_select: NULL argument");
+  MMD_REQUIRE(horizon == H, "mmd_round_select: horizon must be %d", H);
+  MMD_REQUIRE(mode == MMD_REPLAN_CONFLICTED || mode == MMD_REPLAN_INDEPENDENT, "mmd_round_select: unknown mode %d", mode);
+  MMD_REQUIRE(mode != MMD_REPLAN_INDEPENDENT || iters >= 1, "mmd_round_select: iters must be at least 1, got %d", iters);
+  if (int rc = check_collision_bins("mmd_round_select", bins, margin)) return rc;
+  MMD_REQUIRE(n_local >= 1 && n_local <= bins->n_all - bins->robot0, "mmd_round_select: bad robot range");
+  hipStream_t st = (hipStream_t)stream;
+  const int n_all = bins->n_all;
+  int32_t* final_state = state_dev;
+  if (mode == MMD_REPLAN_CONFLICTED) {
+    hipLaunchKernelGGL(round_select_conflicted_kernel, dim3((n_all + 255) / 256), dim3(256), 0, st, robot_counts_dev, n_all, state_dev);
+  } else {
+    // iteration i reads what iteration i - 1 wrote: the two halves of state_dev in turn, the first from the counts alone
+    const int32_t* old_state = nullptr;
+    for (int i = 0; i < iters; ++i) {
+      final_state = state_dev + (size_t)(i & 1) * n_all;
+      hipLaunchKernelGGL(round_select_iter_kernel, dim3((n_all + 3) / 4), dim3(256), 0, st, (const float2*)paths_dev, *bins, margin,
+                         robot_counts_dev, old_state, final_state);
+      old_state = final_state;
+    }
+  }
+  hipLaunchKernelGGL(round_select_partition_kernel, dim3(1), dim3(256), 0, st, final_state, n_all, bins->robot0, n_local, selected_dev,
+                     perm_dev, header_dev);
   MMD_HIP_CHECK(hipGetLastError());
   return 0;
 }

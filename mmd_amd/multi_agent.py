@@ -1,8 +1,10 @@
 """Device-side multi-agent helpers next to the sampler: robot-robot collisions of the best paths
 (RobotPlanarDisk.check_rr_collisions as CBS.get_conflicts uses it, cbs.py:166-246) and the 'least_collisions' batch scan
 (cbs.py:446-458), both also on a cell table of the best paths (count_collisions_binned, path_conflicts: O(N) work per round instead of
-O(N^2)).  Thin wrappers over the C ABI (mmd_rr_collisions, mmd_count_collisions, mmd_count_collisions_binned, mmd_path_conflicts_binned)."""
+O(N^2)).  Thin wrappers over the C ABI (mmd_rr_collisions, mmd_count_collisions, mmd_count_collisions_binned, mmd_path_conflicts_binned), and the
+choice of the robots a round re-plans from that report (select_replan: mmd_round_select)."""
 import ctypes as C
+from dataclasses import dataclass
 
 import numpy as np
 import torch
@@ -129,6 +131,52 @@ def path_conflicts(paths_all, margin=RR_MARGIN, list_cap=0, table=None, row_coun
     _lib.launch("mmd_path_conflicts_binned", paths_all, _lib.require_gpu(paths_all, "paths_all"), C.byref(table.struct), H, float(margin),
                 rows.data_ptr(), robots.data_ptr(), *report_args)
     return summ, robots, lst
+
+
+REPLAN_MODES = {"conflicted": _lib.REPLAN_CONFLICTED, "independent": _lib.REPLAN_INDEPENDENT}
+
+
+@dataclass
+class ReplanSelection:
+    """What select_replan returns, all on the device: selected int32 [N] (0 / 1), perm int32 [N] (the stable partition: the selected ids
+    ascending, then the others ascending), header int32 [4] = (robots selected, of them below the table's robot0, of them in its shard,
+    robots left undecided)."""
+    selected: torch.Tensor
+    perm: torch.Tensor
+    header: torch.Tensor
+
+    def read_header(self):
+        """-> (n_selected, sel_before, n_sel_local, n_undecided) as ints: one 16-byte device -> host copy, made by the first call and
+        kept (later calls copy nothing)."""
+        host = self.__dict__.get("_header_host")
+        if host is None:
+            host = self.__dict__["_header_host"] = tuple(int(v) for v in self.header.cpu().numpy())
+        return host
+
+
+def select_replan(paths_all, table, robot_counts, mode="conflicted", iters=8, n_local=None, margin=RR_MARGIN):
+    """The robots a round re-plans (mmd_round_select), from the round's best paths [N, 64, 2], their collision cell table
+    (constraints.binned_collision_table) and path_conflicts' robot_counts of them.  mode "conflicted": every robot with a conflict;
+    "independent": an independent set of the conflict graph, `iters` Jacobi iterations of priority propagation (a robot with more
+    collisions beats one with fewer, the lower id wins a tie) -- no two selected robots meet, so each is re-planned against neighbours
+    that keep their paths.  The shard of the header is [table.robot0, table.robot0 + n_local); n_local defaults to the table's.
+    -> ReplanSelection.  No host synchronisation."""
+    if mode not in REPLAN_MODES:
+        raise ValueError(f"select_replan: mode must be one of {sorted(REPLAN_MODES)}, got {mode!r}")
+    _collision_table(table, "select_replan")
+    paths_all = paths_all.contiguous()
+    n = paths_all.shape[0]
+    if table.n_all != n or paths_all.shape[1] != H:
+        raise ValueError(f"select_replan: paths {tuple(paths_all.shape)} and a table of {table.n_all} robots")
+    if not (robot_counts.is_cuda and robot_counts.dtype == torch.int32 and robot_counts.is_contiguous() and robot_counts.numel() == n):
+        raise ValueError(f"select_replan: robot_counts must be a contiguous int32 device tensor of {n} words")
+    dev = paths_all.device
+    state = torch.empty((2, n), dtype=torch.int32, device=dev)
+    selected, perm, header = (torch.empty(m, dtype=torch.int32, device=dev) for m in (n, n, 4))
+    _lib.launch("mmd_round_select", paths_all, _lib.require_gpu(paths_all, "paths_all"), C.byref(table.struct), robot_counts.data_ptr(),
+                int(table.n_local if n_local is None else n_local), H, float(margin), REPLAN_MODES[mode], int(iters), state.data_ptr(),
+                selected.data_ptr(), perm.data_ptr(), header.data_ptr())
+    return ReplanSelection(selected, perm, header)
 
 
 def decode_records(words):

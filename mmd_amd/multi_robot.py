@@ -13,6 +13,9 @@ colliding -- reads a device-side conflict report of them (mmd_path_conflicts_bin
 also acts on the report: every conflict becomes a hard constraint point of both its robots (constraints.RoundConstraints, built on the
 device from the round's collision table), kept over the rounds of the call in front of the soft group, as CBS does down a branch;
 plan_rounds(local_rounds=True) re-plans from the previous round's samples with a few noising and denoising steps instead of from noise.
+plan_rounds_subset(replan="conflicted" | "independent") re-samples, from round 1 on, only the robots in conflict, or an independent set of them
+(multi_agent.select_replan): the others keep their paths and samples bit for bit.  A subset round is an ordinary round of the permuted
+instance paths_all[perm], in which the selected robots are a prefix and a rank's selected robots a block of it (replan_round).
 """
 from dataclasses import dataclass
 from math import ceil
@@ -71,6 +74,9 @@ class PlanResult:
     conflict_free: bool              # conflict_counts[-1] == 0
     first_conflict: tuple            # (t, a, b, pa, pb, mid) of the returned paths' first conflict, or None
     dropped_constraints: torch.Tensor = None   # plan_rounds(repair=True): int32 [n_local] on the device, hard points that found their block full
+    # plan_rounds_subset(replan != "all"): the robots sampled per round run, over all ranks ([N, n_selected, ...]), else None.  Set on the
+    # result, not a field: the positional layout of the fields above is what callers construct
+    replanned_counts = None
 
 
 class MultiRobotSampler:
@@ -90,8 +96,10 @@ class MultiRobotSampler:
         self.n_samples = n_samples
         self.device = torch.device(device)
         self.dataset = TrajectoryDatasetFacade(norm_mins, norm_maxs)
+        self.env_id = env_id
         self.guide = GuideManagerTrajectoriesWithVelocity(self.dataset, env_id=env_id, n_robots=self.n_local,
                                                           device=device)
+        self._subset_guides = {}        # replan_round: a guide per subset size, on the same map (the resident SDF texture is shared)
         sl = slice(self.robot0, self.robot0 + self.n_local)
         self._ends = (starts[sl], goals[sl])      # plan(): the straight lines the first round starts from
         st = torch.as_tensor(starts[sl], dtype=torch.float32)
@@ -138,22 +146,30 @@ class MultiRobotSampler:
         """One guided sampling round for the local robots: [n_local*B, H, D] normalised trajectories.  The in-kernel
         Philox noise is keyed by (seed, global trajectory index): every rank passes the SAME seed and gets exactly the
         rows the unsharded run would produce."""
+        return self._sample(self.hard_conds, self.n_local, self.guide, self.robot0, seed, x_init, step_noise, return_chain)
+
+    def _sample(self, hard_conds, n_robots, guide, robot0, seed, x_init=None, step_noise=None, return_chain=False):
+        """`sample` for robots [robot0, robot0 + n_robots) of an instance: their hard conditions, their guide"""
         return self.model.run_inference(
-            None, self.hard_conds, n_samples=self.n_samples, n_robots=self.n_local, horizon=H,
-            return_chain=return_chain, sample_fn=ddpm_sample_fn, guide=self.guide, n_guide_steps=self.n_guide_steps,
+            None, hard_conds, n_samples=self.n_samples, n_robots=n_robots, horizon=H,
+            return_chain=return_chain, sample_fn=ddpm_sample_fn, guide=guide, n_guide_steps=self.n_guide_steps,
             t_start_guide=self.t_start_guide, noise_std_extra_schedule_fn=lambda t: 0.5,
             n_diffusion_steps_without_noise=self.n_extra, warm_start_path_b=x_init, step_noise=step_noise, seed=seed,
-            traj_index_base=self.robot0 * self.n_samples, device=self.device, n_streams=self.n_streams)
+            traj_index_base=robot0 * self.n_samples, device=self.device, n_streams=self.n_streams)
 
     def sample_local(self, prev_trajs, n_noising_steps=3, n_denoising_steps=3, seed=None):
         """A local re-plan round (the X-variants of CBS, cbs.py:424-430, mpd.py:460-517): forward-noise the previous round's normalised
         samples prev_trajs [n_local*B, H, D] n_noising_steps, then n_denoising_steps guided steps (+ the steps without noise) instead
         of the whole loop from noise.  Both draws are keyed by (seed, global trajectory index), as in `sample`."""
+        return self._sample_local(prev_trajs, n_noising_steps, n_denoising_steps, self.hard_conds, self.n_local, self.guide, self.robot0, seed)
+
+    def _sample_local(self, prev_trajs, n_noising_steps, n_denoising_steps, hard_conds, n_robots, guide, robot0, seed):
+        """`sample_local` for robots [robot0, robot0 + n_robots) of an instance"""
         return self.model.run_local_inference(
-            prev_trajs, n_noising_steps, n_denoising_steps, None, self.hard_conds, n_samples=self.n_samples, n_robots=self.n_local,
-            horizon=H, sample_fn=ddpm_sample_fn, guide=self.guide, n_guide_steps=self.n_guide_steps,
+            prev_trajs, n_noising_steps, n_denoising_steps, None, hard_conds, n_samples=self.n_samples, n_robots=n_robots,
+            horizon=H, sample_fn=ddpm_sample_fn, guide=guide, n_guide_steps=self.n_guide_steps,
             t_start_guide=self.t_start_guide, noise_std_extra_schedule_fn=lambda t: 0.5,
-            n_diffusion_steps_without_noise=self.n_extra, seed=seed, traj_index_base=self.robot0 * self.n_samples, device=self.device,
+            n_diffusion_steps_without_noise=self.n_extra, seed=seed, traj_index_base=robot0 * self.n_samples, device=self.device,
             n_streams=self.n_streams)
 
     def unnormalize(self, trajs_normalized):
@@ -170,23 +186,29 @@ class MultiRobotSampler:
         smoothness, mpd.py:366-370) when no paths are known yet.  A robot without any free sample falls back to the same
         criterion over all its samples (`self.last_n_free` tells).  collision_table: a collision cell table of paths_all the caller
         already has (plan_rounds(repair=True)): the counts are read from it.  Returns un-normalised positions [n_local,H,2]."""
+        if collision_table is None and paths_all is not None and self.n_robots >= 2 and self.constraint_table == "binned":
+            collision_table = self._collision_table(paths_all)     # the same integers from the cell lists instead of all N robots
+        paths, self.last_idx, self.last_n_free = self._pick(trajs_normalized, self.guide, self.robot0, self.n_local, paths_all,
+                                                            collision_table)
+        return paths
+
+    def _pick(self, trajs_normalized, guide, robot0, n_robots, paths_all, collision_table):
+        """`best_paths` for robots [robot0, robot0 + n_robots) of the instance paths_all -> (paths [n_robots, H, 2], idx, n_free); the
+        counts come from collision_table (a cell table of paths_all for these robots) where one is given, else from paths_all"""
         from . import postprocess as post
         t = self.unnormalize(trajs_normalized).contiguous()
-        r = post.postprocess_batch(self.guide, t, n_robots=self.n_local, smooth=False)
+        r = post.postprocess_batch(guide, t, n_robots=n_robots, smooth=False)
         if paths_all is None or self.n_robots < 2:
-            idx, n_free = post.select_best(r.free_mask, self.n_local, cost_a=r.path_length, cost_b=r.smoothness)
+            idx, n_free = post.select_best(r.free_mask, n_robots, cost_a=r.path_length, cost_b=r.smoothness)
         else:
             from .multi_agent import count_collisions, count_collisions_binned
             if collision_table is not None:
-                counts = count_collisions_binned(t, collision_table, self.n_local)
-            elif self.constraint_table == "binned":     # the same integers from the cell lists instead of all N robots
-                counts = count_collisions_binned(t, self._collision_table(paths_all), self.n_local)
+                counts = count_collisions_binned(t, collision_table, n_robots)
             else:
-                counts = count_collisions(t, paths_all, self.robot0, self.n_local)
-            idx, n_free = post.select_best(r.free_mask, self.n_local, counts=counts.view(-1))
-        self.last_n_free, self.last_idx = n_free, idx
-        tv = t.view(self.n_local, self.n_samples, H, D)
-        return tv[torch.arange(self.n_local, device=t.device), idx.long()][..., :2].contiguous()
+                counts = count_collisions(t, paths_all, robot0, n_robots)
+            idx, n_free = post.select_best(r.free_mask, n_robots, counts=counts.view(-1))
+        tv = t.view(n_robots, self.n_samples, H, D)
+        return tv[torch.arange(n_robots, device=t.device), idx.long()][..., :2].contiguous(), idx, n_free
 
     def plan_round(self, paths_local, seed=None):
         """all-gather -> constraint table -> guided sampling -> new local best paths."""
@@ -194,6 +216,54 @@ class MultiRobotSampler:
         self.set_other_paths(paths_all)
         trajs = self.sample(seed=seed)
         return trajs, self.best_paths(trajs, paths_all)
+
+    def _subset_guide(self, n_robots):
+        """the guide of a subset round: n_robots robots on the sampler's map, kept by size; `self.guide` and its tables are not touched"""
+        g = self._subset_guides.get(n_robots)
+        if g is None:
+            g = self._subset_guides[n_robots] = GuideManagerTrajectoriesWithVelocity(self.dataset, env_id=self.env_id, n_robots=n_robots,
+                                                                                     device=self.device)
+        return g
+
+    def selected_local_ids(self, selection):
+        """int64 device tensor: this rank's selected robots, as indices into its own robots, ascending.  `selection` is
+        multi_agent.select_replan's for this rank's shard (a collision table of robot0 = self.robot0, n_local = self.n_local)."""
+        _, sel_before, n_sel_local, _ = selection.read_header()
+        return selection.perm[sel_before:sel_before + n_sel_local].long() - self.robot0
+
+    def replan_round(self, paths_all, selection, seed, prev_trajs=None, n_noising_steps=3, n_denoising_steps=3):
+        """plan_round for this rank's SELECTED robots only (multi_agent.select_replan on this rank's collision table of paths_all), the
+        other robots' paths held: the round of the permuted instance paths_all[perm], in which the selected robots are the prefix and
+        this rank's the block [sel_before, sel_before + n_sel_local) -- the table (dense or cell) on the permuted paths, sampling with
+        the global trajectory index sel_before * B (from noise, or with prev_trajs, the selected robots' [n_sel_local * B, H, D] rows,
+        as sample_local does), the pick against the permuted paths.  The rows are those the full round of the permuted instance gives
+        these robots, whatever the sharding.  -> (trajs_sub [n_sel_local * B, H, D], best_sub [n_sel_local, H, 2], local_ids: the
+        selected robots as indices into this rank's robots, on the device).  Nothing selected here: no launch, empty tensors."""
+        _, sel_before, n_sel, _ = selection.read_header()
+        local_ids = self.selected_local_ids(selection)
+        if n_sel == 0:
+            return (torch.empty((0, H, D), dtype=torch.float32, device=self.device),
+                    torch.empty((0, H, 2), dtype=torch.float32, device=self.device), local_ids)
+        paths_perm = paths_all.index_select(0, selection.perm.long()).contiguous()
+        hard_conds = {row: v.index_select(0, local_ids) for row, v in self.hard_conds.items()}
+        guide = self._subset_guide(n_sel)
+        table = None
+        if self.constraint_table == "binned":
+            guide.reset_extra_costs()
+            guide.set_binned_constraints(binned_constraints_from_paths(paths_perm, sel_before, n_sel, self.radius, self.w_soft))
+            table = binned_collision_table(paths_perm, sel_before, n_sel, self.radius)
+        else:
+            guide.set_packed_constraints(soft_constraints_from_paths(paths_perm, sel_before, n_sel, self.radius, self.w_soft))
+        if prev_trajs is None:
+            trajs = self._sample(hard_conds, n_sel, guide, sel_before, seed)
+        else:
+            trajs = self._sample_local(prev_trajs, n_noising_steps, n_denoising_steps, hard_conds, n_sel, guide, sel_before, seed)
+        best, idx, n_free = self._pick(trajs, guide, sel_before, n_sel, paths_perm, table)
+        if getattr(self, "last_idx", None) is not None and self.last_idx.shape[0] == self.n_local:
+            # the robots not re-planned keep their entries
+            self.last_idx = self.last_idx.clone().index_copy_(0, local_ids, idx.to(self.last_idx.dtype))
+            self.last_n_free = self.last_n_free.clone().index_copy_(0, local_ids, n_free.to(self.last_n_free.dtype))
+        return trajs, best, local_ids
 
     def plan(self, paths_local=None, max_rounds=8, seed=0, list_cap=0):
         """Rounds of plan_round until the gathered best paths are free of robot-robot conflicts, at most max_rounds of them.  Round k
@@ -208,7 +278,15 @@ class MultiRobotSampler:
 
     def plan_rounds(self, paths_local=None, max_rounds=8, seed=0, list_cap=0, repair=False, hard_slots=32,
                     weight_grad_cost_constraints=2e-1, t_pad=2, local_rounds=False, n_noising_steps=3, n_denoising_steps=3):
-        """plan()'s loop -- with repair and local_rounds off, exactly plan() -- and two independent ways to act on the report.
+        """plan()'s loop -- with repair and local_rounds off, exactly plan() -- and two independent ways to act on the report (below);
+        plan_rounds_subset is this call with a third, the choice of the robots a round re-plans.  -> PlanResult."""
+        return MultiRobotSampler.plan_rounds_subset(self, paths_local, max_rounds, seed, list_cap, repair, hard_slots,
+                                                    weight_grad_cost_constraints, t_pad, local_rounds, n_noising_steps, n_denoising_steps)
+
+    def plan_rounds_subset(self, paths_local=None, max_rounds=8, seed=0, list_cap=0, repair=False, hard_slots=32,
+                           weight_grad_cost_constraints=2e-1, t_pad=2, local_rounds=False, n_noising_steps=3, n_denoising_steps=3,
+                           replan="all", independent_iters=8):
+        """plan()'s loop -- with repair and local_rounds off and replan="all", exactly plan() -- and three ways to act on the report.
 
         repair=True (convert_conflicts_to_constraints, mmd/common/conflict_conversion.py:41-55; cbs.py:407-413): the round's collision
         cell table is built once and serves the report, the pick and the hard points -- every record (t, a, b, mid) gives a and b the
@@ -217,8 +295,25 @@ class MultiRobotSampler:
         (`self.round_constraints`; PlanResult.dropped_constraints counts the points that found it full).  It needs the dense table with
         the inter-robot term: constraint_table="binned" or inter_robot=False raise.
         local_rounds=True: rounds k >= 1 re-plan from round k - 1's samples (sample_local: n_noising_steps forward, n_denoising_steps
-        back) instead of from noise.  -> PlanResult."""
-        from .multi_agent import path_conflicts, read_summary
+        back) instead of from noise.
+        replan: which robots a round k >= 1 samples (round 0 samples every robot: straight lines are not samples).  "all": every robot.
+        "conflicted": the robots of the report's conflicts.  "independent": an independent set of the conflict graph, independent_iters
+        iterations of multi_agent.select_replan -- every re-planned robot is guided against neighbours that keep their paths this
+        round.  Such a round builds its collision table once, selects on the device, reads the selection's 16-byte header (the one
+        device -> host copy it adds) and runs replan_round; robots not selected keep their path, their samples and their last_idx /
+        last_n_free entries bit for bit.  Every rank computes the same selection from the same gathered paths: no new collective, and a
+        rank with nothing selected still takes part in the all-gather.  PlanResult.replanned_counts lists the robots sampled per
+        round.  It needs the inter-robot term and does not combine with repair (the round table is laid out per local robot and does
+        not follow a permutation).  -> PlanResult."""
+        from .multi_agent import path_conflicts, read_summary, select_replan
+        if replan not in ("all", "conflicted", "independent"):
+            raise ValueError(f"plan_rounds_subset: replan must be 'all', 'conflicted' or 'independent', got {replan!r}")
+        subset = replan != "all"
+        if subset and not self.inter_robot:
+            raise ValueError(f"plan_rounds_subset(replan={replan!r}) needs inter_robot=True: without the inter-robot term no robot is in conflict with another")
+        if subset and repair:
+            raise ValueError(f"plan_rounds_subset(replan={replan!r}) does not combine with repair=True: the round table is laid out per local robot "
+                             "and does not follow a permutation")
         if repair and (self.constraint_table == "binned" or not self.inter_robot):
             raise ValueError("plan_rounds(repair=True) needs constraint_table='dense' and inter_robot=True: the library takes hard groups only in "
                              "the dense table, not next to a cell table")
@@ -231,15 +326,31 @@ class MultiRobotSampler:
             rc = self.round_constraints = RoundConstraints(self.n_robots, self.robot0, self.n_local, hard_slots, self.radius,
                                                            weight_grad_cost_constraints, self.w_soft, device=self.device)
         trajs, counts, k = None, [], 0
+        replanned = [] if subset else None
+        B = self.n_samples
         while True:
             paths_all = all_gather_paths(paths_local, self.world_size, self.group).contiguous()
             last = k == max_rounds
-            table = self._collision_table(paths_all) if rc is not None else None       # one table a round: report, hard points, pick
+            select = subset and k > 0 and self.n_robots >= 2
+            # one table a round: report, hard points, pick; or report and selection
+            table = self._collision_table(paths_all) if rc is not None or select else None
             summ, robots, lst = path_conflicts(paths_all, list_cap=list_cap, table=table)
             count, first = read_summary(summ)
             counts.append(count)
             if last or (k > 0 and count == 0):
                 break
+            if select:
+                sel = select_replan(paths_all, table, robots, replan, independent_iters)
+                replanned.append(sel.read_header()[0])
+                ids = self.selected_local_ids(sel)
+                prev = trajs.view(self.n_local, B, H, D).index_select(0, ids).view(-1, H, D) if local_rounds else None
+                trajs_sub, best_sub, ids = self.replan_round(paths_all, sel, seed + k, prev, n_noising_steps, n_denoising_steps)
+                if ids.numel():
+                    paths_local = paths_local.clone().index_copy_(0, ids, best_sub)       # (paths_all may be this very tensor)
+                    trajs.view(self.n_local, B, H, D).index_copy_(0, ids, trajs_sub.view(-1, B, H, D))
+                self._collision = None
+                k += 1
+                continue
             others = paths_all if self.inter_robot else None
             if rc is not None:
                 rc.append_conflicts(paths_all, table, t_pad=t_pad)
@@ -252,6 +363,11 @@ class MultiRobotSampler:
             else:
                 trajs = self.sample(seed=seed + k)
             paths_local = self.best_paths(trajs, others, collision_table=table)
+            if subset:
+                replanned.append(self.n_robots)
+                trajs = trajs.clone()           # the buffer later rounds scatter into (and not a view of the sampling chain)
             k += 1
         self.last_conflict_list = lst
-        return PlanResult(paths_local, trajs, k, counts, robots, count == 0, first, rc.dropped if rc is not None else None)
+        res = PlanResult(paths_local, trajs, k, counts, robots, count == 0, first, rc.dropped if rc is not None else None)
+        res.replanned_counts = replanned
+        return res

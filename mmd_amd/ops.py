@@ -1,5 +1,5 @@
 """PyTorch-ROCm custom ops over the C ABI (include/mmd_amd.h): `torch.ops.mmd_amd.{unet_forward, guide_steps,
-p_sample_loop, ddim_sample, solution_stats, bin_constraints_from_paths, count_collisions_binned, path_conflicts,
+p_sample_loop, ddim_sample, solution_stats, bin_constraints_from_paths, count_collisions_binned, path_conflicts, round_select,
 round_constraints_init, round_soft_from_paths, conflict_constraints_append}`.  They take tensors instead of raw pointers, run on torch's CURRENT HIP stream
 without any host synchronisation (so they can be captured into a hipGraph with torch.cuda.graph) and register fake
 (meta) implementations so that torch.compile / FakeTensor tracing sees their output shapes.  The C header stays the ABI
@@ -181,7 +181,7 @@ def _(paths, radius, lo_x, lo_y, hi_x, hi_y, nx, ny):
     return (paths.new_empty((64, nx * ny + 1), dtype=torch.int32), paths.new_empty((64, 9 * paths.shape[0], 4)))
 
 
-# ---- count_collisions_binned / path_conflicts ----------------------------------------------------------------------
+# ---- count_collisions_binned / path_conflicts / round_select ----------------------------------------------------------------------
 def _collision_table(paths, robot0, n_local):
     from . import constraints
     _check_traj(paths, "paths", "n_all", 2)
@@ -216,6 +216,28 @@ def path_conflicts(paths: torch.Tensor, margin: float, list_cap: int) -> Tuple[t
 def _(paths, margin, list_cap):
     return (paths.new_empty(16, dtype=torch.int32), paths.new_empty(paths.shape[0], dtype=torch.int32),
             paths.new_empty((list_cap, 12), dtype=torch.int32))
+
+
+@torch.library.custom_op("mmd_amd::round_select", mutates_args=(), device_types="cuda")
+def round_select(paths: torch.Tensor, robot_counts: torch.Tensor, robot0: int, n_local: int, margin: float, mode: int,
+                 iters: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The robots a round re-plans, from the best paths [n_all, 64, 2] and path_conflicts' robot_counts of them (mmd_bin_paths +
+    mmd_round_select; mode 0 = every robot in conflict, 1 = an independent set by `iters` iterations): (selected int32 [n_all], 0 / 1;
+    perm int32 [n_all], the selected ids then the others; header int32 [4] = selected, of them below robot0, of them in
+    [robot0, robot0 + n_local), left undecided)."""
+    from . import multi_agent
+    names = {v: k for k, v in multi_agent.REPLAN_MODES.items()}
+    if mode not in names:
+        raise RuntimeError(f"mmd_amd op: round_select mode must be one of {sorted(names)}, got {mode}")
+    _check_words(robot_counts, "robot_counts", (paths.shape[0],))
+    sel = multi_agent.select_replan(paths, _collision_table(paths, robot0, n_local), robot_counts, names[mode], iters, n_local, margin)
+    return sel.selected, sel.perm, sel.header
+
+
+@round_select.register_fake
+def _(paths, robot_counts, robot0, n_local, margin, mode, iters):
+    n = paths.shape[0]
+    return paths.new_empty(n, dtype=torch.int32), paths.new_empty(n, dtype=torch.int32), paths.new_empty(4, dtype=torch.int32)
 
 
 # ---- the round table: round_constraints_init / round_soft_from_paths / conflict_constraints_append -------------------------------
