@@ -511,6 +511,27 @@ int mmd_round_select(const float* paths_dev, const mmd_cons_bins* bins, const in
                      float margin, int mode, int iters, int32_t* state_dev, int32_t* selected_dev, int32_t* perm_dev, int32_t* header_dev,
                      void* stream);
 
+/* ---- the framed all-pairs table: many-robot rounds in a world larger than one tile ------------------------------------------------
+ * Every robot plans in the model's own tile frame; offsets_dev [n_all, 2] places each robot's window in a global frame (global = local +
+ * offset), and paths_dev [n_all, H, 2] holds GLOBAL positions.  For local robot i (r = robot0 + i) and time step t >= 1, walk j = 0 ..
+ * n_all - 1 without j == r: q = (paths[j][t].x - off[r].x, paths[j][t].y - off[r].y), one fp32 subtraction per axis; j is INCLUDED iff
+ * window_lo.x <= q.x <= window_hi.x and the same in y (plain fp32 compares: a NaN is excluded).  The s-th included j in ascending id is
+ * written as (q.x, q.y, radius, radius |radius|) into slot s of robot i, column t -- mmd_pack_constraints' slot rule, so the host pack of
+ * the included points gives the same table.  An included point past slot `slots` - 1 is not written and counts into dropped_dev[i] (summed
+ * over t); slots from the fill up, and every slot of column t = 0, hold the empty word (0, 0, -1, -1).  used_dev[i] = the largest fill
+ * over t.  One group per robot: grp_slot_off[i] = i slots, robot_grp_off[i] = i, grp_weight[i] = weight; max_slots_per_robot = slots,
+ * cons_uniform_radius = radius.  ell_out_dev [n_local slots][H][4], grp_slot_off_dev and robot_grp_off_dev [n_local + 1], grp_weight_dev,
+ * used_dev, dropped_dev [n_local].  window_lo / window_hi: host, the robot's local frame.  The culling is exact for the guided step when
+ * the window covers the normaliser's position limits widened by (1 + 1/16) radius: the step clips every position into those limits and a
+ * point acts only within its radius (the argument is next to the kernel).  With zero offsets, an unbounded window and slots = n_all - 1
+ * the columns t >= 1 are mmd_soft_constraints_from_paths' bit for bit.  One launch, no atomics, no host synchronisation; O(n_all) work
+ * per (robot, time step).  NULL pointers, horizon != H, n_all outside [2, 4096], a robot range outside [0, n_all), slots outside
+ * [1, n_all - 1], radius <= 0 or window_lo[k] >= window_hi[k] are error returns before any launch. */
+int mmd_framed_constraints_from_paths(const float* paths_dev, const float* offsets_dev, int n_all, int robot0, int n_local, int horizon,
+                                      int slots, float radius, float weight, const float window_lo[2], const float window_hi[2],
+                                      float* ell_out_dev, int32_t* grp_slot_off_dev, float* grp_weight_dev, int32_t* robot_grp_off_dev,
+                                      int32_t* used_dev, int32_t* dropped_dev, void* stream);
+
 /* ------------------------------------------------------------------------------------------------------------
  * The statistics of a returned solution (scripts/inference/inference_multi_agent.py:285-342, run_multi_agent_trial)
  * ---------------------------------------------------------------------------------------------------------- */

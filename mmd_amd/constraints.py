@@ -180,6 +180,82 @@ def soft_constraints_from_paths(paths: torch.Tensor, robot0: int, n_local: int, 
     return ell, gso, gw, rgo, float(radius)
 
 
+FRAME_WINDOW_SLACK = 1.0625      # a robot's window is the position limits widened by (1 + 1/16) x the radius (csrc/multi_agent.hip)
+
+
+def framed_window(limits, radius):
+    """(lo [2], hi [2]) float32: `limits` = (lo, hi) widened by 1.0625 x radius per side, computed in fp32 -- the window
+    framed_constraints_from_paths culls with when none is given."""
+    w = np.float32(FRAME_WINDOW_SLACK) * np.float32(radius)
+    return (np.asarray(limits[0], dtype=np.float32) - w).astype(np.float32), (np.asarray(limits[1], dtype=np.float32) + w).astype(np.float32)
+
+
+def framed_constraints_table(paths, offsets, robot0, n_local, slots, radius, weight, window):
+    """mmd_framed_constraints_from_paths on checked tensors -> (ell, grp_slot_off, grp_weight, robot_grp_off, used, dropped).  One launch
+    on the current stream, no host synchronisation."""
+    n_all, dev = paths.shape[0], paths.device
+    ell = torch.empty((n_local * slots, H, 4), dtype=torch.float32, device=dev)
+    gso = torch.empty(n_local + 1, dtype=torch.int32, device=dev)
+    gw = torch.empty(n_local, dtype=torch.float32, device=dev)
+    rgo = torch.empty(n_local + 1, dtype=torch.int32, device=dev)
+    used = torch.empty(n_local, dtype=torch.int32, device=dev)
+    dropped = torch.empty(n_local, dtype=torch.int32, device=dev)
+    lo, hi = (C.c_float * 2)(*[float(v) for v in window[0]]), (C.c_float * 2)(*[float(v) for v in window[1]])
+    _lib.launch("mmd_framed_constraints_from_paths", paths, _lib.require_gpu(paths, "paths"), _lib.require_gpu(offsets, "offsets"), n_all,
+                int(robot0), int(n_local), H, int(slots), float(radius), float(weight), lo, hi, ell.data_ptr(), gso.data_ptr(),
+                gw.data_ptr(), rgo.data_ptr(), used.data_ptr(), dropped.data_ptr())
+    return ell, gso, gw, rgo, used, dropped
+
+
+def framed_constraints_from_paths(paths: torch.Tensor, offsets: torch.Tensor, robot0: int, n_local: int, slots: int,
+                                  radius=VERTEX_CONSTRAINT_RADIUS, weight=2e-2, window=None):
+    """The inter-robot soft constraints of robots that each plan in the model's own tile frame, at offsets [N, 2] in a global frame (global
+    = local + offset): paths [N, H, 2] GLOBAL best-path positions of all robots on this device.  Local robot r's block holds, per time
+    step t >= 1, the other robots' points paths[j][t] - offsets[r] that fall into `window` = (lo, hi) of r's local frame (default:
+    environments.LIMITS widened by 1.0625 x radius, in fp32), packed in ascending id into `slots` slots: the table's size follows the
+    local density, not N, and the guided step's result is that of the unculled all-pairs table (a point outside the window can never
+    come within `radius` of a clipped trajectory).  -> (ell, grp_slot_off, grp_weight, robot_grp_off, radius) as set_packed_constraints
+    takes them, then used int32 [n_local] (the most slots a robot filled at one time step) and dropped int32 [n_local] (included points
+    that found the block full; 0 at slots = framed_slot_bound while every path stays in its own window), both on the device."""
+    if paths.dim() != 3 or paths.shape[1] != H or paths.shape[2] != 2:
+        raise ValueError(f"framed_constraints_from_paths: paths [N, {H}, 2], got {tuple(paths.shape)}")
+    n_all = paths.shape[0]
+    if tuple(offsets.shape) != (n_all, 2):
+        raise ValueError(f"framed_constraints_from_paths: offsets [{n_all}, 2], got {tuple(offsets.shape)}")
+    if not (n_all >= 2 and n_local >= 1 and robot0 >= 0 and robot0 + n_local <= n_all):
+        raise ValueError("framed_constraints_from_paths: bad robot range")
+    if not 1 <= int(slots) <= n_all - 1:
+        raise ValueError(f"framed_constraints_from_paths: slots must be in [1, {n_all - 1}], got {slots}")
+    if window is None:
+        from .environments import LIMITS
+        window = framed_window(LIMITS, radius)
+    out = framed_constraints_table(paths, offsets, robot0, n_local, slots, radius, weight, window)
+    return out[:4] + (float(radius),) + out[4:]
+
+
+def framed_slot_bound(offsets, robot0, n_local, limits=None, radius=VERTEX_CONSTRAINT_RADIUS):
+    """The static slot bound of framed_constraints_from_paths, on the host from the offsets [N, 2] alone: per local robot the number of
+    OTHER robots whose window box offset_j + limits intersects this robot's widened window offset_r + (limits -/+ 1.0625 x radius); the
+    maximum over the local robots, clamped to [1, N - 1].  While every path stays inside its own window box, no included point is ever
+    dropped at this many slots.  The boxes are closed and compared with a few fp32 ulp of the coordinates' size to spare, so the rounding
+    of the device's fp32 subtraction cannot include a robot this count left out."""
+    if limits is None:
+        from .environments import LIMITS
+        limits = LIMITS
+    off = np.asarray(torch.as_tensor(offsets).detach().cpu().numpy(), dtype=np.float64).reshape(-1, 2)
+    n = off.shape[0]
+    if not (n >= 2 and n_local >= 1 and robot0 >= 0 and robot0 + n_local <= n):
+        raise ValueError("framed_slot_bound: bad robot range")
+    wlo, whi = (np.asarray(v, dtype=np.float64) for v in framed_window(limits, radius))
+    lo, hi = np.asarray(limits[0], dtype=np.float64), np.asarray(limits[1], dtype=np.float64)
+    eps = 4.0 * float(np.finfo(np.float32).eps) * (np.abs(off).max() + max(np.abs(wlo).max(), np.abs(whi).max()))
+    worst = 0
+    for r in range(robot0, robot0 + n_local):
+        hit = np.all((off + hi >= off[r] + wlo - eps) & (off + lo <= off[r] + whi + eps), axis=1)
+        worst = max(worst, int(hit.sum()) - 1)                          # (robot r's own box always intersects)
+    return min(max(worst, 1), n - 1)
+
+
 BIN_CELL_SLACK = 1.0625          # a cell side is at least (1 + 1/16) x the radius (csrc/guide.hip: the cover argument above bin_cell)
 BIN_MAX_CELLS = 32               # per axis, of the default grid
 

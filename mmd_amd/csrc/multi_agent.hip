@@ -18,7 +18,9 @@
 //     cbs.py:407-413), appended round after round from the same cell table, and behind them the soft all-pairs group;
 //   * which robots a round re-plans (mmd_round_select): the robots in conflict, or an independent set of the conflict graph found by
 //     priority propagation on the same cell table -- CBS re-plans one agent of a conflict against the others' fixed paths (cbs.py:316-324);
-//     a round does that for every robot of the set at once -- and the stable partition that makes the selected robots a prefix.
+//     a round does that for every robot of the set at once -- and the stable partition that makes the selected robots a prefix;
+//   * the framed all-pairs table of a round in a world larger than one tile (mmd_framed_constraints_from_paths): every robot plans in
+//     the model's tile frame at its own offset, and its table keeps the other robots' global points that fall into its window.
 #include <hip/hip_runtime.h>
 
 #include <climits>
@@ -445,6 +447,80 @@ __global__ __launch_bounds__(256) void conflict_constraints_kernel(const float2*
   if (t == 0) dropped[r] += drop;
 }
 
+// ---- the framed all-pairs table: every robot plans in the model's tile frame, the robots meet in a global frame ---------------------
+//
+// Robot r's trajectory lives in the model's own frame (the tile [-1, 1]^2 the normaliser spans); off[r] places that window in the world:
+// global = local + off[r].  The other robots' gathered paths are global, so robot r sees robot j's point at q = paths[j][t] - off[r] (one
+// fp32 subtraction per axis).  The table keeps q only where it lies in the robot's WINDOW [window_lo, window_hi] (local frame, closed,
+// plain fp32 compares: a NaN fails them and is left out), packed by mmd_pack_constraints' rule: the s-th kept robot, in ascending id, goes
+// to slot s of column t.  So a robot owns S slots whatever n_all is, S is sized by the local density, and every guided-step kernel reads
+// the table as it reads any other.
+//
+// WHY LEAVING THE OTHERS OUT IS EXACT.  The guided step un-normalises with an unconditional clip, so the position p it measures from lies
+// in the normaliser's position limits [min, max] up to the rounding of (c + 1) / 2 (max - min) + min with c in [-1, 1]: a few ulp of the
+// limits' magnitude.  A point acts on p only within its radius R: the guided step's test fma(dx, dx, dy dy) <= R|R| (guide.hip:
+// cons_term) needs |dx|, |dy| <= R (1 + 2^-23) by COVER's argument (the radicand is at least each rounded square).  The Python layer
+// passes the window limits -/+ 1.0625 R -- the 1/16 slack of the cell rule.  A q outside it differs from every such p by more than
+// 1.0625 R - (those few ulp) on one axis, which is above R by R / 16 less a few 1e-7: it can never act, at any step of any sample.  A
+// table without it gives the guided step the same ACTIVE TERMS, in ascending id.  Not the same bits as the all-pairs table: the step
+// sums a group's slots in four accumulators by slot index, and culling moves a robot to another slot, so the rounding of the sum may
+// differ (the dense table's 2e-6 against the oracle holds for both); the host pack of the included points has the same slots and the
+// same bits.  What the caller must keep true is only that the window covers limits -/+ R with that slack.
+//
+// One wave per local robot, lane = time step t, four robots a workgroup, no atomics, no LDS (conflict_constraints_kernel's shape).  Lane t
+// reads paths[j][t]: the wave reads one 512-byte row per j, four rows a trip (the loads of a trip are issued together; a trip past the
+// end re-reads the last row and drops it), and writes 1 KiB rows of the table.  O(n_all) per lane, whatever the density: a walk over
+// candidate lists or a world cell table would be O(neighbours), and is not done here.  A kept point past slot S - 1 is not written and
+// counts into dropped[i]; the lane's fill stays at S, so what was written is a prefix of the list.  Slots from the fill on, and all of
+// column 0 (constraints cover t >= 1), get the empty word (0, 0, -1, -1) mmd_pack_constraints leaves in an unused slot.
+__global__ __launch_bounds__(256) void framed_constraints_kernel(const float2* __restrict__ paths, const float2* __restrict__ offsets,
+                                                                  int n_all, int robot0, int n_local, int S, float radius, float weight,
+                                                                  float2 wlo, float2 whi, float4* __restrict__ ell,
+                                                                  int* __restrict__ grp_slot_off, float* __restrict__ grp_weight,
+                                                                  int* __restrict__ robot_grp_off, int* __restrict__ used,
+                                                                  int* __restrict__ dropped) {
+  const int t = threadIdx.x & 63;
+  const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (i >= n_local) return;
+  const int r = robot0 + i;
+  const float2 off = offsets[r];
+  float4* const col = ell + (size_t)i * S * H + t;                        // the robot's block, column t
+  const float r2 = radius * fabsf(radius);
+  int f = 0, drop = 0;
+  for (int j0 = 0; j0 < n_all; j0 += 4) {
+    float2 p[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) p[k] = paths[(size_t)min(j0 + k, n_all - 1) * H + t];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int j = j0 + k;
+      const float qx = p[k].x - off.x, qy = p[k].y - off.y;
+      const bool in = qx >= wlo.x && qx <= whi.x && qy >= wlo.y && qy <= whi.y;
+      if (!(t >= 1 && j < n_all && j != r && in)) continue;
+      if (f < S) {
+        col[(size_t)f * H] = make_float4(qx, qy, radius, r2);
+        ++f;
+      } else {
+        ++drop;
+      }
+    }
+  }
+  const int fill = wave_max(f);
+  for (; f < S; ++f) col[(size_t)f * H] = make_float4(0.f, 0.f, -1.f, -1.f);
+  drop = wave_sum(drop);
+  if (t == 0) {                                                           // one group of S slots per robot
+    used[i] = fill;
+    dropped[i] = drop;
+    grp_slot_off[i] = i * S;
+    grp_weight[i] = weight;
+    robot_grp_off[i] = i;
+    if (i == n_local - 1) {
+      grp_slot_off[n_local] = n_local * S;
+      robot_grp_off[n_local] = n_local;
+    }
+  }
+}
+
 // ---- which robots a round re-plans: the robots in conflict, or an independent set of the conflict graph -----------------------------
 //
 // The conflict graph: robots r != j are neighbours iff rr_hit(p_r(t), p_j(t), margin) at some t in [0, H).  rr_hit is symmetric in its two
@@ -729,6 +805,29 @@ int mmd_conflict_constraints_append(const float* paths_dev, const mmd_cons_bins*
   hipLaunchKernelGGL(conflict_constraints_kernel, dim3((n_local + 3) / 4), dim3(256), 0, (hipStream_t)stream, (const float2*)paths_dev,
                      *bins, n_local, hard_slots, hard_slots + bins->n_all - 1, t_pad < H ? t_pad : H, margin, radius, (float4*)ell_dev,
                      fill_dev, dropped_dev);
+  MMD_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+int mmd_framed_constraints_from_paths(const float* paths_dev, const float* offsets_dev, int n_all, int robot0, int n_local, int horizon,
+                                      int slots, float radius, float weight, const float window_lo[2], const float window_hi[2],
+                                      float* ell_out_dev, int32_t* grp_slot_off_dev, float* grp_weight_dev, int32_t* robot_grp_off_dev,
+                                      int32_t* used_dev, int32_t* dropped_dev, void* stream) {
+  const char* who = "mmd_framed_constraints_from_paths";
+  MMD_REQUIRE(paths_dev && offsets_dev && window_lo && window_hi && ell_out_dev && grp_slot_off_dev && grp_weight_dev && robot_grp_off_dev &&
+                  used_dev && dropped_dev, "%s: NULL argument", who);
+  MMD_REQUIRE(horizon == H, "%s: horizon must be %d", who, H);
+  MMD_REQUIRE(n_all >= 2 && n_all <= 4096, "%s: n_all must be in [2, 4096], got %d", who, n_all);
+  MMD_REQUIRE(n_local >= 1 && robot0 >= 0 && robot0 < n_all && n_local <= n_all - robot0, "%s: bad robot range", who);
+  MMD_REQUIRE(slots >= 1 && slots <= n_all - 1, "%s: slots must be in [1, n_all - 1], got %d", who, slots);
+  MMD_REQUIRE(radius > 0.f, "%s: radius must be positive", who);
+  for (int k = 0; k < 2; ++k)
+    MMD_REQUIRE(window_lo[k] < window_hi[k], "%s: empty window (axis %d: %g >= %g)", who, k, window_lo[k], window_hi[k]);
+  // (n_local slots H <= 4096 x 4095 x 64 < 2^31: the guided step's int index of the table's (slot, t) words holds)
+  hipLaunchKernelGGL(framed_constraints_kernel, dim3((n_local + 3) / 4), dim3(256), 0, (hipStream_t)stream, (const float2*)paths_dev,
+                     (const float2*)offsets_dev, n_all, robot0, n_local, slots, radius, weight, make_float2(window_lo[0], window_lo[1]),
+                     make_float2(window_hi[0], window_hi[1]), (float4*)ell_out_dev, grp_slot_off_dev, grp_weight_dev, robot_grp_off_dev,
+                     used_dev, dropped_dev);
   MMD_HIP_CHECK(hipGetLastError());
   return 0;
 }

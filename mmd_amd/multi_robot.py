@@ -16,6 +16,7 @@ plan_rounds(local_rounds=True) re-plans from the previous round's samples with a
 plan_rounds_subset(replan="conflicted" | "independent") re-samples, from round 1 on, only the robots in conflict, or an independent set of them
 (multi_agent.select_replan): the others keep their paths and samples bit for bit.  A subset round is an ordinary round of the permuted
 instance paths_all[perm], in which the selected robots are a prefix and a rank's selected robots a block of it (replan_round).
+Every robot here lives on the model's one tile; world.WorldRobotSampler is the same loop for robots that each carry an offset into a larger world.
 """
 from dataclasses import dataclass
 from math import ceil
@@ -73,7 +74,9 @@ class PlanResult:
     robot_counts: torch.Tensor       # int32 [N] on the device: (t, other robot) collisions of every robot, of the returned paths
     conflict_free: bool              # conflict_counts[-1] == 0
     first_conflict: tuple            # (t, a, b, pa, pb, mid) of the returned paths' first conflict, or None
-    dropped_constraints: torch.Tensor = None   # plan_rounds(repair=True): int32 [n_local] on the device, hard points that found their block full
+    # plan_rounds(repair=True): int32 [n_local] on the device, hard points that found their block full; world.WorldRobotSampler: the
+    # framed table's dropped points of the last round
+    dropped_constraints: torch.Tensor = None
     # plan_rounds_subset(replan != "all"): the robots sampled per round run, over all ranks ([N, n_selected, ...]), else None.  Set on the
     # result, not a field: the positional layout of the fields above is what callers construct
     replanned_counts = None
@@ -125,6 +128,11 @@ class MultiRobotSampler:
         if self._collision is None or self._collision[0] is not paths_all:
             self._collision = (paths_all, binned_collision_table(paths_all.contiguous(), self.robot0, self.n_local, self.radius))
         return self._collision[1]
+
+    def _report_on_own_table(self):
+        """Whether plan()'s conflict report reads this sampler's _collision_table (a subclass whose table is not the default one:
+        world.WorldRobotSampler) instead of the default table multi_agent.path_conflicts builds for itself.  The same integers either way."""
+        return False
 
     def set_other_paths(self, paths_all):
         """paths_all [N,H,2] un-normalised best paths of ALL robots (this device) or None (no inter-robot term).  With the cell table
@@ -333,7 +341,7 @@ class MultiRobotSampler:
             last = k == max_rounds
             select = subset and k > 0 and self.n_robots >= 2
             # one table a round: report, hard points, pick; or report and selection
-            table = self._collision_table(paths_all) if rc is not None or select else None
+            table = self._collision_table(paths_all) if rc is not None or select or self._report_on_own_table() else None
             summ, robots, lst = path_conflicts(paths_all, list_cap=list_cap, table=table)
             count, first = read_summary(summ)
             counts.append(count)

@@ -1,6 +1,7 @@
 """PyTorch-ROCm custom ops over the C ABI (include/mmd_amd.h): `torch.ops.mmd_amd.{unet_forward, guide_steps,
 p_sample_loop, ddim_sample, solution_stats, bin_constraints_from_paths, count_collisions_binned, path_conflicts, round_select,
-round_constraints_init, round_soft_from_paths, conflict_constraints_append}`.  They take tensors instead of raw pointers, run on torch's CURRENT HIP stream
+round_constraints_init, round_soft_from_paths, conflict_constraints_append,
+framed_constraints_from_paths}`.  They take tensors instead of raw pointers, run on torch's CURRENT HIP stream
 without any host synchronisation (so they can be captured into a hipGraph with torch.cuda.graph) and register fake
 (meta) implementations so that torch.compile / FakeTensor tracing sees their output shapes.  The C header stays the ABI
 of record: every op is a thin wrapper over the same entry point the host mirror classes call through ctypes.
@@ -298,3 +299,25 @@ def conflict_constraints_append(ell: torch.Tensor, fill: torch.Tensor, dropped: 
     _check_words(dropped, "dropped", (n_local,))
     _lib.launch("mmd_conflict_constraints_append", ell, paths.data_ptr(), C.byref(table.struct), int(n_local), 64, int(hard_slots),
                 int(t_pad), float(margin), float(radius), ell.data_ptr(), fill.data_ptr(), dropped.data_ptr())
+
+
+# ---- framed_constraints_from_paths ---------------------------------------------------------------------------------
+@torch.library.custom_op("mmd_amd::framed_constraints_from_paths", mutates_args=(), device_types="cuda")
+def framed_constraints_from_paths(paths: torch.Tensor, offsets: torch.Tensor, robot0: int, n_local: int, slots: int, radius: float,
+                                  weight: float, lo_x: float, lo_y: float, hi_x: float,
+                                  hi_y: float) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The framed all-pairs table of the GLOBAL best paths [n_all, 64, 2] of robots at offsets [n_all, 2] (mmd_framed_constraints_from_paths),
+    culled with the window (lo, hi) of a robot's local frame: (ell float32 [n_local slots, 64, 4], grp_slot_off int32 [n_local + 1],
+    grp_weight float32 [n_local], robot_grp_off int32 [n_local + 1], used int32 [n_local], dropped int32 [n_local])."""
+    from . import constraints
+    _check_traj(paths, "paths", "n_all", 2)
+    if not (offsets.is_cuda and offsets.dtype == torch.float32 and offsets.is_contiguous() and tuple(offsets.shape) == (paths.shape[0], 2)):
+        raise RuntimeError(f"mmd_amd op: offsets must be a contiguous float32 CUDA(HIP) tensor [{paths.shape[0]}, 2]")
+    return constraints.framed_constraints_table(paths, offsets, int(robot0), int(n_local), int(slots), radius, weight, ((lo_x, lo_y), (hi_x, hi_y)))
+
+
+@framed_constraints_from_paths.register_fake
+def _(paths, offsets, robot0, n_local, slots, radius, weight, lo_x, lo_y, hi_x, hi_y):
+    return (paths.new_empty((n_local * slots, 64, 4)), paths.new_empty(n_local + 1, dtype=torch.int32), paths.new_empty(n_local),
+            paths.new_empty(n_local + 1, dtype=torch.int32), paths.new_empty(n_local, dtype=torch.int32),
+            paths.new_empty(n_local, dtype=torch.int32))

@@ -1,0 +1,204 @@
+"""Many-robot rounds in a world larger than one tile: per-robot frames.
+
+The model plans on its own tile, [-1, 1]^2 (the span of the normaliser); MultiRobotSampler puts every robot on that one tile.  Here robot
+r plans in that same frame but carries an offset that places its window in a global frame -- global = local + offset[r] -- and the robots
+interact in the global frame: starts, goals, the gathered best paths, the pick's collision counts and the conflict report are all global.
+Nothing of the model or the guided step changes (translation invariance is what the method already relies on when it composes tile
+models); the only new device code is the framed all-pairs table (constraints.framed_constraints_from_paths,
+mmd_framed_constraints_from_paths): robot r's block holds the other robots' points, shifted into r's frame, that fall into r's window
+widened by 1.0625 x the constraint radius.  A trajectory is clipped to the normaliser's limits, so a point outside that window can never
+act on it: the table is exact and its size follows the local density, not N.
+"""
+import numpy as np
+import torch
+
+from . import synth
+from .constraints import (BIN_CELL_SLACK, VERTEX_CONSTRAINT_RADIUS, binned_collision_table, framed_constraints_from_paths,
+                          framed_slot_bound)
+from .environments import LIMITS, MAP_BOXES, map_sdf
+from .multi_robot import D, H, MultiRobotSampler, shard_range
+
+WORLD_MAX_CELLS = 64             # per axis: what the library takes for a cell table (the default grid of constraints.bin_grid stops at 32)
+TILE_PITCH = 2.0                 # the side of a tile: window origins on maps with obstacles are multiples of it
+OBSTACLE_MARGIN = 0.16           # trials.get_start_goal_pos_random_in_env's obstacle_margin
+
+
+def _f32(a, what, n=None):
+    a = np.ascontiguousarray(torch.as_tensor(a).detach().cpu().numpy(), dtype=np.float32)
+    if a.ndim != 2 or a.shape[1] != 2 or (n is not None and a.shape[0] != n):
+        raise ValueError(f"WorldRobotSampler: {what} must be [{'N' if n is None else n}, 2], got {a.shape}")
+    return a
+
+
+def world_limits(offsets, limits=LIMITS):
+    """(lo, hi) of the box that holds every robot's window: the collision cell table of a world is laid over it"""
+    off = np.asarray(offsets, dtype=np.float64).reshape(-1, 2)
+    return (tuple(float(off[:, k].min() + limits[0][k]) for k in range(2)), tuple(float(off[:, k].max() + limits[1][k]) for k in range(2)))
+
+
+def world_grid(limits, radius):
+    """(nx, ny): the finest grid over `limits`, up to 64 cells per axis, whose cells are at least (1 + 1/16) x radius wide"""
+    n = []
+    for k in range(2):
+        cells = min(WORLD_MAX_CELLS, int(np.floor((float(limits[1][k]) - float(limits[0][k])) / (BIN_CELL_SLACK * float(radius)))))
+        if cells < 1:
+            raise ValueError(f"world_grid: axis {k} cannot hold a cell of {BIN_CELL_SLACK} x radius")
+        n.append(cells)
+    return tuple(n)
+
+
+class WorldRobotSampler(MultiRobotSampler):
+    """MultiRobotSampler for robots that each plan in the model's tile frame at their own offset in a global frame.  starts, goals [N, 2],
+    the paths plan_round / plan take and return and PlanResult.paths_local are GLOBAL; offsets [N, 2] (every rank holds all of them);
+    the hard conditions are start - offset and goal - offset, which must lie in the normaliser's position limits.  neighbor_slots: the
+    slots per robot of the framed table (None: constraints.framed_slot_bound, computed once from the offsets).  constraint_table="dense"
+    counts the pick's collisions over all pairs; "binned" reads them, and plan()'s report, off a collision cell table over the world's
+    limits.  The guided step reads the framed all-pairs table either way.  After every set_other_paths, `last_used` / `last_dropped`
+    (int32 [n_local], on the device) tell the most slots a robot filled at one time step and the included points that found its block
+    full.  `window` (an attribute, None = the default) is the culling window; a measurement may open it to compare with the all-pairs form.
+    plan_rounds(repair=True) and plan_rounds_subset(replan != "all") are refused: their tables are built without frames."""
+
+    def __init__(self, model, starts, goals, offsets, env_id="EnvEmpty2D", n_samples=64, rank=0, world_size=1,
+                 norm_mins=synth.NORM_MINS, norm_maxs=synth.NORM_MAXS, n_guide_steps=20, start_guide_steps_fraction=0.5,
+                 n_diffusion_steps_without_noise=1, weight_grad_cost_soft_constraints=2e-2, radius=VERTEX_CONSTRAINT_RADIUS,
+                 device="cuda", group=None, n_streams=0, inter_robot=True, constraint_table="dense", neighbor_slots=None):
+        starts, goals, offsets = _f32(starts, "starts"), _f32(goals, "goals"), _f32(offsets, "offsets")
+        n = starts.shape[0]
+        if goals.shape[0] != n or offsets.shape[0] != n:
+            raise ValueError(f"WorldRobotSampler: {n} starts, {goals.shape[0]} goals, {offsets.shape[0]} offsets")
+        local_starts, local_goals = starts - offsets, goals - offsets                      # one fp32 subtraction per axis
+        lo, hi = np.asarray(norm_mins, np.float32)[:2], np.asarray(norm_maxs, np.float32)[:2]
+        for name, p in (("start", local_starts), ("goal", local_goals)):
+            bad = np.flatnonzero(~np.all((p >= lo) & (p <= hi), axis=1))
+            if bad.size:
+                r = int(bad[0])
+                raise ValueError(f"WorldRobotSampler: the {name} of robot {r} is {p[r].tolist()} in its own frame, outside the normaliser's "
+                                 f"limits {lo.tolist()} .. {hi.tolist()}")
+        robot0, n_local = shard_range(n, rank, world_size)
+        if neighbor_slots is None:
+            neighbor_slots = framed_slot_bound(offsets, robot0, n_local, LIMITS, radius) if n >= 2 else 1
+        if n >= 2 and not 1 <= int(neighbor_slots) <= n - 1:
+            raise ValueError(f"WorldRobotSampler: neighbor_slots must be in [1, {n - 1}], got {neighbor_slots}")
+        super().__init__(model, local_starts, local_goals, env_id=env_id, n_samples=n_samples, rank=rank, world_size=world_size,
+                         norm_mins=norm_mins, norm_maxs=norm_maxs, n_guide_steps=n_guide_steps,
+                         start_guide_steps_fraction=start_guide_steps_fraction,
+                         n_diffusion_steps_without_noise=n_diffusion_steps_without_noise,
+                         weight_grad_cost_soft_constraints=weight_grad_cost_soft_constraints, radius=radius, device=device, group=group,
+                         n_streams=n_streams, inter_robot=inter_robot, constraint_table=constraint_table)
+        sl = slice(self.robot0, self.robot0 + self.n_local)
+        self._ends = (starts[sl], goals[sl])             # plan(): the straight lines of the GLOBAL ends
+        self.neighbor_slots = int(neighbor_slots)
+        self.offsets = torch.from_numpy(offsets).to(self.device)
+        self.world_limits = world_limits(offsets)
+        self.world_grid = world_grid(self.world_limits, radius)
+        self.window = None              # the culling window in a robot's frame; None: constraints.framed_window(LIMITS, radius)
+        self.last_used = self.last_dropped = None
+
+    # ---- the three places where a round meets the other robots ----------------------------------------------------------------------
+    def _collision_table(self, paths_all):
+        """The collision cell table of the global paths over the world's limits (a robot outside them lands in a border cell: the cell
+        index is clamped, which keeps neighbours in neighbouring cells)."""
+        if self._collision is None or self._collision[0] is not paths_all:
+            self._collision = (paths_all, binned_collision_table(paths_all.contiguous(), self.robot0, self.n_local, self.radius,
+                                                                 limits=self.world_limits, grid=self.world_grid))
+        return self._collision[1]
+
+    def _report_on_own_table(self):
+        return self.constraint_table == "binned" and self.n_robots >= 2
+
+    def set_other_paths(self, paths_all):
+        """paths_all [N, H, 2] GLOBAL best paths of all robots (this device) or None: the framed table of the local robots for the guided
+        step, and with constraint_table="binned" the world collision table for best_paths."""
+        self._collision = None
+        self.last_used = self.last_dropped = None
+        if paths_all is None or self.n_robots < 2:
+            self.guide.reset_extra_costs()
+            return
+        cons = framed_constraints_from_paths(paths_all.contiguous(), self.offsets, self.robot0, self.n_local, self.neighbor_slots,
+                                             self.radius, self.w_soft, self.window)
+        self.guide.set_packed_constraints(cons[:5])
+        self.last_used, self.last_dropped = cons[5], cons[6]
+        if self.constraint_table == "binned":
+            self._collision_table(paths_all)
+
+    def _pick(self, trajs_normalized, guide, robot0, n_robots, paths_all, collision_table):
+        """MultiRobotSampler._pick with the samples shifted to the global frame for everything between robots: the map and the joint
+        limits are checked in the robot's own frame, the collisions are counted against the global paths, the picks are global."""
+        from . import postprocess as post
+        t = self.unnormalize(trajs_normalized).contiguous()
+        r = post.postprocess_batch(guide, t, n_robots=n_robots, smooth=False)
+        tg = t.view(n_robots, self.n_samples, H, D).clone()
+        tg[..., :2] += self.offsets[robot0:robot0 + n_robots, None, None, :]              # positions + offset, one fp32 add
+        if paths_all is None or self.n_robots < 2:
+            idx, n_free = post.select_best(r.free_mask, n_robots, cost_a=r.path_length, cost_b=r.smoothness)
+        else:
+            from .multi_agent import count_collisions, count_collisions_binned
+            flat = tg.view(-1, H, D)
+            if collision_table is not None:
+                counts = count_collisions_binned(flat, collision_table, n_robots)
+            else:
+                counts = count_collisions(flat, paths_all, robot0, n_robots)
+            idx, n_free = post.select_best(r.free_mask, n_robots, counts=counts.view(-1))
+        return tg[torch.arange(n_robots, device=t.device), idx.long()][..., :2].contiguous(), idx, n_free
+
+    # ---- the loop: MultiRobotSampler's, through the methods above -------------------------------------------------------------------
+    def plan_rounds(self, paths_local=None, max_rounds=8, seed=0, list_cap=0, repair=False, hard_slots=32,
+                    weight_grad_cost_constraints=2e-1, t_pad=2, local_rounds=False, n_noising_steps=3, n_denoising_steps=3):
+        return WorldRobotSampler.plan_rounds_subset(self, paths_local, max_rounds, seed, list_cap, repair, hard_slots,
+                                                    weight_grad_cost_constraints, t_pad, local_rounds, n_noising_steps, n_denoising_steps)
+
+    def plan_rounds_subset(self, paths_local=None, max_rounds=8, seed=0, list_cap=0, repair=False, hard_slots=32,
+                           weight_grad_cost_constraints=2e-1, t_pad=2, local_rounds=False, n_noising_steps=3, n_denoising_steps=3,
+                           replan="all", independent_iters=8):
+        """MultiRobotSampler.plan_rounds_subset on global paths.  PlanResult.dropped_constraints is `last_dropped` of the last round run
+        (a device tensor, or None when no table was built)."""
+        if repair:
+            raise ValueError("WorldRobotSampler: repair=True is not supported: the round table is built without per-robot frames")
+        if replan != "all":
+            raise ValueError(f"WorldRobotSampler: replan={replan!r} is not supported: replan_round builds its tables without per-robot frames")
+        res = MultiRobotSampler.plan_rounds_subset(self, paths_local, max_rounds, seed, list_cap, False, hard_slots,
+                                                   weight_grad_cost_constraints, t_pad, local_rounds, n_noising_steps, n_denoising_steps,
+                                                   "all", independent_iters)
+        res.dropped_constraints = self.last_dropped
+        return res
+
+    def replan_round(self, *args, **kwargs):
+        raise ValueError("WorldRobotSampler: replan_round is not supported: it builds its tables without per-robot frames")
+
+
+def random_world_instance(n_robots, extent, seed, env_id="EnvEmpty2D", min_separation=0.15, max_draws=200000):
+    """A random many-robot instance in a square world of side `extent`, centred on the origin -> (starts, goals, offsets), float32
+    [n_robots, 2] each, starts and goals global.  Per robot, from numpy.random.Generator(PCG64(seed)) as
+    trials.get_start_goal_pos_random_in_env draws: a window origin such that the window offset + [-1, 1]^2 lies inside the world
+    (continuous on a map without obstacles, snapped to the tile pitch 2.0 on a map with them, so that the tiles do not overlap), then a
+    start and a goal uniform in +-0.95 of the window; the draw is accepted iff both are more than OBSTACLE_MARGIN away from the map's
+    obstacles (environments.map_sdf) and the start (the goal) is more than min_separation away from every earlier robot's start (goal),
+    measured globally.  Raises RuntimeError after max_draws draws."""
+    env_id = getattr(env_id, "__name__", env_id)
+    if not extent >= TILE_PITCH:
+        raise ValueError(f"random_world_instance: a world of side {extent} cannot hold a window of side {TILE_PITCH}")
+    rng = np.random.Generator(np.random.PCG64(seed))
+    snapped = len(MAP_BOXES[env_id.replace("ExtraObjects", "")][0]) > 0
+    tiles = int(np.floor(extent / TILE_PITCH))
+    half = np.float32((extent - TILE_PITCH) / 2.0)
+    starts, goals, offsets = (np.zeros((0, 2), np.float32) for _ in range(3))
+    draws = 0
+    while len(starts) < n_robots:
+        if draws >= max_draws:
+            raise RuntimeError(f"random_world_instance: {n_robots} robots not placed in a world of side {extent} on {env_id} after "
+                               f"{max_draws} draws (min_separation={min_separation}); {len(starts)} placed")
+        draws += 1
+        if snapped:
+            off = (rng.integers(0, tiles, (1, 2)).astype(np.float32) * np.float32(TILE_PITCH) - np.float32((tiles - 1) * TILE_PITCH / 2.0))
+        else:
+            off = (rng.random((1, 2), dtype=np.float32) * np.float32(2.0) - np.float32(1.0)) * half
+        off = off.astype(np.float32)
+        ends = (rng.random((2, 2), dtype=np.float32) * np.float32(1.9) - np.float32(0.95)).astype(np.float32)      # local start, goal
+        if snapped and not bool((map_sdf(ends, env_id) > OBSTACLE_MARGIN).all()):
+            continue
+        st, go = ends[:1] + off, ends[1:] + off
+        if len(starts) and not (np.all(np.sqrt(np.sum((st - starts) ** 2, axis=1)) > min_separation)
+                                and np.all(np.sqrt(np.sum((go - goals) ** 2, axis=1)) > min_separation)):
+            continue
+        starts, goals, offsets = np.concatenate([starts, st]), np.concatenate([goals, go]), np.concatenate([offsets, off])
+    return starts, goals, offsets

@@ -1,0 +1,210 @@
+"""-m gpu: many-robot rounds with per-robot frames (mmd_framed_constraints_from_paths; constraints.framed_constraints_from_paths;
+world.WorldRobotSampler).  The yardsticks: for the table the numpy model of world_model (pinned to mmd_pack_constraints by
+tests/test_world_host.py) and soft_constraints_from_paths; for the guided step the list form through the host pack (exact) and the
+oracle on ALL other robots' points, unculled (2e-6, the tolerance test_soft_constraints_from_paths_kernel uses for the dense table);
+for the rounds MultiRobotSampler itself and a numpy brute force of the conflict report.  Every other comparison is exact."""
+from math import ceil
+
+import numpy as np
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+from mmd_amd import _lib, synth                                                  # noqa: E402
+from mmd_amd.constraints import framed_constraints_from_paths, framed_slot_bound, soft_constraints_from_paths   # noqa: E402
+import world_model as M                                                          # noqa: E402
+from cases import H, D                                                           # noqa: E402
+
+T, B = 25, 4
+W_SOFT = 2e-2
+R = float(M.RADIUS)
+
+
+def _words(t):
+    return t.cpu().numpy().view(np.int32)
+
+
+def _framed(paths, offsets, robot0, n_local, S, window=None):
+    return framed_constraints_from_paths(torch.from_numpy(np.array(paths)).cuda(), torch.from_numpy(np.array(offsets)).cuda(), robot0,
+                                         n_local, S, R, W_SOFT, window)
+
+
+# ---- 1. the table is the model, bit for bit ---------------------------------------------------------------------------------------------
+def test_framed_table_is_the_model_bit_for_bit():
+    paths, offsets = M.edge_instance()
+    S = 3
+    want = M.framed_table(paths, offsets, 2, 3, S, M.RADIUS, W_SOFT)
+    ell, gso, gw, rgo, radius, used, dropped = _framed(paths, offsets, 2, 3, S)
+    assert radius == R and ell.shape == (3 * S, H, 4)
+    assert int(want[5].sum()) > 0 and int(want[4].max()) == S                     # drops occur
+    for got, ref in zip((ell, gso, gw, rgo, used, dropped), want):
+        assert got.dtype == torch.from_numpy(ref).dtype and np.array_equal(_words(got), ref.view(np.int32))
+    # rank shards of the same instance concatenate to the unsharded table
+    whole = _framed(paths, offsets, 0, 7, S)
+    ref = M.framed_table(paths, offsets, 0, 7, S, M.RADIUS, W_SOFT)
+    for k, m in zip((0, 1, 2, 3, 5, 6), range(6)):
+        assert np.array_equal(_words(whole[k]), ref[m].view(np.int32))
+    for splits in (((0, 4), (4, 3)), ((0, 1), (1, 5), (6, 1))):
+        parts = [_framed(paths, offsets, r0, nl, S) for r0, nl in splits]
+        for k in (0, 2, 5, 6):                                                    # ell, weights, used, dropped: rows of the robots
+            assert torch.equal(torch.cat([p[k] for p in parts]).view(torch.int32), whole[k].view(torch.int32))
+        for p, (r0, nl) in zip(parts, splits):                                   # the offsets count from the shard's first robot
+            assert p[1].tolist() == [i * S for i in range(nl + 1)] and p[3].tolist() == list(range(nl + 1))
+
+
+# ---- 2. ties to the existing all-pairs kernel -------------------------------------------------------------------------------------------
+def test_unframed_unbounded_table_is_soft_constraints_from_paths():
+    starts, goals = synth.start_goal_circle(6, 0.8)
+    paths = synth.straight_line_paths(starts, goals, H)
+    dev = torch.from_numpy(paths).cuda()
+    window = ((-1e30, -1e30), (1e30, 1e30))
+    for robot0, n_local in ((0, 6), (2, 3)):
+        ell, gso, gw, rgo, radius, used, dropped = _framed(paths, np.zeros((6, 2), np.float32), robot0, n_local, 5, window)
+        s_ell, s_gso, s_gw, s_rgo, s_radius = soft_constraints_from_paths(dev, robot0, n_local, R, W_SOFT)
+        assert torch.equal(ell[:, 1:].view(torch.int32), s_ell[:, 1:].view(torch.int32))
+        assert torch.equal(gso, s_gso) and torch.equal(gw.view(torch.int32), s_gw.view(torch.int32)) and torch.equal(rgo, s_rgo)
+        assert radius == s_radius and used.tolist() == [5] * n_local and not dropped.any()
+        assert np.array_equal(ell[:, 0].cpu().numpy(), np.tile(M.EMPTY, (n_local * 5, 1)))          # column 0 is inactive
+
+
+# ---- 3. the guided step on the framed table -----------------------------------------------------------------------------------------------
+def _two_clusters(n_a, n_b, radius=0.8):
+    """n_a robots at offset (0, 0) and n_b at (6, 0), each cluster on a circle with antipodal goals -> (starts, goals, offsets), global"""
+    offsets = np.float32([[0, 0]] * n_a + [[6, 0]] * n_b)
+    sa, ga = synth.start_goal_circle(n_a, radius)
+    sb, gb = synth.start_goal_circle(n_b, radius)
+    return (np.concatenate([sa, sb]) + offsets).astype(np.float32), (np.concatenate([ga, gb]) + offsets).astype(np.float32), offsets
+
+
+def _world(starts, goals, offsets, **kw):
+    import gpu_common as gc
+    from mmd_amd.world import WorldRobotSampler
+    kw.setdefault("n_samples", B)
+    return WorldRobotSampler(gc.hip_model(T), starts, goals, offsets, env_id="EnvEmpty2D", **kw)
+
+
+def test_guided_step_on_the_framed_table_is_the_unculled_one():
+    import cases
+    import gpu_common as gc
+    from oracle import mmd_oracle as O
+    n = 5
+    starts, goals, offsets = _two_clusters(3, 2)
+    paths = synth.straight_line_paths(starts, goals, H)
+    paths[2, :, 0] = np.float32(1.06)                      # a neighbour beyond the position limits, inside the window: it acts on clipped samples
+    paths[2, :, 1] = np.linspace(-1.1, 1.1, H, dtype=np.float32)
+    s = _world(starts, goals, offsets)
+    assert s.neighbor_slots == 2 == framed_slot_bound(offsets, 0, n, radius=R)
+    dev = torch.from_numpy(paths).cuda()
+    s.set_other_paths(dev)
+    assert s.last_used.tolist() == [2, 2, 2, 1, 1] and not s.last_dropped.any()
+    wlo, whi = M.default_window()
+    included, everyone = [], []
+    for r in range(n):
+        q, tr = M.point_list(paths, offsets, r, wlo, whi)
+        included.append([O.ConstraintGroup(q=torch.from_numpy(q), t_range=torch.tensor(tr, dtype=torch.float32),
+                                           radius=torch.full((len(tr),), R), weight=W_SOFT)])
+        local = (paths - offsets[r][None, None, :]).astype(np.float32)             # ALL other robots, the far cluster too
+        everyone.append(O.soft_constraints_from_paths(torch.from_numpy(local), r, R, W_SOFT))
+        assert len(tr) < everyone[-1].q.shape[0]
+    g_host = gc.hip_guide("EnvEmpty2D", included, n_robots=n)
+    x = (torch.from_numpy(synth.synth_noise(71, (n * B, H, D))) * 0.5).cuda()
+    x[:B, :, 0] = x[:B, :, 0].abs() * 0.2 + 0.95                                  # robot 0's samples along and beyond the x = 1 limit
+    hard = torch.stack((s.hard_conds[0], s.hard_conds[H - 1]), 1).contiguous()
+    y_framed = s.guide.guide_steps(x.clone(), hard, _lib.HARD_ROWS_START_GOAL, 2)
+    y_host = g_host.guide_steps(x.clone(), hard, _lib.HARD_ROWS_START_GOAL, 2)
+    assert torch.isfinite(y_framed).all() and torch.equal(y_framed, y_host)
+    free = gc.hip_guide("EnvEmpty2D", [[] for _ in range(n)], n_robots=n)
+    assert not torch.equal(free.guide_steps(x.clone(), hard, _lib.HARD_ROWS_START_GOAL, 2), y_framed)       # the table acts
+    noise = torch.from_numpy(synth.synth_noise(72, (n * B, H, D))).cuda()
+    steps = []
+    for g in (s.guide, g_host):
+        ys = x.clone()
+        s.model.sample_step(ys, s.hard_conds, 3, guide=g, n_guide_steps=20, t_start_guide=ceil(0.5 * T),
+                            noise_std_extra_schedule_fn=lambda t: 0.5, n_robots=n, noise=noise)
+        steps.append(ys)
+    assert torch.isfinite(steps[0]).all() and torch.equal(steps[0], steps[1])
+    # the oracle on every other robot's point, unculled: the culling loses nothing on the device
+    gp = cases.guide_params("EnvEmpty2D")
+    grad = s.guide(x)
+    worst = 0.0
+    for r in range(n):
+        ref = O.guide_grad(x[r * B:(r + 1) * B].cpu(), gp, [everyone[r]], clip_mode="always")
+        worst = max(worst, float((grad[r * B:(r + 1) * B].cpu() - ref).abs().max()))
+    print(f"framed guided step against the unculled oracle: worst abs difference {worst:.3e}")
+    assert worst < 2e-6
+    # the all-pairs form of the table (every robot in every block): the same active terms, other slots, so only the sum's rounding moves
+    g_all = gc.hip_guide("EnvEmpty2D", [[] for _ in range(n)], n_robots=n)
+    g_all.set_packed_constraints(framed_constraints_from_paths(dev, s.offsets, 0, n, n - 1, R, W_SOFT, ((-1e30, -1e30), (1e30, 1e30)))[:5])
+    assert float((g_all(x) - grad).abs().max()) < 2e-6
+    # general staging (4-tuple) and uniform-radius staging (5-tuple) agree
+    cons = framed_constraints_from_paths(dev, s.offsets, 0, n, 2, R, W_SOFT)
+    g_gen = gc.hip_guide("EnvEmpty2D", [[] for _ in range(n)], n_robots=n)
+    g_gen.set_packed_constraints(cons[:4])
+    assert torch.equal(g_gen(x), grad)
+
+
+# ---- 4. a world of one tile is MultiRobotSampler ------------------------------------------------------------------------------------------
+def test_round_with_zero_offsets_is_the_base_round():
+    import gpu_common as gc
+    from mmd_amd.multi_robot import MultiRobotSampler
+    n = 6
+    starts, goals = synth.start_goal_circle(n, 0.8)
+    zero = np.zeros((n, 2), np.float32)
+    p0 = torch.from_numpy(synth.straight_line_paths(starts, goals, H)).cuda()
+    base = MultiRobotSampler(gc.hip_model(T), starts, goals, env_id="EnvEmpty2D", n_samples=2 * B)
+    t_base, p_base = base.plan_round(p0, seed=31)
+    w = _world(starts, goals, zero, n_samples=2 * B, neighbor_slots=n - 1)
+    t_w, p_w = w.plan_round(p0, seed=31)
+    assert torch.isfinite(t_w).all() and torch.equal(t_w, t_base) and torch.equal(p_w, p_base)
+    assert w.last_used.tolist() == [n - 1] * n and not w.last_dropped.any() and torch.equal(w.last_idx, base.last_idx)
+    # rank 1 of a world of 2, played on this GPU: rows 3 - 5
+    r1 = _world(starts, goals, zero, n_samples=2 * B, neighbor_slots=n - 1, rank=1, world_size=2)
+    assert (r1.robot0, r1.n_local) == (3, 3)
+    r1.set_other_paths(p0)
+    t_r = r1.sample(seed=31)
+    assert torch.equal(t_r, t_base[3 * 2 * B:]) and torch.equal(r1.best_paths(t_r, p0), p_base[3:])
+
+
+# ---- 5. a world ----------------------------------------------------------------------------------------------------------------------------
+def test_plan_in_a_world_of_two_clusters():
+    seed = 40
+    starts, goals, offsets = _two_clusters(3, 3, 0.6)
+    res, samplers = {}, {}
+    for table in ("dense", "binned"):
+        s = samplers[table] = _world(starts, goals, offsets, constraint_table=table)
+        assert s.neighbor_slots == 2
+        res[table] = s.plan(max_rounds=2, seed=seed)
+    r, s = res["dense"], samplers["dense"]
+    assert r.n_rounds >= 1 and torch.isfinite(r.trajs).all()
+    assert int(s.last_used.max()) <= 2 and not s.last_dropped.any()
+    assert r.dropped_constraints is s.last_dropped and r.dropped_constraints.shape == (6,) and r.dropped_constraints.is_cuda
+    # the returned paths are global: each lies in its own window
+    paths = r.paths_local.cpu().numpy()
+    local = paths - offsets[:, None, :]
+    assert np.abs(local).max() <= 1.0 + 1e-6 and paths[3:, :, 0].min() > 4.9
+    # the report of the returned paths against a numpy brute force
+    count, robot_counts, first = M.conflicts(paths)
+    print(f"world of two clusters: conflicts per report {r.conflict_counts}, used max {int(s.last_used.max())}")
+    assert r.conflict_counts[-1] == count and np.array_equal(r.robot_counts.cpu().numpy(), robot_counts)
+    assert (r.first_conflict[:3] if r.first_conflict is not None else None) == first and r.conflict_free == (count == 0)
+    assert len(r.conflict_counts) == r.n_rounds + 1 and r.conflict_counts[0] == M.conflicts(synth.straight_line_paths(starts, goals, H))[0]
+    # the world collision table for the pick and the report: the same result
+    b = res["binned"]
+    assert samplers["binned"].world_limits == ((-1.0, -1.0), (7.0, 1.0)) and samplers["binned"].world_grid == (62, 15)
+    assert torch.equal(b.paths_local, r.paths_local) and torch.equal(b.trajs, r.trajs) and b.conflict_counts == r.conflict_counts
+    assert torch.equal(b.robot_counts, r.robot_counts) and b.n_rounds == r.n_rounds
+    assert (b.first_conflict is None) == (r.first_conflict is None)
+    if r.first_conflict is not None:
+        assert b.first_conflict[:3] == r.first_conflict[:3] and all(np.array_equal(u, v) for u, v in zip(b.first_conflict[3:], r.first_conflict[3:]))
+    # plan() is the loop of plan_round calls, and a cluster nobody can reach changes nothing: the first cluster alone, as robots 0 - 2
+    hand = _world(starts, goals, offsets)
+    lone = _world(starts[:3], goals[:3], offsets[:3])
+    assert lone.neighbor_slots == 2
+    p = torch.from_numpy(synth.straight_line_paths(starts, goals, H)).cuda()
+    q = p[:3].contiguous()
+    for k in range(r.n_rounds):
+        t_hand, p = hand.plan_round(p, seed=seed + k)
+        t_lone, q = lone.plan_round(q, seed=seed + k)
+        assert torch.equal(t_lone, t_hand[:3 * B]) and torch.equal(q, p[:3])
+    assert torch.equal(t_hand, r.trajs) and torch.equal(p, r.paths_local)
