@@ -583,7 +583,9 @@ int mmd_solution_stats(const float* paths_dev, int n_agents, int horizon_global,
  *     (alpha [num_interpolation] host = torch.linspace(0, 1, n + 2)[1:n+1], trajectory/utils.py:73-86) and each point
  *     is tested against the fixed-object SDF grids and workspace boundaries of `env` (only its map / boundary fields
  *     are read: limits_*, grid_*, n_grids, sdf_grids_dev, robot_map_dev, ws_*) with `margin` (= robot radius,
- *     tasks.py:251-253): waypoint_collisions_dev [n_traj][(H-1) * num_interpolation] (may be NULL);
+ *     tasks.py:251-253): waypoint_collisions_dev [n_traj][(H-1) * num_interpolation] (may be NULL); num_interpolation = 0
+ *     tests the H support points themselves, as interpolate_traj_via_points returns the trajectory then
+ *     (trajectory/utils.py:76-77): waypoint_collisions_dev [n_traj][H] (with all_free != 0 nothing is written);
  *   - free_dev[n] = 1 iff no interpolated point collides and every support point lies inside [q_min, q_max]
  *     (tasks.py:262-281); all_free != 0 skips both tests (PlanningTaskEnsemble, tasks_ensemble.py:271-277);
  *   - path_length_dev / smoothness_dev [n_traj]: sum_t ||p_{t+1} - p_t||, sum_t ||v_{t+1} - v_t||;
@@ -597,7 +599,9 @@ int mmd_postprocess_trajs(const mmd_guide_desc* env, const float* trajs_dev, int
                           void* stream);
 
 /* Per robot, the index (within its samples_per_robot samples) of the best FREE sample: with counts_dev == NULL the
- * argmin of cost_a (+ cost_b if not NULL) (torch.argmin(cost_all), mpd.py:366-370); with counts_dev the first free
+ * argmin of cost_a (+ cost_b if not NULL) (torch.argmin(cost_all), mpd.py:366-370) in torch.argmin's order: the first
+ * index wins among equal keys, and a NaN key counts as smaller than every number (the first NaN candidate is the pick; a NaN on
+ * a sample that is no candidate is ignored); with counts_dev the first free
  * sample with the fewest robot-robot collisions (CBS 'least_collisions', cbs.py:446-458).  n_free_dev[r] = number of
  * free samples; when it is 0 the pick is made over all samples instead.  summary_dev (optional, fp32 [n_traj + n_robots]): the free
  * flags as 0 / 1 followed by the picks -- laid out so that, with path_length_dev / smoothness_dev of mmd_postprocess_trajs placed right
@@ -613,10 +617,11 @@ int mmd_points_collision(const mmd_guide_desc* env, const float* points_dev, int
 
 /* LimitsNormalizer.unnormalize (mmd/datasets/normalization.py:157-168; TrajectoryDataset.unnormalize_trajectories, what MPD.__call__
  * applies to the sampled chain, mpd.py:344-347) for n_points float4 states (x, y, vx, vy): a tensor is clipped to [-1, 1] as a WHOLE iff any of
- * its elements lies outside [-1 - eps, 1 + eps] (the reference's data-dependent clip, decided on the device), then x_u = (x + 1) / 2 *
- * (maxs - mins) + mins.  One call may hold SEVERAL tensors interleaved (the chains of R planner calls batched robot-major, [steps][R][B*H]):
+ * its elements lies outside [-1 - eps, 1 + eps] (the reference's data-dependent clip, decided on the device) AND none is a NaN (with a NaN
+ * the reference's `x.max() > 1 + eps or x.min() < -1 - eps` is false: the tensor stays unclipped and no NaN ever becomes a number), then
+ * x_u = (x + 1) / 2 * (maxs - mins) + mins.  One call may hold SEVERAL tensors interleaved (the chains of R planner calls batched robot-major, [steps][R][B*H]):
  * point i belongs to tensor (i % period_points) / segment_points, each tensor gets its own clip decision; period_points = segment_points = 0
- * means one tensor.  flags_dev: period_points / segment_points uint32 of scratch.  mins / maxs: host [4].  out_dev may alias x_dev. */
+ * means one tensor.  flags_dev: period_points / segment_points uint32 of scratch (per tensor: byte 0 = out of range, byte 1 = NaN seen).  mins / maxs: host [4].  out_dev may alias x_dev. */
 int mmd_unnormalize_trajs(const float* x_dev, size_t n_points, size_t period_points, size_t segment_points, const float* mins,
                           const float* maxs, float eps, float* out_dev, uint32_t* flags_dev, void* stream);
 

@@ -119,7 +119,12 @@ __global__ __launch_bounds__(MAX_BLOCKS * 64) void postprocess_kernel(PostArgs a
 
   // interpolated points of segment p -> p+1: x_p * alpha + x_{p+1} * (1 - alpha)   (trajectory/utils.py:80-81)
   bool coll = false;
-  if (p < L - 1 && !a.all_free) {
+  if (a.n_interp == 0 && !a.all_free) {
+    // num_interpolation <= 0: interpolate_traj_via_points returns the trajectory itself (trajectory/utils.py:76-77), so the
+    // support points are the ones tested, the last included: waypoint_collisions is [n_traj][L]
+    coll = point_collides(a.env, grid, x.x, x.y, a.margin);
+    if (a.waypoint_coll) a.waypoint_coll[(size_t)traj * L + p] = coll ? 1 : 0;
+  } else if (p < L - 1 && !a.all_free) {
     for (int j = 0; j < a.n_interp; ++j) {
       const float px = x.x * a.alpha[j] + nx * a.one_minus_alpha[j];
       const float py = x.y * a.alpha[j] + ny * a.one_minus_alpha[j];
@@ -169,9 +174,18 @@ __global__ __launch_bounds__(MAX_BLOCKS * 64) void postprocess_kernel(PostArgs a
   }
 }
 
-// per robot: index of the best sample among the free ones.  counts == null: argmin of cost_a (+ cost_b) (torch.argmin:
-// first minimum); counts != null: first free sample with the fewest collisions (strict '<' scan, cbs.py:452).  When no
-// sample is free, idx = the same criterion over ALL samples and n_free = 0 (the caller decides what to do with it).
+// the order of torch.argmin over (key, index): a NaN key comes before every number, the lower index before the higher among
+// equal keys (and among NaNs).  An empty candidate (+inf, 0x7fffffff) comes after every real one.
+__device__ __forceinline__ bool pick_before(float ka, int ia, float kb, int ib) {
+  const bool na = ka != ka, nb = kb != kb;
+  if (na != nb) return na;
+  return ka < kb || ((na || ka == kb) && ia < ib);
+}
+
+// per robot: index of the best sample among the free ones.  counts == null: argmin of cost_a (+ cost_b) with torch.argmin's
+// order (first minimum; a NaN key is smaller than every number, so the first NaN among the candidates wins); counts != null:
+// first free sample with the fewest collisions (strict '<' scan, cbs.py:452).  When no sample is free, idx = the same
+// criterion over ALL samples and n_free = 0 (the caller decides what to do with it).
 __global__ __launch_bounds__(64) void select_best_kernel(const unsigned char* __restrict__ free_mask,
                                                          const float* __restrict__ cost_a, const float* __restrict__ cost_b,
                                                          const int* __restrict__ counts, int B, int* __restrict__ idx_best,
@@ -188,13 +202,13 @@ __global__ __launch_bounds__(64) void select_best_kernel(const unsigned char* __
     const size_t i = (size_t)r * B + b;
     if (nf > 0 && !free_mask[i]) continue;
     const float key = counts ? (float)counts[i] : (cost_b ? cost_a[i] + cost_b[i] : cost_a[i]);
-    if (key < best || (key == best && b < best_i) || best_i == 0x7fffffff) { best = key; best_i = b; }
+    if (pick_before(key, b, best, best_i)) { best = key; best_i = b; }
   }
 #pragma unroll
   for (int m = 32; m >= 1; m >>= 1) {
     const float ob = __shfl_xor(best, m);
     const int oi = __shfl_xor(best_i, m);
-    if (oi != 0x7fffffff && (best_i == 0x7fffffff || ob < best || (ob == best && oi < best_i))) { best = ob; best_i = oi; }
+    if (pick_before(ob, oi, best, best_i)) { best = ob; best_i = oi; }
   }
   if (lane == 0) {
     idx_best[r] = best_i == 0x7fffffff ? -1 : best_i;
@@ -240,19 +254,26 @@ __global__ __launch_bounds__(256) void variance_waypoints_kernel(const float4* _
 }
 
 // LimitsNormalizer.unnormalize (mmd/datasets/normalization.py:157-168) of a whole chain on the device, with the reference's
-// data-dependent clip -- the WHOLE tensor is clipped to [-1, 1] iff ANY element lies outside [-1 - eps, 1 + eps] -- decided by a
-// reduction kernel into a device flag (no host round trip: the torch form `if x.max() > 1 + eps or x.min() < -1 - eps` costs two
-// reductions and two synchronisations per planner call), then x_u = (x + 1) / 2 * (max - min) + min with torch's separate
-// roundings (no FMA contraction: this file is compiled with fp contract off).
+// data-dependent clip -- the WHOLE tensor is clipped to [-1, 1] iff `x.max() > 1 + eps or x.min() < -1 - eps` -- decided by a
+// reduction kernel into a device flag (no host round trip: the torch form costs two reductions and two synchronisations per
+// planner call), then x_u = (x + 1) / 2 * (max - min) + min with torch's separate roundings (no FMA contraction: this file is
+// compiled with fp contract off).  A NaN anywhere in the tensor makes x.max() and x.min() NaN and both comparisons false: such a
+// tensor is NOT clipped, whatever else it holds, and its NaNs stay NaNs.  The flag word of a tensor therefore carries two
+// facts in two of its bytes: FLAG_OUT = an element out of range, FLAG_NAN = a NaN seen; clip iff the first and not the second.
+constexpr int FLAG_OUT = 0, FLAG_NAN = 1;                     // byte of the little-endian flag word
 __global__ __launch_bounds__(256) void range_flag_kernel(const float4* __restrict__ x, size_t n, size_t period, size_t segment, float eps,
                                                          uint32_t* __restrict__ flags) {
   const float hi = 1.f + eps, lo = -1.f - eps;
+  unsigned char* fb = reinterpret_cast<unsigned char*>(flags);
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
     const float4 v = x[i];
     const bool out = v.x > hi || v.y > hi || v.z > hi || v.w > hi || v.x < lo || v.y < lo || v.z < lo || v.w < lo;
-    // a relaxed store (a plain global_store) of the one value a flag ever takes (a wave's lanes with the same flag coalesce into one write; an atomic per element
+    const bool has_nan = v.x != v.x || v.y != v.y || v.z != v.z || v.w != v.w;
+    // relaxed byte stores (plain global_store_byte) of the one value a flag byte ever takes (a wave's lanes with the same flag coalesce into one write; an atomic per element
     // serialises on a DDPM chain, whose x_T rows are a third out of range: +0.35 ms per planner call, measured)
-    if (out) __hip_atomic_store(flags + (i % period) / segment, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    unsigned char* f = fb + 4 * ((i % period) / segment);
+    if (out) __hip_atomic_store(f + FLAG_OUT, (unsigned char)1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (has_nan) __hip_atomic_store(f + FLAG_NAN, (unsigned char)1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
 }
 struct UnnormArgs { float mins[4], range[4]; };
@@ -260,9 +281,10 @@ __global__ __launch_bounds__(256) void unnormalize_kernel(const float4* __restri
                                                           size_t segment, UnnormArgs a, const uint32_t* __restrict__ flags) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const bool clip = flags[(i % period) / segment] != 0u;
+  const uint32_t w = flags[(i % period) / segment];
+  const bool clip = ((w >> (8 * FLAG_OUT)) & 0xffu) != 0u && ((w >> (8 * FLAG_NAN)) & 0xffu) == 0u;
   auto f = [&](float v, int d) {
-    if (clip) v = fminf(fmaxf(v, -1.f), 1.f);                // torch.clip(x, -1, 1)
+    if (clip) v = fminf(fmaxf(v, -1.f), 1.f);                // torch.clip(x, -1, 1); no NaN reaches this line
     v = (v + 1.f) / 2.f;
     return v * a.range[d] + a.mins[d];
   };

@@ -70,8 +70,9 @@ def postprocess_batch(guide, trajs, n_robots=1, num_interpolation=5, margin=ROBO
         r.path_length = torch.empty(n, dtype=torch.float32, device=dev)
         r.smoothness = torch.empty(n, dtype=torch.float32, device=dev)
     r.smoothed = torch.empty_like(trajs) if smooth else None
-    r.waypoint_collisions = (torch.empty((n, (h - 1) * num_interpolation), dtype=torch.uint8, device=dev)
-                             if want_waypoints else None)
+    # num_interpolation = 0 tests the support points themselves (trajectory/utils.py:76-77): [n, h]
+    n_wp = h if num_interpolation == 0 and not all_free else (h - 1) * num_interpolation
+    r.waypoint_collisions = torch.empty((n, n_wp), dtype=torch.uint8, device=dev) if want_waypoints else None
     alpha = interpolation_alphas(num_interpolation)
     sav = _savgol_dev(h, dev, window_size, poly_order) if smooth else None
     fp = C.POINTER(C.c_float)
