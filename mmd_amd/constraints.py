@@ -162,6 +162,25 @@ def pack_constraints(per_robot_groups: Sequence[Sequence[Tuple[CostConstraint, f
     return out
 
 
+def group_tensors(n_slots, n_groups, n_robots, device):
+    """(ell [n_slots, H, 4] float32, grp_slot_off [n_groups + 1] int32, grp_weight [n_groups] float32, robot_grp_off [n_robots + 1] int32),
+    unwritten, on `device`: the four tensors of an ELL table that a device builder (csrc/cons_tables.hip, mmd_path_constraints) fills."""
+    return (torch.empty((n_slots, H, 4), dtype=torch.float32, device=device), torch.empty(n_groups + 1, dtype=torch.int32, device=device),
+            torch.empty(n_groups, dtype=torch.float32, device=device), torch.empty(n_robots + 1, dtype=torch.int32, device=device))
+
+
+def _check_paths(paths, who, n_all=None):
+    """Raise unless paths is [N, H, 2] (N = n_all where given)"""
+    if paths.dim() != 3 or tuple(paths.shape[1:]) != (H, 2) or (n_all is not None and paths.shape[0] != n_all):
+        raise ValueError(f"{who}: paths [{'N' if n_all is None else n_all}, {H}, 2], got {tuple(paths.shape)}")
+
+
+def _check_robot_range(who, n_all, robot0, n_local):
+    """Raise unless [robot0, robot0 + n_local) is a non-empty range of n_all >= 2 robots (check_robot_range, csrc/cons_table_dev.h)"""
+    if not (n_all >= 2 and n_local >= 1 and robot0 >= 0 and robot0 + n_local <= n_all):
+        raise ValueError(f"{who}: bad robot range")
+
+
 def soft_constraints_from_paths(paths: torch.Tensor, robot0: int, n_local: int, radius=VERTEX_CONSTRAINT_RADIUS,
                                 weight=2e-2):
     """Device-side all-pairs soft constraints (replaces cbs.py:468-508 for equal start times).  paths [N,H,2]
@@ -169,18 +188,14 @@ def soft_constraints_from_paths(paths: torch.Tensor, robot0: int, n_local: int, 
     robots [robot0, robot0+n_local)."""
     lib = _lib.load()
     n_all = paths.shape[0]
-    dev = paths.device
-    ell = torch.empty((n_local * (n_all - 1), H, 4), dtype=torch.float32, device=dev)
-    gso = torch.empty(n_local + 1, dtype=torch.int32, device=dev)
-    gw = torch.empty(n_local, dtype=torch.float32, device=dev)
-    rgo = torch.empty(n_local + 1, dtype=torch.int32, device=dev)
+    ell, gso, gw, rgo = group_tensors(n_local * (n_all - 1), n_local, n_local, paths.device)
     _lib.launch("mmd_soft_constraints_from_paths", paths, _lib.require_gpu(paths, "paths"), n_all, robot0, n_local, H,
                                                    float(radius), float(weight), ell.data_ptr(), gso.data_ptr(),
                                                    gw.data_ptr(), rgo.data_ptr())
     return ell, gso, gw, rgo, float(radius)
 
 
-FRAME_WINDOW_SLACK = 1.0625      # a robot's window is the position limits widened by (1 + 1/16) x the radius (csrc/multi_agent.hip)
+FRAME_WINDOW_SLACK = 1.0625      # a robot's window is the position limits widened by (1 + 1/16) x the radius (csrc/cons_tables.hip)
 
 
 def framed_window(limits, radius):
@@ -194,10 +209,7 @@ def framed_constraints_table(paths, offsets, robot0, n_local, slots, radius, wei
     """mmd_framed_constraints_from_paths on checked tensors -> (ell, grp_slot_off, grp_weight, robot_grp_off, used, dropped).  One launch
     on the current stream, no host synchronisation."""
     n_all, dev = paths.shape[0], paths.device
-    ell = torch.empty((n_local * slots, H, 4), dtype=torch.float32, device=dev)
-    gso = torch.empty(n_local + 1, dtype=torch.int32, device=dev)
-    gw = torch.empty(n_local, dtype=torch.float32, device=dev)
-    rgo = torch.empty(n_local + 1, dtype=torch.int32, device=dev)
+    ell, gso, gw, rgo = group_tensors(n_local * slots, n_local, n_local, dev)
     used = torch.empty(n_local, dtype=torch.int32, device=dev)
     dropped = torch.empty(n_local, dtype=torch.int32, device=dev)
     lo, hi = (C.c_float * 2)(*[float(v) for v in window[0]]), (C.c_float * 2)(*[float(v) for v in window[1]])
@@ -217,13 +229,11 @@ def framed_constraints_from_paths(paths: torch.Tensor, offsets: torch.Tensor, ro
     come within `radius` of a clipped trajectory).  -> (ell, grp_slot_off, grp_weight, robot_grp_off, radius) as set_packed_constraints
     takes them, then used int32 [n_local] (the most slots a robot filled at one time step) and dropped int32 [n_local] (included points
     that found the block full; 0 at slots = framed_slot_bound while every path stays in its own window), both on the device."""
-    if paths.dim() != 3 or paths.shape[1] != H or paths.shape[2] != 2:
-        raise ValueError(f"framed_constraints_from_paths: paths [N, {H}, 2], got {tuple(paths.shape)}")
+    _check_paths(paths, "framed_constraints_from_paths")
     n_all = paths.shape[0]
     if tuple(offsets.shape) != (n_all, 2):
         raise ValueError(f"framed_constraints_from_paths: offsets [{n_all}, 2], got {tuple(offsets.shape)}")
-    if not (n_all >= 2 and n_local >= 1 and robot0 >= 0 and robot0 + n_local <= n_all):
-        raise ValueError("framed_constraints_from_paths: bad robot range")
+    _check_robot_range("framed_constraints_from_paths", n_all, robot0, n_local)
     if not 1 <= int(slots) <= n_all - 1:
         raise ValueError(f"framed_constraints_from_paths: slots must be in [1, {n_all - 1}], got {slots}")
     if window is None:
@@ -244,8 +254,7 @@ def framed_slot_bound(offsets, robot0, n_local, limits=None, radius=VERTEX_CONST
         limits = LIMITS
     off = np.asarray(torch.as_tensor(offsets).detach().cpu().numpy(), dtype=np.float64).reshape(-1, 2)
     n = off.shape[0]
-    if not (n >= 2 and n_local >= 1 and robot0 >= 0 and robot0 + n_local <= n):
-        raise ValueError("framed_slot_bound: bad robot range")
+    _check_robot_range("framed_slot_bound", n, robot0, n_local)
     wlo, whi = (np.asarray(v, dtype=np.float64) for v in framed_window(limits, radius))
     lo, hi = np.asarray(limits[0], dtype=np.float64), np.asarray(limits[1], dtype=np.float64)
     eps = 4.0 * float(np.finfo(np.float32).eps) * (np.abs(off).max() + max(np.abs(wlo).max(), np.abs(whi).max()))
@@ -256,7 +265,7 @@ def framed_slot_bound(offsets, robot0, n_local, limits=None, radius=VERTEX_CONST
     return min(max(worst, 1), n - 1)
 
 
-BIN_CELL_SLACK = 1.0625          # a cell side is at least (1 + 1/16) x the radius (csrc/guide.hip: the cover argument above bin_cell)
+BIN_CELL_SLACK = 1.0625          # a cell side is at least (1 + 1/16) x the radius (csrc/guide.hip: COVER; the build is csrc/cons_tables.hip)
 BIN_MAX_CELLS = 32               # per axis, of the default grid
 
 
@@ -346,10 +355,8 @@ def binned_constraints_from_paths(paths: torch.Tensor, robot0: int, n_local: int
         from .environments import LIMITS
         limits = LIMITS
     n_all = paths.shape[0]
-    if paths.dim() != 3 or paths.shape[1] != H or paths.shape[2] != 2:
-        raise ValueError(f"binned_constraints_from_paths: paths [N, {H}, 2], got {tuple(paths.shape)}")
-    if not (n_all >= 2 and n_local >= 1 and robot0 >= 0 and robot0 + n_local <= n_all):
-        raise ValueError("binned_constraints_from_paths: bad robot range")
+    _check_paths(paths, "binned_constraints_from_paths")
+    _check_robot_range("binned_constraints_from_paths", n_all, robot0, n_local)
     grid = bin_grid(limits, radius) if grid is None else tuple(int(v) for v in grid)
     check_bin_grid(limits, radius, grid)
     if int(first_step) not in (0, 1):
@@ -380,8 +387,7 @@ class RoundConstraints:
     def __init__(self, n_all, robot0, n_local, hard_slots=32, radius=VERTEX_CONSTRAINT_RADIUS, w_hard=2e-1, w_soft=2e-2,
                  hard_radius=None, device="cuda"):
         self.n_all, self.robot0, self.n_local, self.hard_slots = int(n_all), int(robot0), int(n_local), int(hard_slots)
-        if not (self.n_all >= 2 and self.n_local >= 1 and self.robot0 >= 0 and self.robot0 + self.n_local <= self.n_all):
-            raise ValueError("RoundConstraints: bad robot range")
+        _check_robot_range("RoundConstraints", self.n_all, self.robot0, self.n_local)
         if self.hard_slots < 1:
             raise ValueError(f"RoundConstraints: hard_slots must be at least 1, got {hard_slots}")
         self.radius = float(radius)
@@ -389,10 +395,7 @@ class RoundConstraints:
         self.w_hard, self.w_soft = float(w_hard), float(w_soft)
         self.slots_per_robot = self.hard_slots + self.n_all - 1
         dev = torch.device(device)
-        self.ell = torch.empty((self.n_local * self.slots_per_robot, H, 4), dtype=torch.float32, device=dev)
-        self.gso = torch.empty(2 * self.n_local + 1, dtype=torch.int32, device=dev)
-        self.gw = torch.empty(2 * self.n_local, dtype=torch.float32, device=dev)
-        self.rgo = torch.empty(self.n_local + 1, dtype=torch.int32, device=dev)
+        self.ell, self.gso, self.gw, self.rgo = group_tensors(self.n_local * self.slots_per_robot, 2 * self.n_local, self.n_local, dev)
         self.fill = torch.empty((self.n_local, H), dtype=torch.int32, device=dev)
         self.dropped = torch.empty(self.n_local, dtype=torch.int32, device=dev)
         self.reset()
@@ -404,8 +407,7 @@ class RoundConstraints:
                     self.dropped.data_ptr())
 
     def _paths(self, paths_all, what):
-        if paths_all.dim() != 3 or tuple(paths_all.shape) != (self.n_all, H, 2):
-            raise ValueError(f"RoundConstraints.{what}: paths [{self.n_all}, {H}, 2], got {tuple(paths_all.shape)}")
+        _check_paths(paths_all, f"RoundConstraints.{what}", self.n_all)
         return _lib.require_gpu(paths_all.contiguous(), "paths_all")
 
     def set_soft(self, paths_all):

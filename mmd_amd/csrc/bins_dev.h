@@ -1,5 +1,5 @@
-// The cell lookup of a cell table (include/mmd_amd.h: mmd_cons_bins), shared by the kernel that builds the table, the guided step that
-// walks it (guide.hip) and the collision kernels that walk it (multi_agent.hip): one text, so every walker looks where the builder put.
+// The cell lookup of a cell table (include/mmd_amd.h: mmd_cons_bins), shared by the kernel that builds the table (cons_tables.hip) and the
+// kernels that walk it (guide.hip, multi_agent.hip, cons_tables.hip): one text, so every walker looks where the builder put.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -24,7 +24,9 @@ __device__ __forceinline__ CellList own_cell_list(const mmd_cons_bins& b, int t,
   return CellList{reinterpret_cast<const float4*>(b.entries_dev) + (size_t)t * 9 * b.n_all, off[0], off[1]};
 }
 
-// a cell table as a kernel may walk it: every field but the two device arrays' contents (guide.hip)
+// a cell table as a kernel may walk it: every field but the two device arrays' contents (cons_tables.hip)
 int check_cons_bins(const mmd_cons_bins* b);
+// ... and as a kernel may take collision decisions at `margin` on it (COVER, multi_agent.hip); `who`: the entry point, for the error text
+int check_collision_bins(const char* who, const mmd_cons_bins* bins, float margin);
 
 }  // namespace mmd

@@ -1,4 +1,4 @@
-// The one fp32 form of the robot-robot collision decision, shared by every kernel that makes it (multi_agent.hip, trial_stats.hip).
+// The one fp32 form of the robot-robot collision decision, shared by every kernel that makes it (multi_agent.hip, trial_stats.hip, cons_tables.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -13,12 +13,8 @@
 // the NORMALISED one (sample_functions.py:104), as the reference does.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
 #include <atomic>
 #include <cmath>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
 
 #include "../../include/mmd_amd.h"
 #include "../../include/mmd_amd_debug.h"
@@ -508,7 +504,7 @@ __global__ __launch_bounds__(256) void ddpm_guide_coop_kernel(GuideDev g, StepDe
 //
 // Cell index of a coordinate, per axis, in fp32: clamp(floor((p - lo) * inv_cell), 0, n - 1).  (Clamped as a float and then converted:
 // the same integer as clamp((int)floorf(..), 0, n - 1) wherever that conversion is defined, and defined for every p.)  Not contracted:
-// there is no add behind the product.  The build kernel and the step kernel run this one function.
+// there is no add behind the product.  The build kernel (cons_tables.hip: bin_cons_kernel) and the step kernel run this one function.
 //
 // COVER: a lane at p needs every table point q that cons_term accepts, i.e. with fma(dx, dx, dy * dy) <= R|R| in fp32, and it reads the
 // list of its own cell, which holds the points of the 3 x 3 cells around it: so |cell(p) - cell(q)| <= 1 per axis must hold for every
@@ -642,100 +638,6 @@ __global__ void cross_condition_kernel(float4* __restrict__ x1, float4* __restri
   if (c2) c2[(size_t)b * H + ind2] = w;
 }
 
-// all-pairs soft constraints from best paths (cbs.py:468-508): slot j of local robot i = other robot j (+1 past i)
-__global__ void soft_cons_kernel(const float2* __restrict__ paths, int n_all, int robot0, int n_local, float radius,
-                                 float weight, float4* __restrict__ ell, int* __restrict__ grp_slot_off,
-                                 float* __restrict__ grp_weight, int* __restrict__ robot_grp_off) {
-  const int slots = n_all - 1;
-  const size_t tot = (size_t)n_local * slots * H;
-  for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < tot; idx += (size_t)gridDim.x * blockDim.x) {
-    const int t = idx % H;
-    const int j = (idx / H) % slots;
-    const int i = idx / ((size_t)H * slots);
-    const int other = j + (j >= robot0 + i ? 1 : 0);
-    const float2 p = paths[(size_t)other * H + t];
-    const float r = t >= 1 ? radius : -1.f;                               // constraints cover t in [1, H-1]
-    ell[idx] = make_float4(p.x, p.y, r, r * fabsf(r));
-  }
-  const int tid = blockIdx.x * blockDim.x + threadIdx.x;
-  if (tid <= n_local) {
-    grp_slot_off[tid] = tid * slots;
-    robot_grp_off[tid] = tid;
-    if (tid < n_local) grp_weight[tid] = weight;
-  }
-}
-
-// The cell table of mmd_cons_bins from the best paths: ONE workgroup per time step t, no atomics, so a list is in ascending robot id by
-// construction.  The step's n_all points and cell indices (ix << 16 | iy) are staged in LDS; thread i owns the cells [i cpt, (i + 1) cpt)
-// (cell = ix * ny + iy) and walks the robots 0 .. n_all - 1 in order twice: to count its cells' entries and, after the block's prefix
-// sum, to write them.  A robot is in the lists of the (at most nine) cells within one index of its own, so a time step's lists fit its
-// segment of 9 n_all entries.  Time steps below first_step get empty lists: a constraint table starts at 1 (time step 0 has no
-// constraint, soft_cons_kernel: t in [1, H - 1]), a collision table (mmd_bin_paths) at 0.
-constexpr int BIN_THREADS = 256;
-__global__ __launch_bounds__(BIN_THREADS) void bin_cons_kernel(const float2* __restrict__ paths, int n_all, float lo0, float lo1, float inv0,
-                                                               float inv1, int nx, int ny, int first_step, int* __restrict__ cell_off,
-                                                               float4* __restrict__ entries) {
-  extern __shared__ __attribute__((aligned(16))) float2 lds_pts[];       // [n_all] points, [n_all] cells, [BIN_THREADS] scan
-  int* const lds_cell = reinterpret_cast<int*>(lds_pts + n_all);
-  int* const scan = lds_cell + n_all;
-  const int t = blockIdx.x, tid = threadIdx.x, ncell = nx * ny;
-  int* const off = cell_off + (size_t)t * (ncell + 1);
-  if (t < first_step) {
-    for (int c = tid; c <= ncell; c += BIN_THREADS) off[c] = 0;
-    return;
-  }
-  for (int r = tid; r < n_all; r += BIN_THREADS) {
-    const float2 p = paths[(size_t)r * H + t];
-    lds_pts[r] = p;
-    lds_cell[r] = bin_cell(p.x, lo0, inv0, nx) << 16 | bin_cell(p.y, lo1, inv1, ny);
-  }
-  __syncthreads();
-  const int cpt = (ncell + BIN_THREADS - 1) / BIN_THREADS;
-  const int c0 = min(tid * cpt, ncell), c1 = min(c0 + cpt, ncell);
-  auto near = [&](int rc, int ix, int iy) { return abs((rc >> 16) - ix) <= 1 && abs((rc & 0xffff) - iy) <= 1; };
-  int cnt = 0;
-  for (int c = c0; c < c1; ++c) {
-    const int ix = c / ny, iy = c - ix * ny;
-    for (int r = 0; r < n_all; ++r) cnt += near(lds_cell[r], ix, iy) ? 1 : 0;
-  }
-  scan[tid] = cnt;
-  __syncthreads();
-  for (int d = 1; d < BIN_THREADS; d <<= 1) {                            // inclusive prefix sum over the threads
-    const int add = tid >= d ? scan[tid - d] : 0;
-    __syncthreads();
-    scan[tid] += add;
-    __syncthreads();
-  }
-  int pos = scan[tid] - cnt;
-  float4* const seg = entries + (size_t)t * 9 * n_all;
-  for (int c = c0; c < c1; ++c) {
-    const int ix = c / ny, iy = c - ix * ny;
-    off[c] = pos;
-    for (int r = 0; r < n_all; ++r)
-      if (near(lds_cell[r], ix, iy)) {
-        const float2 p = lds_pts[r];
-        seg[pos++] = make_float4(p.x, p.y, __builtin_bit_cast(float, r), 0.f);
-      }
-  }
-  if (tid == BIN_THREADS - 1) off[ncell] = scan[tid];
-}
-
-constexpr int BIN_MAX_ROBOTS = 4096;     // 12 B of LDS per robot in bin_cons_kernel
-constexpr int BIN_MAX_CELLS = 64;        // per axis
-
-// a cell table as a guided step or a collision kernel may use it (every field but the two device arrays' contents)
-int check_cons_bins(const mmd_cons_bins* b) {
-  MMD_REQUIRE(b->cell_off_dev && b->entries_dev, "cons_bins: NULL table");
-  MMD_REQUIRE(b->nx >= 1 && b->nx <= BIN_MAX_CELLS && b->ny >= 1 && b->ny <= BIN_MAX_CELLS, "cons_bins: grid %d x %d outside [1, %d]", b->nx,
-              b->ny, BIN_MAX_CELLS);
-  MMD_REQUIRE(b->n_all >= 2 && b->robot0 >= 0 && b->robot0 < b->n_all, "cons_bins: bad robot range");
-  MMD_REQUIRE(b->radius > 0.f, "cons_bins: radius must be positive");
-  for (int k = 0; k < 2; ++k)
-    MMD_REQUIRE(b->inv_cell[k] > 0.f && 1.0 / (double)b->inv_cell[k] >= 1.0625 * (double)b->radius * (1.0 - 1e-6),
-                "cons_bins: cells smaller than (1 + 1/16) x the radius");
-  return 0;
-}
-
 int fill_guide(const mmd_guide_desc* d, GuideDev& g) {
   MMD_REQUIRE(d->n_grids == 0 || (d->sdf_grids_dev && d->grid_nx >= 1 && d->grid_ny >= 1), "guide: SDF grid missing");
   if (d->cons_bins) {
@@ -848,103 +750,6 @@ int launch_init(float* x, float* chain, const float* hard, unsigned long long ha
 using namespace mmd;
 
 extern "C" {
-
-int mmd_pack_constraints(int n_groups, const int32_t* n_pts, const float* const* q, const float* const* t_range,
-                         const float* const* radius, int horizon, float* ell_out, int max_slots, int32_t* slots_out) {
-  MMD_REQUIRE(horizon == H, "mmd_pack_constraints: horizon must be %d", H);
-  int used = 0;
-  for (int g = 0; g < n_groups; ++g) {
-    // a point is active at integer t iff t >= t0 and t < t1 (float ranges, cost_functions.py:304-305)
-    std::vector<int> fill(H, 0);
-    for (int c = 0; c < n_pts[g]; ++c) {
-      const int t0 = (int)ceilf(t_range[g][2 * c]), t1 = (int)ceilf(t_range[g][2 * c + 1]);
-      for (int t = t0 < 0 ? 0 : t0; t < t1 && t < H; ++t) ++fill[t];
-    }
-    int slots = 0;
-    for (int t = 0; t < H; ++t) slots = fill[t] > slots ? fill[t] : slots;
-    slots_out[g] = slots;
-    if (!ell_out) { used += slots; continue; }      // sizing pass
-    MMD_REQUIRE(used + slots <= max_slots, "mmd_pack_constraints: need more than %d slots", max_slots);
-    for (int s = 0; s < slots; ++s)
-      for (int t = 0; t < H; ++t) {
-        float* e = ell_out + ((size_t)(used + s) * H + t) * 4;
-        e[0] = 0.f; e[1] = 0.f; e[2] = -1.f; e[3] = -1.f;
-      }
-    std::fill(fill.begin(), fill.end(), 0);
-    for (int c = 0; c < n_pts[g]; ++c) {
-      const int t0 = (int)ceilf(t_range[g][2 * c]), t1 = (int)ceilf(t_range[g][2 * c + 1]);
-      for (int t = t0 < 0 ? 0 : t0; t < t1 && t < H; ++t) {
-        float* e = ell_out + ((size_t)(used + fill[t]) * H + t) * 4;
-        e[0] = q[g][2 * c]; e[1] = q[g][2 * c + 1]; e[2] = radius[g][c];
-        e[3] = radius[g][c] * fabsf(radius[g][c]);
-        ++fill[t];
-      }
-    }
-    used += slots;
-  }
-  return 0;
-}
-
-int mmd_soft_constraints_from_paths(const float* paths_dev, int n_all, int robot0, int n_local, int horizon,
-                                    float radius, float weight, float* ell_out_dev, int32_t* grp_slot_off_dev,
-                                    float* grp_weight_dev, int32_t* robot_grp_off_dev, void* stream) {
-  MMD_REQUIRE(horizon == H, "horizon must be %d", H);
-  MMD_REQUIRE(n_all >= 2 && n_local >= 1 && robot0 >= 0 && robot0 + n_local <= n_all, "bad robot range");
-  const size_t tot = (size_t)n_local * (n_all - 1) * H;
-  int grid = (int)((tot + 255) / 256);
-  if (grid > 2048) grid = 2048;
-  if (grid * 256 < n_local + 1) grid = (n_local + 1 + 255) / 256;
-  hipLaunchKernelGGL(soft_cons_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const float2*)paths_dev, n_all,
-                     robot0, n_local, radius, weight, (float4*)ell_out_dev, grp_slot_off_dev, grp_weight_dev,
-                     robot_grp_off_dev);
-  MMD_HIP_CHECK(hipGetLastError());
-  return 0;
-}
-
-size_t mmd_cons_bins_bytes(int n_all, int nx, int ny, size_t* off_bytes, size_t* entry_bytes) {
-  const bool ok = n_all >= 0 && nx >= 1 && ny >= 1;
-  const size_t ob = ok ? (size_t)H * ((size_t)nx * ny + 1) * sizeof(int32_t) : 0;
-  const size_t eb = ok ? (size_t)H * 9 * n_all * 4 * sizeof(float) : 0;
-  if (off_bytes) *off_bytes = ob;
-  if (entry_bytes) *entry_bytes = eb;
-  return ob + eb;
-}
-
-// the table build behind mmd_bin_constraints_from_paths (first_step = 1) and mmd_bin_paths; `who` names the entry point in the error text
-static int bin_paths(const char* who, const float* paths_dev, int n_all, int horizon, float radius, const float lo[2], const float hi[2],
-                     int nx, int ny, int first_step, int32_t* cell_off_dev, float* entries_dev, void* stream) {
-  MMD_REQUIRE(paths_dev && lo && hi && cell_off_dev && entries_dev, "%s: NULL argument", who);
-  MMD_REQUIRE(horizon == H, "%s: horizon must be %d", who, H);
-  MMD_REQUIRE(first_step == 0 || first_step == 1, "%s: first_step must be 0 or 1, got %d", who, first_step);
-  MMD_REQUIRE(n_all >= 2 && n_all <= BIN_MAX_ROBOTS, "%s: n_all must be in [2, %d]", who, BIN_MAX_ROBOTS);
-  MMD_REQUIRE(radius > 0.f, "%s: radius must be positive", who);
-  MMD_REQUIRE(nx >= 1 && nx <= BIN_MAX_CELLS && ny >= 1 && ny <= BIN_MAX_CELLS, "%s: grid %d x %d outside [1, %d]", who, nx, ny,
-              BIN_MAX_CELLS);
-  const int n[2] = {nx, ny};
-  float inv[2];
-  for (int k = 0; k < 2; ++k) {
-    MMD_REQUIRE(hi[k] > lo[k], "%s: empty limits", who);
-    // the cover argument above bin_cell needs (1 + 1/16) R <= the cell side
-    MMD_REQUIRE(((double)hi[k] - (double)lo[k]) / n[k] >= 1.0625 * (double)radius,
-                "%s: cells smaller than (1 + 1/16) x the radius (axis %d: %g < %g)", who, k, ((double)hi[k] - (double)lo[k]) / n[k],
-                1.0625 * (double)radius);
-    inv[k] = (float)n[k] / (hi[k] - lo[k]);                  // mmd_cons_bins.inv_cell: this fp32 quotient
-  }
-  hipLaunchKernelGGL(bin_cons_kernel, dim3(H), dim3(BIN_THREADS), (size_t)n_all * 12 + BIN_THREADS * sizeof(int), (hipStream_t)stream,
-                     (const float2*)paths_dev, n_all, lo[0], lo[1], inv[0], inv[1], nx, ny, first_step, cell_off_dev, (float4*)entries_dev);
-  MMD_HIP_CHECK(hipGetLastError());
-  return 0;
-}
-
-int mmd_bin_constraints_from_paths(const float* paths_dev, int n_all, int horizon, float radius, const float lo[2], const float hi[2],
-                                   int nx, int ny, int32_t* cell_off_dev, float* entries_dev, void* stream) {
-  return bin_paths("mmd_bin_constraints_from_paths", paths_dev, n_all, horizon, radius, lo, hi, nx, ny, 1, cell_off_dev, entries_dev, stream);
-}
-
-int mmd_bin_paths(const float* paths_dev, int n_all, int horizon, float reach, const float lo[2], const float hi[2], int nx, int ny,
-                  int first_step, int32_t* cell_off_dev, float* entries_dev, void* stream) {
-  return bin_paths("mmd_bin_paths", paths_dev, n_all, horizon, reach, lo, hi, nx, ny, first_step, cell_off_dev, entries_dev, stream);
-}
 
 int mmd_guide_steps(const mmd_guide_desc* d, float* x_dev, const float* hard_dev, uint64_t hard_rows, int n_robots,
                     int samples_per_robot, int n_steps, float* chain_dev, void* stream) {

@@ -1,4 +1,4 @@
-// Device-side parameter blocks of the guide / DDPM-step kernel, shared by guide.hip and api.hip.
+// Device-side parameter blocks of the guide / DDPM-step kernel, shared by guide.hip, api.hip and postprocess.hip (its tables: cons_tables.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 

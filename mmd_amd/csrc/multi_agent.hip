@@ -13,22 +13,19 @@
 //   * the same pick and the conflict report of a round's best paths on a CELL table of those paths (include/mmd_amd.h: mmd_cons_bins,
 //     built by mmd_bin_paths with first_step = 0): a point meets only the robots in the list of its own cell, so a round of N robots
 //     costs O(N x list length) where the kernels above walk all N (or all N^2 pairs);
-//   * the round table of a many-robot round that repairs its conflicts: per local robot the hard points of the conflicts seen so far
-//     (convert_conflicts_to_constraints, mmd/common/conflict_conversion.py:41-55; CBS passes them in front of the soft group,
-//     cbs.py:407-413), appended round after round from the same cell table, and behind them the soft all-pairs group;
 //   * which robots a round re-plans (mmd_round_select): the robots in conflict, or an independent set of the conflict graph found by
 //     priority propagation on the same cell table -- CBS re-plans one agent of a conflict against the others' fixed paths (cbs.py:316-324);
-//     a round does that for every robot of the set at once -- and the stable partition that makes the selected robots a prefix;
-//   * the framed all-pairs table of a round in a world larger than one tile (mmd_framed_constraints_from_paths): every robot plans in
-//     the model's tile frame at its own offset, and its table keeps the other robots' global points that fall into its window.
+//     a round does that for every robot of the set at once -- and the stable partition that makes the selected robots a prefix.
+// The guided step's other tables are built in cons_tables.hip: only mmd_path_constraints is here, with the mmd_agent_path states it reads.
 #include <hip/hip_runtime.h>
 
 #include <climits>
 
 #include "../../include/mmd_amd.h"
-#include "bins_dev.h"             // own_cell_list / check_cons_bins: the cell table of guide.hip
+#include "bins_dev.h"             // own_cell_list / check_collision_bins: the cell table built in cons_tables.hip
 #include "collision_dev.h"        // torch_norm2 / rr_hit: the pinned fp32 form of the collision decision (sets fp contract(off))
 #include "common.h"
+#include "cons_table_dev.h"       // slot_word / empty_word / one_group_per_robot / check_robot_range: what every ELL table builder shares
 #include "wave_dev.h"             // wave_sum / block_sum / block_prefix / block_prefix_count
 
 namespace mmd {
@@ -341,11 +338,7 @@ __global__ void path_constraints_kernel(const mmd_agent_path* __restrict__ agent
                                         int hard, int horizon, float radius, float weight, int n_slots, float4* __restrict__ ell,
                                         int* __restrict__ grp_slot_off, float* __restrict__ grp_weight, int* __restrict__ robot_grp_off) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t == 0 && grp_slot_off) {                   // one group of n_slots slots for one robot
-    grp_slot_off[0] = 0; grp_slot_off[1] = n_slots;
-    grp_weight[0] = weight;
-    robot_grp_off[0] = 0; robot_grp_off[1] = 1;
-  }
+  if (t == 0 && grp_slot_off) one_group_per_robot(0, 1, n_slots, weight, grp_slot_off, grp_weight, robot_grp_off);
   if (t >= horizon) return;
   int fill = 0;
   // soft: range (t, t + 1); hard: clamped to (max(0, min(t, H-1)), min(H-1, t + 1)), i.e. active only for t <= H - 2
@@ -358,167 +351,11 @@ __global__ void path_constraints_kernel(const mmd_agent_path* __restrict__ agent
       const int last = self_last >= 0 ? self_last : o.length - 1;
       if (tj < 0 || tj > o.length - 1 || t > last) continue;
       const float2 p = sample_pos(o.batch_dev, o.index, o.length, tj);
-      ell[(size_t)fill * horizon + t] = make_float4(p.x, p.y, radius, radius * fabsf(radius));
+      ell[(size_t)fill * horizon + t] = slot_word(p.x, p.y, radius);
       ++fill;
     }
   }
-  for (; fill < n_slots; ++fill) ell[(size_t)fill * horizon + t] = make_float4(0.f, 0.f, -1.f, -1.f);
-}
-
-// ---- the round table of a many-robot round: per local robot a hard group (conflict points), then the soft all-pairs group ------------
-//
-// Local robot r owns S = S_h + n_all - 1 slots from r S on: [r S, r S + S_h) is group 2 r (hard), the rest group 2 r + 1 (soft).  The
-// offsets depend on no data, so the three kernels below need no sizing pass and no synchronisation between them.
-
-// offsets, weights, every hard slot inactive, fill and dropped zeroed
-__global__ void round_init_kernel(int n_local, int S_h, int S, float w_hard, float w_soft, float4* __restrict__ ell,
-                                  int* __restrict__ grp_slot_off, float* __restrict__ grp_weight, int* __restrict__ robot_grp_off,
-                                  int* __restrict__ fill, int* __restrict__ dropped) {
-  const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, step = (size_t)gridDim.x * blockDim.x;
-  const size_t per = (size_t)S_h * H;
-  for (size_t idx = tid; idx < (size_t)n_local * per; idx += step) {
-    const size_t r = idx / per;
-    ell[r * S * H + (idx - r * per)] = make_float4(0.f, 0.f, -1.f, -1.f);
-  }
-  for (size_t idx = tid; idx < (size_t)n_local * H; idx += step) fill[idx] = 0;
-  for (size_t r = tid; r <= (size_t)n_local; r += step) {
-    robot_grp_off[r] = 2 * (int)r;
-    grp_slot_off[2 * r] = (int)r * S;
-    if (r == (size_t)n_local) break;
-    grp_slot_off[2 * r + 1] = (int)r * S + S_h;
-    grp_weight[2 * r] = w_hard;
-    grp_weight[2 * r + 1] = w_soft;
-    dropped[r] = 0;
-  }
-}
-
-// the soft block of every local robot: the words soft_cons_kernel (guide.hip) writes for that robot, behind its hard block
-__global__ void round_soft_kernel(const float2* __restrict__ paths, int n_all, int robot0, int n_local, int S_h, float radius,
-                                  float4* __restrict__ ell) {
-  const int slots = n_all - 1, S = S_h + slots;
-  const size_t tot = (size_t)n_local * slots * H;
-  for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < tot; idx += (size_t)gridDim.x * blockDim.x) {
-    const int t = idx % H;
-    const int j = (idx / H) % slots;
-    const int i = idx / ((size_t)H * slots);
-    const int other = j + (j >= robot0 + i ? 1 : 0);
-    const float2 p = paths[(size_t)other * H + t];
-    const float r = t >= 1 ? radius : -1.f;                               // constraints cover t in [1, H-1]
-    ell[((size_t)i * S + S_h + j) * H + t] = make_float4(p.x, p.y, r, r * fabsf(r));
-  }
-}
-
-// The hard points of a round's conflicts (convert_conflicts_to_constraints, mmd/common/conflict_conversion.py:41-55: both agents of a
-// conflict at tc get the midpoint with range (tc - t_pad, tc + t_pad)), appended behind what earlier rounds left.  One wave per local
-// robot, lane = time step t, four robots a workgroup, no atomics, no LDS.  mmd_pack_constraints' rule -- a point's slot at t is the
-// number of earlier points of the list active at t -- needs no list here: the robot's records in report order are tc ascending, then
-// the other robot ascending (a record (tc, a, b) has a < b: the partners below the robot's id come first), a list of the cell table is
-// in ascending id (COVER above: every partner is in the list of the robot's own cell), and the points active at t are those of
-// tc in [t - t_pad + 1, t + t_pad].  So lane t walks exactly its own points in list order and counts its own slots.  The midpoint is
-// write_conflict's expression (the sum commutes: the same bits whichever robot of the pair the lane serves).  A point past slot
-// S_h - 1 is dropped and counted; the lane's fill stays at S_h, so everything later is dropped too and what was written is a prefix.
-__global__ __launch_bounds__(256) void conflict_constraints_kernel(const float2* __restrict__ paths, mmd_cons_bins b, int n_local, int S_h,
-                                                                    int S, int t_pad, float margin, float radius, float4* __restrict__ ell,
-                                                                    int* __restrict__ fill, int* __restrict__ dropped) {
-  const int t = threadIdx.x & 63;
-  const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (r >= n_local) return;
-  const int a = b.robot0 + r;
-  float4* const col = ell + (size_t)r * S * H + t;                        // the robot's hard block, column t
-  const float r2 = radius * fabsf(radius);
-  int f = fill[(size_t)r * H + t], drop = 0;
-  const int tc1 = min(t + t_pad, H - 1);
-  for (int tc = max(t - t_pad + 1, 0); tc <= tc1; ++tc) {
-    const float2 pa = paths[(size_t)a * H + tc];
-    const CellList l = own_cell_list(b, tc, pa.x, pa.y);
-    for (int e = l.e0; e < l.e1; ++e) {
-      const float4 q = l.ent[e];
-      if (__builtin_bit_cast(int, q.z) == a || !rr_hit(pa, make_float2(q.x, q.y), margin)) continue;
-      if (f < S_h) {
-        col[(size_t)f * H] = make_float4((pa.x + q.x) / 2.f, (pa.y + q.y) / 2.f, radius, r2);
-        ++f;
-      } else {
-        ++drop;
-      }
-    }
-  }
-  fill[(size_t)r * H + t] = f;
-  drop = wave_sum(drop);
-  if (t == 0) dropped[r] += drop;
-}
-
-// ---- the framed all-pairs table: every robot plans in the model's tile frame, the robots meet in a global frame ---------------------
-//
-// Robot r's trajectory lives in the model's own frame (the tile [-1, 1]^2 the normaliser spans); off[r] places that window in the world:
-// global = local + off[r].  The other robots' gathered paths are global, so robot r sees robot j's point at q = paths[j][t] - off[r] (one
-// fp32 subtraction per axis).  The table keeps q only where it lies in the robot's WINDOW [window_lo, window_hi] (local frame, closed,
-// plain fp32 compares: a NaN fails them and is left out), packed by mmd_pack_constraints' rule: the s-th kept robot, in ascending id, goes
-// to slot s of column t.  So a robot owns S slots whatever n_all is, S is sized by the local density, and every guided-step kernel reads
-// the table as it reads any other.
-//
-// WHY LEAVING THE OTHERS OUT IS EXACT.  The guided step un-normalises with an unconditional clip, so the position p it measures from lies
-// in the normaliser's position limits [min, max] up to the rounding of (c + 1) / 2 (max - min) + min with c in [-1, 1]: a few ulp of the
-// limits' magnitude.  A point acts on p only within its radius R: the guided step's test fma(dx, dx, dy dy) <= R|R| (guide.hip:
-// cons_term) needs |dx|, |dy| <= R (1 + 2^-23) by COVER's argument (the radicand is at least each rounded square).  The Python layer
-// passes the window limits -/+ 1.0625 R -- the 1/16 slack of the cell rule.  A q outside it differs from every such p by more than
-// 1.0625 R - (those few ulp) on one axis, which is above R by R / 16 less a few 1e-7: it can never act, at any step of any sample.  A
-// table without it gives the guided step the same ACTIVE TERMS, in ascending id.  Not the same bits as the all-pairs table: the step
-// sums a group's slots in four accumulators by slot index, and culling moves a robot to another slot, so the rounding of the sum may
-// differ (the dense table's 2e-6 against the oracle holds for both); the host pack of the included points has the same slots and the
-// same bits.  What the caller must keep true is only that the window covers limits -/+ R with that slack.
-//
-// One wave per local robot, lane = time step t, four robots a workgroup, no atomics, no LDS (conflict_constraints_kernel's shape).  Lane t
-// reads paths[j][t]: the wave reads one 512-byte row per j, four rows a trip (the loads of a trip are issued together; a trip past the
-// end re-reads the last row and drops it), and writes 1 KiB rows of the table.  O(n_all) per lane, whatever the density: a walk over
-// candidate lists or a world cell table would be O(neighbours), and is not done here.  A kept point past slot S - 1 is not written and
-// counts into dropped[i]; the lane's fill stays at S, so what was written is a prefix of the list.  Slots from the fill on, and all of
-// column 0 (constraints cover t >= 1), get the empty word (0, 0, -1, -1) mmd_pack_constraints leaves in an unused slot.
-__global__ __launch_bounds__(256) void framed_constraints_kernel(const float2* __restrict__ paths, const float2* __restrict__ offsets,
-                                                                  int n_all, int robot0, int n_local, int S, float radius, float weight,
-                                                                  float2 wlo, float2 whi, float4* __restrict__ ell,
-                                                                  int* __restrict__ grp_slot_off, float* __restrict__ grp_weight,
-                                                                  int* __restrict__ robot_grp_off, int* __restrict__ used,
-                                                                  int* __restrict__ dropped) {
-  const int t = threadIdx.x & 63;
-  const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (i >= n_local) return;
-  const int r = robot0 + i;
-  const float2 off = offsets[r];
-  float4* const col = ell + (size_t)i * S * H + t;                        // the robot's block, column t
-  const float r2 = radius * fabsf(radius);
-  int f = 0, drop = 0;
-  for (int j0 = 0; j0 < n_all; j0 += 4) {
-    float2 p[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) p[k] = paths[(size_t)min(j0 + k, n_all - 1) * H + t];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const int j = j0 + k;
-      const float qx = p[k].x - off.x, qy = p[k].y - off.y;
-      const bool in = qx >= wlo.x && qx <= whi.x && qy >= wlo.y && qy <= whi.y;
-      if (!(t >= 1 && j < n_all && j != r && in)) continue;
-      if (f < S) {
-        col[(size_t)f * H] = make_float4(qx, qy, radius, r2);
-        ++f;
-      } else {
-        ++drop;
-      }
-    }
-  }
-  const int fill = wave_max(f);
-  for (; f < S; ++f) col[(size_t)f * H] = make_float4(0.f, 0.f, -1.f, -1.f);
-  drop = wave_sum(drop);
-  if (t == 0) {                                                           // one group of S slots per robot
-    used[i] = fill;
-    dropped[i] = drop;
-    grp_slot_off[i] = i * S;
-    grp_weight[i] = weight;
-    robot_grp_off[i] = i;
-    if (i == n_local - 1) {
-      grp_slot_off[n_local] = n_local * S;
-      robot_grp_off[n_local] = n_local;
-    }
-  }
+  for (; fill < n_slots; ++fill) ell[(size_t)fill * horizon + t] = empty_word();
 }
 
 // ---- which robots a round re-plans: the robots in conflict, or an independent set of the conflict graph -----------------------------
@@ -666,15 +503,6 @@ static int check_conflict_list(const char* who, mmd_conflict*& list_dev, int lis
   return 0;
 }
 
-// what the two collision entry points on a cell table share: the table's own checks, and margin <= radius (COVER above)
-static int check_collision_bins(const char* who, const mmd_cons_bins* bins, float margin) {
-  MMD_REQUIRE(bins, "%s: NULL table", who);
-  if (int rc = check_cons_bins(bins)) return rc;
-  MMD_REQUIRE(margin <= bins->radius, "%s: margin %g above the table's radius %g (a list could miss a colliding robot)", who, margin,
-              bins->radius);
-  return 0;
-}
-
 int mmd_count_collisions_binned(const float* trajs_dev, const mmd_cons_bins* bins, int n_local, int samples_per_robot, float margin,
                                 int32_t* counts_dev, void* stream) {
   MMD_REQUIRE(trajs_dev && counts_dev, "mmd_count_collisions_binned: NULL argument");
@@ -759,79 +587,6 @@ int mmd_path_constraints(const mmd_agent_path* agents_dev, int n_state, int agen
   return 0;
 }
 
-// what the three round-table entry points require of the shape: the guided step indexes the table's (slot, t) words with an int
-static int check_round_table(const char* who, int n_all, int robot0, int n_local, int horizon, int hard_slots) {
-  MMD_REQUIRE(horizon == H, "%s: horizon must be %d", who, H);
-  MMD_REQUIRE(hard_slots >= 1, "%s: hard_slots must be at least 1, got %d", who, hard_slots);
-  MMD_REQUIRE(n_all >= 2 && n_local >= 1 && robot0 >= 0 && robot0 < n_all && n_local <= n_all - robot0, "%s: bad robot range", who);
-  MMD_REQUIRE((long long)n_local * ((long long)hard_slots + n_all - 1) * H <= INT_MAX, "%s: a table of more than 2^31 - 1 points", who);
-  return 0;
-}
-
-static int grid_for(size_t items) {
-  const size_t g = (items + 255) / 256;
-  return g > 2048 ? 2048 : (g < 1 ? 1 : (int)g);
-}
-
-int mmd_round_constraints_init(int n_all, int n_local, int horizon, int hard_slots, float weight_hard, float weight_soft, float* ell_dev,
-                               int32_t* grp_slot_off_dev, float* grp_weight_dev, int32_t* robot_grp_off_dev, int32_t* fill_dev,
-                               int32_t* dropped_dev, void* stream) {
-  MMD_REQUIRE(ell_dev && grp_slot_off_dev && grp_weight_dev && robot_grp_off_dev && fill_dev && dropped_dev,
-              "mmd_round_constraints_init: NULL argument");
-  if (int rc = check_round_table("mmd_round_constraints_init", n_all, 0, n_local, horizon, hard_slots)) return rc;
-  hipLaunchKernelGGL(round_init_kernel, dim3(grid_for((size_t)n_local * hard_slots * H)), dim3(256), 0, (hipStream_t)stream, n_local,
-                     hard_slots, hard_slots + n_all - 1, weight_hard, weight_soft, (float4*)ell_dev, grp_slot_off_dev, grp_weight_dev,
-                     robot_grp_off_dev, fill_dev, dropped_dev);
-  MMD_HIP_CHECK(hipGetLastError());
-  return 0;
-}
-
-int mmd_round_soft_from_paths(const float* paths_dev, int n_all, int robot0, int n_local, int horizon, int hard_slots, float radius,
-                              float* ell_dev, void* stream) {
-  MMD_REQUIRE(paths_dev && ell_dev, "mmd_round_soft_from_paths: NULL argument");
-  if (int rc = check_round_table("mmd_round_soft_from_paths", n_all, robot0, n_local, horizon, hard_slots)) return rc;
-  hipLaunchKernelGGL(round_soft_kernel, dim3(grid_for((size_t)n_local * (n_all - 1) * H)), dim3(256), 0, (hipStream_t)stream,
-                     (const float2*)paths_dev, n_all, robot0, n_local, hard_slots, radius, (float4*)ell_dev);
-  MMD_HIP_CHECK(hipGetLastError());
-  return 0;
-}
-
-int mmd_conflict_constraints_append(const float* paths_dev, const mmd_cons_bins* bins, int n_local, int horizon, int hard_slots, int t_pad,
-                                    float margin, float radius, float* ell_dev, int32_t* fill_dev, int32_t* dropped_dev, void* stream) {
-  MMD_REQUIRE(paths_dev && ell_dev && fill_dev && dropped_dev, "mmd_conflict_constraints_append: NULL argument");
-  MMD_REQUIRE(t_pad >= 1, "mmd_conflict_constraints_append: t_pad must be at least 1, got %d", t_pad);
-  if (int rc = check_collision_bins("mmd_conflict_constraints_append", bins, margin)) return rc;
-  if (int rc = check_round_table("mmd_conflict_constraints_append", bins->n_all, bins->robot0, n_local, horizon, hard_slots)) return rc;
-  hipLaunchKernelGGL(conflict_constraints_kernel, dim3((n_local + 3) / 4), dim3(256), 0, (hipStream_t)stream, (const float2*)paths_dev,
-                     *bins, n_local, hard_slots, hard_slots + bins->n_all - 1, t_pad < H ? t_pad : H, margin, radius, (float4*)ell_dev,
-                     fill_dev, dropped_dev);
-  MMD_HIP_CHECK(hipGetLastError());
-  return 0;
-}
-
-int mmd_framed_constraints_from_paths(const float* paths_dev, const float* offsets_dev, int n_all, int robot0, int n_local, int horizon,
-                                      int slots, float radius, float weight, const float window_lo[2], const float window_hi[2],
-                                      float* ell_out_dev, int32_t* grp_slot_off_dev, float* grp_weight_dev, int32_t* robot_grp_off_dev,
-                                      int32_t* used_dev, int32_t* dropped_dev, void* stream) {
-  const char* who = "mmd_framed_constraints_from_paths";
-  MMD_REQUIRE(paths_dev && offsets_dev && window_lo && window_hi && ell_out_dev && grp_slot_off_dev && grp_weight_dev && robot_grp_off_dev &&
-                  used_dev && dropped_dev, "%s: NULL argument", who);
-  MMD_REQUIRE(horizon == H, "%s: horizon must be %d", who, H);
-  MMD_REQUIRE(n_all >= 2 && n_all <= 4096, "%s: n_all must be in [2, 4096], got %d", who, n_all);
-  MMD_REQUIRE(n_local >= 1 && robot0 >= 0 && robot0 < n_all && n_local <= n_all - robot0, "%s: bad robot range", who);
-  MMD_REQUIRE(slots >= 1 && slots <= n_all - 1, "%s: slots must be in [1, n_all - 1], got %d", who, slots);
-  MMD_REQUIRE(radius > 0.f, "%s: radius must be positive", who);
-  for (int k = 0; k < 2; ++k)
-    MMD_REQUIRE(window_lo[k] < window_hi[k], "%s: empty window (axis %d: %g >= %g)", who, k, window_lo[k], window_hi[k]);
-  // (n_local slots H <= 4096 x 4095 x 64 < 2^31: the guided step's int index of the table's (slot, t) words holds)
-  hipLaunchKernelGGL(framed_constraints_kernel, dim3((n_local + 3) / 4), dim3(256), 0, (hipStream_t)stream, (const float2*)paths_dev,
-                     (const float2*)offsets_dev, n_all, robot0, n_local, slots, radius, weight, make_float2(window_lo[0], window_lo[1]),
-                     make_float2(window_hi[0], window_hi[1]), (float4*)ell_out_dev, grp_slot_off_dev, grp_weight_dev, robot_grp_off_dev,
-                     used_dev, dropped_dev);
-  MMD_HIP_CHECK(hipGetLastError());
-  return 0;
-}
-
 int mmd_round_select(const float* paths_dev, const mmd_cons_bins* bins, const int32_t* robot_counts_dev, int n_local, int horizon,
                      float margin, int mode, int iters, int32_t* state_dev, int32_t* selected_dev, int32_t* perm_dev, int32_t* header_dev,
                      void* stream) {
@@ -840,7 +595,7 @@ int mmd_round_select(const float* paths_dev, const mmd_cons_bins* bins, const in
   MMD_REQUIRE(mode == MMD_REPLAN_CONFLICTED || mode == MMD_REPLAN_INDEPENDENT, "mmd_round_select: unknown mode %d", mode);
   MMD_REQUIRE(mode != MMD_REPLAN_INDEPENDENT || iters >= 1, "mmd_round_select: iters must be at least 1, got %d", iters);
   if (int rc = check_collision_bins("mmd_round_select", bins, margin)) return rc;
-  MMD_REQUIRE(n_local >= 1 && n_local <= bins->n_all - bins->robot0, "mmd_round_select: bad robot range");
+  if (int rc = check_robot_range("mmd_round_select", bins->n_all, bins->robot0, n_local)) return rc;
   hipStream_t st = (hipStream_t)stream;
   const int n_all = bins->n_all;
   int32_t* final_state = state_dev;

@@ -1,5 +1,5 @@
-// The wave64 and 256-thread-block sums and prefixes of the collision, statistics and selection kernels (multi_agent.hip, trial_stats.hip,
-// postprocess.hip): one text each, so the fixed order that a float sum's bits depend on is the same order everywhere.  Sets no fp contract.
+// The wave64 and 256-thread-block sums and prefixes of the collision, statistics, selection and table kernels (multi_agent.hip, trial_stats.hip,
+// postprocess.hip, cons_tables.hip): one text each, so the fixed order that a float sum's bits depend on is the same order everywhere.  Sets no fp contract.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -242,10 +242,8 @@ def path_constraints_table(table, n_state, agent, agent_start, agent_last, hard,
         _lib.launch("mmd_path_constraints", table, table.data_ptr(), int(n_state), int(agent), int(agent_start), int(agent_last),
                     int(bool(hard)), H, float(radius), float(weight), int(n_slots), ell_out.data_ptr(), None, None, None)
         return ell_out
-    ell = torch.empty((max(n_slots, 1), H, 4), dtype=torch.float32, device=dev)
-    gso = torch.empty(2, dtype=torch.int32, device=dev)
-    gw = torch.empty(1, dtype=torch.float32, device=dev)
-    rgo = torch.empty(2, dtype=torch.int32, device=dev)
+    from .constraints import group_tensors
+    ell, gso, gw, rgo = group_tensors(max(n_slots, 1), 1, 1, dev)
     _lib.launch("mmd_path_constraints", table, table.data_ptr(), int(n_state), int(agent), int(agent_start), int(agent_last),
                 int(bool(hard)), H, float(radius), float(weight), int(n_slots), ell.data_ptr(), gso.data_ptr(), gw.data_ptr(),
                 rgo.data_ptr())

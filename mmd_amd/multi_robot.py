@@ -141,14 +141,19 @@ class MultiRobotSampler:
         self._collision = None
         if paths_all is None or self.n_robots < 2:
             self.guide.reset_extra_costs()
-        elif self.constraint_table == "binned":
-            self.guide.reset_extra_costs()
-            self.guide.set_binned_constraints(binned_constraints_from_paths(
-                paths_all.contiguous(), self.robot0, self.n_local, self.radius, self.w_soft))
+            return
+        self._set_inter_robot_table(self.guide, paths_all.contiguous(), self.robot0, self.n_local)
+        if self.constraint_table == "binned":
             self._collision_table(paths_all)
+
+    def _set_inter_robot_table(self, guide, paths, robot0, n):
+        """The inter-robot table of `paths` [N, H, 2] (contiguous) for robots [robot0, robot0 + n) on `guide`, in place of whatever
+        constraints it had: the cell table or the all-pairs table, by constraint_table, with the sampler's radius and weight."""
+        guide.reset_extra_costs()
+        if self.constraint_table == "binned":
+            guide.set_binned_constraints(binned_constraints_from_paths(paths, robot0, n, self.radius, self.w_soft))
         else:
-            self.guide.set_packed_constraints(soft_constraints_from_paths(
-                paths_all.contiguous(), self.robot0, self.n_local, self.radius, self.w_soft))
+            guide.set_packed_constraints(soft_constraints_from_paths(paths, robot0, n, self.radius, self.w_soft))
 
     def sample(self, seed=None, x_init=None, step_noise=None, return_chain=False):
         """One guided sampling round for the local robots: [n_local*B, H, D] normalised trajectories.  The in-kernel
@@ -255,13 +260,9 @@ class MultiRobotSampler:
         paths_perm = paths_all.index_select(0, selection.perm.long()).contiguous()
         hard_conds = {row: v.index_select(0, local_ids) for row, v in self.hard_conds.items()}
         guide = self._subset_guide(n_sel)
-        table = None
-        if self.constraint_table == "binned":
-            guide.reset_extra_costs()
-            guide.set_binned_constraints(binned_constraints_from_paths(paths_perm, sel_before, n_sel, self.radius, self.w_soft))
-            table = binned_collision_table(paths_perm, sel_before, n_sel, self.radius)
-        else:
-            guide.set_packed_constraints(soft_constraints_from_paths(paths_perm, sel_before, n_sel, self.radius, self.w_soft))
+        self._set_inter_robot_table(guide, paths_perm, sel_before, n_sel)
+        # (a table of its own, not cached: _collision stays the caller's)
+        table = binned_collision_table(paths_perm, sel_before, n_sel, self.radius) if self.constraint_table == "binned" else None
         if prev_trajs is None:
             trajs = self._sample(hard_conds, n_sel, guide, sel_before, seed)
         else:

@@ -259,11 +259,9 @@ def round_constraints_init(like: torch.Tensor, n_all: int, n_local: int, hard_sl
     """A fresh round table on the device of `like` (mmd_round_constraints_init): (ell float32 [n_local S, 64, 4] with S = hard_slots +
     n_all - 1 -- the hard blocks inactive, the soft blocks unwritten --, grp_slot_off int32 [2 n_local + 1], grp_weight float32
     [2 n_local], robot_grp_off int32 [n_local + 1], fill int32 [n_local, 64] = 0, dropped int32 [n_local] = 0)."""
+    from .constraints import group_tensors
     S = int(hard_slots) + int(n_all) - 1
-    ell = like.new_empty((max(n_local, 0) * max(S, 0), 64, 4), dtype=torch.float32)
-    gso = like.new_empty(2 * n_local + 1, dtype=torch.int32)
-    gw = like.new_empty(2 * n_local, dtype=torch.float32)
-    rgo = like.new_empty(n_local + 1, dtype=torch.int32)
+    ell, gso, gw, rgo = group_tensors(max(n_local, 0) * max(S, 0), 2 * n_local, n_local, like.device)
     fill = like.new_empty((n_local, 64), dtype=torch.int32)
     dropped = like.new_empty(n_local, dtype=torch.int32)
     _lib.launch("mmd_round_constraints_init", like, int(n_all), int(n_local), 64, int(hard_slots), float(weight_hard), float(weight_soft),

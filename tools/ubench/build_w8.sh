@@ -2,7 +2,7 @@
 # builds the W8 arms of tools/ubench/fatwave_conv.hip (and the kernel-form arms beside them) into build_tmp/ (cross-compiles)
 cd "$(dirname "$0")/../.."
 mkdir -p build_tmp
-REST="mmd_amd/csrc/unet.hip mmd_amd/csrc/unet_layers.hip mmd_amd/csrc/guide.hip mmd_amd/csrc/api.hip mmd_amd/csrc/multi_agent.hip mmd_amd/csrc/postprocess.hip"
+REST="mmd_amd/csrc/unet.hip mmd_amd/csrc/unet_layers.hip mmd_amd/csrc/guide.hip mmd_amd/csrc/cons_tables.hip mmd_amd/csrc/api.hip mmd_amd/csrc/multi_agent.hip mmd_amd/csrc/postprocess.hip"
 cc() { /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fno-slp-vectorize -w "$@" tools/ubench/fatwave_conv.hip $REST; }
 cc -DPARTS=63 -o build_tmp/ub_base_p63 &
 cc -DPARTS=7 -o build_tmp/ub_base_p7 &
