@@ -29,7 +29,8 @@ struct GuideDev {
   int n_xs, n_xb;
 };
 
-// signed distance of the env's extra objects at p and its gradient (torch's sub-gradients: the first minimum / maximum);
+// signed distance of the env's extra objects at p and its gradient (torch's sub-gradients: the first minimum over the objects, a tie inside a
+// box split evenly);
 // no object at all: sdf = 1 (an empty MultiSphereField, primitives.py:109-110).  kTorchNorm: the two norms in torch.norm's fp32 form
 // sqrt(fma(y, y, x * x)), as the occupancy decision sdf < margin needs (postprocess.hip); the guide keeps its own arithmetic.
 template <bool kTorchNorm = false>
@@ -56,8 +57,11 @@ __device__ __forceinline__ float extra_sdf(const float4* __restrict__ xs, int n_
       best = d;
       const float sx = dx > 0.f ? 1.f : (dx < 0.f ? -1.f : 0.f), sy = dy > 0.f ? 1.f : (dy < 0.f ? -1.f : 0.f);
       if (mq <= 0.f) {                                     // inside the inner box: d = max q - rad
-        gx = qx >= qy ? sx : 0.f;
-        gy = qx >= qy ? 0.f : sy;
+        // torch's sub-gradients at the ties (primitives.py:331-332): amax over (qx, qy) splits qx == qy evenly, and minimum(max q, 0)
+        // passes half at max q == 0 (relu(q) and the norm of zero pass nothing there)
+        const float h = mq < 0.f ? 1.f : 0.5f;
+        gx = qx > qy ? h * sx : (qx < qy ? 0.f : 0.5f * h * sx);
+        gy = qx < qy ? h * sy : (qx > qy ? 0.f : 0.5f * h * sy);
       } else {                                             // outside: d = ||relu(q)|| - rad
         gx = rx / n * sx;
         gy = ry / n * sy;
