@@ -53,7 +53,9 @@ int64_t mmd_unet_tensor_numel(int unet_input_dim, int n_levels, int index);
  * against mmd_unet_tensor_numel.  Also precomputes, on the GPU, the time-embedding projections of every integer
  * diffusion step t in [0, n_diffusion_steps) (TimeEncoder + the 12 cond_mlp heads; t is identical across the
  * batch, mmd/models/diffusion_models/diffusion_model_base.py:27-29). */
-typedef struct mmd_unet_options {     /* creation-time choices, fixed for the life of the handle; NULL / all zero = defaults */
+typedef struct mmd_unet_options {     /* creation-time choices, fixed for the life of the handle.  NULL = every default.  An all-zero
+                                       * struct is the defaults EXCEPT rtb_fused: 0 there selects "no fused block"; pass a negative
+                                       * rtb_fused (or NULL) for its default */
   uint32_t flags;                     /* MMD_UNET_* below */
   int32_t rtb_fused;                  /* layer-by-layer path, A/B: the widest ResidualTemporalBlock run as ONE launch (channels);
                                        * 0 = none, < 0 = default (64) */

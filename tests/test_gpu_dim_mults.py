@@ -92,6 +92,24 @@ def test_layered_forward_bits_do_not_depend_on_the_batch(monkeypatch, dm):
         assert err < 6e-6, err
 
 
+EDGE_NETS = (("mfma_d32_1248", 32, (1, 2, 4, 8), {}), ("valu_d32_124", 32, (1, 2, 4), dict(layered=True, layered_valu=True)),
+             ("valu_d40_124", 40, (1, 2, 4), {}))
+
+
+@pytest.mark.parametrize("tag,uid,dm,options", EDGE_NETS, ids=[n[0] for n in EDGE_NETS])
+def test_layered_forward_bits_at_the_launch_rules_edges(tag, uid, dm, options):
+    """The decision edges of the launch rules: the vector-ALU Conv1dBlock kernel takes 2 output channels per thread from 192 trajectories
+    and 4 from 768, the plain convs and the matrix-pipe kernel choose their slices against 768 workgroups.  One input at the batch sizes
+    either side of each edge (191, 192, 767, 768, 769) against the same rows of a batch of 1536, bit for bit -- the matrix-pipe path
+    (32, four levels) and the all-vector-ALU path (32, three levels, layered_valu; 40, whose widths have no matrix-pipe form)."""
+    unet = _unet(uid, dm, **options)
+    x = (torch.from_numpy(synth.synth_noise(908, (1536, H, D))) * 0.7).cuda()
+    whole = unet(x, 7)
+    assert torch.isfinite(whole).all()
+    for n in (191, 192, 767, 768, 769):
+        assert torch.equal(unet(x[:n].contiguous(), 7), whole[:n]), n
+
+
 def _g17_chain_case():
     g = np.load(os.path.join(GOLDEN, "g17_unet_dim_mults.npz"))
     T, B, s_x, s_n = (int(v) for v in g["meta"])

@@ -1,6 +1,7 @@
 """Forward time of the layer-by-layer TemporalUnet path (csrc/unet_layers.hip) by batch size: option 1 = UNET_DIM_MULTS[1] = (1, 2, 4, 8),
-and option 0 forced onto the path (TemporalUnet(layered=True)) beside the fused kernel.  MMD_AMD_LAYERED_VALU=1 (read HERE by this tool and passed to TemporalUnet(layered_valu=...) -> mmd_unet_options; the library reads no environment): the
-vector-ALU Conv1dBlock kernel instead of conv5_mfma_kernel.  Usage: layered_time.py [n ...]"""
+and option 0 forced onto the path (TemporalUnet(layered=True)) beside the fused kernel.  MMD_AMD_LAYERED_VALU=1 (read HERE by this tool and passed to TemporalUnet(layered_valu=...) -> mmd_unet_options; the library reads no environment): every
+layer on the vector-ALU kernels (conv5_block_kernel / conv_plain_kernel, csrc/layers_valu_dev.h) instead of mconv_kernel (csrc/mconv_dev.h).
+Usage: layered_time.py [n ...]"""
 import os
 import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
