@@ -631,6 +631,30 @@ int mmd_unnormalize_trajs(const float* x_dev, size_t n_points, size_t period_poi
  * n_traj^2 entries of triu(cdist(p_t, p_t), 1); the metric is their sum over t. */
 int mmd_variance_waypoints(const float* trajs_dev, int n_traj, int horizon, float* var_per_waypoint_dev, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Custom maps: the fixed objects' SDF grid built on the device from spheres and rounded boxes
+ * ---------------------------------------------------------------------------------------------------------- */
+
+/* GridMapSDF.precompute_sdf (deps/torch_robotics/torch_robotics/environments/grid_map_sdf.py:34-63) for one
+ * ObjectField([MultiSphereField(spheres), MultiBoxField(boxes)]) at the identity pose (primitives.py:108-115, :326-333, :569-572):
+ * grid_dev[ix * ny + iy] = (sdf, dsdf/dx, dsdf/dy, 0) at the node (xs_dev[ix], ys_dev[iy]) -- one map's slice [nx][ny] of
+ * mmd_guide_desc.sdf_grids_dev.  The node coordinates are the caller's (torch.linspace(lo, hi, n) of the reference, computed once on the
+ * host), so the nodes are the reference's to the bit.
+ *   spheres_dev [n_spheres][4] = (cx, cy, r, 0)             -- mmd_guide_desc.extra_spheres_dev's layout
+ *   boxes_dev   [n_boxes][4]   = (cx, cy, half x, half y)   -- mmd_guide_desc.extra_boxes_dev's layout; rounding radius 0.15 x the smaller size
+ * The value and the gradient are those of torch autograd on the host, bit for bit but for the sign of a zero (plain fp32, no contraction, both norms as
+ * sqrt(fma(y, y, x * x)), correctly rounded division and square root), with torch's sub-gradients at the ties:
+ *   - among equal minima the first wins, spheres before boxes, in table order (torch.min over the primitives, then over the fields);
+ *   - an empty sphere field is the constant 1 with gradient 0 and takes part in the minimum first (primitives.py:109-110); an empty box
+ *     field is left out; no primitive at all: (1, 0, 0, 0) everywhere;
+ *   - a sphere centred on the node has gradient 0 (torch.norm's backward at 0);
+ *   - inside a box the amax tie qx == qy splits evenly, and minimum(max q, 0) passes half at max q == 0 (primitives.py:331-332);
+ *   - a gradient component that is zero is +0 (autograd's own zero may be -0 = 0 * -1 where a field has one primitive: equal in value).
+ * Error returns, before anything is launched: a NULL table with a non-zero count or a negative count, nx or ny below 1, nx * ny of
+ * 2^31 - 256 or more, a NULL coordinate row, a NULL grid. */
+int mmd_sdf_grid_build(const float* spheres_dev, int n_spheres, const float* boxes_dev, int n_boxes, const float* xs_dev, int nx,
+                       const float* ys_dev, int ny, float* grid_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -175,6 +175,8 @@ _SIGNATURES = {
                                         C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mmd_cross_condition": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_float),
                                       C.POINTER(C.c_float), C.c_int, C.c_void_p]),
+    "mmd_sdf_grid_build": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                     C.c_void_p]),
 }
 
 # include/mmd_amd_debug.h: measurement hooks (bench.py / tools), not part of the drop-in boundary

@@ -11,6 +11,7 @@ import torch
 
 from . import _lib
 from .constraints import CostConstraint, PathConstraintGroup, build_path_groups, pack_constraints
+from . import environments
 from .environments import LIMITS, sdf_grid_texture
 
 ROBOT_RADIUS = 0.05                 # mmd/config/mmd_params.py:30
@@ -18,21 +19,54 @@ ROBOT_RADIUS = 0.05                 # mmd/config/mmd_params.py:30
 # Device-side sharing (SURVEY §8f-3): one resident SDF texture per (map set, device) for every guide / task facade of the
 # process (the reference precomputes the grid once per planner object, grid_map_sdf.py:34-63, N+1 times per instance).
 _TEXTURES = {}
-N_TEXTURE_UPLOADS = 0
+N_TEXTURE_UPLOADS = 0               # host-built textures copied to a device (shipped maps)
+N_TEXTURE_BUILDS = 0                # texture slices built on a device by mmd_sdf_grid_build (registered maps)
 
 
 def device_sdf_textures(maps, device):
-    """[n_maps, n_grids=1, nx, ny, 4] float32 on `device`, uploaded once per process."""
-    global N_TEXTURE_UPLOADS
+    """[n_maps, n_grids=1, nx, ny, 4] float32 on `device`, resident once per process.  A shipped map's slice is the host texture,
+    uploaded; a registered map's (environments.register_map) is built on the device from its primitives."""
+    global N_TEXTURE_UPLOADS, N_TEXTURE_BUILDS
     device = torch.device(device)
     if device.type == "cuda" and device.index is None:
         device = torch.device("cuda", torch.cuda.current_device())
     key = (tuple(maps), str(device))
     if key not in _TEXTURES:
-        tex = np.stack([sdf_grid_texture(m) for m in maps])[:, None]
-        _TEXTURES[key] = torch.from_numpy(np.ascontiguousarray(tex)).to(device)
-        N_TEXTURE_UPLOADS += 1
+        built = [m for m in maps if environments.is_registered(m)]
+        if not built:
+            tex = np.stack([sdf_grid_texture(m) for m in maps])[:, None]
+            _TEXTURES[key] = torch.from_numpy(np.ascontiguousarray(tex)).to(device)
+            N_TEXTURE_UPLOADS += 1
+        else:
+            nx, ny = environments.grid_shape()
+            tex = torch.empty(len(maps), 1, nx, ny, 4, dtype=torch.float32, device=device)
+            for i, m in enumerate(maps):
+                if m in built:
+                    environments.device_sdf_grid(*environments.map_primitives(m), device, out=tex[i, 0])
+                    N_TEXTURE_BUILDS += 1
+                else:
+                    tex[i, 0].copy_(torch.from_numpy(sdf_grid_texture(m)))
+            N_TEXTURE_UPLOADS += len(built) < len(maps)
+            _TEXTURES[key] = tex
     return _TEXTURES[key]
+
+
+def rebuild_resident_textures(name):
+    """environments.update_map: every resident slice of the registered map `name` is rebuilt in place, in its storage, on the current
+    stream of its device."""
+    global N_TEXTURE_BUILDS
+    for (maps, _), tex in _TEXTURES.items():
+        for i, m in enumerate(maps):
+            if environments.is_registered(m) and m.replace("ExtraObjects", "") == name:
+                with torch.cuda.device(tex.device):
+                    environments.device_sdf_grid(*environments.map_primitives(m), tex.device, out=tex[i, 0])
+                N_TEXTURE_BUILDS += 1
+
+
+def drop_resident_textures(name):
+    """environments.unregister_map: forget the resident textures that hold `name` (an object built on one keeps its tensor)."""
+    for key in [k for k in _TEXTURES if any(m.replace("ExtraObjects", "") == name for m in k[0])]:
+        del _TEXTURES[key]
 
 
 class GuideManagerTrajectoriesWithVelocity:
@@ -62,8 +96,7 @@ class GuideManagerTrajectoriesWithVelocity:
         self._grids = device_sdf_textures(maps, self.device)                  # [n_maps, n_grids=1, nx, ny, 4], shared
         self._robot_map = torch.tensor([maps.index(e) for e in env_ids], dtype=torch.int32, device=self.device)
         self._n_maps = len(maps)
-        from .environments import MAP_BOXES
-        self._obstacle_free = all(len(MAP_BOXES[m.replace("ExtraObjects", "")][0]) == 0 for m in maps)
+        self._obstacle_free = not any(environments.map_has_obstacles(m) for m in maps)
         # use_guide_on_extra_objects_only (mpd.py:216-219): the only collision field is task.get_collision_fields_extra_objects()
         # = the env's extra ObjectField (EMPTY in every shipped map: env_*_extra_objects.py MultiSphereField([]), sdf == 1;
         # `extra_objects` below otherwise) -- no fixed-object grid and no workspace walls in the guide; GP prior and

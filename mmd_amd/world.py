@@ -15,7 +15,7 @@ import torch
 from . import synth
 from .constraints import (BIN_CELL_SLACK, VERTEX_CONSTRAINT_RADIUS, binned_collision_table, framed_constraints_from_paths,
                           framed_slot_bound)
-from .environments import LIMITS, MAP_BOXES, map_sdf
+from .environments import LIMITS, map_has_obstacles, map_sdf
 from .multi_robot import D, H, MultiRobotSampler, shard_range
 
 WORLD_MAX_CELLS = 64             # per axis: what the library takes for a cell table (the default grid of constraints.bin_grid stops at 32)
@@ -178,7 +178,7 @@ def random_world_instance(n_robots, extent, seed, env_id="EnvEmpty2D", min_separ
     if not extent >= TILE_PITCH:
         raise ValueError(f"random_world_instance: a world of side {extent} cannot hold a window of side {TILE_PITCH}")
     rng = np.random.Generator(np.random.PCG64(seed))
-    snapped = len(MAP_BOXES[env_id.replace("ExtraObjects", "")][0]) > 0
+    snapped = map_has_obstacles(env_id)
     tiles = int(np.floor(extent / TILE_PITCH))
     half = np.float32((extent - TILE_PITCH) / 2.0)
     starts, goals, offsets = (np.zeros((0, 2), np.float32) for _ in range(3))
