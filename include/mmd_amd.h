@@ -655,6 +655,28 @@ int mmd_variance_waypoints(const float* trajs_dev, int n_traj, int horizon, floa
 int mmd_sdf_grid_build(const float* spheres_dev, int n_spheres, const float* boxes_dev, int n_boxes, const float* xs_dev, int nx,
                        const float* ys_dev, int ny, float* grid_dev, void* stream);
 
+/* The same texture from an OCCUPANCY BITMAP (a floor plan, a benchmark grid, a costmap): an exact Euclidean distance transform with
+ * nearest-site tracking.  occ_dev [nx][ny] bytes, non-zero = occupied, indexed like the grid: cell (ix, iy) is the cell the lookup
+ * floor((p - lo) / (hi - lo) * n) gives a point; `cell` is the cell pitch.  grid_dev[ix * ny + iy] = (sdf, dsdf/dx, dsdf/dy, 0):
+ *   - the site of a cell is the nearest cell of the other class by D2 = (ix - jx)^2 + (iy - jy)^2 (an exact integer), the
+ *     lexicographically smallest (jx, jy) among equal D2;
+ *   - s = sqrt(float(D2)), v = cell * s - 0.5 * cell (the surface lies on the cell edge), plain fp32, one rounding per operation;
+ *   - a free cell: (+v, (ix - jx) / s, (iy - jy) / s, 0), away from the obstacle; with v not below 1: (1, 0, 0, 0), the constant-1 field
+ *     of the primitive maps;
+ *   - an occupied cell: (-v, (jx - ix) / s, (jy - iy) / s, 0), towards free space;
+ *   - a zero component is +0; no occupied cell at all: (1, 0, 0, 0) everywhere; no free cell at all: (-1, 0, 0, 0) everywhere (both
+ *     decided on the device: the call does not synchronise).
+ * mmd_amd/environments.py::occupancy_sdf_texture is the same definition on the host, and the grid is that texture bit for bit.
+ * work_dev: mmd_sdf_grid_occupancy_work_bytes(nx, ny) bytes of device memory (two [nx][ny] int16 tables: per row, the signed iy offset to
+ * the nearest occupied and to the nearest free cell), 2-byte aligned, overwritten by every call; the result does not depend on what it held.
+ * Error returns, before anything is launched: NULL occupancy, grid or workspace; nx or ny below 1 or above MMD_OCCUPANCY_MAX_SIDE (every D2
+ * is then an exact fp32 integer); a cell that is not finite and positive; work_bytes too small.
+ * mmd_sdf_grid_occupancy_work_bytes returns 0 for a size the build refuses. */
+#define MMD_OCCUPANCY_MAX_SIDE 2048
+size_t mmd_sdf_grid_occupancy_work_bytes(int nx, int ny);
+int mmd_sdf_grid_from_occupancy(const unsigned char* occ_dev, int nx, int ny, float cell, float* grid_dev, void* work_dev,
+                                size_t work_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

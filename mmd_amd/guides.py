@@ -20,12 +20,13 @@ ROBOT_RADIUS = 0.05                 # mmd/config/mmd_params.py:30
 # process (the reference precomputes the grid once per planner object, grid_map_sdf.py:34-63, N+1 times per instance).
 _TEXTURES = {}
 N_TEXTURE_UPLOADS = 0               # host-built textures copied to a device (shipped maps)
-N_TEXTURE_BUILDS = 0                # texture slices built on a device by mmd_sdf_grid_build (registered maps)
+N_TEXTURE_BUILDS = 0                # texture slices built on a device (registered maps: mmd_sdf_grid_build / mmd_sdf_grid_from_occupancy)
 
 
 def device_sdf_textures(maps, device):
     """[n_maps, n_grids=1, nx, ny, 4] float32 on `device`, resident once per process.  A shipped map's slice is the host texture,
-    uploaded; a registered map's (environments.register_map) is built on the device from its primitives."""
+    uploaded; a registered map's (environments.register_map / register_occupancy_map) is built on the device from its primitives or
+    its bitmap."""
     global N_TEXTURE_UPLOADS, N_TEXTURE_BUILDS
     device = torch.device(device)
     if device.type == "cuda" and device.index is None:
@@ -42,7 +43,7 @@ def device_sdf_textures(maps, device):
             tex = torch.empty(len(maps), 1, nx, ny, 4, dtype=torch.float32, device=device)
             for i, m in enumerate(maps):
                 if m in built:
-                    environments.device_sdf_grid(*environments.map_primitives(m), device, out=tex[i, 0])
+                    environments.build_resident_texture(m, device, tex[i, 0])
                     N_TEXTURE_BUILDS += 1
                 else:
                     tex[i, 0].copy_(torch.from_numpy(sdf_grid_texture(m)))
@@ -51,15 +52,19 @@ def device_sdf_textures(maps, device):
     return _TEXTURES[key]
 
 
-def rebuild_resident_textures(name):
-    """environments.update_map: every resident slice of the registered map `name` is rebuilt in place, in its storage, on the current
-    stream of its device."""
+def rebuild_resident_textures(name, device_occupancy=None):
+    """environments.update_map / update_occupancy_map: every resident slice of the registered map `name` is rebuilt in place, in its
+    storage, on the current stream of its device, by the builder of its kind.  device_occupancy: the new bitmap as a device tensor,
+    used as it is for the slices on its device."""
     global N_TEXTURE_BUILDS
     for (maps, _), tex in _TEXTURES.items():
         for i, m in enumerate(maps):
             if environments.is_registered(m) and m.replace("ExtraObjects", "") == name:
                 with torch.cuda.device(tex.device):
-                    environments.device_sdf_grid(*environments.map_primitives(m), tex.device, out=tex[i, 0])
+                    if device_occupancy is not None and device_occupancy.device == tex.device:
+                        environments.device_occupancy_sdf_grid(device_occupancy, tex.device, out=tex[i, 0])
+                    else:
+                        environments.build_resident_texture(m, tex.device, tex[i, 0])
                 N_TEXTURE_BUILDS += 1
 
 
