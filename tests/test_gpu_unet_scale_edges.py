@@ -6,7 +6,6 @@ below puts the cases that could break that into ONE batch, so that they also sha
 largest |x| that is a negative value, magnitudes from 2^-70 to 2^30, +inf and NaN.  One forward per kernel at the smallest sizes that
 reach it: n = 3 per launch -> unet_kernel<1>; n = 5 with two_per_workgroup_max = -1 -> unet_kernel<4> (a full workgroup + a ragged one);
 n = 257 -> unet_kernel<2> (the smallest size it runs at)."""
-import numpy as np
 import pytest
 import torch
 
@@ -18,34 +17,10 @@ from oracle import mmd_oracle as O                 # noqa: E402
 from cases import H, D, rel_l2                     # noqa: E402
 
 T_STEP = 63
-# the rows of the edge batch, in an order that puts the inf / NaN samples into workgroups with finite ones: rows 5 .. 8 are one workgroup of
-# unet_kernel<4> (launches of five rows: 0-4, 5-9, 10-14), rows (5, 6) and (7, 8) two workgroups of unet_kernel<2>
-NAMES = ["zero", "neg_zero", "2^-70", "2^-20", "1e-3", "one", "inf", "eight", "nan", "2^30", "neg_max"]
-ORACLE_ROWS = ["neg_zero", "1e-3", "one", "eight", "neg_max"]    # within the scales test_unet_forward_input_range covers (1e-3 .. 8)
-NON_FINITE = ["inf", "nan"]
-
-
-def edge_batch():
-    x = synth.synth_noise(177, (len(NAMES), H, D))
-    row = {k: i for i, k in enumerate(NAMES)}
-    x[row["zero"]] = 0.0
-    x[row["neg_zero"]].reshape(-1)[::3] = -0.0
-    for k, s in (("2^-70", 2.0 ** -70), ("2^-20", 2.0 ** -20), ("1e-3", 1e-3), ("eight", 8.0), ("2^30", 2.0 ** 30)):
-        x[row[k]] *= np.float32(s)
-    x[row["neg_max"], 40, 2] = -(np.abs(x[row["neg_max"]]).max() + 1.0)      # the largest |x| is a negative value
-    x[row["inf"], 9, 1] = np.inf
-    x[row["nan"], 33, 0] = np.nan
-    assert np.signbit(x[row["neg_zero"]].reshape(-1)[::3]).all() and x[row["neg_max"]].min() == -np.abs(x[row["neg_max"]]).max()
-    return torch.from_numpy(x)
-
-
-def plain_batch():
-    """the edge batch with the inf / NaN samples replaced by ordinary ones"""
-    x = edge_batch()
-    fill = torch.from_numpy(synth.synth_noise(178, (len(NON_FINITE), H, D)))
-    for j, k in enumerate(NON_FINITE):
-        x[NAMES.index(k)] = fill[j]
-    return x
+# the rows of the edge batch (tests/layered_edge_cases.py, shared with the layer-by-layer path's tests), in an order that puts the inf / NaN
+# samples into workgroups with finite ones: rows 5 .. 8 are one workgroup of unet_kernel<4> (launches of five rows: 0-4, 5-9, 10-14), rows
+# (5, 6) and (7, 8) two workgroups of unet_kernel<2>
+from layered_edge_cases import NAMES, ORACLE_ROWS, NON_FINITE, edge_batch, plain_batch     # noqa: E402
 
 
 def forward_with(kernel, x):
