@@ -17,6 +17,13 @@ plan_rounds_subset(replan="conflicted" | "independent") re-samples, from round 1
 (multi_agent.select_replan): the others keep their paths and samples bit for bit.  A subset round is an ordinary round of the permuted
 instance paths_all[perm], in which the selected robots are a prefix and a rank's selected robots a block of it (replan_round).
 Every robot here lives on the model's one tile; world.WorldRobotSampler is the same loop for robots that each carry an offset into a larger world.
+
+How the class is laid out: one sampling call (_run) behind sample, sample_local, replan_round and the loop; three places where a round meets
+the other robots, each written once for robots [robot0, robot0 + n) of an instance `paths`, so that the full round and the subset round run
+the same code -- the guide table (set_other_paths -> _set_inter_robot_table), the collision cell table (_collision_table, cached, and
+replan_round's uncached one -> _build_collision_table) and the pick (best_paths -> _pick -> _in_shared_frame); and the loop
+(plan_rounds_subset), whose rounds are _full_round and _subset_round.  _set_inter_robot_table, _build_collision_table and _in_shared_frame are
+the hooks a subclass with per-robot frames overrides.
 """
 from dataclasses import dataclass
 from math import ceil
@@ -121,12 +128,20 @@ class MultiRobotSampler:
         self.inter_robot = inter_robot
         self._collision = None          # "binned": (paths_all, its collision table), kept from set_other_paths for best_paths
         self.round_constraints = None   # plan_rounds(repair=True): the call's constraints.RoundConstraints
+        self.last_idx = self.last_n_free = None     # best_paths: the pick per local robot and how many of its samples were free
+        self.last_conflict_list = None              # plan(list_cap > 0): the first records of the final report
+
+    # ---- the three places where a round meets the other robots: each takes (paths, robot0, n), so that the full round and the subset
+    # ---- round (replan_round) run the same code; a subclass with frames (world.WorldRobotSampler) overrides only the three hooks
+    def _build_collision_table(self, paths, robot0, n):
+        """hook: the collision cell table (every time step listed) of `paths` [N, H, 2] (contiguous) for robots [robot0, robot0 + n)"""
+        return binned_collision_table(paths, robot0, n, self.radius)
 
     def _collision_table(self, paths_all):
         """The collision cell table of paths_all (every time step listed): built once per round, by set_other_paths or by the first
         best_paths that needs it."""
         if self._collision is None or self._collision[0] is not paths_all:
-            self._collision = (paths_all, binned_collision_table(paths_all.contiguous(), self.robot0, self.n_local, self.radius))
+            self._collision = (paths_all, self._build_collision_table(paths_all.contiguous(), self.robot0, self.n_local))
         return self._collision[1]
 
     def _report_on_own_table(self):
@@ -147,7 +162,7 @@ class MultiRobotSampler:
             self._collision_table(paths_all)
 
     def _set_inter_robot_table(self, guide, paths, robot0, n):
-        """The inter-robot table of `paths` [N, H, 2] (contiguous) for robots [robot0, robot0 + n) on `guide`, in place of whatever
+        """hook: the inter-robot table of `paths` [N, H, 2] (contiguous) for robots [robot0, robot0 + n) on `guide`, in place of whatever
         constraints it had: the cell table or the all-pairs table, by constraint_table, with the sampler's radius and weight."""
         guide.reset_extra_costs()
         if self.constraint_table == "binned":
@@ -159,31 +174,27 @@ class MultiRobotSampler:
         """One guided sampling round for the local robots: [n_local*B, H, D] normalised trajectories.  The in-kernel
         Philox noise is keyed by (seed, global trajectory index): every rank passes the SAME seed and gets exactly the
         rows the unsharded run would produce."""
-        return self._sample(self.hard_conds, self.n_local, self.guide, self.robot0, seed, x_init, step_noise, return_chain)
-
-    def _sample(self, hard_conds, n_robots, guide, robot0, seed, x_init=None, step_noise=None, return_chain=False):
-        """`sample` for robots [robot0, robot0 + n_robots) of an instance: their hard conditions, their guide"""
-        return self.model.run_inference(
-            None, hard_conds, n_samples=self.n_samples, n_robots=n_robots, horizon=H,
-            return_chain=return_chain, sample_fn=ddpm_sample_fn, guide=guide, n_guide_steps=self.n_guide_steps,
-            t_start_guide=self.t_start_guide, noise_std_extra_schedule_fn=lambda t: 0.5,
-            n_diffusion_steps_without_noise=self.n_extra, warm_start_path_b=x_init, step_noise=step_noise, seed=seed,
-            traj_index_base=robot0 * self.n_samples, device=self.device, n_streams=self.n_streams)
+        return self._run(self.hard_conds, self.n_local, self.guide, self.robot0, seed, x_init=x_init, step_noise=step_noise,
+                         return_chain=return_chain)
 
     def sample_local(self, prev_trajs, n_noising_steps=3, n_denoising_steps=3, seed=None):
         """A local re-plan round (the X-variants of CBS, cbs.py:424-430, mpd.py:460-517): forward-noise the previous round's normalised
         samples prev_trajs [n_local*B, H, D] n_noising_steps, then n_denoising_steps guided steps (+ the steps without noise) instead
         of the whole loop from noise.  Both draws are keyed by (seed, global trajectory index), as in `sample`."""
-        return self._sample_local(prev_trajs, n_noising_steps, n_denoising_steps, self.hard_conds, self.n_local, self.guide, self.robot0, seed)
+        return self._run(self.hard_conds, self.n_local, self.guide, self.robot0, seed, prev_trajs, n_noising_steps, n_denoising_steps)
 
-    def _sample_local(self, prev_trajs, n_noising_steps, n_denoising_steps, hard_conds, n_robots, guide, robot0, seed):
-        """`sample_local` for robots [robot0, robot0 + n_robots) of an instance"""
-        return self.model.run_local_inference(
-            prev_trajs, n_noising_steps, n_denoising_steps, None, hard_conds, n_samples=self.n_samples, n_robots=n_robots,
-            horizon=H, sample_fn=ddpm_sample_fn, guide=guide, n_guide_steps=self.n_guide_steps,
-            t_start_guide=self.t_start_guide, noise_std_extra_schedule_fn=lambda t: 0.5,
-            n_diffusion_steps_without_noise=self.n_extra, seed=seed, traj_index_base=robot0 * self.n_samples, device=self.device,
-            n_streams=self.n_streams)
+    def _run(self, hard_conds, n_robots, guide, robot0, seed, prev_trajs=None, n_noising_steps=3, n_denoising_steps=3, x_init=None,
+             step_noise=None, return_chain=False):
+        """The one sampling call, for robots [robot0, robot0 + n_robots) of an instance with their hard conditions and their guide:
+        `sample` (from noise, or from x_init) when prev_trajs is None, else `sample_local` from prev_trajs [n_robots * B, H, D]"""
+        shared = dict(n_samples=self.n_samples, n_robots=n_robots, horizon=H, sample_fn=ddpm_sample_fn, guide=guide,
+                      n_guide_steps=self.n_guide_steps, t_start_guide=self.t_start_guide, noise_std_extra_schedule_fn=lambda t: 0.5,
+                      n_diffusion_steps_without_noise=self.n_extra, seed=seed, traj_index_base=robot0 * self.n_samples,
+                      device=self.device, n_streams=self.n_streams)
+        if prev_trajs is None:
+            return self.model.run_inference(None, hard_conds, return_chain=return_chain, warm_start_path_b=x_init, step_noise=step_noise,
+                                            **shared)
+        return self.model.run_local_inference(prev_trajs, n_noising_steps, n_denoising_steps, None, hard_conds, **shared)
 
     def unnormalize(self, trajs_normalized):
         nz = self.dataset.normalizer
@@ -207,10 +218,13 @@ class MultiRobotSampler:
 
     def _pick(self, trajs_normalized, guide, robot0, n_robots, paths_all, collision_table):
         """`best_paths` for robots [robot0, robot0 + n_robots) of the instance paths_all -> (paths [n_robots, H, 2], idx, n_free); the
-        counts come from collision_table (a cell table of paths_all for these robots) where one is given, else from paths_all"""
+        counts come from collision_table (a cell table of paths_all for these robots) where one is given, else from paths_all.  The map
+        and the joint limits are checked in the robots' own frame; the collisions are counted, and the picks returned, in the frame the
+        robots share (_in_shared_frame)"""
         from . import postprocess as post
         t = self.unnormalize(trajs_normalized).contiguous()
         r = post.postprocess_batch(guide, t, n_robots=n_robots, smooth=False)
+        t = self._in_shared_frame(t, robot0, n_robots)
         if paths_all is None or self.n_robots < 2:
             idx, n_free = post.select_best(r.free_mask, n_robots, cost_a=r.path_length, cost_b=r.smoothness)
         else:
@@ -222,6 +236,11 @@ class MultiRobotSampler:
             idx, n_free = post.select_best(r.free_mask, n_robots, counts=counts.view(-1))
         tv = t.view(n_robots, self.n_samples, H, D)
         return tv[torch.arange(n_robots, device=t.device), idx.long()][..., :2].contiguous(), idx, n_free
+
+    def _in_shared_frame(self, t, robot0, n_robots):
+        """hook: the un-normalised samples t [n_robots * B, H, D] (contiguous) of robots [robot0, robot0 + n_robots) in the frame the
+        robots share.  Here every robot lives in that frame: t itself, no copy and no launch"""
+        return t
 
     def plan_round(self, paths_local, seed=None):
         """all-gather -> constraint table -> guided sampling -> new local best paths."""
@@ -262,13 +281,10 @@ class MultiRobotSampler:
         guide = self._subset_guide(n_sel)
         self._set_inter_robot_table(guide, paths_perm, sel_before, n_sel)
         # (a table of its own, not cached: _collision stays the caller's)
-        table = binned_collision_table(paths_perm, sel_before, n_sel, self.radius) if self.constraint_table == "binned" else None
-        if prev_trajs is None:
-            trajs = self._sample(hard_conds, n_sel, guide, sel_before, seed)
-        else:
-            trajs = self._sample_local(prev_trajs, n_noising_steps, n_denoising_steps, hard_conds, n_sel, guide, sel_before, seed)
+        table = self._build_collision_table(paths_perm, sel_before, n_sel) if self.constraint_table == "binned" else None
+        trajs = self._run(hard_conds, n_sel, guide, sel_before, seed, prev_trajs, n_noising_steps, n_denoising_steps)
         best, idx, n_free = self._pick(trajs, guide, sel_before, n_sel, paths_perm, table)
-        if getattr(self, "last_idx", None) is not None and self.last_idx.shape[0] == self.n_local:
+        if self.last_idx is not None and self.last_idx.shape[0] == self.n_local:
             # the robots not re-planned keep their entries
             self.last_idx = self.last_idx.clone().index_copy_(0, local_ids, idx.to(self.last_idx.dtype))
             self.last_n_free = self.last_n_free.clone().index_copy_(0, local_ids, n_free.to(self.last_n_free.dtype))
@@ -314,7 +330,7 @@ class MultiRobotSampler:
         rank with nothing selected still takes part in the all-gather.  PlanResult.replanned_counts lists the robots sampled per
         round.  It needs the inter-robot term and does not combine with repair (the round table is laid out per local robot and does
         not follow a permutation).  -> PlanResult."""
-        from .multi_agent import path_conflicts, read_summary, select_replan
+        from .multi_agent import path_conflicts, read_summary
         if replan not in ("all", "conflicted", "independent"):
             raise ValueError(f"plan_rounds_subset: replan must be 'all', 'conflicted' or 'independent', got {replan!r}")
         subset = replan != "all"
@@ -336,47 +352,64 @@ class MultiRobotSampler:
                                                            weight_grad_cost_constraints, self.w_soft, device=self.device)
         trajs, counts, k = None, [], 0
         replanned = [] if subset else None
-        B = self.n_samples
         while True:
             paths_all = all_gather_paths(paths_local, self.world_size, self.group).contiguous()
-            last = k == max_rounds
             select = subset and k > 0 and self.n_robots >= 2
             # one table a round: report, hard points, pick; or report and selection
             table = self._collision_table(paths_all) if rc is not None or select or self._report_on_own_table() else None
             summ, robots, lst = path_conflicts(paths_all, list_cap=list_cap, table=table)
             count, first = read_summary(summ)
             counts.append(count)
-            if last or (k > 0 and count == 0):
+            if k == max_rounds or (k > 0 and count == 0):
                 break
             if select:
-                sel = select_replan(paths_all, table, robots, replan, independent_iters)
-                replanned.append(sel.read_header()[0])
-                ids = self.selected_local_ids(sel)
-                prev = trajs.view(self.n_local, B, H, D).index_select(0, ids).view(-1, H, D) if local_rounds else None
-                trajs_sub, best_sub, ids = self.replan_round(paths_all, sel, seed + k, prev, n_noising_steps, n_denoising_steps)
-                if ids.numel():
-                    paths_local = paths_local.clone().index_copy_(0, ids, best_sub)       # (paths_all may be this very tensor)
-                    trajs.view(self.n_local, B, H, D).index_copy_(0, ids, trajs_sub.view(-1, B, H, D))
-                self._collision = None
-                k += 1
-                continue
-            others = paths_all if self.inter_robot else None
-            if rc is not None:
-                rc.append_conflicts(paths_all, table, t_pad=t_pad)
-                rc.set_soft(paths_all)
-                self.guide.set_packed_constraints(rc.tensors())
+                paths_local, n_sampled = self._subset_round(paths_all, table, robots, replan, independent_iters, seed + k, paths_local, trajs,
+                                                            local_rounds, n_noising_steps, n_denoising_steps)
             else:
-                self.set_other_paths(others)
-            if local_rounds and k > 0:
-                trajs = self.sample_local(trajs, n_noising_steps, n_denoising_steps, seed=seed + k)
-            else:
-                trajs = self.sample(seed=seed + k)
-            paths_local = self.best_paths(trajs, others, collision_table=table)
+                prev = trajs if local_rounds and k > 0 else None
+                trajs, paths_local = self._full_round(paths_all, table, rc, t_pad, seed + k, prev, n_noising_steps, n_denoising_steps)
+                n_sampled = self.n_robots
+                if subset:
+                    trajs = trajs.clone()       # the buffer later rounds scatter into (and not a view of the sampling chain)
             if subset:
-                replanned.append(self.n_robots)
-                trajs = trajs.clone()           # the buffer later rounds scatter into (and not a view of the sampling chain)
+                replanned.append(n_sampled)
             k += 1
         self.last_conflict_list = lst
         res = PlanResult(paths_local, trajs, k, counts, robots, count == 0, first, rc.dropped if rc is not None else None)
         res.replanned_counts = replanned
         return res
+
+    def _full_round(self, paths_all, table, rc, t_pad, seed, prev_trajs, n_noising_steps, n_denoising_steps):
+        """A round of the loop that samples every local robot: the inter-robot table of paths_all, or with rc (repair) the round's
+        conflicts (read off `table`) as hard points in front of it; sampling from noise, or from prev_trajs as sample_local does; the
+        pick (counted on `table` where there is one) -> (trajs, paths_local)"""
+        others = paths_all if self.inter_robot else None
+        if rc is not None:
+            rc.append_conflicts(paths_all, table, t_pad=t_pad)
+            rc.set_soft(paths_all)
+            self.guide.set_packed_constraints(rc.tensors())
+        else:
+            self.set_other_paths(others)
+        if prev_trajs is None:
+            trajs = self.sample(seed=seed)              # (the public methods: a subclass may put its own sampling there)
+        else:
+            trajs = self.sample_local(prev_trajs, n_noising_steps, n_denoising_steps, seed=seed)
+        return trajs, self.best_paths(trajs, others, collision_table=table)
+
+    def _subset_round(self, paths_all, table, robot_counts, replan, independent_iters, seed, paths_local, trajs, local_rounds,
+                      n_noising_steps, n_denoising_steps):
+        """A round of the loop that samples only the robots multi_agent.select_replan selects from the round's table and report
+        (replan_round; with local_rounds from their rows of trajs, else from noise) and scatters their samples into trajs
+        [n_local * B, H, D], in place, and their picks into a copy of paths_local -> (paths_local, robots selected over all ranks)"""
+        from .multi_agent import select_replan
+        B = self.n_samples
+        selection = select_replan(paths_all, table, robot_counts, replan, independent_iters)
+        n_selected = selection.read_header()[0]
+        ids = self.selected_local_ids(selection)
+        prev = trajs.view(self.n_local, B, H, D).index_select(0, ids).view(-1, H, D) if local_rounds else None
+        trajs_sub, best_sub, ids = self.replan_round(paths_all, selection, seed, prev, n_noising_steps, n_denoising_steps)
+        if ids.numel():
+            paths_local = paths_local.clone().index_copy_(0, ids, best_sub)       # (paths_all may be this very tensor)
+            trajs.view(self.n_local, B, H, D).index_copy_(0, ids, trajs_sub.view(-1, B, H, D))
+        self._collision = None
+        return paths_local, n_selected

@@ -8,6 +8,10 @@ models); the only new device code is the framed all-pairs table (constraints.fra
 mmd_framed_constraints_from_paths): robot r's block holds the other robots' points, shifted into r's frame, that fall into r's window
 widened by 1.0625 x the constraint radius.  A trajectory is clipped to the normaliser's limits, so a point outside that window can never
 act on it: the table is exact and its size follows the local density, not N.
+
+WorldRobotSampler is MultiRobotSampler with the frame put into the three hooks through which a round meets the other robots: the guide
+table (_set_inter_robot_table: the framed table), the collision cell table (_build_collision_table: laid over the world's limits) and the
+samples the pick counts and returns (_in_shared_frame: positions + offset).  Every method body, the loop included, is the base class's.
 """
 import numpy as np
 import torch
@@ -56,7 +60,8 @@ class WorldRobotSampler(MultiRobotSampler):
     limits.  The guided step reads the framed all-pairs table either way.  After every set_other_paths, `last_used` / `last_dropped`
     (int32 [n_local], on the device) tell the most slots a robot filled at one time step and the included points that found its block
     full.  `window` (an attribute, None = the default) is the culling window; a measurement may open it to compare with the all-pairs form.
-    plan_rounds(repair=True) and plan_rounds_subset(replan != "all") are refused: their tables are built without frames."""
+    plan_rounds(repair=True), plan_rounds_subset(replan != "all") and replan_round are refused: the round table of repair has no frames, and
+    the hooks here take the offsets in robot order, not in the order of a subset round's permuted instance."""
 
     def __init__(self, model, starts, goals, offsets, env_id="EnvEmpty2D", n_samples=64, rank=0, world_size=1,
                  norm_mins=synth.NORM_MINS, norm_maxs=synth.NORM_MAXS, n_guide_steps=20, start_guide_steps_fraction=0.5,
@@ -94,52 +99,33 @@ class WorldRobotSampler(MultiRobotSampler):
         self.window = None              # the culling window in a robot's frame; None: constraints.framed_window(LIMITS, radius)
         self.last_used = self.last_dropped = None
 
-    # ---- the three places where a round meets the other robots ----------------------------------------------------------------------
-    def _collision_table(self, paths_all):
+    # ---- the three places where the frame enters a round: MultiRobotSampler's hooks -------------------------------------------------------
+    def _build_collision_table(self, paths, robot0, n):
         """The collision cell table of the global paths over the world's limits (a robot outside them lands in a border cell: the cell
         index is clamped, which keeps neighbours in neighbouring cells)."""
-        if self._collision is None or self._collision[0] is not paths_all:
-            self._collision = (paths_all, binned_collision_table(paths_all.contiguous(), self.robot0, self.n_local, self.radius,
-                                                                 limits=self.world_limits, grid=self.world_grid))
-        return self._collision[1]
+        return binned_collision_table(paths, robot0, n, self.radius, limits=self.world_limits, grid=self.world_grid)
 
     def _report_on_own_table(self):
         return self.constraint_table == "binned" and self.n_robots >= 2
 
     def set_other_paths(self, paths_all):
-        """paths_all [N, H, 2] GLOBAL best paths of all robots (this device) or None: the framed table of the local robots for the guided
-        step, and with constraint_table="binned" the world collision table for best_paths."""
-        self._collision = None
+        """MultiRobotSampler.set_other_paths on GLOBAL best paths: the framed table of the local robots for the guided step, and with
+        constraint_table="binned" the world collision table for best_paths.  `last_used` / `last_dropped` are None where no table is built."""
         self.last_used = self.last_dropped = None
-        if paths_all is None or self.n_robots < 2:
-            self.guide.reset_extra_costs()
-            return
-        cons = framed_constraints_from_paths(paths_all.contiguous(), self.offsets, self.robot0, self.n_local, self.neighbor_slots,
-                                             self.radius, self.w_soft, self.window)
-        self.guide.set_packed_constraints(cons[:5])
-        self.last_used, self.last_dropped = cons[5], cons[6]
-        if self.constraint_table == "binned":
-            self._collision_table(paths_all)
+        super().set_other_paths(paths_all)
 
-    def _pick(self, trajs_normalized, guide, robot0, n_robots, paths_all, collision_table):
-        """MultiRobotSampler._pick with the samples shifted to the global frame for everything between robots: the map and the joint
-        limits are checked in the robot's own frame, the collisions are counted against the global paths, the picks are global."""
-        from . import postprocess as post
-        t = self.unnormalize(trajs_normalized).contiguous()
-        r = post.postprocess_batch(guide, t, n_robots=n_robots, smooth=False)
+    def _set_inter_robot_table(self, guide, paths, robot0, n):
+        """The framed all-pairs table, whatever constraint_table says (that chooses the pick's and the report's table only)"""
+        guide.reset_extra_costs()
+        cons = framed_constraints_from_paths(paths, self.offsets, robot0, n, self.neighbor_slots, self.radius, self.w_soft, self.window)
+        guide.set_packed_constraints(cons[:5])
+        self.last_used, self.last_dropped = cons[5], cons[6]
+
+    def _in_shared_frame(self, t, robot0, n_robots):
+        """The samples shifted to the global frame, for everything between robots: a copy, positions + offset, one fp32 add"""
         tg = t.view(n_robots, self.n_samples, H, D).clone()
-        tg[..., :2] += self.offsets[robot0:robot0 + n_robots, None, None, :]              # positions + offset, one fp32 add
-        if paths_all is None or self.n_robots < 2:
-            idx, n_free = post.select_best(r.free_mask, n_robots, cost_a=r.path_length, cost_b=r.smoothness)
-        else:
-            from .multi_agent import count_collisions, count_collisions_binned
-            flat = tg.view(-1, H, D)
-            if collision_table is not None:
-                counts = count_collisions_binned(flat, collision_table, n_robots)
-            else:
-                counts = count_collisions(flat, paths_all, robot0, n_robots)
-            idx, n_free = post.select_best(r.free_mask, n_robots, counts=counts.view(-1))
-        return tg[torch.arange(n_robots, device=t.device), idx.long()][..., :2].contiguous(), idx, n_free
+        tg[..., :2] += self.offsets[robot0:robot0 + n_robots, None, None, :]
+        return tg.view(-1, H, D)
 
     # ---- the loop: MultiRobotSampler's, through the methods above -------------------------------------------------------------------
     def plan_rounds(self, paths_local=None, max_rounds=8, seed=0, list_cap=0, repair=False, hard_slots=32,
@@ -155,15 +141,15 @@ class WorldRobotSampler(MultiRobotSampler):
         if repair:
             raise ValueError("WorldRobotSampler: repair=True is not supported: the round table is built without per-robot frames")
         if replan != "all":
-            raise ValueError(f"WorldRobotSampler: replan={replan!r} is not supported: replan_round builds its tables without per-robot frames")
-        res = MultiRobotSampler.plan_rounds_subset(self, paths_local, max_rounds, seed, list_cap, False, hard_slots,
+            raise ValueError(f"WorldRobotSampler: replan={replan!r} is not supported: the per-robot frames do not follow the permutation of a subset round")
+        res = MultiRobotSampler.plan_rounds_subset(self, paths_local, max_rounds, seed, list_cap, repair, hard_slots,
                                                    weight_grad_cost_constraints, t_pad, local_rounds, n_noising_steps, n_denoising_steps,
-                                                   "all", independent_iters)
+                                                   replan, independent_iters)
         res.dropped_constraints = self.last_dropped
         return res
 
     def replan_round(self, *args, **kwargs):
-        raise ValueError("WorldRobotSampler: replan_round is not supported: it builds its tables without per-robot frames")
+        raise ValueError("WorldRobotSampler: replan_round is not supported: the per-robot frames do not follow the permutation of a subset round")
 
 
 def random_world_instance(n_robots, extent, seed, env_id="EnvEmpty2D", min_separation=0.15, max_draws=200000):

@@ -153,8 +153,10 @@ def test_round_with_zero_offsets_is_the_base_round():
     zero = np.zeros((n, 2), np.float32)
     p0 = torch.from_numpy(synth.straight_line_paths(starts, goals, H)).cuda()
     base = MultiRobotSampler(gc.hip_model(T), starts, goals, env_id="EnvEmpty2D", n_samples=2 * B)
+    assert base.last_idx is None and base.last_n_free is None                     # nothing picked yet
     t_base, p_base = base.plan_round(p0, seed=31)
     w = _world(starts, goals, zero, n_samples=2 * B, neighbor_slots=n - 1)
+    assert w.last_idx is None and w.last_n_free is None
     t_w, p_w = w.plan_round(p0, seed=31)
     assert torch.isfinite(t_w).all() and torch.equal(t_w, t_base) and torch.equal(p_w, p_base)
     assert w.last_used.tolist() == [n - 1] * n and not w.last_dropped.any() and torch.equal(w.last_idx, base.last_idx)
@@ -164,6 +166,11 @@ def test_round_with_zero_offsets_is_the_base_round():
     r1.set_other_paths(p0)
     t_r = r1.sample(seed=31)
     assert torch.equal(t_r, t_base[3 * 2 * B:]) and torch.equal(r1.best_paths(t_r, p0), p_base[3:])
+    # the loops, each sampler from its own straight lines (the same ones): local rounds, and plan()
+    for loop in (lambda s: s.plan_rounds(max_rounds=2, seed=31, local_rounds=True), lambda s: s.plan(max_rounds=2, seed=31)):
+        rb, rw = loop(base), loop(w)
+        assert torch.equal(rw.paths_local, rb.paths_local) and torch.equal(rw.trajs, rb.trajs) and torch.equal(rw.robot_counts, rb.robot_counts)
+        assert rw.conflict_counts == rb.conflict_counts and rw.n_rounds == rb.n_rounds and torch.equal(w.last_idx, base.last_idx)
 
 
 # ---- 5. a world ----------------------------------------------------------------------------------------------------------------------------
