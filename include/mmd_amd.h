@@ -677,6 +677,34 @@ size_t mmd_sdf_grid_occupancy_work_bytes(int nx, int ny);
 int mmd_sdf_grid_from_occupancy(const unsigned char* occ_dev, int nx, int ny, float cell, float* grid_dev, void* work_dev,
                                 size_t work_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * World maps: one texture for a world larger than a tile, the robots' windows cut from it on the device
+ * ---------------------------------------------------------------------------------------------------------- */
+
+/* Robot windows of a WORLD texture (mmd_sdf_grid_from_occupancy of a bitmap of up to 2048 cells per side): n_windows slices of
+ * mmd_guide_desc.sdf_grids_dev, in one launch.  world_grid_dev [wnx][wny][4], origins_dev [n_windows][2] = (i0, j0) int32 on the device,
+ * windows_dev [n_windows][nx][ny][4]:
+ *   windows[k][ix][iy] = world[clamp(i0_k + ix, 0, wnx - 1)][clamp(j0_k + iy, 0, wny - 1)],
+ * all four words copied as bits (NaN payloads and the sign of a zero survive).  The origins are device data, so the source index is
+ * clamped per axis: that is the defined result for an origin outside the world (any int32), not an error.  A window of the world's
+ * transform is not the transform of the cropped bitmap: an obstacle just outside the window acts on the texels near its border, and
+ * overlapping windows agree where they overlap.  The windows must not overlap the world grid in memory.
+ * Error returns, before anything is launched: n_windows negative or above MMD_SDF_GRID_MAX_WINDOWS; wnx or wny below 1; nx (ny) below 1
+ * or above wnx (wny); wnx * wny of 2^31 - 256 or more; with n_windows > 0, a NULL world grid, origins or windows.  n_windows == 0
+ * returns 0 and launches nothing. */
+#define MMD_SDF_GRID_MAX_WINDOWS 65535
+int mmd_sdf_grid_windows(const float* world_grid_dev, int wnx, int wny, const int32_t* origins_dev /* [n][2] */, int n_windows,
+                         int nx, int ny, float* windows_dev /* [n][nx][ny][4] */, void* stream);
+
+/* The texel every consumer of a texture reads for a point: out_dev[i] = grid_dev[ix][iy] (four words) with, per axis and in fp32,
+ * ix = floor((px - lo[0]) / |hi[0] - lo[0]| * nx) clamped to [0, nx - 1] -- the sequence of the guided step's gather and of the
+ * post-sampling collision test, so "is this point free on the resident texture" has their answer.  points_dev [n_points][2],
+ * out_dev [n_points][4].  A point with a non-finite coordinate gives four NaNs and reads no texel.
+ * Error returns, before anything is launched: a negative n_points; nx or ny below 1 or nx * ny above 2^31 - 1; NULL limits, limits that are
+ * not finite or an axis of zero extent; with n_points > 0, a NULL grid, points or out.  n_points == 0 returns 0 and launches nothing. */
+int mmd_sdf_grid_lookup(const float* grid_dev, int nx, int ny, const float lo[2], const float hi[2],
+                        const float* points_dev /* [n][2] */, int n_points, float* out_dev /* [n][4] */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -179,6 +179,9 @@ _SIGNATURES = {
                                      C.c_void_p]),
     "mmd_sdf_grid_occupancy_work_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "mmd_sdf_grid_from_occupancy": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "mmd_sdf_grid_windows": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "mmd_sdf_grid_lookup": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_void_p, C.c_int,
+                                      C.c_void_p, C.c_void_p]),
 }
 
 # include/mmd_amd_debug.h: measurement hooks (bench.py / tools), not part of the drop-in boundary

@@ -104,6 +104,48 @@ __global__ __launch_bounds__(OCC_THREADS) void occupancy_sdf_kernel(const unsign
   grid[node] = out;
 }
 
+// ---- world maps: robot windows cut from one resident world texture, and the texel of a point (include/mmd_amd.h: mmd_sdf_grid_windows,
+// ---- mmd_sdf_grid_lookup).  Two memory-bound kernels: no LDS, no atomics, no scratch.
+constexpr int WIN_THREADS = 256;
+
+// The clamped gather windows[k][ix][iy] = world[clamp(i0_k + ix)][clamp(j0_k + iy)], one thread per output texel, cell = ix * ny + iy: a
+// wave stores 64 consecutive 16-byte texels and, off the world's border, loads 64 consecutive ones of a world row (two row segments where
+// the wave crosses a window row's end).  The window is blockIdx.y, so the origin is one wave-uniform 8-byte scalar load.  The texel
+// travels as four 32-bit words: NaN payloads and the sign of a zero survive.  The origin is device data and may be anything: it is
+// clamped to [-nx, wnx] first (the same texel as without, and i0 + ix then cannot overflow).
+__global__ __launch_bounds__(WIN_THREADS) void sdf_grid_windows_kernel(const uint4* __restrict__ world, int wnx, int wny,
+                                                                       const int2* __restrict__ origins, int nx, int ny, int n_cells,
+                                                                       uint4* __restrict__ windows) {
+  const int cell = blockIdx.x * WIN_THREADS + threadIdx.x;
+  if (cell >= n_cells) return;
+  const int k = blockIdx.y;
+  const int2 o = origins[k];
+  const int i0 = min(max(o.x, -nx), wnx), j0 = min(max(o.y, -ny), wny);
+  const int ix = cell / ny, iy = cell - ix * ny;
+  const int sx = min(max(i0 + ix, 0), wnx - 1), sy = min(max(j0 + iy, 0), wny - 1);
+  windows[(size_t)k * n_cells + cell] = world[(size_t)sx * wny + sy];
+}
+
+// The texel every consumer of a texture reads for a point (guide.hip's gather, postprocess.hip: point_collides): per axis
+// floor((p - lo) / |hi - lo| * n) in fp32, clamped to [0, n - 1] -- clamped as a float and then converted, the same integer as
+// clamp((int)floorf(..)) wherever that conversion is defined, and defined for every finite p.  One thread per point: an 8-byte load, one
+// 16-byte gather, one 16-byte store.  A point with a non-finite coordinate: four NaNs and no gather.
+__global__ __launch_bounds__(WIN_THREADS) void sdf_grid_lookup_kernel(const float4* __restrict__ grid, int nx, int ny, float lo_x, float lo_y,
+                                                                      float dim_x, float dim_y, const float2* __restrict__ points,
+                                                                      int n_points, float4* __restrict__ out) {
+  const int i = blockIdx.x * WIN_THREADS + threadIdx.x;
+  if (i >= n_points) return;
+  const float2 p = points[i];
+  if (!(fabsf(p.x) <= FLT_MAX && fabsf(p.y) <= FLT_MAX)) {
+    const float nan = __builtin_nanf("");
+    out[i] = make_float4(nan, nan, nan, nan);
+    return;
+  }
+  const int ix = (int)fminf(fmaxf(floorf((p.x - lo_x) / dim_x * (float)nx), 0.f), (float)(nx - 1));
+  const int iy = (int)fminf(fmaxf(floorf((p.y - lo_y) / dim_y * (float)ny), 0.f), (float)(ny - 1));
+  out[i] = grid[(size_t)ix * ny + iy];
+}
+
 }  // namespace mmd
 
 using namespace mmd;
@@ -153,6 +195,47 @@ int mmd_sdf_grid_from_occupancy(const unsigned char* occ_dev, int nx, int ny, fl
   MMD_HIP_CHECK(hipGetLastError());
   hipLaunchKernelGGL(occupancy_sdf_kernel, blocks, threads, 0, (hipStream_t)stream, occ_dev, (const short*)to_occ, (const short*)to_free,
                      nx, ny, n_nodes, cell, (float4*)grid_dev);
+  MMD_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+int mmd_sdf_grid_windows(const float* world_grid_dev, int wnx, int wny, const int32_t* origins_dev, int n_windows, int nx, int ny,
+                         float* windows_dev, void* stream) {
+  MMD_REQUIRE(n_windows >= 0 && n_windows <= MMD_SDF_GRID_MAX_WINDOWS, "mmd_sdf_grid_windows: n_windows = %d (0 to %d: the window is a block index)",
+              n_windows, MMD_SDF_GRID_MAX_WINDOWS);
+  MMD_REQUIRE(wnx >= 1 && wny >= 1, "mmd_sdf_grid_windows: a world of %d x %d texels (at least 1 x 1)", wnx, wny);
+  MMD_REQUIRE(nx >= 1 && ny >= 1 && nx <= wnx && ny <= wny, "mmd_sdf_grid_windows: windows of %d x %d texels (1 x 1 up to the world's %d x %d)",
+              nx, ny, wnx, wny);
+  MMD_REQUIRE((long long)wnx * wny <= INT_MAX - WIN_THREADS, "mmd_sdf_grid_windows: a world of %d x %d texels does not fit a 32-bit index", wnx,
+              wny);
+  if (n_windows == 0) return 0;
+  MMD_REQUIRE(world_grid_dev, "mmd_sdf_grid_windows: NULL world grid");
+  MMD_REQUIRE(origins_dev, "mmd_sdf_grid_windows: NULL origins");
+  MMD_REQUIRE(windows_dev, "mmd_sdf_grid_windows: NULL windows");
+  const int n_cells = nx * ny;                 // (<= wnx * wny)
+  hipLaunchKernelGGL(sdf_grid_windows_kernel, dim3((n_cells + WIN_THREADS - 1) / WIN_THREADS, n_windows), dim3(WIN_THREADS), 0,
+                     (hipStream_t)stream, (const uint4*)world_grid_dev, wnx, wny, (const int2*)origins_dev, nx, ny, n_cells,
+                     (uint4*)windows_dev);
+  MMD_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+int mmd_sdf_grid_lookup(const float* grid_dev, int nx, int ny, const float lo[2], const float hi[2], const float* points_dev, int n_points,
+                        float* out_dev, void* stream) {
+  MMD_REQUIRE(n_points >= 0 && n_points <= INT_MAX - WIN_THREADS, "mmd_sdf_grid_lookup: n_points = %d (0 to 2^31 - 257)", n_points);
+  MMD_REQUIRE(nx >= 1 && ny >= 1, "mmd_sdf_grid_lookup: a grid of %d x %d texels (at least 1 x 1)", nx, ny);
+  MMD_REQUIRE((long long)nx * ny <= INT_MAX, "mmd_sdf_grid_lookup: a grid of %d x %d texels does not fit a 32-bit index", nx, ny);
+  MMD_REQUIRE(lo && hi, "mmd_sdf_grid_lookup: NULL limits");
+  const float dim_x = fabsf(hi[0] - lo[0]), dim_y = fabsf(hi[1] - lo[1]);
+  MMD_REQUIRE(fabsf(lo[0]) <= FLT_MAX && fabsf(lo[1]) <= FLT_MAX && dim_x > 0.f && dim_x <= FLT_MAX && dim_y > 0.f && dim_y <= FLT_MAX,
+              "mmd_sdf_grid_lookup: limits (%g, %g) .. (%g, %g) (finite, a non-zero extent per axis)", (double)lo[0], (double)lo[1],
+              (double)hi[0], (double)hi[1]);
+  if (n_points == 0) return 0;
+  MMD_REQUIRE(grid_dev, "mmd_sdf_grid_lookup: NULL grid");
+  MMD_REQUIRE(points_dev, "mmd_sdf_grid_lookup: NULL points");
+  MMD_REQUIRE(out_dev, "mmd_sdf_grid_lookup: NULL out");
+  hipLaunchKernelGGL(sdf_grid_lookup_kernel, dim3((n_points + WIN_THREADS - 1) / WIN_THREADS), dim3(WIN_THREADS), 0, (hipStream_t)stream,
+                     (const float4*)grid_dev, nx, ny, lo[0], lo[1], dim_x, dim_y, (const float2*)points_dev, n_points, (float4*)out_dev);
   MMD_HIP_CHECK(hipGetLastError());
   return 0;
 }

@@ -13,6 +13,11 @@ resident device texture of a registered map is built by the library (mmd_sdf_gri
 Occupancy maps (register_occupancy_map): a [nx, ny] bitmap of the tile's cells -- a floor plan, a benchmark grid, a costmap -- instead
 of primitives.  occupancy_sdf_texture (numpy, an exact Euclidean distance transform with nearest-site tracking) is the definition;
 the resident texture is built by mmd_sdf_grid_from_occupancy, bit for bit the same.  Both kinds share one name space.
+
+World maps (register_world_map): one bitmap for a world larger than a tile, up to 2048 cells per side.  The world's texture is
+occupancy_sdf_texture of the whole bitmap; a robot's map is the 400 x 400 window of it at the robot's offset (world_map_windows is the
+definition, world_window_name its map name); on a device the windows are cut from the resident world texture by mmd_sdf_grid_windows.
+The section at the end of this file.
 """
 import ctypes as C
 
@@ -71,6 +76,7 @@ def register_map(name, boxes=(), spheres=()):
     if _EXTRA_SUFFIX in name:
         raise ValueError(f"register_map: {name!r} contains {_EXTRA_SUFFIX!r}, which is stripped from map names")
     content = _checked_primitives(boxes, spheres)
+    _refuse_world_name(name, "register_map")
     if name in _OCCUPANCY:
         raise ValueError(f"register_map: {name!r} is registered as an occupancy map")
     if name in _REGISTERED and _REGISTERED[name] != content:
@@ -98,6 +104,8 @@ def registered_maps():
 def map_primitives(name):
     """(boxes [(cx, cy, size_x, size_y)], spheres [(cx, cy, r)]) of a shipped or registered map."""
     base = _base_name(name)
+    if _window_of(base) is not None:
+        raise ValueError(f"map_primitives: {name!r} is a window of a world map (world_map_occupancy returns the world's bitmap)")
     if base in _OCCUPANCY:
         raise ValueError(f"map_primitives: {name!r} is an occupancy map (map_occupancy returns its bitmap)")
     if base in _REGISTERED:
@@ -119,8 +127,13 @@ def is_occupancy_map(name):
 
 def map_has_obstacles(name):
     """Whether the map's fixed objects have an SDF grid (mmd_guide_desc.n_grids = 1).  A registered map always has one, even without
-    primitives or occupied cells: update_map / update_occupancy_map may give it some while a guide that reads the grid is alive."""
+    primitives or occupied cells: update_map / update_occupancy_map may give it some while a guide that reads the grid is alive.
+    A window of a world map: whether the world has an occupied cell now (a guide built on a window of an empty world reads no grid, and
+    an update_world_map that adds the first obstacle does not reach it)."""
     base = _base_name(name)
+    window = _window_of(base)
+    if window is not None:
+        return b"\x01" in _WORLD_MAPS[window[0]][1]
     return base in _REGISTERED or base in _OCCUPANCY or len(MAP_BOXES[base][0]) > 0
 
 
@@ -151,7 +164,7 @@ def _primitives_sdf(x, boxes, spheres):
 def map_sdf(points, map_name):
     x = torch.as_tensor(points, dtype=torch.float32)
     base = _base_name(map_name)
-    if base in _OCCUPANCY:
+    if base in _OCCUPANCY or _window_of(base) is not None:
         return _nearest_cell_sdf(x, sdf_grid_texture(base))
     if base in _REGISTERED:
         return _primitives_sdf(x, *_REGISTERED[base])
@@ -185,6 +198,11 @@ def _drop_host_texture(name):
 def sdf_grid_texture(map_name, cell_size=SDF_CELL_SIZE):
     """float32 numpy [nx, ny, 4] = (sdf, dsdf/dx, dsdf/dy, 0): the texture layout mmd_guide_desc expects."""
     base = _base_name(map_name)
+    window = _window_of(base)
+    if window is not None:                                       # (the host crop of the world's texture, which is cached by content)
+        if grid_shape(cell_size) != grid_shape():
+            raise ValueError(f"sdf_grid_texture: the world map {window[0]!r} has one cell per grid cell at {SDF_CELL_SIZE}, not at {cell_size}")
+        return world_map_windows(window[0], [window[1:]])[0]
     content = _OCCUPANCY.get(base, _REGISTERED.get(base))        # (None: a shipped map, whose content never changes)
     hit = _TEXTURE_CACHE.get((base, cell_size))
     if hit is not None and hit[0] == content:
@@ -374,6 +392,7 @@ def register_occupancy_map(name, occupancy):
     taken name -- of either kind -- is refused."""
     _checked_map_name(name, "register_occupancy_map")
     content = _checked_occupancy(occupancy, "register_occupancy_map", grid_shape()).tobytes()
+    _refuse_world_name(name, "register_occupancy_map")
     if name in _REGISTERED:
         raise ValueError(f"register_occupancy_map: {name!r} is registered as a map of primitives")
     if name in _OCCUPANCY and _OCCUPANCY[name] != content:
@@ -409,8 +428,16 @@ def device_occupancy_sdf_grid(occupancy, device, out=None):
     else:
         host = occupancy.cpu().numpy() if isinstance(occupancy, torch.Tensor) else occupancy
         occ = torch.from_numpy(_checked_occupancy(host, "device_occupancy_sdf_grid", (nx, ny))).to(device)
+    return _occupancy_build(occ, out)
+
+
+def _occupancy_build(occ, out):
+    """mmd_sdf_grid_from_occupancy of the uint8 device bitmap occ [nx, ny] into out [nx, ny, 4], with a workspace of its own, on the
+    current stream of out's device."""
+    from . import _lib
+    nx, ny = occ.shape
     n_bytes = int(_lib.load().mmd_sdf_grid_occupancy_work_bytes(nx, ny))
-    work = torch.empty(n_bytes, dtype=torch.uint8, device=device)
+    work = torch.empty(n_bytes, dtype=torch.uint8, device=out.device)
     _lib.launch("mmd_sdf_grid_from_occupancy", out, C.c_void_p(occ.data_ptr()), nx, ny, SDF_CELL_SIZE, _lib.require_gpu(out, "out"),
                 C.c_void_p(work.data_ptr()), n_bytes)
     return out
@@ -462,3 +489,282 @@ def resize_occupancy(occ, shape=(400, 400)):
     jx = (2 * np.arange(nx, dtype=np.int64) + 1) * occ.shape[0] // (2 * nx)
     jy = (2 * np.arange(ny, dtype=np.int64) + 1) * occ.shape[1] // (2 * ny)
     return np.ascontiguousarray(occ[jx[:, None], jy[None, :]])
+
+
+# ---- world maps: one bitmap for a world larger than a tile, a robot's map is a window of it ------------------------------------------------
+# register_world_map takes a floor plan of up to OCCUPANCY_MAX_SIDE cells per side at the tile's cell pitch.  Its SDF texture is
+# occupancy_sdf_texture of the whole bitmap (world_map_texture); the map of a robot whose window covers global offset + LIMITS is the
+# 400 x 400 crop of that texture at the window's origin cell (world_map_windows).  The crop of the world's transform is NOT the
+# transform of the cropped bitmap: an obstacle just outside a window still acts on the cells near its border, and overlapping windows
+# agree where they overlap.  A window has a map name of its own (world_window_name), usable wherever a map name is.  On a device the world
+# texture is resident once (guides.device_world_texture, built by mmd_sdf_grid_from_occupancy) and the windows of a map set are cut
+# from it by mmd_sdf_grid_windows.  World maps have a registry of their own: registered_maps() does not list them.
+_WORLD_MAPS = {}           # name -> ((WX, WY), the uint8 bitmap (0 / 1) as bytes, row-major, (origin x, origin y) as floats)
+_WORLD_TEXTURE_CACHE = {}  # name -> (content the texture was built from, texture)
+_WINDOW_SEPARATOR = "@"    # a window's map name: "<world>@<i0>,<j0>", the window's origin cell in the world
+
+
+def _window_of(map_name):
+    """(world, i0, j0) of the map name of a window of a REGISTERED world map (the last '@' splits it), else None."""
+    head, sep, tail = _base_name(map_name).rpartition(_WINDOW_SEPARATOR) if isinstance(map_name, str) else ("", "", "")
+    if not sep or head not in _WORLD_MAPS:
+        return None
+    cells = tail.split(",")
+    if len(cells) != 2 or not all(c.isascii() and c.isdigit() for c in cells):
+        return None
+    return head, int(cells[0]), int(cells[1])
+
+
+def _refuse_world_name(name, what):
+    if name in _WORLD_MAPS:
+        raise ValueError(f"{what}: {name!r} is registered as a world map")
+    if _window_of(name) is not None:
+        raise ValueError(f"{what}: {name!r} names a window of the world map {_window_of(name)[0]!r}")
+
+
+def _host_array(a):
+    return a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+
+
+def _world(name, what):
+    if name not in _WORLD_MAPS:
+        raise ValueError(f"{what}: {name!r} is not a registered world map (registered: {list(registered_world_maps())})")
+    return _WORLD_MAPS[name]
+
+
+def _checked_world_occupancy(occupancy, what, shape=None):
+    occ = _checked_occupancy(_host_array(occupancy), what, shape)
+    lo = grid_shape()
+    if not all(lo[k] <= occ.shape[k] <= OCCUPANCY_MAX_SIDE for k in range(2)):
+        raise ValueError(f"{what}: a world of {occ.shape[0]} x {occ.shape[1]} cells; each side holds {lo[0]} x {lo[1]} (one window) to "
+                         f"{OCCUPANCY_MAX_SIDE} cells")
+    return occ
+
+
+def register_world_map(name, occupancy, origin=None):
+    """A map larger than a tile: occupancy [WX, WY], non-zero = occupied, indexed [ix, iy] like the texture, each side between
+    grid_shape() (400) and OCCUPANCY_MAX_SIDE (2048) cells of SDF_CELL_SIZE.  origin: the global position of the lower corner of cell
+    (0, 0); default (-WX, -WY) * SDF_CELL_SIZE / 2, the world centred on the global origin.  The name rules are register_map's; world
+    maps have a registry of their own (registered_world_maps), but the names are shared: a shipped or registered tile map's name is
+    refused here, a world map's name (and the name of one of its windows) is refused by register_map and register_occupancy_map.  The
+    same content under a name twice is a no-op; other content under a taken name is refused (update_world_map replaces a bitmap)."""
+    _checked_map_name(name, "register_world_map")
+    if _WINDOW_SEPARATOR in name and _window_of(name) is not None:
+        raise ValueError(f"register_world_map: {name!r} names a window of the world map {_window_of(name)[0]!r}")
+    occ = _checked_world_occupancy(occupancy, "register_world_map")
+    if origin is None:
+        origin = (-occ.shape[0] * SDF_CELL_SIZE / 2.0, -occ.shape[1] * SDF_CELL_SIZE / 2.0)
+    org = np.asarray(_host_array(origin), dtype=np.float64).reshape(-1)
+    if org.shape != (2,) or not np.isfinite(org).all():
+        raise ValueError(f"register_world_map: origin = two finite numbers, got {origin!r}")
+    if name in _REGISTERED or name in _OCCUPANCY:
+        raise ValueError(f"register_world_map: {name!r} is registered as a tile map")
+    taken = [n for n in registered_maps() if n.startswith(name + _WINDOW_SEPARATOR)]
+    if name not in _WORLD_MAPS and taken:
+        raise ValueError(f"register_world_map: the registered map {taken[0]!r} has the form of a window name of {name!r}")
+    content = (tuple(occ.shape), occ.tobytes(), (float(org[0]), float(org[1])))
+    if name in _WORLD_MAPS and _WORLD_MAPS[name] != content:
+        raise ValueError(f"register_world_map: {name!r} is registered with another bitmap or origin (update_world_map replaces the bitmap)")
+    _WORLD_MAPS[name] = content
+
+
+def update_world_map(name, occupancy):
+    """Replace a world map's bitmap (same shape, same origin).  Every resident world texture of the name is rebuilt in place and every
+    resident window slice cut from it is cut again in place (same storage, same pointers), on the current stream of its device, one
+    cut launch per map set: live guides and samplers see the new obstacles on their next call.  The host texture is dropped."""
+    shape, _, origin = _world(name, "update_world_map")
+    occ = _checked_world_occupancy(occupancy, "update_world_map", shape)
+    _WORLD_MAPS[name] = (shape, occ.tobytes(), origin)
+    _WORLD_TEXTURE_CACHE.pop(name, None)
+    from . import guides
+    guides.rebuild_world_textures(name)
+
+
+def unregister_world_map(name):
+    """Forget a world map, its host texture, its resident world textures and every resident map set that holds one of its windows
+    (objects built on one keep theirs)."""
+    _world(name, "unregister_world_map")
+    from . import guides
+    guides.drop_world_textures(name)            # (while the name still parses as a world's)
+    del _WORLD_MAPS[name]
+    _WORLD_TEXTURE_CACHE.pop(name, None)
+
+
+def registered_world_maps():
+    """The names of the registered world maps, sorted."""
+    return tuple(sorted(_WORLD_MAPS))
+
+
+def is_world_map(name):
+    return isinstance(name, str) and name in _WORLD_MAPS
+
+
+def is_world_window(name):
+    """Whether `name` is the map name of a window of a registered world map (world_window_name)."""
+    return _window_of(name) is not None
+
+
+def world_window(name):
+    """(world, (i0, j0)) of a window's map name."""
+    w = _window_of(name)
+    if w is None:
+        raise ValueError(f"world_window: {name!r} is not a window of a registered world map")
+    return w[0], (w[1], w[2])
+
+
+def world_map_occupancy(name):
+    """The bitmap of a world map: a uint8 [WX, WY] copy, 1 = occupied."""
+    shape, content, _ = _world(name, "world_map_occupancy")
+    return np.frombuffer(content, np.uint8).reshape(shape).copy()
+
+
+def world_map_origin(name):
+    """The global position of the lower corner of cell (0, 0)."""
+    return _world(name, "world_map_origin")[2]
+
+
+def world_map_limits(name):
+    """(lo, hi), global: the lower corner of cell (0, 0) and the upper corner of the last cell."""
+    shape, _, origin = _world(name, "world_map_limits")
+    return origin, tuple(origin[k] + shape[k] * SDF_CELL_SIZE for k in range(2))
+
+
+def world_map_texture(name):
+    """float32 [WX, WY, 4]: occupancy_sdf_texture of the world's bitmap, THE DEFINITION of the world's texture.  Cached by content
+    (seconds in numpy at 640 x 520, minutes at 2048 x 2048: the resident device texture is the practical one at full size)."""
+    _, content, _ = _world(name, "world_map_texture")
+    hit = _WORLD_TEXTURE_CACHE.get(name)
+    if hit is None or hit[0] != content:
+        hit = _WORLD_TEXTURE_CACHE[name] = (content, occupancy_sdf_texture(world_map_occupancy(name)))
+    return hit[1]
+
+
+def _checked_window_origins(name, origins, what):
+    """int32 [n, 2] origin cells, each a window that lies inside the world"""
+    shape = _world(name, what)[0]
+    raw = _host_array(origins)
+    org = raw.reshape(-1, 2)
+    if raw.size == 0 or org.dtype.kind not in "iu":
+        raise ValueError(f"{what}: origins [n, 2] of integer cells, got dtype {raw.dtype}, shape {raw.shape}")
+    n = grid_shape()
+    bad = np.flatnonzero(((org < 0) | (org > np.asarray([shape[0] - n[0], shape[1] - n[1]]))).any(1))
+    if bad.size:
+        k = int(bad[0])
+        raise ValueError(f"{what}: window {k} at origin cell {org[k].tolist()} is outside the world {name!r}: origins 0 .. "
+                         f"{[shape[0] - n[0], shape[1] - n[1]]}")
+    return np.ascontiguousarray(org, dtype=np.int32)
+
+
+def world_map_windows(name, origins):
+    """float32 [n, 400, 400, 4]: window k is world_map_texture(name)[i0:i0 + 400, j0:j0 + 400] for origins[k] = (i0, j0), a copy, bit for
+    bit: THE DEFINITION of a window's texture.  Origins outside [0, W - 400] are refused."""
+    org = _checked_window_origins(name, origins, "world_map_windows")
+    tex = world_map_texture(name)
+    nx, ny = grid_shape()
+    return np.stack([tex[i0:i0 + nx, j0:j0 + ny] for i0, j0 in org.tolist()])
+
+
+def _window_cells(name, offsets, what):
+    """(q, shape): the windows' origins in cells, float64 [n, 2], not yet rounded -- q = (offset + LIMITS[0] - origin) / cell"""
+    shape, _, origin = _world(name, what)
+    off = np.asarray(_host_array(offsets), dtype=np.float64)
+    if off.size == 0 or off.shape[-1] != 2:
+        raise ValueError(f"{what}: offsets [n, 2], got shape {off.shape}")
+    return (off.reshape(-1, 2) + np.asarray(LIMITS[0], np.float64) - np.asarray(origin, np.float64)) / np.float64(SDF_CELL_SIZE), shape
+
+
+def world_map_window_origins(name, offsets):
+    """int32 [N, 2]: the origin cells of the robots' windows.  Robot r's window covers global offsets[r] + LIMITS, so its origin is
+    (offset + LIMITS[0] - origin) / SDF_CELL_SIZE per axis, in float64.  It must lie within 1e-3 of an integer (float32 offsets that are
+    multiples of the cell pitch are not exact; half a cell off is an error) and inside [0, W - 400]; otherwise ValueError names the
+    first robot at fault and whether it is off the cell grid or outside the world.  snap_to_world_map gives offsets that pass."""
+    q, shape = _window_cells(name, offsets, "world_map_window_origins")
+    r = np.rint(q)
+    n = grid_shape()
+    with np.errstate(invalid="ignore"):
+        off_grid = ~(np.abs(q - r) <= 1e-3)
+        outside = ~off_grid & ((r < 0) | (r > np.asarray([shape[0] - n[0], shape[1] - n[1]], np.float64)))
+    bad = np.flatnonzero((off_grid | outside).any(1))
+    if bad.size:
+        k = int(bad[0])
+        if off_grid[k].any():
+            raise ValueError(f"world_map_window_origins: the window of robot {k} is off the cell grid of {name!r}: its origin is at cell "
+                             f"{q[k].tolist()} (snap_to_world_map gives the nearest valid offsets)")
+        raise ValueError(f"world_map_window_origins: the window of robot {k} is outside the world {name!r}: its origin cell "
+                         f"{r[k].astype(np.int64).tolist()} is not in 0 .. {[shape[0] - n[0], shape[1] - n[1]]}")
+    return r.astype(np.int32)
+
+
+def snap_to_world_map(name, offsets):
+    """float32 offsets of the shape given: per robot the nearest offsets whose window starts on a cell and lies inside the world."""
+    q, shape = _window_cells(name, offsets, "snap_to_world_map")
+    if not np.isfinite(q).all():
+        raise ValueError("snap_to_world_map: every offset must be finite")
+    n = grid_shape()
+    cells = np.clip(np.rint(q), 0, np.asarray([shape[0] - n[0], shape[1] - n[1]], np.float64))
+    origin = np.asarray(_WORLD_MAPS[name][2], np.float64)
+    out = cells * np.float64(SDF_CELL_SIZE) + origin - np.asarray(LIMITS[0], np.float64)
+    return out.astype(np.float32).reshape(np.shape(_host_array(offsets)))
+
+
+def world_window_name(name, offset_or_origin):
+    """The map name of one window of the world map `name`, usable wherever a map name is (GuideManagerTrajectoriesWithVelocity env_id /
+    robot_env_ids, MPD env_id, MPDEnsemble env_ids, MultiRobotSampler env_id): "<name>@<i0>,<j0>".  offset_or_origin: two INTEGERS are the
+    window's origin cell (i0, j0); two floats are a robot's offset (world_map_window_origins' rules apply).  Windows at equal origins have
+    equal names and share a resident slice."""
+    a = _host_array(offset_or_origin)
+    if a.size != 2:
+        raise ValueError(f"world_window_name: one offset (x, y) or one origin cell (i0, j0), got shape {a.shape}")
+    if a.dtype.kind in "iu":
+        i0, j0 = _checked_window_origins(name, a.reshape(1, 2), "world_window_name")[0].tolist()
+    else:
+        i0, j0 = world_map_window_origins(name, a.reshape(1, 2))[0].tolist()
+    return f"{name}{_WINDOW_SEPARATOR}{i0},{j0}"
+
+
+def _texel_indices(points, lo, hi, shape):
+    """(ix, iy, finite): the texel of float32 points [n, 2] on a grid of `shape` over lo .. hi, the fp32 sequence of every consumer of a
+    texture and of mmd_sdf_grid_lookup: floor((p - lo) / |hi - lo| * n) clamped to [0, n - 1] (as a float, then converted)."""
+    f = np.float32
+    lo, hi = np.asarray(lo, f), np.asarray(hi, f)
+    dim = np.abs(hi - lo)
+    finite = np.isfinite(points).all(1)
+    p = np.where(finite[:, None], points, f(0))
+    with np.errstate(over="ignore"):
+        idx = [np.clip(np.floor((p[:, k] - lo[k]) / dim[k] * f(shape[k])), f(0), f(shape[k] - 1)).astype(np.int64) for k in range(2)]
+    return idx[0], idx[1], finite
+
+
+def world_map_sdf(points_global, name, device=None):
+    """The world texture's nearest-cell value at global points [..., 2] -> float32 [...], NaN at a point with a non-finite coordinate.
+    device=None: on the host texture (world_map_texture: slow to build at full world size), a CPU tensor.  With a device: read off the
+    resident world texture by mmd_sdf_grid_lookup, a tensor on that device -- the practical source of truth for "is this start free"."""
+    shape = _world(name, "world_map_sdf")[0]
+    lo, hi = world_map_limits(name)
+    if device is None:
+        pts = np.ascontiguousarray(_host_array(points_global), dtype=np.float32)
+        ix, iy, finite = _texel_indices(pts.reshape(-1, 2), lo, hi, shape)
+        val = np.where(finite, world_map_texture(name)[ix, iy, 0], np.float32(np.nan))
+        return torch.from_numpy(np.ascontiguousarray(val.reshape(pts.shape[:-1]), dtype=np.float32))
+    from . import _lib, guides
+    tex = guides.device_world_texture(name, device)
+    pts = torch.as_tensor(points_global, dtype=torch.float32).to(tex.device).contiguous()
+    flat = pts.reshape(-1, 2)
+    out = torch.empty(flat.shape[0], 4, dtype=torch.float32, device=tex.device)
+    _lib.launch("mmd_sdf_grid_lookup", tex, _lib.require_gpu(tex, "world texture"), shape[0], shape[1], (C.c_float * 2)(*lo),
+                (C.c_float * 2)(*hi), _lib.require_gpu(flat, "points"), flat.shape[0], _lib.require_gpu(out, "out"))
+    return out[:, 0].reshape(pts.shape[:-1])
+
+
+def device_world_sdf_grid(name, device, out=None):
+    """The [WX, WY, 4] texture of the world map `name`, built on `device` by mmd_sdf_grid_from_occupancy: world_map_texture bit for
+    bit, for the upload of one byte per cell.  out= rebuilds a resident texture in place on the current stream."""
+    shape = _world(name, "device_world_sdf_grid")[0]
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    if out is None:
+        out = torch.empty(shape[0], shape[1], 4, dtype=torch.float32, device=device)
+    elif tuple(out.shape) != (shape[0], shape[1], 4) or out.device != device:
+        raise ValueError(f"device_world_sdf_grid: out must be [{shape[0]}, {shape[1]}, 4] on {device}, got {tuple(out.shape)} on {out.device}")
+    return _occupancy_build(torch.from_numpy(world_map_occupancy(name)).to(device), out)

@@ -108,7 +108,7 @@ class MultiRobotSampler:
         self.dataset = TrajectoryDatasetFacade(norm_mins, norm_maxs)
         self.env_id = env_id
         self.guide = GuideManagerTrajectoriesWithVelocity(self.dataset, env_id=env_id, n_robots=self.n_local,
-                                                          device=device)
+                                                          robot_env_ids=self._robot_env_ids(self.robot0, self.n_local), device=device)
         self._subset_guides = {}        # replan_round: a guide per subset size, on the same map (the resident SDF texture is shared)
         sl = slice(self.robot0, self.robot0 + self.n_local)
         self._ends = (starts[sl], goals[sl])      # plan(): the straight lines the first round starts from
@@ -132,7 +132,12 @@ class MultiRobotSampler:
         self.last_conflict_list = None              # plan(list_cap > 0): the first records of the final report
 
     # ---- the three places where a round meets the other robots: each takes (paths, robot0, n), so that the full round and the subset
-    # ---- round (replan_round) run the same code; a subclass with frames (world.WorldRobotSampler) overrides only the three hooks
+    # ---- round (replan_round) run the same code; a subclass with frames (world.WorldRobotSampler) overrides only the three hooks, and
+    # ---- _robot_env_ids where its robots read maps of their own
+    def _robot_env_ids(self, robot0, n):
+        """hook: the map names of robots [robot0, robot0 + n) for a guide's robot_env_ids, or None: every robot on the sampler's env_id"""
+        return None
+
     def _build_collision_table(self, paths, robot0, n):
         """hook: the collision cell table (every time step listed) of `paths` [N, H, 2] (contiguous) for robots [robot0, robot0 + n)"""
         return binned_collision_table(paths, robot0, n, self.radius)
@@ -254,6 +259,7 @@ class MultiRobotSampler:
         g = self._subset_guides.get(n_robots)
         if g is None:
             g = self._subset_guides[n_robots] = GuideManagerTrajectoriesWithVelocity(self.dataset, env_id=self.env_id, n_robots=n_robots,
+                                                                                     robot_env_ids=self._robot_env_ids(self.robot0, n_robots),
                                                                                      device=self.device)
         return g
 

@@ -19,6 +19,7 @@ import torch
 from . import synth
 from .constraints import (BIN_CELL_SLACK, VERTEX_CONSTRAINT_RADIUS, binned_collision_table, framed_constraints_from_paths,
                           framed_slot_bound)
+from . import environments
 from .environments import LIMITS, map_has_obstacles, map_sdf
 from .multi_robot import D, H, MultiRobotSampler, shard_range
 
@@ -57,8 +58,10 @@ class WorldRobotSampler(MultiRobotSampler):
     the hard conditions are start - offset and goal - offset, which must lie in the normaliser's position limits.  neighbor_slots: the
     slots per robot of the framed table (None: constraints.framed_slot_bound, computed once from the offsets).  constraint_table="dense"
     counts the pick's collisions over all pairs; "binned" reads them, and plan()'s report, off a collision cell table over the world's
-    limits.  The guided step reads the framed all-pairs table either way.  After every set_other_paths, `last_used` / `last_dropped`
-    (int32 [n_local], on the device) tell the most slots a robot filled at one time step and the included points that found its block
+    limits.  The guided step reads the framed all-pairs table either way.  env_id may name a world map (environments.register_world_map):
+    robot r's map is then the window of the world's texture at offsets[r], which must lie on the world's cell grid and inside the world
+    (environments.snap_to_world_map); robots at equal offsets share a resident slice.  Starts and goals inside an obstacle are not refused.
+    After every set_other_paths, `last_used` / `last_dropped` (int32 [n_local], on the device) tell the most slots a robot filled at one time step and the included points that found its block
     full.  `window` (an attribute, None = the default) is the culling window; a measurement may open it to compare with the all-pairs form.
     plan_rounds(repair=True), plan_rounds_subset(replan != "all") and replan_round are refused: the round table of repair has no frames, and
     the hooks here take the offsets in robot order, not in the order of a subset round's permuted instance."""
@@ -84,6 +87,11 @@ class WorldRobotSampler(MultiRobotSampler):
             neighbor_slots = framed_slot_bound(offsets, robot0, n_local, LIMITS, radius) if n >= 2 else 1
         if n >= 2 and not 1 <= int(neighbor_slots) <= n - 1:
             raise ValueError(f"WorldRobotSampler: neighbor_slots must be in [1, {n - 1}], got {neighbor_slots}")
+        # a world map: every robot reads its own window of it; offsets off the cell grid or outside the world raise here, before any device work
+        self._window_ids = None
+        if environments.is_world_map(env_id):
+            self._window_ids = [environments.world_window_name(env_id, org)
+                                for org in environments.world_map_window_origins(env_id, offsets)]
         super().__init__(model, local_starts, local_goals, env_id=env_id, n_samples=n_samples, rank=rank, world_size=world_size,
                          norm_mins=norm_mins, norm_maxs=norm_maxs, n_guide_steps=n_guide_steps,
                          start_guide_steps_fraction=start_guide_steps_fraction,
@@ -100,6 +108,11 @@ class WorldRobotSampler(MultiRobotSampler):
         self.last_used = self.last_dropped = None
 
     # ---- the three places where the frame enters a round: MultiRobotSampler's hooks -------------------------------------------------------
+    def _robot_env_ids(self, robot0, n):
+        """On a world map (environments.register_world_map) robot r's map is its window of the world, environments.world_window_name(env_id,
+        offsets[r]); on a tile map every robot's window shows that tile (None)"""
+        return None if self._window_ids is None else self._window_ids[robot0:robot0 + n]
+
     def _build_collision_table(self, paths, robot0, n):
         """The collision cell table of the global paths over the world's limits (a robot outside them lands in a border cell: the cell
         index is clamped, which keeps neighbours in neighbouring cells)."""
@@ -183,6 +196,37 @@ def random_world_instance(n_robots, extent, seed, env_id="EnvEmpty2D", min_separ
         if snapped and not bool((map_sdf(ends, env_id) > OBSTACLE_MARGIN).all()):
             continue
         st, go = ends[:1] + off, ends[1:] + off
+        if len(starts) and not (np.all(np.sqrt(np.sum((st - starts) ** 2, axis=1)) > min_separation)
+                                and np.all(np.sqrt(np.sum((go - goals) ** 2, axis=1)) > min_separation)):
+            continue
+        starts, goals, offsets = np.concatenate([starts, st]), np.concatenate([goals, go]), np.concatenate([offsets, off])
+    return starts, goals, offsets
+
+
+def random_world_map_instance(name, n_robots, seed, min_separation=0.15, max_draws=200000):
+    """A random many-robot instance on the world map `name` (environments.register_world_map) -> (starts, goals, offsets), float32
+    [n_robots, 2] each, starts and goals global.  Drawn as random_world_instance draws, from numpy.random.Generator(PCG64(seed)): per
+    robot a window origin uniform over the valid origin cells of the world (so the offset lies on the cell grid and the window inside the
+    world), then a start and a goal uniform in +-0.95 of the window; the draw is accepted iff the world texture's nearest-cell value
+    (environments.world_map_sdf on the host texture) at both global points exceeds OBSTACLE_MARGIN and the start (the goal) is more than
+    min_separation away from every earlier robot's start (goal).  Raises RuntimeError after max_draws draws."""
+    shape = environments.world_map_occupancy(name).shape
+    nx, ny = environments.grid_shape()
+    rng = np.random.Generator(np.random.PCG64(seed))
+    starts, goals, offsets = (np.zeros((0, 2), np.float32) for _ in range(3))
+    draws = 0
+    while len(starts) < n_robots:
+        if draws >= max_draws:
+            raise RuntimeError(f"random_world_map_instance: {n_robots} robots not placed on the world map {name!r} after {max_draws} draws "
+                               f"(min_separation={min_separation}); {len(starts)} placed")
+        draws += 1
+        cells = np.stack([rng.integers(0, shape[0] - nx + 1, (1,)), rng.integers(0, shape[1] - ny + 1, (1,))], axis=1)
+        off = environments.snap_to_world_map(name, (cells * environments.SDF_CELL_SIZE + np.asarray(environments.world_map_origin(name))
+                                                    - np.asarray(LIMITS[0])))
+        ends = (rng.random((2, 2), dtype=np.float32) * np.float32(1.9) - np.float32(0.95)).astype(np.float32)      # local start, goal
+        st, go = ends[:1] + off, ends[1:] + off
+        if not bool((environments.world_map_sdf(np.concatenate([st, go]), name) > OBSTACLE_MARGIN).all()):
+            continue
         if len(starts) and not (np.all(np.sqrt(np.sum((st - starts) ** 2, axis=1)) > min_separation)
                                 and np.all(np.sqrt(np.sum((go - goals) ** 2, axis=1)) > min_separation)):
             continue
