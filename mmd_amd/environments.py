@@ -12,14 +12,18 @@ resident device texture of a registered map is built by the library (mmd_sdf_gri
 
 Occupancy maps (register_occupancy_map): a [nx, ny] bitmap of the tile's cells -- a floor plan, a benchmark grid, a costmap -- instead
 of primitives.  occupancy_sdf_texture (numpy, an exact Euclidean distance transform with nearest-site tracking) is the definition;
-the resident texture is built by mmd_sdf_grid_from_occupancy, bit for bit the same.  Both kinds share one name space.
+the resident texture is built by mmd_sdf_grid_from_occupancy, bit for bit the same.
 
 World maps (register_world_map): one bitmap for a world larger than a tile, up to 2048 cells per side.  The world's texture is
 occupancy_sdf_texture of the whole bitmap; a robot's map is the 400 x 400 window of it at the robot's offset (world_map_windows is the
 definition, world_window_name its map name); on a device the windows are cut from the resident world texture by mmd_sdf_grid_windows.
-The section at the end of this file.
+
+The shipped maps are the constant table MAP_BOXES; the three registered kinds share ONE registry and one name space, and resolve_map is
+the one reading of a map name: what differs per kind is a `match` on the kind it returns.  The host textures of every kind share one
+cache keyed by content.  The textures resident on a device, and what an update or an unregistration does to them, are map_textures.py's.
 """
 import ctypes as C
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -36,17 +40,133 @@ MAP_BOXES = {
 }
 LIMITS = ((-1.0, -1.0), (1.0, 1.0))
 SDF_CELL_SIZE = 0.005
+OCCUPANCY_MAX_SIDE = 2048  # MMD_OCCUPANCY_MAX_SIDE: 2 * 2047^2 < 2^24, so every squared distance is an exact float32
 
+
+# ---- the registry and the map names ---------------------------------------------------------------------------------------------------
+class MapRecord(NamedTuple):
+    kind: str              # "primitives" | "occupancy" (the tile kinds: registered_maps) | "world" (registered_world_maps)
+    content: object        # hashable; "the same content under a name twice is a no-op" compares it, and so does the host texture cache:
+    #                        primitives: (boxes, spheres), tuples of float tuples rounded to fp32; occupancy: the [nx, ny] uint8 bitmap
+    #                        (0 / 1) as bytes, row-major; world: ((WX, WY), its bitmap as bytes, (origin x, origin y) as floats)
+
+
+_TILE_KINDS = ("primitives", "occupancy")
+# kind -> (what a refusal calls it, what register_* calls other content under a taken name, the two calls that take a map of the kind)
+_KINDS = {"primitives": ("map of primitives", "other primitives", "update_map", "unregister_map"),
+          "occupancy": ("occupancy map", "another bitmap", "update_occupancy_map", "unregister_map"),
+          "world": ("world map", "another bitmap or origin", "update_world_map", "unregister_world_map")}
+_MAPS = {}                 # name -> MapRecord
 _EXTRA_SUFFIX = "ExtraObjects"
-_REGISTERED = {}           # name -> (boxes, spheres): tuples of float tuples, rounded to fp32
-_OCCUPANCY = {}            # name -> the [nx, ny] uint8 bitmap (0 / 1) as bytes, row-major: the other kind of registered map
-_TEXTURE_CACHE = {}        # (base name, cell size) -> (content the texture was built from, texture)
+_WINDOW_SEPARATOR = "@"    # a window's map name: "<world>@<i0>,<j0>", the window's origin cell in the world
 
 
-def _base_name(map_name):
-    return map_name.replace(_EXTRA_SUFFIX, "")
+def resolve_map(map_name, unknown_ok=False):
+    """(kind, base name, record, window origin) of a map name, the one reading of it.  The suffix 'ExtraObjects' is stripped from every
+    name.  kind "shipped": a key of MAP_BOXES (record None); "primitives" / "occupancy": a registered tile map and its record; "window":
+    "<world>@<i0>,<j0>" of a REGISTERED world map, split at the last '@' -- the base name is the world's, the record the world's, the
+    origin (i0, j0), elsewhere None.  Any other name, a world map's own among them, and anything that is no string: KeyError, or four
+    times None with unknown_ok (the predicates)."""
+    if isinstance(map_name, str):
+        base = map_name.replace(_EXTRA_SUFFIX, "")
+        if base in MAP_BOXES:
+            return "shipped", base, None, None
+        rec = _MAPS.get(base)
+        if rec is not None and rec.kind in _TILE_KINDS:
+            return rec.kind, base, rec, None
+        world, _, tail = base.rpartition(_WINDOW_SEPARATOR)
+        cells = tail.split(",")
+        rec = _MAPS.get(world)
+        if rec is not None and rec.kind == "world" and len(cells) == 2 and all(c.isascii() and c.isdigit() for c in cells):
+            return "window", world, rec, (int(cells[0]), int(cells[1]))
+    if unknown_ok:
+        return None, None, None, None
+    raise KeyError(f"unknown map {map_name!r} (shipped: {sorted(MAP_BOXES)}; registered: {list(registered_maps())}; windows of the "
+                   f"world maps {list(registered_world_maps())})")
 
 
+def is_registered(name):
+    return resolve_map(name, True)[0] in _TILE_KINDS
+
+
+def is_occupancy_map(name):
+    return resolve_map(name, True)[0] == "occupancy"
+
+
+def is_world_window(name):
+    """Whether `name` is the map name of a window of a registered world map (world_window_name)."""
+    return resolve_map(name, True)[0] == "window"
+
+
+def is_world_map(name):
+    return isinstance(name, str) and name in _MAPS and _MAPS[name].kind == "world"
+
+
+def registered_maps():
+    """The names of the registered tile maps of both kinds, sorted."""
+    return tuple(sorted(n for n, rec in _MAPS.items() if rec.kind in _TILE_KINDS))
+
+
+def registered_world_maps():
+    """The names of the registered world maps, sorted."""
+    return tuple(sorted(n for n, rec in _MAPS.items() if rec.kind == "world"))
+
+
+def _register(what, name, kind, content):
+    """The name rules and the clash rule of every register_*.  A new name is a non-empty string, no shipped name, without 'ExtraObjects'.
+    A name belongs to at most ONE kind, a window's name to its world: a name taken by another kind is refused, a tile or world name may
+    not be a window name of a registered world, and a world may not be registered while a tile map's name begins "<world>@".  The same
+    content under a taken name is a no-op, other content is refused."""
+    if not isinstance(name, str) or not name:
+        raise ValueError(f"{what}: a non-empty string name, got {name!r}")
+    if name in MAP_BOXES:
+        raise ValueError(f"{what}: {name!r} is a shipped map")
+    if _EXTRA_SUFFIX in name:
+        raise ValueError(f"{what}: {name!r} contains {_EXTRA_SUFFIX!r}, which is stripped from map names")
+    content = content()                                     # (checked only under a name that may be registered at all)
+    taken = _MAPS.get(name)
+    if taken is not None and taken.kind != kind:
+        raise ValueError(f"{what}: {name!r} is the name of a registered {_KINDS[taken.kind][0]}{', a tile map' * (taken.kind in _TILE_KINDS)}")
+    if is_world_window(name):
+        raise ValueError(f"{what}: {name!r} names a window of the world map {world_window(name)[0]!r}")
+    tiles = [n for n in registered_maps() if n.startswith(name + _WINDOW_SEPARATOR)] if kind == "world" and taken is None else []
+    if tiles:
+        raise ValueError(f"{what}: the registered map {tiles[0]!r} has the form of a window name of {name!r}")
+    if taken is not None and taken.content != content:
+        raise ValueError(f"{what}: {name!r} is registered with {_KINDS[kind][1]} ({_KINDS[kind][2]} replaces the content)")
+    _MAPS[name] = MapRecord(kind, content)
+
+
+def _record(what, name, *kinds):
+    """The record of `name`, which must be registered as one of `kinds`; the refusal names the calls that take the kind it is."""
+    rec = _MAPS.get(name) if isinstance(name, str) else None
+    if rec is None or rec.kind not in kinds:
+        has = "" if rec is None else ": it is a registered {0}, which {2} and {3} take".format(*_KINDS[rec.kind])
+        raise ValueError(f"{what}: {name!r} is not a registered {' or '.join(_KINDS[k][0] for k in kinds)}{has}")
+    return rec
+
+
+def _resident():
+    """The textures resident on the devices (map_textures.py): the one place this module reaches them."""
+    from . import map_textures
+    return map_textures
+
+
+def _replace(name, content, **how):
+    """update_*: the new content, no host texture of the old one, and every resident texture that holds the name rebuilt in place."""
+    _MAPS[name] = MapRecord(_MAPS[name].kind, content)
+    _drop_host_texture(name)
+    _resident().rebuild_resident_textures(name, **how)
+
+
+def _forget(name):
+    """unregister_*: the resident textures that hold the name go while it still resolves, then its host texture and the name itself."""
+    _resident().drop_resident_textures(name)
+    _drop_host_texture(name)
+    del _MAPS[name]
+
+
+# ---- maps of primitives -----------------------------------------------------------------------------------------------------------------
 def _primitive_rows(rows, width, what):
     a = np.asarray(list(rows), dtype=np.float32)
     if a.size == 0:
@@ -69,60 +189,35 @@ def register_map(name, boxes=(), spheres=()):
     centers and radii) on the tile LIMITS at SDF_CELL_SIZE, usable wherever a shipped map name is.  Registering the same content under a
     name twice is a no-op; other content under a taken name, a shipped name and a name that contains 'ExtraObjects' (the suffix is
     stripped from every map name) are refused."""
-    if not isinstance(name, str) or not name:
-        raise ValueError(f"register_map: a non-empty string name, got {name!r}")
-    if name in MAP_BOXES:
-        raise ValueError(f"register_map: {name!r} is a shipped map")
-    if _EXTRA_SUFFIX in name:
-        raise ValueError(f"register_map: {name!r} contains {_EXTRA_SUFFIX!r}, which is stripped from map names")
-    content = _checked_primitives(boxes, spheres)
-    _refuse_world_name(name, "register_map")
-    if name in _OCCUPANCY:
-        raise ValueError(f"register_map: {name!r} is registered as an occupancy map")
-    if name in _REGISTERED and _REGISTERED[name] != content:
-        raise ValueError(f"register_map: {name!r} is registered with other primitives (update_map replaces them)")
-    _REGISTERED[name] = content
+    _register("register_map", name, "primitives", lambda: _checked_primitives(boxes, spheres))
+
+
+def update_map(name, boxes=(), spheres=()):
+    """Replace a registered map's primitives and rebuild every resident device texture slice of that name in place (same storage): guides
+    and task facades that share it see the new map on their next call.  The host texture of the name is dropped."""
+    _record("update_map", name, "primitives")
+    _replace(name, _checked_primitives(boxes, spheres))
 
 
 def unregister_map(name):
     """Forget a registered map of either kind, its host texture and every resident device texture that holds it (objects built on it
     keep theirs)."""
-    if name not in _REGISTERED and name not in _OCCUPANCY:
-        raise ValueError(f"unregister_map: {name!r} is not a registered map")
-    _REGISTERED.pop(name, None)
-    _OCCUPANCY.pop(name, None)
-    _drop_host_texture(name)
-    from . import guides
-    guides.drop_resident_textures(name)
-
-
-def registered_maps():
-    """The names of the registered maps of both kinds, sorted."""
-    return tuple(sorted(set(_REGISTERED) | set(_OCCUPANCY)))
+    _record("unregister_map", name, *_TILE_KINDS)
+    _forget(name)
 
 
 def map_primitives(name):
     """(boxes [(cx, cy, size_x, size_y)], spheres [(cx, cy, r)]) of a shipped or registered map."""
-    base = _base_name(name)
-    if _window_of(base) is not None:
-        raise ValueError(f"map_primitives: {name!r} is a window of a world map (world_map_occupancy returns the world's bitmap)")
-    if base in _OCCUPANCY:
-        raise ValueError(f"map_primitives: {name!r} is an occupancy map (map_occupancy returns its bitmap)")
-    if base in _REGISTERED:
-        return _REGISTERED[base]
-    if base not in MAP_BOXES:
-        raise KeyError(f"unknown map {name!r} (shipped: {sorted(MAP_BOXES)}; registered: {list(registered_maps())})")
-    centers, sizes = MAP_BOXES[base]
-    return tuple((float(c[0]), float(c[1]), float(s[0]), float(s[1])) for c, s in zip(centers, sizes)), ()
-
-
-def is_registered(name):
-    base = _base_name(name)
-    return base in _REGISTERED or base in _OCCUPANCY
-
-
-def is_occupancy_map(name):
-    return _base_name(name) in _OCCUPANCY
+    kind, base, rec, _ = resolve_map(name)
+    match kind:
+        case "shipped":
+            return tuple((float(c[0]), float(c[1]), float(s[0]), float(s[1])) for c, s in zip(*MAP_BOXES[base])), ()
+        case "primitives":
+            return rec.content
+        case "occupancy":
+            raise ValueError(f"map_primitives: {name!r} is an occupancy map (map_occupancy returns its bitmap)")
+        case "window":
+            raise ValueError(f"map_primitives: {name!r} is a window of a world map (world_map_occupancy returns the world's bitmap)")
 
 
 def map_has_obstacles(name):
@@ -130,11 +225,10 @@ def map_has_obstacles(name):
     primitives or occupied cells: update_map / update_occupancy_map may give it some while a guide that reads the grid is alive.
     A window of a world map: whether the world has an occupied cell now (a guide built on a window of an empty world reads no grid, and
     an update_world_map that adds the first obstacle does not reach it)."""
-    base = _base_name(name)
-    window = _window_of(base)
-    if window is not None:
-        return b"\x01" in _WORLD_MAPS[window[0]][1]
-    return base in _REGISTERED or base in _OCCUPANCY or len(MAP_BOXES[base][0]) > 0
+    kind, base, rec, _ = resolve_map(name)
+    if kind == "window":
+        return b"\x01" in rec.content[1]
+    return kind != "shipped" or len(MAP_BOXES[base][0]) > 0
 
 
 def _rounded_box_sdfs(x, centers, sizes):
@@ -148,7 +242,7 @@ def _rounded_box_sdfs(x, centers, sizes):
 def _primitives_sdf(x, boxes, spheres):
     """ObjectField([MultiSphereField(spheres), MultiBoxField(boxes)]) at the identity pose (primitives.py:108-115, :326-333, :569-572):
     torch.min over the stacked fields, spheres first, so the first of equal minima takes the gradient; an empty sphere field is the
-    constant 1, an empty box field is left out."""
+    constant 1, an empty box field is left out.  The shipped maps are their boxes and no spheres."""
     fields = []
     if len(spheres) == 0:
         fields.append(torch.ones_like(x[..., 0]))
@@ -162,19 +256,11 @@ def _primitives_sdf(x, boxes, spheres):
 
 
 def map_sdf(points, map_name):
-    x = torch.as_tensor(points, dtype=torch.float32)
-    base = _base_name(map_name)
-    if base in _OCCUPANCY or _window_of(base) is not None:
-        return _nearest_cell_sdf(x, sdf_grid_texture(base))
-    if base in _REGISTERED:
-        return _primitives_sdf(x, *_REGISTERED[base])
-    centers, sizes = MAP_BOXES[base]
-    ones = torch.ones_like(x[..., 0])
-    if len(centers) == 0:
-        return ones
-    centers = torch.tensor(centers, dtype=torch.float32)
-    sizes = torch.tensor(sizes, dtype=torch.float32)
-    return torch.minimum(ones, torch.min(_rounded_box_sdfs(x, centers, sizes), dim=-1)[0])
+    """The map's SDF at points [..., 2] -> float32 tensor [...]: the analytic field of a map of primitives, shipped or registered; the
+    nearest-cell value of the host texture (texel_values) of an occupancy map or a window, which have no analytic field."""
+    if resolve_map(map_name)[0] in ("shipped", "primitives"):
+        return _primitives_sdf(torch.as_tensor(points, dtype=torch.float32), *map_primitives(map_name))
+    return torch.from_numpy(texel_values(sdf_grid_texture(map_name), points)[0])
 
 
 def grid_shape(cell_size=SDF_CELL_SIZE):
@@ -190,31 +276,36 @@ def grid_node_rows(cell_size=SDF_CELL_SIZE):
     return torch.linspace(lo[0], hi[0], nx), torch.linspace(lo[1], hi[1], ny)
 
 
+# ---- host textures ------------------------------------------------------------------------------------------------------------------------
+_HOST_TEXTURES = {}        # (tile map's base name or world map's name, cell size) -> (content the texture was built from, texture)
+
+
+def _host_texture(name, cell_size, content, build):
+    hit = _HOST_TEXTURES.get((name, cell_size))
+    if hit is None or hit[0] != content:
+        hit = _HOST_TEXTURES[(name, cell_size)] = (content, build())
+    return hit[1]
+
+
 def _drop_host_texture(name):
-    for key in [k for k in _TEXTURE_CACHE if k[0] == name]:
-        del _TEXTURE_CACHE[key]
+    for key in [k for k in _HOST_TEXTURES if k[0] == name]:
+        del _HOST_TEXTURES[key]
 
 
 def sdf_grid_texture(map_name, cell_size=SDF_CELL_SIZE):
     """float32 numpy [nx, ny, 4] = (sdf, dsdf/dx, dsdf/dy, 0): the texture layout mmd_guide_desc expects."""
-    base = _base_name(map_name)
-    window = _window_of(base)
-    if window is not None:                                       # (the host crop of the world's texture, which is cached by content)
-        if grid_shape(cell_size) != grid_shape():
-            raise ValueError(f"sdf_grid_texture: the world map {window[0]!r} has one cell per grid cell at {SDF_CELL_SIZE}, not at {cell_size}")
-        return world_map_windows(window[0], [window[1:]])[0]
-    content = _OCCUPANCY.get(base, _REGISTERED.get(base))        # (None: a shipped map, whose content never changes)
-    hit = _TEXTURE_CACHE.get((base, cell_size))
-    if hit is not None and hit[0] == content:
-        return hit[1]
-    if base in _OCCUPANCY:
-        if grid_shape(cell_size) != grid_shape():
-            raise ValueError(f"sdf_grid_texture: the occupancy map {base!r} has one cell per grid cell at {SDF_CELL_SIZE}, not at {cell_size}")
-        tex = occupancy_sdf_texture(map_occupancy(base), cell_size)
-    else:
-        tex = _texture(lambda pts: map_sdf(pts, map_name), *grid_node_rows(cell_size))
-    _TEXTURE_CACHE[(base, cell_size)] = (content, tex)
-    return tex
+    kind, base, rec, origin = resolve_map(map_name)
+    if kind in ("occupancy", "window") and grid_shape(cell_size) != grid_shape():
+        raise ValueError(f"sdf_grid_texture: the {_KINDS[rec.kind][0]} {base!r} has one cell per grid cell at {SDF_CELL_SIZE}, not at "
+                         f"{cell_size}")
+    match kind:
+        case "window":                                           # (the host crop of the world's texture, which is cached by content)
+            return world_map_windows(base, [origin])[0]
+        case "occupancy":
+            return _host_texture(base, cell_size, rec.content, lambda: occupancy_sdf_texture(map_occupancy(base), cell_size))
+    prims = map_primitives(base)                                 # (a shipped map's content never changes: None)
+    return _host_texture(base, cell_size, rec and rec.content,
+                         lambda: _texture(lambda pts: _primitives_sdf(pts, *prims), *grid_node_rows(cell_size)))
 
 
 def _texture(sdf_fn, xs, ys):
@@ -237,18 +328,65 @@ def primitives_sdf_texture(boxes, spheres, xs, ys):
                     torch.as_tensor(ys, dtype=torch.float32))
 
 
+def _host_array(a):
+    return a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+
+
+def _texel_indices(points, lo, hi, shape):
+    """(ix, iy, finite): the texel of float32 points [n, 2] on a grid of `shape` over lo .. hi, the fp32 sequence of every consumer of a
+    texture and of mmd_sdf_grid_lookup: floor((p - lo) / |hi - lo| * n) clamped to [0, n - 1] (as a float, then converted)."""
+    f = np.float32
+    lo, hi = np.asarray(lo, f), np.asarray(hi, f)
+    dim = np.abs(hi - lo)
+    finite = np.isfinite(points).all(1)
+    p = np.where(finite[:, None], points, f(0))
+    with np.errstate(over="ignore"):
+        idx = [np.clip(np.floor((p[:, k] - lo[k]) / dim[k] * f(shape[k])), f(0), f(shape[k] - 1)).astype(np.int64) for k in range(2)]
+    return idx[0], idx[1], finite
+
+
+def texel_values(tex, points, lo=LIMITS[0], hi=LIMITS[1]):
+    """(values, finite), float32 and bool numpy [...]: channel 0 of texture `tex` [nx, ny, 4] over lo .. hi at the texel of every point
+    [..., 2] (GridMapSDF's cell lookup, grid_map_sdf.py:81-99, by _texel_indices), THE host lookup of a texture: a point however far out
+    reads the clamped border cell, as on the device; a point with a non-finite coordinate reads as point 0 and has finite = False."""
+    pts = np.ascontiguousarray(_host_array(points), dtype=np.float32)
+    ix, iy, finite = _texel_indices(pts.reshape(-1, 2), lo, hi, tex.shape[:2])
+    return tex[ix, iy, 0].reshape(pts.shape[:-1]), finite.reshape(pts.shape[:-1])
+
+
 # ---- the grid on the device ---------------------------------------------------------------------------------------
 _NODE_ROWS_DEV = {}        # device -> (xs, ys) of the tile's grid
 
 
+def resolved_device(device):
+    """torch.device(device), a 'cuda' without an index resolved to the current device."""
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    return device
+
+
+def _out_texture(what, shape, device, out):
+    """(device, out): the device resolved; `out` allocated as the float32 texture [shape[0], shape[1], 4] there, or checked to be one."""
+    device = resolved_device(device)
+    if out is None:
+        out = torch.empty(shape[0], shape[1], 4, dtype=torch.float32, device=device)
+    elif tuple(out.shape) != (shape[0], shape[1], 4) or out.device != device:
+        raise ValueError(f"{what}: out must be [{shape[0]}, {shape[1]}, 4] on {device}, got {tuple(out.shape)} on {out.device}")
+    return device, out
+
+
+def primitive_table_layout(boxes, spheres):
+    """The library's tables of float32 boxes [n, 4] = (cx, cy, size_x, size_y) and spheres [n, 3] = (cx, cy, r): boxes [n][4] = (cx, cy,
+    half x, half y), spheres [n][4] = (cx, cy, r, 0) -- mmd_guide_desc's extra_boxes_dev / extra_spheres_dev layouts.  Layout only."""
+    return (np.concatenate([boxes[:, :2], boxes[:, 2:] / np.float32(2)], 1),
+            np.concatenate([spheres, np.zeros((len(spheres), 1), np.float32)], 1))
+
+
 def primitive_tables(boxes, spheres):
-    """The library's tables: spheres [n][4] = (cx, cy, r, 0), boxes [n][4] = (cx, cy, half x, half y) -- mmd_guide_desc's extra_spheres_dev /
-    extra_boxes_dev layouts -- as float32 numpy."""
+    """(boxes, spheres) checked as register_map checks them, in the library's layouts (primitive_table_layout), as float32 numpy."""
     boxes, spheres = _checked_primitives(boxes, spheres)
-    sph = np.asarray(spheres, dtype=np.float32).reshape(-1, 3)
-    box = np.asarray(boxes, dtype=np.float32).reshape(-1, 4)
-    return (np.concatenate([box[:, :2], box[:, 2:] / np.float32(2)], 1),
-            np.concatenate([sph, np.zeros((len(sph), 1), np.float32)], 1))
+    return primitive_table_layout(np.asarray(boxes, dtype=np.float32).reshape(-1, 4), np.asarray(spheres, dtype=np.float32).reshape(-1, 3))
 
 
 def device_sdf_grid(boxes, spheres, device, out=None):
@@ -256,14 +394,8 @@ def device_sdf_grid(boxes, spheres, device, out=None):
     host, bit for bit but for the sign of a zero (+0 here), for the upload of the primitives and the two rows of node coordinates.  out= rebuilds a resident texture in place
     on the current stream."""
     from . import _lib
-    device = torch.device(device)
-    if device.type == "cuda" and device.index is None:
-        device = torch.device("cuda", torch.cuda.current_device())
     nx, ny = grid_shape()
-    if out is None:
-        out = torch.empty(nx, ny, 4, dtype=torch.float32, device=device)
-    elif tuple(out.shape) != (nx, ny, 4) or out.device != device:
-        raise ValueError(f"device_sdf_grid: out must be [{nx}, {ny}, 4] on {device}, got {tuple(out.shape)} on {out.device}")
+    device, out = _out_texture("device_sdf_grid", (nx, ny), device, out)
     box, sph = primitive_tables(boxes, spheres)
     rows = _NODE_ROWS_DEV.get(str(device))
     if rows is None:
@@ -276,22 +408,19 @@ def device_sdf_grid(boxes, spheres, device, out=None):
     return out
 
 
-def update_map(name, boxes=(), spheres=()):
-    """Replace a registered map's primitives and rebuild every resident device texture slice of that name in place (same storage): guides
-    and task facades that share it see the new map on their next call.  The host texture of the name is dropped."""
-    if name in _OCCUPANCY:
-        raise ValueError(f"update_map: {name!r} is an occupancy map (update_occupancy_map replaces its bitmap)")
-    if name not in _REGISTERED:
-        raise ValueError(f"update_map: {name!r} is not a registered map")
-    _REGISTERED[name] = _checked_primitives(boxes, spheres)
-    _drop_host_texture(name)
-    from . import guides
-    guides.rebuild_resident_textures(name)
+def build_resident_texture(map_name, device, out):
+    """The registered map's texture into the resident slice `out`, by the builder of its kind."""
+    kind, _, rec, _ = resolve_map(map_name)
+    match kind:
+        case "primitives":
+            return device_sdf_grid(*rec.content, device, out=out)
+        case "occupancy":
+            return device_occupancy_sdf_grid(_bitmap(rec.content, grid_shape()), device, out=out)
+    raise ValueError(f"build_resident_texture: {map_name!r} is no registered tile map")
 
 
 # ---- occupancy maps -------------------------------------------------------------------------------------------------
 _OCC_NONE = 1 << 14        # "this row holds no such cell": its square is above every real squared distance (csrc/sdf_grid.hip: OCC_NONE)
-OCCUPANCY_MAX_SIDE = 2048  # MMD_OCCUPANCY_MAX_SIDE: 2 * 2047^2 < 2^24, so every squared distance is an exact float32
 
 
 def _row_offsets(site):
@@ -367,22 +496,9 @@ def occupancy_sdf_texture(occ, cell=SDF_CELL_SIZE):
     return tex
 
 
-def _nearest_cell_sdf(x, tex):
-    """The texture's value at points x [..., 2] by GridMapSDF's cell lookup (grid_map_sdf.py:81-99), as every consumer of the texture reads it."""
-    lo, hi = torch.tensor(LIMITS[0]), torch.tensor(LIMITS[1])
-    dims = torch.tensor(tex.shape[:2])
-    idx = torch.floor((x - lo) / (hi - lo) * dims.to(torch.float32)).long()
-    idx = torch.minimum(torch.maximum(idx, torch.zeros_like(dims)), dims - 1)
-    return torch.from_numpy(tex[..., 0])[idx[..., 0], idx[..., 1]]
-
-
-def _checked_map_name(name, what):
-    if not isinstance(name, str) or not name:
-        raise ValueError(f"{what}: a non-empty string name, got {name!r}")
-    if name in MAP_BOXES:
-        raise ValueError(f"{what}: {name!r} is a shipped map")
-    if _EXTRA_SUFFIX in name:
-        raise ValueError(f"{what}: {name!r} contains {_EXTRA_SUFFIX!r}, which is stripped from map names")
+def _bitmap(content, shape):
+    """The uint8 [nx, ny] bitmap (1 = occupied) a registry record holds as bytes, read-only"""
+    return np.frombuffer(content, np.uint8).reshape(shape)
 
 
 def register_occupancy_map(name, occupancy):
@@ -390,44 +506,30 @@ def register_occupancy_map(name, occupancy):
     texture (x along the first axis; occupancy_from_ascii and resize_occupancy bring a text grid there).  Usable wherever a map name is;
     the name rules are register_map's, and both kinds share the names: the same bitmap under a name twice is a no-op, other content under a
     taken name -- of either kind -- is refused."""
-    _checked_map_name(name, "register_occupancy_map")
-    content = _checked_occupancy(occupancy, "register_occupancy_map", grid_shape()).tobytes()
-    _refuse_world_name(name, "register_occupancy_map")
-    if name in _REGISTERED:
-        raise ValueError(f"register_occupancy_map: {name!r} is registered as a map of primitives")
-    if name in _OCCUPANCY and _OCCUPANCY[name] != content:
-        raise ValueError(f"register_occupancy_map: {name!r} is registered with another bitmap (update_occupancy_map replaces it)")
-    _OCCUPANCY[name] = content
+    _register("register_occupancy_map", name, "occupancy",
+              lambda: _checked_occupancy(occupancy, "register_occupancy_map", grid_shape()).tobytes())
 
 
 def map_occupancy(name):
     """The bitmap of a registered occupancy map: a uint8 [nx, ny] copy, 1 = occupied."""
-    base = _base_name(name)
-    if base not in _OCCUPANCY:
+    kind, _, rec, _ = resolve_map(name, True)
+    if kind != "occupancy":
         raise ValueError(f"map_occupancy: {name!r} is not a registered occupancy map")
-    return np.frombuffer(_OCCUPANCY[base], np.uint8).reshape(grid_shape()).copy()
+    return _bitmap(rec.content, grid_shape()).copy()
 
 
 def device_occupancy_sdf_grid(occupancy, device, out=None):
     """The [nx, ny, 4] texture of the tile's bitmap `occupancy` (numpy or torch, on the host or already on `device`), built on `device` by
     mmd_sdf_grid_from_occupancy: occupancy_sdf_texture bit for bit, for the upload of 160 kB (none for a device tensor).  out= rebuilds a
     resident texture in place on the current stream."""
-    from . import _lib
-    device = torch.device(device)
-    if device.type == "cuda" and device.index is None:
-        device = torch.device("cuda", torch.cuda.current_device())
     nx, ny = grid_shape()
-    if out is None:
-        out = torch.empty(nx, ny, 4, dtype=torch.float32, device=device)
-    elif tuple(out.shape) != (nx, ny, 4) or out.device != device:
-        raise ValueError(f"device_occupancy_sdf_grid: out must be [{nx}, {ny}, 4] on {device}, got {tuple(out.shape)} on {out.device}")
+    device, out = _out_texture("device_occupancy_sdf_grid", (nx, ny), device, out)
     if isinstance(occupancy, torch.Tensor) and occupancy.device == device:
         if tuple(occupancy.shape) != (nx, ny):
             raise ValueError(f"device_occupancy_sdf_grid: an occupancy bitmap of shape [{nx}, {ny}], got {list(occupancy.shape)}")
         occ = (occupancy != 0).to(torch.uint8).contiguous()
     else:
-        host = occupancy.cpu().numpy() if isinstance(occupancy, torch.Tensor) else occupancy
-        occ = torch.from_numpy(_checked_occupancy(host, "device_occupancy_sdf_grid", (nx, ny))).to(device)
+        occ = torch.from_numpy(_checked_occupancy(_host_array(occupancy), "device_occupancy_sdf_grid", (nx, ny))).to(device)
     return _occupancy_build(occ, out)
 
 
@@ -443,28 +545,13 @@ def _occupancy_build(occ, out):
     return out
 
 
-def build_resident_texture(map_name, device, out):
-    """The registered map's texture into the resident slice `out`, by the builder of its kind."""
-    base = _base_name(map_name)
-    if base in _OCCUPANCY:
-        return device_occupancy_sdf_grid(map_occupancy(base), device, out=out)
-    return device_sdf_grid(*map_primitives(map_name), device, out=out)
-
-
 def update_occupancy_map(name, occupancy):
     """Replace a registered occupancy map's bitmap (numpy or torch, on the host or on a device) and rebuild every resident device texture
     slice of that name in place (same storage), on the current stream: guides and task facades that share it see the new map on their next
     call.  A bitmap that is already on a slice's device is used where it is; the registry keeps a host copy.  The host texture of the name is dropped."""
-    if name in _REGISTERED:
-        raise ValueError(f"update_occupancy_map: {name!r} is a map of primitives (update_map replaces those)")
-    if name not in _OCCUPANCY:
-        raise ValueError(f"update_occupancy_map: {name!r} is not a registered occupancy map")
+    _record("update_occupancy_map", name, "occupancy")
     dev_occ = occupancy if isinstance(occupancy, torch.Tensor) and occupancy.is_cuda else None
-    host = occupancy.cpu().numpy() if isinstance(occupancy, torch.Tensor) else occupancy
-    _OCCUPANCY[name] = _checked_occupancy(host, "update_occupancy_map", grid_shape()).tobytes()
-    _drop_host_texture(name)
-    from . import guides
-    guides.rebuild_resident_textures(name, device_occupancy=dev_occ)
+    _replace(name, _checked_occupancy(_host_array(occupancy), "update_occupancy_map", grid_shape()).tobytes(), device_occupancy=dev_occ)
 
 
 def occupancy_from_ascii(rows, occupied="@OTW"):
@@ -497,39 +584,17 @@ def resize_occupancy(occ, shape=(400, 400)):
 # 400 x 400 crop of that texture at the window's origin cell (world_map_windows).  The crop of the world's transform is NOT the
 # transform of the cropped bitmap: an obstacle just outside a window still acts on the cells near its border, and overlapping windows
 # agree where they overlap.  A window has a map name of its own (world_window_name), usable wherever a map name is.  On a device the world
-# texture is resident once (guides.device_world_texture, built by mmd_sdf_grid_from_occupancy) and the windows of a map set are cut
-# from it by mmd_sdf_grid_windows.  World maps have a registry of their own: registered_maps() does not list them.
-_WORLD_MAPS = {}           # name -> ((WX, WY), the uint8 bitmap (0 / 1) as bytes, row-major, (origin x, origin y) as floats)
-_WORLD_TEXTURE_CACHE = {}  # name -> (content the texture was built from, texture)
-_WINDOW_SEPARATOR = "@"    # a window's map name: "<world>@<i0>,<j0>", the window's origin cell in the world
-
-
-def _window_of(map_name):
-    """(world, i0, j0) of the map name of a window of a REGISTERED world map (the last '@' splits it), else None."""
-    head, sep, tail = _base_name(map_name).rpartition(_WINDOW_SEPARATOR) if isinstance(map_name, str) else ("", "", "")
-    if not sep or head not in _WORLD_MAPS:
-        return None
-    cells = tail.split(",")
-    if len(cells) != 2 or not all(c.isascii() and c.isdigit() for c in cells):
-        return None
-    return head, int(cells[0]), int(cells[1])
-
-
-def _refuse_world_name(name, what):
-    if name in _WORLD_MAPS:
-        raise ValueError(f"{what}: {name!r} is registered as a world map")
-    if _window_of(name) is not None:
-        raise ValueError(f"{what}: {name!r} names a window of the world map {_window_of(name)[0]!r}")
-
-
-def _host_array(a):
-    return a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
-
-
+# texture is resident once (map_textures.device_world_texture, built by mmd_sdf_grid_from_occupancy) and the windows of a map set are cut
+# from it by mmd_sdf_grid_windows.  registered_maps() does not list the world maps.
 def _world(name, what):
-    if name not in _WORLD_MAPS:
-        raise ValueError(f"{what}: {name!r} is not a registered world map (registered: {list(registered_world_maps())})")
-    return _WORLD_MAPS[name]
+    """(shape, bitmap as bytes, origin) of a registered world map"""
+    return _record(what, name, "world").content
+
+
+def _max_origin(shape):
+    """The largest window origin of a world of `shape` cells, per axis"""
+    n = grid_shape()
+    return [shape[0] - n[0], shape[1] - n[1]]
 
 
 def _checked_world_occupancy(occupancy, what, shape=None):
@@ -541,31 +606,24 @@ def _checked_world_occupancy(occupancy, what, shape=None):
     return occ
 
 
-def register_world_map(name, occupancy, origin=None):
-    """A map larger than a tile: occupancy [WX, WY], non-zero = occupied, indexed [ix, iy] like the texture, each side between
-    grid_shape() (400) and OCCUPANCY_MAX_SIDE (2048) cells of SDF_CELL_SIZE.  origin: the global position of the lower corner of cell
-    (0, 0); default (-WX, -WY) * SDF_CELL_SIZE / 2, the world centred on the global origin.  The name rules are register_map's; world
-    maps have a registry of their own (registered_world_maps), but the names are shared: a shipped or registered tile map's name is
-    refused here, a world map's name (and the name of one of its windows) is refused by register_map and register_occupancy_map.  The
-    same content under a name twice is a no-op; other content under a taken name is refused (update_world_map replaces a bitmap)."""
-    _checked_map_name(name, "register_world_map")
-    if _WINDOW_SEPARATOR in name and _window_of(name) is not None:
-        raise ValueError(f"register_world_map: {name!r} names a window of the world map {_window_of(name)[0]!r}")
+def _world_content(occupancy, origin):
     occ = _checked_world_occupancy(occupancy, "register_world_map")
     if origin is None:
         origin = (-occ.shape[0] * SDF_CELL_SIZE / 2.0, -occ.shape[1] * SDF_CELL_SIZE / 2.0)
     org = np.asarray(_host_array(origin), dtype=np.float64).reshape(-1)
     if org.shape != (2,) or not np.isfinite(org).all():
         raise ValueError(f"register_world_map: origin = two finite numbers, got {origin!r}")
-    if name in _REGISTERED or name in _OCCUPANCY:
-        raise ValueError(f"register_world_map: {name!r} is registered as a tile map")
-    taken = [n for n in registered_maps() if n.startswith(name + _WINDOW_SEPARATOR)]
-    if name not in _WORLD_MAPS and taken:
-        raise ValueError(f"register_world_map: the registered map {taken[0]!r} has the form of a window name of {name!r}")
-    content = (tuple(occ.shape), occ.tobytes(), (float(org[0]), float(org[1])))
-    if name in _WORLD_MAPS and _WORLD_MAPS[name] != content:
-        raise ValueError(f"register_world_map: {name!r} is registered with another bitmap or origin (update_world_map replaces the bitmap)")
-    _WORLD_MAPS[name] = content
+    return tuple(occ.shape), occ.tobytes(), (float(org[0]), float(org[1]))
+
+
+def register_world_map(name, occupancy, origin=None):
+    """A map larger than a tile: occupancy [WX, WY], non-zero = occupied, indexed [ix, iy] like the texture, each side between
+    grid_shape() (400) and OCCUPANCY_MAX_SIDE (2048) cells of SDF_CELL_SIZE.  origin: the global position of the lower corner of cell
+    (0, 0); default (-WX, -WY) * SDF_CELL_SIZE / 2, the world centred on the global origin.  The name rules are register_map's; world
+    maps are listed apart (registered_world_maps), but the names are shared: a shipped or registered tile map's name is
+    refused here, a world map's name (and the name of one of its windows) is refused by register_map and register_occupancy_map.  The
+    same content under a name twice is a no-op; other content under a taken name is refused (update_world_map replaces a bitmap)."""
+    _register("register_world_map", name, "world", lambda: _world_content(occupancy, origin))
 
 
 def update_world_map(name, occupancy):
@@ -573,49 +631,28 @@ def update_world_map(name, occupancy):
     resident window slice cut from it is cut again in place (same storage, same pointers), on the current stream of its device, one
     cut launch per map set: live guides and samplers see the new obstacles on their next call.  The host texture is dropped."""
     shape, _, origin = _world(name, "update_world_map")
-    occ = _checked_world_occupancy(occupancy, "update_world_map", shape)
-    _WORLD_MAPS[name] = (shape, occ.tobytes(), origin)
-    _WORLD_TEXTURE_CACHE.pop(name, None)
-    from . import guides
-    guides.rebuild_world_textures(name)
+    _replace(name, (shape, _checked_world_occupancy(occupancy, "update_world_map", shape).tobytes(), origin))
 
 
 def unregister_world_map(name):
     """Forget a world map, its host texture, its resident world textures and every resident map set that holds one of its windows
     (objects built on one keep theirs)."""
     _world(name, "unregister_world_map")
-    from . import guides
-    guides.drop_world_textures(name)            # (while the name still parses as a world's)
-    del _WORLD_MAPS[name]
-    _WORLD_TEXTURE_CACHE.pop(name, None)
-
-
-def registered_world_maps():
-    """The names of the registered world maps, sorted."""
-    return tuple(sorted(_WORLD_MAPS))
-
-
-def is_world_map(name):
-    return isinstance(name, str) and name in _WORLD_MAPS
-
-
-def is_world_window(name):
-    """Whether `name` is the map name of a window of a registered world map (world_window_name)."""
-    return _window_of(name) is not None
+    _forget(name)
 
 
 def world_window(name):
     """(world, (i0, j0)) of a window's map name."""
-    w = _window_of(name)
-    if w is None:
+    kind, world, _, origin = resolve_map(name, True)
+    if kind != "window":
         raise ValueError(f"world_window: {name!r} is not a window of a registered world map")
-    return w[0], (w[1], w[2])
+    return world, origin
 
 
 def world_map_occupancy(name):
     """The bitmap of a world map: a uint8 [WX, WY] copy, 1 = occupied."""
     shape, content, _ = _world(name, "world_map_occupancy")
-    return np.frombuffer(content, np.uint8).reshape(shape).copy()
+    return _bitmap(content, shape).copy()
 
 
 def world_map_origin(name):
@@ -632,45 +669,42 @@ def world_map_limits(name):
 def world_map_texture(name):
     """float32 [WX, WY, 4]: occupancy_sdf_texture of the world's bitmap, THE DEFINITION of the world's texture.  Cached by content
     (seconds in numpy at 640 x 520, minutes at 2048 x 2048: the resident device texture is the practical one at full size)."""
-    _, content, _ = _world(name, "world_map_texture")
-    hit = _WORLD_TEXTURE_CACHE.get(name)
-    if hit is None or hit[0] != content:
-        hit = _WORLD_TEXTURE_CACHE[name] = (content, occupancy_sdf_texture(world_map_occupancy(name)))
-    return hit[1]
+    content = _world(name, "world_map_texture")
+    return _host_texture(name, SDF_CELL_SIZE, content, lambda: occupancy_sdf_texture(world_map_occupancy(name)))
 
 
-def _checked_window_origins(name, origins, what):
-    """int32 [n, 2] origin cells, each a window that lies inside the world"""
-    shape = _world(name, what)[0]
+def checked_window_origins(name, origins, what):
+    """int32 [n, 2] origin cells, each a window that lies inside the world; `what` names the caller in a refusal"""
+    limit = _max_origin(_world(name, what)[0])
     raw = _host_array(origins)
     org = raw.reshape(-1, 2)
     if raw.size == 0 or org.dtype.kind not in "iu":
         raise ValueError(f"{what}: origins [n, 2] of integer cells, got dtype {raw.dtype}, shape {raw.shape}")
-    n = grid_shape()
-    bad = np.flatnonzero(((org < 0) | (org > np.asarray([shape[0] - n[0], shape[1] - n[1]]))).any(1))
+    bad = np.flatnonzero(((org < 0) | (org > np.asarray(limit))).any(1))
     if bad.size:
         k = int(bad[0])
-        raise ValueError(f"{what}: window {k} at origin cell {org[k].tolist()} is outside the world {name!r}: origins 0 .. "
-                         f"{[shape[0] - n[0], shape[1] - n[1]]}")
+        raise ValueError(f"{what}: window {k} at origin cell {org[k].tolist()} is outside the world {name!r}: origins 0 .. {limit}")
     return np.ascontiguousarray(org, dtype=np.int32)
 
 
 def world_map_windows(name, origins):
     """float32 [n, 400, 400, 4]: window k is world_map_texture(name)[i0:i0 + 400, j0:j0 + 400] for origins[k] = (i0, j0), a copy, bit for
     bit: THE DEFINITION of a window's texture.  Origins outside [0, W - 400] are refused."""
-    org = _checked_window_origins(name, origins, "world_map_windows")
+    org = checked_window_origins(name, origins, "world_map_windows")
     tex = world_map_texture(name)
     nx, ny = grid_shape()
     return np.stack([tex[i0:i0 + nx, j0:j0 + ny] for i0, j0 in org.tolist()])
 
 
 def _window_cells(name, offsets, what):
-    """(q, shape): the windows' origins in cells, float64 [n, 2], not yet rounded -- q = (offset + LIMITS[0] - origin) / cell"""
+    """(q, limit): the windows' origins in cells, float64 [n, 2], not yet rounded -- q = (offset + LIMITS[0] - origin) / cell -- and the
+    largest origin of the world"""
     shape, _, origin = _world(name, what)
     off = np.asarray(_host_array(offsets), dtype=np.float64)
     if off.size == 0 or off.shape[-1] != 2:
         raise ValueError(f"{what}: offsets [n, 2], got shape {off.shape}")
-    return (off.reshape(-1, 2) + np.asarray(LIMITS[0], np.float64) - np.asarray(origin, np.float64)) / np.float64(SDF_CELL_SIZE), shape
+    q = (off.reshape(-1, 2) + np.asarray(LIMITS[0], np.float64) - np.asarray(origin, np.float64)) / np.float64(SDF_CELL_SIZE)
+    return q, _max_origin(shape)
 
 
 def world_map_window_origins(name, offsets):
@@ -678,12 +712,11 @@ def world_map_window_origins(name, offsets):
     (offset + LIMITS[0] - origin) / SDF_CELL_SIZE per axis, in float64.  It must lie within 1e-3 of an integer (float32 offsets that are
     multiples of the cell pitch are not exact; half a cell off is an error) and inside [0, W - 400]; otherwise ValueError names the
     first robot at fault and whether it is off the cell grid or outside the world.  snap_to_world_map gives offsets that pass."""
-    q, shape = _window_cells(name, offsets, "world_map_window_origins")
+    q, limit = _window_cells(name, offsets, "world_map_window_origins")
     r = np.rint(q)
-    n = grid_shape()
     with np.errstate(invalid="ignore"):
         off_grid = ~(np.abs(q - r) <= 1e-3)
-        outside = ~off_grid & ((r < 0) | (r > np.asarray([shape[0] - n[0], shape[1] - n[1]], np.float64)))
+        outside = ~off_grid & ((r < 0) | (r > np.asarray(limit, np.float64)))
     bad = np.flatnonzero((off_grid | outside).any(1))
     if bad.size:
         k = int(bad[0])
@@ -691,19 +724,17 @@ def world_map_window_origins(name, offsets):
             raise ValueError(f"world_map_window_origins: the window of robot {k} is off the cell grid of {name!r}: its origin is at cell "
                              f"{q[k].tolist()} (snap_to_world_map gives the nearest valid offsets)")
         raise ValueError(f"world_map_window_origins: the window of robot {k} is outside the world {name!r}: its origin cell "
-                         f"{r[k].astype(np.int64).tolist()} is not in 0 .. {[shape[0] - n[0], shape[1] - n[1]]}")
+                         f"{r[k].astype(np.int64).tolist()} is not in 0 .. {limit}")
     return r.astype(np.int32)
 
 
 def snap_to_world_map(name, offsets):
     """float32 offsets of the shape given: per robot the nearest offsets whose window starts on a cell and lies inside the world."""
-    q, shape = _window_cells(name, offsets, "snap_to_world_map")
+    q, limit = _window_cells(name, offsets, "snap_to_world_map")
     if not np.isfinite(q).all():
         raise ValueError("snap_to_world_map: every offset must be finite")
-    n = grid_shape()
-    cells = np.clip(np.rint(q), 0, np.asarray([shape[0] - n[0], shape[1] - n[1]], np.float64))
-    origin = np.asarray(_WORLD_MAPS[name][2], np.float64)
-    out = cells * np.float64(SDF_CELL_SIZE) + origin - np.asarray(LIMITS[0], np.float64)
+    cells = np.clip(np.rint(q), 0, np.asarray(limit, np.float64))
+    out = cells * np.float64(SDF_CELL_SIZE) + np.asarray(world_map_origin(name), np.float64) - np.asarray(LIMITS[0], np.float64)
     return out.astype(np.float32).reshape(np.shape(_host_array(offsets)))
 
 
@@ -716,23 +747,10 @@ def world_window_name(name, offset_or_origin):
     if a.size != 2:
         raise ValueError(f"world_window_name: one offset (x, y) or one origin cell (i0, j0), got shape {a.shape}")
     if a.dtype.kind in "iu":
-        i0, j0 = _checked_window_origins(name, a.reshape(1, 2), "world_window_name")[0].tolist()
+        i0, j0 = checked_window_origins(name, a.reshape(1, 2), "world_window_name")[0].tolist()
     else:
         i0, j0 = world_map_window_origins(name, a.reshape(1, 2))[0].tolist()
     return f"{name}{_WINDOW_SEPARATOR}{i0},{j0}"
-
-
-def _texel_indices(points, lo, hi, shape):
-    """(ix, iy, finite): the texel of float32 points [n, 2] on a grid of `shape` over lo .. hi, the fp32 sequence of every consumer of a
-    texture and of mmd_sdf_grid_lookup: floor((p - lo) / |hi - lo| * n) clamped to [0, n - 1] (as a float, then converted)."""
-    f = np.float32
-    lo, hi = np.asarray(lo, f), np.asarray(hi, f)
-    dim = np.abs(hi - lo)
-    finite = np.isfinite(points).all(1)
-    p = np.where(finite[:, None], points, f(0))
-    with np.errstate(over="ignore"):
-        idx = [np.clip(np.floor((p[:, k] - lo[k]) / dim[k] * f(shape[k])), f(0), f(shape[k] - 1)).astype(np.int64) for k in range(2)]
-    return idx[0], idx[1], finite
 
 
 def world_map_sdf(points_global, name, device=None):
@@ -742,12 +760,10 @@ def world_map_sdf(points_global, name, device=None):
     shape = _world(name, "world_map_sdf")[0]
     lo, hi = world_map_limits(name)
     if device is None:
-        pts = np.ascontiguousarray(_host_array(points_global), dtype=np.float32)
-        ix, iy, finite = _texel_indices(pts.reshape(-1, 2), lo, hi, shape)
-        val = np.where(finite, world_map_texture(name)[ix, iy, 0], np.float32(np.nan))
-        return torch.from_numpy(np.ascontiguousarray(val.reshape(pts.shape[:-1]), dtype=np.float32))
-    from . import _lib, guides
-    tex = guides.device_world_texture(name, device)
+        val, finite = texel_values(world_map_texture(name), points_global, lo, hi)
+        return torch.from_numpy(np.where(finite, val, np.float32(np.nan)))
+    from . import _lib
+    tex = _resident().device_world_texture(name, device)
     pts = torch.as_tensor(points_global, dtype=torch.float32).to(tex.device).contiguous()
     flat = pts.reshape(-1, 2)
     out = torch.empty(flat.shape[0], 4, dtype=torch.float32, device=tex.device)
@@ -759,12 +775,5 @@ def world_map_sdf(points_global, name, device=None):
 def device_world_sdf_grid(name, device, out=None):
     """The [WX, WY, 4] texture of the world map `name`, built on `device` by mmd_sdf_grid_from_occupancy: world_map_texture bit for
     bit, for the upload of one byte per cell.  out= rebuilds a resident texture in place on the current stream."""
-    shape = _world(name, "device_world_sdf_grid")[0]
-    device = torch.device(device)
-    if device.type == "cuda" and device.index is None:
-        device = torch.device("cuda", torch.cuda.current_device())
-    if out is None:
-        out = torch.empty(shape[0], shape[1], 4, dtype=torch.float32, device=device)
-    elif tuple(out.shape) != (shape[0], shape[1], 4) or out.device != device:
-        raise ValueError(f"device_world_sdf_grid: out must be [{shape[0]}, {shape[1]}, 4] on {device}, got {tuple(out.shape)} on {out.device}")
+    device, out = _out_texture("device_world_sdf_grid", _world(name, "device_world_sdf_grid")[0], device, out)
     return _occupancy_build(torch.from_numpy(world_map_occupancy(name)).to(device), out)

@@ -11,149 +11,17 @@ import torch
 
 from . import _lib
 from .constraints import CostConstraint, PathConstraintGroup, build_path_groups, pack_constraints
-from . import environments
-from .environments import LIMITS, sdf_grid_texture
+from . import environments, map_textures
+from .environments import LIMITS
+from .map_textures import device_sdf_textures, device_world_texture  # noqa: F401  (device_world_texture: for the callers of this module)
 
 ROBOT_RADIUS = 0.05                 # mmd/config/mmd_params.py:30
 
-# Device-side sharing (SURVEY §8f-3): one resident SDF texture per (map set, device) for every guide / task facade of the
-# process (the reference precomputes the grid once per planner object, grid_map_sdf.py:34-63, N+1 times per instance).
-_TEXTURES = {}
-_WORLD_TEXTURES = {}                # (world map, device) -> its resident texture [WX, WY, 4]
-_WINDOW_CUTS = {}                   # key of _TEXTURES -> [(world map, first slice, origins int32 [n, 2] on the device)]: its window slices
-N_TEXTURE_UPLOADS = 0               # host-built textures copied to a device (shipped maps)
-# Texture slices built on a device, by ONE rule: + 1 for every texture a library call writes whole.  A registered map's slice built or rebuilt
-# (mmd_sdf_grid_build / mmd_sdf_grid_from_occupancy): 1.  A world texture built or rebuilt from its bitmap (mmd_sdf_grid_from_occupancy):
-# 1.  A cut (mmd_sdf_grid_windows): 1 per window slice it writes, so n for a launch of n windows.
-N_TEXTURE_BUILDS = 0
 
-
-def _resolve(device):
-    device = torch.device(device)
-    if device.type == "cuda" and device.index is None:
-        device = torch.device("cuda", torch.cuda.current_device())
-    return device
-
-
-def device_world_texture(name, device):
-    """[WX, WY, 4] float32: the texture of the world map `name` (environments.register_world_map), resident once per (name, device), built
-    there by mmd_sdf_grid_from_occupancy: environments.world_map_texture bit for bit.  Counts 1 in N_TEXTURE_BUILDS when it is built."""
-    global N_TEXTURE_BUILDS
-    device = _resolve(device)
-    key = (name, str(device))
-    if key not in _WORLD_TEXTURES:
-        _WORLD_TEXTURES[key] = environments.device_world_sdf_grid(name, device)
-        N_TEXTURE_BUILDS += 1
-    return _WORLD_TEXTURES[key]
-
-
-def _window_runs(maps):
-    """[(world, first slice, [(i0, j0), ...])]: the window names among `maps`, as runs of neighbouring slices of one world.  The names of a
-    world's windows share a prefix, so in a sorted map set they are one run per world (another map whose name sorts in between splits it)."""
-    runs = []
-    for i, m in enumerate(maps):
-        if not environments.is_world_window(m):
-            continue
-        world, origin = environments.world_window(m)
-        if runs and runs[-1][0] == world and runs[-1][1] + len(runs[-1][2]) == i:
-            runs[-1][2].append(origin)
-        else:
-            runs.append((world, i, [origin]))
-    return runs
-
-
-def _cut_windows(tex, cuts):
-    """One mmd_sdf_grid_windows launch per (world, first slice, origins): the window slices straight into the set's storage `tex`, on the
-    current stream of its device."""
-    global N_TEXTURE_BUILDS
-    for world, first, origins in cuts:
-        wtex = device_world_texture(world, tex.device)
-        n = origins.shape[0]
-        _lib.launch("mmd_sdf_grid_windows", tex, _lib.require_gpu(wtex, "world texture"), wtex.shape[0], wtex.shape[1],
-                    C.c_void_p(origins.data_ptr()), n, tex.shape[2], tex.shape[3], _lib.require_gpu(tex[first:first + n], "window slices"))
-        N_TEXTURE_BUILDS += n
-
-
-def device_sdf_textures(maps, device):
-    """[n_maps, n_grids=1, nx, ny, 4] float32 on `device`, resident once per process.  A shipped map's slice is the host texture,
-    uploaded; a registered map's (environments.register_map / register_occupancy_map) is built on the device from its primitives or
-    its bitmap; the slice of a window of a world map (environments.world_window_name) is cut on the device from the world's resident
-    texture (device_world_texture), all windows of one world in one mmd_sdf_grid_windows launch.  The set is of unique names: windows
-    at equal origins are one slice.  N_TEXTURE_BUILDS counts by the rule stated at its definition."""
-    global N_TEXTURE_UPLOADS, N_TEXTURE_BUILDS
-    device = _resolve(device)
-    key = (tuple(maps), str(device))
-    if key not in _TEXTURES:
-        built = [m for m in maps if environments.is_registered(m)]
-        runs = _window_runs(maps)
-        if not built and not runs:
-            tex = np.stack([sdf_grid_texture(m) for m in maps])[:, None]
-            _TEXTURES[key] = torch.from_numpy(np.ascontiguousarray(tex)).to(device)
-            N_TEXTURE_UPLOADS += 1
-        else:
-            nx, ny = environments.grid_shape()
-            cuts = [(world, first, torch.from_numpy(environments._checked_window_origins(world, np.asarray(origins), "device_sdf_textures"))
-                     .to(device)) for world, first, origins in runs]
-            cut = {first + k for _, first, origins in runs for k in range(len(origins))}
-            tex = torch.empty(len(maps), 1, nx, ny, 4, dtype=torch.float32, device=device)
-            for i, m in enumerate(maps):
-                if m in built:
-                    environments.build_resident_texture(m, device, tex[i, 0])
-                    N_TEXTURE_BUILDS += 1
-                elif i not in cut:
-                    tex[i, 0].copy_(torch.from_numpy(sdf_grid_texture(m)))
-            _cut_windows(tex, cuts)
-            N_TEXTURE_UPLOADS += len(built) + len(cut) < len(maps)
-            _TEXTURES[key] = tex
-            if cuts:
-                _WINDOW_CUTS[key] = cuts
-    return _TEXTURES[key]
-
-
-def rebuild_world_textures(name):
-    """environments.update_world_map: every resident texture of the world map `name` is rebuilt in place from the registry's bitmap, then
-    every resident window slice cut from it is cut again in place, one launch per (map set, run of its windows): same storage, same
-    pointers, on the current stream of the device.  N_TEXTURE_BUILDS: 1 per world texture, 1 per window slice."""
-    global N_TEXTURE_BUILDS
-    for (world, _), wtex in _WORLD_TEXTURES.items():
-        if world == name:
-            environments.device_world_sdf_grid(name, wtex.device, out=wtex)
-            N_TEXTURE_BUILDS += 1
-    for key, cuts in _WINDOW_CUTS.items():
-        _cut_windows(_TEXTURES[key], [c for c in cuts if c[0] == name])
-
-
-def drop_world_textures(name):
-    """environments.unregister_world_map: forget the resident textures of the world map `name` and the map sets that hold a window of it
-    (an object built on one keeps its tensor)."""
-    for key in [k for k in _WORLD_TEXTURES if k[0] == name]:
-        del _WORLD_TEXTURES[key]
-    for key in [k for k, cuts in _WINDOW_CUTS.items() if any(c[0] == name for c in cuts)]:
-        del _WINDOW_CUTS[key]
-        _TEXTURES.pop(key, None)
-
-
-def rebuild_resident_textures(name, device_occupancy=None):
-    """environments.update_map / update_occupancy_map: every resident slice of the registered map `name` is rebuilt in place, in its
-    storage, on the current stream of its device, by the builder of its kind.  device_occupancy: the new bitmap as a device tensor,
-    used as it is for the slices on its device."""
-    global N_TEXTURE_BUILDS
-    for (maps, _), tex in _TEXTURES.items():
-        for i, m in enumerate(maps):
-            if environments.is_registered(m) and m.replace("ExtraObjects", "") == name:
-                with torch.cuda.device(tex.device):
-                    if device_occupancy is not None and device_occupancy.device == tex.device:
-                        environments.device_occupancy_sdf_grid(device_occupancy, tex.device, out=tex[i, 0])
-                    else:
-                        environments.build_resident_texture(m, tex.device, tex[i, 0])
-                N_TEXTURE_BUILDS += 1
-
-
-def drop_resident_textures(name):
-    """environments.unregister_map: forget the resident textures that hold `name` (an object built on one keeps its tensor)."""
-    for key in [k for k in _TEXTURES if any(m.replace("ExtraObjects", "") == name for m in k[0])]:
-        del _TEXTURES[key]
-        _WINDOW_CUTS.pop(key, None)
+def __getattr__(name):              # the residency counters and caches under their names here, read live: a copy of a counter goes stale
+    if name in ("N_TEXTURE_UPLOADS", "N_TEXTURE_BUILDS", "_TEXTURES", "_WORLD_TEXTURES", "_WINDOW_CUTS"):
+        return getattr(map_textures, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
 class GuideManagerTrajectoriesWithVelocity:
@@ -193,10 +61,10 @@ class GuideManagerTrajectoriesWithVelocity:
         # size y), ...]} (MultiSphereField / MultiBoxField arguments; the box is the rounded one of the fixed objects): evaluated analytically by the
         # kernels, one more field next to the fixed objects' grid.  None / empty = the shipped ExtraObjects maps.
         xo = extra_objects or {}
-        sph = np.asarray(xo.get("spheres", []), dtype=np.float32).reshape(-1, 3)
-        box = np.asarray(xo.get("boxes", []), dtype=np.float32).reshape(-1, 4)
-        self._xs = torch.from_numpy(np.concatenate([sph, np.zeros((len(sph), 1), np.float32)], 1)).to(self.device) if len(sph) else None
-        self._xb = torch.from_numpy(np.concatenate([box[:, :2], box[:, 2:] / np.float32(2)], 1)).to(self.device) if len(box) else None
+        box, sph = environments.primitive_table_layout(np.asarray(xo.get("boxes", []), dtype=np.float32).reshape(-1, 4),
+                                                       np.asarray(xo.get("spheres", []), dtype=np.float32).reshape(-1, 3)) if xo else ((), ())
+        self._xs = torch.from_numpy(sph).to(self.device) if len(sph) else None
+        self._xb = torch.from_numpy(box).to(self.device) if len(box) else None
         # extra costs, per robot (guides.py:176-178, :228-234)
         self.extra_cost_l: List[List[CostConstraint]] = [[] for _ in range(n_robots)]
         self.extra_costs_grad_weight_l: List[List[float]] = [[] for _ in range(n_robots)]

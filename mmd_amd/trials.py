@@ -70,13 +70,7 @@ def get_state_pos_column(num_agents: int, x_pos: float):
 def _grid_sdf(env_name, points):
     """The map's SDF GRID value at float32 points [n, 2]: GridMapSDF's cell lookup (grid_map_sdf.py:81-99) on the grid of
     environments.sdf_grid_texture."""
-    grid = environments.sdf_grid_texture(env_name)[..., 0]
-    lo = np.array(environments.LIMITS[0], np.float32)
-    hi = np.array(environments.LIMITS[1], np.float32)
-    dims = np.array(grid.shape[:2])
-    idx = np.floor((np.asarray(points, np.float32) - lo) / (hi - lo) * dims.astype(np.float32)).astype(np.int64)
-    idx = np.clip(idx, 0, dims - 1)
-    return grid[idx[:, 0], idx[:, 1]]
+    return environments.texel_values(environments.sdf_grid_texture(env_name), points)[0]
 
 
 def get_start_goal_pos_random_in_env(num_agents, env_name, margin=0.15, obstacle_margin=0.16, seed=0, max_draws=200000):

@@ -11,7 +11,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
-from mmd_amd import _lib, environments as E, guides, synth      # noqa: E402
+from mmd_amd import _lib, environments as E, map_textures, synth      # noqa: E402
 from oracle import mmd_oracle as O                               # noqa: E402
 import cases                                                     # noqa: E402
 import occupancy_model as M                                      # noqa: E402
@@ -260,11 +260,11 @@ def test_update_occupancy_map_rebuilds_the_resident_texture_in_place(registry, t
     occ_a[150:260, 170:230] = 1
     occ_c = np.ascontiguousarray(occ_b[::-1, ::-1])
     E.register_occupancy_map("Moving", occ_a)
-    uploads, builds = guides.N_TEXTURE_UPLOADS, guides.N_TEXTURE_BUILDS
+    uploads, builds = map_textures.N_TEXTURE_UPLOADS, map_textures.N_TEXTURE_BUILDS
     old = _gc().hip_guide("Moving", [[]])
     both = _gc().hip_guide("EnvEmpty2D", [[], []], n_robots=2, robot_env_ids=["EnvConveyor2D", "Moving"])
-    assert guides.N_TEXTURE_BUILDS == builds + 2 and guides.N_TEXTURE_UPLOADS == uploads + 1     # (the Conveyor slice is an upload)
-    assert _gc().hip_guide("Moving", [[]])._grids is old._grids and guides.N_TEXTURE_BUILDS == builds + 2      # shared, not rebuilt
+    assert map_textures.N_TEXTURE_BUILDS == builds + 2 and map_textures.N_TEXTURE_UPLOADS == uploads + 1     # (the Conveyor slice is an upload)
+    assert _gc().hip_guide("Moving", [[]])._grids is old._grids and map_textures.N_TEXTURE_BUILDS == builds + 2      # shared, not rebuilt
     assert_same_bits(old._grids[0, 0], E.sdf_grid_texture("Moving"), "before the update")
     x = torch.from_numpy(synth.synth_noise(95, (4, H, D))) * 0.6
     hard = torch.zeros(1, 2, D, device="cuda")
@@ -274,10 +274,10 @@ def test_update_occupancy_map_rebuilds_the_resident_texture_in_place(registry, t
     conveyor = E.sdf_grid_texture("EnvConveyor2D")
 
     def updated(new, host, what):
-        uploads, builds = guides.N_TEXTURE_UPLOADS, guides.N_TEXTURE_BUILDS
+        uploads, builds = map_textures.N_TEXTURE_UPLOADS, map_textures.N_TEXTURE_BUILDS
         E.update_occupancy_map("Moving", new)
         assert (old._grids.data_ptr(), both._grids.data_ptr()) == ptrs
-        assert guides.N_TEXTURE_UPLOADS == uploads and guides.N_TEXTURE_BUILDS == builds + 2    # one per resident slice of the name
+        assert map_textures.N_TEXTURE_UPLOADS == uploads and map_textures.N_TEXTURE_BUILDS == builds + 2    # one per resident slice of the name
         assert_same_bits(old._grids[0, 0], host, what)
         assert_same_bits(both._grids[1, 0], host, what + ", mixed texture")
         assert_same_bits(both._grids[0, 0], conveyor, what + ": the other slice is untouched")

@@ -431,11 +431,11 @@ def test_device_side_sharing_of_models_and_maps():
     inference_multi_agent.py:186-237) hold ONE packed weight blob + ONE time table (sized to the schedule) and ONE SDF
     texture per map on the device."""
     import time
-    from mmd_amd import guides, temporal_unet
+    from mmd_amd import map_textures, temporal_unet
     from mmd_amd.planners import MPD
     sd = synth.synth_unet_state_dict(3)                               # weights no other test uses
     starts, goals = synth.start_goal_circle(8, 0.8)
-    created0, tex0 = temporal_unet.N_DEVICE_MODELS_CREATED, guides.N_TEXTURE_UPLOADS
+    created0, tex0 = temporal_unet.N_DEVICE_MODELS_CREATED, map_textures.N_TEXTURE_UPLOADS
     t0 = time.perf_counter()
     planners = [MPD(start_state_pos=torch.from_numpy(starts[i]), goal_state_pos=torch.from_numpy(goals[i]),
                     **_mpd_kwargs(model_id="EnvDropRegion2D-RobotPlanarDisk", model_state_dict=sd, n_samples=4))
@@ -445,7 +445,7 @@ def test_device_side_sharing_of_models_and_maps():
     dt = time.perf_counter() - t0
     assert all(torch.isfinite(o.trajs_iters).all() for o in outs)
     assert temporal_unet.N_DEVICE_MODELS_CREATED - created0 == 1, "8 planners must share one mmd_unet_create"
-    assert guides.N_TEXTURE_UPLOADS - tex0 <= 1, "8 planners must share one SDF texture upload"
+    assert map_textures.N_TEXTURE_UPLOADS - tex0 <= 1, "8 planners must share one SDF texture upload"
     handles = {p.model.model.handle(25).value for p in planners}
     assert len(handles) == 1
     assert len({p.guide._grids.data_ptr() for p in planners}) == 1

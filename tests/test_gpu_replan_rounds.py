@@ -8,7 +8,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
-from mmd_amd import guides, multi_agent as ma, synth                             # noqa: E402
+from mmd_amd import map_textures, multi_agent as ma, synth                       # noqa: E402
 from mmd_amd.constraints import binned_collision_table                           # noqa: E402
 from mmd_amd.multi_robot import MultiRobotSampler                                # noqa: E402
 import replan_model as S                                                         # noqa: E402
@@ -77,9 +77,9 @@ def test_a_subset_round_is_the_round_of_the_permuted_instance(table):
     sel, robots = _select(s, paths, "conflicted")
     perm = sel.perm.tolist()
     assert perm == [2, 5, 0, 1, 3, 4, 6, 7] and sel.read_header() == (2, 0, 2, 0)
-    uploads = guides.N_TEXTURE_UPLOADS
+    uploads = map_textures.N_TEXTURE_UPLOADS
     t_sub, best_sub, ids = s.replan_round(paths, sel, seed)
-    assert guides.N_TEXTURE_UPLOADS == uploads                                    # the subset's guide shares the resident SDF texture
+    assert map_textures.N_TEXTURE_UPLOADS == uploads                                    # the subset's guide shares the resident SDF texture
     assert ids.tolist() == [2, 5] and ids.is_cuda and t_sub.shape == (2 * B, H, D) and best_sub.shape == (2, H, 2)
     other = _sampler(starts[perm], goals[perm], constraint_table=table)
     paths_perm = paths[sel.perm.long()].contiguous()

@@ -10,7 +10,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
-from mmd_amd import _lib, environments as E, guides, synth      # noqa: E402
+from mmd_amd import _lib, environments as E, guides, map_textures, synth      # noqa: E402
 from oracle import mmd_oracle as O                               # noqa: E402
 import cases                                                     # noqa: E402
 import world_map_model as M                                      # noqa: E402
@@ -298,16 +298,16 @@ def test_update_world_map_rebuilds_and_recuts_in_place(registry):
     starts, goals = offsets + np.float32([-0.8, -0.8]), offsets + np.float32([0.8, -0.7])
     names = [E.world_window_name("Moving", o) for o in offsets]
     assert names[0] == names[2] == "Moving@0,0" and names[1] == "Moving@0,120"
-    uploads, builds = guides.N_TEXTURE_UPLOADS, guides.N_TEXTURE_BUILDS
+    uploads, builds = map_textures.N_TEXTURE_UPLOADS, map_textures.N_TEXTURE_BUILDS
     s = WorldRobotSampler(_gc().hip_model(T), starts, goals, offsets, env_id="Moving", n_samples=4)
-    assert guides.N_TEXTURE_BUILDS == builds + 1 + 2 and guides.N_TEXTURE_UPLOADS == uploads     # the world texture, two window slices
+    assert map_textures.N_TEXTURE_BUILDS == builds + 1 + 2 and map_textures.N_TEXTURE_UPLOADS == uploads     # the world texture, two window slices
     mixed = _gc().hip_guide("EnvEmpty2D", [[], []], n_robots=2, robot_env_ids=["EnvConveyor2D", names[1]])
-    assert guides.N_TEXTURE_BUILDS == builds + 4 and guides.N_TEXTURE_UPLOADS == uploads + 1     # one more slice cut; Conveyor is an upload
+    assert map_textures.N_TEXTURE_BUILDS == builds + 4 and map_textures.N_TEXTURE_UPLOADS == uploads + 1     # one more slice cut; Conveyor is an upload
     live = _gc().hip_guide(names[0], [[]])
-    assert guides.N_TEXTURE_BUILDS == builds + 5
-    assert _gc().hip_guide(names[0], [[]])._grids is live._grids and guides.N_TEXTURE_BUILDS == builds + 5      # shared, not cut again
+    assert map_textures.N_TEXTURE_BUILDS == builds + 5
+    assert _gc().hip_guide(names[0], [[]])._grids is live._grids and map_textures.N_TEXTURE_BUILDS == builds + 5      # shared, not cut again
     wtex = guides.device_world_texture("Moving", "cuda")
-    assert guides.N_TEXTURE_BUILDS == builds + 5                                                 # resident already
+    assert map_textures.N_TEXTURE_BUILDS == builds + 5                                                 # resident already
     ptrs = (wtex.data_ptr(), s.guide._grids.data_ptr(), mixed._grids.data_ptr(), live._grids.data_ptr())
     conveyor = E.sdf_grid_texture("EnvConveyor2D")
     assert_same_words(mixed._grids[0, 0], conveyor, "the shipped slice")
@@ -315,11 +315,11 @@ def test_update_world_map_rebuilds_and_recuts_in_place(registry):
     hard = torch.zeros(1, 2, D, device="cuda")
     before = live.guide_steps(x.clone().cuda(), hard, 0, 5)
 
-    builds = guides.N_TEXTURE_BUILDS
+    builds = map_textures.N_TEXTURE_BUILDS
     E.update_world_map("Moving", occ_b)
     assert (wtex.data_ptr(), s.guide._grids.data_ptr(), mixed._grids.data_ptr(), live._grids.data_ptr()) == ptrs
     assert guides.device_world_texture("Moving", "cuda") is wtex
-    assert guides.N_TEXTURE_BUILDS == builds + 1 + 2 + 1 + 1 and guides.N_TEXTURE_UPLOADS == uploads + 1      # the world; 2, 1 and 1 slices
+    assert map_textures.N_TEXTURE_BUILDS == builds + 1 + 2 + 1 + 1 and map_textures.N_TEXTURE_UPLOADS == uploads + 1      # the world; 2, 1 and 1 slices
     assert_same_words(wtex, E.world_map_texture("Moving"), "the world texture after the update")
     crops = E.world_map_windows("Moving", [(0, 0), (0, 120)])
     assert s.guide._robot_map.cpu().tolist() == [0, 1, 0]
@@ -332,4 +332,4 @@ def test_update_world_map_rebuilds_and_recuts_in_place(registry):
     after = live.guide_steps(x.clone().cuda(), hard, 0, 5)
     assert torch.equal(after, fresh.guide_steps(x.clone().cuda(), hard, 0, 5)) and not torch.equal(after, before)
     E.unregister_world_map("Moving")
-    assert not any(k[0] == "Moving" for k in guides._WORLD_TEXTURES) and not any("Moving@" in m for k in guides._TEXTURES for m in k[0])
+    assert not any(k[0] == "Moving" for k in map_textures._WORLD_TEXTURES) and not any("Moving@" in m for k in map_textures._TEXTURES for m in k[0])

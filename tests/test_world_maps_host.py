@@ -2,6 +2,7 @@
 definition (a window is the crop of the world's transform, not the transform of the cropped bitmap), the one-tile world, random
 instances, and the surface and the argument checks of mmd_sdf_grid_windows / mmd_sdf_grid_lookup, which answer before any launch."""
 import ctypes as C
+import math
 import os
 
 import numpy as np
@@ -92,6 +93,93 @@ def test_registry_and_name_clashes(registry):
         E.unregister_world_map("Big")
     E.register_map("Big@0,37", [(0, 0, 0.1, 0.1)])                                           # free again, as before the world map
     assert E.registered_maps() == tuple(sorted(before + ("Big@0,37", "Floor", "Other@3,4", "Prims")))
+
+
+def test_resolve_map_agrees_with_the_predicates(registry):
+    """environments.resolve_map is the one reading of a map name: over a fixed list of names, the kind it returns (None: KeyError) is what
+    every public predicate answers, and base name, record and origin are the registry's."""
+    E.register_map("Prims", [(0, 0, 0.1, 0.1)])
+    E.register_occupancy_map("Floor", np.zeros((400, 400), np.uint8))
+    E.register_world_map("World", np.zeros((400, 500), np.uint8))
+    window = E.world_window_name("World", (0, 37))
+    assert window == "World@0,37"
+    names = (("EnvHighways2D", "shipped"), ("EnvHighways2DExtraObjects", "shipped"), ("Prims", "primitives"), ("Floor", "occupancy"),
+             ("World", None), (window, "window"), ("World@1,", None), ("World@-1,2", None), ("Other@3,4", None), (7, None))
+    for name, kind in names:
+        try:
+            got = E.resolve_map(name)
+        except KeyError:
+            got = (None,) * 4
+        assert got[0] == kind, name
+        assert E.is_registered(name) == (kind in ("primitives", "occupancy")), name
+        assert E.is_occupancy_map(name) == (kind == "occupancy"), name
+        assert E.is_world_window(name) == (kind == "window"), name
+        assert E.is_world_map(name) == (name == "World"), name
+    assert E.resolve_map("EnvHighways2DExtraObjects") == ("shipped", "EnvHighways2D", None, None)
+    kind, base, rec, origin = E.resolve_map("PrimsExtraObjects")
+    assert (kind, base, origin) == ("primitives", "Prims", None) and rec.kind == "primitives" and rec.content == E.map_primitives("Prims")
+    kind, base, rec, origin = E.resolve_map(window + "ExtraObjects")
+    assert (kind, base, origin) == ("window", "World", (0, 37)) and rec.kind == "world" and E.world_window(window) == ("World", (0, 37))
+    with pytest.raises(KeyError, match="Other@3,4"):
+        E.sdf_grid_texture("Other@3,4")
+
+
+def test_guides_reads_the_residency_counters_live():
+    """guides still answers to the counters' and caches' names: the values of map_textures at the time of the read, never a copy."""
+    from mmd_amd import guides, map_textures
+    assert guides._TEXTURES is map_textures._TEXTURES and guides._WORLD_TEXTURES is map_textures._WORLD_TEXTURES
+    assert guides.device_world_texture is map_textures.device_world_texture
+    before = map_textures.N_TEXTURE_BUILDS
+    map_textures.N_TEXTURE_BUILDS = before + 3
+    try:
+        assert guides.N_TEXTURE_BUILDS == before + 3 and guides.N_TEXTURE_UPLOADS == map_textures.N_TEXTURE_UPLOADS
+    finally:
+        map_textures.N_TEXTURE_BUILDS = before
+    with pytest.raises(AttributeError):
+        guides.N_TEXTURE_NOTHING
+
+
+def _texel_model(p, lo, hi, n):
+    """One axis of the texel of a point in plain Python: the fp32 sequence (p - lo) / |hi - lo| * n, one rounding per operation, then
+    min(max(floor, 0), n - 1) on Python integers.  No float outside the integer range is converted: an infinite product is past the
+    border it points to."""
+    f = np.float32
+    with np.errstate(over="ignore"):
+        t = (f(p) - f(lo)) / abs(f(hi) - f(lo)) * f(n)
+    if np.isinf(t):
+        return n - 1 if t > 0 else 0
+    return min(max(math.floor(float(t)), 0), n - 1)
+
+
+def test_one_texel_lookup_on_the_host(registry):
+    """The host has ONE texel lookup (environments.texel_values on _texel_indices).  400 x 400 over LIMITS: every cell edge on both axes,
+    10 000 random points in +-1.2, the limits themselves and points far outside, +-1e30 and +-3e38 (whose scaled coordinate is past
+    int64, or infinite) -- exactly the indices of the plain-Python model; map_sdf of an occupancy map and trials._grid_sdf return the
+    texture's value at those indices."""
+    import torch
+    from mmd_amd import trials
+    f = np.float32
+    edges = np.arange(-210, 211) * 0.005
+    special = [1.0, -1.0, np.nextafter(f(1), f(0)), -np.nextafter(f(1), f(0)), 1e30, -1e30, 3e38, -3e38]
+    pts = np.concatenate([np.stack([edges, edges[::-1]], 1), np.stack([special, special[::-1]], 1),
+                          np.random.Generator(np.random.PCG64(11)).uniform(-1.2, 1.2, (10000, 2))]).astype(f)
+    assert np.isfinite(pts).all()
+    want = np.array([[_texel_model(p[k], E.LIMITS[0][k], E.LIMITS[1][k], 400) for k in range(2)] for p in pts.tolist()])
+    assert want.min() == 0 and want.max() == 399 and len(np.unique(want[:, 0])) == 400
+    ix, iy, finite = E._texel_indices(pts, E.LIMITS[0], E.LIMITS[1], (400, 400))
+    assert finite.all() and np.array_equal(ix, want[:, 0]) and np.array_equal(iy, want[:, 1])
+    # a texture that names its texel, in the place of the map's own (the transform of a bitmap takes longer than this whole test)
+    E.register_occupancy_map("Lookup", np.zeros((400, 400), np.uint8))
+    tex = np.zeros((400, 400, 4), f)
+    tex[..., 0] = np.arange(160000, dtype=f).reshape(400, 400)
+    E._HOST_TEXTURES[("Lookup", E.SDF_CELL_SIZE)] = (E.resolve_map("Lookup")[2].content, tex)
+    assert E.sdf_grid_texture("Lookup") is tex
+    value = (want[:, 0] * 400 + want[:, 1]).astype(f)
+    got = E.map_sdf(pts, "Lookup")
+    assert got.dtype == torch.float32 and np.array_equal(got.numpy(), value)
+    assert np.array_equal(trials._grid_sdf("Lookup", pts), value)
+    values, finite = E.texel_values(tex, pts[:10400].reshape(100, 104, 2))                   # any leading shape
+    assert values.shape == finite.shape == (100, 104) and finite.all() and np.array_equal(values.reshape(-1), value[:10400])
 
 
 def test_shape_limits(registry):

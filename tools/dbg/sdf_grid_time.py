@@ -22,7 +22,7 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
-from mmd_amd import environments as E, guides, synth                                  # noqa: E402
+from mmd_amd import environments as E, guides, map_textures, synth                                  # noqa: E402
 from mmd_amd.normalization import TrajectoryDatasetFacade                              # noqa: E402
 
 WARMUP, PASSES = 3, 15
@@ -102,10 +102,10 @@ def main():
         ptr = guide._grids.data_ptr()
         _, up = timed(update)
         assert guide._grids.data_ptr() == ptr
-        builds = guides.N_TEXTURE_BUILDS
+        builds = map_textures.N_TEXTURE_BUILDS
         _, re = timed(recreate)
         say(f"{n:10d} | update_map {up:12.1f} | unregister + register + new guide (device build) {re:12.1f} | {re / up:6.1f} x   "
-            f"({guides.N_TEXTURE_BUILDS - builds} device builds on the right-hand side)")
+            f"({map_textures.N_TEXTURE_BUILDS - builds} device builds on the right-hand side)")
         E.unregister_map("Live")
     if len(sys.argv) > 1:
         with open(sys.argv[1], "w") as f:
