@@ -705,6 +705,67 @@ int mmd_sdf_grid_windows(const float* world_grid_dev, int wnx, int wny, const in
 int mmd_sdf_grid_lookup(const float* grid_dev, int nx, int ny, const float lo[2], const float hi[2],
                         const float* points_dev /* [n][2] */, int n_points, float* out_dev /* [n][4] */, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * World routes: geodesic distance fields of a texture's routable cells, and the tiles a descent crosses
+ * ---------------------------------------------------------------------------------------------------------- */
+
+/* The distance fields of n_fields goals over one SDF texture grid_dev [nx][ny][4] (any map's: a world texture, a tile's slice).  All
+ * integers are exact; mmd_amd/world_routes.py (routable_cells, grid_distance_field) is the same definition on the host.
+ *   routable[ix][iy] = grid[ix][iy][0] > clearance (a strict fp32 compare: a NaN texel is not routable) and
+ *                      region[0] <= ix < region[2] and region[1] <= iy < region[3]   (region = (i_lo, j_lo, i_hi, j_hi), a host array)
+ *   dist[f][ix][iy]  = the length in steps of the shortest 4-connected path over routable cells from goals[f] to (ix, iy), unit cost per
+ *                      step; MMD_GRID_DIST_UNREACHED on a cell that is not routable or cannot be reached.  goals_dev [n_fields][2] =
+ *                      (ix, iy) int32 on the device: a goal that is not routable or lies outside the grid gives a field that is
+ *                      UNREACHED everywhere, not an error.
+ * The method is a block-tiled Bellman-Ford: a workgroup owns a block of MMD_GRID_DIST_BLOCK x MMD_GRID_DIST_BLOCK cells of one field,
+ * relaxes it in LDS against a one-cell halo until nothing in it changes, writes back what fell and marks itself changed; a block runs
+ * in a sweep iff it or one of its 4 neighbour blocks changed in the sweep before.  One launch per sweep: nothing inside a sweep waits on
+ * another workgroup, and the result does not depend on the order or the placement of the workgroups (the argument stands next to the
+ * kernel, csrc/grid_route.hip).
+ *   restart != 0: every cell becomes UNREACHED, a routable goal 0, and the goal's block is flagged; then n_sweeps sweeps.
+ *   restart == 0: n_sweeps more sweeps on dist_dev and work_dev as the previous call on the same arguments left them.  A caller restarts
+ *                 after the texture, the clearance, the region or a goal changed.
+ *   changed_dev[f] = the number of blocks of field f that lowered a value in the call's last sweep (after a restart with n_sweeps == 0: 1
+ *                 if the goal was seeded, else 0).  0 means converged: dist[f] is the exact field, and further sweeps do nothing.
+ * The call runs exactly n_sweeps sweeps and does not synchronise: the convergence policy is the caller's (the number of routable cells
+ * + 2 sweeps always suffice; an open grid of bx x by blocks needs at most bx + by).
+ * work_dev: mmd_grid_distance_work_bytes(nx, ny, n_fields) bytes, 4-byte aligned: per field a sweep count and one int32 per block.  A
+ * restart initialises it; between a restart and its continuations the caller leaves it alone.
+ * Error returns, before anything is launched: nx or ny below 1 or above MMD_OCCUPANCY_MAX_SIDE; n_fields negative or above
+ * MMD_GRID_DIST_MAX_FIELDS (the field is a block index); n_sweeps negative; a clearance that is not finite; a NULL region, or one with
+ * lo > hi or outside [0, nx] x [0, ny]; with n_fields > 0, a NULL grid, goals, dist, workspace or changed, or work_bytes too small.
+ * n_fields == 0, or n_sweeps == 0 with restart == 0, returns 0 and launches nothing.
+ * mmd_grid_distance_work_bytes returns 0 for a size the call refuses. */
+#define MMD_GRID_DIST_BLOCK 64
+#define MMD_GRID_DIST_UNREACHED 0x7fffffff
+#define MMD_GRID_DIST_MAX_FIELDS 65535
+size_t mmd_grid_distance_work_bytes(int nx, int ny, int n_fields);
+int mmd_grid_distance_field(const float* grid_dev, int nx, int ny, float clearance, const int32_t region[4],
+                            const int32_t* goals_dev /* [n_fields][2] */, int n_fields, int restart, int n_sweeps,
+                            int32_t* dist_dev /* [n_fields][nx][ny] */, void* work_dev, size_t work_bytes,
+                            int32_t* changed_dev /* [n_fields] */, void* stream);
+
+/* The descent of n_queries starts through converged fields, one lane per query, and the lattice tiles each walk crosses
+ * (mmd_amd/world_routes.py::descend is the same definition on the host).  Lattice tile (a, b) covers the cells
+ * [o_i + a * tile, o_i + (a + 1) * tile) x [o_j + b * tile, o_j + (b + 1) * tile), lattice_origin = (o_i, o_j), a host array.
+ * Query q starts at cell starts_dev[q] in field field_dev[q], both device data.  From cell c with d = dist[c], while d > 0: the
+ * candidates are the neighbours in the order +x, -x, +y, -y that lie inside the grid and hold exactly d - 1; the walk takes the first
+ * candidate in the lattice tile of c, or, if there is none, the first candidate.  tiles_dev[q] starts with the start's tile and gets a
+ * tile each time the walk enters a tile other than the last one listed (a tile may occur twice).  summary_dev[q] = (steps, n_tiles,
+ * status, 0):
+ *   0  ok: steps = dist[start], n_tiles tiles written
+ *   1  the start holds MMD_GRID_DIST_UNREACHED: steps = -1, n_tiles = 0, nothing written
+ *   2  stuck: no neighbour holds d - 1 (the field was not converged); the walk stops there, steps and n_tiles are what it covered
+ *   3  more than max_tiles tiles: n_tiles is the true count, the first max_tiles are written, steps = dist[start]
+ *   4  the start lies outside the grid, or the field index outside [0, n_fields): steps = -1, n_tiles = 0, nothing written
+ * The loop runs at most dist[start] times whatever the field holds (d falls by one per step); rows of tiles_dev behind n_tiles are not
+ * written.  Error returns, before anything is launched: nx or ny below 1 or above MMD_OCCUPANCY_MAX_SIDE; a negative n_fields or
+ * n_queries; tile or max_tiles below 1; a NULL lattice_origin or one beyond +-2^30; with n_queries > 0, a NULL dist (with n_fields > 0),
+ * starts, field indices, tiles or summary.  n_queries == 0 returns 0 and launches nothing. */
+int mmd_grid_descend(const int32_t* dist_dev, int nx, int ny, int n_fields, const int32_t* starts_dev /* [n][2] */,
+                     const int32_t* field_dev /* [n] */, int n_queries, int tile, const int32_t lattice_origin[2], int max_tiles,
+                     int32_t* tiles_dev /* [n][max_tiles][2] */, int32_t* summary_dev /* [n][4] */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -182,7 +182,13 @@ _SIGNATURES = {
     "mmd_sdf_grid_windows": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "mmd_sdf_grid_lookup": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_void_p, C.c_int,
                                       C.c_void_p, C.c_void_p]),
+    "mmd_grid_distance_work_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "mmd_grid_distance_field": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_float, C.POINTER(C.c_int32), C.c_void_p, C.c_int, C.c_int,
+                                          C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "mmd_grid_descend": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int32),
+                                   C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
+GRID_DIST_BLOCK, GRID_DIST_UNREACHED = 64, 0x7fffffff       # MMD_GRID_DIST_BLOCK, MMD_GRID_DIST_UNREACHED
 
 # include/mmd_amd_debug.h: measurement hooks (bench.py / tools), not part of the drop-in boundary
 _DEBUG_SIGNATURES = {
