@@ -766,6 +766,49 @@ int mmd_grid_descend(const int32_t* dist_dev, int nx, int ny, int n_fields, cons
                      const int32_t* field_dev /* [n] */, int n_queries, int tile, const int32_t lattice_origin[2], int max_tiles,
                      int32_t* tiles_dev /* [n][max_tiles][2] */, int32_t* summary_dev /* [n][4] */, void* stream);
 
+/* mmd_grid_descend with the support cells of the cell path (mmd_amd/world_routes.py::descend_samples is the same definition on the
+ * host).  The walk, tiles_dev and summary_dev are mmd_grid_descend's, word for word.  The cell path is c_0 (the start) .. c_steps (the
+ * goal); visit k, the k-th listed tile, owns the path indices [f_k, f_k + m_k), m_k >= 1, and
+ *   visit_cells_dev[q][k] = m_k
+ *   cells_dev[q][k][j]    = c[f_k + (j * (m_k - 1) + 31) / 63], j = 0 .. 63 (integer division): monotone in j, j = 0 the visit's first
+ *                           cell and j = 63 its last; with m_k = 1 all 64 are that cell.
+ * Rows of visit_cells_dev and cells_dev behind a query's n_tiles, and all rows of a query whose status is not 0, are written 0 (every
+ * word of both buffers is written).  One lane per query walks the field twice, with no buffer proportional to the path: the first walk
+ * counts m_k, the second emits each visit's samples as it passes them.  Each walk's loop runs at most dist[start] times whatever the
+ * field holds.  Error returns, before anything is launched: those of mmd_grid_descend, max_tiles above MMD_ROUTE_SEED_MAX_TILES, a NULL
+ * visit_cells or cells with n_queries > 0.  n_queries == 0 returns 0 and launches nothing. */
+#define MMD_ROUTE_SEED_POINTS 64
+#define MMD_ROUTE_SEED_MAX_TILES 16
+int mmd_grid_descend_samples(const int32_t* dist_dev, int nx, int ny, int n_fields, const int32_t* starts_dev /* [n][2] */,
+                             const int32_t* field_dev /* [n] */, int n_queries, int tile, const int32_t lattice_origin[2], int max_tiles,
+                             int32_t* tiles_dev /* [n][max_tiles][2] */, int32_t* summary_dev /* [n][4] */,
+                             int32_t* visit_cells_dev /* [n][max_tiles] */, int32_t* cells_dev /* [n][max_tiles][64][2] */, void* stream);
+
+/* The seed trajectories of n_routes routes, in trajs_final's format, from what mmd_grid_descend_samples wrote
+ * (mmd_amd/world_routes.py::seed_trajectory is the same definition on the host, bit for bit).  Every operation is one fp32 rounding,
+ * with no fused multiply-add.  Route q with status 0 has K = n_tiles visits and N = 64 K points, i = 64 k + j:
+ *   p[i]   = lo + ((float)cell + 0.5f) * pitch per axis, pitch = |hi - lo| / (float)n: the centre of cells_dev[q][k][j]; its texel is
+ *            that cell.  p[0] = start_points_dev[q] and p[N - 1] = goal_points_dev[q], which stay fixed.
+ *   smooth_iters Jacobi iterations, every interior i from the values of the iteration before: c = 0.5f * (p[i - 1] + p[i + 1]) per axis;
+ *            (ix, iy) = the texel of c (mmd_sdf_grid_lookup's sequence); p'[i] = c iff grid[ix][iy][0] > clearance (strict: a NaN
+ *            rejects) and (ix, iy) is a cell of lattice tile tiles_dev[q][i / 64]; else p'[i] = p[i].
+ *   v[i]   = (p[i + 1] - p[i - 1]) / two_dt per axis (correctly rounded), 0 at i = 0 and i = N - 1.
+ *   seeds_dev[q][i] = (p.x, p.y, v.x, v.y); rows behind N are 0.
+ *   clear_min_dev[q] = the least grid[texel of p[i]][0] over the final points, least in the order of the values' bits (-0 below +0, a
+ *            NaN beyond the infinity of its sign): one defined word whatever the texture holds.
+ * A route whose status is not 0, or whose n_tiles is below 1, gets all-zero rows and clear_min 0, and reads no texel; n_tiles above
+ * max_tiles counts as max_tiles.  The seed keeps the clearance at its support points, in their own tiles; it says nothing about the
+ * segments between them.  One workgroup per route; the result does not depend on the launch shape.
+ * Error returns, before anything is launched: nx or ny below 1 or above MMD_OCCUPANCY_MAX_SIDE; NULL or non-finite limits or a zero
+ * extent; a clearance that is not finite; two_dt not finite or <= 0; smooth_iters or n_routes negative; tile below 1; max_tiles outside
+ * 1 .. MMD_ROUTE_SEED_MAX_TILES; a NULL lattice_origin or one beyond +-2^30; with n_routes > 0, a NULL grid, cells, tiles, summary,
+ * start or goal points, seeds or clear_min.  n_routes == 0 returns 0 and launches nothing. */
+int mmd_route_seeds(const float* grid_dev, int nx, int ny, const float lo[2], const float hi[2], float clearance,
+                    const int32_t* cells_dev /* [n][max_tiles][64][2] */, const int32_t* tiles_dev /* [n][max_tiles][2] */,
+                    const int32_t* summary_dev /* [n][4] */, int n_routes, int tile, const int32_t lattice_origin[2], int max_tiles,
+                    const float* start_points_dev /* [n][2] */, const float* goal_points_dev /* [n][2] */, int smooth_iters, float two_dt,
+                    float* seeds_dev /* [n][max_tiles * 64][4] */, float* clear_min_dev /* [n] */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

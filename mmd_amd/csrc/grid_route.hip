@@ -8,6 +8,7 @@
 
 #include "../../include/mmd_amd.h"
 #include "common.h"
+#include "grid_route_dev.h"
 
 namespace mmd {
 
@@ -178,12 +179,7 @@ __global__ __launch_bounds__(GD_THREADS) void grid_distance_count_kernel(int n_f
   }
 }
 
-// ---- the descent: one lane per query (include/mmd_amd.h: mmd_grid_descend) ----
-__device__ __forceinline__ long long floor_div(long long a, long long b) {     // b > 0
-  const long long q = a / b;
-  return (a % b < 0) ? q - 1 : q;
-}
-
+// ---- the descent: one lane per query (include/mmd_amd.h: mmd_grid_descend; floor_div: grid_route_dev.h) ----
 // From the start cell, while d > 0: the neighbours in the order +x, -x, +y, -y that lie inside the grid and hold exactly d - 1; the first
 // of them in the current cell's lattice tile, else the first.  The loop runs at most dist[start] times, whatever the field holds: d falls
 // by one per step.  The lanes of a wave walk unrelated cells: four scattered 4-byte loads per step and lane, no LDS, no atomics.

@@ -20,6 +20,13 @@ __device__ __forceinline__ int wave_max(int v) {
   return v;
 }
 
+// minimum over the wave, on every lane: the same butterfly
+__device__ __forceinline__ int wave_min(int v) {
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) v = min(v, __shfl_xor(v, m));
+  return v;
+}
+
 // sum over a 256-thread block, on every thread.  LAST: the kernel's last use of lds4, which needs no barrier behind the read
 template <bool LAST = false>
 __device__ __forceinline__ int block_sum(int v, int* lds4) {
