@@ -26,6 +26,7 @@ RTBS = ["downs.0.0", "downs.0.1", "downs.1.0", "downs.1.1", "downs.2.0", "downs.
         "mid_block1", "mid_block2"]                                   # state_dict order, as csrc/unet.hip packs them
 CONV_BLOCKS = [f"{r}.blocks.{i}" for r in RTBS for i in (0, 1)] + ["final_conv.0"]
 LAYERED_SETS = ("colspread",) + L.CONTRAST_SETS
+EMULATION_MARGIN = 2.0                # a kernel against the emulation of its own operand rounding (test_f16_mode_is_on_and_within_twice_its_emulation)
 
 
 def _seed0():
@@ -176,20 +177,30 @@ def scale_bounds(sd_np, T=T_STEPS):
 
 # ---- the emulation
 def _dyn_scale(x):
-    """per sample 2^(10 - floor(log2 M)), M the sample's largest |x|, at most 2^73 (dyn_scale, csrc/f16x2.h)"""
-    m = x.abs().amax(dim=(1, 2), keepdim=True)
+    """per sample 2^(10 - floor(log2 M)), M the sample's largest |x|, at most 2^73 (dyn_scale, csrc/f16x2.h); the exponent is read in
+    float64 whatever x's type (a power of two: exact in either)"""
+    m = x.abs().amax(dim=(1, 2), keepdim=True).double()
     m = torch.where(m > 0, m, torch.full_like(m, 2.0 ** -80))
-    return torch.exp2(torch.clamp(10 - torch.floor(torch.log2(m)), max=73.0))
+    return torch.exp2(torch.clamp(10 - torch.floor(torch.log2(m)), max=73.0)).to(x.dtype)
 
 
 def _col_scale(w, dims):
     """per output channel the power of two that puts its largest |w| into [2^14, 2^15); 1 for an all-zero one (f16_scale_for)"""
-    m = w.abs().amax(dim=dims, keepdim=True)
-    return torch.where(m > 0, torch.exp2(14 - torch.floor(torch.log2(torch.where(m > 0, m, torch.ones_like(m))))), torch.ones_like(m))
+    m = w.abs().amax(dim=dims, keepdim=True).double()
+    s = torch.where(m > 0, torch.exp2(14 - torch.floor(torch.log2(torch.where(m > 0, m, torch.ones_like(m))))), torch.ones_like(m))
+    return s.to(w.dtype)
 
 
-def _two_pieces(v, s, low_piece):
+def _keep_bits(v, bits):
+    """v rounded to `bits` significant bits (to nearest; 0, inf and NaN pass)"""
+    m, e = torch.frexp(v)
+    return torch.where(torch.isfinite(v), torch.ldexp(torch.round(torch.ldexp(m, torch.tensor(bits))), e - bits), v)
+
+
+def _two_pieces(v, s, low_piece, bits=11):
     hi = (v * s).half().to(v.dtype)
+    if bits != 11:            # ONE rounding of v s to `bits` bits (not a second one behind fp16's) wherever fp16 holds it as a normal number
+        hi = torch.where(torch.isfinite(hi) & (hi.abs() >= 2.0 ** -14), _keep_bits(v * s, bits), hi)
     if not low_piece:
         return hi / s
     return (hi + (v * s - hi).half().to(v.dtype)) / s
@@ -215,39 +226,48 @@ def _oracle_functional(**swapped):
         O.F = real
 
 
-def emulated_forward(sd_np, x, t, T=T_STEPS, low_piece=True, mish="torch", static_scale=None):
+def emulated_forward(sd_np, x, t, T=T_STEPS, low_piece=True, mish="torch", static_scale=None, dtype=torch.float64, operand_bits=11,
+                     weight_scale="column"):
     """The float64 oracle forward with every conv's input and weight rounded to two fp16 pieces under the kernel's scales: the input per
     sample by dyn_scale, but for conv B of every residual block and final_conv.1, whose inputs carry static_act_scale; the weights
     per output channel (a ConvTranspose1d per output channel and parity, as its two packs).
     The mutants: low_piece=False drops the second piece of both operands; mish="kernel" restates Mish as gn_mish.h does,
-    "kernel_noclamp" the same without the clamp at 20; static_scale=s uses the constant s wherever the packer computes one."""
+    "kernel_noclamp" the same without the clamp at 20; static_scale=s uses the constant s wherever the packer computes one;
+    operand_bits=b keeps b significant bits of the high piece where fp16 keeps 11; weight_scale="tensor" scales a weight by ONE power
+    of two where the packer has one per output channel.  dtype=torch.float32: the same roundings under the same scales (they are
+    powers of two, chosen in float64) with the state dict, the input and every operation of the forward in float32."""
+    assert weight_scale in ("column", "tensor"), weight_scale
     sd64 = {k: v.double() for k, v in O.state_dict_to_torch(sd_np).items()}
+    sd = sd64 if dtype == torch.float64 else {k: v.to(dtype) for k, v in sd64.items()}
     tb = time_bias_absmax(sd64, T)
     static = {}
     for r in RTBS:
-        static[sd64[f"{r}.blocks.1.block.0.weight"].data_ptr()] = static_act_scale(
+        static[sd[f"{r}.blocks.1.block.0.weight"].data_ptr()] = static_act_scale(
             sd_np[f"{r}.blocks.0.block.2.weight"], sd_np[f"{r}.blocks.0.block.2.bias"], tb[r].numpy())
-    static[sd64["final_conv.1.weight"].data_ptr()] = static_act_scale(
+    static[sd["final_conv.1.weight"].data_ptr()] = static_act_scale(
         sd_np["final_conv.0.block.2.weight"], sd_np["final_conv.0.block.2.bias"], np.zeros(32))
     real = O.F
+
+    def pieces(v, s):
+        return _two_pieces(v, s, low_piece, operand_bits)
 
     def conv1d(x, w, *args, **kw):
         s = static.get(w.data_ptr())
         sx = _dyn_scale(x) if s is None else (s if static_scale is None else static_scale)
-        return real.conv1d(_two_pieces(x, sx, low_piece), _two_pieces(w, _col_scale(w, (1, 2)), low_piece), *args, **kw)
+        return real.conv1d(pieces(x, sx), pieces(w, _col_scale(w, (1, 2) if weight_scale == "column" else (0, 1, 2))), *args, **kw)
 
     def conv_transpose1d(x, w, *args, **kw):                     # [cin, cout, 4]: taps (3, 1) make the even outputs, (2, 0) the odd ones
         sw = torch.empty_like(w)
         for taps in ((1, 3), (0, 2)):
-            sw[:, :, taps] = _col_scale(w[:, :, taps], (0, 2)).expand(w.shape[0], -1, 2)
-        return real.conv_transpose1d(_two_pieces(x, _dyn_scale(x), low_piece), _two_pieces(w, sw, low_piece), *args, **kw)
+            sw[:, :, taps] = _col_scale(w[:, :, taps], (0, 2) if weight_scale == "column" else (0, 1, 2)).expand(w.shape[0], w.shape[1], 2)
+        return real.conv_transpose1d(pieces(x, _dyn_scale(x)), pieces(w, sw), *args, **kw)
 
     swapped = dict(conv1d=conv1d, conv_transpose1d=conv_transpose1d)
     if mish != "torch":
         assert mish in ("kernel", "kernel_noclamp"), mish
         swapped["mish"] = lambda y: kernel_mish(y, clamp=mish == "kernel") if y.ndim == 3 else real.mish(y)   # (the time MLP: mish_exact)
     with _oracle_functional(**swapped):
-        return O.unet_forward(sd64, x.double(), torch.full((x.shape[0],), t, dtype=torch.long))
+        return O.unet_forward(sd, x.to(dtype), torch.full((x.shape[0],), t, dtype=torch.long))
 
 
 def traced_forward(sd_np, x, t):

@@ -110,7 +110,7 @@ def test_every_time_step_on_the_time_bias_set():
 
 
 # ---- 5. beyond the range
-EMULATION_MARGIN = 2.0
+EMULATION_MARGIN = E.EMULATION_MARGIN
 
 
 @pytest.mark.parametrize("wset", E.OUT_OF_RANGE)
