@@ -809,6 +809,30 @@ int mmd_route_seeds(const float* grid_dev, int nx, int ny, const float lo[2], co
                     const float* start_points_dev /* [n][2] */, const float* goal_points_dev /* [n][2] */, int smooth_iters, float two_dt,
                     float* seeds_dev /* [n][max_tiles * 64][4] */, float* clear_min_dev /* [n] */, void* stream);
 
+/* World fleets: the next sub-goal and the window of n_queries robots, each read off the converged field of its goal, one lane per query
+ * (mmd_amd/world_fleet.py::window_goal is the same definition on the host, where its two facts -- the walk's box lies inside the
+ * window, and a call covers at least min(d, max_steps, reach) steps -- are argued).  Query q starts at cell c0 = starts_dev[q] in field
+ * field_dev[q], whose goal cell is g = goals_dev[field_dev[q]], all device data.  From cell c with d = dist[c], while d > 0, fewer than
+ * max_steps steps are taken, and the chosen next cell n has max(|n.x - c0.x|, |n.y - c0.y|) <= reach: the candidates are the neighbours
+ * that lie inside the grid and hold exactly d - 1, the x-candidate the first of +x, -x and the y-candidate the first of +y, -y; n is the
+ * x-candidate if |g.x - c.x| >= |g.y - c.y|, else the y-candidate, and the other axis's candidate where that axis has none (open ground
+ * gives a diagonal staircase, not an L).  The walk ends before a step that would leave the box.
+ *   cells_dev[q]   = the last cell reached (c0 itself when d == 0 at the start)
+ *   origins_dev[q] = min(max(c0 - window / 2, 0), n - window) per axis: the origin cell of the robot's window of `window` cells per side
+ *   summary_dev[q] = (steps, remaining, status, arrived), remaining = dist[c0] - steps, arrived = 1 iff status is 0 and remaining is 0:
+ *     0  ok
+ *     1  c0 holds MMD_GRID_DIST_UNREACHED: steps = remaining = -1, cell and origin (0, 0)
+ *     2  stuck: no neighbour holds d - 1 (the field was not converged); the walk stops there, the outputs are what it covered
+ *     4  c0 lies outside the grid, or the field index outside [0, n_fields): steps = remaining = -1, cell and origin (0, 0)
+ * Every word of the three outputs is written for every query.  The loop runs at most min(max_steps, dist[c0]) times whatever the field
+ * and the goals hold.  Error returns, before anything is launched: nx or ny below 1 or above MMD_OCCUPANCY_MAX_SIDE; a negative n_fields
+ * or n_queries; window outside 1 .. min(nx, ny); reach outside 1 .. window / 2 - 1; max_steps below 1; with n_queries > 0, a NULL dist
+ * or goals (with n_fields > 0), starts, field indices, cells, origins or summary.  n_queries == 0 returns 0 and launches nothing. */
+int mmd_grid_window_goals(const int32_t* dist_dev, int nx, int ny, int n_fields, const int32_t* starts_dev /* [n][2] */,
+                          const int32_t* field_dev /* [n] */, const int32_t* goals_dev /* [n_fields][2] */, int n_queries, int reach,
+                          int max_steps, int window, int32_t* cells_dev /* [n][2] */, int32_t* origins_dev /* [n][2] */,
+                          int32_t* summary_dev /* [n][4] */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -728,6 +728,15 @@ def world_map_window_origins(name, offsets):
     return r.astype(np.int32)
 
 
+def world_map_window_offsets(name, origins):
+    """float32 [n, 2]: the offsets of the windows at the origin cells `origins` (integers [n, 2], each a window inside the world), the
+    inverse of world_map_window_origins: origin * SDF_CELL_SIZE + world origin - LIMITS[0] per axis in float64, then float32
+    (snap_to_world_map's formula on whole cells).  world_map_window_origins accepts the result and returns the origins."""
+    org = checked_window_origins(name, origins, "world_map_window_offsets")
+    out = org.astype(np.float64) * np.float64(SDF_CELL_SIZE) + np.asarray(world_map_origin(name), np.float64) - np.asarray(LIMITS[0], np.float64)
+    return out.astype(np.float32)
+
+
 def snap_to_world_map(name, offsets):
     """float32 offsets of the shape given: per robot the nearest offsets whose window starts on a cell and lies inside the world."""
     q, limit = _window_cells(name, offsets, "snap_to_world_map")

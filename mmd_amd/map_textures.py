@@ -86,6 +86,16 @@ def device_sdf_textures(maps, device):
     return _TEXTURES[key]
 
 
+def release_sdf_textures(maps, device):
+    """Forget the resident textures of exactly the map set `maps` on `device` (the names in device_sdf_textures' order) and its window
+    cuts: the next device_sdf_textures of the set builds it again, and update_* no longer reaches it.  An object built on the set keeps
+    its tensor.  For a caller that builds map sets it will not use again (world_fleet.WorldFleet: one set of windows per epoch, 2.56 MB a
+    window).  -> whether the set was resident."""
+    key = (tuple(maps), str(environments.resolved_device(device)))
+    _WINDOW_CUTS.pop(key, None)
+    return _TEXTURES.pop(key, None) is not None
+
+
 def rebuild_resident_textures(name, device_occupancy=None):
     """environments.update_*: whatever resident texture holds the registered name is rebuilt in place -- same storage, same pointers -- on
     the current stream of its device.  A tile map: every slice of the name, by the builder of its kind; device_occupancy is the new
