@@ -833,6 +833,49 @@ int mmd_grid_window_goals(const int32_t* dist_dev, int nx, int ny, int n_fields,
                           int max_steps, int window, int32_t* cells_dev /* [n][2] */, int32_t* origins_dev /* [n][2] */,
                           int32_t* summary_dev /* [n][4] */, void* stream);
 
+/* mmd_grid_window_goals with the support cells of the walk's cell path (mmd_amd/world_fleet.py::window_goal_samples is the same
+ * definition on the host).  The walk, cells_dev, origins_dev and summary_dev are mmd_grid_window_goals', word for word.  The cell path
+ * is c_0 = c0 .. c_steps = the last cell reached, and
+ *   samples_dev[q][j] = c[(j * steps + 31) / 63], j = 0 .. 63 (integer division; mmd_grid_descend_samples' spacing for a visit of
+ *                       steps + 1 cells): monotone in j, j = 0 the start and j = 63 the sub-goal cell; with steps = 0 all 64 are c0.
+ * A query whose status is not 0 (a stuck walk included) gets 64 zero rows.  Every word of the four outputs is written for every query.
+ * One lane per query walks the field twice, with no buffer proportional to the path: the first walk fixes `steps`, the second emits the
+ * samples as it passes them.  Each walk's loop runs at most min(max_steps, dist[c0]) times whatever the field and the goals hold; a step
+ * lands on a cell that holds one less than the one before, so steps < nx * ny <= 2^22 and 63 * steps stays inside an int32.
+ * Error returns, before anything is launched: those of mmd_grid_window_goals, and a NULL samples with n_queries > 0.  n_queries == 0
+ * returns 0 and launches nothing. */
+int mmd_grid_window_goal_samples(const int32_t* dist_dev, int nx, int ny, int n_fields, const int32_t* starts_dev /* [n][2] */,
+                                 const int32_t* field_dev /* [n] */, const int32_t* goals_dev /* [n_fields][2] */, int n_queries, int reach,
+                                 int max_steps, int window, int32_t* cells_dev /* [n][2] */, int32_t* origins_dev /* [n][2] */,
+                                 int32_t* summary_dev /* [n][4] */, int32_t* samples_dev /* [n][64][2] */, void* stream);
+
+/* The seed trajectories of n_robots robots of a fleet, in trajs_final's format, from what mmd_grid_window_goal_samples wrote
+ * (mmd_amd/world_fleet.py::window_seed is the same definition on the host, bit for bit): mmd_route_seeds' seed of one visit whose tile
+ * is the robot's own window, the cells [origins_dev[r], origins_dev[r] + window) per axis.  Every operation is one fp32 rounding, with no
+ * fused multiply-add.  Robot r with status 0 (summary_dev[r][2]) has 64 points:
+ *   p[j]   = lo + ((float)cell + 0.5f) * pitch per axis, pitch = |hi - lo| / (float)n: the centre of samples_dev[r][j].
+ *            p[0] = start_points_dev[r] and p[63] = goal_points_dev[r], which stay fixed.
+ *   smooth_iters Jacobi iterations, every interior j from the values of the iteration before: c = 0.5f * (p[j - 1] + p[j + 1]) per axis;
+ *            (ix, iy) = the texel of c (mmd_sdf_grid_lookup's sequence); p'[j] = c iff grid[ix][iy][0] > clearance (strict: a NaN
+ *            rejects) and (ix, iy) is a cell of the robot's window; else p'[j] = p[j].
+ *   v[j]   = (p[j + 1] - p[j - 1]) / two_dt per axis (correctly rounded), 0 at j = 0 and j = 63.
+ *   seeds_dev[r][j] = (p.x, p.y, v.x, v.y)
+ *   clear_min_dev[r] = the least grid[texel of p[j]][0] over the final points, in mmd_route_seeds' order of the values' bits.
+ * The window test is a guard for hand-built samples: the samples of a fleet's walk lie in the box of radius `reach` round the start,
+ * the box lies in the window, and the window is convex, so a midpoint of two points in it never leaves it.  Samples and origins are
+ * device data and may hold any words: a sample is only converted to a float, the texel index is clamped to the grid whatever a point
+ * holds, and the window test is taken in 64 bits.  A robot whose status is not 0 gets 64 zero rows and clear_min 0, and reads no
+ * texel.  One wave per robot, a point per lane in registers, the neighbours read across lanes: no LDS and no barrier.
+ * Error returns, before anything is launched: nx or ny below 1 or above MMD_OCCUPANCY_MAX_SIDE; NULL or non-finite limits or a zero
+ * extent; a clearance that is not finite; two_dt not finite or <= 0; smooth_iters or n_robots negative; window below 1; with
+ * n_robots > 0, a NULL grid, samples, origins, summary, start or goal points, seeds or clear_min.  n_robots == 0 returns 0 and launches
+ * nothing. */
+int mmd_window_seeds(const float* grid_dev, int nx, int ny, const float lo[2], const float hi[2], float clearance,
+                     const int32_t* samples_dev /* [n][64][2] */, const int32_t* origins_dev /* [n][2] */,
+                     const int32_t* summary_dev /* [n][4] */, int n_robots, int window, const float* start_points_dev /* [n][2] */,
+                     const float* goal_points_dev /* [n][2] */, int smooth_iters, float two_dt, float* seeds_dev /* [n][64][4] */,
+                     float* clear_min_dev /* [n] */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

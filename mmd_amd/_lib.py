@@ -194,6 +194,11 @@ _SIGNATURES = {
                                   C.c_void_p, C.c_void_p, C.c_void_p]),
     "mmd_grid_window_goals": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                         C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mmd_grid_window_goal_samples": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                               C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mmd_window_seeds": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_void_p,
+                                   C.c_void_p]),
 }
 ROUTE_SEED_POINTS, ROUTE_SEED_MAX_TILES = 64, 16            # MMD_ROUTE_SEED_POINTS, MMD_ROUTE_SEED_MAX_TILES
 GRID_DIST_BLOCK, GRID_DIST_UNREACHED = 64, 0x7fffffff       # MMD_GRID_DIST_BLOCK, MMD_GRID_DIST_UNREACHED

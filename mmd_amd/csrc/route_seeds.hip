@@ -10,6 +10,7 @@
 #include "../../include/mmd_amd.h"
 #include "common.h"
 #include "grid_route_dev.h"
+#include "seed_dev.h"
 #include "wave_dev.h"
 // every float operation below is one rounding: no fused multiply-add
 #pragma clang fp contract(off)
@@ -122,16 +123,6 @@ __global__ __launch_bounds__(DS_THREADS) void grid_descend_samples_kernel(const 
 }
 
 // ---- the seed: one workgroup per route ----
-// The texel of a point: sdf_grid.hip's sdf_grid_lookup_kernel, operation for operation (fmaxf drops a NaN: index 0)
-struct SeedGrid { int nx, ny; float lo_x, lo_y, dim_x, dim_y, pitch_x, pitch_y; };
-__device__ __forceinline__ int2 seed_texel(const SeedGrid& g, float2 p) {
-  return make_int2((int)fminf(fmaxf(floorf((p.x - g.lo_x) / g.dim_x * (float)g.nx), 0.f), (float)(g.nx - 1)),
-                   (int)fminf(fmaxf(floorf((p.y - g.lo_y) / g.dim_y * (float)g.ny), 0.f), (float)(g.ny - 1)));
-}
-
-// a float's bits as an int32 that orders like the float (-0 below +0, a NaN beyond the infinity of its sign); its own inverse
-__device__ __forceinline__ int order_key(int bits) { return bits ^ ((bits >> 31) & 0x7fffffff); }
-
 // Workgroup = route, 256 threads x 4 points (point i = t + 256 r: a wave's 64 points are one tile visit, so a wave behind the route's K
 // visits only meets the barriers).  The chain lives in LDS as two float2 buffers; iteration `it` reads buffer it & 1 and writes the other,
 // every interior point from its two neighbours of the iteration before (Jacobi: no order within an iteration matters, so the result does

@@ -7,17 +7,12 @@
 
 #include "../../include/mmd_amd.h"
 #include "common.h"
+#include "window_walk_dev.h"
 
 namespace mmd {
 
-constexpr int WG_THREADS = 64;
-constexpr int WG_UNREACHED = MMD_GRID_DIST_UNREACHED;
-constexpr int WG_OK = 0, WG_UNREACHED_START = 1, WG_STUCK = 2, WG_OUTSIDE = 4;       // the status codes of mmd_grid_descend
-
-// One lane per query.  From the start cell c0 with d0 = dist[c0], at most min(max_steps, d0) times: the neighbours that lie inside the
-// grid and hold exactly d - 1, the first of +x, -x and the first of +y, -y; the axis on which the field's goal is farther from the
-// current cell goes first (x on a tie), the other axis serves where that one has no candidate; the walk ends before a step that would
-// leave the box of Chebyshev radius `reach` round c0.  d falls by one per step, so the loop counter IS d0 - d.  The lanes of a wave walk
+// One lane per query.  From the start cell c0 with d0 = dist[c0], at most min(max_steps, d0) times: one step of the rule (window_walk_dev.h:
+// window_step); the walk ends before a step that would leave the box of Chebyshev radius `reach` round c0.  The lanes of a wave walk
 // unrelated cells: four scattered 4-byte loads per step and lane, no LDS, no atomics, nothing that waits on another workgroup.
 __global__ __launch_bounds__(WG_THREADS) void grid_window_goals_kernel(const int* __restrict__ dist_all, int nx, int ny, int n_fields,
                                                                        const int2* __restrict__ starts, const int* __restrict__ field,
@@ -37,27 +32,11 @@ __global__ __launch_bounds__(WG_THREADS) void grid_window_goals_kernel(const int
     summary[q] = make_int4(-1, -1, inside ? WG_UNREACHED_START : WG_OUTSIDE, 0);
     return;
   }
-  const int2 g = goals[f];                                 // device data: any two words (the differences below are taken in 64 bits)
-  int ix = s.x, iy = s.y, steps = 0, status = WG_OK;
-  const int bound = min(max_steps, d0);                    // d0 <= 0: no step
-  for (int k = 0; k < bound; ++k) {
-    const int want = d0 - k - 1;                           // d - 1, d = d0 - k >= 1
-    const bool xp = ix + 1 < nx && dist[(size_t)(ix + 1) * ny + iy] == want;
-    const bool xm = ix > 0 && dist[(size_t)(ix - 1) * ny + iy] == want;
-    const bool yp = iy + 1 < ny && dist[(size_t)ix * ny + iy + 1] == want;
-    const bool ym = iy > 0 && dist[(size_t)ix * ny + iy - 1] == want;
-    const int sx = xp ? 1 : xm ? -1 : 0, sy = yp ? 1 : ym ? -1 : 0;      // the first candidate of each axis, 0: none
-    if (sx == 0 && sy == 0) { status = WG_STUCK; break; }
-    const long long ax = llabs((long long)g.x - ix), ay = llabs((long long)g.y - iy);
-    const bool along_x = sx != 0 && (ax >= ay || sy == 0);
-    const int jx = along_x ? ix + sx : ix, jy = along_x ? iy : iy + sy;
-    if (max(abs(jx - s.x), abs(jy - s.y)) > reach) break;
-    ix = jx; iy = jy;
-    ++steps;
-  }
+  int ix, iy, steps;
+  const int status = window_walk(dist, nx, ny, s, goals[f], reach, max_steps, d0, ix, iy, steps);
   const int remaining = d0 - steps;
   cells[q] = make_int2(ix, iy);
-  origins[q] = make_int2(min(max(s.x - window / 2, 0), nx - window), min(max(s.y - window / 2, 0), ny - window));
+  origins[q] = window_origin(s, nx, ny, window);
   summary[q] = make_int4(steps, remaining, status, status == WG_OK && remaining == 0);
 }
 

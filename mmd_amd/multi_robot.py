@@ -296,6 +296,11 @@ class MultiRobotSampler:
             self.last_n_free = self.last_n_free.clone().index_copy_(0, local_ids, n_free.to(self.last_n_free.dtype))
         return trajs, best, local_ids
 
+    def _run_device(self):
+        """the device the samples live on: self.device with its index resolved ("cuda" is the current device)"""
+        d = self.device
+        return torch.device(d.type, torch.cuda.current_device()) if d.type == "cuda" and d.index is None else d
+
     def plan(self, paths_local=None, max_rounds=8, seed=0, list_cap=0):
         """Rounds of plan_round until the gathered best paths are free of robot-robot conflicts, at most max_rounds of them.  Round k
         (seed + k): all-gather the paths, report their conflicts on the device (multi_agent.path_conflicts; the count crosses in one
@@ -310,9 +315,32 @@ class MultiRobotSampler:
     def plan_rounds(self, paths_local=None, max_rounds=8, seed=0, list_cap=0, repair=False, hard_slots=32,
                     weight_grad_cost_constraints=2e-1, t_pad=2, local_rounds=False, n_noising_steps=3, n_denoising_steps=3):
         """plan()'s loop -- with repair and local_rounds off, exactly plan() -- and two independent ways to act on the report (below);
-        plan_rounds_subset is this call with a third, the choice of the robots a round re-plans.  -> PlanResult."""
+        plan_rounds_subset is this call with a third, the choice of the robots a round re-plans, and plan_rounds_seeded any of them with
+        round 0 started from given trajectories.  -> PlanResult."""
         return MultiRobotSampler.plan_rounds_subset(self, paths_local, max_rounds, seed, list_cap, repair, hard_slots,
                                                     weight_grad_cost_constraints, t_pad, local_rounds, n_noising_steps, n_denoising_steps)
+
+    def plan_rounds_seeded(self, init_trajs, paths_local=None, max_rounds=8, seed=0, list_cap=0, repair=False, hard_slots=32,
+                           weight_grad_cost_constraints=2e-1, t_pad=2, local_rounds=False, n_noising_steps=3, n_denoising_steps=3,
+                           replan="all", independent_iters=8):
+        """plan_rounds_subset (this sampler's: a subclass's refusals and results hold) whose round 0 starts from given trajectories.
+        init_trajs: normalised trajectories [n_local * B, H, D] (float32, contiguous, on the sampler's device): round 0 samples with
+        sample_local(init_trajs, n_noising_steps, n_denoising_steps, seed) instead of sample(seed) from noise.  Later rounds are what
+        they are without it: from noise, or with local_rounds=True from the round before.  paths_local is still what round 0's tables
+        are built on (a caller with seed trajectories passes their positions).  init_trajs=None is plan_rounds_subset, bit for bit; a
+        wrong type, shape, dtype, device or layout raises ValueError before any launch.  -> PlanResult."""
+        if init_trajs is not None:
+            want = (self.n_local * self.n_samples, H, D)
+            if not (isinstance(init_trajs, torch.Tensor) and tuple(init_trajs.shape) == want and init_trajs.dtype == torch.float32
+                    and init_trajs.device == self._run_device() and init_trajs.is_contiguous()):
+                got = (tuple(init_trajs.shape), init_trajs.dtype, init_trajs.device) if isinstance(init_trajs, torch.Tensor) else type(init_trajs)
+                raise ValueError(f"plan_rounds_seeded: init_trajs must be a contiguous float32 tensor {want} on {self._run_device()}, got {got}")
+        self._init_trajs = init_trajs              # read by the loop's round 0 only, and only during this call
+        try:
+            return self.plan_rounds_subset(paths_local, max_rounds, seed, list_cap, repair, hard_slots, weight_grad_cost_constraints, t_pad,
+                                           local_rounds, n_noising_steps, n_denoising_steps, replan, independent_iters)
+        finally:
+            self._init_trajs = None
 
     def plan_rounds_subset(self, paths_local=None, max_rounds=8, seed=0, list_cap=0, repair=False, hard_slots=32,
                            weight_grad_cost_constraints=2e-1, t_pad=2, local_rounds=False, n_noising_steps=3, n_denoising_steps=3,
@@ -372,7 +400,7 @@ class MultiRobotSampler:
                 paths_local, n_sampled = self._subset_round(paths_all, table, robots, replan, independent_iters, seed + k, paths_local, trajs,
                                                             local_rounds, n_noising_steps, n_denoising_steps)
             else:
-                prev = trajs if local_rounds and k > 0 else None
+                prev = getattr(self, "_init_trajs", None) if k == 0 else trajs if local_rounds else None      # (plan_rounds_seeded's)
                 trajs, paths_local = self._full_round(paths_all, table, rc, t_pad, seed + k, prev, n_noising_steps, n_denoising_steps)
                 n_sampled = self.n_robots
                 if subset:

@@ -150,7 +150,8 @@ class WorldRobotSampler(MultiRobotSampler):
                            weight_grad_cost_constraints=2e-1, t_pad=2, local_rounds=False, n_noising_steps=3, n_denoising_steps=3,
                            replan="all", independent_iters=8):
         """MultiRobotSampler.plan_rounds_subset on global paths.  PlanResult.dropped_constraints is `last_dropped` of the last round run
-        (a device tensor, or None when no table was built)."""
+        (a device tensor, or None when no table was built).  plan_rounds_seeded's init_trajs are normalised trajectories in the robots'
+        own frames (trajs_from_global makes them from global seeds)."""
         if repair:
             raise ValueError("WorldRobotSampler: repair=True is not supported: the round table is built without per-robot frames")
         if replan != "all":
@@ -160,6 +161,21 @@ class WorldRobotSampler(MultiRobotSampler):
                                                    replan, independent_iters)
         res.dropped_constraints = self.last_dropped
         return res
+
+    def trajs_from_global(self, seeds):
+        """init_trajs of plan_rounds_seeded from seed trajectories in the global frame: seeds float32 [n_local, 64, 4] (positions and velocities,
+        trajs_final's format; world_fleet.device_window_seeds') of this rank's robots -> normalised [n_local * n_samples, H, D] on the
+        sampler's device.  Per robot: its offset subtracted from x and y (one fp32 subtraction each), dataset.normalize_trajectories,
+        a clip to [-1, 1] (a seed's velocity may exceed the normaliser's limits; positions inside the window are not moved), and the
+        row repeated n_samples times, robot-major.  Torch operations on the device; no host copy."""
+        seeds = torch.as_tensor(seeds)
+        if tuple(seeds.shape) != (self.n_local, H, D) or seeds.dtype != torch.float32:
+            raise ValueError(f"WorldRobotSampler.trajs_from_global: seeds must be float32 [{self.n_local}, {H}, {D}], got {seeds.dtype} "
+                             f"{tuple(seeds.shape)}")
+        local = seeds.to(self.device).clone()
+        local[..., :2] -= self.offsets[self.robot0:self.robot0 + self.n_local, None, :]
+        normed = torch.clip(self.dataset.normalize_trajectories(local), -1.0, 1.0)
+        return normed[:, None].expand(self.n_local, self.n_samples, H, D).reshape(-1, H, D).contiguous()
 
     def replan_round(self, *args, **kwargs):
         raise ValueError("WorldRobotSampler: replan_round is not supported: the per-robot frames do not follow the permutation of a subset round")

@@ -34,6 +34,11 @@ PROGRESS.  On a converged field (status OK) with d0 > 0, steps >= min(d0, max_st
 after k steps the walk is within Chebyshev distance k of c0, and a step can leave the box only if k + 1 > reach.  The walk therefore
 ends by d == 0 (steps = d0), by steps == max_steps, or with steps >= reach.  The next call starts from `cell`, where the same field
 holds `remaining`, so calls repeated from the cell reached arrive after at most ceil(d0 / min(max_steps, reach)) calls (epoch_bound).
+
+An epoch may start from its walk instead of from noise (WorldFleet(seed_epochs=True)).  window_goal_samples keeps 64 support cells of the
+walk's cell path and window_seed turns them into a smoothed chain of points with velocities inside the robot's window; these two numpy
+functions are definitions as well, and mmd_grid_window_goal_samples and mmd_window_seeds (csrc/window_seeds.hip) compute the same
+integers and the same float32 bits.
 """
 import ctypes as C
 from typing import NamedTuple
@@ -43,8 +48,8 @@ import torch
 
 from . import _lib, environments, map_textures
 from .world import OBSTACLE_MARGIN, WorldRobotSampler
-from .world_routes import (ROUTE_OK, ROUTE_OUTSIDE, ROUTE_STUCK, ROUTE_UNREACHED, UNREACHED, _int32_dev, _points, cell_centres,
-                           device_distance_field, world_cells)
+from .world_routes import (ROUTE_OK, ROUTE_OUTSIDE, ROUTE_STUCK, ROUTE_UNREACHED, SEED_POINTS, UNREACHED, _int32_dev, _points, cell_centres,
+                           device_distance_field, sample_offsets, seed_trajectory, world_cells)
 
 _STATUS_NAMES = {ROUTE_OK: "ok", ROUTE_UNREACHED: "unreached", ROUTE_STUCK: "stuck", ROUTE_OUTSIDE: "outside"}
 
@@ -56,6 +61,28 @@ def _checked_walk_args(what, shape, reach, max_steps, window):
         raise ValueError(f"{what}: reach = {reach} (1 to window // 2 - 1), max_steps = {max_steps} (at least 1), window = {window} "
                          f"(at most min(nx, ny) = {min(shape)})")
     return reach, max_steps, window
+
+
+def _walk(dist, start, goal, d0, reach, max_steps):
+    """(the cell path [c_0 = start, .., c_steps], status) of window_goal's walk from a cell of the grid that holds d0 != UNREACHED"""
+    nx, ny = dist.shape
+    (x0, y0), (gx, gy) = start, goal
+    ix, iy, d, status = x0, y0, d0, ROUTE_OK
+    path = [(ix, iy)]
+    while d > 0 and len(path) - 1 < max_steps:
+        holds = lambda jx, jy: 0 <= jx < nx and 0 <= jy < ny and int(dist[jx, jy]) == d - 1                          # noqa: E731
+        along_x = [(ix + s, iy) for s in (1, -1) if holds(ix + s, iy)]
+        along_y = [(ix, iy + s) for s in (1, -1) if holds(ix, iy + s)]
+        if not along_x and not along_y:
+            status = ROUTE_STUCK
+            break
+        first, second = (along_x, along_y) if abs(gx - ix) >= abs(gy - iy) else (along_y, along_x)
+        jx, jy = (first or second)[0]
+        if max(abs(jx - x0), abs(jy - y0)) > reach:
+            break
+        ix, iy, d = jx, jy, d - 1
+        path.append((ix, iy))
+    return path, status
 
 
 def window_goal(dist, start, goal, reach, max_steps, window=400):
@@ -74,20 +101,9 @@ def window_goal(dist, start, goal, reach, max_steps, window=400):
     if d0 == UNREACHED:
         return (0, 0), (0, 0), -1, -1, ROUTE_UNREACHED
     origin = (min(max(x0 - window // 2, 0), nx - window), min(max(y0 - window // 2, 0), ny - window))
-    ix, iy, d, steps, status = x0, y0, d0, 0, ROUTE_OK
-    while d > 0 and steps < max_steps:
-        holds = lambda jx, jy: 0 <= jx < nx and 0 <= jy < ny and int(dist[jx, jy]) == d - 1                          # noqa: E731
-        along_x = [(ix + s, iy) for s in (1, -1) if holds(ix + s, iy)]
-        along_y = [(ix, iy + s) for s in (1, -1) if holds(ix, iy + s)]
-        if not along_x and not along_y:
-            status = ROUTE_STUCK
-            break
-        first, second = (along_x, along_y) if abs(gx - ix) >= abs(gy - iy) else (along_y, along_x)
-        jx, jy = (first or second)[0]
-        if max(abs(jx - x0), abs(jy - y0)) > reach:
-            break
-        ix, iy, d, steps = jx, jy, d - 1, steps + 1
-    return (ix, iy), origin, steps, d0 - steps, status
+    path, status = _walk(dist, (x0, y0), (gx, gy), d0, reach, max_steps)
+    steps = len(path) - 1
+    return path[-1], origin, steps, d0 - steps, status
 
 
 def window_goals(dist, starts, fields, goals, reach, max_steps, window=400):
@@ -110,6 +126,49 @@ def window_goals(dist, starts, fields, goals, reach, max_steps, window=400):
     return cells, origins, summary
 
 
+def window_goal_samples(dist, start, goal, reach, max_steps, window=400):
+    """(cell, origin, steps, remaining, status, samples int32 [64, 2]): window_goal with the support cells of the walk's cell path.  The
+    walk is window_goal's, rule for rule, and the first five results are window_goal's.  The cell path is c_0 = start .. c_steps = cell,
+    and samples[j] = c[sample_offsets(steps + 1)[j]] = c[(j * steps + 31) // 63]: the route seeds' spacing (world_routes.sample_offsets),
+    samples[0] the start and samples[63] the sub-goal cell, every cell of the path while steps <= 63.  With a status other than ROUTE_OK
+    (a stuck walk included) there are no samples: all zero, as descend_samples gives none."""
+    cell, origin, steps, remaining, status = window_goal(dist, start, goal, reach, max_steps, window)
+    samples = np.zeros((SEED_POINTS, 2), np.int32)
+    if status == ROUTE_OK:
+        x0, y0 = int(start[0]), int(start[1])
+        path, _ = _walk(np.asarray(dist), (x0, y0), (int(goal[0]), int(goal[1])), int(dist[x0, y0]), int(reach), int(max_steps))
+        samples[:] = np.asarray(path, np.int32)[sample_offsets(steps + 1)]
+    return cell, origin, steps, remaining, status, samples
+
+
+def window_goals_samples(dist, starts, fields, goals, reach, max_steps, window=400):
+    """(cells, origins, summary, samples int32 [n, 64, 2]): window_goal_samples for every query; the first three results are window_goals'
+    word for word."""
+    dist = np.asarray(dist)
+    starts, goals = np.asarray(starts, np.int64).reshape(-1, 2), np.asarray(goals, np.int64).reshape(-1, 2)
+    fields = np.asarray(fields, np.int64).reshape(-1)
+    cells, origins, summary = window_goals(dist, starts, fields, goals, reach, max_steps, window)
+    samples = np.zeros((len(starts), SEED_POINTS, 2), np.int32)
+    for q in np.flatnonzero(summary[:, 2] == ROUTE_OK):
+        f = int(fields[q])
+        samples[q] = window_goal_samples(dist[f], starts[q], goals[f], reach, max_steps, window)[5]
+    return cells, origins, summary, samples
+
+
+def window_seed(tex, lo, hi, samples, origin, window, start_point, goal_point, clearance=OBSTACLE_MARGIN, smooth_iters=64, dt=5.0 / 64):
+    """(seed float32 [64, 4], clear_min float32): the seed trajectory of one robot's epoch, in trajs_final's format and in the global frame,
+    from window_goal_samples' samples [64, 2] on the texture tex [nx, ny, 4] over lo .. hi.  By definition the route seed
+    (world_routes.seed_trajectory) of one visit whose "tile" is the robot's window, the cells [origin, origin + window) per axis: the
+    cells' centres with the caller's exact start and goal points at the ends, smooth_iters Jacobi iterations that move a support point
+    to the midpoint of its neighbours iff the midpoint's texel exceeds the clearance and lies in the window, central-difference
+    velocities over 2 dt, and the least texel value over the final points.
+    The in-window test is a guard.  For the samples of a fleet's walk it never rejects: every sample lies in the box of radius `reach`
+    round the start, the box lies in the window (CONTAINMENT), the ends lie in their cells, and the window's points are a convex set, so
+    a midpoint of two points of the window is one.  It matters only for hand-built samples, which it keeps where they are."""
+    return seed_trajectory(tex, lo, hi, np.asarray(samples, np.int32).reshape(1, SEED_POINTS, 2), [[0, 0]], window, origin, start_point,
+                           goal_point, clearance, smooth_iters, dt)
+
+
 def epoch_bound(d0, reach, max_steps):
     """The calls of window_goal, each from the cell the one before reached, that bring a robot d0 steps from its goal onto it, at most:
     ceil(d0 / min(max_steps, reach)) (PROGRESS, above)"""
@@ -117,21 +176,27 @@ def epoch_bound(d0, reach, max_steps):
 
 
 # ---- the same on the device ----------------------------------------------------------------------------------------------------------------
-def _window_goals_words(dist_dev, starts, fields, goals, reach, max_steps, window):
-    """device_window_goals' launch -> one int32 tensor [8 n] on the device: cells [n, 2], then origins [n, 2], then summary [n, 4]"""
+def _window_goals_words(dist_dev, starts, fields, goals, reach, max_steps, window, with_samples=False, what="device_window_goals"):
+    """device_window_goals' launch -> one int32 tensor [8 n] on the device: cells [n, 2], then origins [n, 2], then summary [n, 4].
+    with_samples: device_window_goal_samples' launch (mmd_grid_window_goal_samples) -> (that tensor, samples int32 [n, 64, 2])"""
     if dist_dev.dim() != 3 or dist_dev.dtype != torch.int32 or not dist_dev.is_cuda or not dist_dev.is_contiguous():
-        raise ValueError("device_window_goals: dist must be a contiguous int32 CUDA(HIP) tensor [n_fields, nx, ny]")
-    reach, max_steps, window = _checked_walk_args("device_window_goals", tuple(dist_dev.shape[1:]), reach, max_steps, window)
-    starts_dev = _int32_dev(starts, (-1, 2), dist_dev.device, "device_window_goals: starts")
+        raise ValueError(f"{what}: dist must be a contiguous int32 CUDA(HIP) tensor [n_fields, nx, ny]")
+    reach, max_steps, window = _checked_walk_args(what, tuple(dist_dev.shape[1:]), reach, max_steps, window)
+    starts_dev = _int32_dev(starts, (-1, 2), dist_dev.device, f"{what}: starts")
     n = starts_dev.shape[0]
-    fields_dev = _int32_dev(fields, (n,), dist_dev.device, "device_window_goals: fields")
-    goals_dev = _int32_dev(goals, (int(dist_dev.shape[0]), 2), dist_dev.device, "device_window_goals: goals")
+    fields_dev = _int32_dev(fields, (n,), dist_dev.device, f"{what}: fields")
+    goals_dev = _int32_dev(goals, (int(dist_dev.shape[0]), 2), dist_dev.device, f"{what}: goals")
     words = torch.empty(8 * n, dtype=torch.int32, device=dist_dev.device)        # (the summary rows start 16 n bytes in: aligned as int4)
     at = lambda k: C.c_void_p(words.data_ptr() + 4 * k)                          # noqa: E731
-    _lib.launch("mmd_grid_window_goals", dist_dev, C.c_void_p(dist_dev.data_ptr()), int(dist_dev.shape[1]), int(dist_dev.shape[2]),
-                int(dist_dev.shape[0]), C.c_void_p(starts_dev.data_ptr()), C.c_void_p(fields_dev.data_ptr()), C.c_void_p(goals_dev.data_ptr()),
-                n, reach, max_steps, window, at(0), at(2 * n), at(4 * n))
-    return words
+    args = (C.c_void_p(dist_dev.data_ptr()), int(dist_dev.shape[1]), int(dist_dev.shape[2]), int(dist_dev.shape[0]),
+            C.c_void_p(starts_dev.data_ptr()), C.c_void_p(fields_dev.data_ptr()), C.c_void_p(goals_dev.data_ptr()), n, reach, max_steps, window,
+            at(0), at(2 * n), at(4 * n))
+    if not with_samples:
+        _lib.launch("mmd_grid_window_goals", dist_dev, *args)
+        return words
+    samples = torch.empty(n, SEED_POINTS, 2, dtype=torch.int32, device=dist_dev.device)
+    _lib.launch("mmd_grid_window_goal_samples", dist_dev, *args, C.c_void_p(samples.data_ptr()))
+    return words, samples
 
 
 def _split_words(words):
@@ -146,6 +211,44 @@ def device_window_goals(dist_dev, starts, fields, goals, reach, max_steps, windo
     return _split_words(_window_goals_words(dist_dev, starts, fields, goals, reach, max_steps, window))
 
 
+def device_window_goal_samples(dist_dev, starts, fields, goals, reach, max_steps, window=400):
+    """(cells, origins, summary, samples int32 [n, 64, 2]) on dist_dev's device: window_goals_samples() for every query in one launch
+    (mmd_grid_window_goal_samples), word for word.  The first three are device_window_goals' (views of one tensor); dist_dev: any int32
+    fields, as there.  The samples of a query whose status is not ROUTE_OK are zero."""
+    words, samples = _window_goals_words(dist_dev, starts, fields, goals, reach, max_steps, window, True, "device_window_goal_samples")
+    return _split_words(words) + (samples,)
+
+
+def device_window_seeds(tex_dev, lo, hi, samples, origins, summary, window, start_points, goal_points, clearance=OBSTACLE_MARGIN,
+                        smooth_iters=64, dt=5.0 / 64):
+    """(seeds float32 [n, 64, 4], clear_min float32 [n]) on tex_dev's device: window_seed() for every robot in one launch
+    (mmd_window_seeds), bit for bit, from device_window_goal_samples' samples [n, 64, 2], origins [n, 2] and summary [n, 4] (or any
+    contiguous int32 tensors of those shapes on the texture's device) on any texture [nx, ny, 4] over lo .. hi.  The seeds are global
+    points, in trajs_final's format; every row of a robot whose status is not ROUTE_OK is zero, and so is its clear_min."""
+    if tex_dev.dim() != 3 or tex_dev.shape[2] != 4:
+        raise ValueError(f"device_window_seeds: a texture [nx, ny, 4], got {tuple(tex_dev.shape)}")
+    tex_p = _lib.require_gpu(tex_dev, "texture")
+    dev = tex_dev.device
+    ok = lambda t, shape: (isinstance(t, torch.Tensor) and t.dtype == torch.int32 and t.device == dev and t.is_contiguous()      # noqa: E731
+                           and tuple(t.shape[1:]) == shape)
+    if not (ok(summary, (4,)) and summary.shape[0] >= 1 and ok(samples, (SEED_POINTS, 2)) and ok(origins, (2,))
+            and samples.shape[0] == origins.shape[0] == summary.shape[0]):
+        raise ValueError("device_window_seeds: samples [n, 64, 2], origins [n, 2] and summary [n, 4], contiguous int32 on the texture's "
+                         "device, as device_window_goal_samples returns them")
+    n = int(summary.shape[0])
+    two_dt = float(np.float32(2.0 * float(dt)))
+    if int(smooth_iters) < 0 or not (np.isfinite(two_dt) and two_dt > 0) or int(window) < 1:
+        raise ValueError(f"device_window_seeds: smooth_iters = {smooth_iters} (>= 0), dt = {dt} (finite, > 0), window = {window} (>= 1)")
+    pts = [torch.as_tensor(p, dtype=torch.float32).reshape(n, 2).contiguous().to(dev) for p in (start_points, goal_points)]
+    seeds = torch.empty(n, SEED_POINTS, 4, dtype=torch.float32, device=dev)
+    clear_min = torch.empty(n, dtype=torch.float32, device=dev)
+    _lib.launch("mmd_window_seeds", tex_dev, tex_p, int(tex_dev.shape[0]), int(tex_dev.shape[1]), (C.c_float * 2)(*map(float, lo)),
+                (C.c_float * 2)(*map(float, hi)), float(clearance), C.c_void_p(samples.data_ptr()), C.c_void_p(origins.data_ptr()),
+                C.c_void_p(summary.data_ptr()), n, int(window), C.c_void_p(pts[0].data_ptr()), C.c_void_p(pts[1].data_ptr()),
+                int(smooth_iters), two_dt, C.c_void_p(seeds.data_ptr()), C.c_void_p(clear_min.data_ptr()))
+    return seeds, clear_min
+
+
 # ---- the fleet -----------------------------------------------------------------------------------------------------------------------------
 class EpochTargets(NamedTuple):
     """What one epoch plans towards (WorldFleet.epoch_targets), numpy on the host."""
@@ -154,13 +257,17 @@ class EpochTargets(NamedTuple):
     offsets: np.ndarray         # float32 [N, 2]: the windows' offsets (environments.world_map_window_offsets)
     points: np.ndarray          # float32 [N, 2]: the sub-goal points, global: the cell's centre, or the robot's exact goal once `arrived`
     summary: np.ndarray         # int32 [N, 4]: (steps, remaining, status, arrived)
+    samples: torch.Tensor = None    # seed_epochs: int32 [N, 64, 2] on the device, the walks' support cells (never copied back); else None
+    words: torch.Tensor = None      # seed_epochs: int32 [8 N] on the device, (cells, origins, summary) as launched (_split_words); else None
 
 
 class FleetResult(NamedTuple):
     """What WorldFleet.run returns."""
     paths: torch.Tensor         # float32 [N, E * 64, 2] on the device, global: epoch e's paths are columns [64 e, 64 e + 64)
     arrived: np.ndarray         # bool [N]: the robot stands on its exact goal point
-    epochs: list                # per epoch {"conflict_counts", "summary", "offsets"}: the PlanResult's counts, the epoch's targets
+    # per epoch {"conflict_counts", "summary", "offsets"}: the PlanResult's counts, the epoch's targets; with seed_epochs also
+    # "clear_min", float32 [N]: the least texel value over each robot's seed points
+    epochs: list
 
 
 class WorldFleet:
@@ -173,14 +280,34 @@ class WorldFleet:
     reach, max_steps: window_goal's, in cells; reach <= 199 on the model's 400-cell window.  Further keyword arguments go to every
     epoch's WorldRobotSampler (n_samples, constraint_table, ...).  `positions` (float32 [N, 2], global) are the robots' current points.
 
-    Out of scope here: an arrived robot is sampled like any other, between two ends pinned to its goal point, not held still; an epoch
-    starts from noise, not from the cell path; every epoch builds a sampler of its own, the windows of one long-lived sampler are not
-    moved in place; the fleet is not sharded over ranks; repair= and replan=, which WorldRobotSampler refuses."""
+    seed_epochs=True: an epoch starts from its walk instead of from noise.  epoch_targets then runs mmd_grid_window_goal_samples in
+    place of mmd_grid_window_goals (the same three outputs, and the walks' 64 support cells, which stay on the device); step builds every
+    robot's seed trajectory in one mmd_window_seeds launch on the resident world texture -- from the robot's position to its sub-goal
+    point, smooth_iters iterations, at the fleet's clearance, inside the robot's window -- and calls the sampler's
+    plan_rounds_seeded(trajs_from_global(seeds), paths_local=the seeds' positions, local_rounds=True, n_noising_steps,
+    n_denoising_steps): round 0's constraint table is built on the seed paths, not on straight lines through walls, and every round of
+    the epoch is a local re-plan.  Such a round runs n_denoising_steps + n_diffusion_steps_without_noise UNet forwards (3 + 1 = 4 with
+    the defaults: run_local_inference's q_sample is one launch without a forward, then conditional_sample's loop) where a round from
+    noise runs T + 1 (26 at the released T = 25).  An arrived robot has steps = 0: all 64 samples are its goal cell, so its seed
+    runs from its goal point to its goal point inside that one cell (the cell's centre in between, drawn towards the goal point by the
+    smoothing) with velocities of at most half a cell over 2 dt; that is "held still" as far as a seed goes, and the robot is still
+    sampled between its two pinned ends.
+    With seed_epochs=False (the default) nothing of this runs: the code path is the one without the option.
 
-    def __init__(self, model, name, starts, goals, clearance=OBSTACLE_MARGIN, reach=180, max_steps=360, device="cuda",
-                 **world_robot_sampler_kwargs):
+    Out of scope here: an arrived robot is sampled like any other, between two ends pinned to its goal point, not held still; every
+    epoch builds a sampler of its own, the windows of one long-lived sampler are not moved in place; the fleet is not sharded over ranks;
+    repair= and replan=, which WorldRobotSampler refuses.  Whether a seeded epoch resolves conflicts as well as one from noise is not
+    known."""
+
+    def __init__(self, model, name, starts, goals, clearance=OBSTACLE_MARGIN, reach=180, max_steps=360, device="cuda", seed_epochs=False,
+                 smooth_iters=64, n_noising_steps=3, n_denoising_steps=3, **world_robot_sampler_kwargs):
         self.model, self.name, self.device = model, name, environments.resolved_device(device)
         self.clearance = float(clearance)
+        self.seed_epochs = bool(seed_epochs)
+        self.smooth_iters, self.n_noising_steps, self.n_denoising_steps = int(smooth_iters), int(n_noising_steps), int(n_denoising_steps)
+        if self.smooth_iters < 0 or self.n_noising_steps < 0 or self.n_denoising_steps < 1:
+            raise ValueError(f"WorldFleet: smooth_iters = {smooth_iters} (>= 0), n_noising_steps = {n_noising_steps} (>= 0), "
+                             f"n_denoising_steps = {n_denoising_steps} (>= 1)")
         self.sampler_kwargs = dict(world_robot_sampler_kwargs)
         for refused in ("rank", "world_size", "group", "env_id"):
             if refused in self.sampler_kwargs:
@@ -217,6 +344,7 @@ class WorldFleet:
         self.n_robots = n
         self.start_distances = d0.astype(np.int64)
         self.positions = s_pts.copy()
+        self.last_clear_min = None
 
     def _cells(self, points, what):
         """world_cells of the robots' points, with its refusal (a point that is not finite or lies outside the world) naming the robot"""
@@ -234,14 +362,18 @@ class WorldFleet:
         return max(1, max(epoch_bound(d, self.reach, self.max_steps) for d in self.start_distances.tolist()))
 
     def epoch_targets(self, positions):
-        """EpochTargets of the robots at the global points `positions` [N, 2]: one mmd_grid_window_goals launch and one device -> host
-        copy.  A robot's cell is world_cells' texel of its point; its sub-goal point is the centre of the sub-goal cell by cell_centres'
-        fp32 sequence, or, once the sub-goal cell is the goal's (`arrived`), the caller's exact goal point."""
+        """EpochTargets of the robots at the global points `positions` [N, 2]: one mmd_grid_window_goals launch (with seed_epochs: one
+        mmd_grid_window_goal_samples launch, the same words and the samples, which stay on the device) and one device -> host copy.  A
+        robot's cell is world_cells' texel of its point; its sub-goal point is the centre of the sub-goal cell by cell_centres' fp32
+        sequence, or, once the sub-goal cell is the goal's (`arrived`), the caller's exact goal point."""
         pts = _points(positions)
         if pts.shape[0] != self.n_robots:
             raise ValueError(f"WorldFleet.epoch_targets: {pts.shape[0]} positions for {self.n_robots} robots")
         c0 = self._cells(pts, "position")
-        words = _window_goals_words(self.dist, c0, self._fields_dev, self._goals_dev, self.reach, self.max_steps, self.window)
+        if self.seed_epochs:
+            words, samples = _window_goals_words(self.dist, c0, self._fields_dev, self._goals_dev, self.reach, self.max_steps, self.window, True)
+        else:
+            words, samples = _window_goals_words(self.dist, c0, self._fields_dev, self._goals_dev, self.reach, self.max_steps, self.window), None
         cells, origins, summary = (a.copy() for a in _split_words(words.cpu().numpy()))
         bad = np.flatnonzero(summary[:, 2] != ROUTE_OK)
         if bad.size:
@@ -251,20 +383,36 @@ class WorldFleet:
         points = np.ascontiguousarray(cell_centres(cells, self.limits[0], self.limits[1], self.shape), dtype=np.float32)
         arrived = summary[:, 3] == 1
         points[arrived] = self.goal_points[arrived]
-        return EpochTargets(cells, origins, environments.world_map_window_offsets(self.name, origins), points, summary)
+        return EpochTargets(cells, origins, environments.world_map_window_offsets(self.name, origins), points, summary, samples,
+                            words if self.seed_epochs else None)
 
     def step(self, seed, max_rounds=8):
         """One epoch: the targets of the current positions, a WorldRobotSampler from the positions to the sub-goal points on the windows,
-        its plan(max_rounds, seed), and the robots moved to the last points of the returned paths, as they are.  The epoch's window map
-        set is released afterwards (map_textures.release_sdf_textures).  -> (PlanResult, EpochTargets)"""
+        its plan(max_rounds, seed) -- with seed_epochs its plan_rounds_seeded from the epoch's seeds (the class's docstring) --, and the robots
+        moved to the last points of the returned paths, as they are.  The epoch's window map set is released afterwards
+        (map_textures.release_sdf_textures).  -> (PlanResult, EpochTargets); with seed_epochs `last_clear_min` (float32 [N]) holds the
+        seeds' least texel values, from the copy that brings the new positions back."""
         targets = self.epoch_targets(self.positions)
         sampler = WorldRobotSampler(self.model, self.positions, targets.points, targets.offsets, env_id=self.name, device=self.device,
                                     **self.sampler_kwargs)
         try:
-            res = sampler.plan(max_rounds=max_rounds, seed=seed)
+            if self.seed_epochs:
+                _, origins_dev, summary_dev = _split_words(targets.words)
+                seeds, clear_min = device_window_seeds(map_textures.device_world_texture(self.name, self.device), self.limits[0], self.limits[1],
+                                                       targets.samples, origins_dev, summary_dev, self.window, self.positions, targets.points,
+                                                       self.clearance, self.smooth_iters)
+                res = sampler.plan_rounds_seeded(sampler.trajs_from_global(seeds), paths_local=seeds[..., :2].contiguous(),
+                                                 local_rounds=True, n_noising_steps=self.n_noising_steps,
+                                                 n_denoising_steps=self.n_denoising_steps, max_rounds=max_rounds, seed=seed)
+            else:
+                res = sampler.plan(max_rounds=max_rounds, seed=seed)
         finally:
             map_textures.release_sdf_textures(sorted(set(sampler._window_ids)), self.device)
-        self.positions = np.ascontiguousarray(res.paths_local[:, -1, :].cpu().numpy(), dtype=np.float32)
+        if self.seed_epochs:
+            back = torch.cat([res.paths_local[:, -1, :], clear_min[:, None]], dim=1).cpu().numpy()       # one copy: the ends and clear_min
+            self.positions, self.last_clear_min = np.ascontiguousarray(back[:, :2], dtype=np.float32), back[:, 2].copy()
+        else:
+            self.positions = np.ascontiguousarray(res.paths_local[:, -1, :].cpu().numpy(), dtype=np.float32)
         return res, targets
 
     def run(self, max_epochs=None, max_rounds=8, seed=0):
@@ -279,6 +427,8 @@ class WorldFleet:
             res, targets = self.step(seed + e, max_rounds)
             paths.append(res.paths_local)
             epochs.append({"conflict_counts": list(res.conflict_counts), "summary": targets.summary, "offsets": targets.offsets})
+            if self.seed_epochs:
+                epochs[-1]["clear_min"] = self.last_clear_min
             arrived = targets.summary[:, 3] == 1             # the epoch's sub-goal was the goal point: the robot now stands on it
             if arrived.all():
                 break

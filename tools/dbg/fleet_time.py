@@ -11,6 +11,15 @@ reach 180 and max_steps 360 (WorldFleet's defaults), plan(max_rounds = 2):
   sampler   WorldRobotSampler's construction on the epoch's windows, with the cut of its window slices (the map set is released after
             every pass, so every pass cuts);
   rounds    its plan(max_rounds = 2, seed).
+Then the seeded epoch (WorldFleet(seed_epochs=True)) next to the unseeded one, on the same fleet, sampler and windows, the legs
+alternating inside every pass (unseeded rounds, then the seeded leg's four parts, 1 warm-up pass and the median of 5 as above):
+  targets+samples  epoch_targets with seeding on: one launch of mmd_grid_window_goal_samples in place of mmd_grid_window_goals, the same
+                   one copy back (the row next to it is the unseeded epoch_targets, timed in the same passes);
+  seeds            device_window_seeds: the upload of the start and goal points and one launch of mmd_window_seeds, 64 iterations;
+  trajs            WorldRobotSampler.trajs_from_global: torch operations;
+  seeded rounds    plan_rounds_seeded(init_trajs, paths_local = the seeds' positions, local_rounds=True, 3 + 3 steps, max_rounds = 2, seed).
+Before these are timed, robot 0's samples and seed are compared with window_goal_samples and window_seed on the downloaded field and
+texture, word for word and bit for bit.
 Before anything is timed: the field of robot 0's goal is compared with the numpy definition, and the sub-goals of every 8th robot with
 window_goals on the downloaded fields, integer for integer.  Per repeated figure: 1 warm-up pass, then the median of 5 passes.  'gpu ms'
 = HIP events around the pass on the current stream, 'wall ms' = perf_counter around the pass with a device synchronisation at both ends.
@@ -34,6 +43,60 @@ from mmd_amd.world import WorldRobotSampler                                     
 from world_route_time import LINES, random_world, say, timed                                      # noqa: E402
 
 T, B, ROUNDS, SEED = 25, 4, 2, 7
+
+
+def alternating(fns, passes=5, warmup=1):
+    """[(median gpu ms, median wall ms)] of every fn, the fns run one after the other inside every pass"""
+    import statistics
+    gpu, wall = [[] for _ in fns], [[] for _ in fns]
+    for k in range(warmup + passes):
+        for i, fn in enumerate(fns):
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0 = time.perf_counter()
+            e0.record()
+            fn()
+            e1.record()
+            torch.cuda.synchronize()
+            if k >= warmup:
+                gpu[i].append(e0.elapsed_time(e1))
+                wall[i].append(1e3 * (time.perf_counter() - t0))
+    return [(statistics.median(g), statistics.median(w)) for g, w in zip(gpu, wall)]
+
+
+def seeded_leg(fleet, sampler_of, wtex, lo, hi, pick, n):
+    """the seeded epoch next to the unseeded one of the same fleet (the module's docstring)"""
+    fleet.seed_epochs = True
+    t = fleet.epoch_targets(fleet.positions)
+    _, origins_dev, summary_dev = F._split_words(t.words)
+    build = lambda: F.device_window_seeds(wtex, lo, hi, t.samples, origins_dev, summary_dev, fleet.window, fleet.positions, t.points,      # noqa: E731
+                                          fleet.clearance, fleet.smooth_iters)
+    seeds, clear_min = build()
+    f = int(fleet.fields[0])
+    want = F.window_goal_samples(fleet.dist[f].cpu().numpy(), pick[0], fleet.field_goals[f], fleet.reach, fleet.max_steps, fleet.window)
+    assert want[4] == R.ROUTE_OK and np.array_equal(t.samples[0].cpu().numpy(), want[5]), "robot 0's samples are not the definition's"
+    seed0, cmin0 = F.window_seed(wtex.cpu().numpy(), lo, hi, want[5], want[1], fleet.window, fleet.positions[0], t.points[0], fleet.clearance,
+                                 fleet.smooth_iters)
+    assert np.array_equal(seeds[0].cpu().numpy().view(np.int32), seed0.view(np.int32)), "robot 0's seed is not the definition's"
+    assert clear_min[0].cpu().numpy().view(np.int32) == np.float32(cmin0).view(np.int32)
+    sampler = sampler_of()
+    init = sampler.trajs_from_global(seeds)
+    paths0 = seeds[..., :2].contiguous()
+    kw = dict(local_rounds=True, n_noising_steps=fleet.n_noising_steps, n_denoising_steps=fleet.n_denoising_steps, max_rounds=ROUNDS, seed=SEED)
+
+    def targets(on):
+        fleet.seed_epochs = on
+        fleet.epoch_targets(fleet.positions)
+    legs = alternating([lambda: sampler.plan(max_rounds=ROUNDS, seed=SEED), lambda: targets(False), lambda: targets(True), build,
+                        lambda: sampler.trajs_from_global(seeds), lambda: sampler.plan_rounds_seeded(init, paths_local=paths0, **kw)])
+    plain, seeded = sampler.plan(max_rounds=ROUNDS, seed=SEED), sampler.plan_rounds_seeded(init, paths_local=paths0, **kw)
+    map_textures.release_sdf_textures(sorted(set(sampler._window_ids)), "cuda")
+    names = ("unseeded rounds", "unseeded targets", "targets+samples", "seeds", "trajs", "seeded rounds")
+    say(f"N = {n:3d} | one session, legs alternating | " + " | ".join(f"{k}: gpu {g:7.3f} ms, wall {w:7.3f} ms" for k, (g, w) in zip(names, legs)))
+    say(f"N = {n:3d} | unseeded rounds: {plain.n_rounds} run, conflicts {plain.conflict_counts}; seeded rounds ({fleet.n_noising_steps} + "
+        f"{fleet.n_denoising_steps} steps, {fleet.smooth_iters} smoothing iterations): {seeded.n_rounds} run, conflicts "
+        f"{seeded.conflict_counts}; least clear_min {float(clear_min.min()):.4f} at clearance {fleet.clearance}")
+    fleet.seed_epochs = False
 
 
 def main():
@@ -85,6 +148,8 @@ def main():
             f"{fleet.epoch_bound()}, longest way {int(fleet.start_distances.max())} cells | sub-goals: gpu {g_gpu:7.3f} ms, wall {g_wall:7.3f} ms | "
             f"sampler + window cut ({len(set(sampler._window_ids))} windows): gpu {c_gpu:8.2f} ms, wall {c_wall:8.2f} ms | rounds "
             f"({res.n_rounds} run, conflicts {res.conflict_counts}): gpu {p_gpu:8.2f} ms, wall {p_wall:8.2f} ms")
+        seeded_leg(fleet, sampler_of=lambda: WorldRobotSampler(model, fleet.positions, targets.points, targets.offsets, env_id="Timed", n_samples=B),
+                   wtex=wtex, lo=lo, hi=hi, pick=pick, n=n)
         made.clear()
         del fleet, sampler
         torch.cuda.empty_cache()
