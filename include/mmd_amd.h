@@ -876,6 +876,47 @@ int mmd_window_seeds(const float* grid_dev, int nx, int ny, const float lo[2], c
                      const float* goal_points_dev /* [n][2] */, int smooth_iters, float two_dt, float* seeds_dev /* [n][64][4] */,
                      float* clear_min_dev /* [n] */, void* stream);
 
+/* World fleets: the sub-goals of one epoch kept apart (mmd_amd/world_fleet.py::subgoals_apart is the definition on the host, and
+ * subgoals_apart_sweeps(s) the state after s sweeps; the argument stands in that module's docstring).  Query q TAKES PART iff
+ * mmd_grid_window_goals' status for it is 0; its walk is that call's cell path c_q[0 .. walked_q], c_q[0] the start.  Two cells conflict
+ * iff dx^2 + dy^2 < sep^2.  Robots are taken in index order, a lower index has priority: the blockers of robot r are the chosen cells of
+ * the taking-part robots j < r and the START cells of the taking-part robots j > r, and
+ *   k_r = the largest k in [1, walked_r] whose cell c_r[k] conflicts with no blocker, 0 if there is none (the largest feasible index, not
+ *         the longest feasible prefix: a walk may pass a blocker);  the chosen cell is c_r[k_r].
+ * THE FACT: if the start cells of the taking-part robots are pairwise at least sep apart, so are the chosen cells, and every clear is 1
+ * (k = 0 always serves: robots with priority avoided r's start, the others' starts are apart from it by assumption).  mmd_grid_window_goals'
+ * progress bound does NOT hold for k_r: a robot may be held back to k = 0.
+ * The choice is computed as a fixed point.  A sweep gives every robot, all at once, the k of the rule above from the k of the robots
+ * j < r of the sweep before (two buffers, one launch per sweep, one wave per robot; nothing inside a sweep waits on another workgroup and
+ * the result does not depend on the order of the workgroups).  The dependence is strictly lower-triangular: the fixed point is unique,
+ * it is the definition's, n_queries sweeps always reach it, and changed == 0 proves it is reached.
+ *   restart != 0: walks every query, stores the cell paths in work_dev, sets every k to walked; then n_sweeps sweeps.
+ *   restart == 0: n_sweeps more sweeps on work_dev as the previous call on the same arguments left it.
+ * Either way the call then writes, for the state it reached, every word of every output for every query:
+ *   cells_dev[q]   = c_q[k_q]                      origins_dev[q] = mmd_grid_window_goals'
+ *   summary_dev[q] = (k_q, dist[c0] - k_q, 0, dist[c0] == k_q): mmd_grid_window_goals' format, so mmd_window_seeds reads it unchanged
+ *   extra_dev[q]   = (walked_q, clear_q), clear_q = 1 iff the last sweep found that the chosen cell conflicts with no blocker (0 before
+ *                    any sweep; at the fixed point it can be 0 only with k_q = 0)
+ *   samples_dev[q][j] = c_q[(j * k_q + 31) / 63], j = 0 .. 63: mmd_grid_window_goal_samples' spacing on the shortened path; NULL: not written
+ *   changed_dev[0] = the number of robots whose k moved in the call's last sweep (after a restart with n_sweeps == 0: the number of
+ *                    queries that take part)
+ * A query that does not take part gets mmd_grid_window_goals' words, extra (its summary's steps, 0) and zero samples, and blocks nobody.
+ * The call does not synchronise: the convergence policy is the caller's.  work_dev: mmd_grid_window_apart_work_bytes(n_queries,
+ * max_steps) bytes, 16-byte aligned; a restart initialises it, between a restart and its continuations the caller leaves it alone.
+ * Error returns, before anything is launched: those of mmd_grid_window_goals; sep outside 1 .. MMD_WINDOW_APART_MAX_SEP; max_steps above
+ * MMD_WINDOW_APART_MAX_STEPS; a negative n_sweeps; with n_queries > 0, a NULL, misaligned or short workspace, or a NULL cells, origins,
+ * summary, extra or changed.  n_queries == 0 returns 0 and launches nothing.  mmd_grid_window_apart_work_bytes returns 0 for a size the
+ * call refuses (and for n_queries == 0). */
+#define MMD_WINDOW_APART_MAX_STEPS 4095
+#define MMD_WINDOW_APART_MAX_SEP 1024
+size_t mmd_grid_window_apart_work_bytes(int n_queries, int max_steps);
+int mmd_grid_window_goals_apart(const int32_t* dist_dev, int nx, int ny, int n_fields, const int32_t* starts_dev /* [n][2] */,
+                                const int32_t* field_dev /* [n] */, const int32_t* goals_dev /* [n_fields][2] */, int n_queries, int reach,
+                                int max_steps, int window, int sep, int restart, int n_sweeps, void* work_dev, size_t work_bytes,
+                                int32_t* cells_dev /* [n][2] */, int32_t* origins_dev /* [n][2] */, int32_t* summary_dev /* [n][4] */,
+                                int32_t* extra_dev /* [n][2] */, int32_t* samples_dev /* [n][64][2] or NULL */,
+                                int32_t* changed_dev /* [1] */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

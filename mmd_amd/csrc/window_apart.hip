@@ -1,0 +1,241 @@
+// World fleets: every epoch's sub-goals kept apart (include/mmd_amd.h: mmd_grid_window_goals_apart).  The definition is the numpy function
+// subgoals_apart of mmd_amd/world_fleet.py, and the state after s sweeps is subgoals_apart_sweeps(s); the fact a fleet rests on (starts
+// pairwise `sep` apart give chosen cells pairwise `sep` apart) is argued there.  Every value here is an exact integer.  Plain loads and
+// vector stores; no LDS, no atomics, no scratch, and nothing inside a launch waits on another workgroup.
+#include <hip/hip_runtime.h>
+
+#include <climits>
+#include <cstdint>
+
+#include "../../include/mmd_amd.h"
+#include "common.h"
+#include "wave_dev.h"
+#include "window_walk_dev.h"
+
+namespace mmd {
+
+constexpr int WA_MAX_STEPS = MMD_WINDOW_APART_MAX_STEPS, WA_MAX_SEP = MMD_WINDOW_APART_MAX_SEP;
+constexpr int WA_MOVED = 1, WA_CLEAR = 2;                  // the bits of a robot's flag word
+static_assert(WG_THREADS == 64 && MMD_ROUTE_SEED_POINTS == 64, "a wave's 64 lanes are 64 candidates, 64 blockers and 64 samples");
+
+// The workspace of a call on n queries, in this order (every part is a multiple of 16 bytes from the 16-byte aligned base but the last
+// four, which need 8 and 4):
+//   meta   int4 [n]                  (steps, remaining, status, 0): window_goals' summary words of the plain walk
+//   paths  int2 [n][max_steps + 1]   the cells of the walk, c[0 .. steps]; cells behind `steps` are never written and never read
+//   origin int2 [n]
+//   k      int  [2][n]               the two buffers of the sweeps; a call begins and ends with the state in buffer 0
+//   flag   int  [n]                  WA_MOVED: k moved in the last sweep (after a restart: the query takes part); WA_CLEAR
+struct ApartWork {
+  int4* meta;
+  int2* paths;
+  int2* origin;
+  int* k[2];
+  int* flag;
+};
+
+__host__ __device__ inline size_t apart_row(int max_steps) { return (size_t)max_steps + 1; }
+
+static size_t apart_work_bytes(int n, int max_steps) {
+  return (size_t)n * (sizeof(int4) + apart_row(max_steps) * sizeof(int2) + sizeof(int2) + 3 * sizeof(int));
+}
+
+static ApartWork apart_work(void* base, int n, int max_steps) {
+  ApartWork w;
+  w.meta = (int4*)base;
+  w.paths = (int2*)(w.meta + n);
+  w.origin = w.paths + (size_t)n * apart_row(max_steps);
+  w.k[0] = (int*)(w.origin + n);
+  w.k[1] = w.k[0] + n;
+  w.flag = w.k[1] + n;
+  return w;
+}
+
+// ---- 1. the paths: one lane per query ----
+// grid_window_goals_kernel's walk (window_walk_dev.h: window_step), with every visited cell stored in the query's row.  The loop runs at
+// most min(max_steps, d0) times, so the last index written is at most max_steps, the row's last.  A stuck walk keeps the cells it covered
+// (window_goals reports its last one); a query outside the grid or on an unreached cell writes no cell.  Both k buffers start at
+// `steps`, and the flag says "moved" for a query that takes part: nothing is proved before a sweep has run.
+__global__ __launch_bounds__(WG_THREADS) void window_apart_paths_kernel(const int* __restrict__ dist_all, int nx, int ny, int n_fields,
+                                                                        const int2* __restrict__ starts, const int* __restrict__ field,
+                                                                        const int2* __restrict__ goals, int n_queries, int reach,
+                                                                        int max_steps, int window, ApartWork w) {
+  const int q = blockIdx.x * WG_THREADS + threadIdx.x;
+  if (q >= n_queries) return;
+  const int2 s = starts[q];
+  const int f = field[q];
+  const bool inside = f >= 0 && f < n_fields && s.x >= 0 && s.x < nx && s.y >= 0 && s.y < ny;
+  const int* dist = dist_all + (size_t)(inside ? f : 0) * nx * ny;
+  const int d0 = inside ? dist[(size_t)s.x * ny + s.y] : WG_UNREACHED;
+  if (d0 == WG_UNREACHED) {
+    w.meta[q] = make_int4(-1, -1, inside ? WG_UNREACHED_START : WG_OUTSIDE, 0);
+    w.origin[q] = make_int2(0, 0);
+    w.k[0][q] = w.k[1][q] = 0;
+    w.flag[q] = 0;
+    return;
+  }
+  int2* row = w.paths + (size_t)q * apart_row(max_steps);
+  const int2 g = goals[f];
+  int ix = s.x, iy = s.y, steps = 0, status = WG_OK;
+  row[0] = s;
+  const int bound = min(max_steps, d0);
+  for (int k = 0; k < bound; ++k) {
+    const int r = window_step(dist, nx, ny, s, g, reach, d0 - k - 1, ix, iy);
+    if (r < 0) status = WG_STUCK;
+    if (r != 1) break;
+    row[++steps] = make_int2(ix, iy);
+  }
+  w.meta[q] = make_int4(steps, d0 - steps, status, 0);
+  w.origin[q] = window_origin(s, nx, ny, window);
+  w.k[0][q] = w.k[1][q] = status == WG_OK ? steps : 0;
+  w.flag[q] = status == WG_OK ? WA_MOVED : 0;
+}
+
+// ---- 2. one sweep: one wave per robot ----
+// Robot r takes the largest k in [1, walked] whose cell conflicts with no blocker (dx^2 + dy^2 < sep^2), else 0.  Its blockers are the
+// cells c_j[k_prev[j]] of the taking-part robots j < r and the start cells of the taking-part robots j > r: it reads the buffer of the
+// sweep before and writes only its own word of the other buffer, so a sweep is a Jacobi step whatever the order of the workgroups.
+// Candidates: lane l of chunk c holds k = walked - 64 c - l and loads its cell, 8 bytes, next to its neighbours' (descending addresses).
+// Blockers: 64 at a time, one per lane; one farther than reach + sep (Chebyshev) from the robot's start is dropped at once -- every
+// candidate lies within `reach` of the start, so such a blocker is at least sep + 1 > sep cells from each along one axis: the cull is
+// exact.  The survivors of the ballot are broadcast one by one and every lane tests its own candidate.  The first chunk with a feasible
+// lane decides, and its lowest lane holds the largest k; k = 0 always serves, and what its lane found is `clear`.
+// Bounds: walked and every k_prev are clamped to [0, max_steps], so every cell index lies in its row whatever the workspace holds; the
+// chunk loop runs walked / 64 + 1 <= 64 times, the blocker loop ceil(n / 64) times, the broadcast loop at most 64 times.  The squares
+// are taken in 64 bits: cells of a taking-part walk lie in the grid, but the words are device data.
+__global__ __launch_bounds__(WG_THREADS) void window_apart_sweep_kernel(int n_queries, int reach, int max_steps, int sep, ApartWork w,
+                                                                        const int* __restrict__ k_prev, int* __restrict__ k_next) {
+  const int r = blockIdx.x, lane = threadIdx.x;
+  const int4 m = w.meta[r];
+  if (m.z != WG_OK) return;                                // takes no part: one decision per wave
+  const size_t stride = apart_row(max_steps);
+  const int2* row = w.paths + (size_t)r * stride;
+  const int walked = min(max(m.x, 0), max_steps);
+  const int2 s = row[0];
+  const long long far = (long long)reach + sep, sep2 = (long long)sep * sep;
+  int k_new = 0, clear = 0;
+  for (int c = 0; c <= walked / WG_THREADS; ++c) {
+    const int k = walked - c * WG_THREADS - lane;
+    const int2 cand = row[max(k, 0)];
+    bool conflict = false;
+    for (int base = 0; base < n_queries; base += WG_THREADS) {
+      const int j = base + lane;
+      bool blocks = j < n_queries && j != r && w.meta[min(j, n_queries - 1)].z == WG_OK;
+      int2 b = make_int2(0, 0);
+      if (blocks) {
+        b = w.paths[(size_t)j * stride + (j < r ? min(max(k_prev[j], 0), max_steps) : 0)];
+        blocks = max(llabs((long long)b.x - s.x), llabs((long long)b.y - s.y)) <= far;
+      }
+      unsigned long long live = __ballot(blocks);
+      while (live) {
+        const int src = __ffsll((long long)live) - 1;
+        live &= live - 1;
+        const long long dx = (long long)__shfl(b.x, src) - cand.x, dy = (long long)__shfl(b.y, src) - cand.y;
+        conflict |= dx * dx + dy * dy < sep2;
+      }
+    }
+    const unsigned long long serves = __ballot(k == 0 || (k > 0 && !conflict));
+    if (serves) {
+      const int first = __ffsll((long long)serves) - 1;
+      k_new = walked - c * WG_THREADS - first;
+      clear = __shfl((int)!conflict, first);
+      break;
+    }
+  }
+  if (lane == 0) {
+    k_next[r] = k_new;
+    w.flag[r] = (k_new != min(max(k_prev[r], 0), max_steps) ? WA_MOVED : 0) | (clear ? WA_CLEAR : 0);
+  }
+}
+
+// ---- 3. the outputs: one wave per robot, lane j = sample j ----
+// Every word of cells, origins, summary, extra and (if given) samples of the robot, from the state in k_cur; a robot that takes no part
+// gets window_goals' words, extra (steps, 0) and zero samples.  63 * k + 31 stays below 2^18.  The first workgroup also sums the moved
+// flags of all robots (wave_dev.h: wave_sum, a fixed order) into changed[0].  With to_first, the robot's k goes back to buffer 0, the
+// robot's own word: the next call finds the state there.
+__global__ __launch_bounds__(WG_THREADS) void window_apart_emit_kernel(int n_queries, int max_steps, ApartWork w, const int* __restrict__ k_cur,
+                                                                       int to_first, int2* __restrict__ cells, int2* __restrict__ origins,
+                                                                       int4* __restrict__ summary, int2* __restrict__ extra,
+                                                                       int2* __restrict__ samples, int* __restrict__ changed) {
+  const int r = blockIdx.x, j = threadIdx.x;
+  const int4 m = w.meta[r];
+  const bool ok = m.z == WG_OK;
+  const int2* row = w.paths + (size_t)r * apart_row(max_steps);
+  const int walked = min(max(m.x, -1), max_steps);
+  const int k = ok ? min(max(k_cur[r], 0), max(walked, 0)) : walked;          // the index of the cell reported; -1: none
+  if (samples) samples[(size_t)r * WG_THREADS + j] = ok ? row[(j * k + 31) / 63] : make_int2(0, 0);
+  if (j == 0) {
+    cells[r] = k >= 0 ? row[k] : make_int2(0, 0);
+    origins[r] = w.origin[r];
+    summary[r] = ok ? make_int4(k, m.y + (walked - k), WG_OK, m.y + (walked - k) == 0) : make_int4(m.x, m.y, m.z, 0);
+    extra[r] = make_int2(m.x, ok && (w.flag[r] & WA_CLEAR) ? 1 : 0);
+    if (to_first) w.k[0][r] = k_cur[r];
+  }
+  if (r == 0) {
+    int moved = 0;
+    for (int base = 0; base < n_queries; base += WG_THREADS) moved += base + j < n_queries ? (w.flag[base + j] & WA_MOVED) : 0;
+    moved = wave_sum(moved);
+    if (j == 0) changed[0] = moved;
+  }
+}
+
+}  // namespace mmd
+
+using namespace mmd;
+
+extern "C" {
+
+size_t mmd_grid_window_apart_work_bytes(int n_queries, int max_steps) {
+  if (n_queries < 0 || n_queries > INT_MAX - WG_THREADS || max_steps < 1 || max_steps > WA_MAX_STEPS) return 0;
+  return apart_work_bytes(n_queries, max_steps);
+}
+
+int mmd_grid_window_goals_apart(const int32_t* dist_dev, int nx, int ny, int n_fields, const int32_t* starts_dev, const int32_t* field_dev,
+                                const int32_t* goals_dev, int n_queries, int reach, int max_steps, int window, int sep, int restart,
+                                int n_sweeps, void* work_dev, size_t work_bytes, int32_t* cells_dev, int32_t* origins_dev,
+                                int32_t* summary_dev, int32_t* extra_dev, int32_t* samples_dev, int32_t* changed_dev, void* stream) {
+  MMD_REQUIRE(nx >= 1 && ny >= 1 && nx <= MMD_OCCUPANCY_MAX_SIDE && ny <= MMD_OCCUPANCY_MAX_SIDE,
+              "mmd_grid_window_goals_apart: a grid of %d x %d cells (1 to %d per side)", nx, ny, MMD_OCCUPANCY_MAX_SIDE);
+  MMD_REQUIRE(n_fields >= 0, "mmd_grid_window_goals_apart: n_fields = %d (>= 0)", n_fields);
+  MMD_REQUIRE(n_queries >= 0 && n_queries <= INT_MAX - WG_THREADS, "mmd_grid_window_goals_apart: n_queries = %d (0 to 2^31 - 65)", n_queries);
+  MMD_REQUIRE(window >= 1 && window <= nx && window <= ny, "mmd_grid_window_goals_apart: window = %d cells (1 to min(nx, ny) = %d)", window,
+              nx < ny ? nx : ny);
+  MMD_REQUIRE(reach >= 1 && reach <= window / 2 - 1, "mmd_grid_window_goals_apart: reach = %d cells (1 to window / 2 - 1 = %d)", reach,
+              window / 2 - 1);
+  MMD_REQUIRE(max_steps >= 1 && max_steps <= WA_MAX_STEPS, "mmd_grid_window_goals_apart: max_steps = %d (1 to %d: a row of the workspace)",
+              max_steps, WA_MAX_STEPS);
+  MMD_REQUIRE(sep >= 1 && sep <= WA_MAX_SEP, "mmd_grid_window_goals_apart: sep = %d cells (1 to %d)", sep, WA_MAX_SEP);
+  MMD_REQUIRE(n_sweeps >= 0, "mmd_grid_window_goals_apart: n_sweeps = %d (>= 0)", n_sweeps);
+  if (n_queries == 0) return 0;
+  MMD_REQUIRE(dist_dev || n_fields == 0, "mmd_grid_window_goals_apart: NULL dist with n_fields = %d", n_fields);
+  MMD_REQUIRE(goals_dev || n_fields == 0, "mmd_grid_window_goals_apart: NULL goals with n_fields = %d", n_fields);
+  MMD_REQUIRE(starts_dev, "mmd_grid_window_goals_apart: NULL starts");
+  MMD_REQUIRE(field_dev, "mmd_grid_window_goals_apart: NULL field indices");
+  MMD_REQUIRE(work_dev && (uintptr_t)work_dev % 16 == 0, "mmd_grid_window_goals_apart: NULL workspace, or one not aligned to 16 bytes");
+  MMD_REQUIRE(work_bytes >= apart_work_bytes(n_queries, max_steps), "mmd_grid_window_goals_apart: workspace of %zu bytes, %zu needed",
+              work_bytes, apart_work_bytes(n_queries, max_steps));
+  MMD_REQUIRE(cells_dev, "mmd_grid_window_goals_apart: NULL cells");
+  MMD_REQUIRE(origins_dev, "mmd_grid_window_goals_apart: NULL origins");
+  MMD_REQUIRE(summary_dev, "mmd_grid_window_goals_apart: NULL summary");
+  MMD_REQUIRE(extra_dev, "mmd_grid_window_goals_apart: NULL extra");
+  MMD_REQUIRE(changed_dev, "mmd_grid_window_goals_apart: NULL changed");
+  const ApartWork w = apart_work(work_dev, n_queries, max_steps);
+  hipStream_t st = (hipStream_t)stream;
+  if (restart) {
+    hipLaunchKernelGGL(window_apart_paths_kernel, dim3((n_queries + WG_THREADS - 1) / WG_THREADS), dim3(WG_THREADS), 0, st,
+                       (const int*)dist_dev, nx, ny, n_fields, (const int2*)starts_dev, (const int*)field_dev, (const int2*)goals_dev,
+                       n_queries, reach, max_steps, window, w);
+    MMD_HIP_CHECK(hipGetLastError());
+  }
+  int cur = 0;                                             // the buffer that holds the state
+  for (int s = 0; s < n_sweeps; ++s, cur ^= 1) {
+    hipLaunchKernelGGL(window_apart_sweep_kernel, dim3(n_queries), dim3(WG_THREADS), 0, st, n_queries, reach, max_steps, sep, w,
+                       (const int*)w.k[cur], w.k[cur ^ 1]);
+    MMD_HIP_CHECK(hipGetLastError());
+  }
+  hipLaunchKernelGGL(window_apart_emit_kernel, dim3(n_queries), dim3(WG_THREADS), 0, st, n_queries, max_steps, w, (const int*)w.k[cur], cur,
+                     (int2*)cells_dev, (int2*)origins_dev, (int4*)summary_dev, (int2*)extra_dev, (int2*)samples_dev, (int*)changed_dev);
+  MMD_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+}  // extern "C"

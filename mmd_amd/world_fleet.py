@@ -39,6 +39,43 @@ An epoch may start from its walk instead of from noise (WorldFleet(seed_epochs=T
 walk's cell path and window_seed turns them into a smoothed chain of points with velocities inside the robot's window; these two numpy
 functions are definitions as well, and mmd_grid_window_goal_samples and mmd_window_seeds (csrc/window_seeds.hip) compute the same
 integers and the same float32 bits.
+
+SEPARATION (WorldFleet(separation=), opt-in).  An epoch pins both ends of every path, and each walk ignores every other robot: two plain
+sub-goals may be one cell, or closer than the robot-robot margin, and then the epoch has a conflict pinned at t = 63 that no sampling
+resolves, and the next epoch has it pinned at t = 0.  subgoals_apart IS the definition of the sub-goals kept `sep` cells apart; the
+kernels (csrc/window_apart.hip) compute the same integers.
+
+  taking part  query q iff window_goal's status for it is ROUTE_OK; its walk is _walk's cell path c_q[0 .. walked_q], c_q[0] the start
+  conflict     two cells with dx^2 + dy^2 < sep^2, in integers
+  blockers     of robot r, the robots taken in index order (a lower index has priority): the CHOSEN cells of the taking-part robots
+               j < r and the START cells of the taking-part robots j > r
+  k_r          the largest k in [1, walked_r] whose cell c_r[k] conflicts with no blocker, 0 if there is none: the largest feasible index,
+               not the longest feasible prefix (a walk may pass a blocker; the sampler's soft constraints handle the way round it)
+  outputs      cell c_r[k_r]; origin window_goal's; summary (k_r, d0 - k_r, status, d0 == k_r), window_goals' format;
+               extra (walked_r, clear_r), clear_r = 1 iff the chosen cell conflicts with no blocker
+
+APART.  If the start cells of the taking-part robots are pairwise at least sep apart, so are the chosen cells, and every clear is 1.
+k = 0 is always feasible for robot r: the robots with priority chose against r's start, and the robots below r are counted at their
+starts, which are apart from r's by assumption; so the chosen cell of r, c_r[k_r] with k_r >= 1 by the rule or c_r[0] by this, conflicts
+with no blocker.  A chosen cell avoids every earlier choice by construction, and every later choice avoids it, because it is an
+earlier choice for them.  The ends of one epoch are the starts of the next, so the invariant carries through a run
+(tests/test_world_fleet_apart_host.py checks it by brute force over whole runs).  With starts already in conflict the rule still
+answers; clear = 0 marks a robot left on a start that conflicts (only with k = 0).
+
+PROGRESS does NOT hold under separation, and epoch_bound with it: a robot may be held back to k = 0 for as long as others stand in its
+way.  What holds is termination.  remaining never rises, so in every epoch either some robot's remaining falls (some k > 0), which can
+happen only finitely often, or every k is 0; then every robot stays on its cell, the next epoch's inputs are this epoch's, and the
+state repeats for good: if a robot is still off its goal the epoch is STALLED, and WorldFleet.run stops there.  A robot that walks onto
+its goal in this epoch has k > 0: it moves, its start cell may be what held another robot back, and the epoch is not stalled.
+
+The same choice as a fixed point, for the device (subgoals_apart_sweeps).  Start from k_r = walked_r; in one sweep every robot applies
+the rule to the k that the robots j < r held after the sweep before, all at once (Jacobi, two buffers).  k_r depends only on the robots
+j < r: after sweep s the robots 0 .. s - 1 hold the definition's k (robot 0 depends on starts alone; induction), so the fixed point is
+unique, it is subgoals_apart's result, n sweeps always reach it, and a sweep in which no k moved (changed == 0) proves it is reached,
+because a sweep is a function of the state before it.
+
+SUBGOAL_SEPARATION = 23 is the least separation that keeps two end points RR_MARGIN = 0.105 apart when each lies anywhere in its cell
+of 0.005: centres 23 cells apart leave the points at least 23 - sqrt(2) = 21.59 cells = 0.1079 apart; 22 gives 0.1029, too little.
 """
 import ctypes as C
 from typing import NamedTuple
@@ -175,6 +212,110 @@ def epoch_bound(d0, reach, max_steps):
     return -(-int(d0) // min(int(max_steps), int(reach)))
 
 
+# ---- sub-goals kept apart: the definition ------------------------------------------------------------------------------------------------
+SUBGOAL_SEPARATION = 23         # cells; the least separation that keeps two end points RR_MARGIN apart, each anywhere in its cell (docstring)
+
+
+def _checked_sep(what, sep):
+    if int(sep) != sep or not 1 <= int(sep) <= _lib.WINDOW_APART_MAX_SEP:
+        raise ValueError(f"{what}: sep = {sep} (a whole number of cells, 1 to {_lib.WINDOW_APART_MAX_SEP})")
+    return int(sep)
+
+
+def _apart_walks(dist, starts, fields, goals, reach, max_steps, window):
+    """(window_goals' three outputs, [the cell path of every query that takes part, else None])"""
+    dist = np.asarray(dist)
+    starts, goals = np.asarray(starts, np.int64).reshape(-1, 2), np.asarray(goals, np.int64).reshape(-1, 2)
+    fields = np.asarray(fields, np.int64).reshape(-1)
+    cells, origins, summary = window_goals(dist, starts, fields, goals, reach, max_steps, window)
+    paths = [None] * len(starts)
+    for q in np.flatnonzero(summary[:, 2] == ROUTE_OK):
+        f, (x0, y0) = int(fields[q]), (int(starts[q][0]), int(starts[q][1]))
+        paths[q], _ = _walk(dist[f], (x0, y0), (int(goals[f][0]), int(goals[f][1])), int(dist[f][x0, y0]), int(reach), int(max_steps))
+        assert len(paths[q]) - 1 == summary[q, 0]
+    return (cells, origins, summary), paths
+
+
+def _apart_choice(path, blockers, sep):
+    """(k, clear) of one robot: the largest k in [1, walked] whose cell conflicts with no blocker, else 0; clear: the chosen cell conflicts
+    with none.  Two cells conflict iff dx^2 + dy^2 < sep^2."""
+    cells, others = np.asarray(path, np.int64).reshape(-1, 1, 2), np.asarray(blockers, np.int64).reshape(1, -1, 2)
+    free = (((cells - others) ** 2).sum(-1) >= sep * sep).all(1)             # per cell of the path: it conflicts with no blocker
+    feasible = np.flatnonzero(free[1:])
+    return (int(feasible[-1]) + 1, 1) if feasible.size else (0, int(free[0]))
+
+
+def _apart_outputs(plain, paths, ks, clear):
+    """(cells, origins, summary, extra) of the choice ks (per taking-part query) on window_goals' outputs `plain`"""
+    cells, origins, summary = (a.copy() for a in plain)
+    extra = np.stack([summary[:, 0], np.zeros(len(summary), np.int32)], 1).astype(np.int32)
+    for q, path in enumerate(paths):
+        if path is not None:
+            d0 = int(summary[q, 0]) + int(summary[q, 1])
+            cells[q] = path[ks[q]]
+            summary[q] = (ks[q], d0 - ks[q], ROUTE_OK, int(d0 == ks[q]))
+            extra[q, 1] = clear[q]
+    return cells, origins, summary, extra
+
+
+def subgoals_apart(dist, starts, fields, goals, reach, max_steps, sep, window=400):
+    """(cells int32 [n, 2], origins int32 [n, 2], summary int32 [n, 4], extra int32 [n, 2]): window_goals with the sub-goals kept `sep`
+    cells apart (the module's docstring, SEPARATION).  Query q takes part iff window_goals' status for it is ROUTE_OK; the robots are taken
+    in index order, robot r against the chosen cells of the taking-part robots j < r and the start cells of the taking-part robots j > r,
+    and takes the largest k in [1, walked] whose cell conflicts with none of them, else 0.  summary = (k, d0 - k, status, arrived) in
+    window_goals' format, extra = (walked, clear).  A query that does not take part keeps window_goals' words, with extra (steps, 0)."""
+    sep = _checked_sep("subgoals_apart", sep)
+    plain, paths = _apart_walks(dist, starts, fields, goals, reach, max_steps, window)
+    taking = [q for q, p in enumerate(paths) if p is not None]
+    ks, clear = {}, {}
+    for r in taking:
+        blockers = [paths[j][ks[j]] for j in taking if j < r] + [paths[j][0] for j in taking if j > r]
+        ks[r], clear[r] = _apart_choice(paths[r], blockers, sep)
+    return _apart_outputs(plain, paths, ks, clear)
+
+
+def subgoals_apart_sweeps(dist, starts, fields, goals, reach, max_steps, sep, n_sweeps, window=400, with_samples=False):
+    """(cells, origins, summary, extra, changed[, samples]): subgoals_apart's choice as a fixed point, after n_sweeps sweeps from k = walked.
+    In one sweep every robot applies subgoals_apart's rule to the k that the robots j < r held after the sweep before, all at once;
+    `changed` is the number of robots whose k moved in the last sweep, `clear` what the last sweep found.  Before any sweep nothing is
+    known: clear = 0 and changed = the number of queries that take part.  changed == 0 proves the fixed point, which is subgoals_apart's
+    result; n sweeps always reach it (the module's docstring)."""
+    sep = _checked_sep("subgoals_apart_sweeps", sep)
+    if int(n_sweeps) < 0:
+        raise ValueError(f"subgoals_apart_sweeps: n_sweeps = {n_sweeps} (>= 0)")
+    plain, paths = _apart_walks(dist, starts, fields, goals, reach, max_steps, window)
+    taking = [q for q, p in enumerate(paths) if p is not None]
+    ks = {q: len(paths[q]) - 1 for q in taking}
+    clear, changed = {q: 0 for q in taking}, len(taking)
+    for _ in range(int(n_sweeps)):
+        new = {}
+        for r in taking:
+            blockers = [paths[j][ks[j]] for j in taking if j < r] + [paths[j][0] for j in taking if j > r]
+            new[r], clear[r] = _apart_choice(paths[r], blockers, sep)
+        changed = sum(new[q] != ks[q] for q in taking)
+        ks = new
+    out = _apart_outputs(plain, paths, ks, clear) + (changed,)
+    if with_samples:
+        samples = np.zeros((len(paths), SEED_POINTS, 2), np.int32)
+        for q in taking:
+            samples[q] = np.asarray(paths[q][:ks[q] + 1], np.int32)[sample_offsets(ks[q] + 1)]
+        out += (samples,)
+    return out
+
+
+def subgoals_apart_samples(dist, starts, fields, goals, reach, max_steps, sep, window=400):
+    """(cells, origins, summary, extra, samples int32 [n, 64, 2]): subgoals_apart with the support cells of the shortened walks,
+    samples[j] = c[(j * k + 31) // 63] over c[0 .. k]: window_goal_samples' spacing.  A query that does not take part gets zeros."""
+    cells, origins, summary, extra = subgoals_apart(dist, starts, fields, goals, reach, max_steps, sep, window)
+    _, paths = _apart_walks(dist, starts, fields, goals, reach, max_steps, window)
+    samples = np.zeros((len(paths), SEED_POINTS, 2), np.int32)
+    for q, path in enumerate(paths):
+        if path is not None:
+            k = int(summary[q, 0])
+            samples[q] = np.asarray(path[:k + 1], np.int32)[sample_offsets(k + 1)]
+    return cells, origins, summary, extra, samples
+
+
 # ---- the same on the device ----------------------------------------------------------------------------------------------------------------
 def _window_goals_words(dist_dev, starts, fields, goals, reach, max_steps, window, with_samples=False, what="device_window_goals"):
     """device_window_goals' launch -> one int32 tensor [8 n] on the device: cells [n, 2], then origins [n, 2], then summary [n, 4].
@@ -249,6 +390,57 @@ def device_window_seeds(tex_dev, lo, hi, samples, origins, summary, window, star
     return seeds, clear_min
 
 
+def _subgoals_apart_words(dist_dev, starts, fields, goals, reach, max_steps, sep, window, sweeps, with_samples, what="device_subgoals_apart"):
+    """device_subgoals_apart's launches -> (one int32 tensor [10 n + 1] on the device: cells [n, 2], origins [n, 2], summary [n, 4],
+    extra [n, 2], changed [1]; its last copy on the host, numpy; samples int32 [n, 64, 2] on the device or None; the sweeps run)"""
+    if dist_dev.dim() != 3 or dist_dev.dtype != torch.int32 or not dist_dev.is_cuda or not dist_dev.is_contiguous():
+        raise ValueError(f"{what}: dist must be a contiguous int32 CUDA(HIP) tensor [n_fields, nx, ny]")
+    reach, max_steps, window = _checked_walk_args(what, tuple(dist_dev.shape[1:]), reach, max_steps, window)
+    sep, sweeps = _checked_sep(what, sep), int(sweeps)
+    if max_steps > _lib.WINDOW_APART_MAX_STEPS or sweeps < 1:
+        raise ValueError(f"{what}: max_steps = {max_steps} (at most {_lib.WINDOW_APART_MAX_STEPS}), sweeps = {sweeps} (at least 1)")
+    starts_dev = _int32_dev(starts, (-1, 2), dist_dev.device, f"{what}: starts")
+    n = starts_dev.shape[0]
+    fields_dev = _int32_dev(fields, (n,), dist_dev.device, f"{what}: fields")
+    goals_dev = _int32_dev(goals, (int(dist_dev.shape[0]), 2), dist_dev.device, f"{what}: goals")
+    work_bytes = int(_lib.load().mmd_grid_window_apart_work_bytes(n, max_steps))
+    work = torch.empty(work_bytes, dtype=torch.uint8, device=dist_dev.device)
+    words = torch.empty(10 * n + 1, dtype=torch.int32, device=dist_dev.device)     # (the summary rows start 16 n bytes in: aligned as int4)
+    samples = torch.empty(n, SEED_POINTS, 2, dtype=torch.int32, device=dist_dev.device) if with_samples else None
+    at = lambda k: C.c_void_p(words.data_ptr() + 4 * k)                          # noqa: E731
+
+    def launch(restart, n_sweeps):
+        _lib.launch("mmd_grid_window_goals_apart", dist_dev, C.c_void_p(dist_dev.data_ptr()), int(dist_dev.shape[1]), int(dist_dev.shape[2]),
+                    int(dist_dev.shape[0]), C.c_void_p(starts_dev.data_ptr()), C.c_void_p(fields_dev.data_ptr()),
+                    C.c_void_p(goals_dev.data_ptr()), n, reach, max_steps, window, sep, restart, n_sweeps, C.c_void_p(work.data_ptr()),
+                    work_bytes, at(0), at(2 * n), at(4 * n), at(8 * n), C.c_void_p(samples.data_ptr()) if with_samples else None, at(10 * n))
+        return words.cpu().numpy()
+    run = min(sweeps, n + 1)
+    host = launch(1, run)
+    while host[10 * n] != 0 and run < n + 1:                 # n sweeps reach the fixed point, one more reads changed == 0
+        more = min(sweeps, n + 1 - run)
+        host, run = launch(0, more), run + more
+    if host[10 * n] != 0:
+        raise RuntimeError(f"{what}: {int(host[10 * n])} robots still moved in sweep {run} of {n} robots: the workspace was disturbed")
+    return words, host, samples, run
+
+
+def _split_apart_words(words):
+    n = (words.shape[0] - 1) // 10
+    return _split_words(words[:8 * n]) + (words[8 * n:10 * n].reshape(n, 2),)
+
+
+def device_subgoals_apart(dist_dev, starts, fields, goals, reach, max_steps, sep, window=400, sweeps=4, with_samples=False):
+    """(cells int32 [n, 2], origins int32 [n, 2], summary int32 [n, 4], extra int32 [n, 2][, samples int32 [n, 64, 2]], n_sweeps_run) on
+    dist_dev's device: subgoals_apart() (with samples: subgoals_apart_samples()) for every query, word for word, by
+    mmd_grid_window_goals_apart: a restart call with `sweeps` sweeps, then, while `changed` is not zero, `sweeps` more, at most n + 1 in
+    all, the first call included (n reach the fixed point, the one after reads changed == 0).  No queries at all are refused, as
+    device_window_goals refuses them.  Every call ends with one device -> host copy of all words, extra
+    and changed, which live in one tensor: the common case costs one copy.  The first four results are views of that tensor."""
+    words, _, samples, run = _subgoals_apart_words(dist_dev, starts, fields, goals, reach, max_steps, sep, window, sweeps, with_samples)
+    return _split_apart_words(words) + ((samples,) if with_samples else ()) + (run,)
+
+
 # ---- the fleet -----------------------------------------------------------------------------------------------------------------------------
 class EpochTargets(NamedTuple):
     """What one epoch plans towards (WorldFleet.epoch_targets), numpy on the host."""
@@ -259,6 +451,8 @@ class EpochTargets(NamedTuple):
     summary: np.ndarray         # int32 [N, 4]: (steps, remaining, status, arrived)
     samples: torch.Tensor = None    # seed_epochs: int32 [N, 64, 2] on the device, the walks' support cells (never copied back); else None
     words: torch.Tensor = None      # seed_epochs: int32 [8 N] on the device, (cells, origins, summary) as launched (_split_words); else None
+    extra: np.ndarray = None        # separation: int32 [N, 2] = (walked, clear) of subgoals_apart; else None
+    sweeps: int = None              # separation: the sweeps device_subgoals_apart ran; else None
 
 
 class FleetResult(NamedTuple):
@@ -266,7 +460,8 @@ class FleetResult(NamedTuple):
     paths: torch.Tensor         # float32 [N, E * 64, 2] on the device, global: epoch e's paths are columns [64 e, 64 e + 64)
     arrived: np.ndarray         # bool [N]: the robot stands on its exact goal point
     # per epoch {"conflict_counts", "summary", "offsets"}: the PlanResult's counts, the epoch's targets; with seed_epochs also
-    # "clear_min", float32 [N]: the least texel value over each robot's seed points
+    # "clear_min", float32 [N]: the least texel value over each robot's seed points; with separation also "held_back" (int [N]: walked - k),
+    # "sweeps" and "stalled" (every k is 0 and some robot is off its goal: every later epoch would repeat this one)
     epochs: list
 
 
@@ -294,14 +489,25 @@ class WorldFleet:
     sampled between its two pinned ends.
     With seed_epochs=False (the default) nothing of this runs: the code path is the one without the option.
 
+    separation=None (the default) runs exactly the code path without the option.  An int >= 1 (SUBGOAL_SEPARATION = 23 keeps the pinned
+    ends RR_MARGIN apart) keeps every epoch's sub-goals that many cells apart (the module's docstring, SEPARATION): the constructor refuses,
+    naming both robots, two start cells or two goal cells closer than that, and max_steps above 4095; epoch_targets runs
+    device_subgoals_apart (mmd_grid_window_goals_apart: a restart call of 4 sweeps and, while robots still moved, 4 more) in place of
+    mmd_grid_window_goals, with seed_epochs with the samples of the shortened walks, so that mmd_window_seeds, unchanged, builds the seeds
+    on them; EpochTargets gains `extra` (walked, clear) and `sweeps`, every epoch's dict "held_back" (walked - k per robot), "sweeps" and
+    "stalled"; run(max_epochs=None) loops until every robot has arrived or an epoch is stalled (no robot moves, every k is 0: the
+    state would repeat for good), which terminates although epoch_bound no longer holds; an explicit max_epochs still caps it.
+
     Out of scope here: an arrived robot is sampled like any other, between two ends pinned to its goal point, not held still; every
     epoch builds a sampler of its own, the windows of one long-lived sampler are not moved in place; the fleet is not sharded over ranks;
-    repair= and replan=, which WorldRobotSampler refuses.  Whether a seeded epoch resolves conflicts as well as one from noise is not
+    repair= and replan=, which WorldRobotSampler refuses; with separation=, a stalled fleet is reported, not resolved (the priorities are
+    the robots' indices and never rotate, and no robot steps aside), and without it two sub-goals may coincide.  Whether a seeded epoch resolves conflicts as well as one from noise is not
     known."""
 
     def __init__(self, model, name, starts, goals, clearance=OBSTACLE_MARGIN, reach=180, max_steps=360, device="cuda", seed_epochs=False,
-                 smooth_iters=64, n_noising_steps=3, n_denoising_steps=3, **world_robot_sampler_kwargs):
+                 smooth_iters=64, n_noising_steps=3, n_denoising_steps=3, separation=None, **world_robot_sampler_kwargs):
         self.model, self.name, self.device = model, name, environments.resolved_device(device)
+        self.separation = None if separation is None else _checked_sep("WorldFleet: separation", separation)
         self.clearance = float(clearance)
         self.seed_epochs = bool(seed_epochs)
         self.smooth_iters, self.n_noising_steps, self.n_denoising_steps = int(smooth_iters), int(n_noising_steps), int(n_denoising_steps)
@@ -321,6 +527,16 @@ class WorldFleet:
         if n == 0 or self.goal_points.shape[0] != n:
             raise ValueError(f"WorldFleet: {n} starts and {self.goal_points.shape[0]} goals (equal and at least 1)")
         s_cells, g_cells = (self._cells(pts, what) for pts, what in ((s_pts, "start"), (self.goal_points, "goal")))
+        if self.separation is not None:
+            if self.max_steps > _lib.WINDOW_APART_MAX_STEPS:
+                raise ValueError(f"WorldFleet: max_steps = {self.max_steps} with separation= (at most {_lib.WINDOW_APART_MAX_STEPS})")
+            for what, cells in (("start", s_cells), ("goal", g_cells)):
+                d = cells.astype(np.int64)[:, None, :] - cells.astype(np.int64)[None, :, :]
+                close = np.argwhere(np.triu((d * d).sum(-1) < self.separation ** 2, 1))
+                if close.size:
+                    a, b = (int(v) for v in close[0])
+                    raise ValueError(f"WorldFleet: the {what} cells of robots {a} and {b} on {name!r}, {cells[a].tolist()} and "
+                                     f"{cells[b].tolist()}, are closer than separation = {self.separation} cells")
         self.field_goals, which = np.unique(g_cells, axis=0, return_inverse=True)
         self.fields = which.reshape(-1).astype(np.int32)
         tex = map_textures.device_world_texture(name, self.device)
@@ -370,11 +586,18 @@ class WorldFleet:
         if pts.shape[0] != self.n_robots:
             raise ValueError(f"WorldFleet.epoch_targets: {pts.shape[0]} positions for {self.n_robots} robots")
         c0 = self._cells(pts, "position")
+        if self.separation is not None:
+            return self._targets_apart(c0)
         if self.seed_epochs:
             words, samples = _window_goals_words(self.dist, c0, self._fields_dev, self._goals_dev, self.reach, self.max_steps, self.window, True)
         else:
             words, samples = _window_goals_words(self.dist, c0, self._fields_dev, self._goals_dev, self.reach, self.max_steps, self.window), None
         cells, origins, summary = (a.copy() for a in _split_words(words.cpu().numpy()))
+        return self._targets(c0, cells, origins, summary, samples, words if self.seed_epochs else None)
+
+    def _targets(self, c0, cells, origins, summary, *rest):
+        """EpochTargets from a sub-goal launch's words on the host (`rest`: the fields behind `summary`): refuses a robot whose status is
+        not ROUTE_OK, and gives every robot its sub-goal point"""
         bad = np.flatnonzero(summary[:, 2] != ROUTE_OK)
         if bad.size:
             r = int(bad[0])
@@ -383,8 +606,15 @@ class WorldFleet:
         points = np.ascontiguousarray(cell_centres(cells, self.limits[0], self.limits[1], self.shape), dtype=np.float32)
         arrived = summary[:, 3] == 1
         points[arrived] = self.goal_points[arrived]
-        return EpochTargets(cells, origins, environments.world_map_window_offsets(self.name, origins), points, summary, samples,
-                            words if self.seed_epochs else None)
+        return EpochTargets(cells, origins, environments.world_map_window_offsets(self.name, origins), points, summary, *rest)
+
+    def _targets_apart(self, c0):
+        """epoch_targets with separation: device_subgoals_apart's launches (with seed_epochs: with the samples of the shortened walks, which
+        stay on the device) in place of mmd_grid_window_goals; the summary is (k, d0 - k, status, arrived)"""
+        words, host, samples, run = _subgoals_apart_words(self.dist, c0, self._fields_dev, self._goals_dev, self.reach, self.max_steps,
+                                                          self.separation, self.window, 4, self.seed_epochs, "WorldFleet")
+        cells, origins, summary, extra = (a.copy() for a in _split_apart_words(host))
+        return self._targets(c0, cells, origins, summary, samples, words[:8 * self.n_robots] if self.seed_epochs else None, extra, run)
 
     def step(self, seed, max_rounds=8):
         """One epoch: the targets of the current positions, a WorldRobotSampler from the positions to the sub-goal points on the windows,
@@ -420,7 +650,11 @@ class WorldFleet:
         from the starts).  A robot that has arrived keeps taking part, from its goal point to its goal point, so that the others stay
         constrained by it.  -> FleetResult"""
         if max_epochs is None:
-            max_epochs = self.epoch_bound()
+            max_epochs = self.epoch_bound() if self.separation is None else None
+        elif int(max_epochs) < 1:
+            raise ValueError(f"WorldFleet.run: max_epochs = {max_epochs} (at least 1)")
+        if self.separation is not None:
+            return self._run_apart(max_epochs, max_rounds, seed)
         paths, epochs = [], []
         arrived = np.zeros(self.n_robots, bool)
         for e in range(int(max_epochs)):
@@ -435,3 +669,20 @@ class WorldFleet:
         if not paths:
             raise ValueError(f"WorldFleet.run: max_epochs = {max_epochs} (at least 1)")
         return FleetResult(torch.cat(paths, dim=1), arrived, epochs)
+
+    def _run_apart(self, max_epochs, max_rounds, seed):
+        """run with separation: epochs until every robot has arrived or an epoch is stalled (the module's docstring: one of the two comes),
+        at most max_epochs of them if that is given"""
+        paths, epochs, e = [], [], 0
+        while True:
+            res, targets = self.step(seed + e, max_rounds)
+            arrived = targets.summary[:, 3] == 1
+            stalled = bool((targets.summary[:, 0] == 0).all() and not arrived.all())      # no robot moves, one that arrives now included
+            paths.append(res.paths_local)
+            epochs.append({"conflict_counts": list(res.conflict_counts), "summary": targets.summary, "offsets": targets.offsets,
+                           "held_back": targets.extra[:, 0] - targets.summary[:, 0], "sweeps": targets.sweeps, "stalled": stalled})
+            if self.seed_epochs:
+                epochs[-1]["clear_min"] = self.last_clear_min
+            e += 1
+            if arrived.all() or stalled or (max_epochs is not None and e >= int(max_epochs)):
+                return FleetResult(torch.cat(paths, dim=1), arrived, epochs)

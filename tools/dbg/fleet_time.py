@@ -1,6 +1,6 @@
 """What an epoch of a world fleet costs on the device, needs one GPU (run it under `timeout`; one process):
 
-    python tools/dbg/fleet_time.py [OUT.txt]
+    python tools/dbg/fleet_time.py [--apart] [OUT.txt]
 
 The world is world_route_time.py's: 2048 x 2048 cells, 300 random boxes, clearance world.OBSTACLE_MARGIN.  With N = 64 and N = 256 robots,
 starts and distinct goals drawn from the cells that one routable cell reaches, random-init weights, T = 25, B = 4 samples per robot,
@@ -20,6 +20,14 @@ alternating inside every pass (unseeded rounds, then the seeded leg's four parts
   seeded rounds    plan_rounds_seeded(init_trajs, paths_local = the seeds' positions, local_rounds=True, 3 + 3 steps, max_rounds = 2, seed).
 Before these are timed, robot 0's samples and seed are compared with window_goal_samples and window_seed on the downloaded field and
 texture, word for word and bit for bit.
+Then the sub-goals kept apart (WorldFleet(separation=)) next to the plain ones, on the same fleet, alternating inside every pass in the same
+protocol:
+  targets apart    epoch_targets with separation = SUBGOAL_SEPARATION = 23: device_subgoals_apart's restart call of 4 sweeps and its one
+                   copy back, and 4 more sweeps with another copy while robots still moved (the row says how many sweeps ran); the row
+                   next to it is the plain epoch_targets, timed in the same passes.
+The timing fleet's starts are random cells, drawn with no regard to one another, so the leg switches the separation on behind the
+constructor's refusal; starts in conflict only give clear = 0.  Before the leg is timed: every robot that was not held back has the plain
+targets' words, and every k lies in [0, walked].  --apart runs the field build, the plain sub-goals and this leg only.
 Before anything is timed: the field of robot 0's goal is compared with the numpy definition, and the sub-goals of every 8th robot with
 window_goals on the downloaded fields, integer for integer.  Per repeated figure: 1 warm-up pass, then the median of 5 passes.  'gpu ms'
 = HIP events around the pass on the current stream, 'wall ms' = perf_counter around the pass with a device synchronisation at both ends.
@@ -99,8 +107,29 @@ def seeded_leg(fleet, sampler_of, wtex, lo, hi, pick, n):
     fleet.seed_epochs = False
 
 
+def apart_leg(fleet, n):
+    """the sub-goals kept apart next to the plain ones of the same fleet (the module's docstring)"""
+    def targets(separation):
+        fleet.separation = separation
+        return fleet.epoch_targets(fleet.positions)
+    plain, apart = targets(None), targets(F.SUBGOAL_SEPARATION)
+    k, walked, clear = apart.summary[:, 0], apart.extra[:, 0], apart.extra[:, 1]
+    kept = walked == k
+    assert ((0 <= k) & (k <= walked)).all() and np.array_equal(walked, plain.summary[:, 0]), "k outside [0, walked]"
+    assert np.array_equal(apart.cells[kept], plain.cells[kept]) and np.array_equal(apart.summary[kept], plain.summary[kept])
+    legs = alternating([lambda: targets(None), lambda: targets(F.SUBGOAL_SEPARATION)])
+    fleet.separation = None
+    say(f"N = {n:3d} | one session, legs alternating | " + " | ".join(f"{name}: gpu {g:7.3f} ms, wall {w:7.3f} ms" for name, (g, w) in
+                                                                       zip(("plain targets", "targets apart"), legs)))
+    say(f"N = {n:3d} | separation {F.SUBGOAL_SEPARATION} cells: {apart.sweeps} sweeps run, {int((~kept).sum())} robots held back (most "
+        f"{int((walked - k).max())} cells, {int(((k == 0) & (walked > 0)).sum())} to k = 0), {int((clear == 0).sum())} with clear = 0 (starts in "
+        f"conflict); longest walk {int(walked.max())} cells")
+
+
 def main():
     import gpu_common
+    apart_only = "--apart" in sys.argv
+    out = [a for a in sys.argv[1:] if a != "--apart"]
     say(f"# device: {torch.cuda.get_device_name(0)}; 1 warm-up pass, median of 5 (the field build: one pass)")
     occ = random_world(1)
     E.register_world_map("Timed", occ)
@@ -133,6 +162,13 @@ def main():
             assert (targets.cells[r].tolist(), targets.origins[r].tolist(), targets.summary[r].tolist()) == \
                 (want[0][0].tolist(), want[1][0].tolist(), want[2][0].tolist()), f"robot {r}'s sub-goal is not the definition's"
         g_gpu, g_wall = timed(lambda: fleet.epoch_targets(fleet.positions))
+        if apart_only:
+            say(f"N = {n:3d} | fields ({n} goals, {4 * n * occ.size / 2 ** 20:.0f} MiB): wall {t_fields:9.1f} ms | longest way "
+                f"{int(fleet.start_distances.max())} cells | sub-goals: gpu {g_gpu:7.3f} ms, wall {g_wall:7.3f} ms")
+            apart_leg(fleet, n)
+            del fleet
+            torch.cuda.empty_cache()
+            continue
         made = []
 
         def construct():
@@ -150,12 +186,13 @@ def main():
             f"({res.n_rounds} run, conflicts {res.conflict_counts}): gpu {p_gpu:8.2f} ms, wall {p_wall:8.2f} ms")
         seeded_leg(fleet, sampler_of=lambda: WorldRobotSampler(model, fleet.positions, targets.points, targets.offsets, env_id="Timed", n_samples=B),
                    wtex=wtex, lo=lo, hi=hi, pick=pick, n=n)
+        apart_leg(fleet, n)
         made.clear()
         del fleet, sampler
         torch.cuda.empty_cache()
     E.unregister_world_map("Timed")
-    if len(sys.argv) > 1:
-        with open(sys.argv[1], "w") as f:
+    if out:
+        with open(out[0], "w") as f:
             f.write("\n".join(LINES) + "\n")
 
 
