@@ -917,6 +917,42 @@ int mmd_grid_window_goals_apart(const int32_t* dist_dev, int nx, int ny, int n_f
                                 int32_t* extra_dev /* [n][2] */, int32_t* samples_dev /* [n][64][2] or NULL */,
                                 int32_t* changed_dev /* [1] */, void* stream);
 
+/* World fleets: one window set for a whole run, moved between epochs (csrc/fleet_epoch.hip).
+ *
+ * mmd_sdf_grid_windows for windows that mostly stay where they are: the same clamped gather, the same arguments and the same words
+ * written, but window k is left alone -- no texel loaded, none stored -- where held_dev[k] == origins_dev[k] (both words).  held_dev
+ * [n_windows][2]: the origins the slices of windows_dev hold now, device data; NULL: every window is cut.  The call only reads held_dev;
+ * it must not be origins_dev's memory written by another launch in flight (the caller keeps two origin buffers, this move's and the
+ * last one's).  A workgroup's test is two wave-uniform 8-byte loads.  Error returns, before anything is launched:
+ * mmd_sdf_grid_windows'.  n_windows == 0 returns 0 and launches nothing. */
+int mmd_sdf_grid_windows_moved(const float* world_grid_dev, int wnx, int wny, const int32_t* origins_dev /* [n][2] */,
+                               const int32_t* held_dev /* [n][2] or NULL */, int n_windows, int nx, int ny,
+                               float* windows_dev /* [n][nx][ny][4] */, void* stream);
+
+/* Everything a many-robot sampler's state takes from an epoch's targets, from device data alone: one wave per robot, lane = time step.
+ * cells_dev, origins_dev, summary_dev: mmd_grid_window_goals' words (any words: they are converted and compared, never used as an
+ * index).  points_dev: the robots' current points, robot r's two floats at points_dev + r * points_stride (2 for a packed [n][2]; 128
+ * for the last points of paths [n][64][2]; even and at least 2); goal_points_dev [n][2]: their exact goal points; line_a_dev [64]: the
+ * line parameters a_t (numpy.linspace(0, 1, 64) in float32).  Per robot r and axis k, every operation rounded once and none contracted:
+ *   offsets_dev[r][k]   = (float)(((double)origin * offset_terms[0] + offset_terms[1 + k]) - offset_terms[3 + k])
+ *                         -- offset_terms = (cell size, the world's origin x, y, the tile's lower limit x, y), doubles
+ *   subgoals_dev[r][k]  = goal_points_dev[r][k] where summary[r][3] == 1, else centre_terms[k] + ((float)cell + 0.5f) * centre_terms[2 + k]
+ *                         -- centre_terms = (the world's lower limit x, y, its pitch x, y), floats
+ *   hard_first_dev[r]   = normalised (points[r] - offsets[r], 0, 0),  hard_last_dev[r] = normalised (subgoals[r] - offsets[r], 0, 0),
+ *                         normalised(x)[c] = ((x[c] - norm_min[c]) / norm_range[c]) * 2 - 1 with a correctly rounded divide
+ *   lines_dev[r][t][k]  = points[r][k] * (1 - a_t) + subgoals[r][k] * a_t
+ * Every word of the five outputs is written for every robot.  offsets_dev, subgoals_dev and lines_dev are 8-byte aligned, hard_first_dev
+ * and hard_last_dev 16-byte aligned, as are the inputs by their rows (cells, origins, points and goal points 8 bytes, summary 16).  Error
+ * returns, before anything is launched: a negative n_robots; points_stride odd or below 2; NULL offset_terms, centre_terms, norm_min or
+ * norm_range; with n_robots > 0, a NULL or misaligned pointer among the device arguments.  n_robots == 0 returns 0 and launches nothing. */
+int mmd_fleet_epoch_frames(const int32_t* cells_dev /* [n][2] */, const int32_t* origins_dev /* [n][2] */,
+                           const int32_t* summary_dev /* [n][4] */, const float* points_dev /* [n] rows of points_stride floats */,
+                           int points_stride, const float* goal_points_dev /* [n][2] */, int n_robots, const double offset_terms[5],
+                           const float centre_terms[4],
+                           const float norm_min[4], const float norm_range[4], const float* line_a_dev /* [64] */,
+                           float* offsets_dev /* [n][2] */, float* subgoals_dev /* [n][2] */, float* hard_first_dev /* [n][4] */,
+                           float* hard_last_dev /* [n][4] */, float* lines_dev /* [n][64][2] */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

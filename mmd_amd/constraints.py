@@ -258,11 +258,19 @@ def framed_slot_bound(offsets, robot0, n_local, limits=None, radius=VERTEX_CONST
     wlo, whi = (np.asarray(v, dtype=np.float64) for v in framed_window(limits, radius))
     lo, hi = np.asarray(limits[0], dtype=np.float64), np.asarray(limits[1], dtype=np.float64)
     eps = 4.0 * float(np.finfo(np.float32).eps) * (np.abs(off).max() + max(np.abs(wlo).max(), np.abs(whi).max()))
+    box_lo, box_hi = off + lo, off + hi
     worst = 0
-    for r in range(robot0, robot0 + n_local):
-        hit = np.all((off + hi >= off[r] + wlo - eps) & (off + lo <= off[r] + whi + eps), axis=1)
-        worst = max(worst, int(hit.sum()) - 1)                          # (robot r's own box always intersects)
+    rows = max(1, SLOT_BOUND_CHUNK_PAIRS // n)          # the local robots, a chunk of rows at a time: [rows, n, 2] comparisons, never n^2
+    for r0 in range(robot0, robot0 + n_local, rows):
+        own = off[r0:min(r0 + rows, robot0 + n_local)]
+        own_lo, own_hi = own + wlo - eps, own + whi + eps
+        hit = ((box_hi[None, :, 0] >= own_lo[:, None, 0]) & (box_lo[None, :, 0] <= own_hi[:, None, 0])          # per axis: [rows, n] each
+               & (box_hi[None, :, 1] >= own_lo[:, None, 1]) & (box_lo[None, :, 1] <= own_hi[:, None, 1]))
+        worst = max(worst, int(np.count_nonzero(hit, axis=1).max()) - 1)      # (robot r's own box always intersects)
     return min(max(worst, 1), n - 1)
+
+
+SLOT_BOUND_CHUNK_PAIRS = 1 << 20  # framed_slot_bound: robot pairs compared at once (4 MB of comparisons a chunk)
 
 
 BIN_CELL_SLACK = 1.0625          # a cell side is at least (1 + 1/16) x the radius (csrc/guide.hip: COVER; the build is csrc/cons_tables.hip)

@@ -29,7 +29,7 @@ class GuideManagerTrajectoriesWithVelocity:
                  env_id="EnvEmpty2D", obstacle_cutoff_margin=0.05, robot_radius=ROBOT_RADIUS,
                  weight_grad_cost_collision=2e-2, weight_grad_cost_smoothness=8e-2, trajectory_duration=5.0,
                  n_support_points=64, sigma_gp=1.0, n_robots=1, robot_env_ids: Optional[Sequence[str]] = None,
-                 extra_objects_only=False, extra_objects=None, device="cuda", tensor_args=None, **kwargs):
+                 extra_objects_only=False, extra_objects=None, device="cuda", tensor_args=None, window_set=None, **kwargs):
         # GuideManager.clip_gradient (guides.py:228-259).  NB the reference class defaults to clip_grad=False; MPD / MPDEnsemble
         # construct it with clip_grad=True, rule 'norm' (mpd.py:258-265), which is the default here
         if clip_grad and clip_grad_rule not in ("norm", "value"):
@@ -45,13 +45,25 @@ class GuideManagerTrajectoriesWithVelocity:
         self.sigma_gp = sigma_gp
         # collision_margins + cutoff_margin in fp32 (distance_fields.py:117, robot_planar_disk.py:68)
         self.margin = float(np.float32(np.float32(robot_radius * 1.1) + np.float32(obstacle_cutoff_margin)))
-        env_ids = list(robot_env_ids) if robot_env_ids is not None else [env_id] * n_robots
-        self.env_id = env_ids[0]
-        maps = sorted(set(env_ids))
-        self._grids = device_sdf_textures(maps, self.device)                  # [n_maps, n_grids=1, nx, ny, 4], shared
-        self._robot_map = torch.tensor([maps.index(e) for e in env_ids], dtype=torch.int32, device=self.device)
-        self._n_maps = len(maps)
-        self._obstacle_free = not any(environments.map_has_obstacles(m) for m in maps)
+        if window_set is not None:
+            # a window set owned by the caller (map_textures.WorldWindowSet) in place of robot_env_ids: robot r reads slice r, wherever
+            # the set's windows are moved to; whether there is a grid at all is read off the world, as for a window's name
+            if robot_env_ids is not None or window_set.n != n_robots or window_set.device != environments.resolved_device(self.device):
+                raise ValueError(f"window_set: a set of {n_robots} slices on {self.device} in place of robot_env_ids, got {window_set.n} "
+                                 f"on {window_set.device}" + (" and robot_env_ids" if robot_env_ids is not None else ""))
+            self.env_id = environments.world_window_name(window_set.world, np.zeros(2, np.int64))
+            self._grids = window_set.tex
+            self._robot_map = torch.arange(n_robots, dtype=torch.int32, device=self.device)
+            self._n_maps = n_robots
+            self._obstacle_free = not environments.map_has_obstacles(self.env_id)
+        else:
+            env_ids = list(robot_env_ids) if robot_env_ids is not None else [env_id] * n_robots
+            self.env_id = env_ids[0]
+            maps = sorted(set(env_ids))
+            self._grids = device_sdf_textures(maps, self.device)              # [n_maps, n_grids=1, nx, ny, 4], shared
+            self._robot_map = torch.tensor([maps.index(e) for e in env_ids], dtype=torch.int32, device=self.device)
+            self._n_maps = len(maps)
+            self._obstacle_free = not any(environments.map_has_obstacles(m) for m in maps)
         # use_guide_on_extra_objects_only (mpd.py:216-219): the only collision field is task.get_collision_fields_extra_objects()
         # = the env's extra ObjectField (EMPTY in every shipped map: env_*_extra_objects.py MultiSphereField([]), sdf == 1;
         # `extra_objects` below otherwise) -- no fixed-object grid and no workspace walls in the guide; GP prior and

@@ -11,10 +11,12 @@ from . import _lib, environments
 _TEXTURES = {}                      # (map names, device) -> the set's resident textures [n_maps, n_grids=1, nx, ny, 4]
 _WORLD_TEXTURES = {}                # (world map, device) -> its resident texture [WX, WY, 4]
 _WINDOW_CUTS = {}                   # key of _TEXTURES -> [(world map, first slice, origins int32 [n, 2] on the device)]: its window slices
+_WINDOW_SETS = []                   # the live WorldWindowSets: window slices owned by their user, not keyed by names
 N_TEXTURE_UPLOADS = 0               # host-built textures copied to a device: 1 per map set that holds a shipped map, however many
 # Texture slices built on a device, by ONE rule: + 1 for every texture a library call writes whole.  A registered map's slice built or rebuilt
 # (mmd_sdf_grid_build / mmd_sdf_grid_from_occupancy): 1.  A world texture built or rebuilt from its bitmap (mmd_sdf_grid_from_occupancy):
-# 1.  A cut (mmd_sdf_grid_windows): 1 per window slice it writes, so n for a launch of n windows.
+# 1.  A cut (mmd_sdf_grid_windows): 1 per window slice it writes, so n for a launch of n windows; a moved cut (mmd_sdf_grid_windows_moved): 1
+# per slice whose origin changed, which the caller of WorldWindowSet.move knows on the host.
 N_TEXTURE_BUILDS = 0
 
 
@@ -96,11 +98,72 @@ def release_sdf_textures(maps, device):
     return _TEXTURES.pop(key, None) is not None
 
 
+class WorldWindowSet:
+    """n window slices of the world map `world` on one device, owned by their user: slice r is robot r's, whatever the origins (equal
+    origins do not share a slice), the set has no names, and its storage `tex` [n, n_grids=1, nx, ny, 4] and its pointers are stable
+    for its lifetime.  It holds two origin buffers on the device, this move's and the last one's, so that no launch reads and writes
+    one.  The set is registered: environments.update_world_map(world, ..) cuts every slice again in place at its CURRENT origin,
+    unregister_world_map forgets the set (it keeps its tensors), release() takes it out of the registry."""
+
+    def __init__(self, world, n, device):
+        if not environments.is_world_map(world):
+            raise ValueError(f"WorldWindowSet: {world!r} is not a registered world map")
+        if int(n) < 1:
+            raise ValueError(f"WorldWindowSet: n = {n} slices (at least 1)")
+        self.world, self.n, self.device = world, int(n), environments.resolved_device(device)
+        self.tex = torch.empty(self.n, 1, *environments.grid_shape(), 4, dtype=torch.float32, device=self.device)
+        self._origins = [torch.empty(self.n, 2, dtype=torch.int32, device=self.device) for _ in range(2)]
+        self._current = None            # which buffer holds the origins the slices were cut at; None before the first move
+        _WINDOW_SETS.append(self)
+
+    @property
+    def origins(self):
+        """int32 [n, 2] on the device: the origins the slices hold now (the set's own buffer; read only), None before the first move"""
+        return None if self._current is None else self._origins[self._current]
+
+    def _cut(self, origins, held):
+        wtex = device_world_texture(self.world, self.device)
+        _lib.launch("mmd_sdf_grid_windows_moved", self.tex, _lib.require_gpu(wtex, "world texture"), wtex.shape[0], wtex.shape[1],
+                    C.c_void_p(origins.data_ptr()), C.c_void_p(held.data_ptr()) if held is not None else None, self.n, self.tex.shape[2],
+                    self.tex.shape[3], _lib.require_gpu(self.tex, "window slices"))
+
+    def move(self, origins_dev, n_moved):
+        """Move the windows to origins_dev (int32 [n, 2], contiguous, on the set's device; each a window inside the world, which the
+        caller has checked): one device copy of the origins into the set's other buffer and one mmd_sdf_grid_windows_moved launch
+        against the buffer of the last move, on the current stream.  The first move cuts every slice.  n_moved: the slices whose
+        origin differs from the last move's (n on the first), which the caller knows on the host; N_TEXTURE_BUILDS grows by it."""
+        global N_TEXTURE_BUILDS
+        if not (isinstance(origins_dev, torch.Tensor) and origins_dev.dtype == torch.int32 and tuple(origins_dev.shape) == (self.n, 2)
+                and origins_dev.device == self.device and origins_dev.is_contiguous()):
+            raise ValueError(f"WorldWindowSet.move: origins must be a contiguous int32 tensor [{self.n}, 2] on {self.device}")
+        if not 0 <= int(n_moved) <= self.n or (self._current is None and int(n_moved) != self.n):
+            raise ValueError(f"WorldWindowSet.move: n_moved = {n_moved} of {self.n} slices (all of them on the first move)")
+        nxt = 0 if self._current is None else 1 - self._current
+        self._origins[nxt].copy_(origins_dev)
+        self._cut(self._origins[nxt], self.origins)
+        self._current = nxt
+        N_TEXTURE_BUILDS += int(n_moved)
+
+    def recut(self):
+        """update_world_map: every slice again from the world's texture at its current origin, in place.  Nothing before the first move."""
+        global N_TEXTURE_BUILDS
+        if self._current is not None:
+            with torch.cuda.device(self.device):
+                self._cut(self.origins, None)
+            N_TEXTURE_BUILDS += self.n
+
+    def release(self):
+        """Take the set out of the registry: update_world_map no longer reaches it.  -> whether it was registered."""
+        live = any(s is self for s in _WINDOW_SETS)
+        _WINDOW_SETS[:] = [s for s in _WINDOW_SETS if s is not self]
+        return live
+
+
 def rebuild_resident_textures(name, device_occupancy=None):
     """environments.update_*: whatever resident texture holds the registered name is rebuilt in place -- same storage, same pointers -- on
     the current stream of its device.  A tile map: every slice of the name, by the builder of its kind; device_occupancy is the new
     bitmap as a device tensor, used as it is for the slices on its device.  A world map: every resident world texture from the registry's
-    bitmap, then every window slice cut from it again, one launch per (map set, run of its windows).  Counted 1 per slice and world texture."""
+    bitmap, then every window slice cut from it again, one launch per (map set, run of its windows), and every WorldWindowSet of the world at its current origins.  Counted 1 per slice and world texture."""
     global N_TEXTURE_BUILDS
     for (world, _), wtex in _WORLD_TEXTURES.items():
         if world == name:
@@ -118,13 +181,18 @@ def rebuild_resident_textures(name, device_occupancy=None):
                 N_TEXTURE_BUILDS += 1
         if key in _WINDOW_CUTS:
             _cut_windows(tex, [c for c in _WINDOW_CUTS[key] if c[0] == name])
+    for ws in _WINDOW_SETS:
+        if ws.world == name:
+            ws.recut()
 
 
 def drop_resident_textures(name):
     """environments.unregister_*, called while the name still resolves: forget the resident textures of the world map `name` and every map
-    set that holds the tile map `name` or a window of the world map `name` (an object built on one keeps its tensor)."""
+    set that holds the tile map `name` or a window of the world map `name`, and every WorldWindowSet of the world map `name` (an object
+    built on one keeps its tensor)."""
     for key in [k for k in _WORLD_TEXTURES if k[0] == name]:
         del _WORLD_TEXTURES[key]
     for key in [k for k in _TEXTURES if any(environments.resolve_map(m, unknown_ok=True)[1] == name for m in k[0])]:
         del _TEXTURES[key]
         _WINDOW_CUTS.pop(key, None)
+    _WINDOW_SETS[:] = [ws for ws in _WINDOW_SETS if ws.world != name]

@@ -108,7 +108,8 @@ class MultiRobotSampler:
         self.dataset = TrajectoryDatasetFacade(norm_mins, norm_maxs)
         self.env_id = env_id
         self.guide = GuideManagerTrajectoriesWithVelocity(self.dataset, env_id=env_id, n_robots=self.n_local,
-                                                          robot_env_ids=self._robot_env_ids(self.robot0, self.n_local), device=device)
+                                                          robot_env_ids=self._robot_env_ids(self.robot0, self.n_local), device=device,
+                                                          window_set=self._robot_window_set())
         self._subset_guides = {}        # replan_round: a guide per subset size, on the same map (the resident SDF texture is shared)
         sl = slice(self.robot0, self.robot0 + self.n_local)
         self._ends = (starts[sl], goals[sl])      # plan(): the straight lines the first round starts from
@@ -136,6 +137,10 @@ class MultiRobotSampler:
     # ---- _robot_env_ids where its robots read maps of their own
     def _robot_env_ids(self, robot0, n):
         """hook: the map names of robots [robot0, robot0 + n) for a guide's robot_env_ids, or None: every robot on the sampler's env_id"""
+        return None
+
+    def _robot_window_set(self):
+        """hook: a window set of the local robots' own (map_textures.WorldWindowSet) for the guide, in place of map names, or None"""
         return None
 
     def _build_collision_table(self, paths, robot0, n):

@@ -19,7 +19,7 @@ import torch
 from . import synth
 from .constraints import (BIN_CELL_SLACK, VERTEX_CONSTRAINT_RADIUS, binned_collision_table, framed_constraints_from_paths,
                           framed_slot_bound)
-from . import environments
+from . import environments, map_textures
 from .environments import LIMITS, map_has_obstacles, map_sdf
 from .multi_robot import D, H, MultiRobotSampler, shard_range
 
@@ -52,6 +52,33 @@ def world_grid(limits, radius):
     return tuple(n)
 
 
+def _checked_ends(starts, goals, offsets, lo, hi):
+    """(starts, goals, offsets, local starts, local goals), float32 [N, 2] on the host: the one validation of WorldRobotSampler's
+    constructor and of its move; lo, hi: the normaliser's position limits"""
+    starts, goals, offsets = _f32(starts, "starts"), _f32(goals, "goals"), _f32(offsets, "offsets")
+    n = starts.shape[0]
+    if goals.shape[0] != n or offsets.shape[0] != n:
+        raise ValueError(f"WorldRobotSampler: {n} starts, {goals.shape[0]} goals, {offsets.shape[0]} offsets")
+    local_starts, local_goals = starts - offsets, goals - offsets                      # one fp32 subtraction per axis
+    for name, p in (("start", local_starts), ("goal", local_goals)):
+        bad = np.flatnonzero(~np.all((p >= lo) & (p <= hi), axis=1))
+        if bad.size:
+            r = int(bad[0])
+            raise ValueError(f"WorldRobotSampler: the {name} of robot {r} is {p[r].tolist()} in its own frame, outside the normaliser's "
+                             f"limits {lo.tolist()} .. {hi.tolist()}")
+    return starts, goals, offsets, local_starts, local_goals
+
+
+def _checked_slots(neighbor_slots, offsets, robot0, n_local, radius):
+    """neighbor_slots for the host offsets [N, 2]: what the constructor was given, else (None) constraints.framed_slot_bound of them"""
+    n = offsets.shape[0]
+    if neighbor_slots is None:
+        neighbor_slots = framed_slot_bound(offsets, robot0, n_local, LIMITS, radius) if n >= 2 else 1
+    if n >= 2 and not 1 <= int(neighbor_slots) <= n - 1:
+        raise ValueError(f"WorldRobotSampler: neighbor_slots must be in [1, {n - 1}], got {neighbor_slots}")
+    return neighbor_slots
+
+
 class WorldRobotSampler(MultiRobotSampler):
     """MultiRobotSampler for robots that each plan in the model's tile frame at their own offset in a global frame.  starts, goals [N, 2],
     the paths plan_round / plan take and return and PlanResult.paths_local are GLOBAL; offsets [N, 2] (every rank holds all of them);
@@ -60,7 +87,9 @@ class WorldRobotSampler(MultiRobotSampler):
     counts the pick's collisions over all pairs; "binned" reads them, and plan()'s report, off a collision cell table over the world's
     limits.  The guided step reads the framed all-pairs table either way.  env_id may name a world map (environments.register_world_map):
     robot r's map is then the window of the world's texture at offsets[r], which must lie on the world's cell grid and inside the world
-    (environments.snap_to_world_map); robots at equal offsets share a resident slice.  Starts and goals inside an obstacle are not refused.
+    (environments.snap_to_world_map); robots at equal offsets share a resident slice.  own_windows=True (a world map only; a tile map ignores it)
+    gives the sampler a window set of its own instead (map_textures.WorldWindowSet: slice r is local robot r's, storage and pointers
+    stable), which `move` moves in place; release_windows() takes it out of the registry when the sampler is done with.  Starts and goals inside an obstacle are not refused.
     After every set_other_paths, `last_used` / `last_dropped` (int32 [n_local], on the device) tell the most slots a robot filled at one time step and the included points that found its block
     full.  `window` (an attribute, None = the default) is the culling window; a measurement may open it to compare with the all-pairs form.
     plan_rounds(repair=True), plan_rounds_subset(replan != "all") and replan_round are refused: the round table of repair has no frames, and
@@ -69,35 +98,34 @@ class WorldRobotSampler(MultiRobotSampler):
     def __init__(self, model, starts, goals, offsets, env_id="EnvEmpty2D", n_samples=64, rank=0, world_size=1,
                  norm_mins=synth.NORM_MINS, norm_maxs=synth.NORM_MAXS, n_guide_steps=20, start_guide_steps_fraction=0.5,
                  n_diffusion_steps_without_noise=1, weight_grad_cost_soft_constraints=2e-2, radius=VERTEX_CONSTRAINT_RADIUS,
-                 device="cuda", group=None, n_streams=0, inter_robot=True, constraint_table="dense", neighbor_slots=None):
-        starts, goals, offsets = _f32(starts, "starts"), _f32(goals, "goals"), _f32(offsets, "offsets")
+                 device="cuda", group=None, n_streams=0, inter_robot=True, constraint_table="dense", own_windows=False, neighbor_slots=None):
+        self._limits = (np.asarray(norm_mins, np.float32)[:2], np.asarray(norm_maxs, np.float32)[:2])
+        self._fixed_slots = neighbor_slots               # what `move` keeps; None: the bound of every move's offsets
+        starts, goals, offsets, local_starts, local_goals = _checked_ends(starts, goals, offsets, *self._limits)
         n = starts.shape[0]
-        if goals.shape[0] != n or offsets.shape[0] != n:
-            raise ValueError(f"WorldRobotSampler: {n} starts, {goals.shape[0]} goals, {offsets.shape[0]} offsets")
-        local_starts, local_goals = starts - offsets, goals - offsets                      # one fp32 subtraction per axis
-        lo, hi = np.asarray(norm_mins, np.float32)[:2], np.asarray(norm_maxs, np.float32)[:2]
-        for name, p in (("start", local_starts), ("goal", local_goals)):
-            bad = np.flatnonzero(~np.all((p >= lo) & (p <= hi), axis=1))
-            if bad.size:
-                r = int(bad[0])
-                raise ValueError(f"WorldRobotSampler: the {name} of robot {r} is {p[r].tolist()} in its own frame, outside the normaliser's "
-                                 f"limits {lo.tolist()} .. {hi.tolist()}")
         robot0, n_local = shard_range(n, rank, world_size)
-        if neighbor_slots is None:
-            neighbor_slots = framed_slot_bound(offsets, robot0, n_local, LIMITS, radius) if n >= 2 else 1
-        if n >= 2 and not 1 <= int(neighbor_slots) <= n - 1:
-            raise ValueError(f"WorldRobotSampler: neighbor_slots must be in [1, {n - 1}], got {neighbor_slots}")
+        neighbor_slots = _checked_slots(neighbor_slots, offsets, robot0, n_local, radius)
         # a world map: every robot reads its own window of it; offsets off the cell grid or outside the world raise here, before any device work
-        self._window_ids = None
+        self._window_ids = self._windows = self._held_origins = None
         if environments.is_world_map(env_id):
-            self._window_ids = [environments.world_window_name(env_id, org)
-                                for org in environments.world_map_window_origins(env_id, offsets)]
-        super().__init__(model, local_starts, local_goals, env_id=env_id, n_samples=n_samples, rank=rank, world_size=world_size,
-                         norm_mins=norm_mins, norm_maxs=norm_maxs, n_guide_steps=n_guide_steps,
-                         start_guide_steps_fraction=start_guide_steps_fraction,
-                         n_diffusion_steps_without_noise=n_diffusion_steps_without_noise,
-                         weight_grad_cost_soft_constraints=weight_grad_cost_soft_constraints, radius=radius, device=device, group=group,
-                         n_streams=n_streams, inter_robot=inter_robot, constraint_table=constraint_table)
+            origins = environments.world_map_window_origins(env_id, offsets)
+            if own_windows:
+                # a window set of this sampler's own (slice r is local robot r's), which `move` moves in place
+                self._windows = map_textures.WorldWindowSet(env_id, n_local, device)
+            else:
+                self._window_ids = [environments.world_window_name(env_id, org) for org in origins]
+        try:
+            super().__init__(model, local_starts, local_goals, env_id=env_id, n_samples=n_samples, rank=rank, world_size=world_size,
+                             norm_mins=norm_mins, norm_maxs=norm_maxs, n_guide_steps=n_guide_steps,
+                             start_guide_steps_fraction=start_guide_steps_fraction,
+                             n_diffusion_steps_without_noise=n_diffusion_steps_without_noise,
+                             weight_grad_cost_soft_constraints=weight_grad_cost_soft_constraints, radius=radius, device=device, group=group,
+                             n_streams=n_streams, inter_robot=inter_robot, constraint_table=constraint_table)
+            if self._windows is not None:
+                self._move_windows(origins[self.robot0:self.robot0 + self.n_local])
+        except BaseException:
+            WorldRobotSampler.release_windows(self)      # (a set registered for a sampler that was never built)
+            raise
         sl = slice(self.robot0, self.robot0 + self.n_local)
         self._ends = (starts[sl], goals[sl])             # plan(): the straight lines of the GLOBAL ends
         self.neighbor_slots = int(neighbor_slots)
@@ -106,6 +134,75 @@ class WorldRobotSampler(MultiRobotSampler):
         self.world_grid = world_grid(self.world_limits, radius)
         self.window = None              # the culling window in a robot's frame; None: constraints.framed_window(LIMITS, radius)
         self.last_used = self.last_dropped = None
+
+    # ---- one sampler for many sets of ends: the state a constructor takes from (starts, goals, offsets), set again in place ----------------
+    def move(self, starts, goals, offsets):
+        """Give the sampler the state a freshly constructed one would have for these starts, goals and offsets [N, 2] (N as constructed),
+        with the constructor's validation and messages: the hard conditions, the ends of plan()'s straight lines, `offsets`,
+        `world_limits`, `world_grid` and `neighbor_slots` (recomputed unless the constructor was given one).  On a world map the
+        sampler must own its windows (own_windows=True): they are moved in place on the device, and only the slices whose origin
+        changed are cut again; a sampler on the shared named set raises ValueError.  On a tile map any sampler moves.  `move` then
+        `plan*` is the fresh sampler's `plan*`, bit for bit.  Everything is validated before anything is changed."""
+        if self._window_ids is not None:
+            raise ValueError(f"WorldRobotSampler.move: the sampler reads the shared named windows of the world map {self.env_id!r}; "
+                             "construct it with own_windows=True to move it")
+        starts, goals, offsets, local_starts, local_goals = _checked_ends(starts, goals, offsets, *self._limits)
+        if starts.shape[0] != self.n_robots:
+            raise ValueError(f"WorldRobotSampler.move: {starts.shape[0]} robots given to a sampler of {self.n_robots}")
+        neighbor_slots = _checked_slots(self._fixed_slots, offsets, self.robot0, self.n_local, self.radius)
+        limits = world_limits(offsets)
+        grid = world_grid(limits, self.radius)
+        sl = slice(self.robot0, self.robot0 + self.n_local)
+        origins = environments.world_map_window_origins(self.env_id, offsets)[sl] if self._windows is not None else None
+        st, go = torch.from_numpy(local_starts[sl]), torch.from_numpy(local_goals[sl])
+        z = torch.zeros_like(st)
+        nz = self.dataset.normalizer
+        self.hard_conds = {0: nz.normalize(torch.cat((st, z), -1)).to(self.device), H - 1: nz.normalize(torch.cat((go, z), -1)).to(self.device)}
+        self._set_frames((starts[sl], goals[sl]), torch.from_numpy(offsets).to(self.device), neighbor_slots, limits, grid)
+        if origins is not None:
+            self._move_windows(origins)
+
+    def _move_on_device(self, ends, offsets_host, origins_host, offsets_dev, hard_first_dev, hard_last_dev, origins_dev=None):
+        """`move` for a caller that has the state on the device already (world_fleet.WorldFleet, from mmd_fleet_epoch_frames): the host
+        ends (starts, goals) of plan()'s lines, the host offsets [N, 2] (for the slot bound and the world's limits) and origins [N, 2],
+        and on the sampler's device the offsets float32 [N, 2], the normalised hard conditions float32 [n_local, 4] of rows 0 and 63
+        and, on a world map, the origins int32 [n_local, 2].  One process (n_local == N).  The in-limits check is not made: the caller
+        has proved it (a fleet's targets: world_fleet's CONTAINMENT).  Nothing is uploaded."""
+        neighbor_slots = _checked_slots(self._fixed_slots, offsets_host, self.robot0, self.n_local, self.radius)
+        limits = world_limits(offsets_host)
+        grid = world_grid(limits, self.radius)
+        self.hard_conds = {0: hard_first_dev, H - 1: hard_last_dev}
+        self._set_frames(ends, offsets_dev, neighbor_slots, limits, grid)
+        if self._windows is not None:
+            self._move_windows(origins_host, origins_dev)
+
+    def _set_frames(self, ends, offsets_dev, neighbor_slots, limits, grid):
+        self._ends = ends
+        self.neighbor_slots = int(neighbor_slots)
+        self.offsets = offsets_dev
+        self.world_limits, self.world_grid = limits, grid
+        self._collision = None
+        self.last_used = self.last_dropped = None
+
+    def _move_windows(self, origins_host, origins_dev=None):
+        """Move the sampler's own window set to the local robots' origins (int32 [n_local, 2] on the host; origins_dev: the same words on
+        the device where the caller has them).  The slices that move are counted on the host, against the origins of the last move."""
+        origins_host = np.ascontiguousarray(origins_host, dtype=np.int32)
+        if origins_dev is None:
+            origins_dev = torch.from_numpy(origins_host).to(self._windows.device)
+        held = self._held_origins
+        n_moved = self.n_local if held is None else int((origins_host != held).any(1).sum())
+        self._windows.move(origins_dev, n_moved)
+        self._held_origins = origins_host.copy()
+
+    def release_windows(self):
+        """Take the sampler's own window set (own_windows=True) out of map_textures' registry: update_world_map no longer reaches it.
+        The sampler keeps its tensors and still plans.  Nothing on a sampler without a set of its own."""
+        if self._windows is not None:
+            self._windows.release()
+
+    def _robot_window_set(self):
+        return self._windows
 
     # ---- the three places where the frame enters a round: MultiRobotSampler's hooks -------------------------------------------------------
     def _robot_env_ids(self, robot0, n):

@@ -83,7 +83,7 @@ from typing import NamedTuple
 import numpy as np
 import torch
 
-from . import _lib, environments, map_textures
+from . import _lib, environments, map_textures, synth
 from .world import OBSTACLE_MARGIN, WorldRobotSampler
 from .world_routes import (ROUTE_OK, ROUTE_OUTSIDE, ROUTE_STUCK, ROUTE_UNREACHED, SEED_POINTS, UNREACHED, _int32_dev, _points, cell_centres,
                            device_distance_field, sample_offsets, seed_trajectory, world_cells)
@@ -390,6 +390,42 @@ def device_window_seeds(tex_dev, lo, hi, samples, origins, summary, window, star
     return seeds, clear_min
 
 
+def device_epoch_frames(name, words, points, goal_points, norm_mins=synth.NORM_MINS, norm_maxs=synth.NORM_MAXS, line_a=None):
+    """(offsets float32 [n, 2], sub-goal points [n, 2], hard conditions [n, 4] of row 0 and of row 63, straight lines [n, 64, 2]), views
+    of one tensor on the words' device: everything a WorldRobotSampler's state takes from an epoch's targets on the world map `name`,
+    in one launch (mmd_fleet_epoch_frames) and bit for bit what the host gives -- environments.world_map_window_offsets of the
+    origins; world_routes.cell_centres of the cells, or goal_points[r] where summary[r, 3] == 1; the constructor's normalised
+    (point - offset, 0, 0) of `points` and of the sub-goal points; synth.straight_line_paths(points, sub-goal points).
+    words: int32 [8 n] on the device, a sub-goal launch's (cells, origins, summary) in _split_words' layout -- any words: nothing is
+    indexed by them, and nothing is validated (WorldFleet has refused a robot whose status is not ROUTE_OK before this).  points:
+    float32 on that device, [n, 2] in rows of any even stride (the last points paths[:, -1] of paths [n, 64, 2] are taken as they
+    lie); goal_points float32 [n, 2], contiguous, on that device.  The constants the host definitions compute once are computed
+    here by those same expressions; line_a: numpy.linspace(0, 1, 64, dtype=float32) on the device, uploaded here if not given."""
+    if not (isinstance(words, torch.Tensor) and words.dtype == torch.int32 and words.is_cuda and words.dim() == 1 and words.is_contiguous()
+            and words.shape[0] >= 8 and words.shape[0] % 8 == 0):
+        raise ValueError("device_epoch_frames: words must be a contiguous int32 CUDA(HIP) tensor [8 n], n >= 1, as a sub-goal launch leaves it")
+    n, dev = words.shape[0] // 8, words.device
+    ok = lambda t: isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.device == dev and tuple(t.shape) == (n, 2)     # noqa: E731
+    if not (ok(points) and points.stride(1) == 1 and points.stride(0) >= 2 and points.stride(0) % 2 == 0
+            and points.data_ptr() % 8 == 0 and ok(goal_points) and goal_points.is_contiguous()):
+        raise ValueError(f"device_epoch_frames: points (rows of an even stride) and goal_points (contiguous), float32 [{n}, 2] on {dev}")
+    if line_a is None:
+        line_a = torch.from_numpy(np.linspace(0.0, 1.0, SEED_POINTS, dtype=np.float32)).to(dev)
+    lo, hi = (np.asarray(v, np.float32) for v in environments.world_map_limits(name))
+    pitch = np.abs(hi - lo) / np.asarray(environments.world_map_occupancy(name).shape[:2], np.float32)        # cell_centres' pitch
+    mins, maxs = np.asarray(norm_mins, np.float32), np.asarray(norm_maxs, np.float32)
+    out = torch.empty(140 * n, dtype=torch.float32, device=dev)       # offsets 2 n, points 2 n, hard 4 n + 4 n, lines 128 n
+    at = lambda k: C.c_void_p(out.data_ptr() + 4 * k)                 # noqa: E731
+    word = lambda k: C.c_void_p(words.data_ptr() + 4 * k)             # noqa: E731
+    _lib.launch("mmd_fleet_epoch_frames", words, word(0), word(2 * n), word(4 * n), C.c_void_p(points.data_ptr()), int(points.stride(0)),
+                C.c_void_p(goal_points.data_ptr()), n,
+                (C.c_double * 5)(environments.SDF_CELL_SIZE, *map(float, environments.world_map_origin(name)), *map(float, environments.LIMITS[0])),
+                (C.c_float * 4)(*map(float, lo), *map(float, pitch)), (C.c_float * 4)(*map(float, mins)), (C.c_float * 4)(*map(float, maxs - mins)),
+                C.c_void_p(line_a.data_ptr()), at(0), at(2 * n), at(4 * n), at(8 * n), at(12 * n))
+    return (out[:2 * n].view(n, 2), out[2 * n:4 * n].view(n, 2), out[4 * n:8 * n].view(n, 4), out[8 * n:12 * n].view(n, 4),
+            out[12 * n:].view(n, SEED_POINTS, 2))
+
+
 def _subgoals_apart_words(dist_dev, starts, fields, goals, reach, max_steps, sep, window, sweeps, with_samples, what="device_subgoals_apart"):
     """device_subgoals_apart's launches -> (one int32 tensor [10 n + 1] on the device: cells [n, 2], origins [n, 2], summary [n, 4],
     extra [n, 2], changed [1]; its last copy on the host, numpy; samples int32 [n, 64, 2] on the device or None; the sweeps run)"""
@@ -498,15 +534,24 @@ class WorldFleet:
     "stalled"; run(max_epochs=None) loops until every robot has arrived or an epoch is stalled (no robot moves, every k is 0: the
     state would repeat for good), which terminates although epoch_bound no longer holds; an explicit max_epochs still caps it.
 
-    Out of scope here: an arrived robot is sampled like any other, between two ends pinned to its goal point, not held still; every
-    epoch builds a sampler of its own, the windows of one long-lived sampler are not moved in place; the fleet is not sharded over ranks;
+    persistent=False (the default) runs exactly the code path without the option: every epoch builds a WorldRobotSampler, a guide and a
+    named window set of its own and releases the set afterwards.  persistent=True keeps ONE sampler (own_windows=True), one guide and
+    one window set [N, 1, 400, 400, 4] (slice r is robot r's) for the whole run and moves them between epochs on the device
+    (_step_persistent): every result -- paths, conflict counts, summaries, offsets, clear_min -- is the default's bit for bit, with
+    seed_epochs and separation as well; only the time and the memory traffic differ.  close() releases the set, and run()
+    closes when it returns; a neighbor_slots= smaller than some epoch needs is refused by the sampler's own message, in that epoch.
+
+    Out of scope here: an arrived robot is sampled like any other, between two ends pinned to its goal point, not held still; the fleet is not sharded over ranks;
     repair= and replan=, which WorldRobotSampler refuses; with separation=, a stalled fleet is reported, not resolved (the priorities are
     the robots' indices and never rotate, and no robot steps aside), and without it two sub-goals may coincide.  Whether a seeded epoch resolves conflicts as well as one from noise is not
     known."""
 
     def __init__(self, model, name, starts, goals, clearance=OBSTACLE_MARGIN, reach=180, max_steps=360, device="cuda", seed_epochs=False,
-                 smooth_iters=64, n_noising_steps=3, n_denoising_steps=3, separation=None, **world_robot_sampler_kwargs):
+                 smooth_iters=64, n_noising_steps=3, n_denoising_steps=3, separation=None, persistent=False,
+                 **world_robot_sampler_kwargs):
         self.model, self.name, self.device = model, name, environments.resolved_device(device)
+        self.persistent = bool(persistent)
+        self._sampler = self._points_dev = self._points_host = self._goal_points_dev = self._line_a = self._epoch_words = None
         self.separation = None if separation is None else _checked_sep("WorldFleet: separation", separation)
         self.clearance = float(clearance)
         self.seed_epochs = bool(seed_epochs)
@@ -592,6 +637,7 @@ class WorldFleet:
             words, samples = _window_goals_words(self.dist, c0, self._fields_dev, self._goals_dev, self.reach, self.max_steps, self.window, True)
         else:
             words, samples = _window_goals_words(self.dist, c0, self._fields_dev, self._goals_dev, self.reach, self.max_steps, self.window), None
+        self._epoch_words = words                            # (persistent: the frames launch reads them where they are)
         cells, origins, summary = (a.copy() for a in _split_words(words.cpu().numpy()))
         return self._targets(c0, cells, origins, summary, samples, words if self.seed_epochs else None)
 
@@ -613,6 +659,7 @@ class WorldFleet:
         stay on the device) in place of mmd_grid_window_goals; the summary is (k, d0 - k, status, arrived)"""
         words, host, samples, run = _subgoals_apart_words(self.dist, c0, self._fields_dev, self._goals_dev, self.reach, self.max_steps,
                                                           self.separation, self.window, 4, self.seed_epochs, "WorldFleet")
+        self._epoch_words = words[:8 * self.n_robots]
         cells, origins, summary, extra = (a.copy() for a in _split_apart_words(host))
         return self._targets(c0, cells, origins, summary, samples, words[:8 * self.n_robots] if self.seed_epochs else None, extra, run)
 
@@ -621,7 +668,10 @@ class WorldFleet:
         its plan(max_rounds, seed) -- with seed_epochs its plan_rounds_seeded from the epoch's seeds (the class's docstring) --, and the robots
         moved to the last points of the returned paths, as they are.  The epoch's window map set is released afterwards
         (map_textures.release_sdf_textures).  -> (PlanResult, EpochTargets); with seed_epochs `last_clear_min` (float32 [N]) holds the
-        seeds' least texel values, from the copy that brings the new positions back."""
+        seeds' least texel values, from the copy that brings the new positions back.
+        With persistent=True: the same epoch, bit for bit, on the fleet's one sampler (_step_persistent); nothing is released."""
+        if self.persistent:
+            return self._step_persistent(seed, max_rounds)
         targets = self.epoch_targets(self.positions)
         sampler = WorldRobotSampler(self.model, self.positions, targets.points, targets.offsets, env_id=self.name, device=self.device,
                                     **self.sampler_kwargs)
@@ -645,6 +695,53 @@ class WorldFleet:
             self.positions = np.ascontiguousarray(res.paths_local[:, -1, :].cpu().numpy(), dtype=np.float32)
         return res, targets
 
+    def _step_persistent(self, seed, max_rounds):
+        """step() on the one long-lived sampler.  epoch_targets as ever (its one copy back gives the status check, the host origins,
+        the offsets and the slot bound); then one mmd_fleet_epoch_frames launch on the launch's words, the robots' points and their
+        goal points, all on the device, and the sampler moved to what it wrote (WorldRobotSampler._move_on_device: one
+        mmd_sdf_grid_windows_moved launch, which cuts only the slices whose origin changed).  The first epoch builds the sampler
+        with own_windows=True first; its windows then do not move.  No sampler, guide or facade is built, no texture allocated, no
+        window named, no hard condition, offset or line uploaded.  The robots' points of the next epoch are the device slice
+        paths_local[:, -1]; the host copy feeds world_cells and its refusals, as ever."""
+        targets = self.epoch_targets(self.positions)
+        if self._goal_points_dev is None:
+            self._goal_points_dev = torch.from_numpy(self.goal_points).to(self.device)
+            self._line_a = torch.from_numpy(np.linspace(0.0, 1.0, SEED_POINTS, dtype=np.float32)).to(self.device)
+        if self._points_host is not self.positions:          # the first epoch, or positions set by the caller: the only upload of points
+            self._points_dev = torch.from_numpy(np.ascontiguousarray(self.positions, dtype=np.float32).reshape(-1, 2)).to(self.device)
+        if self._sampler is None:
+            self._sampler = WorldRobotSampler(self.model, self.positions, targets.points, targets.offsets, env_id=self.name,
+                                              device=self.device, own_windows=True, **self.sampler_kwargs)
+        sampler, words = self._sampler, self._epoch_words
+        kw = {k: self.sampler_kwargs[k] for k in ("norm_mins", "norm_maxs") if k in self.sampler_kwargs}
+        offsets_dev, points_dev, hard_first, hard_last, lines = device_epoch_frames(self.name, words, self._points_dev, self._goal_points_dev,
+                                                                                   line_a=self._line_a, **kw)
+        _, origins_dev, summary_dev = _split_words(words)
+        sampler._move_on_device((self.positions, targets.points), targets.offsets, targets.origins, offsets_dev, hard_first, hard_last,
+                                origins_dev)
+        if self.seed_epochs:
+            seeds, clear_min = device_window_seeds(map_textures.device_world_texture(self.name, self.device), self.limits[0], self.limits[1],
+                                                   targets.samples, origins_dev, summary_dev, self.window, self._points_dev, points_dev,
+                                                   self.clearance, self.smooth_iters)
+            res = sampler.plan_rounds_seeded(sampler.trajs_from_global(seeds), paths_local=seeds[..., :2].contiguous(),
+                                             local_rounds=True, n_noising_steps=self.n_noising_steps,
+                                             n_denoising_steps=self.n_denoising_steps, max_rounds=max_rounds, seed=seed)
+            back = torch.cat([res.paths_local[:, -1, :], clear_min[:, None]], dim=1).cpu().numpy()       # one copy: the ends and clear_min
+            self.positions, self.last_clear_min = np.ascontiguousarray(back[:, :2], dtype=np.float32), back[:, 2].copy()
+        else:
+            res = sampler.plan_rounds(paths_local=lines, max_rounds=max_rounds, seed=seed)
+            self.positions = np.ascontiguousarray(res.paths_local[:, -1, :].cpu().numpy(), dtype=np.float32)
+        self._points_dev, self._points_host = res.paths_local[:, -1, :], self.positions
+        return res, targets
+
+    def close(self):
+        """persistent=True: release the sampler's window set (update_world_map no longer reaches it) and drop the sampler; the next
+        step builds another.  Nothing otherwise.  run() closes when it returns, also on an exception."""
+        sampler, self._sampler = self._sampler, None
+        self._points_dev = self._points_host = None
+        if sampler is not None:
+            sampler.release_windows()
+
     def run(self, max_epochs=None, max_rounds=8, seed=0):
         """Epochs (epoch e with seed + e) until every robot has arrived, at most max_epochs of them (None: epoch_bound(), which suffices
         from the starts).  A robot that has arrived keeps taking part, from its goal point to its goal point, so that the others stay
@@ -653,8 +750,14 @@ class WorldFleet:
             max_epochs = self.epoch_bound() if self.separation is None else None
         elif int(max_epochs) < 1:
             raise ValueError(f"WorldFleet.run: max_epochs = {max_epochs} (at least 1)")
-        if self.separation is not None:
-            return self._run_apart(max_epochs, max_rounds, seed)
+        try:
+            if self.separation is not None:
+                return self._run_apart(max_epochs, max_rounds, seed)
+            return self._run_plain(max_epochs, max_rounds, seed)
+        finally:
+            self.close()
+
+    def _run_plain(self, max_epochs, max_rounds, seed):
         paths, epochs = [], []
         arrived = np.zeros(self.n_robots, bool)
         for e in range(int(max_epochs)):

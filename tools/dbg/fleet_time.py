@@ -1,6 +1,6 @@
 """What an epoch of a world fleet costs on the device, needs one GPU (run it under `timeout`; one process):
 
-    python tools/dbg/fleet_time.py [--apart] [OUT.txt]
+    python tools/dbg/fleet_time.py [--apart | --persistent] [OUT.txt]
 
 The world is world_route_time.py's: 2048 x 2048 cells, 300 random boxes, clearance world.OBSTACLE_MARGIN.  With N = 64 and N = 256 robots,
 starts and distinct goals drawn from the cells that one routable cell reaches, random-init weights, T = 25, B = 4 samples per robot,
@@ -28,6 +28,16 @@ protocol:
 The timing fleet's starts are random cells, drawn with no regard to one another, so the leg switches the separation on behind the
 constructor's refusal; starts in conflict only give clear = 0.  Before the leg is timed: every robot that was not held back has the plain
 targets' words, and every k lies in [0, walked].  --apart runs the field build, the plain sub-goals and this leg only.
+--persistent times what an epoch pays before it plans, for the fleet's default and for WorldFleet(persistent=True), the two legs
+alternating inside every pass on the same fleet and the same epoch's targets (1 warm-up pass, the median of 5):
+  sampler + window cut   the default's: a WorldRobotSampler built on the epoch's named windows, the map set of the pass before released;
+  persistent setup       one mmd_fleet_epoch_frames launch, one mmd_sdf_grid_windows_moved launch and the sampler's internal move, with
+                         its slot bound (constraints.framed_slot_bound), on ONE sampler built with own_windows=True before the passes.
+                         Before every timed call the sampler's windows are parked, untimed, one cell away from the epoch's origins, so
+                         that the timed move cuts every slice; a third leg parks only the second half of the robots, as if the first half
+                         had arrived and stood still: the timed move then cuts N / 2 slices.
+Before these are timed: after a setup, every robot's slice, offsets and hard conditions are a fresh named sampler's, bit for bit.  It runs
+the field build and these legs only, and leaves out the comparisons with the numpy definitions below (the other modes make them).
 Before anything is timed: the field of robot 0's goal is compared with the numpy definition, and the sub-goals of every 8th robot with
 window_goals on the downloaded fields, integer for integer.  Per repeated figure: 1 warm-up pass, then the median of 5 passes.  'gpu ms'
 = HIP events around the pass on the current stream, 'wall ms' = perf_counter around the pass with a device synchronisation at both ends.
@@ -53,12 +63,15 @@ from world_route_time import LINES, random_world, say, timed                    
 T, B, ROUNDS, SEED = 25, 4, 2, 7
 
 
-def alternating(fns, passes=5, warmup=1):
-    """[(median gpu ms, median wall ms)] of every fn, the fns run one after the other inside every pass"""
+def alternating(fns, passes=5, warmup=1, preps=None):
+    """[(median gpu ms, median wall ms)] of every fn, the fns run one after the other inside every pass; preps[i], where given, runs
+    before fn i, untimed"""
     import statistics
     gpu, wall = [[] for _ in fns], [[] for _ in fns]
     for k in range(warmup + passes):
         for i, fn in enumerate(fns):
+            if preps is not None and preps[i] is not None:
+                preps[i]()
             torch.cuda.synchronize()
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             t0 = time.perf_counter()
@@ -126,10 +139,54 @@ def apart_leg(fleet, n):
         f"conflict); longest walk {int(walked.max())} cells")
 
 
+def persistent_leg(fleet, model, targets, n):
+    """the default's per-epoch set-up next to the persistent one of the same fleet and epoch (the module's docstring)"""
+    words = fleet._epoch_words
+    _, origins_dev, _ = F._split_words(words)
+    points_dev, goals_dev = torch.from_numpy(fleet.positions).cuda(), torch.from_numpy(fleet.goal_points).cuda()
+    line_a = torch.from_numpy(np.linspace(0.0, 1.0, 64, dtype=np.float32)).cuda()
+    ends = (fleet.positions, targets.points)
+    origins = targets.origins.astype(np.int32)
+    away = np.where(origins[:, :1] > 0, origins - np.int32([1, 0]), origins + np.int32([1, 0])).astype(np.int32)     # one cell off, in the world
+    half = away.copy()
+    half[:n // 2] = origins[:n // 2]
+    sampler = WorldRobotSampler(model, fleet.positions, targets.points, targets.offsets, env_id="Timed", n_samples=B, own_windows=True)
+    made = []
+
+    def construct():
+        for s in made:
+            map_textures.release_sdf_textures(sorted(set(s._window_ids)), "cuda")
+        made[:] = [WorldRobotSampler(model, fleet.positions, targets.points, targets.offsets, env_id="Timed", n_samples=B)]
+
+    def setup():
+        offsets_dev, _, hard_first, hard_last, _ = F.device_epoch_frames("Timed", words, points_dev, goals_dev, line_a=line_a)
+        sampler._move_on_device(ends, targets.offsets, origins, offsets_dev, hard_first, hard_last, origins_dev)
+    builds = []
+    for parked in (away, half):
+        sampler._move_windows(parked)
+        before = map_textures.N_TEXTURE_BUILDS
+        setup()
+        builds.append(map_textures.N_TEXTURE_BUILDS - before)
+    construct()
+    fresh = made[0]
+    same = lambda a, b: bool((a.contiguous().view(torch.int32) == b.contiguous().view(torch.int32)).all())        # noqa: E731
+    assert same(sampler.guide._grids[:, 0], fresh.guide._grids[fresh.guide._robot_map.long(), 0]), "a moved slice is not the named one"
+    assert same(sampler.offsets, fresh.offsets) and all(same(sampler.hard_conds[k], fresh.hard_conds[k]) for k in (0, 63))
+    assert (sampler.neighbor_slots, sampler.world_limits, sampler.world_grid) == (fresh.neighbor_slots, fresh.world_limits, fresh.world_grid)
+    legs = alternating([construct, setup, setup], preps=[None, lambda: sampler._move_windows(away), lambda: sampler._move_windows(half)])
+    names = (f"sampler + window cut ({len(set(fresh._window_ids))} windows)", f"persistent setup ({builds[0]} slices cut)",
+             f"persistent setup, half arrived ({builds[1]} slices cut)")
+    say(f"N = {n:3d} | one session, legs alternating | " + " | ".join(f"{k}: gpu {g:7.3f} ms, wall {w:7.3f} ms" for k, (g, w) in zip(names, legs)))
+    say(f"N = {n:3d} | neighbor_slots {sampler.neighbor_slots}; one texture set [{n}, 1, 400, 400, 4] = {sampler.guide._grids.numel() * 4 / 2 ** 20:.0f} MiB "
+        f"for the run, against {len(set(fresh._window_ids))} named slices allocated and cut per epoch")
+    map_textures.release_sdf_textures(sorted(set(fresh._window_ids)), "cuda")
+    sampler.release_windows()
+
+
 def main():
     import gpu_common
-    apart_only = "--apart" in sys.argv
-    out = [a for a in sys.argv[1:] if a != "--apart"]
+    apart_only, persistent_only = "--apart" in sys.argv, "--persistent" in sys.argv
+    out = [a for a in sys.argv[1:] if a not in ("--apart", "--persistent")]
     say(f"# device: {torch.cuda.get_device_name(0)}; 1 warm-up pass, median of 5 (the field build: one pass)")
     occ = random_world(1)
     E.register_world_map("Timed", occ)
@@ -152,6 +209,13 @@ def main():
         torch.cuda.synchronize()
         t_fields = 1e3 * (time.perf_counter() - t0)
         assert fleet.dist.shape[0] == n
+        if persistent_only:
+            say(f"N = {n:3d} | fields ({n} goals, {4 * n * occ.size / 2 ** 20:.0f} MiB): wall {t_fields:9.1f} ms | longest way "
+                f"{int(fleet.start_distances.max())} cells")
+            persistent_leg(fleet, model, fleet.epoch_targets(fleet.positions), n)
+            del fleet
+            torch.cuda.empty_cache()
+            continue
         ref = R.grid_distance_field(rt, fleet.field_goals[fleet.fields[0]][None])
         assert np.array_equal(fleet.dist[int(fleet.fields[0])].cpu().numpy(), ref[0]), "the device field is not the definition's"
         targets = fleet.epoch_targets(fleet.positions)
