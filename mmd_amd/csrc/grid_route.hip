@@ -9,6 +9,7 @@
 #include "../../include/mmd_amd.h"
 #include "common.h"
 #include "grid_route_dev.h"
+#include "walk_args.h"
 
 namespace mmd {
 
@@ -17,7 +18,6 @@ constexpr int GD_LDS = GD_BLOCK + 2;                 // with a one-cell halo
 constexpr int GD_THREADS = 256;
 constexpr int GD_ROWS = GD_BLOCK * GD_BLOCK / GD_THREADS;      // rows of one column that a thread owns: 16 consecutive ones
 constexpr int GD_MAX_ITERS = GD_BLOCK * GD_BLOCK + 1;
-constexpr int GD_UNREACHED = MMD_GRID_DIST_UNREACHED;
 constexpr int GD_NEVER = -1;                         // a block flag: "has not lowered a value since the restart"
 static_assert(GD_THREADS == 4 * GD_BLOCK && GD_ROWS * 4 == GD_BLOCK, "a thread owns one column of a quarter of the block's rows");
 
@@ -44,7 +44,7 @@ __global__ __launch_bounds__(GD_THREADS) void grid_distance_init_kernel(const fl
   const int f = blockIdx.y;
   const int2 g = goals[f];
   const bool seeded = g.x >= 0 && g.x < nx && g.y >= 0 && g.y < ny && gd_routable(tex, ny, clearance, rg, g.x, g.y);
-  dist[(size_t)f * nx * ny + cell] = (seeded && cell == g.x * ny + g.y) ? 0 : GD_UNREACHED;
+  dist[(size_t)f * nx * ny + cell] = (seeded && cell == g.x * ny + g.y) ? 0 : GRID_UNREACHED;
   if (cell < n_blocks)          // (a block holds at least one cell: n_blocks <= nx * ny)
     gd_flags(work, n_fields, f, n_blocks)[cell] = (seeded && cell == (g.x / GD_BLOCK) * nby + g.y / GD_BLOCK) ? 0 : GD_NEVER;
   if (cell == 0) work[f] = 0;
@@ -106,7 +106,7 @@ __global__ __launch_bounds__(GD_THREADS) void grid_distance_sweep_kernel(const f
   for (int k = 0; k < GD_ROWS; ++k) {
     const int ix = i0 + row0 + k;
     const bool inside = ix < nx && iy < ny;
-    loaded[k] = inside ? dist[(size_t)ix * ny + iy] : GD_UNREACHED;
+    loaded[k] = inside ? dist[(size_t)ix * ny + iy] : GRID_UNREACHED;
     if (inside && gd_routable(tex, ny, clearance, rg, ix, iy)) routable |= 1u << k;
     lds[(row0 + k + 1) * GD_LDS + col + 1] = loaded[k];
   }
@@ -116,7 +116,7 @@ __global__ __launch_bounds__(GD_THREADS) void grid_distance_sweep_kernel(const f
     const int hr = side == 0 ? -1 : side == 1 ? GD_BLOCK : k;            // row, column in block coordinates
     const int hc = side == 2 ? -1 : side == 3 ? GD_BLOCK : k;
     const int ix = i0 + hr, jy = j0 + hc;
-    int v = GD_UNREACHED;
+    int v = GRID_UNREACHED;
     if (ix >= 0 && ix < nx && jy >= 0 && jy < ny) v = __hip_atomic_load(&dist[(size_t)ix * ny + jy], GD_RELAXED_AGENT);
     lds[(hr + 1) * GD_LDS + hc + 1] = v;
   }
@@ -179,56 +179,44 @@ __global__ __launch_bounds__(GD_THREADS) void grid_distance_count_kernel(int n_f
   }
 }
 
-// ---- the descent: one lane per query (include/mmd_amd.h: mmd_grid_descend; floor_div: grid_route_dev.h) ----
-// From the start cell, while d > 0: the neighbours in the order +x, -x, +y, -y that lie inside the grid and hold exactly d - 1; the first
-// of them in the current cell's lattice tile, else the first.  The loop runs at most dist[start] times, whatever the field holds: d falls
+// ---- the descent: one lane per query (include/mmd_amd.h: mmd_grid_descend; descend_step: grid_route_dev.h) ----
+// From the start cell, while d > 0: one step of the rule.  The loop runs at most dist[start] times, whatever the field holds: d falls
 // by one per step.  The lanes of a wave walk unrelated cells: four scattered 4-byte loads per step and lane, no LDS, no atomics.
-constexpr int DESCEND_THREADS = 64;
-__global__ __launch_bounds__(DESCEND_THREADS) void grid_descend_kernel(const int* __restrict__ dist_all, int nx, int ny, int n_fields,
-                                                                       const int2* __restrict__ starts, const int* __restrict__ field,
-                                                                       int n_queries, int tile, int o_i, int o_j, int max_tiles,
-                                                                       int2* __restrict__ tiles, int4* __restrict__ summary) {
-  const int q = blockIdx.x * DESCEND_THREADS + threadIdx.x;
+// The entry is walk_entry's, written out with its two exits: through walk_entry the compiler merges them, fetches every argument in front
+// of the first and shares one reciprocal of `tile`, which moves the kernel's scalar-load and v_rcp counts off the figures on record.
+__global__ __launch_bounds__(WALK_THREADS) void grid_descend_kernel(const int* __restrict__ dist_all, int nx, int ny, int n_fields,
+                                                                    const int2* __restrict__ starts, const int* __restrict__ field,
+                                                                    int n_queries, int tile, int o_i, int o_j, int max_tiles,
+                                                                    int2* __restrict__ tiles, int4* __restrict__ summary) {
+  const int q = blockIdx.x * WALK_THREADS + threadIdx.x;
   if (q >= n_queries) return;
   const int2 s = starts[q];
   const int f = field[q];
   if (f < 0 || f >= n_fields || s.x < 0 || s.x >= nx || s.y < 0 || s.y >= ny) {
-    summary[q] = make_int4(-1, 0, 4, 0);
+    summary[q] = make_int4(-1, 0, WALK_OUTSIDE, 0);
     return;
   }
   const int* dist = dist_all + (size_t)f * nx * ny;
   int ix = s.x, iy = s.y;
   const int d0 = dist[(size_t)ix * ny + iy];
-  if (d0 == GD_UNREACHED) {
-    summary[q] = make_int4(-1, 0, 1, 0);
+  if (d0 == GRID_UNREACHED) {
+    summary[q] = make_int4(-1, 0, WALK_UNREACHED_START, 0);
     return;
   }
   int2* out = tiles + (size_t)q * max_tiles;
   long long ta = floor_div((long long)ix - o_i, tile), tb = floor_div((long long)iy - o_j, tile);
-  int n_tiles = 1, steps = 0, status = 0;
+  int n_tiles = 1, steps = 0, status = WALK_OK;
   out[0] = make_int2((int)ta, (int)tb);
   for (int d = d0; d > 0; --d) {
-    int cx = -1, cy = -1;
-    bool same = false;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const int jx = ix + (k == 0) - (k == 1), jy = iy + (k == 2) - (k == 3);
-      if (jx < 0 || jx >= nx || jy < 0 || jy >= ny || same) continue;
-      if (dist[(size_t)jx * ny + jy] != d - 1) continue;
-      const bool in_tile = floor_div((long long)jx - o_i, tile) == ta && floor_div((long long)jy - o_j, tile) == tb;
-      if (cx < 0 || in_tile) { cx = jx; cy = jy; same = in_tile; }
-    }
-    if (cx < 0) { status = 2; break; }
-    ix = cx; iy = cy;
+    const int r = descend_step(dist, nx, ny, tile, o_i, o_j, d, ix, iy, ta, tb);
+    if (r < 0) { status = WALK_STUCK; break; }
     ++steps;
-    if (!same) {
-      ta = floor_div((long long)ix - o_i, tile);
-      tb = floor_div((long long)iy - o_j, tile);
+    if (r == 0) {
       if (n_tiles < max_tiles) out[n_tiles] = make_int2((int)ta, (int)tb);
       ++n_tiles;
     }
   }
-  if (status == 0 && n_tiles > max_tiles) status = 3;
+  if (status == WALK_OK && n_tiles > max_tiles) status = WALK_TILES;
   summary[q] = make_int4(steps, n_tiles, status, 0);
 }
 
@@ -293,24 +281,12 @@ int mmd_grid_distance_field(const float* grid_dev, int nx, int ny, float clearan
 
 int mmd_grid_descend(const int32_t* dist_dev, int nx, int ny, int n_fields, const int32_t* starts_dev, const int32_t* field_dev, int n_queries,
                      int tile, const int32_t lattice_origin[2], int max_tiles, int32_t* tiles_dev, int32_t* summary_dev, void* stream) {
-  MMD_REQUIRE(nx >= 1 && ny >= 1 && nx <= MMD_OCCUPANCY_MAX_SIDE && ny <= MMD_OCCUPANCY_MAX_SIDE,
-              "mmd_grid_descend: a grid of %d x %d cells (1 to %d per side)", nx, ny, MMD_OCCUPANCY_MAX_SIDE);
-  MMD_REQUIRE(n_fields >= 0, "mmd_grid_descend: n_fields = %d (>= 0)", n_fields);
-  MMD_REQUIRE(n_queries >= 0 && n_queries <= INT_MAX - DESCEND_THREADS, "mmd_grid_descend: n_queries = %d (0 to 2^31 - 65)", n_queries);
-  MMD_REQUIRE(tile >= 1, "mmd_grid_descend: tile = %d cells (>= 1)", tile);
-  MMD_REQUIRE(max_tiles >= 1, "mmd_grid_descend: max_tiles = %d (>= 1)", max_tiles);
-  MMD_REQUIRE(lattice_origin, "mmd_grid_descend: NULL lattice_origin");
-  MMD_REQUIRE(lattice_origin[0] >= -(1 << 30) && lattice_origin[0] <= (1 << 30) && lattice_origin[1] >= -(1 << 30) && lattice_origin[1] <= (1 << 30),
-              "mmd_grid_descend: lattice_origin = (%d, %d) (each within +-2^30: a tile index is then an int32)", lattice_origin[0],
-              lattice_origin[1]);
+  if (const int refused = descend_args("mmd_grid_descend", dist_dev, nx, ny, n_fields, starts_dev, field_dev, n_queries, tile, lattice_origin,
+                                       max_tiles, 0, tiles_dev, summary_dev))
+    return refused;
   if (n_queries == 0) return 0;
-  MMD_REQUIRE(dist_dev || n_fields == 0, "mmd_grid_descend: NULL dist with n_fields = %d", n_fields);
-  MMD_REQUIRE(starts_dev, "mmd_grid_descend: NULL starts");
-  MMD_REQUIRE(field_dev, "mmd_grid_descend: NULL field indices");
-  MMD_REQUIRE(tiles_dev, "mmd_grid_descend: NULL tiles");
-  MMD_REQUIRE(summary_dev, "mmd_grid_descend: NULL summary");
-  hipLaunchKernelGGL(grid_descend_kernel, dim3((n_queries + DESCEND_THREADS - 1) / DESCEND_THREADS), dim3(DESCEND_THREADS), 0,
-                     (hipStream_t)stream, (const int*)dist_dev, nx, ny, n_fields, (const int2*)starts_dev, (const int*)field_dev, n_queries, tile,
+  hipLaunchKernelGGL(grid_descend_kernel, dim3((n_queries + WALK_THREADS - 1) / WALK_THREADS), dim3(WALK_THREADS), 0, (hipStream_t)stream,
+                     (const int*)dist_dev, nx, ny, n_fields, (const int2*)starts_dev, (const int*)field_dev, n_queries, tile,
                      lattice_origin[0], lattice_origin[1], max_tiles, (int2*)tiles_dev, (int4*)summary_dev);
   MMD_HIP_CHECK(hipGetLastError());
   return 0;

@@ -11,6 +11,7 @@
 #include "common.h"
 #include "grid_route_dev.h"
 #include "seed_dev.h"
+#include "walk_args.h"
 #include "wave_dev.h"
 // every float operation below is one rounding: no fused multiply-add
 #pragma clang fp contract(off)
@@ -22,69 +23,34 @@ constexpr int RS_MAX_TILES = MMD_ROUTE_SEED_MAX_TILES;
 constexpr int RS_CHAIN = RS_POINTS * RS_MAX_TILES;          // the longest chain: 1024 points
 constexpr int RS_THREADS = 256;
 constexpr int RS_PER_THREAD = RS_CHAIN / RS_THREADS;        // a thread owns the points t, t + 256, t + 512, t + 768
-constexpr int DS_THREADS = 64;
-constexpr int DS_UNREACHED = MMD_GRID_DIST_UNREACHED;
 static_assert(RS_POINTS == 64 && RS_CHAIN == RS_THREADS * RS_PER_THREAD, "a wave's 64 points are one tile visit");
 
-// ---- the samples of a descent: one lane per query ----
-// One step of mmd_grid_descend's walk from cell (ix, iy), which holds d > 0, in lattice tile (ta, tb): the neighbours in the order +x,
-// -x, +y, -y that lie inside the grid and hold exactly d - 1; the first of them in the tile, else the first.  Returns 1 (stayed in the
-// tile), 0 (entered another one: ta, tb are the new tile) or -1 (no candidate; nothing moved).
-__device__ __forceinline__ int descend_step(const int* __restrict__ dist, int nx, int ny, int tile, int o_i, int o_j, int d, int& ix, int& iy,
-                                            long long& ta, long long& tb) {
-  int cx = -1, cy = -1;
-  bool same = false;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const int jx = ix + (k == 0) - (k == 1), jy = iy + (k == 2) - (k == 3);
-    if (jx < 0 || jx >= nx || jy < 0 || jy >= ny || same) continue;
-    if (dist[(size_t)jx * ny + jy] != d - 1) continue;
-    const bool in_tile = floor_div((long long)jx - o_i, tile) == ta && floor_div((long long)jy - o_j, tile) == tb;
-    if (cx < 0 || in_tile) { cx = jx; cy = jy; same = in_tile; }
-  }
-  if (cx < 0) return -1;
-  ix = cx; iy = cy;
-  if (same) return 1;
-  ta = floor_div((long long)ix - o_i, tile);
-  tb = floor_div((long long)iy - o_j, tile);
-  return 0;
-}
-
-// Support point j of a visit of m cells is the visit's cell number off(j) = (j * (m - 1) + 31) / 63, monotone in j.  The walk stands on
-// the visit's cell number t and has emitted every j with off(j) < t: the next j belongs to t iff j * (m - 1) + 31 < (t + 1) * 63.
-__device__ __forceinline__ void emit_samples(int2* __restrict__ row, int& j, int m, int t, int ix, int iy) {
-  while (j < RS_POINTS && (long long)j * (m - 1) + 31 < ((long long)t + 1) * 63) row[j++] = make_int2(ix, iy);
-}
-
+// ---- the samples of a descent: one lane per query (walk_entry, descend_step: grid_route_dev.h; emit_samples: seed_dev.h) ----
 // The lane walks the field twice, with no buffer proportional to the path: the first walk is mmd_grid_descend's and counts the cells of
 // every visit; the second, only for status 0, repeats it and emits each visit's 64 samples as it passes them.  Each walk's loop runs at
 // most dist[start] times, whatever the field holds (d falls by one per step), and emit_samples at most 64 times per visit in all (j only
 // grows).  Every row of visit_cells and cells of the query is written: zero behind n_tiles and for a status other than 0.
-__global__ __launch_bounds__(DS_THREADS) void grid_descend_samples_kernel(const int* __restrict__ dist_all, int nx, int ny, int n_fields,
-                                                                          const int2* __restrict__ starts, const int* __restrict__ field,
-                                                                          int n_queries, int tile, int o_i, int o_j, int max_tiles,
-                                                                          int2* __restrict__ tiles, int4* __restrict__ summary,
-                                                                          int* visit_cells, int2* __restrict__ cells) {
-  const int q = blockIdx.x * DS_THREADS + threadIdx.x;
+__global__ __launch_bounds__(WALK_THREADS) void grid_descend_samples_kernel(const int* __restrict__ dist_all, int nx, int ny, int n_fields,
+                                                                            const int2* __restrict__ starts, const int* __restrict__ field,
+                                                                            int n_queries, int tile, int o_i, int o_j, int max_tiles,
+                                                                            int2* __restrict__ tiles, int4* __restrict__ summary,
+                                                                            int* visit_cells, int2* __restrict__ cells) {
+  const int q = blockIdx.x * WALK_THREADS + threadIdx.x;
   if (q >= n_queries) return;
-  const int2 s = starts[q];
-  const int f = field[q];
+  const WalkEntry e = walk_entry(dist_all, nx, ny, n_fields, starts, field, q);
   int* vc = visit_cells + (size_t)q * max_tiles;
   int2* rows = cells + (size_t)q * max_tiles * RS_POINTS;
-  const bool inside = f >= 0 && f < n_fields && s.x >= 0 && s.x < nx && s.y >= 0 && s.y < ny;
-  const int* dist = dist_all + (inside ? (size_t)f * nx * ny : 0);
-  const int d0 = inside ? dist[(size_t)s.x * ny + s.y] : DS_UNREACHED;
-  int4 sum = make_int4(-1, 0, inside ? 1 : 4, 0);
+  int4 sum = make_int4(-1, 0, e.no_walk, 0);
   int n_visits = 0;
-  if (d0 != DS_UNREACHED) {
+  if (e.d0 != GRID_UNREACHED) {
     int2* out = tiles + (size_t)q * max_tiles;
-    int ix = s.x, iy = s.y;
+    int ix = e.s.x, iy = e.s.y;
     long long ta = floor_div((long long)ix - o_i, tile), tb = floor_div((long long)iy - o_j, tile);
-    int n_tiles = 1, steps = 0, status = 0, m = 1;
+    int n_tiles = 1, steps = 0, status = WALK_OK, m = 1;
     out[0] = make_int2((int)ta, (int)tb);
-    for (int d = d0; d > 0; --d) {
-      const int r = descend_step(dist, nx, ny, tile, o_i, o_j, d, ix, iy, ta, tb);
-      if (r < 0) { status = 2; break; }
+    for (int d = e.d0; d > 0; --d) {
+      const int r = descend_step(e.dist, nx, ny, tile, o_i, o_j, d, ix, iy, ta, tb);
+      if (r < 0) { status = WALK_STUCK; break; }
       ++steps;
       if (r) { ++m; continue; }
       if (n_tiles <= max_tiles) vc[n_tiles - 1] = m;
@@ -93,9 +59,9 @@ __global__ __launch_bounds__(DS_THREADS) void grid_descend_samples_kernel(const 
       m = 1;
     }
     if (n_tiles <= max_tiles) vc[n_tiles - 1] = m;
-    if (status == 0 && n_tiles > max_tiles) status = 3;
+    if (status == WALK_OK && n_tiles > max_tiles) status = WALK_TILES;
     sum = make_int4(steps, n_tiles, status, 0);
-    if (status == 0) n_visits = n_tiles;
+    if (status == WALK_OK) n_visits = n_tiles;
   }
   summary[q] = sum;
   for (int k = n_visits; k < max_tiles; ++k) {
@@ -104,12 +70,12 @@ __global__ __launch_bounds__(DS_THREADS) void grid_descend_samples_kernel(const 
   }
   if (n_visits == 0) return;
 
-  int ix = s.x, iy = s.y;
+  int ix = e.s.x, iy = e.s.y;
   long long ta = floor_div((long long)ix - o_i, tile), tb = floor_div((long long)iy - o_j, tile);
   int k = 0, m = vc[0], t = 0, j = 0;
   emit_samples(rows, j, m, t, ix, iy);
-  for (int d = d0; d > 0; --d) {
-    const int r = descend_step(dist, nx, ny, tile, o_i, o_j, d, ix, iy, ta, tb);
+  for (int d = e.d0; d > 0; --d) {
+    const int r = descend_step(e.dist, nx, ny, tile, o_i, o_j, d, ix, iy, ta, tb);
     if (r < 0) break;                                      // (the first walk passed here)
     if (r) {
       ++t;
@@ -214,8 +180,6 @@ __global__ __launch_bounds__(RS_THREADS) void route_seeds_kernel(const float4* _
   if (t == 0) clear_min[route] = order_key(min(min(lds4[0], lds4[1]), min(lds4[2], lds4[3])));
 }
 
-static bool origin_ok(const int32_t o[2]) { return o[0] >= -(1 << 30) && o[0] <= (1 << 30) && o[1] >= -(1 << 30) && o[1] <= (1 << 30); }
-
 }  // namespace mmd
 
 using namespace mmd;
@@ -225,24 +189,13 @@ extern "C" {
 int mmd_grid_descend_samples(const int32_t* dist_dev, int nx, int ny, int n_fields, const int32_t* starts_dev, const int32_t* field_dev,
                              int n_queries, int tile, const int32_t lattice_origin[2], int max_tiles, int32_t* tiles_dev, int32_t* summary_dev,
                              int32_t* visit_cells_dev, int32_t* cells_dev, void* stream) {
-  MMD_REQUIRE(nx >= 1 && ny >= 1 && nx <= MMD_OCCUPANCY_MAX_SIDE && ny <= MMD_OCCUPANCY_MAX_SIDE,
-              "mmd_grid_descend_samples: a grid of %d x %d cells (1 to %d per side)", nx, ny, MMD_OCCUPANCY_MAX_SIDE);
-  MMD_REQUIRE(n_fields >= 0, "mmd_grid_descend_samples: n_fields = %d (>= 0)", n_fields);
-  MMD_REQUIRE(n_queries >= 0 && n_queries <= INT_MAX - DS_THREADS, "mmd_grid_descend_samples: n_queries = %d (0 to 2^31 - 65)", n_queries);
-  MMD_REQUIRE(tile >= 1, "mmd_grid_descend_samples: tile = %d cells (>= 1)", tile);
-  MMD_REQUIRE(max_tiles >= 1 && max_tiles <= RS_MAX_TILES, "mmd_grid_descend_samples: max_tiles = %d (1 to %d)", max_tiles, RS_MAX_TILES);
-  MMD_REQUIRE(lattice_origin, "mmd_grid_descend_samples: NULL lattice_origin");
-  MMD_REQUIRE(origin_ok(lattice_origin), "mmd_grid_descend_samples: lattice_origin = (%d, %d) (each within +-2^30: a tile index is then an int32)",
-              lattice_origin[0], lattice_origin[1]);
+  if (const int refused = descend_args("mmd_grid_descend_samples", dist_dev, nx, ny, n_fields, starts_dev, field_dev, n_queries, tile,
+                                       lattice_origin, max_tiles, RS_MAX_TILES, tiles_dev, summary_dev))
+    return refused;
   if (n_queries == 0) return 0;
-  MMD_REQUIRE(dist_dev || n_fields == 0, "mmd_grid_descend_samples: NULL dist with n_fields = %d", n_fields);
-  MMD_REQUIRE(starts_dev, "mmd_grid_descend_samples: NULL starts");
-  MMD_REQUIRE(field_dev, "mmd_grid_descend_samples: NULL field indices");
-  MMD_REQUIRE(tiles_dev, "mmd_grid_descend_samples: NULL tiles");
-  MMD_REQUIRE(summary_dev, "mmd_grid_descend_samples: NULL summary");
   MMD_REQUIRE(visit_cells_dev, "mmd_grid_descend_samples: NULL visit_cells");
   MMD_REQUIRE(cells_dev, "mmd_grid_descend_samples: NULL cells");
-  hipLaunchKernelGGL(grid_descend_samples_kernel, dim3((n_queries + DS_THREADS - 1) / DS_THREADS), dim3(DS_THREADS), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(grid_descend_samples_kernel, dim3((n_queries + WALK_THREADS - 1) / WALK_THREADS), dim3(WALK_THREADS), 0, (hipStream_t)stream,
                      (const int*)dist_dev, nx, ny, n_fields, (const int2*)starts_dev, (const int*)field_dev, n_queries, tile, lattice_origin[0],
                      lattice_origin[1], max_tiles, (int2*)tiles_dev, (int4*)summary_dev, (int*)visit_cells_dev, (int2*)cells_dev);
   MMD_HIP_CHECK(hipGetLastError());

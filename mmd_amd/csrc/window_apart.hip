@@ -9,6 +9,7 @@
 
 #include "../../include/mmd_amd.h"
 #include "common.h"
+#include "walk_args.h"
 #include "wave_dev.h"
 #include "window_walk_dev.h"
 
@@ -61,33 +62,29 @@ __global__ __launch_bounds__(WG_THREADS) void window_apart_paths_kernel(const in
                                                                         int max_steps, int window, ApartWork w) {
   const int q = blockIdx.x * WG_THREADS + threadIdx.x;
   if (q >= n_queries) return;
-  const int2 s = starts[q];
-  const int f = field[q];
-  const bool inside = f >= 0 && f < n_fields && s.x >= 0 && s.x < nx && s.y >= 0 && s.y < ny;
-  const int* dist = dist_all + (size_t)(inside ? f : 0) * nx * ny;
-  const int d0 = inside ? dist[(size_t)s.x * ny + s.y] : WG_UNREACHED;
-  if (d0 == WG_UNREACHED) {
-    w.meta[q] = make_int4(-1, -1, inside ? WG_UNREACHED_START : WG_OUTSIDE, 0);
+  const WalkEntry e = walk_entry(dist_all, nx, ny, n_fields, starts, field, q);
+  if (e.d0 == GRID_UNREACHED) {
+    w.meta[q] = make_int4(-1, -1, e.no_walk, 0);
     w.origin[q] = make_int2(0, 0);
     w.k[0][q] = w.k[1][q] = 0;
     w.flag[q] = 0;
     return;
   }
   int2* row = w.paths + (size_t)q * apart_row(max_steps);
-  const int2 g = goals[f];
-  int ix = s.x, iy = s.y, steps = 0, status = WG_OK;
-  row[0] = s;
-  const int bound = min(max_steps, d0);
+  const int2 g = goals[e.f];
+  int ix = e.s.x, iy = e.s.y, steps = 0, status = WALK_OK;
+  row[0] = e.s;
+  const int bound = min(max_steps, e.d0);
   for (int k = 0; k < bound; ++k) {
-    const int r = window_step(dist, nx, ny, s, g, reach, d0 - k - 1, ix, iy);
-    if (r < 0) status = WG_STUCK;
+    const int r = window_step(e.dist, nx, ny, e.s, g, reach, e.d0 - k - 1, ix, iy);
+    if (r < 0) status = WALK_STUCK;
     if (r != 1) break;
     row[++steps] = make_int2(ix, iy);
   }
-  w.meta[q] = make_int4(steps, d0 - steps, status, 0);
-  w.origin[q] = window_origin(s, nx, ny, window);
-  w.k[0][q] = w.k[1][q] = status == WG_OK ? steps : 0;
-  w.flag[q] = status == WG_OK ? WA_MOVED : 0;
+  w.meta[q] = make_int4(steps, e.d0 - steps, status, 0);
+  w.origin[q] = window_origin(e.s, nx, ny, window);
+  w.k[0][q] = w.k[1][q] = status == WALK_OK ? steps : 0;
+  w.flag[q] = status == WALK_OK ? WA_MOVED : 0;
 }
 
 // ---- 2. one sweep: one wave per robot ----
@@ -106,7 +103,7 @@ __global__ __launch_bounds__(WG_THREADS) void window_apart_sweep_kernel(int n_qu
                                                                         const int* __restrict__ k_prev, int* __restrict__ k_next) {
   const int r = blockIdx.x, lane = threadIdx.x;
   const int4 m = w.meta[r];
-  if (m.z != WG_OK) return;                                // takes no part: one decision per wave
+  if (m.z != WALK_OK) return;                              // takes no part: one decision per wave
   const size_t stride = apart_row(max_steps);
   const int2* row = w.paths + (size_t)r * stride;
   const int walked = min(max(m.x, 0), max_steps);
@@ -119,7 +116,7 @@ __global__ __launch_bounds__(WG_THREADS) void window_apart_sweep_kernel(int n_qu
     bool conflict = false;
     for (int base = 0; base < n_queries; base += WG_THREADS) {
       const int j = base + lane;
-      bool blocks = j < n_queries && j != r && w.meta[min(j, n_queries - 1)].z == WG_OK;
+      bool blocks = j < n_queries && j != r && w.meta[min(j, n_queries - 1)].z == WALK_OK;
       int2 b = make_int2(0, 0);
       if (blocks) {
         b = w.paths[(size_t)j * stride + (j < r ? min(max(k_prev[j], 0), max_steps) : 0)];
@@ -158,7 +155,7 @@ __global__ __launch_bounds__(WG_THREADS) void window_apart_emit_kernel(int n_que
                                                                        int2* __restrict__ samples, int* __restrict__ changed) {
   const int r = blockIdx.x, j = threadIdx.x;
   const int4 m = w.meta[r];
-  const bool ok = m.z == WG_OK;
+  const bool ok = m.z == WALK_OK;
   const int2* row = w.paths + (size_t)r * apart_row(max_steps);
   const int walked = min(max(m.x, -1), max_steps);
   const int k = ok ? min(max(k_cur[r], 0), max(walked, 0)) : walked;          // the index of the cell reported; -1: none
@@ -166,7 +163,7 @@ __global__ __launch_bounds__(WG_THREADS) void window_apart_emit_kernel(int n_que
   if (j == 0) {
     cells[r] = k >= 0 ? row[k] : make_int2(0, 0);
     origins[r] = w.origin[r];
-    summary[r] = ok ? make_int4(k, m.y + (walked - k), WG_OK, m.y + (walked - k) == 0) : make_int4(m.x, m.y, m.z, 0);
+    summary[r] = ok ? make_int4(k, m.y + (walked - k), WALK_OK, m.y + (walked - k) == 0) : make_int4(m.x, m.y, m.z, 0);
     extra[r] = make_int2(m.x, ok && (w.flag[r] & WA_CLEAR) ? 1 : 0);
     if (to_first) w.k[0][r] = k_cur[r];
   }
@@ -193,29 +190,16 @@ int mmd_grid_window_goals_apart(const int32_t* dist_dev, int nx, int ny, int n_f
                                 const int32_t* goals_dev, int n_queries, int reach, int max_steps, int window, int sep, int restart,
                                 int n_sweeps, void* work_dev, size_t work_bytes, int32_t* cells_dev, int32_t* origins_dev,
                                 int32_t* summary_dev, int32_t* extra_dev, int32_t* samples_dev, int32_t* changed_dev, void* stream) {
-  MMD_REQUIRE(nx >= 1 && ny >= 1 && nx <= MMD_OCCUPANCY_MAX_SIDE && ny <= MMD_OCCUPANCY_MAX_SIDE,
-              "mmd_grid_window_goals_apart: a grid of %d x %d cells (1 to %d per side)", nx, ny, MMD_OCCUPANCY_MAX_SIDE);
-  MMD_REQUIRE(n_fields >= 0, "mmd_grid_window_goals_apart: n_fields = %d (>= 0)", n_fields);
-  MMD_REQUIRE(n_queries >= 0 && n_queries <= INT_MAX - WG_THREADS, "mmd_grid_window_goals_apart: n_queries = %d (0 to 2^31 - 65)", n_queries);
-  MMD_REQUIRE(window >= 1 && window <= nx && window <= ny, "mmd_grid_window_goals_apart: window = %d cells (1 to min(nx, ny) = %d)", window,
-              nx < ny ? nx : ny);
-  MMD_REQUIRE(reach >= 1 && reach <= window / 2 - 1, "mmd_grid_window_goals_apart: reach = %d cells (1 to window / 2 - 1 = %d)", reach,
-              window / 2 - 1);
-  MMD_REQUIRE(max_steps >= 1 && max_steps <= WA_MAX_STEPS, "mmd_grid_window_goals_apart: max_steps = %d (1 to %d: a row of the workspace)",
-              max_steps, WA_MAX_STEPS);
+  const char* name = "mmd_grid_window_goals_apart";
+  if (const int refused = window_goals_ranges(name, nx, ny, n_fields, n_queries, reach, max_steps, WA_MAX_STEPS, window)) return refused;
   MMD_REQUIRE(sep >= 1 && sep <= WA_MAX_SEP, "mmd_grid_window_goals_apart: sep = %d cells (1 to %d)", sep, WA_MAX_SEP);
   MMD_REQUIRE(n_sweeps >= 0, "mmd_grid_window_goals_apart: n_sweeps = %d (>= 0)", n_sweeps);
   if (n_queries == 0) return 0;
-  MMD_REQUIRE(dist_dev || n_fields == 0, "mmd_grid_window_goals_apart: NULL dist with n_fields = %d", n_fields);
-  MMD_REQUIRE(goals_dev || n_fields == 0, "mmd_grid_window_goals_apart: NULL goals with n_fields = %d", n_fields);
-  MMD_REQUIRE(starts_dev, "mmd_grid_window_goals_apart: NULL starts");
-  MMD_REQUIRE(field_dev, "mmd_grid_window_goals_apart: NULL field indices");
+  if (const int refused = window_goals_inputs(name, dist_dev, goals_dev, n_fields, starts_dev, field_dev)) return refused;
   MMD_REQUIRE(work_dev && (uintptr_t)work_dev % 16 == 0, "mmd_grid_window_goals_apart: NULL workspace, or one not aligned to 16 bytes");
   MMD_REQUIRE(work_bytes >= apart_work_bytes(n_queries, max_steps), "mmd_grid_window_goals_apart: workspace of %zu bytes, %zu needed",
               work_bytes, apart_work_bytes(n_queries, max_steps));
-  MMD_REQUIRE(cells_dev, "mmd_grid_window_goals_apart: NULL cells");
-  MMD_REQUIRE(origins_dev, "mmd_grid_window_goals_apart: NULL origins");
-  MMD_REQUIRE(summary_dev, "mmd_grid_window_goals_apart: NULL summary");
+  if (const int refused = window_goals_outputs(name, cells_dev, origins_dev, summary_dev)) return refused;
   MMD_REQUIRE(extra_dev, "mmd_grid_window_goals_apart: NULL extra");
   MMD_REQUIRE(changed_dev, "mmd_grid_window_goals_apart: NULL changed");
   const ApartWork w = apart_work(work_dev, n_queries, max_steps);

@@ -1,8 +1,7 @@
-// World fleets: the seed trajectory of an epoch.  The fleet's own walk (window_walk_dev.h: the staircase rule of window_goal) with the 64
-// support cells of its cell path (include/mmd_amd.h: mmd_grid_window_goal_samples), and from those every robot's smoothed chain of
-// support points with velocities inside its own window, in trajs_final's format (mmd_window_seeds).  The definitions are the numpy
-// functions window_goal_samples and window_seed of mmd_amd/world_fleet.py: the same integers and the same float32 bits.  Plain loads and
-// vector stores; no LDS, no atomics, no scratch.
+// World fleets: the seed trajectory of an epoch.  From the 64 support cells of every robot's walk (window_goals.hip:
+// mmd_grid_window_goal_samples, or window_apart.hip's shortened walks) every robot's smoothed chain of support points with velocities
+// inside its own window, in trajs_final's format (include/mmd_amd.h: mmd_window_seeds).  The definition is the numpy function window_seed
+// of mmd_amd/world_fleet.py: the same float32 bits.  Plain loads and vector stores; no LDS, no atomics, no scratch.
 #include <hip/hip_runtime.h>
 
 #include <cfloat>
@@ -21,57 +20,6 @@ namespace mmd {
 constexpr int WS_POINTS = MMD_ROUTE_SEED_POINTS;            // support points of a seed: one wave
 static_assert(WS_POINTS == 64 && WS_POINTS == WG_THREADS, "a wave's 64 lanes are a seed's 64 support points");
 
-// ---- the samples of a walk: one lane per query ----
-// The lane walks the field twice, with no buffer proportional to the path (grid_descend_samples_kernel's way): the first walk is
-// grid_window_goals_kernel's and fixes `steps`; the second, only for status 0, repeats it and emits sample j when it stands on the path's
-// cell number off(j) = (j * steps + 31) / 63, monotone in j: one advancing cursor.  Standing on cell t, every j with off(j) < t has been
-// emitted, and the next j belongs to t iff j * steps + 31 < (t + 1) * 63.  All of this is int32: a step lands on a cell that holds one
-// less than the cell before, so the cells of a walk are distinct and steps <= d0 < nx * ny <= 2048^2 = 2^22, whatever the field holds;
-// 63 * steps + 31 and (steps + 1) * 63 stay below 2^28 + 63.  Each walk's loop runs at most min(max_steps, d0) times, the second one
-// `steps` times; the cursor only grows, 64 emissions in all.  Every word of the four outputs of the query is written.
-__global__ __launch_bounds__(WG_THREADS) void grid_window_goal_samples_kernel(const int* __restrict__ dist_all, int nx, int ny, int n_fields,
-                                                                              const int2* __restrict__ starts, const int* __restrict__ field,
-                                                                              const int2* __restrict__ goals, int n_queries, int reach,
-                                                                              int max_steps, int window, int2* __restrict__ cells,
-                                                                              int2* __restrict__ origins, int4* __restrict__ summary,
-                                                                              int2* __restrict__ samples) {
-  const int q = blockIdx.x * WG_THREADS + threadIdx.x;
-  if (q >= n_queries) return;
-  const int2 s = starts[q];
-  const int f = field[q];
-  int2* row = samples + (size_t)q * WS_POINTS;
-  const bool inside = f >= 0 && f < n_fields && s.x >= 0 && s.x < nx && s.y >= 0 && s.y < ny;
-  const int* dist = dist_all + (size_t)(inside ? f : 0) * nx * ny;
-  const int d0 = inside ? dist[(size_t)s.x * ny + s.y] : WG_UNREACHED;
-  int status = inside ? WG_UNREACHED_START : WG_OUTSIDE, steps = 0;
-  int2 g = make_int2(0, 0);
-  if (d0 == WG_UNREACHED) {
-    cells[q] = make_int2(0, 0);
-    origins[q] = make_int2(0, 0);
-    summary[q] = make_int4(-1, -1, status, 0);
-  } else {
-    g = goals[f];
-    int ix, iy;
-    status = window_walk(dist, nx, ny, s, g, reach, max_steps, d0, ix, iy, steps);
-    const int remaining = d0 - steps;
-    cells[q] = make_int2(ix, iy);
-    origins[q] = window_origin(s, nx, ny, window);
-    summary[q] = make_int4(steps, remaining, status, status == WG_OK && remaining == 0);
-  }
-  if (status != WG_OK) {                                   // a walk that did not end well gives no samples
-    for (int j = 0; j < WS_POINTS; ++j) row[j] = make_int2(0, 0);
-    return;
-  }
-
-  int ix = s.x, iy = s.y, j = 0;
-  for (int t = 0;; ++t) {                                  // t = 0 .. steps: the path's cell number
-    while (j < WS_POINTS && j * steps + 31 < (t + 1) * 63) row[j++] = make_int2(ix, iy);
-    if (t >= steps) break;
-    if (window_step(dist, nx, ny, s, g, reach, d0 - t - 1, ix, iy) != 1) break;      // (the first walk passed here)
-  }
-  for (; j < WS_POINTS; ++j) row[j] = make_int2(ix, iy);   // (none left: off(63) = steps.  It keeps "every word is written" off that argument)
-}
-
 // ---- the seed: one wave per robot ----
 // Lane j is support point j and keeps its point in registers.  An iteration reads both neighbours' points of the iteration before across
 // lanes (__shfl_up / __shfl_down by 1: every lane reads before any lane writes, so this is the Jacobi iteration of the definition, with no
@@ -88,7 +36,7 @@ __global__ __launch_bounds__(WS_POINTS) void window_seeds_kernel(const float4* _
                                                                  int* __restrict__ clear_min) {
   const int robot = blockIdx.x, j = threadIdx.x;
   float4* out = seeds + (size_t)robot * WS_POINTS;
-  if (summary[robot].z != WG_OK) {                         // one decision per wave: no chain, no texture read
+  if (summary[robot].z != WALK_OK) {                         // one decision per wave: no chain, no texture read
     out[j] = make_float4(0.f, 0.f, 0.f, 0.f);
     if (j == 0) clear_min[robot] = 0;
     return;
@@ -125,35 +73,6 @@ __global__ __launch_bounds__(WS_POINTS) void window_seeds_kernel(const float4* _
 using namespace mmd;
 
 extern "C" {
-
-int mmd_grid_window_goal_samples(const int32_t* dist_dev, int nx, int ny, int n_fields, const int32_t* starts_dev, const int32_t* field_dev,
-                                 const int32_t* goals_dev, int n_queries, int reach, int max_steps, int window, int32_t* cells_dev,
-                                 int32_t* origins_dev, int32_t* summary_dev, int32_t* samples_dev, void* stream) {
-  MMD_REQUIRE(nx >= 1 && ny >= 1 && nx <= MMD_OCCUPANCY_MAX_SIDE && ny <= MMD_OCCUPANCY_MAX_SIDE,
-              "mmd_grid_window_goal_samples: a grid of %d x %d cells (1 to %d per side)", nx, ny, MMD_OCCUPANCY_MAX_SIDE);
-  MMD_REQUIRE(n_fields >= 0, "mmd_grid_window_goal_samples: n_fields = %d (>= 0)", n_fields);
-  MMD_REQUIRE(n_queries >= 0 && n_queries <= INT_MAX - WG_THREADS, "mmd_grid_window_goal_samples: n_queries = %d (0 to 2^31 - 65)", n_queries);
-  MMD_REQUIRE(window >= 1 && window <= nx && window <= ny, "mmd_grid_window_goal_samples: window = %d cells (1 to min(nx, ny) = %d)", window,
-              nx < ny ? nx : ny);
-  MMD_REQUIRE(reach >= 1 && reach <= window / 2 - 1, "mmd_grid_window_goal_samples: reach = %d cells (1 to window / 2 - 1 = %d)", reach,
-              window / 2 - 1);
-  MMD_REQUIRE(max_steps >= 1, "mmd_grid_window_goal_samples: max_steps = %d (>= 1)", max_steps);
-  if (n_queries == 0) return 0;
-  MMD_REQUIRE(dist_dev || n_fields == 0, "mmd_grid_window_goal_samples: NULL dist with n_fields = %d", n_fields);
-  MMD_REQUIRE(goals_dev || n_fields == 0, "mmd_grid_window_goal_samples: NULL goals with n_fields = %d", n_fields);
-  MMD_REQUIRE(starts_dev, "mmd_grid_window_goal_samples: NULL starts");
-  MMD_REQUIRE(field_dev, "mmd_grid_window_goal_samples: NULL field indices");
-  MMD_REQUIRE(cells_dev, "mmd_grid_window_goal_samples: NULL cells");
-  MMD_REQUIRE(origins_dev, "mmd_grid_window_goal_samples: NULL origins");
-  MMD_REQUIRE(summary_dev, "mmd_grid_window_goal_samples: NULL summary");
-  MMD_REQUIRE(samples_dev, "mmd_grid_window_goal_samples: NULL samples");
-  hipLaunchKernelGGL(grid_window_goal_samples_kernel, dim3((n_queries + WG_THREADS - 1) / WG_THREADS), dim3(WG_THREADS), 0,
-                     (hipStream_t)stream, (const int*)dist_dev, nx, ny, n_fields, (const int2*)starts_dev, (const int*)field_dev,
-                     (const int2*)goals_dev, n_queries, reach, max_steps, window, (int2*)cells_dev, (int2*)origins_dev, (int4*)summary_dev,
-                     (int2*)samples_dev);
-  MMD_HIP_CHECK(hipGetLastError());
-  return 0;
-}
 
 int mmd_window_seeds(const float* grid_dev, int nx, int ny, const float lo[2], const float hi[2], float clearance, const int32_t* samples_dev,
                      const int32_t* origins_dev, const int32_t* summary_dev, int n_robots, int window, const float* start_points_dev,

@@ -1,15 +1,15 @@
-// What the two walk kernels of a world fleet share (window_goals.hip, window_seeds.hip): the entry of a query and the step rule of
-// mmd_amd/world_fleet.py::window_goal.  Every value is an exact integer.
+// What the walk kernels of a world fleet share (window_goals.hip, window_apart.hip): the step rule of
+// mmd_amd/world_fleet.py::window_goal on grid_route_dev.h's entry of a query and status codes, the walk, the window's origin.  Every
+// value is an exact integer.  (The entry points' shared argument checks are host code: walk_args.h.)
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "../../include/mmd_amd.h"
+#include "grid_route_dev.h"
 
 namespace mmd {
 
-constexpr int WG_THREADS = 64;
-constexpr int WG_UNREACHED = MMD_GRID_DIST_UNREACHED;
-constexpr int WG_OK = 0, WG_UNREACHED_START = 1, WG_STUCK = 2, WG_OUTSIDE = 4;       // the status codes of mmd_grid_descend
+constexpr int WG_THREADS = WALK_THREADS;
 
 // One step of the walk from cell (ix, iy), whose neighbours on a shortest path hold `want` (= d - 1, d >= 1 the cell's own value): the
 // neighbours that lie inside the grid and hold exactly `want`, the first of +x, -x and the first of +y, -y; the axis on which the
@@ -33,19 +33,19 @@ __device__ __forceinline__ int window_step(const int* __restrict__ dist, int nx,
   return 1;
 }
 
-// The walk of a query from s with d0 = dist[s] != WG_UNREACHED: at most min(max_steps, d0) steps (d falls by one per step, so the loop
-// counter IS d0 - d; d0 <= 0: no step).  (ix, iy) is the last cell reached, `steps` the steps taken; returns WG_OK or WG_STUCK.
+// The walk of a query from s with d0 = dist[s] != GRID_UNREACHED: at most min(max_steps, d0) steps (d falls by one per step, so the loop
+// counter IS d0 - d; d0 <= 0: no step).  (ix, iy) is the last cell reached, `steps` the steps taken; returns WALK_OK or WALK_STUCK.
 __device__ __forceinline__ int window_walk(const int* __restrict__ dist, int nx, int ny, int2 s, int2 g, int reach, int max_steps, int d0,
                                            int& ix, int& iy, int& steps) {
   ix = s.x; iy = s.y; steps = 0;
   const int bound = min(max_steps, d0);
   for (int k = 0; k < bound; ++k) {
     const int r = window_step(dist, nx, ny, s, g, reach, d0 - k - 1, ix, iy);
-    if (r < 0) return WG_STUCK;
+    if (r < 0) return WALK_STUCK;
     if (r == 0) break;
     ++steps;
   }
-  return WG_OK;
+  return WALK_OK;
 }
 
 // the origin cell of the window of `window` cells per side round the start s, clamped to the grid

@@ -8,7 +8,8 @@ WorldRobotSampler on the windows, and moves the robots to the ends of the return
 its goal.
 
 The numpy function window_goal IS the definition of the sub-goal and the window; the kernel (csrc/window_goals.hip) computes the same
-integers, and the tests hold it to equality.
+integers, and the tests hold it to equality.  Every definition below stands on one function, _walks, which walks every query once and
+keeps its cell path; _path_samples gives the support cells of paths cut at k, _blockers a robot's blockers.
 
   c0 = start, d0 = dist[c0], h = window // 2
   walk    from c = c0 with d = dist[c], while d > 0 and steps < max_steps: the candidates are the neighbours of c inside the grid that
@@ -37,15 +38,15 @@ holds `remaining`, so calls repeated from the cell reached arrive after at most 
 
 An epoch may start from its walk instead of from noise (WorldFleet(seed_epochs=True)).  window_goal_samples keeps 64 support cells of the
 walk's cell path and window_seed turns them into a smoothed chain of points with velocities inside the robot's window; these two numpy
-functions are definitions as well, and mmd_grid_window_goal_samples and mmd_window_seeds (csrc/window_seeds.hip) compute the same
-integers and the same float32 bits.
+functions are definitions as well, and mmd_grid_window_goal_samples (csrc/window_goals.hip: one body with mmd_grid_window_goals' kernel)
+and mmd_window_seeds (csrc/window_seeds.hip) compute the same integers and the same float32 bits.
 
 SEPARATION (WorldFleet(separation=), opt-in).  An epoch pins both ends of every path, and each walk ignores every other robot: two plain
 sub-goals may be one cell, or closer than the robot-robot margin, and then the epoch has a conflict pinned at t = 63 that no sampling
 resolves, and the next epoch has it pinned at t = 0.  subgoals_apart IS the definition of the sub-goals kept `sep` cells apart; the
 kernels (csrc/window_apart.hip) compute the same integers.
 
-  taking part  query q iff window_goal's status for it is ROUTE_OK; its walk is _walk's cell path c_q[0 .. walked_q], c_q[0] the start
+  taking part  query q iff window_goal's status for it is ROUTE_OK; its walk is _walks' cell path c_q[0 .. walked_q], c_q[0] the start
   conflict     two cells with dx^2 + dy^2 < sep^2, in integers
   blockers     of robot r, the robots taken in index order (a lower index has priority): the CHOSEN cells of the taking-part robots
                j < r and the START cells of the taking-part robots j > r
@@ -122,74 +123,74 @@ def _walk(dist, start, goal, d0, reach, max_steps):
     return path, status
 
 
+def _walks(what, dist, starts, fields, goals, reach, max_steps, window):
+    """(window_goals' three arrays, [the cell path c_0 = start .. c_steps of every query whose status is ROUTE_OK, else None]): every
+    query walked once, under the caller's name `what`"""
+    dist = np.asarray(dist)
+    starts, goals = np.asarray(starts, np.int64).reshape(-1, 2), np.asarray(goals, np.int64).reshape(-1, 2)
+    fields = np.asarray(fields, np.int64).reshape(-1)
+    n_fields, nx, ny = dist.shape
+    reach, max_steps, window = _checked_walk_args(what, (nx, ny), reach, max_steps, window)
+    n = len(starts)
+    cells, origins, summary, paths = np.zeros((n, 2), np.int32), np.zeros((n, 2), np.int32), np.zeros((n, 4), np.int32), [None] * n
+    for q in range(n):
+        f, (x0, y0) = int(fields[q]), (int(starts[q][0]), int(starts[q][1]))
+        steps, remaining, status = -1, -1, ROUTE_OUTSIDE
+        if 0 <= f < n_fields and 0 <= x0 < nx and 0 <= y0 < ny:
+            d0, status = int(dist[f, x0, y0]), ROUTE_UNREACHED
+            if d0 != UNREACHED:
+                path, status = _walk(dist[f], (x0, y0), (int(goals[f][0]), int(goals[f][1])), d0, reach, max_steps)
+                steps, remaining = len(path) - 1, d0 - (len(path) - 1)
+                cells[q], origins[q] = path[-1], (min(max(x0 - window // 2, 0), nx - window), min(max(y0 - window // 2, 0), ny - window))
+                paths[q] = path if status == ROUTE_OK else None
+        summary[q] = (steps, remaining, status, int(status == ROUTE_OK and remaining == 0))
+    return (cells, origins, summary), paths
+
+
+def _path_samples(paths, ks):
+    """int32 [n, 64, 2]: the support cells of the paths cut at ks, samples[q, j] = c_q[sample_offsets(ks[q] + 1)[j]] over c_q[0 .. ks[q]];
+    zeros where there is no path"""
+    samples = np.zeros((len(paths), SEED_POINTS, 2), np.int32)
+    for q, path in enumerate(paths):
+        if path is not None:
+            samples[q] = np.asarray(path[:ks[q] + 1], np.int32)[sample_offsets(ks[q] + 1)]
+    return samples
+
+
 def window_goal(dist, start, goal, reach, max_steps, window=400):
     """(cell (ix, iy), origin (i0, j0), steps, remaining, status): the next sub-goal and the window of a robot at the cell `start`, from
     the converged field dist [nx, ny] of the goal cell `goal` (the module's docstring).  status: ROUTE_OK; ROUTE_OUTSIDE (the start is not
     a cell of the grid) and ROUTE_UNREACHED (dist[start] is UNREACHED): steps = remaining = -1, cell and origin (0, 0); ROUTE_STUCK (no
     neighbour holds d - 1: the field was not converged; the outputs are what the walk covered)."""
-    dist = np.asarray(dist)
-    nx, ny = dist.shape
-    reach, max_steps, window = _checked_walk_args("window_goal", (nx, ny), reach, max_steps, window)
-    x0, y0 = int(start[0]), int(start[1])
-    gx, gy = int(goal[0]), int(goal[1])
-    if not (0 <= x0 < nx and 0 <= y0 < ny):
-        return (0, 0), (0, 0), -1, -1, ROUTE_OUTSIDE
-    d0 = int(dist[x0, y0])
-    if d0 == UNREACHED:
-        return (0, 0), (0, 0), -1, -1, ROUTE_UNREACHED
-    origin = (min(max(x0 - window // 2, 0), nx - window), min(max(y0 - window // 2, 0), ny - window))
-    path, status = _walk(dist, (x0, y0), (gx, gy), d0, reach, max_steps)
-    steps = len(path) - 1
-    return path[-1], origin, steps, d0 - steps, status
+    return window_goal_samples(dist, start, goal, reach, max_steps, window)[:5]
 
 
 def window_goals(dist, starts, fields, goals, reach, max_steps, window=400):
     """(cells int32 [n, 2], origins int32 [n, 2], summary int32 [n, 4] = (steps, remaining, status, arrived)): window_goal for query q from
     starts[q] in field dist[fields[q]] of the goal cell goals[fields[q]]; dist [n_fields, nx, ny], goals [n_fields, 2].  A field index
     outside [0, n_fields) gives ROUTE_OUTSIDE.  arrived = 1 iff the status is ROUTE_OK and remaining == 0."""
-    dist = np.asarray(dist)
-    starts, goals = np.asarray(starts, np.int64).reshape(-1, 2), np.asarray(goals, np.int64).reshape(-1, 2)
-    fields = np.asarray(fields, np.int64).reshape(-1)
-    _checked_walk_args("window_goals", dist.shape[1:], reach, max_steps, window)
-    n = len(starts)
-    cells, origins, summary = np.zeros((n, 2), np.int32), np.zeros((n, 2), np.int32), np.zeros((n, 4), np.int32)
-    for q in range(n):
-        f = int(fields[q])
-        if 0 <= f < dist.shape[0]:
-            cells[q], origins[q], steps, remaining, status = window_goal(dist[f], starts[q], goals[f], reach, max_steps, window)
-        else:
-            steps, remaining, status = -1, -1, ROUTE_OUTSIDE
-        summary[q] = (steps, remaining, status, int(status == ROUTE_OK and remaining == 0))
-    return cells, origins, summary
+    return _walks("window_goals", dist, starts, fields, goals, reach, max_steps, window)[0]
 
 
 def window_goal_samples(dist, start, goal, reach, max_steps, window=400):
     """(cell, origin, steps, remaining, status, samples int32 [64, 2]): window_goal with the support cells of the walk's cell path.  The
-    walk is window_goal's, rule for rule, and the first five results are window_goal's.  The cell path is c_0 = start .. c_steps = cell,
-    and samples[j] = c[sample_offsets(steps + 1)[j]] = c[(j * steps + 31) // 63]: the route seeds' spacing (world_routes.sample_offsets),
+    first five results are window_goal's.  The cell path is c_0 = start .. c_steps = cell, and
+    samples[j] = c[sample_offsets(steps + 1)[j]] = c[(j * steps + 31) // 63]: the route seeds' spacing (world_routes.sample_offsets),
     samples[0] the start and samples[63] the sub-goal cell, every cell of the path while steps <= 63.  With a status other than ROUTE_OK
     (a stuck walk included) there are no samples: all zero, as descend_samples gives none."""
-    cell, origin, steps, remaining, status = window_goal(dist, start, goal, reach, max_steps, window)
-    samples = np.zeros((SEED_POINTS, 2), np.int32)
-    if status == ROUTE_OK:
-        x0, y0 = int(start[0]), int(start[1])
-        path, _ = _walk(np.asarray(dist), (x0, y0), (int(goal[0]), int(goal[1])), int(dist[x0, y0]), int(reach), int(max_steps))
-        samples[:] = np.asarray(path, np.int32)[sample_offsets(steps + 1)]
-    return cell, origin, steps, remaining, status, samples
+    nx, ny = np.asarray(dist).shape
+    (cells, origins, summary), paths = _walks("window_goal", np.asarray(dist).reshape(1, nx, ny), [[int(start[0]), int(start[1])]], [0],
+                                              [[int(goal[0]), int(goal[1])]], reach, max_steps, window)
+    steps, remaining, status = (int(v) for v in summary[0, :3])
+    return (tuple(int(v) for v in cells[0]), tuple(int(v) for v in origins[0]), steps, remaining, status,
+            _path_samples(paths, summary[:, 0])[0])
 
 
 def window_goals_samples(dist, starts, fields, goals, reach, max_steps, window=400):
     """(cells, origins, summary, samples int32 [n, 64, 2]): window_goal_samples for every query; the first three results are window_goals'
     word for word."""
-    dist = np.asarray(dist)
-    starts, goals = np.asarray(starts, np.int64).reshape(-1, 2), np.asarray(goals, np.int64).reshape(-1, 2)
-    fields = np.asarray(fields, np.int64).reshape(-1)
-    cells, origins, summary = window_goals(dist, starts, fields, goals, reach, max_steps, window)
-    samples = np.zeros((len(starts), SEED_POINTS, 2), np.int32)
-    for q in np.flatnonzero(summary[:, 2] == ROUTE_OK):
-        f = int(fields[q])
-        samples[q] = window_goal_samples(dist[f], starts[q], goals[f], reach, max_steps, window)[5]
-    return cells, origins, summary, samples
+    plain, paths = _walks("window_goals", dist, starts, fields, goals, reach, max_steps, window)
+    return plain + (_path_samples(paths, plain[2][:, 0]),)
 
 
 def window_seed(tex, lo, hi, samples, origin, window, start_point, goal_point, clearance=OBSTACLE_MARGIN, smooth_iters=64, dt=5.0 / 64):
@@ -222,20 +223,6 @@ def _checked_sep(what, sep):
     return int(sep)
 
 
-def _apart_walks(dist, starts, fields, goals, reach, max_steps, window):
-    """(window_goals' three outputs, [the cell path of every query that takes part, else None])"""
-    dist = np.asarray(dist)
-    starts, goals = np.asarray(starts, np.int64).reshape(-1, 2), np.asarray(goals, np.int64).reshape(-1, 2)
-    fields = np.asarray(fields, np.int64).reshape(-1)
-    cells, origins, summary = window_goals(dist, starts, fields, goals, reach, max_steps, window)
-    paths = [None] * len(starts)
-    for q in np.flatnonzero(summary[:, 2] == ROUTE_OK):
-        f, (x0, y0) = int(fields[q]), (int(starts[q][0]), int(starts[q][1]))
-        paths[q], _ = _walk(dist[f], (x0, y0), (int(goals[f][0]), int(goals[f][1])), int(dist[f][x0, y0]), int(reach), int(max_steps))
-        assert len(paths[q]) - 1 == summary[q, 0]
-    return (cells, origins, summary), paths
-
-
 def _apart_choice(path, blockers, sep):
     """(k, clear) of one robot: the largest k in [1, walked] whose cell conflicts with no blocker, else 0; clear: the chosen cell conflicts
     with none.  Two cells conflict iff dx^2 + dy^2 < sep^2."""
@@ -243,6 +230,11 @@ def _apart_choice(path, blockers, sep):
     free = (((cells - others) ** 2).sum(-1) >= sep * sep).all(1)             # per cell of the path: it conflicts with no blocker
     feasible = np.flatnonzero(free[1:])
     return (int(feasible[-1]) + 1, 1) if feasible.size else (0, int(free[0]))
+
+
+def _blockers(paths, taking, ks, r):
+    """the blockers of robot r: the cells at ks of the taking-part robots j < r and the start cells of the taking-part robots j > r"""
+    return [paths[j][ks[j]] for j in taking if j < r] + [paths[j][0] for j in taking if j > r]
 
 
 def _apart_outputs(plain, paths, ks, clear):
@@ -264,14 +256,7 @@ def subgoals_apart(dist, starts, fields, goals, reach, max_steps, sep, window=40
     in index order, robot r against the chosen cells of the taking-part robots j < r and the start cells of the taking-part robots j > r,
     and takes the largest k in [1, walked] whose cell conflicts with none of them, else 0.  summary = (k, d0 - k, status, arrived) in
     window_goals' format, extra = (walked, clear).  A query that does not take part keeps window_goals' words, with extra (steps, 0)."""
-    sep = _checked_sep("subgoals_apart", sep)
-    plain, paths = _apart_walks(dist, starts, fields, goals, reach, max_steps, window)
-    taking = [q for q, p in enumerate(paths) if p is not None]
-    ks, clear = {}, {}
-    for r in taking:
-        blockers = [paths[j][ks[j]] for j in taking if j < r] + [paths[j][0] for j in taking if j > r]
-        ks[r], clear[r] = _apart_choice(paths[r], blockers, sep)
-    return _apart_outputs(plain, paths, ks, clear)
+    return subgoals_apart_samples(dist, starts, fields, goals, reach, max_steps, sep, window)[:4]
 
 
 def subgoals_apart_sweeps(dist, starts, fields, goals, reach, max_steps, sep, n_sweeps, window=400, with_samples=False):
@@ -283,73 +268,79 @@ def subgoals_apart_sweeps(dist, starts, fields, goals, reach, max_steps, sep, n_
     sep = _checked_sep("subgoals_apart_sweeps", sep)
     if int(n_sweeps) < 0:
         raise ValueError(f"subgoals_apart_sweeps: n_sweeps = {n_sweeps} (>= 0)")
-    plain, paths = _apart_walks(dist, starts, fields, goals, reach, max_steps, window)
+    plain, paths = _walks("window_goals", dist, starts, fields, goals, reach, max_steps, window)
     taking = [q for q, p in enumerate(paths) if p is not None]
     ks = {q: len(paths[q]) - 1 for q in taking}
     clear, changed = {q: 0 for q in taking}, len(taking)
     for _ in range(int(n_sweeps)):
         new = {}
         for r in taking:
-            blockers = [paths[j][ks[j]] for j in taking if j < r] + [paths[j][0] for j in taking if j > r]
-            new[r], clear[r] = _apart_choice(paths[r], blockers, sep)
+            new[r], clear[r] = _apart_choice(paths[r], _blockers(paths, taking, ks, r), sep)
         changed = sum(new[q] != ks[q] for q in taking)
         ks = new
-    out = _apart_outputs(plain, paths, ks, clear) + (changed,)
-    if with_samples:
-        samples = np.zeros((len(paths), SEED_POINTS, 2), np.int32)
-        for q in taking:
-            samples[q] = np.asarray(paths[q][:ks[q] + 1], np.int32)[sample_offsets(ks[q] + 1)]
-        out += (samples,)
-    return out
+    return _apart_outputs(plain, paths, ks, clear) + (changed,) + ((_path_samples(paths, ks),) if with_samples else ())
 
 
 def subgoals_apart_samples(dist, starts, fields, goals, reach, max_steps, sep, window=400):
     """(cells, origins, summary, extra, samples int32 [n, 64, 2]): subgoals_apart with the support cells of the shortened walks,
     samples[j] = c[(j * k + 31) // 63] over c[0 .. k]: window_goal_samples' spacing.  A query that does not take part gets zeros."""
-    cells, origins, summary, extra = subgoals_apart(dist, starts, fields, goals, reach, max_steps, sep, window)
-    _, paths = _apart_walks(dist, starts, fields, goals, reach, max_steps, window)
-    samples = np.zeros((len(paths), SEED_POINTS, 2), np.int32)
-    for q, path in enumerate(paths):
-        if path is not None:
-            k = int(summary[q, 0])
-            samples[q] = np.asarray(path[:k + 1], np.int32)[sample_offsets(k + 1)]
-    return cells, origins, summary, extra, samples
+    sep = _checked_sep("subgoals_apart", sep)
+    plain, paths = _walks("window_goals", dist, starts, fields, goals, reach, max_steps, window)
+    taking = [q for q, p in enumerate(paths) if p is not None]
+    ks, clear = {}, {}
+    for r in taking:
+        ks[r], clear[r] = _apart_choice(paths[r], _blockers(paths, taking, ks, r), sep)
+    return _apart_outputs(plain, paths, ks, clear) + (_path_samples(paths, ks),)
 
 
 # ---- the same on the device ----------------------------------------------------------------------------------------------------------------
-def _window_goals_words(dist_dev, starts, fields, goals, reach, max_steps, window, with_samples=False, what="device_window_goals"):
-    """device_window_goals' launch -> one int32 tensor [8 n] on the device: cells [n, 2], then origins [n, 2], then summary [n, 4].
-    with_samples: device_window_goal_samples' launch (mmd_grid_window_goal_samples) -> (that tensor, samples int32 [n, 64, 2])"""
+def _checked_launch_args(what, dist_dev, reach, max_steps, window):
+    """(reach, max_steps, window) as ints, after the checks of dist_dev and of the walk's arguments under the name `what`: the first
+    refusals of every sub-goal launch, before anything is uploaded"""
     if dist_dev.dim() != 3 or dist_dev.dtype != torch.int32 or not dist_dev.is_cuda or not dist_dev.is_contiguous():
         raise ValueError(f"{what}: dist must be a contiguous int32 CUDA(HIP) tensor [n_fields, nx, ny]")
-    reach, max_steps, window = _checked_walk_args(what, tuple(dist_dev.shape[1:]), reach, max_steps, window)
+    return _checked_walk_args(what, tuple(dist_dev.shape[1:]), reach, max_steps, window)
+
+
+def _walk_launch_args(what, dist_dev, starts, fields, goals, reach, max_steps, window):
+    """(the eleven leading arguments of the three sub-goal entry points, n, the uploaded starts, fields and goals behind three of them:
+    hold them until the launch); reach, max_steps and window are _checked_launch_args' """
     starts_dev = _int32_dev(starts, (-1, 2), dist_dev.device, f"{what}: starts")
     n = starts_dev.shape[0]
     fields_dev = _int32_dev(fields, (n,), dist_dev.device, f"{what}: fields")
     goals_dev = _int32_dev(goals, (int(dist_dev.shape[0]), 2), dist_dev.device, f"{what}: goals")
+    lead = (C.c_void_p(dist_dev.data_ptr()), int(dist_dev.shape[1]), int(dist_dev.shape[2]), int(dist_dev.shape[0]),
+            C.c_void_p(starts_dev.data_ptr()), C.c_void_p(fields_dev.data_ptr()), C.c_void_p(goals_dev.data_ptr()), n, reach, max_steps, window)
+    return lead, n, (starts_dev, fields_dev, goals_dev)
+
+
+def _window_goals_words(dist_dev, starts, fields, goals, reach, max_steps, window, with_samples=False, what="device_window_goals"):
+    """device_window_goals' launch -> (one int32 tensor [8 n] on the device: cells [n, 2], then origins [n, 2], then summary [n, 4]; None).
+    with_samples: device_window_goal_samples' launch (mmd_grid_window_goal_samples) -> (that tensor, samples int32 [n, 64, 2])"""
+    lead, n, _uploads = _walk_launch_args(what, dist_dev, starts, fields, goals, *_checked_launch_args(what, dist_dev, reach, max_steps, window))
     words = torch.empty(8 * n, dtype=torch.int32, device=dist_dev.device)        # (the summary rows start 16 n bytes in: aligned as int4)
     at = lambda k: C.c_void_p(words.data_ptr() + 4 * k)                          # noqa: E731
-    args = (C.c_void_p(dist_dev.data_ptr()), int(dist_dev.shape[1]), int(dist_dev.shape[2]), int(dist_dev.shape[0]),
-            C.c_void_p(starts_dev.data_ptr()), C.c_void_p(fields_dev.data_ptr()), C.c_void_p(goals_dev.data_ptr()), n, reach, max_steps, window,
-            at(0), at(2 * n), at(4 * n))
     if not with_samples:
-        _lib.launch("mmd_grid_window_goals", dist_dev, *args)
-        return words
+        _lib.launch("mmd_grid_window_goals", dist_dev, *lead, at(0), at(2 * n), at(4 * n))
+        return words, None
     samples = torch.empty(n, SEED_POINTS, 2, dtype=torch.int32, device=dist_dev.device)
-    _lib.launch("mmd_grid_window_goal_samples", dist_dev, *args, C.c_void_p(samples.data_ptr()))
+    _lib.launch("mmd_grid_window_goal_samples", dist_dev, *lead, at(0), at(2 * n), at(4 * n), C.c_void_p(samples.data_ptr()))
     return words, samples
 
 
-def _split_words(words):
-    n = words.shape[0] // 8
-    return words[:2 * n].reshape(n, 2), words[2 * n:4 * n].reshape(n, 2), words[4 * n:].reshape(n, 4)
+def _split_words(words, apart=False):
+    """(cells [n, 2], origins [n, 2], summary [n, 4][, extra [n, 2]]), views of a sub-goal launch's words, a tensor or its numpy copy:
+    [8 n], or with `apart` mmd_grid_window_goals_apart's [10 n + 1], with extra and changed behind"""
+    n = (words.shape[0] - 1) // 10 if apart else words.shape[0] // 8
+    out = words[:2 * n].reshape(n, 2), words[2 * n:4 * n].reshape(n, 2), words[4 * n:8 * n].reshape(n, 4)
+    return out + ((words[8 * n:10 * n].reshape(n, 2),) if apart else ())
 
 
 def device_window_goals(dist_dev, starts, fields, goals, reach, max_steps, window=400):
     """(cells int32 [n, 2], origins int32 [n, 2], summary int32 [n, 4]) on dist_dev's device: window_goals() for every query in one launch
     (mmd_grid_window_goals), word for word.  dist_dev: any int32 fields [n_fields, nx, ny] (device_distance_field's, or hand-built
     ones); goals [n_fields, 2]: the fields' goal cells.  The three results are views of one tensor."""
-    return _split_words(_window_goals_words(dist_dev, starts, fields, goals, reach, max_steps, window))
+    return _split_words(_window_goals_words(dist_dev, starts, fields, goals, reach, max_steps, window)[0])
 
 
 def device_window_goal_samples(dist_dev, starts, fields, goals, reach, max_steps, window=400):
@@ -429,16 +420,11 @@ def device_epoch_frames(name, words, points, goal_points, norm_mins=synth.NORM_M
 def _subgoals_apart_words(dist_dev, starts, fields, goals, reach, max_steps, sep, window, sweeps, with_samples, what="device_subgoals_apart"):
     """device_subgoals_apart's launches -> (one int32 tensor [10 n + 1] on the device: cells [n, 2], origins [n, 2], summary [n, 4],
     extra [n, 2], changed [1]; its last copy on the host, numpy; samples int32 [n, 64, 2] on the device or None; the sweeps run)"""
-    if dist_dev.dim() != 3 or dist_dev.dtype != torch.int32 or not dist_dev.is_cuda or not dist_dev.is_contiguous():
-        raise ValueError(f"{what}: dist must be a contiguous int32 CUDA(HIP) tensor [n_fields, nx, ny]")
-    reach, max_steps, window = _checked_walk_args(what, tuple(dist_dev.shape[1:]), reach, max_steps, window)
+    reach, max_steps, window = _checked_launch_args(what, dist_dev, reach, max_steps, window)
     sep, sweeps = _checked_sep(what, sep), int(sweeps)
     if max_steps > _lib.WINDOW_APART_MAX_STEPS or sweeps < 1:
         raise ValueError(f"{what}: max_steps = {max_steps} (at most {_lib.WINDOW_APART_MAX_STEPS}), sweeps = {sweeps} (at least 1)")
-    starts_dev = _int32_dev(starts, (-1, 2), dist_dev.device, f"{what}: starts")
-    n = starts_dev.shape[0]
-    fields_dev = _int32_dev(fields, (n,), dist_dev.device, f"{what}: fields")
-    goals_dev = _int32_dev(goals, (int(dist_dev.shape[0]), 2), dist_dev.device, f"{what}: goals")
+    lead, n, _uploads = _walk_launch_args(what, dist_dev, starts, fields, goals, reach, max_steps, window)
     work_bytes = int(_lib.load().mmd_grid_window_apart_work_bytes(n, max_steps))
     work = torch.empty(work_bytes, dtype=torch.uint8, device=dist_dev.device)
     words = torch.empty(10 * n + 1, dtype=torch.int32, device=dist_dev.device)     # (the summary rows start 16 n bytes in: aligned as int4)
@@ -446,10 +432,8 @@ def _subgoals_apart_words(dist_dev, starts, fields, goals, reach, max_steps, sep
     at = lambda k: C.c_void_p(words.data_ptr() + 4 * k)                          # noqa: E731
 
     def launch(restart, n_sweeps):
-        _lib.launch("mmd_grid_window_goals_apart", dist_dev, C.c_void_p(dist_dev.data_ptr()), int(dist_dev.shape[1]), int(dist_dev.shape[2]),
-                    int(dist_dev.shape[0]), C.c_void_p(starts_dev.data_ptr()), C.c_void_p(fields_dev.data_ptr()),
-                    C.c_void_p(goals_dev.data_ptr()), n, reach, max_steps, window, sep, restart, n_sweeps, C.c_void_p(work.data_ptr()),
-                    work_bytes, at(0), at(2 * n), at(4 * n), at(8 * n), C.c_void_p(samples.data_ptr()) if with_samples else None, at(10 * n))
+        _lib.launch("mmd_grid_window_goals_apart", dist_dev, *lead, sep, restart, n_sweeps, C.c_void_p(work.data_ptr()), work_bytes, at(0),
+                    at(2 * n), at(4 * n), at(8 * n), C.c_void_p(samples.data_ptr()) if with_samples else None, at(10 * n))
         return words.cpu().numpy()
     run = min(sweeps, n + 1)
     host = launch(1, run)
@@ -461,11 +445,6 @@ def _subgoals_apart_words(dist_dev, starts, fields, goals, reach, max_steps, sep
     return words, host, samples, run
 
 
-def _split_apart_words(words):
-    n = (words.shape[0] - 1) // 10
-    return _split_words(words[:8 * n]) + (words[8 * n:10 * n].reshape(n, 2),)
-
-
 def device_subgoals_apart(dist_dev, starts, fields, goals, reach, max_steps, sep, window=400, sweeps=4, with_samples=False):
     """(cells int32 [n, 2], origins int32 [n, 2], summary int32 [n, 4], extra int32 [n, 2][, samples int32 [n, 64, 2]], n_sweeps_run) on
     dist_dev's device: subgoals_apart() (with samples: subgoals_apart_samples()) for every query, word for word, by
@@ -474,19 +453,19 @@ def device_subgoals_apart(dist_dev, starts, fields, goals, reach, max_steps, sep
     device_window_goals refuses them.  Every call ends with one device -> host copy of all words, extra
     and changed, which live in one tensor: the common case costs one copy.  The first four results are views of that tensor."""
     words, _, samples, run = _subgoals_apart_words(dist_dev, starts, fields, goals, reach, max_steps, sep, window, sweeps, with_samples)
-    return _split_apart_words(words) + ((samples,) if with_samples else ()) + (run,)
+    return _split_words(words, apart=True) + ((samples,) if with_samples else ()) + (run,)
 
 
 # ---- the fleet -----------------------------------------------------------------------------------------------------------------------------
 class EpochTargets(NamedTuple):
-    """What one epoch plans towards (WorldFleet.epoch_targets), numpy on the host."""
+    """What one epoch plans towards (WorldFleet.epoch_targets): numpy on the host, and the launch's own tensors on the device."""
     cells: np.ndarray           # int32 [N, 2]: the sub-goal cells in the world
     origins: np.ndarray         # int32 [N, 2]: the windows' origin cells
     offsets: np.ndarray         # float32 [N, 2]: the windows' offsets (environments.world_map_window_offsets)
     points: np.ndarray          # float32 [N, 2]: the sub-goal points, global: the cell's centre, or the robot's exact goal once `arrived`
     summary: np.ndarray         # int32 [N, 4]: (steps, remaining, status, arrived)
     samples: torch.Tensor = None    # seed_epochs: int32 [N, 64, 2] on the device, the walks' support cells (never copied back); else None
-    words: torch.Tensor = None      # seed_epochs: int32 [8 N] on the device, (cells, origins, summary) as launched (_split_words); else None
+    words: torch.Tensor = None      # int32 [8 N] on the device, (cells, origins, summary) as launched (_split_words); with separation a view
     extra: np.ndarray = None        # separation: int32 [N, 2] = (walked, clear) of subgoals_apart; else None
     sweeps: int = None              # separation: the sweeps device_subgoals_apart ran; else None
 
@@ -522,36 +501,43 @@ class WorldFleet:
     noise runs T + 1 (26 at the released T = 25).  An arrived robot has steps = 0: all 64 samples are its goal cell, so its seed
     runs from its goal point to its goal point inside that one cell (the cell's centre in between, drawn towards the goal point by the
     smoothing) with velocities of at most half a cell over 2 dt; that is "held still" as far as a seed goes, and the robot is still
-    sampled between its two pinned ends.
-    With seed_epochs=False (the default) nothing of this runs: the code path is the one without the option.
+    sampled between its two pinned ends.  With seed_epochs=False (the default) nothing of this runs.
 
-    separation=None (the default) runs exactly the code path without the option.  An int >= 1 (SUBGOAL_SEPARATION = 23 keeps the pinned
-    ends RR_MARGIN apart) keeps every epoch's sub-goals that many cells apart (the module's docstring, SEPARATION): the constructor refuses,
-    naming both robots, two start cells or two goal cells closer than that, and max_steps above 4095; epoch_targets runs
+    separation=None (the default): every robot's sub-goal is its walk's end, whatever the others do.  An int >= 1
+    (SUBGOAL_SEPARATION = 23 keeps the pinned ends RR_MARGIN apart) keeps every epoch's sub-goals that many cells apart (the module's
+    docstring, SEPARATION): the constructor refuses, naming both robots, two start cells or two goal cells closer than that, and
+    max_steps above 4095; epoch_targets runs
     device_subgoals_apart (mmd_grid_window_goals_apart: a restart call of 4 sweeps and, while robots still moved, 4 more) in place of
     mmd_grid_window_goals, with seed_epochs with the samples of the shortened walks, so that mmd_window_seeds, unchanged, builds the seeds
     on them; EpochTargets gains `extra` (walked, clear) and `sweeps`, every epoch's dict "held_back" (walked - k per robot), "sweeps" and
     "stalled"; run(max_epochs=None) loops until every robot has arrived or an epoch is stalled (no robot moves, every k is 0: the
     state would repeat for good), which terminates although epoch_bound no longer holds; an explicit max_epochs still caps it.
 
-    persistent=False (the default) runs exactly the code path without the option: every epoch builds a WorldRobotSampler, a guide and a
-    named window set of its own and releases the set afterwards.  persistent=True keeps ONE sampler (own_windows=True), one guide and
+    persistent=False (the default): every epoch builds a WorldRobotSampler, a guide and a named window set of its own and releases the
+    set afterwards.  persistent=True keeps ONE sampler (own_windows=True), one guide and
     one window set [N, 1, 400, 400, 4] (slice r is robot r's) for the whole run and moves them between epochs on the device
-    (_step_persistent): every result -- paths, conflict counts, summaries, offsets, clear_min -- is the default's bit for bit, with
+    (_moved_sampler): every result -- paths, conflict counts, summaries, offsets, clear_min -- is the default's bit for bit, with
     seed_epochs and separation as well; only the time and the memory traffic differ.  close() releases the set, and run()
     closes when it returns; a neighbor_slots= smaller than some epoch needs is refused by the sampler's own message, in that epoch.
 
-    Out of scope here: an arrived robot is sampled like any other, between two ends pinned to its goal point, not held still; the fleet is not sharded over ranks;
-    repair= and replan=, which WorldRobotSampler refuses; with separation=, a stalled fleet is reported, not resolved (the priorities are
-    the robots' indices and never rotate, and no robot steps aside), and without it two sub-goals may coincide.  Whether a seeded epoch resolves conflicts as well as one from noise is not
-    known."""
+    The three options share one epoch_targets, one step and one run; each is a branch where its launch, its sampler or its stop rule
+    differs.  EpochTargets.words is the sub-goal launch's device words [8 N] under every option (they were None without seed_epochs
+    while only the seeded epoch read them; the persistent step reads them as well).
+
+    Out of scope here:
+      - an arrived robot is sampled like any other, between two ends pinned to its goal point, not held still;
+      - the fleet is not sharded over ranks;
+      - repair= and replan=, which WorldRobotSampler refuses;
+      - with separation=, a stalled fleet is reported, not resolved (the priorities are the robots' indices and never rotate, and no
+        robot steps aside); without it two sub-goals may coincide.
+    Whether a seeded epoch resolves conflicts as well as one from noise is not known."""
 
     def __init__(self, model, name, starts, goals, clearance=OBSTACLE_MARGIN, reach=180, max_steps=360, device="cuda", seed_epochs=False,
                  smooth_iters=64, n_noising_steps=3, n_denoising_steps=3, separation=None, persistent=False,
                  **world_robot_sampler_kwargs):
         self.model, self.name, self.device = model, name, environments.resolved_device(device)
         self.persistent = bool(persistent)
-        self._sampler = self._points_dev = self._points_host = self._goal_points_dev = self._line_a = self._epoch_words = None
+        self._sampler = self._points_dev = self._points_host = self._goal_points_dev = self._line_a = None
         self.separation = None if separation is None else _checked_sep("WorldFleet: separation", separation)
         self.clearance = float(clearance)
         self.seed_epochs = bool(seed_epochs)
@@ -623,27 +609,23 @@ class WorldFleet:
         return max(1, max(epoch_bound(d, self.reach, self.max_steps) for d in self.start_distances.tolist()))
 
     def epoch_targets(self, positions):
-        """EpochTargets of the robots at the global points `positions` [N, 2]: one mmd_grid_window_goals launch (with seed_epochs: one
-        mmd_grid_window_goal_samples launch, the same words and the samples, which stay on the device) and one device -> host copy.  A
-        robot's cell is world_cells' texel of its point; its sub-goal point is the centre of the sub-goal cell by cell_centres' fp32
-        sequence, or, once the sub-goal cell is the goal's (`arrived`), the caller's exact goal point."""
+        """EpochTargets of the robots at the global points `positions` [N, 2]: one sub-goal launch -- mmd_grid_window_goals; with
+        seed_epochs mmd_grid_window_goal_samples, the same words and the samples, which stay on the device; with separation
+        device_subgoals_apart's launches (with seed_epochs: with the samples of the shortened walks), whose summary is
+        (k, d0 - k, status, arrived) -- and one device -> host copy (with separation: one per call of the entry point).  A robot's cell
+        is world_cells' texel of its point; its sub-goal point is the centre of the sub-goal cell by cell_centres' fp32 sequence, or,
+        once the sub-goal cell is the goal's (`arrived`), the caller's exact goal point.  Refuses a robot whose status is not ROUTE_OK."""
         pts = _points(positions)
         if pts.shape[0] != self.n_robots:
             raise ValueError(f"WorldFleet.epoch_targets: {pts.shape[0]} positions for {self.n_robots} robots")
         c0 = self._cells(pts, "position")
-        if self.separation is not None:
-            return self._targets_apart(c0)
-        if self.seed_epochs:
-            words, samples = _window_goals_words(self.dist, c0, self._fields_dev, self._goals_dev, self.reach, self.max_steps, self.window, True)
+        walk = (self.dist, c0, self._fields_dev, self._goals_dev, self.reach, self.max_steps)
+        if self.separation is None:
+            (words, samples), sweeps = _window_goals_words(*walk, self.window, self.seed_epochs), None
+            host = words.cpu().numpy()
         else:
-            words, samples = _window_goals_words(self.dist, c0, self._fields_dev, self._goals_dev, self.reach, self.max_steps, self.window), None
-        self._epoch_words = words                            # (persistent: the frames launch reads them where they are)
-        cells, origins, summary = (a.copy() for a in _split_words(words.cpu().numpy()))
-        return self._targets(c0, cells, origins, summary, samples, words if self.seed_epochs else None)
-
-    def _targets(self, c0, cells, origins, summary, *rest):
-        """EpochTargets from a sub-goal launch's words on the host (`rest`: the fields behind `summary`): refuses a robot whose status is
-        not ROUTE_OK, and gives every robot its sub-goal point"""
+            words, host, samples, sweeps = _subgoals_apart_words(*walk, self.separation, self.window, 4, self.seed_epochs, "WorldFleet")
+        cells, origins, summary, *extra = (a.copy() for a in _split_words(host, apart=self.separation is not None))
         bad = np.flatnonzero(summary[:, 2] != ROUTE_OK)
         if bad.size:
             r = int(bad[0])
@@ -652,58 +634,17 @@ class WorldFleet:
         points = np.ascontiguousarray(cell_centres(cells, self.limits[0], self.limits[1], self.shape), dtype=np.float32)
         arrived = summary[:, 3] == 1
         points[arrived] = self.goal_points[arrived]
-        return EpochTargets(cells, origins, environments.world_map_window_offsets(self.name, origins), points, summary, *rest)
+        return EpochTargets(cells, origins, environments.world_map_window_offsets(self.name, origins), points, summary, samples,
+                            words[:8 * self.n_robots], extra[0] if extra else None, sweeps)
 
-    def _targets_apart(self, c0):
-        """epoch_targets with separation: device_subgoals_apart's launches (with seed_epochs: with the samples of the shortened walks, which
-        stay on the device) in place of mmd_grid_window_goals; the summary is (k, d0 - k, status, arrived)"""
-        words, host, samples, run = _subgoals_apart_words(self.dist, c0, self._fields_dev, self._goals_dev, self.reach, self.max_steps,
-                                                          self.separation, self.window, 4, self.seed_epochs, "WorldFleet")
-        self._epoch_words = words[:8 * self.n_robots]
-        cells, origins, summary, extra = (a.copy() for a in _split_apart_words(host))
-        return self._targets(c0, cells, origins, summary, samples, words[:8 * self.n_robots] if self.seed_epochs else None, extra, run)
-
-    def step(self, seed, max_rounds=8):
-        """One epoch: the targets of the current positions, a WorldRobotSampler from the positions to the sub-goal points on the windows,
-        its plan(max_rounds, seed) -- with seed_epochs its plan_rounds_seeded from the epoch's seeds (the class's docstring) --, and the robots
-        moved to the last points of the returned paths, as they are.  The epoch's window map set is released afterwards
-        (map_textures.release_sdf_textures).  -> (PlanResult, EpochTargets); with seed_epochs `last_clear_min` (float32 [N]) holds the
-        seeds' least texel values, from the copy that brings the new positions back.
-        With persistent=True: the same epoch, bit for bit, on the fleet's one sampler (_step_persistent); nothing is released."""
-        if self.persistent:
-            return self._step_persistent(seed, max_rounds)
-        targets = self.epoch_targets(self.positions)
-        sampler = WorldRobotSampler(self.model, self.positions, targets.points, targets.offsets, env_id=self.name, device=self.device,
-                                    **self.sampler_kwargs)
-        try:
-            if self.seed_epochs:
-                _, origins_dev, summary_dev = _split_words(targets.words)
-                seeds, clear_min = device_window_seeds(map_textures.device_world_texture(self.name, self.device), self.limits[0], self.limits[1],
-                                                       targets.samples, origins_dev, summary_dev, self.window, self.positions, targets.points,
-                                                       self.clearance, self.smooth_iters)
-                res = sampler.plan_rounds_seeded(sampler.trajs_from_global(seeds), paths_local=seeds[..., :2].contiguous(),
-                                                 local_rounds=True, n_noising_steps=self.n_noising_steps,
-                                                 n_denoising_steps=self.n_denoising_steps, max_rounds=max_rounds, seed=seed)
-            else:
-                res = sampler.plan(max_rounds=max_rounds, seed=seed)
-        finally:
-            map_textures.release_sdf_textures(sorted(set(sampler._window_ids)), self.device)
-        if self.seed_epochs:
-            back = torch.cat([res.paths_local[:, -1, :], clear_min[:, None]], dim=1).cpu().numpy()       # one copy: the ends and clear_min
-            self.positions, self.last_clear_min = np.ascontiguousarray(back[:, :2], dtype=np.float32), back[:, 2].copy()
-        else:
-            self.positions = np.ascontiguousarray(res.paths_local[:, -1, :].cpu().numpy(), dtype=np.float32)
-        return res, targets
-
-    def _step_persistent(self, seed, max_rounds):
-        """step() on the one long-lived sampler.  epoch_targets as ever (its one copy back gives the status check, the host origins,
-        the offsets and the slot bound); then one mmd_fleet_epoch_frames launch on the launch's words, the robots' points and their
-        goal points, all on the device, and the sampler moved to what it wrote (WorldRobotSampler._move_on_device: one
-        mmd_sdf_grid_windows_moved launch, which cuts only the slices whose origin changed).  The first epoch builds the sampler
-        with own_windows=True first; its windows then do not move.  No sampler, guide or facade is built, no texture allocated, no
-        window named, no hard condition, offset or line uploaded.  The robots' points of the next epoch are the device slice
-        paths_local[:, -1]; the host copy feeds world_cells and its refusals, as ever."""
-        targets = self.epoch_targets(self.positions)
+    def _moved_sampler(self, targets):
+        """persistent=True: (the fleet's one sampler, moved to the epoch's targets; the robots' points and their sub-goal points [N, 2]
+        on the device; the straight lines between them [N, 64, 2]).  One mmd_fleet_epoch_frames launch on the launch's words, the
+        robots' points and their goal points, all on the device, and the sampler moved to what it wrote
+        (WorldRobotSampler._move_on_device: one mmd_sdf_grid_windows_moved launch, which cuts only the slices whose origin changed).
+        The first epoch builds the sampler with own_windows=True first; its windows then do not move.  No sampler, guide or facade is
+        built, no texture allocated, no window named, no hard condition, offset or line uploaded.  The robots' points of the next
+        epoch are the device slice paths_local[:, -1]; the host copy feeds world_cells and its refusals, as ever."""
         if self._goal_points_dev is None:
             self._goal_points_dev = torch.from_numpy(self.goal_points).to(self.device)
             self._line_a = torch.from_numpy(np.linspace(0.0, 1.0, SEED_POINTS, dtype=np.float32)).to(self.device)
@@ -712,26 +653,52 @@ class WorldFleet:
         if self._sampler is None:
             self._sampler = WorldRobotSampler(self.model, self.positions, targets.points, targets.offsets, env_id=self.name,
                                               device=self.device, own_windows=True, **self.sampler_kwargs)
-        sampler, words = self._sampler, self._epoch_words
         kw = {k: self.sampler_kwargs[k] for k in ("norm_mins", "norm_maxs") if k in self.sampler_kwargs}
-        offsets_dev, points_dev, hard_first, hard_last, lines = device_epoch_frames(self.name, words, self._points_dev, self._goal_points_dev,
-                                                                                   line_a=self._line_a, **kw)
-        _, origins_dev, summary_dev = _split_words(words)
-        sampler._move_on_device((self.positions, targets.points), targets.offsets, targets.origins, offsets_dev, hard_first, hard_last,
-                                origins_dev)
+        offsets_dev, points_dev, hard_first, hard_last, lines = device_epoch_frames(self.name, targets.words, self._points_dev,
+                                                                                   self._goal_points_dev, line_a=self._line_a, **kw)
+        self._sampler._move_on_device((self.positions, targets.points), targets.offsets, targets.origins, offsets_dev, hard_first, hard_last,
+                                      _split_words(targets.words)[1])
+        return self._sampler, self._points_dev, points_dev, lines
+
+    def step(self, seed, max_rounds=8):
+        """One epoch: the targets of the current positions; the epoch's sampler from the positions to the sub-goal points -- a fresh
+        WorldRobotSampler on named windows, whose map set is released afterwards (map_textures.release_sdf_textures), or, with
+        persistent=True, the fleet's one sampler moved in place (_moved_sampler; nothing is released), the same epoch bit for bit --;
+        its plan -- plan(max_rounds, seed) on the fresh sampler, plan_rounds from the straight lines the frames launch wrote on the moved
+        one, and with seed_epochs plan_rounds_seeded from the epoch's seeds on either (the class's docstring); the seeds' ends are the
+        points as they come: host arrays, which device_window_seeds uploads, or the moved sampler's device tensors --; and the robots
+        moved to the last points of the returned paths, as they are.  -> (PlanResult, EpochTargets); with seed_epochs `last_clear_min`
+        (float32 [N]) holds the seeds' least texel values, from the copy that brings the new positions back."""
+        targets = self.epoch_targets(self.positions)
+        if self.persistent:
+            sampler, starts, goals, lines = self._moved_sampler(targets)
+        else:
+            starts, goals = self.positions, targets.points
+            sampler = WorldRobotSampler(self.model, starts, goals, targets.offsets, env_id=self.name, device=self.device, **self.sampler_kwargs)
+        try:
+            if self.seed_epochs:
+                _, origins_dev, summary_dev = _split_words(targets.words)
+                seeds, clear_min = device_window_seeds(map_textures.device_world_texture(self.name, self.device), self.limits[0], self.limits[1],
+                                                       targets.samples, origins_dev, summary_dev, self.window, starts, goals, self.clearance,
+                                                       self.smooth_iters)
+                res = sampler.plan_rounds_seeded(sampler.trajs_from_global(seeds), paths_local=seeds[..., :2].contiguous(),
+                                                 local_rounds=True, n_noising_steps=self.n_noising_steps,
+                                                 n_denoising_steps=self.n_denoising_steps, max_rounds=max_rounds, seed=seed)
+            elif self.persistent:
+                res = sampler.plan_rounds(paths_local=lines, max_rounds=max_rounds, seed=seed)
+            else:
+                res = sampler.plan(max_rounds=max_rounds, seed=seed)
+        finally:
+            if not self.persistent:
+                map_textures.release_sdf_textures(sorted(set(sampler._window_ids)), self.device)
+        ends = res.paths_local[:, -1, :]
         if self.seed_epochs:
-            seeds, clear_min = device_window_seeds(map_textures.device_world_texture(self.name, self.device), self.limits[0], self.limits[1],
-                                                   targets.samples, origins_dev, summary_dev, self.window, self._points_dev, points_dev,
-                                                   self.clearance, self.smooth_iters)
-            res = sampler.plan_rounds_seeded(sampler.trajs_from_global(seeds), paths_local=seeds[..., :2].contiguous(),
-                                             local_rounds=True, n_noising_steps=self.n_noising_steps,
-                                             n_denoising_steps=self.n_denoising_steps, max_rounds=max_rounds, seed=seed)
-            back = torch.cat([res.paths_local[:, -1, :], clear_min[:, None]], dim=1).cpu().numpy()       # one copy: the ends and clear_min
+            back = torch.cat([ends, clear_min[:, None]], dim=1).cpu().numpy()            # one copy: the ends and clear_min
             self.positions, self.last_clear_min = np.ascontiguousarray(back[:, :2], dtype=np.float32), back[:, 2].copy()
         else:
-            res = sampler.plan_rounds(paths_local=lines, max_rounds=max_rounds, seed=seed)
-            self.positions = np.ascontiguousarray(res.paths_local[:, -1, :].cpu().numpy(), dtype=np.float32)
-        self._points_dev, self._points_host = res.paths_local[:, -1, :], self.positions
+            self.positions = np.ascontiguousarray(ends.cpu().numpy(), dtype=np.float32)
+        if self.persistent:
+            self._points_dev, self._points_host = ends, self.positions
         return res, targets
 
     def close(self):
@@ -745,47 +712,26 @@ class WorldFleet:
     def run(self, max_epochs=None, max_rounds=8, seed=0):
         """Epochs (epoch e with seed + e) until every robot has arrived, at most max_epochs of them (None: epoch_bound(), which suffices
         from the starts).  A robot that has arrived keeps taking part, from its goal point to its goal point, so that the others stay
-        constrained by it.  -> FleetResult"""
+        constrained by it.  With separation: until every robot has arrived or an epoch is stalled (the module's docstring: one of the two
+        comes), at most max_epochs of them if that is given.  -> FleetResult"""
+        apart = self.separation is not None
         if max_epochs is None:
-            max_epochs = self.epoch_bound() if self.separation is None else None
+            max_epochs = None if apart else self.epoch_bound()
         elif int(max_epochs) < 1:
             raise ValueError(f"WorldFleet.run: max_epochs = {max_epochs} (at least 1)")
+        paths, epochs = [], []
         try:
-            if self.separation is not None:
-                return self._run_apart(max_epochs, max_rounds, seed)
-            return self._run_plain(max_epochs, max_rounds, seed)
+            while True:
+                res, targets = self.step(seed + len(epochs), max_rounds)
+                arrived = targets.summary[:, 3] == 1         # the epoch's sub-goal was the goal point: the robot now stands on it
+                paths.append(res.paths_local)
+                epochs.append({"conflict_counts": list(res.conflict_counts), "summary": targets.summary, "offsets": targets.offsets})
+                stalled = bool(apart and (targets.summary[:, 0] == 0).all() and not arrived.all())  # no robot moves, one that arrives now included
+                if apart:
+                    epochs[-1].update(held_back=targets.extra[:, 0] - targets.summary[:, 0], sweeps=targets.sweeps, stalled=stalled)
+                if self.seed_epochs:
+                    epochs[-1]["clear_min"] = self.last_clear_min
+                if arrived.all() or stalled or (max_epochs is not None and len(epochs) >= int(max_epochs)):
+                    return FleetResult(torch.cat(paths, dim=1), arrived, epochs)
         finally:
             self.close()
-
-    def _run_plain(self, max_epochs, max_rounds, seed):
-        paths, epochs = [], []
-        arrived = np.zeros(self.n_robots, bool)
-        for e in range(int(max_epochs)):
-            res, targets = self.step(seed + e, max_rounds)
-            paths.append(res.paths_local)
-            epochs.append({"conflict_counts": list(res.conflict_counts), "summary": targets.summary, "offsets": targets.offsets})
-            if self.seed_epochs:
-                epochs[-1]["clear_min"] = self.last_clear_min
-            arrived = targets.summary[:, 3] == 1             # the epoch's sub-goal was the goal point: the robot now stands on it
-            if arrived.all():
-                break
-        if not paths:
-            raise ValueError(f"WorldFleet.run: max_epochs = {max_epochs} (at least 1)")
-        return FleetResult(torch.cat(paths, dim=1), arrived, epochs)
-
-    def _run_apart(self, max_epochs, max_rounds, seed):
-        """run with separation: epochs until every robot has arrived or an epoch is stalled (the module's docstring: one of the two comes),
-        at most max_epochs of them if that is given"""
-        paths, epochs, e = [], [], 0
-        while True:
-            res, targets = self.step(seed + e, max_rounds)
-            arrived = targets.summary[:, 3] == 1
-            stalled = bool((targets.summary[:, 0] == 0).all() and not arrived.all())      # no robot moves, one that arrives now included
-            paths.append(res.paths_local)
-            epochs.append({"conflict_counts": list(res.conflict_counts), "summary": targets.summary, "offsets": targets.offsets,
-                           "held_back": targets.extra[:, 0] - targets.summary[:, 0], "sweeps": targets.sweeps, "stalled": stalled})
-            if self.seed_epochs:
-                epochs[-1]["clear_min"] = self.last_clear_min
-            e += 1
-            if arrived.all() or stalled or (max_epochs is not None and e >= int(max_epochs)):
-                return FleetResult(torch.cat(paths, dim=1), arrived, epochs)

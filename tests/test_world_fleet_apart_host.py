@@ -221,6 +221,25 @@ def test_entry_point_argument_checks():
             (kw, lib.mmd_last_error())
 
 
+def test_entry_point_and_wrapper_check_order_with_two_faults():
+    """the order of the checks, which a caller with two faults sees: ranges (the shared ones, then sep and n_sweeps), the input pointers,
+    the workspace, the output pointers; in the wrapper dist, the walk's arguments, sep, then the cap and the sweeps"""
+    import torch
+    lib, p = _lib.load(), C.c_void_p(256)
+    size = lib.mmd_grid_window_apart_work_bytes(7, 9)
+
+    def call(sep=3, n_sweeps=4, field=p, work=p, cells=p, extra=p):
+        assert lib.mmd_grid_window_goals_apart(p, 40, 30, 2, p, field, p, 7, 5, 9, 12, sep, 1, n_sweeps, work, size, cells, p, p, extra, p, p,
+                                               None) == 2
+        return lib.mmd_last_error()
+    for kw, word in ((dict(sep=0, cells=None), b"sep"), (dict(n_sweeps=-1, field=None), b"n_sweeps"), (dict(work=None, cells=None), b"workspace"),
+                     (dict(field=None, work=None), b"NULL field"), (dict(cells=None, extra=None), b"NULL cells")):
+        assert word in call(**kw), (kw, call(**kw))
+    dist = torch.zeros(1, 40, 30, dtype=torch.int32)         # on the CPU: the first refusal, whatever else is wrong
+    with pytest.raises(ValueError, match="dist must be a contiguous int32"):
+        F.device_subgoals_apart(dist, [[1, 1]], [0], [[2, 2]], 5, 5000, 0, window=12, sweeps=0)
+
+
 # ---- 4. the fleet's refusals and defaults ------------------------------------------------------------------------------------------------------------
 def test_fleet_refusals_and_defaults():
     assert inspect.signature(F.WorldFleet.__init__).parameters["separation"].default is None

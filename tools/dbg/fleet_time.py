@@ -141,7 +141,7 @@ def apart_leg(fleet, n):
 
 def persistent_leg(fleet, model, targets, n):
     """the default's per-epoch set-up next to the persistent one of the same fleet and epoch (the module's docstring)"""
-    words = fleet._epoch_words
+    words = targets.words
     _, origins_dev, _ = F._split_words(words)
     points_dev, goals_dev = torch.from_numpy(fleet.positions).cuda(), torch.from_numpy(fleet.goal_points).cuda()
     line_a = torch.from_numpy(np.linspace(0.0, 1.0, 64, dtype=np.float32)).cuda()
