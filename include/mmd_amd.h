@@ -612,6 +612,45 @@ int mmd_select_best(const uint8_t* free_dev, const float* cost_a_dev, const floa
                     int n_robots, int samples_per_robot, int32_t* idx_best_dev, int32_t* n_free_dev, float* summary_dev,
                     void* stream);
 
+/* A planning round's pick in one pass (MultiRobotSampler.best_paths of the dense-table round): for the robots of a sampling call, straight
+ * from their NORMALISED samples x_dev [n_robots * samples_per_robot, H, 4], what the chain un-normalise (with the clip to [-1, 1] applied to
+ * every element: torch.clip, a NaN stays a NaN) -> mmd_postprocess_trajs (all_free = 0, no smoothing) -> mmd_count_collisions ->
+ * mmd_select_best -> gather of the picks' positions computes, bit for bit, in two kernels: per sample (one wave, lane = support point) the
+ * free flag, path length + smoothness and the collision count against paths_all_dev; per robot the pick (mmd_select_best's rule: the free
+ * samples first, the fewest collisions or, with paths_all_dev == NULL, the smallest path length + smoothness, the first index among equals,
+ * all samples when none is free) and its un-normalised positions. */
+typedef struct mmd_round_pick {
+  const float* paths_all_dev;     /* [n_all, H, 2] un-normalised best paths of all robots, or NULL: the cost rule */
+  int32_t n_all;                  /* robots in paths_all_dev (ignored without it) */
+  int32_t robot0;                 /* index in paths_all_dev of the call's first robot (its own path is not counted) */
+  float norm_min[4], norm_max[4]; /* the normaliser's limits: x_u = (clip(x) + 1) / 2 * (max - min) + min */
+  int32_t num_interpolation;      /* as mmd_postprocess_trajs, with its host table alpha [num_interpolation] */
+  const float* alpha;
+  float margin;                   /* map / workspace margin (the robot radius) */
+  float q_min[2], q_max[2];       /* joint limits of the support points */
+  float rr_margin;                /* robot-robot collision distance (mmd_count_collisions' margin) */
+  float* paths_out_dev;           /* [n_robots, H, 2]: the picks' un-normalised positions */
+  int32_t* idx_out_dev;           /* [n_robots]: the pick within the robot's samples */
+  int32_t* n_free_out_dev;        /* [n_robots]: free samples of the robot */
+  void* scratch_dev;              /* n_robots * samples_per_robot * 8 bytes */
+} mmd_round_pick;
+
+/* The pick of robots [0, n_robots) of x_dev on `stream`.  env: only its map / boundary fields are read, as in mmd_postprocess_trajs;
+ * robot r reads map robot_map_dev[r]. */
+int mmd_round_pick_paths(const mmd_guide_desc* env, const mmd_round_pick* pick, const float* x_dev, int n_robots,
+                         int samples_per_robot, void* stream);
+
+/* mmd_p_sample_loop followed by mmd_round_pick_paths of its final samples (env = guide, which must not be NULL), in one call.  With
+ * stream chunks, every chunk's pick is enqueued on the chunk's own stream behind its last step, before the join: the pick of the chunk
+ * that finishes first runs beside the other chunk's last step, and the caller's stream sees the one join.  With one chunk, or without
+ * side streams, the pick follows the loop on the caller's stream.  pick->paths_all_dev must not be written while the call runs (it is the
+ * previous round's gathered paths).  Samples and picks are bitwise those of the two calls made one after the other. */
+int mmd_p_sample_loop_pick(mmd_unet_t unet, const mmd_sampler_desc* s, const mmd_guide_desc* guide, float* x_dev,
+                           const float* hard_dev, int n_robots, int samples_per_robot, int n_steps,
+                           int n_steps_without_noise, int init_noise, const float* step_noise_dev, uint64_t seed,
+                           float* chain_dev, void* workspace_dev, size_t workspace_bytes, const mmd_round_pick* pick,
+                           void* stream);
+
 /* PlanningTask.compute_collision (tasks.py:141-143, :204-232; occupancy of the fixed objects + workspace boundaries)
  * for n_points positions (x, y at points_dev[i * point_stride + {0, 1}]) on map `map_index` of `env`. */
 int mmd_points_collision(const mmd_guide_desc* env, const float* points_dev, int n_points, int point_stride, int map_index,

@@ -43,6 +43,16 @@ class GuideDesc(C.Structure):
     ]
 
 
+class RoundPick(C.Structure):             # mmd_round_pick
+    _fields_ = [
+        ("paths_all_dev", C.c_void_p), ("n_all", C.c_int32), ("robot0", C.c_int32),
+        ("norm_min", C.c_float * 4), ("norm_max", C.c_float * 4),
+        ("num_interpolation", C.c_int32), ("alpha", C.POINTER(C.c_float)),
+        ("margin", C.c_float), ("q_min", C.c_float * 2), ("q_max", C.c_float * 2), ("rr_margin", C.c_float),
+        ("paths_out_dev", C.c_void_p), ("idx_out_dev", C.c_void_p), ("n_free_out_dev", C.c_void_p), ("scratch_dev", C.c_void_p),
+    ]
+
+
 class SamplerDesc(C.Structure):
     _fields_ = [
         ("n_diffusion_steps", C.c_int32),
@@ -132,6 +142,10 @@ _SIGNATURES = {
     "mmd_p_sample_loop": (C.c_int, [C.c_void_p, C.POINTER(SamplerDesc), C.POINTER(GuideDesc), C.c_void_p, C.c_void_p,
                                     C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p,
                                     C.c_void_p, C.c_size_t, C.c_void_p]),
+    "mmd_p_sample_loop_pick": (C.c_int, [C.c_void_p, C.POINTER(SamplerDesc), C.POINTER(GuideDesc), C.c_void_p, C.c_void_p,
+                                         C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p,
+                                         C.c_void_p, C.c_size_t, C.POINTER(RoundPick), C.c_void_p]),
+    "mmd_round_pick_paths": (C.c_int, [C.POINTER(GuideDesc), C.POINTER(RoundPick), C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "mmd_ddim_sample": (C.c_int, [C.c_void_p, C.POINTER(SamplerDesc), C.c_void_p, C.c_void_p, C.c_int, C.POINTER(GuideDesc),
                                   C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p,
                                   C.c_size_t, C.c_void_p]),

@@ -18,6 +18,7 @@
 #include "../../include/mmd_amd_debug.h"
 #include "common.h"
 #include "guide_dev.h"
+#include "round_pick.h"
 
 // caller-owned event-pair pool (include/mmd_amd_debug.h); the unet handle itself is immutable after creation
 struct mmd_profiler_s {
@@ -259,15 +260,23 @@ int mmd_debug_ddpm_step_trace(mmd_unet_t unet, const mmd_sampler_desc* s, const 
                    mu_dev, guide_chain_dev, trace_dev, stream);
 }
 
-int mmd_p_sample_loop(mmd_unet_t unet, const mmd_sampler_desc* s, const mmd_guide_desc* guide, float* x_dev,
-                      const float* hard_dev, int n_robots, int samples_per_robot, int n_steps,
-                      int n_steps_without_noise, int init_noise, const float* step_noise_dev, uint64_t seed,
-                      float* chain_dev, void* workspace_dev, size_t workspace_bytes, void* stream) {
-  MMD_REQUIRE(unet && s && x_dev && hard_dev && workspace_dev, "mmd_p_sample_loop: NULL argument");
+}  // extern "C"
+
+namespace mmd {
+
+// The body of mmd_p_sample_loop and of mmd_p_sample_loop_pick (`who`).  pick != NULL: the round's pick of the final samples
+// (round_pick.hip) behind every chunk's last step, on the chunk's own stream, before the join.
+static int sample_loop(const char* who, mmd_unet_t unet, const mmd_sampler_desc* s, const mmd_guide_desc* guide, float* x_dev,
+                       const float* hard_dev, int n_robots, int samples_per_robot, int n_steps, int n_steps_without_noise, int init_noise,
+                       const float* step_noise_dev, uint64_t seed, float* chain_dev, void* workspace_dev, size_t workspace_bytes,
+                       const mmd_round_pick* pick, void* stream) {
+  MMD_REQUIRE(unet && s && x_dev && hard_dev && workspace_dev, "%s: NULL argument", who);
   const int n = n_robots * samples_per_robot;
-  MMD_REQUIRE(n >= 1, "mmd_p_sample_loop: empty batch");
+  MMD_REQUIRE(n >= 1, "%s: empty batch", who);
   MMD_REQUIRE(n_steps >= 0 && n_steps <= s->n_diffusion_steps && n_steps_without_noise >= 0, "bad step counts");
-  MMD_REQUIRE(workspace_bytes >= mmd_sampler_workspace_bytes(unet, n), "mmd_p_sample_loop: workspace too small");
+  MMD_REQUIRE(workspace_bytes >= mmd_sampler_workspace_bytes(unet, n), "%s: workspace too small", who);
+  if (pick)
+    if (int rc = round_pick_check(who, guide, pick, x_dev, n_robots, samples_per_robot)) return rc;
   hipStream_t st = (hipStream_t)stream;
   const size_t traj_floats = (size_t)n * H * D;
   GuideDev g{};
@@ -351,16 +360,43 @@ int mmd_p_sample_loop(mmd_unet_t unet, const mmd_sampler_desc* s, const mmd_guid
       if (br) prof_end(prof, cs[c]);
     }
   }
+  // the pick of a chunk's robots behind its last step: the chunk that finishes first picks beside the other's last step
+  for (int c = 0; c < nch && rc == 0 && pick; ++c)
+    rc = round_pick_launch(guide, pick, x_dev, n_robots, r0[c], r0[c + 1] - r0[c], samples_per_robot, cs[c]);
   // join on every exit path: an error above must not leave the caller's stream detached from the side streams
   if (nch > 1)
     for (int c = 0; c < nch; ++c) {
       if (hipEventRecord(S->join[c], cs[c]) != hipSuccess || hipStreamWaitEvent(st, S->join[c], 0) != hipSuccess) {
-        if (rc == 0) { set_error("mmd_p_sample_loop: joining side stream %d failed", c); rc = 1; }
+        if (rc == 0) { set_error("%s: joining side stream %d failed", who, c); rc = 1; }
       }
     }
   if (rc) return rc;
   MMD_HIP_CHECK(hipGetLastError());
   return 0;
+}
+
+}  // namespace mmd
+
+using namespace mmd;
+
+extern "C" {
+
+int mmd_p_sample_loop(mmd_unet_t unet, const mmd_sampler_desc* s, const mmd_guide_desc* guide, float* x_dev,
+                      const float* hard_dev, int n_robots, int samples_per_robot, int n_steps,
+                      int n_steps_without_noise, int init_noise, const float* step_noise_dev, uint64_t seed,
+                      float* chain_dev, void* workspace_dev, size_t workspace_bytes, void* stream) {
+  return sample_loop("mmd_p_sample_loop", unet, s, guide, x_dev, hard_dev, n_robots, samples_per_robot, n_steps, n_steps_without_noise,
+                     init_noise, step_noise_dev, seed, chain_dev, workspace_dev, workspace_bytes, nullptr, stream);
+}
+
+int mmd_p_sample_loop_pick(mmd_unet_t unet, const mmd_sampler_desc* s, const mmd_guide_desc* guide, float* x_dev,
+                           const float* hard_dev, int n_robots, int samples_per_robot, int n_steps,
+                           int n_steps_without_noise, int init_noise, const float* step_noise_dev, uint64_t seed,
+                           float* chain_dev, void* workspace_dev, size_t workspace_bytes, const mmd_round_pick* pick,
+                           void* stream) {
+  MMD_REQUIRE(pick && guide, "mmd_p_sample_loop_pick: NULL pick or guide");
+  return sample_loop("mmd_p_sample_loop_pick", unet, s, guide, x_dev, hard_dev, n_robots, samples_per_robot, n_steps, n_steps_without_noise,
+                     init_noise, step_noise_dev, seed, chain_dev, workspace_dev, workspace_bytes, pick, stream);
 }
 
 int mmd_p_sample_loop_ensemble(const mmd_ensemble_tile* tiles, int n_tiles, const mmd_cross_cond* cross, int n_cross,

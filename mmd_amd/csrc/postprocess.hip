@@ -13,73 +13,9 @@
 // tiles), lane = support point: neighbours through DPP, reductions through ballots / wave shuffles, the SDF texture is
 // the guide's resident one.  The interpolation and the grid index are computed with the
 // reference's exact fp32 operation sequence (no FMA contraction), so the collision / free split is bit-exact.
-#include <hip/hip_runtime.h>
-
-#include <cmath>
-
-#include "../../include/mmd_amd.h"
-#include "common.h"
-
-// before guide_dev.h: its extra_sdf decides occupancy here, operation for operation (guide.hip keeps its own contraction)
-#pragma clang fp contract(off)
-
-#include "guide_dev.h"
-#include "wave_dev.h"             // wave_sum
+#include "postprocess_dev.h"     // the fragments shared with round_pick.hip (sets fp contract(off) before it includes guide_dev.h)
 
 namespace mmd {
-
-constexpr int MAX_INTERP = 16;
-
-struct EnvDev {
-  float lo[2], dim[2];
-  int nx, ny, n_grids;
-  const float4* grids;        // [n_maps][n_grids][nx][ny]
-  const int* robot_map;       // per-robot map index or null
-  float ws_min[2], ws_max[2];
-  const float4* xs;           // the env's extra objects (mmd_guide_desc.extra_spheres_dev / extra_boxes_dev)
-  const float4* xb;
-  int n_xs, n_xb;
-};
-
-static int fill_env(const mmd_guide_desc* d, EnvDev& e) {
-  MMD_REQUIRE(d->n_grids == 0 || (d->sdf_grids_dev && d->grid_nx >= 1 && d->grid_ny >= 1), "postprocess: SDF grid missing");
-  for (int k = 0; k < 2; ++k) {
-    e.lo[k] = d->limits_lo[k];
-    e.dim[k] = fabsf(d->limits_hi[k] - d->limits_lo[k]);
-    e.ws_min[k] = d->ws_min[k];
-    e.ws_max[k] = d->ws_max[k];
-  }
-  e.nx = d->grid_nx; e.ny = d->grid_ny; e.n_grids = d->n_grids;
-  e.grids = reinterpret_cast<const float4*>(d->sdf_grids_dev);
-  e.robot_map = d->robot_map_dev;
-  e.xs = reinterpret_cast<const float4*>(d->extra_spheres_dev); e.n_xs = d->extra_spheres_dev ? d->n_extra_spheres : 0;
-  e.xb = reinterpret_cast<const float4*>(d->extra_boxes_dev); e.n_xb = d->extra_boxes_dev ? d->n_extra_boxes : 0;
-  return 0;
-}
-
-// occupancy of one point: any fixed-object SDF (nearest cell) or any of the 4 workspace-boundary distances below `margin`
-__device__ __forceinline__ bool point_collides(const EnvDev& e, const float4* __restrict__ grid, float px, float py,
-                                               float margin) {
-  bool c = false;
-  if (e.n_grids > 0) {
-    int ix = (int)floorf((px - e.lo[0]) / e.dim[0] * (float)e.nx);
-    int iy = (int)floorf((py - e.lo[1]) / e.dim[1] * (float)e.ny);
-    ix = min(max(ix, 0), e.nx - 1);
-    iy = min(max(iy, 0), e.ny - 1);
-    for (int k = 0; k < e.n_grids; ++k) c = c || grid[((size_t)k * e.nx + ix) * e.ny + iy].x < margin;
-  }
-  if (e.n_xs + e.n_xb > 0) {                                // env.get_df_obj_list(): the fixed grid + obj_extra_list
-    float gx, gy;
-    c = c || extra_sdf<true>(e.xs, e.n_xs, e.xb, e.n_xb, px, py, gx, gy) < margin;
-  }
-  c = c || (px - e.ws_min[0] < margin) || (py - e.ws_min[1] < margin) || (e.ws_max[0] - px < margin) ||
-      (e.ws_max[1] - py < margin);
-  return c;
-}
-
-__device__ __forceinline__ float lane_next_f(float v) {   // lane t reads lane t + 1 (wave_shl:1)
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x130, 0xf, 0xf, true));
-}
 
 struct PostArgs {
   EnvDev env;
@@ -113,9 +49,7 @@ __global__ __launch_bounds__(MAX_BLOCKS * 64) void postprocess_kernel(PostArgs a
     const float4 n = tr[p + 1];
     nx = n.x; ny = n.y; nz = n.z; nw = n.w;
   }
-  const int robot = traj / a.samples_per_robot;
-  const int map = a.env.robot_map ? a.env.robot_map[robot] : 0;
-  const float4* grid = a.env.grids + (size_t)map * a.env.n_grids * a.env.nx * a.env.ny;
+  const float4* grid = robot_grid(a.env, traj / a.samples_per_robot);
 
   // interpolated points of segment p -> p+1: x_p * alpha + x_{p+1} * (1 - alpha)   (trajectory/utils.py:80-81)
   bool coll = false;
@@ -126,8 +60,8 @@ __global__ __launch_bounds__(MAX_BLOCKS * 64) void postprocess_kernel(PostArgs a
     if (a.waypoint_coll) a.waypoint_coll[(size_t)traj * L + p] = coll ? 1 : 0;
   } else if (p < L - 1 && !a.all_free) {
     for (int j = 0; j < a.n_interp; ++j) {
-      const float px = x.x * a.alpha[j] + nx * a.one_minus_alpha[j];
-      const float py = x.y * a.alpha[j] + ny * a.one_minus_alpha[j];
+      const float px = interp_coord(x.x, nx, a.alpha[j], a.one_minus_alpha[j]);
+      const float py = interp_coord(x.y, ny, a.alpha[j], a.one_minus_alpha[j]);
       const bool c = point_collides(a.env, grid, px, py, a.margin);
       coll = coll || c;
       if (a.waypoint_coll) a.waypoint_coll[((size_t)traj * (L - 1) + p) * a.n_interp + j] = c ? 1 : 0;
@@ -136,16 +70,12 @@ __global__ __launch_bounds__(MAX_BLOCKS * 64) void postprocess_kernel(PostArgs a
     for (int j = 0; j < a.n_interp; ++j) a.waypoint_coll[((size_t)traj * (L - 1) + p) * a.n_interp + j] = 0;
   }
   // joint limits of the support points (tasks.py:270-276)
-  const bool inside = x.x >= a.q_min[0] && x.x <= a.q_max[0] && x.y >= a.q_min[1] && x.y <= a.q_max[1];
+  const bool inside = inside_limits(x.x, x.y, a.q_min, a.q_max);
   const bool bad = a.all_free ? false : (coll || !inside);
   const unsigned long long wave_bad = __ballot(bad);
   // path length / smoothness: sum_p || diff ||  (metrics.py:13-14, :36-38)
   float pl = 0.f, sm = 0.f;
-  if (p < L - 1) {
-    const float dx = nx - x.x, dy = ny - x.y, dvx = nz - x.z, dvy = nw - x.w;
-    pl = sqrtf(dx * dx + dy * dy);
-    sm = sqrtf(dvx * dvx + dvy * dvy);
-  }
+  if (p < L - 1) segment_costs(x, nx, ny, nz, nw, pl, sm);
   pl = wave_sum(pl);
   sm = wave_sum(sm);
   if (t == 0) { red[k][0] = pl; red[k][1] = sm; bad_any[k] = wave_bad ? 1 : 0; }
@@ -174,14 +104,6 @@ __global__ __launch_bounds__(MAX_BLOCKS * 64) void postprocess_kernel(PostArgs a
   }
 }
 
-// the order of torch.argmin over (key, index): a NaN key comes before every number, the lower index before the higher among
-// equal keys (and among NaNs).  An empty candidate (+inf, 0x7fffffff) comes after every real one.
-__device__ __forceinline__ bool pick_before(float ka, int ia, float kb, int ib) {
-  const bool na = ka != ka, nb = kb != kb;
-  if (na != nb) return na;
-  return ka < kb || ((na || ka == kb) && ia < ib);
-}
-
 // per robot: index of the best sample among the free ones.  counts == null: argmin of cost_a (+ cost_b) with torch.argmin's
 // order (first minimum; a NaN key is smaller than every number, so the first NaN among the candidates wins); counts != null:
 // first free sample with the fewest collisions (strict '<' scan, cbs.py:452).  When no sample is free, idx = the same
@@ -191,29 +113,17 @@ __global__ __launch_bounds__(64) void select_best_kernel(const unsigned char* __
                                                          const int* __restrict__ counts, int B, int* __restrict__ idx_best,
                                                          int* __restrict__ n_free, float* __restrict__ summary) {
   const int r = blockIdx.x, lane = threadIdx.x;
-  int nf = 0;
-  for (int b = lane; b < B; b += 64) nf += free_mask[(size_t)r * B + b] ? 1 : 0;
   if (summary)                                                // the host's one transfer: free flags as floats, then the picks
     for (int b = lane; b < B; b += 64) summary[(size_t)r * B + b] = free_mask[(size_t)r * B + b] ? 1.f : 0.f;
-  nf = wave_sum(nf);
-  float best = INFINITY;
-  int best_i = 0x7fffffff;
-  for (int b = lane; b < B; b += 64) {
+  int nf;
+  const int best_i = wave_pick(B, [&](int b) { return free_mask[(size_t)r * B + b] != 0; }, [&](int b) {
     const size_t i = (size_t)r * B + b;
-    if (nf > 0 && !free_mask[i]) continue;
-    const float key = counts ? (float)counts[i] : (cost_b ? cost_a[i] + cost_b[i] : cost_a[i]);
-    if (pick_before(key, b, best, best_i)) { best = key; best_i = b; }
-  }
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) {
-    const float ob = __shfl_xor(best, m);
-    const int oi = __shfl_xor(best_i, m);
-    if (pick_before(ob, oi, best, best_i)) { best = ob; best_i = oi; }
-  }
+    return counts ? (float)counts[i] : (cost_b ? cost_a[i] + cost_b[i] : cost_a[i]);
+  }, nf);
   if (lane == 0) {
-    idx_best[r] = best_i == 0x7fffffff ? -1 : best_i;
+    idx_best[r] = best_i;
     n_free[r] = nf;
-    if (summary) summary[(size_t)gridDim.x * B + r] = (float)(best_i == 0x7fffffff ? -1 : best_i);
+    if (summary) summary[(size_t)gridDim.x * B + r] = (float)best_i;
   }
 }
 
@@ -276,7 +186,6 @@ __global__ __launch_bounds__(256) void range_flag_kernel(const float4* __restric
     if (has_nan) __hip_atomic_store(f + FLAG_NAN, (unsigned char)1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
 }
-struct UnnormArgs { float mins[4], range[4]; };
 __global__ __launch_bounds__(256) void unnormalize_kernel(const float4* __restrict__ x, float4* __restrict__ out, size_t n, size_t period,
                                                           size_t segment, UnnormArgs a, const uint32_t* __restrict__ flags) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -285,8 +194,7 @@ __global__ __launch_bounds__(256) void unnormalize_kernel(const float4* __restri
   const bool clip = ((w >> (8 * FLAG_OUT)) & 0xffu) != 0u && ((w >> (8 * FLAG_NAN)) & 0xffu) == 0u;
   auto f = [&](float v, int d) {
     if (clip) v = fminf(fmaxf(v, -1.f), 1.f);                // torch.clip(x, -1, 1); no NaN reaches this line
-    v = (v + 1.f) / 2.f;
-    return v * a.range[d] + a.mins[d];
+    return unnorm_coord(v, a, d);
   };
   const float4 v = x[i];
   out[i] = make_float4(f(v.x, 0), f(v.y, 1), f(v.z, 2), f(v.w, 3));

@@ -171,19 +171,23 @@ class GaussianDiffusionModel:
             hard[:, slot], mask = val, mask | (1 << row)
         return hard.contiguous(), mask
 
+    takes_round_pick = True       # p_sample_loop(round_pick=...): what multi_robot.MultiRobotSampler asks before it sends one
+
     # ---- sampling ---------------------------------------------------------------------------------------------
     @torch.no_grad()
     def p_sample_loop(self, shape, hard_conds, n_diffusion_steps, context=None, return_chain=False,
                       sample_fn=ddpm_sample_fn, n_diffusion_steps_without_noise=0, warm_start_path_b=None,
                       guide=None, n_guide_steps=1, t_start_guide=float("inf"), noise_std_extra_schedule_fn=None,
                       n_robots=1, step_noise=None, seed=None, device="cuda", n_streams=0, traj_index_base=0,
-                      scale_grad_by_std=False, robot_seeds=None, **sample_kwargs):
+                      scale_grad_by_std=False, robot_seeds=None, round_pick=None, **sample_kwargs):
         """diffusion_model_base.py:162-211.  Extensions: `n_robots` (batch = n_robots * n_samples, robot-major),
         `step_noise` [n_steps_total, B, H, D] + `warm_start_path_b` as x_T to inject every Gaussian draw (parity
         tests), `seed` for the in-kernel Philox stream otherwise, `traj_index_base` = global index of this call's first
         trajectory (a rank sampling robots [r0, r1) of a bigger instance passes r0 * n_samples and draws exactly the noise
         those rows get in the unsharded call); `robot_seeds` [n_robots]: one Philox stream per robot -- the batch then draws
-        exactly what n_robots separate one-robot calls with those seeds draw (planners.plan_batched)."""
+        exactly what n_robots separate one-robot calls with those seeds draw (planners.plan_batched); `round_pick` (an object whose
+        `.struct` is a filled _lib.RoundPick: multi_robot.MultiRobotSampler's): the call is mmd_p_sample_loop_pick, which also picks every
+        robot's best sample into the struct's outputs, per stream chunk behind the chunk's last step."""
         if sample_fn is not ddpm_sample_fn:
             raise NotImplementedError("only ddpm_sample_fn is implemented (DDIM: conditional_sample(ddim=True) / ddim_sample)")
         if context is not None:
@@ -212,10 +216,14 @@ class GaussianDiffusionModel:
         ws = self.model.workspace(B_total, device, sampler=True)
         if seed is None:
             seed = next_stream_seed(self.seed)
-        _lib.launch("mmd_p_sample_loop", x, self.model.handle(self.n_diffusion_steps, device), C.byref(s), C.byref(gd) if gd is not None else None,
+        if round_pick is not None and gd is None:
+            raise ValueError("p_sample_loop(round_pick=...) needs the guide: the pick reads its map")
+        _lib.launch("mmd_p_sample_loop" if round_pick is None else "mmd_p_sample_loop_pick", x, self.model.handle(self.n_diffusion_steps, device),
+            C.byref(s), C.byref(gd) if gd is not None else None,
             x.data_ptr(), hard.data_ptr(), n_robots, B_total // n_robots, n_diffusion_steps,
             n_diffusion_steps_without_noise, init_noise, step_noise.data_ptr() if step_noise is not None else None,
-            C.c_uint64(seed), chain.data_ptr() if chain is not None else None, ws.data_ptr(), ws.numel())
+            C.c_uint64(seed), chain.data_ptr() if chain is not None else None, ws.data_ptr(), ws.numel(),
+            *(() if round_pick is None else (C.byref(round_pick.struct),)))
         if return_chain:
             return x, chain.transpose(0, 1)                      # [B, steps+1, H, D] like torch.stack(chain, dim=1)
         return x

@@ -25,6 +25,7 @@ replan_round's uncached one -> _build_collision_table) and the pick (best_paths 
 (plan_rounds_subset), whose rounds are _full_round and _subset_round.  _set_inter_robot_table, _build_collision_table and _in_shared_frame are
 the hooks a subclass with per-robot frames overrides.
 """
+import ctypes as C
 from dataclasses import dataclass
 from math import ceil
 
@@ -87,6 +88,11 @@ class PlanResult:
     # plan_rounds_subset(replan != "all"): the robots sampled per round run, over all ranks ([N, n_selected, ...]), else None.  Set on the
     # result, not a field: the positional layout of the fields above is what callers construct
     replanned_counts = None
+
+
+class _RoundPickRequest:
+    """A round's mmd_round_pick and the tensors it points at (MultiRobotSampler._round_pick_request)."""
+    __slots__ = ("struct", "paths", "idx", "n_free", "scratch", "paths_all", "alpha")
 
 
 class MultiRobotSampler:
@@ -194,13 +200,16 @@ class MultiRobotSampler:
         return self._run(self.hard_conds, self.n_local, self.guide, self.robot0, seed, prev_trajs, n_noising_steps, n_denoising_steps)
 
     def _run(self, hard_conds, n_robots, guide, robot0, seed, prev_trajs=None, n_noising_steps=3, n_denoising_steps=3, x_init=None,
-             step_noise=None, return_chain=False):
+             step_noise=None, return_chain=False, round_pick=None):
         """The one sampling call, for robots [robot0, robot0 + n_robots) of an instance with their hard conditions and their guide:
-        `sample` (from noise, or from x_init) when prev_trajs is None, else `sample_local` from prev_trajs [n_robots * B, H, D]"""
+        `sample` (from noise, or from x_init) when prev_trajs is None, else `sample_local` from prev_trajs [n_robots * B, H, D].
+        round_pick (_round_pick_request): the call also picks these robots' best samples (_sample_and_pick)"""
         shared = dict(n_samples=self.n_samples, n_robots=n_robots, horizon=H, sample_fn=ddpm_sample_fn, guide=guide,
                       n_guide_steps=self.n_guide_steps, t_start_guide=self.t_start_guide, noise_std_extra_schedule_fn=lambda t: 0.5,
                       n_diffusion_steps_without_noise=self.n_extra, seed=seed, traj_index_base=robot0 * self.n_samples,
                       device=self.device, n_streams=self.n_streams)
+        if round_pick is not None:
+            shared["round_pick"] = round_pick
         if prev_trajs is None:
             return self.model.run_inference(None, hard_conds, return_chain=return_chain, warm_start_path_b=x_init, step_noise=step_noise,
                                             **shared)
@@ -252,12 +261,78 @@ class MultiRobotSampler:
         robots share.  Here every robot lives in that frame: t itself, no copy and no launch"""
         return t
 
+    # ---- a full round's sampling and pick: one native call (mmd_p_sample_loop_pick) where the round is the plain one ----
+    _native_pick = True         # private switch: False keeps every round on sample + best_paths (the A/B of tests/test_gpu_round_pick.py)
+
+    def _takes_native_pick(self, collision_table):
+        """THE place that says which full rounds sample and pick in one native call: the dense table, no collision table handed in
+        (plan_rounds(repair=True) counts on its own), and the sampling, the pick and the frame all the base class's -- a subclass that
+        overrides any of them (world.WorldRobotSampler: per-robot frames) keeps sample + best_paths, as do the cell-table rounds, the
+        repair rounds and the subset rounds (replan_round)."""
+        cls, base = type(self), MultiRobotSampler
+        own = ("_in_shared_frame", "_pick", "best_paths", "unnormalize", "sample", "sample_local", "_run")
+        return (self._native_pick and self.constraint_table == "dense" and collision_table is None
+                and getattr(self.model, "takes_round_pick", False)          # (a model whose p_sample_loop knows the request)
+                and all(getattr(cls, name) is getattr(base, name) for name in own))
+
+    def _round_pick_request(self, paths_all):
+        """The mmd_round_pick of this rank's robots against paths_all (None, or fewer than two robots: the cost rule), with fresh outputs:
+        .paths [n_local, H, 2], .idx, .n_free (what _pick returns), .struct for the call.  Everything the struct points at is held here."""
+        from . import _lib, postprocess as post
+        from .multi_agent import RR_MARGIN
+        n, dev = self.n_local * self.n_samples, self.device
+        rp = _RoundPickRequest()
+        rp.paths = torch.empty((self.n_local, H, 2), dtype=torch.float32, device=dev)
+        rp.idx = torch.empty(self.n_local, dtype=torch.int32, device=dev)
+        rp.n_free = torch.empty(self.n_local, dtype=torch.int32, device=dev)
+        rp.scratch = torch.empty(2 * n, dtype=torch.float32, device=dev)
+        rp.paths_all = paths_all.contiguous() if paths_all is not None and self.n_robots >= 2 else None
+        host = getattr(self, "_pick_host", None)
+        if host is None:            # once per sampler: the normaliser's limits on the host, postprocess_batch's default alpha table (as _pick calls it)
+            nz = self.dataset.normalizer
+            host = self._pick_host = ([float(v) for v in nz.mins.float().cpu()], [float(v) for v in nz.maxs.float().cpu()],
+                                      post.interpolation_alphas(5))
+        rp.alpha = host[2]
+        s = rp.struct = _lib.RoundPick()
+        s.paths_all_dev = rp.paths_all.data_ptr() if rp.paths_all is not None else None
+        s.n_all, s.robot0 = self.n_robots, self.robot0
+        s.norm_min, s.norm_max = (C.c_float * 4)(*host[0]), (C.c_float * 4)(*host[1])
+        s.num_interpolation, s.alpha = len(rp.alpha), rp.alpha.ctypes.data_as(C.POINTER(C.c_float))
+        s.margin, s.rr_margin = post.ROBOT_RADIUS, RR_MARGIN
+        s.q_min, s.q_max = (C.c_float * 2)(*post.Q_MIN), (C.c_float * 2)(*post.Q_MAX)
+        s.paths_out_dev, s.idx_out_dev, s.n_free_out_dev = rp.paths.data_ptr(), rp.idx.data_ptr(), rp.n_free.data_ptr()
+        s.scratch_dev = rp.scratch.data_ptr()
+        return rp
+
+    def _pick_native(self, trajs_normalized, paths_all=None):
+        """_pick of this rank's robots on the dense table as the one native pass alone (mmd_round_pick_paths) -> (paths, idx, n_free),
+        the same bits; what _sample_and_pick's call enqueues behind the sampling loop."""
+        from . import _lib
+        rp = self._round_pick_request(paths_all)
+        _lib.launch("mmd_round_pick_paths", trajs_normalized, C.byref(self.guide.desc()), C.byref(rp.struct),
+                    _lib.require_gpu(trajs_normalized, "trajs_normalized"), self.n_local, self.n_samples)
+        return rp.paths, rp.idx, rp.n_free
+
+    def _sample_and_pick(self, others, collision_table, seed, prev_trajs=None, n_noising_steps=3, n_denoising_steps=3):
+        """A full round's sampling (from noise, or from prev_trajs as sample_local does) and its pick -> (trajs, paths_local), with
+        last_idx / last_n_free filled: one native call where _takes_native_pick says so, else sample / sample_local + best_paths."""
+        if self._takes_native_pick(collision_table):
+            rp = self._round_pick_request(others)
+            trajs = self._run(self.hard_conds, self.n_local, self.guide, self.robot0, seed, prev_trajs, n_noising_steps, n_denoising_steps,
+                              round_pick=rp)
+            self.last_idx, self.last_n_free = rp.idx, rp.n_free
+            return trajs, rp.paths
+        if prev_trajs is None:
+            trajs = self.sample(seed=seed)              # (the public methods: a subclass may put its own sampling there)
+        else:
+            trajs = self.sample_local(prev_trajs, n_noising_steps, n_denoising_steps, seed=seed)
+        return trajs, self.best_paths(trajs, others, collision_table=collision_table)
+
     def plan_round(self, paths_local, seed=None):
         """all-gather -> constraint table -> guided sampling -> new local best paths."""
         paths_all = all_gather_paths(paths_local, self.world_size, self.group) if self.inter_robot else None
         self.set_other_paths(paths_all)
-        trajs = self.sample(seed=seed)
-        return trajs, self.best_paths(trajs, paths_all)
+        return self._sample_and_pick(paths_all, None, seed)
 
     def _subset_guide(self, n_robots):
         """the guide of a subset round: n_robots robots on the sampler's map, kept by size; `self.guide` and its tables are not touched"""
@@ -429,11 +504,7 @@ class MultiRobotSampler:
             self.guide.set_packed_constraints(rc.tensors())
         else:
             self.set_other_paths(others)
-        if prev_trajs is None:
-            trajs = self.sample(seed=seed)              # (the public methods: a subclass may put its own sampling there)
-        else:
-            trajs = self.sample_local(prev_trajs, n_noising_steps, n_denoising_steps, seed=seed)
-        return trajs, self.best_paths(trajs, others, collision_table=table)
+        return self._sample_and_pick(others, table, seed, prev_trajs, n_noising_steps, n_denoising_steps)
 
     def _subset_round(self, paths_all, table, robot_counts, replan, independent_iters, seed, paths_local, trajs, local_rounds,
                       n_noising_steps, n_denoising_steps):
