@@ -992,6 +992,46 @@ int mmd_fleet_epoch_frames(const int32_t* cells_dev /* [n][2] */, const int32_t*
                            float* offsets_dev /* [n][2] */, float* subgoals_dev /* [n][2] */, float* hard_first_dev /* [n][4] */,
                            float* hard_last_dev /* [n][4] */, float* lines_dev /* [n][64][2] */, void* stream);
 
+/* World fleets: the report of a whole run (mmd_amd/world_fleet.py::run_report is the definition on the host: the same integers and the
+ * same float32 bits, `length` apart).  paths_dev [n][L][2]: global points, column by column; grid_dev: any texture [nx][ny][4] over
+ * lo .. hi; goals_dev [n][2].  A texel is mmd_sdf_grid_lookup's, a value channel 0 of the texel, the norm sqrt(fma(dy, dy, dx * dx)), and
+ * every other operation is rounded once.  A point with a coordinate that is not finite is BAD and takes part in nothing else, nor does a
+ * segment with a bad end.  Segment t runs from a = p[t] to b = p[t + 1]; its interior points are q_j = a + (b - a) * ((float)j /
+ * (float)(n_interp + 1)), j = 1 .. n_interp (an interior point that is not finite is not checked).
+ * report_dev, int32 words, MMD_FLEET_REPORT_HEADER + 11 n (+ L with column_conflicts), 8-byte aligned:
+ *   header   [0 .. 1] conflict_count, 64 bits: the pairs i < j with ||p_i[t] - p_j[t]|| < rr_margin, summed over the columns t
+ *            [2 .. 3] the first conflict, 64 bits: t << 24 | i << 12 | j, the least (t, then i, then j); all ones if there is none
+ *            [4] robots_hit  [5] robots_in_conflict  [6] robots_arrived  [7] 0
+ *   conflicts [n]        per robot the (t, other robot) in conflict
+ *   column_conflicts [L] per column its pairs in conflict; only with column_conflicts == 1
+ *   then ten arrays [n]: points_hit (waypoints with value < margin), interp_hit (interior points likewise), first_hit (the least t whose
+ *            waypoint or one of whose segment's interior points is hit, -1 if none), bad_points, outside (finite waypoints not in
+ *            lo <= p <= hi; they read the clamped border texel and still take part), arrival (the least c with every column t >= c
+ *            finite and ||p[t] - goal|| <= goal_tol; L if the last column is not), clear_min (float: the least value over all points
+ *            checked in the order of the values' bits, a NaN beyond the infinity of its sign; +inf if there are none), length (float: the
+ *            sum of the segment lengths, per lane in column order, then the wave's butterfly), max_step (float: the longest segment, 0 if
+ *            there is none), end_error (float: ||p[L - 1] - goal||, the NaN 0x7fc00000 if that point or the goal is bad)
+ * One wave per robot for the per-robot words; all pairs of robots on LDS tiles of 32 robots x 64 columns for the conflicts (no n x n
+ * buffer); integer atomics only, so every word but `length` is independent of scheduling, and `length` is a fixed order.  The call
+ * writes every word it describes and does not synchronise.
+ * Error returns, before anything is launched and with the report untouched: n_robots outside 0 .. MMD_FLEET_REPORT_MAX_ROBOTS; length
+ * outside 2 .. MMD_FLEET_REPORT_MAX_LENGTH; nx or ny below 1 or above MMD_OCCUPANCY_MAX_SIDE; NULL or non-finite limits or a zero extent;
+ * a margin or rr_margin that is not finite; n_interp outside 0 .. MMD_FLEET_REPORT_MAX_INTERP; goal_tol negative or not finite;
+ * column_conflicts not 0 or 1; with n_robots > 0, NULL or misaligned paths (8 bytes), grid (16), goals (8) or report (8).
+ * n_robots == 0 returns 0, launches nothing and writes nothing. */
+#define MMD_FLEET_REPORT_MAX_ROBOTS 4096
+#define MMD_FLEET_REPORT_MAX_LENGTH 65535
+#define MMD_FLEET_REPORT_MAX_INTERP 63
+#define MMD_FLEET_REPORT_HEADER 8
+#define MMD_FLEET_REPORT_CONFLICT_COUNT 0
+#define MMD_FLEET_REPORT_FIRST_KEY 2
+#define MMD_FLEET_REPORT_ROBOTS_HIT 4
+#define MMD_FLEET_REPORT_ROBOTS_IN_CONFLICT 5
+#define MMD_FLEET_REPORT_ROBOTS_ARRIVED 6
+int mmd_fleet_run_report(const float* paths_dev /* [n][L][2] */, int n_robots, int length, const float* grid_dev /* [nx][ny][4] */, int nx,
+                         int ny, const float lo[2], const float hi[2], const float* goals_dev /* [n][2] */, float margin, float rr_margin,
+                         int n_interp, float goal_tol, int column_conflicts, int32_t* report_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

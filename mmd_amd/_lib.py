@@ -222,6 +222,8 @@ _SIGNATURES = {
     "mmd_fleet_epoch_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_double),
                                          C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mmd_fleet_run_report": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                       C.c_void_p, C.c_float, C.c_float, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p]),
 }
 WINDOW_APART_MAX_STEPS, WINDOW_APART_MAX_SEP = 4095, 1024   # MMD_WINDOW_APART_MAX_STEPS, MMD_WINDOW_APART_MAX_SEP
 ROUTE_SEED_POINTS, ROUTE_SEED_MAX_TILES = 64, 16            # MMD_ROUTE_SEED_POINTS, MMD_ROUTE_SEED_MAX_TILES

@@ -1,7 +1,7 @@
 """PyTorch-ROCm custom ops over the C ABI (include/mmd_amd.h): `torch.ops.mmd_amd.{unet_forward, guide_steps,
 p_sample_loop, ddim_sample, solution_stats, bin_constraints_from_paths, count_collisions_binned, path_conflicts, round_select,
 round_constraints_init, round_soft_from_paths, conflict_constraints_append,
-framed_constraints_from_paths}`.  They take tensors instead of raw pointers, run on torch's CURRENT HIP stream
+framed_constraints_from_paths, fleet_run_report}`.  They take tensors instead of raw pointers, run on torch's CURRENT HIP stream
 without any host synchronisation (so they can be captured into a hipGraph with torch.cuda.graph) and register fake
 (meta) implementations so that torch.compile / FakeTensor tracing sees their output shapes.  The C header stays the ABI
 of record: every op is a thin wrapper over the same entry point the host mirror classes call through ctypes.
@@ -319,3 +319,25 @@ def _(paths, offsets, robot0, n_local, slots, radius, weight, lo_x, lo_y, hi_x, 
     return (paths.new_empty((n_local * slots, 64, 4)), paths.new_empty(n_local + 1, dtype=torch.int32), paths.new_empty(n_local),
             paths.new_empty(n_local + 1, dtype=torch.int32), paths.new_empty(n_local, dtype=torch.int32),
             paths.new_empty(n_local, dtype=torch.int32))
+
+
+# ---- fleet_run_report ------------------------------------------------------------------------------------------------
+@torch.library.custom_op("mmd_amd::fleet_run_report", mutates_args=(), device_types="cuda")
+def fleet_run_report(paths: torch.Tensor, tex: torch.Tensor, goals: torch.Tensor, lo_x: float, lo_y: float, hi_x: float, hi_y: float,
+                     margin: float, rr_margin: float, n_interp: int, goal_tol: float, column_conflicts: bool) -> torch.Tensor:
+    """The report of a whole run's global paths [N, L, 2] on the texture tex [nx, ny, 4] over (lo, hi), against goals [N, 2]
+    (mmd_fleet_run_report): its one buffer, int32 [8 + 11 N (+ L with column_conflicts)] in include/mmd_amd.h's layout, which
+    world_fleet.report_from_words reads from a host copy.  No synchronisation and no copy here."""
+    from . import world_fleet
+    if not (goals.is_cuda and goals.dtype == torch.float32 and goals.device == paths.device):
+        raise RuntimeError("mmd_amd op: goals must be a float32 CUDA(HIP) tensor on the paths' device")
+    try:
+        return world_fleet.device_run_report_words(paths, tex, (lo_x, lo_y), (hi_x, hi_y), goals, margin, rr_margin, n_interp, goal_tol,
+                                                   column_conflicts)
+    except ValueError as e:
+        raise RuntimeError(f"mmd_amd op: {e}") from e
+
+
+@fleet_run_report.register_fake
+def _(paths, tex, goals, lo_x, lo_y, hi_x, hi_y, margin, rr_margin, n_interp, goal_tol, column_conflicts):
+    return paths.new_empty(8 + 11 * paths.shape[0] + (paths.shape[1] if column_conflicts else 0), dtype=torch.int32)
