@@ -7,7 +7,8 @@
 //     multi_agent.hip (postprocess_dev.h, collision_dev.h) in their order, sums over the wave with the same butterfly.
 //   * round_pick_robot_kernel: one wave per robot.  select_best_kernel's scan (postprocess_dev.h: wave_pick) over the robot's samples, then
 //     the pick's positions, un-normalised again from the sample.
-// Bitwise the results of the chain of calls (tests/test_gpu_round_pick.py).
+// Bitwise the results of the chain of calls (tests/test_gpu_round_pick.py), and held to its definition on the CPU (tests/round_pick_model.py)
+// at every decision edge and pick size (tests/test_gpu_round_pick_edges.py).
 #include "postprocess_dev.h"      // sets fp contract(off)
 #include "collision_dev.h"        // torch_norm2
 #include "round_pick.h"
