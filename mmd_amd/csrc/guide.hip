@@ -20,6 +20,7 @@
 #include "../../include/mmd_amd_debug.h"
 #include "bins_dev.h"
 #include "common.h"
+#include "cons_table_dev.h"
 #include "guide_dev.h"
 
 namespace mmd {
@@ -70,6 +71,7 @@ __device__ __forceinline__ float lane_next(float v) {
 // is a multiple of 8 -- so a 128..256-robot instance (weak scaling over 4-8 GPUs) still reads most of its table from LDS.
 constexpr int LDS_SLOTS_SMALL = 40;
 constexpr int LDS_SLOTS_MAX = 144;
+static_assert(LDS_SLOTS_SMALL % 8 == 0 && LDS_SLOTS_MAX % 8 == 0, "a staged table is padded to a multiple of 8 slots inside these (stage_cons)");
 
 // -sum over a slot range of d/||d|| for points with ||d|| <= R  (CostConstraint, cost_functions.py:297-326), from a
 // [slot][t] table `tab` (LDS or global) of (qx, qy, R, R|R|).  A point is active iff R >= 0 and not (dist > R)
@@ -109,22 +111,23 @@ __device__ __forceinline__ f32x2g cons_term(f32x2g a, f32x2g p, f32x2g q, float 
 }
 // one table entry as (q, R|R|): the general table holds (qx, qy, R, R|R|) (R < 0: empty, R|R| < 0 <= d2), the compact on-chip
 // table (qx, qy) with one radius for every active point and "no point" stored as (1e30, 1e30): dist^2 = inf > R^2
+// none(): an entry that cannot act in that form -- what pads a staged table (stage_cons)
 template <bool COMPACT> struct ConsTab;
 template <> struct ConsTab<false> {
+  typedef float4 entry;
   const float4* tab;
   float r2;
-  __device__ __forceinline__ f32x2g add(f32x2g a, f32x2g p, int slot, int t) const {
-    const float4 c = tab[slot * H + t];
-    return cons_term(a, p, f32x2g{c.x, c.y}, c.w);
-  }
+  static __device__ __forceinline__ entry none() { return empty_word(); }
+  __device__ __forceinline__ f32x2g term(f32x2g a, f32x2g p, entry c) const { return cons_term(a, p, f32x2g{c.x, c.y}, c.w); }
+  __device__ __forceinline__ f32x2g add(f32x2g a, f32x2g p, int slot, int t) const { return term(a, p, tab[slot * H + t]); }
 };
 template <> struct ConsTab<true> {
+  typedef float2 entry;
   const float2* tab;
   float r2;
-  __device__ __forceinline__ f32x2g add(f32x2g a, f32x2g p, int slot, int t) const {
-    const float2 c = tab[slot * H + t];
-    return cons_term(a, p, f32x2g{c.x, c.y}, r2);
-  }
+  static __device__ __forceinline__ entry none() { return make_float2(1e30f, 1e30f); }
+  __device__ __forceinline__ f32x2g term(f32x2g a, f32x2g p, entry c) const { return cons_term(a, p, f32x2g{c.x, c.y}, r2); }
+  __device__ __forceinline__ f32x2g add(f32x2g a, f32x2g p, int slot, int t) const { return term(a, p, tab[slot * H + t]); }
 };
 // accumulator (rel + i) & 3 += slot (first + i) of `tab` for i in [0, n): rel = the first slot's index relative to its group
 template <class TAB>
@@ -189,12 +192,73 @@ struct GroupMeta {
   }
 };
 
+// the SDF cell of a position without grids: n_grids == 0 means the map has no fixed objects (sdf == 1 everywhere,
+// primitives.py:109-110), so the hinge of this cell is 0
+__device__ __forceinline__ float4 no_cell() { return make_float4(1e30f, 0.f, 0.f, 0.f); }
+
+// CostCollision over the SDF grids: w_coll * clip(d/dp max_k relu(margin - sdf_k(p)))  (t >= 1; field_factor.py range [1,None]); cell0 =
+// grid 0's cell (ix, iy) of p = (px, py), or no_cell()
+template <bool DUMP>
+__device__ __forceinline__ f32x2g map_term(const GuideDev& g, const float4* __restrict__ grid, int ix, int iy, float4 cell0, float px, float py,
+                                           unsigned int& flags) {
+  float best = fmaxf(g.margin - cell0.x, 0.f), gx = 0.f, gy = 0.f;
+  unsigned win = 0;
+  if (best > 0.f) { gx = -cell0.y; gy = -cell0.z; }
+  for (int k = 1; k < g.n_grids; ++k) {
+    const float4 c = grid[((size_t)k * g.nx + ix) * g.ny + iy];
+    const float v = fmaxf(g.margin - c.x, 0.f);
+    if (v > best) { best = v; gx = -c.y; gy = -c.z; win = (unsigned)k; }
+  }
+  if (g.n_xs + g.n_xb > 0) {                             // the env's extra objects: one more field, analytic
+    float ex, ey;
+    const float v = fmaxf(g.margin - extra_sdf(g.xs, g.n_xs, g.xb, g.n_xb, px, py, ex, ey), 0.f);
+    if (v > best) { best = v; gx = -ex; gy = -ey; win = 7u; }
+  }
+  const bool clipped = clip_grad(g, gx, gy);
+  if constexpr (DUMP) {
+    if (best > 0.f) flags |= 1u | (win & 7u) << 1;
+    flags |= (clipped ? 1u : 0u) << 8;
+  }
+  return f32x2g{g.w_coll * gx, g.w_coll * gy};
+}
+
+// A launch on a map without grids and without extra objects (EnvEmpty2D: the planning rounds' own map) has the same map term at every
+// point and in every iteration: map_term of no_cell(), which is w_coll * 0.  It is evaluated once per launch, by map_term itself so
+// that it is that value for every parameter set, and the iterations skip the cell index (two IEEE divides), the gather, the arg max and
+// the clip behind a wave-uniform branch.  The trace instantiation reports the cell and never skips.
+struct MapFree {
+  bool on;
+  f32x2g o;
+};
+template <bool DUMP>
+__device__ __forceinline__ MapFree map_free_term(const GuideDev& g) {
+  MapFree m{!DUMP && g.n_grids == 0 && g.n_xs + g.n_xb == 0, f32x2g{0.f, 0.f}};
+  if (m.on) {
+    GuideDev e = g;                                          // (the compiler does not carry m.on into map_term's loop bounds)
+    e.n_grids = e.n_xs = e.n_xb = 0;
+    unsigned int flags = 0;
+    const f32x2g o = map_term<false>(e, nullptr, 0, 0, no_cell(), 0.f, 0.f, flags);
+    m.o.x = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, o.x)));
+    m.o.y = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, o.y)));
+  }
+  return m;
+}
+
+// the one constraint group a robot has under a cell table (BinnedSum), or whose slots its workgroup has staged, all of them
+// (PaddedSum): no group tables to read in the iterations, its weight is the sum's
+struct OneGroup {
+  static constexpr bool kOneGroup = true;
+  float w;
+  __device__ __forceinline__ void load(const GuideDev&, int, int) {}
+  __device__ __forceinline__ float weight(const GuideDev&, int) const { return w; }
+};
+
 // group_sum(grp, p) = the slot sum of constraint group grp at the lane's position p (the canonical four-accumulator tree above)
 // DUMP (mmd_debug_ddpm_step_trace only): the iteration's discrete decisions of this support point -> tr[0 .. MMD_TRACE_WORDS)
 // (layout: include/mmd_amd_debug.h).  The constraint masks are re-derived slot by slot from the L2-resident table with
 // cons_term's own expression, so they are the decisions the sums above took.
 template <bool DUMP = false, class GROUPSUM, class GROUPW>
-__device__ __forceinline__ float4 guide_grad(const GuideDev& g, float4 xn, int t, const float4* __restrict__ grid,
+__device__ __forceinline__ float4 guide_grad(const GuideDev& g, float4 xn, int t, const float4* __restrict__ grid, const MapFree& mf,
                                              int grp0, int grp1, GROUPSUM group_sum, GROUPW group_weight, unsigned int* tr = nullptr) {
   unsigned int flags = 0;
   // LimitsNormalizer.unnormalize (normalization.py:157-168), clip applied unconditionally
@@ -211,12 +275,16 @@ __device__ __forceinline__ float4 guide_grad(const GuideDev& g, float4 xn, int t
   const bool interior = t > 0 && t < H - 1;   // rows 0 and H-1 are zeroed for every term (guides.py:217-218)
 
   // SDF gathers are issued first and consumed last: their L2 latency hides behind the GP / constraint arithmetic
-  int ix = (int)floorf((px - g.lo[0]) / g.dim[0] * (float)g.nx);
-  int iy = (int)floorf((py - g.lo[1]) / g.dim[1] * (float)g.ny);
-  ix = min(max(ix, 0), g.nx - 1);
-  iy = min(max(iy, 0), g.ny - 1);
-  // n_grids == 0: the map has no fixed objects (sdf == 1 everywhere, primitives.py:109-110) -> the term is identically 0
-  const float4 cell0 = g.n_grids > 0 ? grid[(size_t)ix * g.ny + iy] : make_float4(1e30f, 0.f, 0.f, 0.f);
+  int ix, iy;                                                // (read by map_term alone, which !mf.on guards as well: no value, no
+  float4 cell0;                                              //  copies on the map-free path)
+  if (!mf.on) {
+    cell0 = no_cell();
+    ix = (int)floorf((px - g.lo[0]) / g.dim[0] * (float)g.nx);
+    iy = (int)floorf((py - g.lo[1]) / g.dim[1] * (float)g.ny);
+    ix = min(max(ix, 0), g.nx - 1);
+    iy = min(max(iy, 0), g.ny - 1);
+    if (g.n_grids > 0) cell0 = grid[(size_t)ix * g.ny + iy];
+  }
 
   // --- CostCollision over the workspace boundaries (distance_fields.py:354-367)
   float wsx, wsy;
@@ -289,29 +357,10 @@ __device__ __forceinline__ float4 guide_grad(const GuideDev& g, float4 xn, int t
     const float w = group_weight(grp);
     cx += w * gx; cy += w * gy;
   }
-  // --- CostCollision over the SDF grids: d/dp max_k relu(margin - sdf_k(p))  (t >= 1; field_factor.py range [1,None])
-  float ox, oy;
-  {
-    float best = fmaxf(g.margin - cell0.x, 0.f), gx = 0.f, gy = 0.f;
-    unsigned win = 0;
-    if (best > 0.f) { gx = -cell0.y; gy = -cell0.z; }
-    for (int k = 1; k < g.n_grids; ++k) {
-      const float4 c = grid[((size_t)k * g.nx + ix) * g.ny + iy];
-      const float v = fmaxf(g.margin - c.x, 0.f);
-      if (v > best) { best = v; gx = -c.y; gy = -c.z; win = (unsigned)k; }
-    }
-    if (g.n_xs + g.n_xb > 0) {                             // the env's extra objects: one more field, analytic
-      float ex, ey;
-      const float v = fmaxf(g.margin - extra_sdf(g.xs, g.n_xs, g.xb, g.n_xb, px, py, ex, ey), 0.f);
-      if (v > best) { best = v; gx = -ex; gy = -ey; win = 7u; }
-    }
-    const bool clipped = clip_grad(g, gx, gy);
-    if constexpr (DUMP) {
-      if (best > 0.f) flags |= 1u | (win & 7u) << 1;
-      flags |= (clipped ? 1u : 0u) << 8;
-    }
-    ox = g.w_coll * gx; oy = g.w_coll * gy;
-  }
+  // --- CostCollision over the SDF grids (map_term), or its one value on a map without any (MapFree)
+  f32x2g o = mf.o;
+  if (!mf.on) o = map_term<DUMP>(g, grid, ix, iy, cell0, px, py, flags);
+  const float ox = o.x, oy = o.y;
   if constexpr (DUMP) {
     tr[0] = (unsigned int)(ix * g.ny + iy);
     tr[1] = flags | (unsigned int)min(grp1 - grp0, 15) << 20;
@@ -326,21 +375,33 @@ __device__ __forceinline__ float4 guide_grad(const GuideDev& g, float4 xn, int t
 // ---- What the two step kernels below share, each fragment written once: the kernels are required to produce the same bits, so they
 // ---- run the same text.  They keep only how a trajectory maps to waves and how a group's slot sum is split over them.
 
-// Up to lds_slots slots of `robot`'s constraint table -> LDS, by the NT threads of the workgroup (the caller's barrier follows)
-template <bool COMPACT, int NT>
+// Up to lds_slots slots of `robot`'s constraint table -> LDS, by the NT threads of the workgroup (the caller's barrier follows).
+//
+// PAD (the one-wave kernel; its launch sizes LDS for lds_slots rounded up to a multiple of 8): lds_n > 0 staged slots are followed by
+// ConsTab<COMPACT>::none() entries up to the next multiple of 8, so that a robot's one group, staged whole, can be summed in trips of
+// exactly eight slots (PaddedSum).  A padding slot cannot change the sum's bits: it runs cons_term with d2 > r2 (compact: q = 1e30 and
+// p is finite -- the unnormaliser clips, a NaN included -- so d2 = inf; general: r2 = -1 < 0 <= d2), hence m = 0 and a <- fma(-d, 0, a)
+// = a + (-+0), which is a for a != 0 and +0 for a = +0 (round to nearest: +0 + -0 = +0).  An accumulator is never -0: a chain starts at
+// +0, an fma whose exact result is zero gives -0 only if both addends are -0 (the addend a is not, by induction), and a nonzero exact
+// result does not round to zero (SAME BITS below has the numbers).  Were p not finite, the padding would do what every real slot
+// does: d = NaN or inf makes the term NaN whether m is 0 or not, and the sum is NaN with or without it.  An empty table (a robot
+// whose groups have no slots) is not padded.
+template <bool COMPACT, int NT, bool PAD>
 __device__ __forceinline__ void stage_cons(const GuideDev& g, int robot, int lds_slots, float4* lds_cons, int& lds_slot0, int& lds_n) {
   lds_slot0 = __builtin_amdgcn_readfirstlane(g.grp_slot_off[g.robot_grp_off[robot]]);
   lds_n = min(__builtin_amdgcn_readfirstlane(g.grp_slot_off[g.robot_grp_off[robot + 1]]) - lds_slot0, lds_slots);
   const float4* src = g.cons + (size_t)lds_slot0 * H;
+  typename ConsTab<COMPACT>::entry* dst = reinterpret_cast<typename ConsTab<COMPACT>::entry*>(lds_cons);
   if constexpr (COMPACT) {
-    float2* dst = reinterpret_cast<float2*>(lds_cons);
     for (int i = threadIdx.x; i < lds_n * H; i += NT) {
       const float4 c = src[i];
-      dst[i] = c.z < 0.f ? make_float2(1e30f, 1e30f) : make_float2(c.x, c.y);
+      dst[i] = c.z < 0.f ? ConsTab<true>::none() : make_float2(c.x, c.y);
     }
   } else {
     for (int i = threadIdx.x; i < lds_n * H; i += NT) lds_cons[i] = src[i];
   }
+  if constexpr (PAD)
+    for (int i = lds_n * H + threadIdx.x; i < ((lds_n + 7) & ~7) * H; i += NT) dst[i] = ConsTab<COMPACT>::none();
 }
 
 // The slots of group grp in order: the LDS-resident ones (the lds_n slots of the table from lds_slot0 on, staged by stage_cons<COMPACT>)
@@ -359,6 +420,59 @@ __device__ __forceinline__ void group_slots(const GuideDev& g, const GroupMeta& 
   const int g0 = lds_n > 0 ? max(s0, lds_slot0 + lds_n) : s0;                                    // global part
   if (s1 > g0) acc(ConsTab<false>{g.cons, 0.f}, g0, s1 - g0, g0 - s0);
 }
+
+// The slot sum of a robot's ONE group when stage_cons<.., PAD> has staged all of it: LDS slots [0, n8), n8 = the group's slot count
+// rounded up to a multiple of 8, the group's first slot at 0 (rel = 0: slot i belongs to accumulator i & 3, which a trip of eight
+// keeps).  Trips of exactly eight slots: no remainder code, no accumulator selection.  The first trip's entries are read once per
+// launch (hold_first: the table does not change over the iterations) and stay in registers; the reads of every later trip are issued
+// before the arithmetic of the trip in front of it, into two buffers of eight entries, and the scheduling barriers keep them there --
+// so no LDS wait sits in front of its consumer.  The read behind the last trip repeats that trip's and is dropped: no branch around a
+// read.  Every real slot goes through ConsTab::term into the accumulator and in the order cons_accumulate4 gives it; the padding
+// leaves the bits alone (stage_cons): the canonical sum.
+template <bool COMPACT>
+struct PaddedSum {
+  typedef typename ConsTab<COMPACT>::entry entry;
+  ConsTab<COMPACT> tab;
+  int n8, t;
+  float weight;
+  entry first[8];
+  __device__ __forceinline__ void load(entry (&c)[8], int slot) const {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) c[j] = tab.tab[(slot + j) * H + t];
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  __device__ __forceinline__ void apply(Acc4& acc, const entry (&c)[8], f32x2g p) const {
+#pragma unroll
+    for (int j = 0; j < 8; j += 4) {
+      acc.a0 = tab.term(acc.a0, p, c[j]);
+      acc.a1 = tab.term(acc.a1, p, c[j + 1]);
+      acc.a2 = tab.term(acc.a2, p, c[j + 2]);
+      acc.a3 = tab.term(acc.a3, p, c[j + 3]);
+    }
+  }
+  // (waited for here, s_waitcnt lgkmcnt(0), once: left pending into the iterations next to a scalar load, the first use inside them
+  // would wait for everything outstanding, the reads just issued for the second trip included)
+  __device__ __forceinline__ void hold_first() {
+    load(first, 0);
+    __builtin_amdgcn_s_waitcnt(0xc07f);
+  }
+  __device__ __forceinline__ f32x2g operator()(const OneGroup&, int, f32x2g p) const {
+    Acc4 acc = acc4_zero();
+    entry b[8], c[8];
+    const int last = n8 - 8;                                 // the last trip's first slot
+    load(b, min(8, last));
+    apply(acc, first, p);
+    int i = 8;                                               // b holds the trip at slot i (where i <= last)
+    for (; i + 8 <= last; i += 16) {
+      load(c, i + 8);
+      apply(acc, b, p);
+      load(b, min(i + 16, last));
+      apply(acc, c, p);
+    }
+    if (i <= last) apply(acc, b, p);
+    return acc4_total(acc);
+  }
+};
 
 // The lane's support point after the step's model update (as it is in a guide-only launch: eps is not read then).  (s and v by value:
 // through references the compiler merges the three updates' code differently from the statements written out in a kernel.)
@@ -387,13 +501,14 @@ __device__ __forceinline__ void guide_iterations(const GuideDev& g, const StepDe
   META gm;
   if constexpr (META::kOneGroup) gm.w = group_sum.weight;
   gm.load(g, grp0, grp1);
+  const MapFree mf = map_free_term<DUMP>(g);
   for (int it = 0; it < s.n_guide_steps; ++it) {
     unsigned int* tr = nullptr;
     if constexpr (DUMP) {
       tr = s.trace + ((size_t)it * s.guide_chain_stride + idx) * MMD_TRACE_WORDS;
       for (int w = 0; w < MMD_TRACE_WORDS; ++w) tr[w] = 0u;
     }
-    const float4 gr = guide_grad<DUMP>(g, v, t, grid, grp0, grp1, [&](int grp, f32x2g p) { return group_sum(gm, grp, p); },
+    const float4 gr = guide_grad<DUMP>(g, v, t, grid, mf, grp0, grp1, [&](int grp, f32x2g p) { return group_sum(gm, grp, p); },
                                        [&](int grp) { return gm.weight(g, grp); }, tr);
     // (x + model_var * grad with scale_grad_by_std, sample_functions.py:100-104; grad_scale = 1 otherwise: the fma is then the add)
     v.x = __builtin_fmaf(s.grad_scale, gr.x, v.x); v.y = __builtin_fmaf(s.grad_scale, gr.y, v.y);
@@ -432,7 +547,7 @@ __global__ __launch_bounds__(WPB * 64) void ddpm_guide_kernel(GuideDev g, StepDe
   if (s.do_guide && g.robot_grp_off) {
     const int rb0 = traj_b / samples_per_robot;
     const int rb1 = min(traj_b + WPB - 1, s.traj_end - 1) / samples_per_robot;
-    if (rb0 == rb1) stage_cons<COMPACT, WPB * 64>(g, rb0, lds_slots, lds_cons, lds_slot0, lds_n);
+    if (rb0 == rb1) stage_cons<COMPACT, WPB * 64, true>(g, rb0, lds_slots, lds_cons, lds_slot0, lds_n);
   }
   __syncthreads();
   if (!valid) return;
@@ -447,7 +562,22 @@ __global__ __launch_bounds__(WPB * 64) void ddpm_guide_kernel(GuideDev g, StepDe
     // first one -- guide_gradient_steps, sample_functions.py:89-107)
     if (s.mu_out) s.mu_out[idx] = v;
   }
-  if (s.do_guide)
+  // the staged table (of this wave's robot: lds_n > 0) is the robot's one group, all of it: the padded, straight-line slot pass.
+  // Anything else -- a second group, slots left in the L2-resident table, no table, the trace -- goes through group_slots.
+  bool padded = false;
+  if constexpr (!DUMP) {
+    if (s.do_guide && lds_n > 0) {
+      const int g0 = __builtin_amdgcn_readfirstlane(g.robot_grp_off[robot]), g1 = __builtin_amdgcn_readfirstlane(g.robot_grp_off[robot + 1]);
+      padded = g1 - g0 == 1 && __builtin_amdgcn_readfirstlane(g.grp_slot_off[g1]) - lds_slot0 == lds_n;
+      if (padded) {
+        const float w = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, g.grp_weight[g0])));
+        PaddedSum<COMPACT> sum{{reinterpret_cast<const typename ConsTab<COMPACT>::entry*>(lds_cons), g.uniform_r2}, (lds_n + 7) & ~7, t, w};
+        sum.hold_first();
+        guide_iterations<false, OneGroup>(g, s, robot, t, idx, v, is_hard, hv, true, sum);
+      }
+    }
+  }
+  if (s.do_guide && !padded)
     guide_iterations<DUMP>(g, s, robot, t, idx, v, is_hard, hv, true, [&](const GroupMeta& gm, int grp, f32x2g p) {
       Acc4 acc = acc4_zero();
       group_slots<COMPACT>(g, gm, grp, lds_cons, lds_slot0, lds_n,
@@ -475,7 +605,7 @@ __global__ __launch_bounds__(256) void ddpm_guide_coop_kernel(GuideDev g, StepDe
   const int robot = traj / samples_per_robot;
   float2* const xch = reinterpret_cast<float2*>(reinterpret_cast<char*>(lds_cons) + (size_t)lds_slots * H * (COMPACT ? 8 : 16));
   int lds_slot0 = 0, lds_n = 0;
-  if (s.do_guide && g.robot_grp_off) stage_cons<COMPACT, 256>(g, robot, lds_slots, lds_cons, lds_slot0, lds_n);
+  if (s.do_guide && g.robot_grp_off) stage_cons<COMPACT, 256, false>(g, robot, lds_slots, lds_cons, lds_slot0, lds_n);
   __syncthreads();
   const size_t idx = (size_t)traj * H + t;
   float4 v = model_update(s, x[idx], eps, idx);
@@ -526,14 +656,6 @@ __global__ __launch_bounds__(256) void ddpm_guide_coop_kernel(GuideDev g, StepDe
 // of the GPU), the padding of a lane whose list has ended -- run cons_term with m = 0 and leave their accumulator's bits alone.  (p is
 // finite: the unnormaliser clips.  Time step 0 has empty lists where the dense table has R = -1.)
 // (bin_cell and the lookup of a point's own list, own_cell_list, are in bins_dev.h: the collision kernels of multi_agent.hip walk the same lists.)
-
-// the one constraint group a robot has under a cell table: no group tables to read, its weight is the table's
-struct OneGroup {
-  static constexpr bool kOneGroup = true;
-  float w;
-  __device__ __forceinline__ void load(const GuideDev&, int, int) {}
-  __device__ __forceinline__ float weight(const GuideDev&, int) const { return w; }
-};
 
 // group_sum of the cell table at the lane's point p (time step t, the lane's robot = global id `self`).  The wave walks the lists four
 // entries a trip -- the loads of a trip are issued together -- while any lane has entries left.
@@ -722,7 +844,9 @@ int launch_step(const GuideDev& g, StepDev s, float* x, const float* eps, const 
                                 hipFuncAttributeMaxDynamicSharedMemorySize, LDS_SLOTS_MAX * H * 16);
       attr_devices.fetch_or(bit, std::memory_order_release);
     }
-    launch(compact ? ddpm_guide_kernel<8, true> : ddpm_guide_kernel<8, false>, (n_traj + 7) / 8, 512, (size_t)slots * bytes_per_slot, slots);
+    // (LDS for the staged slots and their padding to a multiple of 8 -- stage_cons: big is one, so this stays inside the opt-in)
+    launch(compact ? ddpm_guide_kernel<8, true> : ddpm_guide_kernel<8, false>, (n_traj + 7) / 8, 512,
+           (size_t)((slots + 7) & ~7) * bytes_per_slot, slots);
   } else {
     const int slots = guided ? small : 0;
     launch(compact ? ddpm_guide_kernel<4, true> : ddpm_guide_kernel<4, false>, (n_traj + 3) / 4, 256, (size_t)slots * bytes_per_slot, slots);
