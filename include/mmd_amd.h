@@ -956,6 +956,50 @@ int mmd_grid_window_goals_apart(const int32_t* dist_dev, int nx, int ny, int n_f
                                 int32_t* extra_dev /* [n][2] */, int32_t* samples_dev /* [n][64][2] or NULL */,
                                 int32_t* changed_dev /* [1] */, void* stream);
 
+/* World fleets: standing robots step aside for the robots they hold back, and those walk in the same epoch
+ * (mmd_amd/world_fleet.py::subgoals_aside is the definition on the host; safety and containment are argued in that module's docstring;
+ * csrc/window_aside.hip).  The call continues mmd_grid_window_goals_apart: apart_work_dev is that call's workspace for the same n_queries
+ * and max_steps AT ITS FIXED POINT (changed == 0), which gives every query's walk c_q[0 .. walked_q] and k_q; it is only read.
+ *   stands_j   j takes part and k_j == 0;      held_r   stands_r and walked_r >= 1
+ *   clears(j)  the r with held_r, r != j, stands_j, c_j[0] in conflict with c_r[1], and (not held_j or r < j);  j YIELDS iff it is not empty
+ *   side step  of a yielder j, the yielders taken in index order: l(c) is the 4-connected BFS distance from c_j[0] over the cells of the grid
+ *              within Chebyshev distance aside_reach of it that j's own field dist[field[j]] reaches; among the cells with
+ *              1 <= l(c) <= aside_steps that conflict with no final cell of another taking-part robot (a yielder i > j still on its start)
+ *              and with no cell of the walk of any r in clears(j), the least (l(c), dist[field[j]][c], ix, iy); none: j stays
+ *   release    r with held_r that did not move aside and lies in clears(j) of some j that did, in index order: mmd_grid_window_goals_apart's
+ *              rule on c_r against the final cells of all others (a released robot of higher index still on its start) gives k'_r
+ * THE FACTS: start cells pairwise sep apart give final cells pairwise sep apart; a side cell lies within aside_reach <= reach of the start,
+ * hence in the robot's window.  No liveness is claimed.
+ * The choice is a fixed point of sweeps (two buffers; per sweep one launch of one 256-thread workgroup per robot for the side steps --
+ * LDS: the patch of (2 aside_reach + 3)^2 uint16 levels -- and one of one wave per robot for the release, which reads the side steps just
+ * written).  A yielder depends on the yielders below it only, a released robot on the side steps and on the released robots below it:
+ * the fixed point is unique, it is the definition's, 2 n_queries sweeps always reach it, and changed == 0 proves it is reached.
+ *   restart != 0: derives the roles from the apart workspace and resets the state (nobody moved, nobody released); then n_sweeps sweeps.
+ *   restart == 0: n_sweeps more sweeps on work_dev as the previous call on the same arguments left it.
+ * Either way the call then writes, for the state it reached, every word of every output for every query:
+ *   a robot that moved aside   cells = the side cell c, summary = (l(c), dist[field][c], 0, dist[field][c] == 0)
+ *   a released robot           cells = c_r[k'_r], summary = (k'_r, dist[c0] - k'_r, 0, dist[c0] == k'_r)
+ *   everyone else              mmd_grid_window_goals_apart's cells and summary
+ *   origins_dev, extra_dev     mmd_grid_window_goals_apart's words
+ *   aside_dev[q] = (role bits, l): 1 HELD, 2 YIELDS, 4 MOVED, 8 RELEASED; l = 0 unless MOVED; (0, 0) for a query that takes no part
+ *   changed_dev[0] = the number of side steps plus the number of k that moved in the call's last sweep (after a restart with
+ *                    n_sweeps == 0: the number of queries that take part)
+ * Field values are taken as distances in [0, 2^22): the tie on l is broken by min(max(value, 0), 2^22 - 1).
+ * The call does not synchronise.  work_dev: mmd_grid_window_aside_work_bytes(n_queries) bytes, 16-byte aligned; a restart initialises it.
+ * Error returns, before anything is launched: the ranges of mmd_grid_window_goals_apart; aside_reach outside
+ * 1 .. min(reach, MMD_WINDOW_ASIDE_MAX_REACH); aside_steps outside 1 .. MMD_WINDOW_ASIDE_MAX_STEPS; a negative n_sweeps; with
+ * n_queries > 0, a NULL dist (with n_fields > 0) or field, a NULL, misaligned or short workspace of either kind, or a NULL output.
+ * n_queries == 0 returns 0 and launches nothing.  mmd_grid_window_aside_work_bytes returns 0 for a size the call refuses (and for 0). */
+#define MMD_WINDOW_ASIDE_MAX_REACH 63
+#define MMD_WINDOW_ASIDE_MAX_STEPS 4095
+size_t mmd_grid_window_aside_work_bytes(int n_queries);
+int mmd_grid_window_goals_aside(const int32_t* dist_dev, int nx, int ny, int n_fields, const int32_t* field_dev /* [n] */, int n_queries,
+                                int reach, int max_steps, int window, int sep, int aside_reach, int aside_steps, int restart, int n_sweeps,
+                                const void* apart_work_dev, size_t apart_work_bytes, void* work_dev, size_t work_bytes,
+                                int32_t* cells_dev /* [n][2] */, int32_t* origins_dev /* [n][2] */, int32_t* summary_dev /* [n][4] */,
+                                int32_t* extra_dev /* [n][2] */, int32_t* aside_dev /* [n][2] */, int32_t* changed_dev /* [1] */,
+                                void* stream);
+
 /* World fleets: one window set for a whole run, moved between epochs (csrc/fleet_epoch.hip).
  *
  * mmd_sdf_grid_windows for windows that mostly stay where they are: the same clamped gather, the same arguments and the same words

@@ -217,6 +217,10 @@ _SIGNATURES = {
     "mmd_grid_window_goals_apart": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                               C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mmd_grid_window_aside_work_bytes": (C.c_size_t, [C.c_int]),
+    "mmd_grid_window_goals_aside": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                              C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p,
+                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mmd_sdf_grid_windows_moved": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                              C.c_void_p]),
     "mmd_fleet_epoch_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_double),
@@ -226,6 +230,7 @@ _SIGNATURES = {
                                        C.c_void_p, C.c_float, C.c_float, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p]),
 }
 WINDOW_APART_MAX_STEPS, WINDOW_APART_MAX_SEP = 4095, 1024   # MMD_WINDOW_APART_MAX_STEPS, MMD_WINDOW_APART_MAX_SEP
+WINDOW_ASIDE_MAX_REACH, WINDOW_ASIDE_MAX_STEPS = 63, 4095   # MMD_WINDOW_ASIDE_MAX_REACH, MMD_WINDOW_ASIDE_MAX_STEPS
 ROUTE_SEED_POINTS, ROUTE_SEED_MAX_TILES = 64, 16            # MMD_ROUTE_SEED_POINTS, MMD_ROUTE_SEED_MAX_TILES
 GRID_DIST_BLOCK, GRID_DIST_UNREACHED = 64, 0x7fffffff       # MMD_GRID_DIST_BLOCK, MMD_GRID_DIST_UNREACHED
 

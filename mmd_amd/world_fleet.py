@@ -75,6 +75,51 @@ j < r: after sweep s the robots 0 .. s - 1 hold the definition's k (robot 0 depe
 unique, it is subgoals_apart's result, n sweeps always reach it, and a sweep in which no k moved (changed == 0) proves it is reached,
 because a sweep is a function of the state before it.
 
+STEPPING ASIDE (WorldFleet(step_aside=True), opt-in, on top of the separation).  A walk is a fixed descent of its goal's field and cannot
+go round another robot, so a robot that stands still -- it has arrived, or it is itself held -- is a wall for every walk that passes
+within sep cells of it, and the run ends stalled.  subgoals_aside IS the definition of an epoch in which such a robot steps aside and
+the robot it held walks at once; the kernels (csrc/window_aside.hip) compute the same integers.
+
+  phase 1    subgoals_apart, unchanged: k_r, walked_r, the walks c_r[0 .. walked_r], cell_r = c_r[k_r] of every query that takes part
+  roles      stands_j: j takes part and k_j == 0.  held_r: stands_r and walked_r >= 1.  clears(j): the r with held_r, r != j, stands_j,
+             c_j[0] in conflict with c_r[1], and (not held_j or r < j); j YIELDS iff clears(j) is not empty.  A standing robot that is not
+             held (it has arrived, or walked = 0) yields to anyone, a held robot only to held robots of lower index.
+  phase 2    the yielders in ascending index.  l_j(c) is the 4-connected BFS distance from c_j[0] over the cells of the grid within
+             Chebyshev distance aside_reach of it that j's OWN field reaches (it is finite exactly on the routable cells connected to the
+             goal, the start among them: no texture is needed).  The candidates are the cells with 1 <= l_j(c) <= aside_steps that
+             conflict with (a) no cell_i of a taking-part i != j that does not yield, (b) no final cell of a yielder i < j, (c) no start
+             of a yielder i > j, (d) no cell c_r[0 .. walked_r] of any r in clears(j); the choice is the least
+             (l_j(c), own field at c, ix, iy), and with no candidate the robot stays.
+  phase 3    released: the r with held_r that did not move aside and lie in clears(j) of some j that did.  In ascending index r applies
+             subgoals_apart's rule to its walk once more, against the final cells of all other taking-part robots as they stand then
+             (a released robot of higher index still on its start).  Without this phase the yielder walks back in the next epoch before
+             the held robot has moved.
+  outputs    moved aside: cell = the side cell, summary (l, own field there, status, own field there == 0); released: cell c_r[k'],
+             summary (k', d0 - k', status, d0 == k'); everyone else phase 1's words; origins and extra are phase 1's;
+             aside = (role bits, l): ASIDE_HELD 1, ASIDE_YIELDS 2, ASIDE_MOVED 4, ASIDE_RELEASED 8, l = 0 unless MOVED
+
+SAFETY.  If the start cells of the taking-part robots are pairwise sep apart, so are the final cells.  The invariant is that the robots'
+CURRENT cells are pairwise apart.  It holds after phase 1 (APART).  Phase 2 moves yielder j to a cell that conflicts with no current cell
+of another robot, for (a), (b) and (c) together are exactly those: a robot that does not yield is on cell_i, a yielder below j on its final
+cell, a yielder above j on its start, which is its cell_i because it stands.  Phase 3 moves a released robot to c_r[k'], k' >= 1, which
+conflicts with no current cell of another robot, or leaves it where it is.  Every move keeps the invariant, and the cells after the last
+move are the final cells (a robot that moved aside is never released, so each robot moves at most once, but the argument does not need
+it).  The ends of one epoch are the starts of the next, so the fact carries through a run (tests/test_world_fleet_aside_host.py checks
+it by brute force over whole runs).
+CONTAINMENT.  The side cell lies in the box of radius aside_reach <= reach round the start, hence in the window (CONTAINMENT above).
+CLEARED.  The side cell conflicts with no cell of the walk of any r in clears(j) (class d): from its start r walks the same cells in the
+next epoch, and none of them conflicts with j's new place.
+No liveness is claimed.  The targets are a function of the robots' cells alone, so a run whose tuple of start cells occurred before would
+repeat for good: that epoch is reported CYCLING and the run stops there; observed on the 24-robot batches of the tests (40 x 30 cells,
+sep 3, box 5, 10 steps, seeds 0 .. 19): 19 of 20 open, 18 of 20 door and 9 of 20 serpentine runs arrive, each of which stalls without
+the rule; the rest cycle, and one stalls.  At the fleet's own scale (400 x 400 open cells, sep 23, reach 180, 32 robots, box 48) the one
+of six seeds that stalls arrives with one side step.  Planning quality with trained weights is not known.
+
+On the device the order among yielders and among released robots is a fixed point of Jacobi sweeps: a yielder reads the side steps that the
+yielders below it held after the sweep before, a released robot the side steps of this sweep and the k of the released robots below it;
+both depend on lower indices only (and the release on all side steps), so the fixed point is unique, it is subgoals_aside's result,
+2 n sweeps always reach it (n settle the side steps, n more the release), and changed == 0 proves it.
+
 SUBGOAL_SEPARATION = 23 is the least separation that keeps two end points RR_MARGIN = 0.105 apart when each lies anywhere in its cell
 of 0.005: centres 23 cells apart leave the points at least 23 - sqrt(2) = 21.59 cells = 0.1079 apart; 22 gives 0.1029, too little.
 
@@ -299,6 +344,80 @@ def subgoals_apart_samples(dist, starts, fields, goals, reach, max_steps, sep, w
     return _apart_outputs(plain, paths, ks, clear) + (_path_samples(paths, ks),)
 
 
+# ---- standing robots step aside: the definition --------------------------------------------------------------------------------------------
+ASIDE_HELD, ASIDE_YIELDS, ASIDE_MOVED, ASIDE_RELEASED = 1, 2, 4, 8              # the role bits of aside[:, 0]
+
+
+def _checked_aside(what, reach, aside_reach, aside_steps):
+    if (int(aside_reach) != aside_reach or int(aside_steps) != aside_steps or not 1 <= int(aside_reach) <= min(int(reach), _lib.WINDOW_ASIDE_MAX_REACH)
+            or not 1 <= int(aside_steps) <= _lib.WINDOW_ASIDE_MAX_STEPS):
+        raise ValueError(f"{what}: aside_reach = {aside_reach} (1 to min(reach, {_lib.WINDOW_ASIDE_MAX_REACH}) = "
+                         f"{min(int(reach), _lib.WINDOW_ASIDE_MAX_REACH)}), aside_steps = {aside_steps} (1 to {_lib.WINDOW_ASIDE_MAX_STEPS})")
+    return int(aside_reach), int(aside_steps)
+
+
+def _aside_levels(own, start, aside_reach, aside_steps):
+    """{cell: l} for the cells with l <= aside_steps: l the 4-connected BFS distance from `start` over the cells of the grid that the field
+    `own` [nx, ny] reaches and that lie within Chebyshev distance aside_reach of the start (the whole path stays among them)"""
+    nx, ny = own.shape
+    levels, front = {tuple(start): 0}, [tuple(start)]
+    for l in range(1, aside_steps + 1):
+        nxt = []
+        for (x, y) in front:
+            for c in ((x + 1, y), (x - 1, y), (x, y + 1), (x, y - 1)):
+                if (c not in levels and 0 <= c[0] < nx and 0 <= c[1] < ny and max(abs(c[0] - start[0]), abs(c[1] - start[1])) <= aside_reach
+                        and int(own[c]) != UNREACHED):
+                    levels[c] = l
+                    nxt.append(c)
+        front = nxt
+        if not front:
+            break
+    return levels
+
+
+def subgoals_aside(dist, starts, fields, goals, reach, max_steps, sep, aside_reach, aside_steps, window=400):
+    """(cells, origins, summary, extra, aside int32 [n, 2] = (role bits, l)): subgoals_apart, and then the standing robots step aside for
+    the robots they hold back, and those walk in the same epoch (the module's docstring, STEPPING ASIDE).  The first four results are in
+    subgoals_apart's formats; origins and extra are subgoals_apart's words.  Role bits: ASIDE_HELD 1, ASIDE_YIELDS 2, ASIDE_MOVED 4,
+    ASIDE_RELEASED 8; l is the length of the side step, 0 unless MOVED.  A robot that moved: cell = its side cell,
+    summary = (l, dist_own[side], ROUTE_OK, dist_own[side] == 0); a released robot: summary = (k', d0 - k', ROUTE_OK, d0 == k'),
+    cell = c_r[k']; every other query keeps subgoals_apart's words.  aside_reach in 1 .. min(reach, 63), aside_steps in 1 .. 4095."""
+    sep = _checked_sep("subgoals_aside", sep)
+    plain, paths = _walks("window_goals", dist, starts, fields, goals, reach, max_steps, window)
+    aside_reach, aside_steps = _checked_aside("subgoals_aside", reach, aside_reach, aside_steps)
+    dist, fields = np.asarray(dist), np.asarray(fields, np.int64).reshape(-1)
+    taking = [q for q, p in enumerate(paths) if p is not None]
+    ks, clear = {}, {}
+    for r in taking:                                         # phase 1: subgoals_apart
+        ks[r], clear[r] = _apart_choice(paths[r], _blockers(paths, taking, ks, r), sep)
+    cells, origins, summary, extra = _apart_outputs(plain, paths, ks, clear)
+    aside = np.zeros((len(paths), 2), np.int32)
+    conflict = lambda a, b: (a[0] - b[0]) ** 2 + (a[1] - b[1]) ** 2 < sep * sep                                       # noqa: E731
+    stands = [j for j in taking if ks[j] == 0]
+    held = [r for r in stands if len(paths[r]) >= 2]
+    clears = {j: [r for r in held if r != j and conflict(paths[j][0], paths[r][1]) and (j not in held or r < j)] for j in stands}
+    final = {q: paths[q][ks[q]] for q in taking}             # every robot's final cell, as the phases move them
+    moved = {}
+    for j in (j for j in stands if clears[j]):               # phase 2: the yielders, in ascending index
+        own = dist[fields[j]]
+        blockers = [final[i] for i in taking if i != j] + [c for r in clears[j] for c in paths[r]]
+        best = min(((l, int(own[c]), c[0], c[1]) for c, l in _aside_levels(own, paths[j][0], aside_reach, aside_steps).items()
+                    if l >= 1 and not any(conflict(c, b) for b in blockers)), default=None)
+        if best is not None:
+            moved[j], final[j] = best[0], (best[2], best[3])
+            cells[j], summary[j] = final[j], (best[0], best[1], ROUTE_OK, int(best[1] == 0))
+    released = [r for r in held if r not in moved and any(r in clears[j] for j in moved)]
+    for r in released:                                       # phase 3: the released robots walk, in ascending index
+        k, _ = _apart_choice(paths[r], [final[i] for i in taking if i != r], sep)
+        d0 = int(summary[r, 0]) + int(summary[r, 1])
+        final[r] = paths[r][k]
+        cells[r], summary[r] = final[r], (k, d0 - k, ROUTE_OK, int(d0 == k))
+    for q in taking:
+        aside[q] = (ASIDE_HELD * (q in held) | ASIDE_YIELDS * bool(clears.get(q)) | ASIDE_MOVED * (q in moved) | ASIDE_RELEASED * (q in released),
+                    moved.get(q, 0))
+    return cells, origins, summary, extra, aside
+
+
 # ---- the report of a run: the definition ---------------------------------------------------------------------------------------------------
 REPORT_MAX_ROBOTS, REPORT_MAX_LENGTH, REPORT_MAX_INTERP = 4096, 65535, 63       # MMD_FLEET_REPORT_MAX_*
 REPORT_HEADER = 8                                                              # MMD_FLEET_REPORT_HEADER: int32 words before the arrays
@@ -505,12 +624,13 @@ def _window_goals_words(dist_dev, starts, fields, goals, reach, max_steps, windo
     return words, samples
 
 
-def _split_words(words, apart=False):
-    """(cells [n, 2], origins [n, 2], summary [n, 4][, extra [n, 2]]), views of a sub-goal launch's words, a tensor or its numpy copy:
-    [8 n], or with `apart` mmd_grid_window_goals_apart's [10 n + 1], with extra and changed behind"""
-    n = (words.shape[0] - 1) // 10 if apart else words.shape[0] // 8
+def _split_words(words, apart=False, aside=False):
+    """(cells [n, 2], origins [n, 2], summary [n, 4][, extra [n, 2][, aside [n, 2]]]), views of a sub-goal launch's words, a tensor or its
+    numpy copy: [8 n], or with `apart` mmd_grid_window_goals_apart's [10 n + 1], with extra and changed behind, or with `aside`
+    mmd_grid_window_goals_aside's [12 n + 1], with extra, aside and changed behind"""
+    n = (words.shape[0] - 1) // (12 if aside else 10) if apart or aside else words.shape[0] // 8
     out = words[:2 * n].reshape(n, 2), words[2 * n:4 * n].reshape(n, 2), words[4 * n:8 * n].reshape(n, 4)
-    return out + ((words[8 * n:10 * n].reshape(n, 2),) if apart else ())
+    return out + ((words[8 * n:10 * n].reshape(n, 2),) if apart or aside else ()) + ((words[10 * n:12 * n].reshape(n, 2),) if aside else ())
 
 
 def device_window_goals(dist_dev, starts, fields, goals, reach, max_steps, window=400):
@@ -594,9 +714,12 @@ def device_epoch_frames(name, words, points, goal_points, norm_mins=synth.NORM_M
             out[12 * n:].view(n, SEED_POINTS, 2))
 
 
-def _subgoals_apart_words(dist_dev, starts, fields, goals, reach, max_steps, sep, window, sweeps, with_samples, what="device_subgoals_apart"):
+def _subgoals_apart_words(dist_dev, starts, fields, goals, reach, max_steps, sep, window, sweeps, with_samples, what="device_subgoals_apart",
+                          kept=None):
     """device_subgoals_apart's launches -> (one int32 tensor [10 n + 1] on the device: cells [n, 2], origins [n, 2], summary [n, 4],
-    extra [n, 2], changed [1]; its last copy on the host, numpy; samples int32 [n, 64, 2] on the device or None; the sweeps run)"""
+    extra [n, 2], changed [1]; its last copy on the host, numpy; samples int32 [n, 64, 2] on the device or None; the sweeps run).
+    kept: a dict that receives the workspace at its fixed point, its size, the launch's leading arguments with their uploads, and n, for
+    the launch that continues from it (_subgoals_aside_words)"""
     reach, max_steps, window = _checked_launch_args(what, dist_dev, reach, max_steps, window)
     sep, sweeps = _checked_sep(what, sep), int(sweeps)
     if max_steps > _lib.WINDOW_APART_MAX_STEPS or sweeps < 1:
@@ -619,6 +742,8 @@ def _subgoals_apart_words(dist_dev, starts, fields, goals, reach, max_steps, sep
         host, run = launch(0, more), run + more
     if host[10 * n] != 0:
         raise RuntimeError(f"{what}: {int(host[10 * n])} robots still moved in sweep {run} of {n} robots: the workspace was disturbed")
+    if kept is not None:
+        kept.update(work=work, work_bytes=work_bytes, lead=lead, uploads=_uploads, n=n)
     return words, host, samples, run
 
 
@@ -631,6 +756,48 @@ def device_subgoals_apart(dist_dev, starts, fields, goals, reach, max_steps, sep
     and changed, which live in one tensor: the common case costs one copy.  The first four results are views of that tensor."""
     words, _, samples, run = _subgoals_apart_words(dist_dev, starts, fields, goals, reach, max_steps, sep, window, sweeps, with_samples)
     return _split_words(words, apart=True) + ((samples,) if with_samples else ()) + (run,)
+
+
+def _subgoals_aside_words(dist_dev, starts, fields, goals, reach, max_steps, sep, aside_reach, aside_steps, window, sweeps,
+                          what="device_subgoals_aside"):
+    """device_subgoals_aside's launches -> (one int32 tensor [12 n + 1] on the device: cells [n, 2], origins [n, 2], summary [n, 4],
+    extra [n, 2], aside [n, 2], changed [1]; its last copy on the host, numpy; the sweeps of phase 1; the sweeps run here).  Phase 1 is
+    _subgoals_apart_words' loop to its fixed point, whose workspace mmd_grid_window_goals_aside then reads."""
+    reach, max_steps, window = _checked_launch_args(what, dist_dev, reach, max_steps, window)
+    sep = _checked_sep(what, sep)
+    aside_reach, aside_steps = _checked_aside(what, reach, aside_reach, aside_steps)
+    kept = {}
+    _, _, _, apart_run = _subgoals_apart_words(dist_dev, starts, fields, goals, reach, max_steps, sep, window, sweeps, False, what, kept)
+    n, lead, sweeps = kept["n"], kept["lead"], int(sweeps)
+    work_bytes = int(_lib.load().mmd_grid_window_aside_work_bytes(n))
+    work = torch.empty(work_bytes, dtype=torch.uint8, device=dist_dev.device)
+    words = torch.empty(12 * n + 1, dtype=torch.int32, device=dist_dev.device)     # (the summary rows start 16 n bytes in: aligned as int4)
+    at = lambda k: C.c_void_p(words.data_ptr() + 4 * k)                          # noqa: E731
+
+    def launch(restart, n_sweeps):
+        _lib.launch("mmd_grid_window_goals_aside", dist_dev, *lead[:4], lead[5], n, reach, max_steps, window, sep, aside_reach, aside_steps,
+                    restart, n_sweeps, C.c_void_p(kept["work"].data_ptr()), kept["work_bytes"], C.c_void_p(work.data_ptr()), work_bytes, at(0),
+                    at(2 * n), at(4 * n), at(8 * n), at(10 * n), at(12 * n))
+        return words.cpu().numpy()
+    cap = 2 * n + 1                                          # 2 n sweeps reach the fixed point, one more reads changed == 0
+    run = min(sweeps, cap)
+    host = launch(1, run)
+    while host[12 * n] != 0 and run < cap:
+        more = min(sweeps, cap - run)
+        host, run = launch(0, more), run + more
+    if host[12 * n] != 0:
+        raise RuntimeError(f"{what}: {int(host[12 * n])} robots still moved in sweep {run} of {n} robots: the workspace was disturbed")
+    return words, host, apart_run, run
+
+
+def device_subgoals_aside(dist_dev, starts, fields, goals, reach, max_steps, sep, aside_reach, aside_steps, window=400, sweeps=4):
+    """(cells int32 [n, 2], origins int32 [n, 2], summary int32 [n, 4], extra int32 [n, 2], aside int32 [n, 2], n_sweeps_run) on dist_dev's
+    device: subgoals_aside() for every query, word for word.  Phase 1 is device_subgoals_apart's loop; then
+    mmd_grid_window_goals_aside on its workspace: a restart call with `sweeps` sweeps, then, while `changed` is not zero, `sweeps` more, at
+    most 2 n + 1 in all (2 n reach the fixed point, the one after reads changed == 0); n_sweeps_run counts these, not phase 1's.  Every call
+    of either entry point ends with one device -> host copy of all its words.  The five arrays are views of one tensor."""
+    words, _, _, run = _subgoals_aside_words(dist_dev, starts, fields, goals, reach, max_steps, sep, aside_reach, aside_steps, window, sweeps)
+    return _split_words(words, aside=True) + (run,)
 
 
 def device_run_report_words(paths_dev, tex_dev, lo, hi, goals, margin, rr_margin=RR_MARGIN, n_interp=3, goal_tol=None, column_conflicts=False):
@@ -694,6 +861,7 @@ class EpochTargets(NamedTuple):
     words: torch.Tensor = None      # int32 [8 N] on the device, (cells, origins, summary) as launched (_split_words); with separation a view
     extra: np.ndarray = None        # separation: int32 [N, 2] = (walked, clear) of subgoals_apart; else None
     sweeps: int = None              # separation: the sweeps device_subgoals_apart ran; else None
+    aside: np.ndarray = None        # step_aside: int32 [N, 2] = (role bits, l) of subgoals_aside; else None
 
 
 class FleetResult(NamedTuple):
@@ -702,7 +870,8 @@ class FleetResult(NamedTuple):
     arrived: np.ndarray         # bool [N]: the robot stands on its exact goal point
     # per epoch {"conflict_counts", "summary", "offsets"}: the PlanResult's counts, the epoch's targets; with seed_epochs also
     # "clear_min", float32 [N]: the least texel value over each robot's seed points; with separation also "held_back" (int [N]: walked - k),
-    # "sweeps" and "stalled" (every k is 0 and some robot is off its goal: every later epoch would repeat this one)
+    # "sweeps" and "stalled" (every k is 0 and some robot is off its goal: every later epoch would repeat this one); with step_aside also
+    # "aside" (int32 [N, 2]: role bits, l), "moved_aside", "released" (int: how many robots) and "cycling" (these start cells occurred before)
     epochs: list
 
 
@@ -739,6 +908,19 @@ class WorldFleet:
     "stalled"; run(max_epochs=None) loops until every robot has arrived or an epoch is stalled (no robot moves, every k is 0: the
     state would repeat for good), which terminates although epoch_bound no longer holds; an explicit max_epochs still caps it.
 
+    step_aside=False (the default): a robot that the separation holds back waits, and a fleet whose robots all wait is stalled.  True
+    (needs separation=; refused with seed_epochs=True): a standing robot steps aside for the robots it holds back, into a cell of its
+    box of radius aside_reach (at most min(reach, 63)) at most aside_steps (at most 4095) steps away, and the robots it held walk in the
+    same epoch (the module's docstring, STEPPING ASIDE: every epoch's pinned ends stay `separation` apart, and a side cell lies in the
+    robot's window).  epoch_targets runs device_subgoals_aside's launches in place of device_subgoals_apart's
+    (mmd_grid_window_goals_apart to its fixed point, then mmd_grid_window_goals_aside on its workspace: a restart call of 4 sweeps and,
+    while the state still moved, 4 more); EpochTargets gains `aside` (role bits, l), every epoch's dict "aside", "moved_aside" and
+    "released" (how many robots) and "cycling" (the tuple of the robots' start cells occurred earlier in the run: epoch_targets is a
+    function of the cells alone, so the run would repeat for good; run() returns after that epoch).  "stalled" keeps its expression: a
+    robot that moved aside has summary[:, 0] = l >= 1, so an epoch with a side step is not stalled; "held_back" keeps its expression too
+    and means nothing for a robot that moved aside.  run(max_epochs=None) is refused: no bound on the epochs is proven, so the caller
+    states the cap.  persistent=True works as ever, bit for bit: the launch's first 8 N words keep their layout.
+
     persistent=False (the default): every epoch builds a WorldRobotSampler, a guide and a named window set of its own and releases the
     set afterwards.  persistent=True keeps ONE sampler (own_windows=True), one guide and
     one window set [N, 1, 400, 400, 4] (slice r is robot r's) for the whole run and moves them between epochs on the device
@@ -757,15 +939,20 @@ class WorldFleet:
       - an arrived robot is sampled like any other, between two ends pinned to its goal point, not held still;
       - the fleet is not sharded over ranks;
       - repair= and replan=, which WorldRobotSampler refuses;
-      - with separation=, a stalled fleet is reported, not resolved (the priorities are the robots' indices and never rotate, and no
-        robot steps aside); without it two sub-goals may coincide.
+      - with separation= alone a stalled fleet is reported, not resolved; with step_aside=True no liveness is proven (a fleet may still
+        stall or cycle), a cycling fleet is reported and not broken (the priorities are the robots' indices and never rotate), and
+        seeded epochs are not built (a side step has no support cells); without separation two sub-goals may coincide.
     Whether a seeded epoch resolves conflicts as well as one from noise is not known."""
 
     def __init__(self, model, name, starts, goals, clearance=OBSTACLE_MARGIN, reach=180, max_steps=360, device="cuda", seed_epochs=False,
-                 smooth_iters=64, n_noising_steps=3, n_denoising_steps=3, separation=None, persistent=False,
-                 **world_robot_sampler_kwargs):
+                 smooth_iters=64, n_noising_steps=3, n_denoising_steps=3, separation=None, persistent=False, step_aside=False,
+                 aside_reach=48, aside_steps=96, **world_robot_sampler_kwargs):
         self.model, self.name, self.device = model, name, environments.resolved_device(device)
-        self.persistent = bool(persistent)
+        self.persistent, self.step_aside = bool(persistent), bool(step_aside)
+        if self.step_aside and separation is None:
+            raise ValueError("WorldFleet: step_aside=True needs separation= (robots step aside for robots that the separation holds back)")
+        if self.step_aside and seed_epochs:
+            raise ValueError("WorldFleet: step_aside=True with seed_epochs=True is not built: a side step has no support cells yet")
         self._sampler = self._points_dev = self._points_host = self._goal_points_dev = self._line_a = self._report_goals_dev = None
         self.separation = None if separation is None else _checked_sep("WorldFleet: separation", separation)
         self.clearance = float(clearance)
@@ -781,6 +968,8 @@ class WorldFleet:
         self.shape = tuple(environments.world_map_occupancy(name).shape)
         self.window = int(environments.grid_shape()[0])
         self.reach, self.max_steps, _ = _checked_walk_args("WorldFleet", self.shape, reach, max_steps, self.window)
+        self.aside_reach, self.aside_steps = (_checked_aside("WorldFleet", self.reach, aside_reach, aside_steps) if self.step_aside
+                                              else (aside_reach, aside_steps))
         self.limits = environments.world_map_limits(name)
         s_pts, self.goal_points = _points(starts), _points(goals)
         n = s_pts.shape[0]
@@ -852,9 +1041,12 @@ class WorldFleet:
         if self.separation is None:
             (words, samples), sweeps = _window_goals_words(*walk, self.window, self.seed_epochs), None
             host = words.cpu().numpy()
+        elif self.step_aside:
+            words, host, sweeps, _ = _subgoals_aside_words(*walk, self.separation, self.aside_reach, self.aside_steps, self.window, 4, "WorldFleet")
+            samples = None
         else:
             words, host, samples, sweeps = _subgoals_apart_words(*walk, self.separation, self.window, 4, self.seed_epochs, "WorldFleet")
-        cells, origins, summary, *extra = (a.copy() for a in _split_words(host, apart=self.separation is not None))
+        cells, origins, summary, *extra = (a.copy() for a in _split_words(host, apart=self.separation is not None, aside=self.step_aside))
         bad = np.flatnonzero(summary[:, 2] != ROUTE_OK)
         if bad.size:
             r = int(bad[0])
@@ -864,7 +1056,7 @@ class WorldFleet:
         arrived = summary[:, 3] == 1
         points[arrived] = self.goal_points[arrived]
         return EpochTargets(cells, origins, environments.world_map_window_offsets(self.name, origins), points, summary, samples,
-                            words[:8 * self.n_robots], extra[0] if extra else None, sweeps)
+                            words[:8 * self.n_robots], extra[0] if extra else None, sweeps, extra[1] if self.step_aside else None)
 
     def _moved_sampler(self, targets):
         """persistent=True: (the fleet's one sampler, moved to the epoch's targets; the robots' points and their sub-goal points [N, 2]
@@ -960,12 +1152,17 @@ class WorldFleet:
         comes), at most max_epochs of them if that is given.  -> FleetResult"""
         apart = self.separation is not None
         if max_epochs is None:
+            if self.step_aside:
+                raise ValueError("WorldFleet.run: step_aside=True needs max_epochs (no bound on the epochs is proven: the caller states the cap)")
             max_epochs = None if apart else self.epoch_bound()
         elif int(max_epochs) < 1:
             raise ValueError(f"WorldFleet.run: max_epochs = {max_epochs} (at least 1)")
-        paths, epochs = [], []
+        paths, epochs, seen = [], [], set()
         try:
             while True:
+                if self.step_aside:                          # the targets are a function of the robots' cells alone: a repeat repeats for good
+                    at = world_cells(self.name, self.positions).tobytes()
+                    cycling, _ = at in seen, seen.add(at)
                 res, targets = self.step(seed + len(epochs), max_rounds)
                 arrived = targets.summary[:, 3] == 1         # the epoch's sub-goal was the goal point: the robot now stands on it
                 paths.append(res.paths_local)
@@ -973,9 +1170,12 @@ class WorldFleet:
                 stalled = bool(apart and (targets.summary[:, 0] == 0).all() and not arrived.all())  # no robot moves, one that arrives now included
                 if apart:
                     epochs[-1].update(held_back=targets.extra[:, 0] - targets.summary[:, 0], sweeps=targets.sweeps, stalled=stalled)
+                if self.step_aside:
+                    epochs[-1].update(aside=targets.aside, moved_aside=int(((targets.aside[:, 0] & ASIDE_MOVED) != 0).sum()),
+                                      released=int(((targets.aside[:, 0] & ASIDE_RELEASED) != 0).sum()), cycling=cycling)
                 if self.seed_epochs:
                     epochs[-1]["clear_min"] = self.last_clear_min
-                if arrived.all() or stalled or (max_epochs is not None and len(epochs) >= int(max_epochs)):
+                if arrived.all() or stalled or (self.step_aside and cycling) or (max_epochs is not None and len(epochs) >= int(max_epochs)):
                     return FleetResult(torch.cat(paths, dim=1), arrived, epochs)
         finally:
             self.close()

@@ -1,6 +1,6 @@
 """What an epoch of a world fleet costs on the device, needs one GPU (run it under `timeout`; one process):
 
-    python tools/dbg/fleet_time.py [--apart | --persistent] [OUT.txt]
+    python tools/dbg/fleet_time.py [--apart | --persistent | --aside] [OUT.txt]
 
 The world is world_route_time.py's: 2048 x 2048 cells, 300 random boxes, clearance world.OBSTACLE_MARGIN.  With N = 64 and N = 256 robots,
 starts and distinct goals drawn from the cells that one routable cell reaches, random-init weights, T = 25, B = 4 samples per robot,
@@ -38,6 +38,15 @@ alternating inside every pass on the same fleet and the same epoch's targets (1 
                          had arrived and stood still: the timed move then cuts N / 2 slices.
 Before these are timed: after a setup, every robot's slice, offsets and hard conditions are a fresh named sampler's, bit for bit.  It runs
 the field build and these legs only, and leaves out the comparisons with the numpy definitions below (the other modes make them).
+--aside times WorldFleet.epoch_targets with step_aside=True (aside_reach 48, aside_steps 96: device_subgoals_apart's loop, then
+mmd_grid_window_goals_aside's restart call of 4 sweeps with its copy back, and 4 more while its state still moved) next to the same call
+with the separation alone, which is the parent commit's path unchanged, the two legs alternating inside every pass on the same fleet:
+  as drawn        the random starts at reach 180: the row says how many robots are held and yield (at this scale, few or none);
+  pairs staged    8 pairs of robots put where the rule works: the goals of robots 2 i and 2 i + 1 are c + (23, 0) and c for a cell c with a
+                  free row, robot 2 i + 1 stands on c and robot 2 i on c - (23, 0), and the reach is 40, so that robot 2 i's walk ends
+                  17 cells beyond c and every cell of it conflicts with the standing robot; both legs run at that reach, with aside_reach 40.
+Before a leg is timed: every robot that neither moved aside nor was released has the words of the separation alone.  It runs the field
+build and these legs only.
 Before anything is timed: the field of robot 0's goal is compared with the numpy definition, and the sub-goals of every 8th robot with
 window_goals on the downloaded fields, integer for integer.  Per repeated figure: 1 warm-up pass, then the median of 5 passes.  'gpu ms'
 = HIP events around the pass on the current stream, 'wall ms' = perf_counter around the pass with a device synchronisation at both ends.
@@ -139,6 +148,46 @@ def apart_leg(fleet, n):
         f"conflict); longest walk {int(walked.max())} cells")
 
 
+ASIDE_PAIRS = 8
+
+
+def aside_pairs(cells, reached, rng, n_pairs=ASIDE_PAIRS, sep=F.SUBGOAL_SEPARATION):
+    """[(c - (sep, 0), c, c + (sep, 0))] for n_pairs cells c whose row is connected ground from c - sep to c + sep, the triples 3 sep apart:
+    a robot that stands on c holds one that walks the row from the first cell to the last with a reach below 2 sep"""
+    found = []
+    while len(found) < n_pairs:
+        c = cells[rng.integers(0, len(cells))]
+        if sep <= c[0] < reached.shape[0] - sep and reached[c[0] - sep:c[0] + sep + 1, c[1]].all() and \
+                all(max(abs(int(c[0]) - int(o[1][0])), abs(int(c[1]) - int(o[1][1]))) >= 3 * sep for o in found):
+            found.append((c - np.asarray([sep, 0]), c, c + np.asarray([sep, 0])))
+    return found
+
+
+def aside_leg(fleet, pairs, lo, hi, shape, n):
+    """epoch_targets with step_aside next to the separation alone, on the same fleet (the module's docstring)"""
+    def targets(step_aside, positions):
+        fleet.step_aside = step_aside
+        return fleet.epoch_targets(positions)
+    fleet.separation, fleet.aside_reach, fleet.aside_steps = F.SUBGOAL_SEPARATION, 48, 96
+    staged = fleet.positions.copy()                          # the pairs staged: the odd robot on its goal, the even one 23 cells before it
+    for i, (before, c, _) in enumerate(pairs):
+        staged[2 * i], staged[2 * i + 1] = R.cell_centres(before[None], lo, hi, shape)[0], R.cell_centres(c[None], lo, hi, shape)[0]
+    for what, positions, reach in (("as drawn, reach 180", fleet.positions, 180), ("pairs staged, reach 40", staged, 40)):
+        fleet.reach, fleet.aside_reach = reach, min(48, reach)
+        apart, aside = targets(False, positions), targets(True, positions)
+        bits = aside.aside[:, 0]
+        kept = (bits & (F.ASIDE_MOVED | F.ASIDE_RELEASED)) == 0
+        assert np.array_equal(aside.cells[kept], apart.cells[kept]) and np.array_equal(aside.summary[kept], apart.summary[kept])
+        assert np.array_equal(aside.extra, apart.extra) and np.array_equal(aside.origins, apart.origins)
+        legs = alternating([lambda: targets(False, positions), lambda: targets(True, positions)])
+        say(f"N = {n:3d} | {what} | one session, legs alternating | " + " | ".join(f"{name}: gpu {g:7.3f} ms, wall {w:7.3f} ms" for name, (g, w) in
+                                                                                  zip(("targets apart", "targets aside"), legs)))
+        say(f"N = {n:3d} | {what} | {apart.sweeps} sweeps of phase 1; held {int((bits & F.ASIDE_HELD != 0).sum())}, yield "
+            f"{int((bits & F.ASIDE_YIELDS != 0).sum())}, moved aside {int((bits & F.ASIDE_MOVED != 0).sum())} (longest side step "
+            f"{int(aside.aside[:, 1].max())} cells), released {int((bits & F.ASIDE_RELEASED != 0).sum())}")
+    fleet.separation, fleet.step_aside, fleet.reach = None, False, 180
+
+
 def persistent_leg(fleet, model, targets, n):
     """the default's per-epoch set-up next to the persistent one of the same fleet and epoch (the module's docstring)"""
     words = targets.words
@@ -185,8 +234,8 @@ def persistent_leg(fleet, model, targets, n):
 
 def main():
     import gpu_common
-    apart_only, persistent_only = "--apart" in sys.argv, "--persistent" in sys.argv
-    out = [a for a in sys.argv[1:] if a not in ("--apart", "--persistent")]
+    apart_only, persistent_only, aside_only = "--apart" in sys.argv, "--persistent" in sys.argv, "--aside" in sys.argv
+    out = [a for a in sys.argv[1:] if a not in ("--apart", "--persistent", "--aside")]
     say(f"# device: {torch.cuda.get_device_name(0)}; 1 warm-up pass, median of 5 (the field build: one pass)")
     occ = random_world(1)
     E.register_world_map("Timed", occ)
@@ -202,6 +251,9 @@ def main():
     model = gpu_common.hip_model(T)
     for n in (64, 256):
         pick = cells[rng.choice(len(cells), 2 * n, replace=False)]
+        pairs = aside_pairs(cells, reached, rng) if aside_only else []
+        for i, (_, c, beyond) in enumerate(pairs):
+            pick[n + 2 * i], pick[n + 2 * i + 1] = beyond, c
         starts, goals = R.cell_centres(pick[:n], lo, hi, occ.shape), R.cell_centres(pick[n:], lo, hi, occ.shape)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -226,6 +278,13 @@ def main():
             assert (targets.cells[r].tolist(), targets.origins[r].tolist(), targets.summary[r].tolist()) == \
                 (want[0][0].tolist(), want[1][0].tolist(), want[2][0].tolist()), f"robot {r}'s sub-goal is not the definition's"
         g_gpu, g_wall = timed(lambda: fleet.epoch_targets(fleet.positions))
+        if aside_only:
+            say(f"N = {n:3d} | fields ({n} goals, {4 * n * occ.size / 2 ** 20:.0f} MiB): wall {t_fields:9.1f} ms | longest way "
+                f"{int(fleet.start_distances.max())} cells | sub-goals: gpu {g_gpu:7.3f} ms, wall {g_wall:7.3f} ms")
+            aside_leg(fleet, pairs, lo, hi, occ.shape, n)
+            del fleet
+            torch.cuda.empty_cache()
+            continue
         if apart_only:
             say(f"N = {n:3d} | fields ({n} goals, {4 * n * occ.size / 2 ** 20:.0f} MiB): wall {t_fields:9.1f} ms | longest way "
                 f"{int(fleet.start_distances.max())} cells | sub-goals: gpu {g_gpu:7.3f} ms, wall {g_wall:7.3f} ms")
