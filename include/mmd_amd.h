@@ -849,7 +849,7 @@ int mmd_route_seeds(const float* grid_dev, int nx, int ny, const float lo[2], co
                     float* seeds_dev /* [n][max_tiles * 64][4] */, float* clear_min_dev /* [n] */, void* stream);
 
 /* World fleets: the next sub-goal and the window of n_queries robots, each read off the converged field of its goal, one lane per query
- * (mmd_amd/world_fleet.py::window_goal is the same definition on the host, where its two facts -- the walk's box lies inside the
+ * (mmd_amd/fleet_subgoals.py::window_goal is the same definition on the host, where its two facts -- the walk's box lies inside the
  * window, and a call covers at least min(d, max_steps, reach) steps -- are argued).  Query q starts at cell c0 = starts_dev[q] in field
  * field_dev[q], whose goal cell is g = goals_dev[field_dev[q]], all device data.  From cell c with d = dist[c], while d > 0, fewer than
  * max_steps steps are taken, and the chosen next cell n has max(|n.x - c0.x|, |n.y - c0.y|) <= reach: the candidates are the neighbours
@@ -872,7 +872,7 @@ int mmd_grid_window_goals(const int32_t* dist_dev, int nx, int ny, int n_fields,
                           int max_steps, int window, int32_t* cells_dev /* [n][2] */, int32_t* origins_dev /* [n][2] */,
                           int32_t* summary_dev /* [n][4] */, void* stream);
 
-/* mmd_grid_window_goals with the support cells of the walk's cell path (mmd_amd/world_fleet.py::window_goal_samples is the same
+/* mmd_grid_window_goals with the support cells of the walk's cell path (mmd_amd/fleet_subgoals.py::window_goal_samples is the same
  * definition on the host).  The walk, cells_dev, origins_dev and summary_dev are mmd_grid_window_goals', word for word.  The cell path
  * is c_0 = c0 .. c_steps = the last cell reached, and
  *   samples_dev[q][j] = c[(j * steps + 31) / 63], j = 0 .. 63 (integer division; mmd_grid_descend_samples' spacing for a visit of
@@ -889,7 +889,7 @@ int mmd_grid_window_goal_samples(const int32_t* dist_dev, int nx, int ny, int n_
                                  int32_t* summary_dev /* [n][4] */, int32_t* samples_dev /* [n][64][2] */, void* stream);
 
 /* The seed trajectories of n_robots robots of a fleet, in trajs_final's format, from what mmd_grid_window_goal_samples wrote
- * (mmd_amd/world_fleet.py::window_seed is the same definition on the host, bit for bit): mmd_route_seeds' seed of one visit whose tile
+ * (mmd_amd/fleet_subgoals.py::window_seed is the same definition on the host, bit for bit): mmd_route_seeds' seed of one visit whose tile
  * is the robot's own window, the cells [origins_dev[r], origins_dev[r] + window) per axis.  Every operation is one fp32 rounding, with no
  * fused multiply-add.  Robot r with status 0 (summary_dev[r][2]) has 64 points:
  *   p[j]   = lo + ((float)cell + 0.5f) * pitch per axis, pitch = |hi - lo| / (float)n: the centre of samples_dev[r][j].
@@ -915,7 +915,7 @@ int mmd_window_seeds(const float* grid_dev, int nx, int ny, const float lo[2], c
                      const float* goal_points_dev /* [n][2] */, int smooth_iters, float two_dt, float* seeds_dev /* [n][64][4] */,
                      float* clear_min_dev /* [n] */, void* stream);
 
-/* World fleets: the sub-goals of one epoch kept apart (mmd_amd/world_fleet.py::subgoals_apart is the definition on the host, and
+/* World fleets: the sub-goals of one epoch kept apart (mmd_amd/fleet_subgoals.py::subgoals_apart is the definition on the host, and
  * subgoals_apart_sweeps(s) the state after s sweeps; the argument stands in that module's docstring).  Query q TAKES PART iff
  * mmd_grid_window_goals' status for it is 0; its walk is that call's cell path c_q[0 .. walked_q], c_q[0] the start.  Two cells conflict
  * iff dx^2 + dy^2 < sep^2.  Robots are taken in index order, a lower index has priority: the blockers of robot r are the chosen cells of
@@ -957,7 +957,7 @@ int mmd_grid_window_goals_apart(const int32_t* dist_dev, int nx, int ny, int n_f
                                 int32_t* changed_dev /* [1] */, void* stream);
 
 /* World fleets: standing robots step aside for the robots they hold back, and those walk in the same epoch
- * (mmd_amd/world_fleet.py::subgoals_aside is the definition on the host; safety and containment are argued in that module's docstring;
+ * (mmd_amd/fleet_subgoals.py::subgoals_aside is the definition on the host; safety and containment are argued in that module's docstring;
  * csrc/window_aside.hip).  The call continues mmd_grid_window_goals_apart: apart_work_dev is that call's workspace for the same n_queries
  * and max_steps AT ITS FIXED POINT (changed == 0), which gives every query's walk c_q[0 .. walked_q] and k_q; it is only read.
  *   stands_j   j takes part and k_j == 0;      held_r   stands_r and walked_r >= 1
@@ -1036,7 +1036,7 @@ int mmd_fleet_epoch_frames(const int32_t* cells_dev /* [n][2] */, const int32_t*
                            float* offsets_dev /* [n][2] */, float* subgoals_dev /* [n][2] */, float* hard_first_dev /* [n][4] */,
                            float* hard_last_dev /* [n][4] */, float* lines_dev /* [n][64][2] */, void* stream);
 
-/* World fleets: the report of a whole run (mmd_amd/world_fleet.py::run_report is the definition on the host: the same integers and the
+/* World fleets: the report of a whole run (mmd_amd/fleet_report.py::run_report is the definition on the host: the same integers and the
  * same float32 bits, `length` apart).  paths_dev [n][L][2]: global points, column by column; grid_dev: any texture [nx][ny][4] over
  * lo .. hi; goals_dev [n][2].  A texel is mmd_sdf_grid_lookup's, a value channel 0 of the texel, the norm sqrt(fma(dy, dy, dx * dx)), and
  * every other operation is rounded once.  A point with a coordinate that is not finite is BAD and takes part in nothing else, nor does a

@@ -1,7 +1,7 @@
 // World fleets: the report of a whole run (include/mmd_amd.h: mmd_fleet_run_report).  The paths [n][L][2] of a run against the map they
 // were planned on -- every waypoint and n_interp interior points of every segment --, against each other at every column, and against
 // their goals, into ONE buffer that the host reads with one copy.  The definition is the numpy function run_report of
-// mmd_amd/world_fleet.py: the same integers and the same float32 bits (`length` apart: a float sum, whose order is fixed here and
+// mmd_amd/fleet_report.py: the same integers and the same float32 bits (`length` apart: a float sum, whose order is fixed here and
 // is not the definition's).  Two kernels: one wave per robot over its columns, and all pairs of robots over tiles of
 // FR_TILE robots x 64 columns staged in LDS.  Integer atomics only: every count is order-independent.
 #include <hip/hip_runtime.h>

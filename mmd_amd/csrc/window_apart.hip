@@ -1,5 +1,5 @@
 // World fleets: every epoch's sub-goals kept apart (include/mmd_amd.h: mmd_grid_window_goals_apart).  The definition is the numpy function
-// subgoals_apart of mmd_amd/world_fleet.py, and the state after s sweeps is subgoals_apart_sweeps(s); the fact a fleet rests on (starts
+// subgoals_apart of mmd_amd/fleet_subgoals.py, and the state after s sweeps is subgoals_apart_sweeps(s); the fact a fleet rests on (starts
 // pairwise `sep` apart give chosen cells pairwise `sep` apart) is argued there.  Every value here is an exact integer.  Plain loads and
 // vector stores; no LDS, no atomics, no scratch, and nothing inside a launch waits on another workgroup.
 #include <hip/hip_runtime.h>
@@ -11,6 +11,7 @@
 #include "common.h"
 #include "walk_args.h"
 #include "wave_dev.h"
+#include "window_apart_dev.h"
 #include "window_apart_work.h"
 #include "window_walk_dev.h"
 
@@ -66,7 +67,7 @@ __global__ __launch_bounds__(WG_THREADS) void window_apart_paths_kernel(const in
 // lane decides, and its lowest lane holds the largest k; k = 0 always serves, and what its lane found is `clear`.
 // Bounds: walked and every k_prev are clamped to [0, max_steps], so every cell index lies in its row whatever the workspace holds; the
 // chunk loop runs walked / 64 + 1 <= 64 times, the blocker loop ceil(n / 64) times, the broadcast loop at most 64 times.  The squares
-// are taken in 64 bits: cells of a taking-part walk lie in the grid, but the words are device data.
+// are taken in 64 bits (window_apart_dev.h: cells_conflict, with the cull cell_near and the clamps walked_of, k_in_row).
 __global__ __launch_bounds__(WG_THREADS) void window_apart_sweep_kernel(int n_queries, int reach, int max_steps, int sep, ApartWork w,
                                                                         const int* __restrict__ k_prev, int* __restrict__ k_next) {
   const int r = blockIdx.x, lane = threadIdx.x;
@@ -74,7 +75,7 @@ __global__ __launch_bounds__(WG_THREADS) void window_apart_sweep_kernel(int n_qu
   if (m.z != WALK_OK) return;                              // takes no part: one decision per wave
   const size_t stride = apart_row(max_steps);
   const int2* row = w.paths + (size_t)r * stride;
-  const int walked = min(max(m.x, 0), max_steps);
+  const int walked = walked_of(w, r, max_steps);
   const int2 s = row[0];
   const long long far = (long long)reach + sep, sep2 = (long long)sep * sep;
   int k_new = 0, clear = 0;
@@ -87,15 +88,14 @@ __global__ __launch_bounds__(WG_THREADS) void window_apart_sweep_kernel(int n_qu
       bool blocks = j < n_queries && j != r && w.meta[min(j, n_queries - 1)].z == WALK_OK;
       int2 b = make_int2(0, 0);
       if (blocks) {
-        b = w.paths[(size_t)j * stride + (j < r ? min(max(k_prev[j], 0), max_steps) : 0)];
-        blocks = max(llabs((long long)b.x - s.x), llabs((long long)b.y - s.y)) <= far;
+        b = w.paths[(size_t)j * stride + (j < r ? k_in_row(k_prev, j, max_steps) : 0)];
+        blocks = cell_near(b, s, far);
       }
       unsigned long long live = __ballot(blocks);
       while (live) {
         const int src = __ffsll((long long)live) - 1;
         live &= live - 1;
-        const long long dx = (long long)__shfl(b.x, src) - cand.x, dy = (long long)__shfl(b.y, src) - cand.y;
-        conflict |= dx * dx + dy * dy < sep2;
+        conflict |= cells_conflict(make_int2(__shfl(b.x, src), __shfl(b.y, src)), cand, sep2);
       }
     }
     const unsigned long long serves = __ballot(k == 0 || (k > 0 && !conflict));
@@ -108,15 +108,15 @@ __global__ __launch_bounds__(WG_THREADS) void window_apart_sweep_kernel(int n_qu
   }
   if (lane == 0) {
     k_next[r] = k_new;
-    w.flag[r] = (k_new != min(max(k_prev[r], 0), max_steps) ? WA_MOVED : 0) | (clear ? WA_CLEAR : 0);
+    w.flag[r] = (k_new != k_in_row(k_prev, r, max_steps) ? WA_MOVED : 0) | (clear ? WA_CLEAR : 0);
   }
 }
 
 // ---- 3. the outputs: one wave per robot, lane j = sample j ----
-// Every word of cells, origins, summary, extra and (if given) samples of the robot, from the state in k_cur; a robot that takes no part
-// gets window_goals' words, extra (steps, 0) and zero samples.  63 * k + 31 stays below 2^18.  The first workgroup also sums the moved
-// flags of all robots (wave_dev.h: wave_sum, a fixed order) into changed[0].  With to_first, the robot's k goes back to buffer 0, the
-// robot's own word: the next call finds the state there.
+// Every word of cells, origins, summary, extra (window_apart_dev.h: emitted_k and what follows it) and (if given) samples of the robot, from the state
+// in k_cur; a robot that takes no part gets window_goals' words, extra (steps, 0) and zero samples.  63 * k + 31 stays below 2^18.  The
+// first workgroup also sums the moved flags of all robots (wave_dev.h: wave_sum, a fixed order) into changed[0].  With to_first, the
+// robot's k goes back to buffer 0, the robot's own word: the next call finds the state there.
 __global__ __launch_bounds__(WG_THREADS) void window_apart_emit_kernel(int n_queries, int max_steps, ApartWork w, const int* __restrict__ k_cur,
                                                                        int to_first, int2* __restrict__ cells, int2* __restrict__ origins,
                                                                        int4* __restrict__ summary, int2* __restrict__ extra,
@@ -125,14 +125,13 @@ __global__ __launch_bounds__(WG_THREADS) void window_apart_emit_kernel(int n_que
   const int4 m = w.meta[r];
   const bool ok = m.z == WALK_OK;
   const int2* row = w.paths + (size_t)r * apart_row(max_steps);
-  const int walked = min(max(m.x, -1), max_steps);
-  const int k = ok ? min(max(k_cur[r], 0), max(walked, 0)) : walked;          // the index of the cell reported; -1: none
+  const int k = emitted_k(m, ok, k_cur, r, max_steps);
   if (samples) samples[(size_t)r * WG_THREADS + j] = ok ? row[(j * k + 31) / 63] : make_int2(0, 0);
   if (j == 0) {
-    cells[r] = k >= 0 ? row[k] : make_int2(0, 0);
+    cells[r] = emitted_cell(row, k);
     origins[r] = w.origin[r];
-    summary[r] = ok ? make_int4(k, m.y + (walked - k), WALK_OK, m.y + (walked - k) == 0) : make_int4(m.x, m.y, m.z, 0);
-    extra[r] = make_int2(m.x, ok && (w.flag[r] & WA_CLEAR) ? 1 : 0);
+    summary[r] = ok ? summary_at(m, k, max_steps) : make_int4(m.x, m.y, m.z, 0);
+    extra[r] = emitted_extra(w, r, m, ok);
     if (to_first) w.k[0][r] = k_cur[r];
   }
   if (r == 0) {

@@ -1,5 +1,5 @@
 // World fleets: standing robots step aside for the robots they hold back (include/mmd_amd.h: mmd_grid_window_goals_aside).  The definition
-// is the numpy function subgoals_aside of mmd_amd/world_fleet.py; safety and containment are argued there.  The call reads the workspace of
+// is the numpy function subgoals_aside of mmd_amd/fleet_subgoals.py; safety and containment are argued there.  The call reads the workspace of
 // mmd_grid_window_goals_apart at its fixed point (phase 1: meta, paths, origin, k[0], flag) and never writes it.  Every value here is an
 // exact integer.  Plain loads and vector stores, LDS in the side step only; no atomics, no scratch, and nothing inside a launch waits on
 // another workgroup.  Every index read from device memory is clamped before it is used.
@@ -12,6 +12,7 @@
 #include "common.h"
 #include "walk_args.h"
 #include "wave_dev.h"
+#include "window_apart_dev.h"
 #include "window_apart_work.h"
 #include "window_walk_dev.h"
 
@@ -56,20 +57,10 @@ static AsideWork aside_work(void* base, int n) {
   return a;
 }
 
-__device__ __forceinline__ bool cells_conflict(int2 a, int2 b, long long sep2) {
-  const long long dx = (long long)a.x - b.x, dy = (long long)a.y - b.y;
-  return dx * dx + dy * dy < sep2;
-}
-
-__device__ __forceinline__ bool cell_near(int2 b, int2 s, long long far) {
-  return max(llabs((long long)b.x - s.x), llabs((long long)b.y - s.y)) <= far;
-}
-
 __device__ __forceinline__ int2 side_cell(int word) { return make_int2((word >> 16) & 0xffff, word & 0xffff); }
 
-// phase 1's words of query q, clamped: does it take part, the cells its walk covered, its k
-__device__ __forceinline__ int walked_of(const ApartWork& w, int q, int max_steps) { return min(max(w.meta[q].x, 0), max_steps); }
-__device__ __forceinline__ int k1_of(const ApartWork& w, int q, int max_steps) { return min(max(w.k[0][q], 0), walked_of(w, q, max_steps)); }
+// phase 1's words of query q, clamped (window_apart_dev.h: walked_of, k_of): the cells its walk covered, its k, does it take part
+__device__ __forceinline__ int k1_of(const ApartWork& w, int q, int max_steps) { return k_of(w.k[0], w, q, max_steps); }
 __device__ __forceinline__ int base_roles(const ApartWork& w, int q, int max_steps, int n_fields) {
   if (n_fields < 1 || w.meta[q].z != WALK_OK) return 0;
   const bool stands = k1_of(w, q, max_steps) == 0;
@@ -336,7 +327,7 @@ __global__ __launch_bounds__(WG_THREADS) void window_aside_release_kernel(int n_
         int2 b = make_int2(0, 0);
         if (blocks) {
           const int2 sc = side_cur[i];
-          const int ki = i < r ? min(max(k_prev[i], 0), walked_of(w, i, max_steps)) : k1_of(w, i, max_steps);
+          const int ki = i < r ? k_of(k_prev, w, i, max_steps) : k1_of(w, i, max_steps);
           b = sc.x > 0 ? side_cell(sc.y) : w.paths[(size_t)i * stride + ki];
           blocks = cell_near(b, s, far);
         }
@@ -378,12 +369,10 @@ __global__ __launch_bounds__(WG_THREADS) void window_aside_emit_kernel(const int
     const int rr = a.roles[q];
     const bool ok = (rr & AS_TAKES) != 0;
     const int2* row = w.paths + (size_t)q * apart_row(max_steps);
-    const int walked = min(max(m.x, -1), max_steps);
     const int2 sc = side_cur[q];
     const int kk = k_cur[q];
-    const int k = ok ? min(max(kk, 0), max(walked, 0)) : walked;                             // the index of the cell reported; -1: none
     origins[q] = w.origin[q];
-    extra[q] = make_int2(m.x, ok && (w.flag[q] & WA_CLEAR) ? 1 : 0);
+    extra[q] = emitted_extra(w, q, m, ok);
     if (ok && n_fields >= 1 && (rr & AS_YIELDS) && sc.x > 0) {
       int2 cell = side_cell(sc.y);
       cell = make_int2(min(cell.x, nx - 1), min(cell.y, ny - 1));
@@ -392,8 +381,9 @@ __global__ __launch_bounds__(WG_THREADS) void window_aside_emit_kernel(const int
       summary[q] = make_int4(sc.x, d, WALK_OK, d == 0);
       aside[q] = make_int2((rr & (AS_HELD | AS_YIELDS)) | AS_MOVED, sc.x);
     } else {
-      cells[q] = k >= 0 ? row[k] : make_int2(0, 0);
-      summary[q] = ok ? make_int4(k, m.y + (walked - k), WALK_OK, m.y + (walked - k) == 0) : make_int4(m.x, m.y, m.z, 0);
+      const int k = emitted_k(m, ok, k_cur, q, max_steps);
+      cells[q] = emitted_cell(row, k);
+      summary[q] = ok ? summary_at(m, k, max_steps) : make_int4(m.x, m.y, m.z, 0);
       aside[q] = make_int2(ok ? (rr & (AS_HELD | AS_YIELDS)) | (a.released[q] ? AS_RELEASED : 0) : 0, 0);
     }
     if (to_first) {

@@ -1,6 +1,6 @@
 // World fleets: every robot's next sub-goal and window, read off its goal's distance field, alone or with the 64 support cells of the
 // walk's cell path (include/mmd_amd.h: mmd_grid_window_goals, mmd_grid_window_goal_samples).  The definitions are the numpy functions
-// window_goal and window_goal_samples of mmd_amd/world_fleet.py, where the two facts a fleet rests on (containment of the walk's box in the
+// window_goal and window_goal_samples of mmd_amd/fleet_subgoals.py, where the two facts a fleet rests on (containment of the walk's box in the
 // window, progress per call) are stated and argued; every value here is an exact integer.  Plain loads and vector stores; no LDS, no
 // atomics, no scratch.
 #include <hip/hip_runtime.h>

@@ -1,7 +1,7 @@
 // World fleets: the seed trajectory of an epoch.  From the 64 support cells of every robot's walk (window_goals.hip:
 // mmd_grid_window_goal_samples, or window_apart.hip's shortened walks) every robot's smoothed chain of support points with velocities
 // inside its own window, in trajs_final's format (include/mmd_amd.h: mmd_window_seeds).  The definition is the numpy function window_seed
-// of mmd_amd/world_fleet.py: the same float32 bits.  Plain loads and vector stores; no LDS, no atomics, no scratch.
+// of mmd_amd/fleet_subgoals.py: the same float32 bits.  Plain loads and vector stores; no LDS, no atomics, no scratch.
 #include <hip/hip_runtime.h>
 
 #include <cfloat>

@@ -1,5 +1,5 @@
 // What the walk kernels of a world fleet share (window_goals.hip, window_apart.hip): the step rule of
-// mmd_amd/world_fleet.py::window_goal on grid_route_dev.h's entry of a query and status codes, the walk, the window's origin.  Every
+// mmd_amd/fleet_subgoals.py::window_goal on grid_route_dev.h's entry of a query and status codes, the walk, the window's origin.  Every
 // value is an exact integer.  (The entry points' shared argument checks are host code: walk_args.h.)
 #pragma once
 #include <hip/hip_runtime.h>

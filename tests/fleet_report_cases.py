@@ -8,6 +8,7 @@ import numpy as np
 import fp32_forms
 from mmd_amd import environments as E
 from mmd_amd import world_fleet as F
+from mmd_amd.fleet_report import _order_key
 
 f32 = np.float32
 CELL = 0.0625
@@ -157,8 +158,8 @@ def loop_report(paths, tex, lo, hi, goals, margin, rr_margin, n_interp, goal_tol
             if seg_hit and out["first_hit"][r] < 0:
                 out["first_hit"][r] = t
         if checked:
-            keys = F._order_key(np.asarray(checked, f32).view(np.int32))
-            out["clear_min"][r] = F._order_key(np.asarray([keys.min()], np.int32)).view(f32)[0]
+            keys = _order_key(np.asarray(checked, f32).view(np.int32))
+            out["clear_min"][r] = _order_key(np.asarray([keys.min()], np.int32)).view(f32)[0]
         out["max_step"][r] = out["lengths"][r].max()
         c = length
         while c > 0 and finite(paths[r, c - 1]) and norm(paths[r, c - 1], goals[r]) <= goal_tol:

@@ -16,6 +16,7 @@ import world_fleet_apart_model as A                              # noqa: E402
 import world_fleet_aside_model as S                              # noqa: E402
 import world_fleet_model as M                                    # noqa: E402
 from mmd_amd import _lib, environments as E, world_fleet as F    # noqa: E402
+from mmd_amd.fleet_subgoals import _walk                         # noqa: E402
 from mmd_amd.multi_agent import RR_MARGIN                        # noqa: E402
 from mmd_amd.world_routes import ROUTE_OK                        # noqa: E402
 
@@ -161,7 +162,7 @@ def test_kernel_is_the_definition(name):
     elif name.startswith("walk of") or name == "aside_reach 63":
         walked = int(want[3][0, 0])
         assert walked > 256 and want[4][0].tolist() == [S.HELD | S.RELEASED, 0] and want[4][1].tolist() == [S.YIELDS | S.MOVED, 3]
-        box = np.abs(np.asarray(F._walk(dist[0], tuple(starts[0]), tuple(goals[0]), int(dist[0][tuple(starts[0])]), args[0], args[1])[0])
+        box = np.abs(np.asarray(_walk(dist[0], tuple(starts[0]), tuple(goals[0]), int(dist[0][tuple(starts[0])]), args[0], args[1])[0])
                      - starts[1]).max(1) <= args[3] + args[2]
         assert box[:256].any() and box[256:].any()           # class (d) survives the cull in more than one chunk of 256 walk cells
     elif name == "aside_reach 1":

@@ -6,6 +6,7 @@ import numpy as np
 import world_fleet_apart_model as A
 import world_fleet_model as M
 from mmd_amd import world_fleet as F
+from mmd_amd.fleet_subgoals import _walk, _walks
 from mmd_amd.world_routes import ROUTE_OK
 
 SEP = A.SEP
@@ -38,7 +39,7 @@ def roles_by_hand(dist, starts, which, goals, args):
     them"""
     reach, max_steps, sep, _, _, window = args
     k, walked = F.subgoals_apart(dist, starts, which, goals, reach, max_steps, sep, window)[2:4]
-    _, paths = F._walks("window_goals", dist, starts, which, goals, reach, max_steps, window)
+    _, paths = _walks("window_goals", dist, starts, which, goals, reach, max_steps, window)
     n = len(starts)
     stands = [paths[q] is not None and k[q, 0] == 0 for q in range(n)]
     held = [stands[q] and walked[q, 0] >= 1 for q in range(n)]
@@ -174,7 +175,7 @@ def long_walk(shape, reach, aside_reach, window, pitch=6, height=31):
     routable[:shape[0] - 3, height] = False
     start, goal = (3, 3), (shape[0] - 3, 3)
     real = M.fields(routable, [goal])
-    path, status = F._walk(real[0], start, goal, int(real[0][start]), reach, 4000)
+    path, status = _walk(real[0], start, goal, int(real[0][start]), reach, 4000)
     assert status == ROUTE_OK
     dist = np.concatenate([real, np.zeros((1,) + tuple(shape), np.int32)])
     starts = [start] + path[3::3]
