@@ -280,7 +280,10 @@ size_t mmd_sampler_workspace_bytes(mmd_unet_t unet, int n_traj);
 /* One ddpm_sample_fn call + the apply_hard_conditioning that follows it in p_sample_loop
  * (diffusion_model_base.py:199-203): x <- step(x) for loop index i (i < 0 means t = 0, no noise).
  * guide may be NULL (no guidance).  noise_dev [n_traj,H,4] is the injected randn_like draw, or NULL to draw it
- * in-kernel from Philox4x32-10 keyed by (seed, draw_index). */
+ * in-kernel from Philox4x32-10 keyed by (seed, draw_index).
+ * Non-finite values: the x0 clamp is x_recon.clamp_(-1., 1.) (diffusion_model_base.py:155) -- a NaN x0 (a NaN network output, or
+ * 0 * inf) stays NaN, +-inf goes to the bound; a trajectory whose forward is NaN stays NaN in every row that is not pinned, in this
+ * call and in every sampling loop (the step in the UNet launch's tail included), and is for the pick to discard. */
 int mmd_ddpm_step(mmd_unet_t unet, const mmd_sampler_desc* s, const mmd_guide_desc* guide, float* x_dev,
                   const float* hard_dev, int n_robots, int samples_per_robot, int i, const float* noise_dev,
                   uint64_t seed, uint32_t draw_index, void* workspace_dev, size_t workspace_bytes, void* stream);
@@ -315,7 +318,8 @@ int mmd_q_sample(float* x_dev, const float* x_start_dev, const float* noise_dev,
                  int n_traj, void* stream);
 
 /* apply_cross_conditioning for one (m1, m2) tile pair (sample_functions.py:17-31): row ind1 of x1 := min(row ind2
- * of x2 + rel, boundary); then row ind2 of x2 := max(row ind1 of x1 - rel, -boundary); rel / boundary are [4] host. */
+ * of x2 + rel, boundary); then row ind2 of x2 := max(row ind1 of x1 - rel, -boundary); rel / boundary are [4] host.
+ * min / max are torch.min / torch.max: a NaN in the stitch row is NaN in both tiles afterwards, never the boundary. */
 int mmd_cross_condition(float* x1_dev, float* x2_dev, int ind1, int ind2, const float* rel, const float* boundary,
                         int n_traj, void* stream);
 

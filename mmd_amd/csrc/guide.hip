@@ -749,12 +749,13 @@ __global__ void cross_condition_kernel(float4* __restrict__ x1, float4* __restri
   }
   const float4 v2 = x2[(size_t)b * H + ind2];
   float4 v1;
-  v1.x = fminf(v2.x + rel.x, bnd.x); v1.y = fminf(v2.y + rel.y, bnd.y);
-  v1.z = fminf(v2.z + rel.z, bnd.z); v1.w = fminf(v2.w + rel.w, bnd.w);
+  // (torch.min / torch.max: a NaN in the stitch row stays NaN in both tiles -- min_nan / max_nan, clip_dev.h)
+  v1.x = min_nan(v2.x + rel.x, bnd.x); v1.y = min_nan(v2.y + rel.y, bnd.y);
+  v1.z = min_nan(v2.z + rel.z, bnd.z); v1.w = min_nan(v2.w + rel.w, bnd.w);
   x1[(size_t)b * H + ind1] = v1;
   float4 w;
-  w.x = fmaxf(v1.x - rel.x, -bnd.x); w.y = fmaxf(v1.y - rel.y, -bnd.y);
-  w.z = fmaxf(v1.z - rel.z, -bnd.z); w.w = fmaxf(v1.w - rel.w, -bnd.w);
+  w.x = max_nan(v1.x - rel.x, -bnd.x); w.y = max_nan(v1.y - rel.y, -bnd.y);
+  w.z = max_nan(v1.z - rel.z, -bnd.z); w.w = max_nan(v1.w - rel.w, -bnd.w);
   x2[(size_t)b * H + ind2] = w;
   if (c1) c1[(size_t)b * H + ind1] = v1;
   if (c2) c2[(size_t)b * H + ind2] = w;

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/mmd_amd.h"
+#include "clip_dev.h"
 #include "common.h"
 
 namespace mmd {
@@ -112,9 +113,10 @@ __device__ __forceinline__ float4 traj_normal4(unsigned long long seed, const un
 }
 
 // p_mean_variance (diffusion_model_base.py:148-160): x0 = a x - b eps; clamp; mean = c1 x0 + c2 x.  Explicit fmas: the step
-// kernel and the UNet kernel's fused unguided step (unet_kernel.h) must round identically.
+// kernel and the UNet kernel's fused unguided step (unet_kernel.h) must round identically.  The clamp is x_recon.clamp_(-1., 1.)
+// (diffusion_model_base.py:155): a NaN x0 stays NaN (clip_dev.h), so a trajectory whose network output is NaN stays NaN to the pick.
 __device__ __forceinline__ float ddpm_mean1(float x, float e, float a, float b, float c1, float c2) {
-  const float x0 = fminf(fmaxf(__builtin_fmaf(a, x, -(b * e)), -1.f), 1.f);
+  const float x0 = clip_unit(__builtin_fmaf(a, x, -(b * e)));
   return __builtin_fmaf(c1, x0, c2 * x);
 }
 __device__ __forceinline__ float4 ddpm_posterior_mean(float4 v, float4 e, float a, float b, float c1, float c2) {

@@ -11,6 +11,7 @@
 // at every decision edge and pick size (tests/test_gpu_round_pick_edges.py).
 #include "postprocess_dev.h"      // sets fp contract(off)
 #include "collision_dev.h"        // torch_norm2
+#include "clip_dev.h"             // clip_unit: torch.clip(v, -1, 1), a NaN passes through
 #include "round_pick.h"
 
 namespace mmd {
@@ -30,9 +31,6 @@ struct PickArgs {
   int* idx;                     // [n_robots]
   int* n_free;                  // [n_robots]
 };
-
-// torch.clip(v, -1, 1): a NaN passes through
-__device__ __forceinline__ float clip_unit(float v) { return v != v ? v : fminf(fmaxf(v, -1.f), 1.f); }
 
 // MultiRobotSampler.unnormalize of one state
 __device__ __forceinline__ float4 unnorm_clipped(const float4& v, const UnnormArgs& un) {

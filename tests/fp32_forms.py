@@ -10,16 +10,19 @@ MARGIN = np.float32(2.1 * 0.05)          # RobotPlanarDisk.check_rr_collisions: 
 
 
 def fma_f32(a, b, c):
-    """fp32 fma(a, b, c) = round_fp32(a * b + c), a single rounding, elementwise over float32 arrays."""
-    a, b, c = (np.asarray(v, np.float32).astype(np.float64) for v in (a, b, c))
-    p = a * b                                              # exact: 48 significant bits
-    s = p + c
-    bb = s - p
-    e = (p - (s - bb)) + (c - bb)                          # TwoSum: p + c = s + e exactly
-    bits = s.view(np.int64)
-    even = (bits & 1) == 0
-    odd = np.where((e != 0) & even, np.nextafter(s, s + e), s)       # round to odd
-    return odd.astype(np.float32)
+    """fp32 fma(a, b, c) = round_fp32(a * b + c), a single rounding, elementwise over float32 arrays.  The odd neighbour is taken on the
+    side of the error term's SIGN: |e| may lie below half an ulp of s (an addend of 1 next to a product of 1e30), where s + e rounds back to
+    s and a tie of the product would be broken to even instead of by the addend.  Where a * b + c is not finite the result is that inf or
+    NaN (the error-free sum is not defined there)."""
+    with np.errstate(all="ignore"):
+        a, b, c = (np.asarray(v, np.float32).astype(np.float64) for v in (a, b, c))
+        p = a * b                                              # exact: 48 significant bits
+        s = p + c
+        bb = s - p
+        e = (p - (s - bb)) + (c - bb)                          # TwoSum: p + c = s + e exactly
+        even = (s.view(np.int64) & 1) == 0
+        odd = np.where((e != 0) & even & np.isfinite(s), np.nextafter(s, np.where(e > 0, np.inf, -np.inf)), s)       # round to odd
+        return odd.astype(np.float32)
 
 
 def torch_norm2(dx, dy):
