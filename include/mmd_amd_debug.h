@@ -61,6 +61,30 @@ size_t mmd_unet_weight_bytes(mmd_unet_t unet);
 /* The handle's mmd_unet_options.precision (MMD_UNET_PRECISION_*); -1 for NULL. */
 int mmd_unet_precision(mmd_unet_t unet);
 
+/* The fused kernel's packed block as the HOST builds it (no GPU call; the fused configuration unet_input_dim 32, 3 levels only), and
+ * the directory of its parameter-record tables.  A table holds one record per channel unit of `channels_per_record` adjacent output
+ * channels; a record is `n_fields` fields, each field's channels side by side, zero padded to `record_floats` (a multiple of 4; every
+ * table starts 16-byte aligned): float f of channel c = blob[offset + (c / cpr) * record_floats + f * cpr + c % cpr].  Fields by kind:
+ *   MMD_UNET_REC_EPI       conv bias, GroupNorm weight, GroupNorm bias, inverse weight scale of the conv's f16x2 pack (conv B: / the
+ *                          static scale of its input)                                      "<block>.a" / "<block>.b" / "final"
+ *   MMD_UNET_REC_EPI_RES   the same four + the 1x1 residual conv's bias and the inverse scale of its pack   "<block>.a", first block of a stage
+ *   MMD_UNET_REC_TAIL_DOWN Downsample1d: bias, inverse scale of its pack                   "down0", "down1"
+ *   MMD_UNET_REC_TAIL_UP   ConvTranspose1d: bias, inverse scales of the even / odd parity pack   "up0", "up1"
+ *   MMD_UNET_REC_OUT       final 1x1 conv (4 channels): bias, inverse scale / static input scale   "final.out"
+ * <block> = d00 d01 d10 d11 d20 d21 u00 u01 u10 u11 mid1 mid2 (state_dict order).
+ * blob_out (may be NULL) receives up to blob_cap floats, tables (may be NULL) up to tables_cap entries; *blob_floats / *n_tables
+ * report the full counts.  mmd_unet_weight_bytes of a handle created from the same tensors = 4 * *blob_floats. */
+enum { MMD_UNET_REC_EPI = 0, MMD_UNET_REC_EPI_RES = 1, MMD_UNET_REC_TAIL_DOWN = 2, MMD_UNET_REC_TAIL_UP = 3, MMD_UNET_REC_OUT = 4 };
+typedef struct mmd_unet_record_table {
+  char name[16];
+  uint64_t offset;               /* floats from the start of the block */
+  int32_t kind, channels;        /* MMD_UNET_REC_*; output channels of the conv */
+  int32_t channels_per_record, n_fields, record_floats, reserved;
+} mmd_unet_record_table;
+int mmd_debug_unet_pack(int unet_input_dim, int n_levels, int n_diffusion_steps, const float* const* tensors, const int64_t* numels,
+                        int n_tensors, float* blob_out, size_t blob_cap, size_t* blob_floats, mmd_unet_record_table* tables,
+                        int tables_cap, int* n_tables);
+
 /* Decision trace of ONE guided ddpm_sample_fn step (sample_functions.py:40-107): mmd_ddpm_step on the one-wave step kernel with
  * the dump compiled in -- the same arithmetic, bit for bit, as every production launch shape -- which additionally writes
  *   mu_dev          [n_traj][64][4]  (optional) the posterior mean as the first guide iteration sees it (hard rows are pinned after an iteration, not before the first)

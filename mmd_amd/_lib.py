@@ -250,6 +250,8 @@ _DEBUG_SIGNATURES = {
                                             C.c_void_p, C.c_void_p]),
     "mmd_unet_weight_bytes": (C.c_size_t, [C.c_void_p]),
     "mmd_unet_precision": (C.c_int, [C.c_void_p]),
+    "mmd_debug_unet_pack": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_int, C.c_void_p,
+                                      C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
     "mmd_debug_ddpm_step_trace": (C.c_int, [C.c_void_p, C.POINTER(SamplerDesc), C.POINTER(GuideDesc), C.c_void_p, C.c_void_p,
                                             C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_size_t,
                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -3,8 +3,10 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
+#include <cstdio>
 #include <cstring>
 #include <memory>
+#include <string>
 #include <vector>
 
 #include "../../include/mmd_amd.h"
@@ -132,10 +134,10 @@ static float static_act_scale(const float* gamma, const float* beta, const std::
 }
 
 
-struct ConvW { size_t bias, gamma, beta, wbf, isc; };   // wbf / isc: f16x2 pack and its inverse channel scales
-struct RtbW { ConvW a, b; size_t res_bias, res_isc, res_bf, res_c1_bf; int tb_off; size_t a_c1_bf; float act_a; };
-// a stage's tail conv: Downsample1d = one f16x2 pack and its inverse scales, ConvTranspose1d = the two parity packs (wbf[1] = 0: none)
-struct TailW { size_t bias, wbf[2], isc[2]; };
+struct ConvW { size_t wbf, rec; };   // f16x2 pack; the conv's epilogue records (push_records)
+struct RtbW { ConvW a, b; size_t res_bf, res_c1_bf; int tb_off; size_t a_c1_bf; float act_a; };
+// a stage's tail conv: Downsample1d = one f16x2 pack, ConvTranspose1d = the two parity packs (wbf[1] = 0: none); its records
+struct TailW { size_t rec, wbf[2]; };
 
 // what the packer leaves behind: offsets (in floats) into the blob, and the static activation scales
 struct UnetPack {
@@ -143,9 +145,11 @@ struct UnetPack {
   RtbW rtb[12];              // state_dict order: d00 d01 d10 d11 d20 d21 u00 u01 u10 u11 mid1 mid2
   TailW down[2], up[2];
   ConvW fin;
-  size_t fin_w1 = 0, fin_b1 = 0, fin_is1 = 0;    // final 1x1 conv: f16x2 pack (N padded to 16), bias, inverse scales / fin_act
+  size_t fin_w1 = 0, fin_rec1 = 0;               // final 1x1 conv: f16x2 pack (N padded to 16), records {bias, inverse scale / fin_act}
   float fin_act = 1.f;                           // static scale of the final block's activations
   size_t raw_time[4], raw_cw[12], raw_cb[12];    // the time MLP's and the cond_mlps' fp32 parameters (time_table_kernel)
+  mmd_unet_record_table tables[32];              // directory of the record tables (mmd_debug_unet_pack)
+  int n_tables = 0;
 };
 
 }  // namespace mmd
@@ -176,6 +180,33 @@ static size_t push(std::vector<float>& blob, const float* p, int64_t n) {
   while (blob.size() % 4) blob.push_back(0.f);
   return off;
 }
+// 1 / (scale * in_scale) per channel (powers of two: exact)
+static std::vector<float> inverse_scales(const std::vector<float>& sc, float in_scale = 1.f) {
+  std::vector<float> r(sc.size());
+  for (size_t i = 0; i < sc.size(); ++i) r[i] = 1.f / (sc[i] * in_scale);
+  return r;
+}
+// One table of parameter records as the kernels read them (unet_kernel.h, rec_load): per unit of `cpr` adjacent channels the fields in
+// order, each field's channels side by side, zero padded to whole float4; the table starts 16-byte aligned.  fields[f]: [channels]
+// floats OUTSIDE the blob (it grows here).  The table is entered in the pack's directory under `name`.
+static size_t push_records(std::vector<float>& blob, UnetPack& p, const std::string& name, int kind, int channels, int cpr,
+                           const std::vector<const float*>& fields) {
+  while (blob.size() % 4) blob.push_back(0.f);
+  const size_t off = blob.size();
+  const int nf = (int)fields.size(), rf = (nf * cpr + 3) / 4 * 4;
+  blob.resize(off + (size_t)(channels / cpr) * rf, 0.f);
+  for (int c = 0; c < channels; ++c)
+    for (int f = 0; f < nf; ++f) blob[off + (size_t)(c / cpr) * rf + f * cpr + c % cpr] = fields[f][c];
+  if (p.n_tables < (int)(sizeof(p.tables) / sizeof(p.tables[0]))) {
+    mmd_unet_record_table& t = p.tables[p.n_tables];
+    t = mmd_unet_record_table{};
+    snprintf(t.name, sizeof(t.name), "%s", name.c_str());
+    t.offset = off; t.kind = kind; t.channels = channels;
+    t.channels_per_record = cpr; t.n_fields = nf; t.record_floats = rf;
+  }
+  ++p.n_tables;
+  return off;
+}
 
 // The pack each of the twelve residual blocks gets (state_dict order).  pairs: interleaved column pairs, where a wave owns two
 // n-tiles (every stage body but ups.0's).  Conv A's form: downs.0's first conv (4 -> 32) as one im2col chunk; the
@@ -191,6 +222,7 @@ static const BlockPack kBlockPack[12] = {
 // f16x2 pack its stage body reads -- direct packs (pack_rd), the 1x1 residual conv of a stage's first RTB as a one-tap pack of its own.
 static void pack_unet(const Spec& s, const float* const* tensors, int T, std::vector<float>& blob, UnetPack& p) {
   const std::vector<int> taps5 = {0, 1, 2, 3, 4}, taps3 = {0, 1, 2}, taps1 = {0};
+  p.n_tables = 0;
   for (int i = 0; i < 4; ++i) p.raw_time[i] = push(blob, tensors[s.t_time[i]], s.numel[s.t_time[i]]);
   int tb_off = 0;
   const std::vector<std::vector<float>> tbmax = time_bias_absmax(tensors, s, T);
@@ -200,15 +232,18 @@ static void pack_unet(const Spec& s, const float* const* tensors, int T, std::ve
     RtbW& W = p.rtb[r];
     W = RtbW{};
     while (blob.size() % 4) blob.push_back(0.f);
+    const int cpr = B.pairs ? 2 : 1;   // channels per record: the lane's adjacent pair, or ups.0's one channel per lane
     {                         // conv A: direct f16x2 (rd_taps) with a dynamic input scale
-      const std::vector<float> sc = rd_col_scales(tensors[R.t_w0], R.cout, R.cin, 5, taps5, false);
-      W.a.isc = push_inverse(blob, sc);
+      const std::vector<float> sc = rd_col_scales(tensors[R.t_w0], R.cout, R.cin, 5, taps5, false), isc = inverse_scales(sc);
       if (B.a == A_IDENT) {
         W.a.wbf = pack_rd(blob, tensors[R.t_w0], R.cout, R.cin, 0, R.cin, 5, taps5, false, B.pairs, sc);
+        W.a.rec = push_records(blob, p, std::string(B.name) + ".a", MMD_UNET_REC_EPI, R.cout, cpr,
+                               {tensors[R.t_b0], tensors[R.t_g0], tensors[R.t_be0], isc.data()});
       } else {                // first RTB of a stage: its 1x1 residual conv [cout][cin] rides on conv A's centre tap
         const float* wres = tensors[R.t_rw];
-        const std::vector<float> scr = rd_col_scales(wres, R.cout, R.cin, 1, taps1, false);
-        W.res_isc = push_inverse(blob, scr);
+        const std::vector<float> scr = rd_col_scales(wres, R.cout, R.cin, 1, taps1, false), iscr = inverse_scales(scr);
+        W.a.rec = push_records(blob, p, std::string(B.name) + ".a", MMD_UNET_REC_EPI_RES, R.cout, cpr,
+                               {tensors[R.t_b0], tensors[R.t_g0], tensors[R.t_be0], isc.data(), tensors[R.t_rb], iscr.data()});
         if (B.a == A_IM2COL4) {
           W.a.wbf = pack_im2col4(blob, tensors[R.t_w0], R.cout, false, sc);
           W.res_bf = pack_im2col4(blob, wres, R.cout, true, scr);
@@ -223,62 +258,51 @@ static void pack_unet(const Spec& s, const float* const* tensors, int T, std::ve
         }
       }
     }
-    W.a.bias = push(blob, tensors[R.t_b0], R.cout);
-    W.a.gamma = push(blob, tensors[R.t_g0], R.cout);
-    W.a.beta = push(blob, tensors[R.t_be0], R.cout);
     {                         // conv B: direct f16x2, its input scaled by the static act_a
       W.act_a = static_act_scale(tensors[R.t_g0], tensors[R.t_be0], tbmax[r], R.cout);
-      const std::vector<float> sc = rd_col_scales(tensors[R.t_w1], R.cout, R.cout, 5, taps5, false);
-      W.b.isc = push_inverse(blob, sc, W.act_a);
+      const std::vector<float> sc = rd_col_scales(tensors[R.t_w1], R.cout, R.cout, 5, taps5, false), isc = inverse_scales(sc, W.act_a);
       W.b.wbf = pack_rd(blob, tensors[R.t_w1], R.cout, R.cout, 0, R.cout, 5, taps5, false, B.pairs, sc);
+      W.b.rec = push_records(blob, p, std::string(B.name) + ".b", MMD_UNET_REC_EPI, R.cout, cpr,
+                             {tensors[R.t_b1], tensors[R.t_g1], tensors[R.t_be1], isc.data()});
     }
-    W.b.bias = push(blob, tensors[R.t_b1], R.cout);
-    W.b.gamma = push(blob, tensors[R.t_g1], R.cout);
-    W.b.beta = push(blob, tensors[R.t_be1], R.cout);
     p.raw_cw[r] = push(blob, tensors[R.t_cw], (int64_t)R.cout * 32);
     p.raw_cb[r] = push(blob, tensors[R.t_cb], R.cout);
-    W.res_bias = R.res ? push(blob, tensors[R.t_rb], R.cout) : 0;
     W.tb_off = tb_off;
     tb_off += R.cout;
   }
   p.tb_total = tb_off;
   for (int i = 0; i < 2; ++i) {
     const int c = s.dims[i + 1];
-    p.down[i].bias = push(blob, tensors[s.t_down[i][1]], c);
     {                         // Downsample1d as a direct f16x2 conv (taps 0..2, interleaved column pairs) read at stride 2
-      const std::vector<float> sct = rd_col_scales(tensors[s.t_down[i][0]], c, c, 3, taps3, false);
-      p.down[i].isc[0] = push_inverse(blob, sct);
+      const std::vector<float> sct = rd_col_scales(tensors[s.t_down[i][0]], c, c, 3, taps3, false), isct = inverse_scales(sct);
       p.down[i].wbf[0] = pack_rd(blob, tensors[s.t_down[i][0]], c, c, 0, c, 3, taps3, false, true, sct);
+      p.down[i].rec = push_records(blob, p, "down" + std::to_string(i), MMD_UNET_REC_TAIL_DOWN, c, 2, {tensors[s.t_down[i][1]], isct.data()});
     }
     const int cu = s.dims[2 - i];
     // ConvTranspose1d(k=4, s=2, p=1): out[2m] = in[m-1] W3 + in[m] W1 ; out[2m+1] = in[m] W2 + in[m+1] W0, as two direct f16x2
-    // parity passes (ups.1: interleaved column pairs)
-    p.up[i].bias = push(blob, tensors[s.t_up[i][1]], cu);
+    // parity passes (ups.1: interleaved column pairs; ups.0: one channel per lane and record)
     {
       const std::vector<int> ke = {3, 1}, ko = {2, 0};
-      const std::vector<float> sce = rd_col_scales(tensors[s.t_up[i][0]], cu, cu, 4, ke, true);
-      const std::vector<float> sco = rd_col_scales(tensors[s.t_up[i][0]], cu, cu, 4, ko, true);
-      p.up[i].isc[0] = push_inverse(blob, sce);
-      p.up[i].isc[1] = push_inverse(blob, sco);
+      const std::vector<float> sce = rd_col_scales(tensors[s.t_up[i][0]], cu, cu, 4, ke, true), isce = inverse_scales(sce);
+      const std::vector<float> sco = rd_col_scales(tensors[s.t_up[i][0]], cu, cu, 4, ko, true), isco = inverse_scales(sco);
       p.up[i].wbf[0] = pack_rd(blob, tensors[s.t_up[i][0]], cu, cu, 0, cu, 4, ke, true, i == 1, sce);
       p.up[i].wbf[1] = pack_rd(blob, tensors[s.t_up[i][0]], cu, cu, 0, cu, 4, ko, true, i == 1, sco);
+      p.up[i].rec = push_records(blob, p, "up" + std::to_string(i), MMD_UNET_REC_TAIL_UP, cu, i == 1 ? 2 : 1,
+                                 {tensors[s.t_up[i][1]], isce.data(), isco.data()});
     }
   }
   {                           // final block (in ups.1's stage body): k5 conv with a dynamic input scale, 1x1 conv behind a static one
-    const std::vector<float> sc = rd_col_scales(tensors[s.t_final[0]], 32, 32, 5, taps5, false);
-    p.fin.isc = push_inverse(blob, sc);
+    const std::vector<float> sc = rd_col_scales(tensors[s.t_final[0]], 32, 32, 5, taps5, false), isc = inverse_scales(sc);
     p.fin.wbf = pack_rd(blob, tensors[s.t_final[0]], 32, 32, 0, 32, 5, taps5, false, true, sc);
-    p.fin.bias = push(blob, tensors[s.t_final[1]], 32);
-    p.fin.gamma = push(blob, tensors[s.t_final[2]], 32);
-    p.fin.beta = push(blob, tensors[s.t_final[3]], 32);
+    p.fin.rec = push_records(blob, p, "final", MMD_UNET_REC_EPI, 32, 2, {tensors[s.t_final[1]], tensors[s.t_final[2]], tensors[s.t_final[3]], isc.data()});
     p.fin_act = static_act_scale(tensors[s.t_final[2]], tensors[s.t_final[3]], std::vector<float>(32, 0.f), 32);
     std::vector<float> sc1 = rd_col_scales(tensors[s.t_final[4]], 4, 32, 1, taps1, false);
-    p.fin_is1 = push_inverse(blob, sc1, p.fin_act);
+    const std::vector<float> isc1 = inverse_scales(sc1, p.fin_act);
     std::vector<float> w1(16 * 32, 0.f);      // N padded to one n-tile
     memcpy(w1.data(), tensors[s.t_final[4]], sizeof(float) * 4 * 32);
     sc1.resize(16, 1.f);
     p.fin_w1 = pack_rd(blob, w1.data(), 16, 32, 0, 32, 1, taps1, false, false, sc1);
-    p.fin_b1 = push(blob, tensors[s.t_final[5]], 4);
+    p.fin_rec1 = push_records(blob, p, "final.out", MMD_UNET_REC_OUT, 4, 1, {tensors[s.t_final[5]], isc1.data()});
   }
 }
 
@@ -300,13 +324,10 @@ static int fill_time_table(const mmd_unet_s* u, const Spec& s, hipStream_t st) {
 
 static RtbPtrs rtb_ptrs(const mmd_unet_s* u, const RtbW& w, int t) {
   RtbPtrs p{};
-  p.ba = u->blob + w.a.bias; p.ga = u->blob + w.a.gamma; p.bea = u->blob + w.a.beta;
+  p.ra = u->blob + w.a.rec; p.rb = u->blob + w.b.rec;
   p.tb = u->ttable + (size_t)t * u->w.tb_total + w.tb_off;
-  p.bb = u->blob + w.b.bias; p.gb = u->blob + w.b.gamma; p.beb = u->blob + w.b.beta;
   p.wa_bf = w.a.wbf ? reinterpret_cast<const uint4*>(u->blob + w.a.wbf) : nullptr;
   p.wb_bf = w.b.wbf ? reinterpret_cast<const uint4*>(u->blob + w.b.wbf) : nullptr;
-  p.isa = w.a.wbf ? u->blob + w.a.isc : nullptr;
-  p.isb = w.b.wbf ? u->blob + w.b.isc : nullptr;
   p.act_a = w.act_a;
   return p;
 }
@@ -318,19 +339,13 @@ static ChainArgs args_chain(const mmd_unet_s* u, const int* rtb, int n_ident, co
   const RtbW& w0 = u->w.rtb[rtb[0]];
   a.r0 = rtb_ptrs(u, w0, t);
   a.wa0_c1_bf = w0.a_c1_bf ? reinterpret_cast<const uint4*>(u->blob + w0.a_c1_bf) : nullptr;
-  a.br = u->blob + w0.res_bias;
-  a.isr = w0.res_isc ? u->blob + w0.res_isc : nullptr;
   a.wres_bf = w0.res_bf ? reinterpret_cast<const uint4*>(u->blob + w0.res_bf) : nullptr;
   a.wres_c1_bf = w0.res_c1_bf ? reinterpret_cast<const uint4*>(u->blob + w0.res_c1_bf) : nullptr;
   for (int k = 0; k < n_ident; ++k) a.ri[k] = rtb_ptrs(u, u->w.rtb[rtb[1 + k]], t);
   if (tail) {
-    a.bt = u->blob + tail->bias;
+    a.rt = u->blob + tail->rec;
     a.wt_bf0 = reinterpret_cast<const uint4*>(u->blob + tail->wbf[0]);
-    a.ist0 = u->blob + tail->isc[0];
-    if (tail->wbf[1]) {
-      a.wt_bf1 = reinterpret_cast<const uint4*>(u->blob + tail->wbf[1]);
-      a.ist1 = u->blob + tail->isc[1];
-    }
+    if (tail->wbf[1]) a.wt_bf1 = reinterpret_cast<const uint4*>(u->blob + tail->wbf[1]);
   }
   return a;
 }
@@ -350,12 +365,10 @@ static UnetArgs unet_args(const mmd_unet_s* u, const float* x, int t, int n, flo
   a.c[4] = args_chain(u, kU1, 1, &p.up[1], nullptr, t, n);
   a.fin.out = eps;
   a.fin.w5 = reinterpret_cast<const uint4*>(u->blob + p.fin.wbf);
-  a.fin.isc = u->blob + p.fin.isc;
-  a.fin.bias = u->blob + p.fin.bias; a.fin.gamma = u->blob + p.fin.gamma; a.fin.beta = u->blob + p.fin.beta;
+  a.fin.rec5 = u->blob + p.fin.rec;
   a.fin.act = p.fin_act;
   a.fin.w1_bf = reinterpret_cast<const uint4*>(u->blob + p.fin_w1);
-  a.fin.is1 = u->blob + p.fin_is1;
-  a.fin.w1_bias = u->blob + p.fin_b1;
+  a.fin.rec1 = u->blob + p.fin_rec1;
   return a;
 }
 
@@ -535,6 +548,29 @@ int mmd_debug_set_trace(void* dev_ptr) {
 #endif
 
 int mmd_unet_precision(mmd_unet_t u) { return u ? u->precision : -1; }
+
+int mmd_debug_unet_pack(int unet_input_dim, int n_levels, int n_diffusion_steps, const float* const* tensors, const int64_t* numels,
+                        int n_tensors, float* blob_out, size_t blob_cap, size_t* blob_floats, mmd_unet_record_table* tables,
+                        int tables_cap, int* n_tables) {
+  Spec s;
+  MMD_REQUIRE(fused_config(unet_input_dim, n_levels) && build_spec(unet_input_dim, n_levels, s),
+              "mmd_debug_unet_pack: the fused kernel's configuration only (unet_input_dim 32, 3 levels), got (%d, %d)", unet_input_dim, n_levels);
+  MMD_REQUIRE(tensors && numels && n_tensors == (int)s.numel.size(), "mmd_debug_unet_pack: expected %d parameter tensors", (int)s.numel.size());
+  for (int i = 0; i < n_tensors; ++i)
+    MMD_REQUIRE(numels[i] == s.numel[i] && tensors[i] != nullptr, "parameter tensor %d has %lld elements, expected %lld",
+                i, (long long)numels[i], (long long)s.numel[i]);
+  MMD_REQUIRE(n_diffusion_steps >= 1, "n_diffusion_steps must be >= 1");
+  std::vector<float> blob;
+  std::unique_ptr<UnetPack> p(new UnetPack());
+  pack_unet(s, tensors, n_diffusion_steps, blob, *p);
+  MMD_REQUIRE(p->n_tables <= (int)(sizeof(p->tables) / sizeof(p->tables[0])), "mmd_debug_unet_pack: %d record tables exceed the directory", p->n_tables);
+  if (blob_floats) *blob_floats = blob.size();
+  if (n_tables) *n_tables = p->n_tables;
+  if (blob_out) memcpy(blob_out, blob.data(), sizeof(float) * (blob.size() < blob_cap ? blob.size() : blob_cap));
+  if (tables)
+    for (int i = 0; i < p->n_tables && i < tables_cap; ++i) tables[i] = p->tables[i];
+  return 0;
+}
 
 size_t mmd_unet_weight_bytes(mmd_unet_t u) {
   if (!u) return 0;

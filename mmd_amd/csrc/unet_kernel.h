@@ -68,14 +68,10 @@ constexpr int N_PIECES = 2;
 struct FinalArgs {
   float* out;             // eps [n, 64, 4]
   const uint4* w5;        // f16x2 pack of the k5 conv (interleaved column pairs)
-  const float* isc;       // [32] inverse channel scales of w5
-  const float* bias;      // [32]
-  const float* gamma;     // [32] GroupNorm weight
-  const float* beta;      // [32] GroupNorm bias
+  const float* rec5;      // [16] epilogue records of the k5 conv (channel pairs: bias, GroupNorm weight / bias, inverse scales of w5)
   float act;              // static power-of-two scale of the block's output activations = the 1x1 conv's f16x2 input
   const uint4* w1_bf;     // f16x2 pack of the 1x1 conv (one n-tile, columns >= 4 zero)
-  const float* is1;       // [4] inverse channel scales of w1_bf / act
-  const float* w1_bias;   // [4]
+  const float* rec1;      // [4] records of the 1x1 conv's output channels: {bias, inverse channel scale of w1_bf / act, 0, 0}
 };
 
 // GroupNorm-epilogue parameters of a conv for the lane's NT adjacent channels.  They are REQUESTED BEFORE the conv's taps (the
@@ -92,6 +88,96 @@ __device__ __forceinline__ Epi<NT> epi_load(const float* b, const float* g, cons
     e.be[t] = be[c0 + t];
     e.is[t] = isc ? isc[c0 + t] : 1.f;
     e.tb[t] = tb ? tb[c0 + t] : 0.f;
+  }
+  return e;
+}
+// The kernels below read these parameters from RECORD TABLES the packer writes (unet.hip, push_records): one record per channel unit of
+// NT adjacent channels (the lane's c0 .. c0 + NT - 1: unit c0 / NT), its fields in order, each field's NT channels side by side, zero
+// padded to whole float4 -- {b0, b1, g0, g1, be0, be1, is0, is1} for NT = 2 -- so a lane fetches a conv's constants with one
+// global_load_dwordx4 per 16 bytes where the separate arrays took one narrow load per field and channel (a whole vector-memory
+// instruction each, counted by the same in-order vmcnt as the weight ring).  The values are the floats the arrays held.
+constexpr int rec_floats(int fields, int nt) { return (fields * nt + 3) / 4 * 4; }
+template <int FIELDS, int NT> struct Rec {
+  float v[FIELDS * NT];
+  __device__ __forceinline__ float at(int field, int t) const { return v[field * NT + t]; }
+};
+// (whole float4 first; the record's last 1 - 3 floats in front of its padding as one narrower load, so no register waits for a zero)
+template <int FIELDS, int NT>
+__device__ __forceinline__ Rec<FIELDS, NT> rec_load(const float* table, unsigned unit) {
+  typedef float f32x3 __attribute__((ext_vector_type(3)));
+  constexpr int F = FIELDS * NT, Q = F / 4, REM = F % 4;
+  const float* p = table + unit * (unsigned)rec_floats(FIELDS, NT);
+  Rec<FIELDS, NT> r;
+#pragma unroll
+  for (int i = 0; i < Q; ++i) {
+    const f32x4 q = *reinterpret_cast<const f32x4*>(p + 4 * i);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) r.v[4 * i + j] = q[j];
+  }
+  if constexpr (REM == 3) {
+    const f32x3 q = *reinterpret_cast<const f32x3*>(p + 4 * Q);
+    r.v[4 * Q] = q[0]; r.v[4 * Q + 1] = q[1]; r.v[4 * Q + 2] = q[2];
+  } else if constexpr (REM == 2) {
+    const float2 q = *reinterpret_cast<const float2*>(p + 4 * Q);
+    r.v[4 * Q] = q.x; r.v[4 * Q + 1] = q.y;
+  } else if constexpr (REM == 1) {
+    r.v[4 * Q] = p[4 * Q];
+  }
+  return r;
+}
+// the time bias of channels c0 .. c0 + NT - 1 (row t of the time table: the one epilogue parameter that is not a constant of the model),
+// one load per lane
+template <int NT>
+__device__ __forceinline__ void tb_load(float (&d)[NT], const float* tb, unsigned c0) {
+  static_assert(NT == 1 || NT == 2, "a lane owns one channel or an adjacent (even, odd) pair");
+  if constexpr (NT == 2) {
+    const float2 v = *reinterpret_cast<const float2*>(tb + c0);   // (c0 even, rows and blocks of the table start at even columns)
+    d[0] = v.x; d[1] = v.y;
+  } else {
+    d[0] = tb[c0];
+  }
+}
+// fields 0 .. 3 of a record = a GroupNorm epilogue's constants; tb: the conv's time-bias row or null
+template <int NT, int FIELDS>
+__device__ __forceinline__ Epi<NT> epi_of(const Rec<FIELDS, NT>& r, const float* tb, unsigned c0) {
+  Epi<NT> e;
+#pragma unroll
+  for (int t = 0; t < NT; ++t) {
+    e.b[t] = r.at(0, t);
+    e.g[t] = r.at(1, t);
+    e.be[t] = r.at(2, t);
+    e.is[t] = r.at(3, t);
+    e.tb[t] = 0.f;
+  }
+  if (tb) tb_load<NT>(e.tb, tb, c0);
+  return e;
+}
+template <int NT>
+__device__ __forceinline__ Epi<NT> epi_rec(const float* table, const float* tb, unsigned c0) {
+  return epi_of<NT>(rec_load<4, NT>(table, c0 / NT), tb, c0);
+}
+// ... of a stage's first conv A, whose record carries the 1x1 residual conv's bias and inverse weight scales behind them (fields 4, 5)
+template <int NT>
+__device__ __forceinline__ Epi<NT> epi_rec_res(const float* table, const float* tb, unsigned c0, float (&br)[NT], float (&isr)[NT]) {
+  const Rec<6, NT> r = rec_load<6, NT>(table, c0 / NT);
+#pragma unroll
+  for (int t = 0; t < NT; ++t) {
+    br[t] = r.at(4, t);
+    isr[t] = r.at(5, t);
+  }
+  return epi_of<NT>(r, tb, c0);
+}
+// A tail conv's record: its bias and the inverse channel scales of its NP packs (Downsample1d: one; ConvTranspose1d: the two parity passes)
+template <int NT, int NP> struct TailRec { float bt[NT], is[NP][NT]; };
+template <int NT, int NP>
+__device__ __forceinline__ TailRec<NT, NP> tail_rec(const float* table, unsigned c0) {
+  const Rec<1 + NP, NT> r = rec_load<1 + NP, NT>(table, c0 / NT);
+  TailRec<NT, NP> e;
+#pragma unroll
+  for (int t = 0; t < NT; ++t) {
+    e.bt[t] = r.at(0, t);
+#pragma unroll
+    for (int p = 0; p < NP; ++p) e.is[p][t] = r.at(1 + p, t);
   }
   return e;
 }
@@ -194,10 +280,11 @@ __device__ __forceinline__ float dpp_add(float v) {   // v + v[DPP-permuted lane
 constexpr int MAX_IDENT = 3;
 
 struct RtbPtrs {
-  const float* ba; const float* ga; const float* bea; const float* tb;   // conv A: bias, GroupNorm weight / bias, time bias [C_out]
-  const float* bb; const float* gb; const float* beb;                    // conv B
+  // Epilogue records (rec_load) of conv A / conv B per channel unit: bias, GroupNorm weight / bias, inverse per-channel weight scale of
+  // the f16x2 pack (conv B: / act_a); a stage's first conv A: + the 1x1 residual conv's bias and inverse weight scale
+  const float* ra; const float* rb;
+  const float* tb;                          // conv A's time bias [C_out] (row t of the time table)
   const uint4* wa_bf; const uint4* wb_bf;   // f16x2 packs of the two convs
-  const float* isa; const float* isb;       // [C_out] inverse per-channel weight scales of the f16x2 packs (isb: / act_a)
   float act_a;                              // static power-of-two scale of conv A's output activations = conv B's f16x2 input
 };
 
@@ -205,14 +292,11 @@ struct ChainArgs {
   const float* in0;                      // [n, L, C0] network input (first chain only)
   RtbPtrs r0;
   const uint4* wa0_c1_bf;                // conv A pack of the second input chunk (up stages: cat(x, skip))
-  const float* br;                       // bias of the 1x1 residual conv
-  const float* isr;                      // [C_out] inverse scale of the residual weights in their f16x2 pack
   const uint4* wres_bf;                  // f16x2 pack of the 1x1 residual conv (first input chunk)
   const uint4* wres_c1_bf;               // ... of the second input chunk (up stages)
   const uint4* wt_bf0; const uint4* wt_bf1;   // f16x2 pack(s) of the tail conv: Downsample1d, or the two parity passes of Upsample1d
-  const float* ist0; const float* ist1;       // ... their inverse channel scales
   RtbPtrs ri[MAX_IDENT];
-  const float* bt;                       // tail conv bias
+  const float* rt;                       // tail records (tail_rec): the tail conv's bias, the inverse channel scales of its pack(s)
   int n;
 };
 
@@ -247,9 +331,14 @@ static_assert(UNET_LDS_FLOATS * 4 == 76960, "LDS of a workgroup");
 
 // GroupNorm-epilogue parameters of an RTB's conv A (with its time bias, tb_off floats into the table) / conv B for channels c0 ..
 template <int NT>
-__device__ __forceinline__ Epi<NT> epi_a(const RtbPtrs& R, int tb_off, int c0) { return epi_load<NT>(R.ba, R.ga, R.bea, R.tb + tb_off, R.isa, c0); }
+__device__ __forceinline__ Epi<NT> epi_a(const RtbPtrs& R, int tb_off, int c0) { return epi_rec<NT>(R.ra, R.tb + tb_off, c0); }
 template <int NT>
-__device__ __forceinline__ Epi<NT> epi_b(const RtbPtrs& R, int c0) { return epi_load<NT>(R.bb, R.gb, R.beb, nullptr, R.isb, c0); }
+__device__ __forceinline__ Epi<NT> epi_b(const RtbPtrs& R, int c0) { return epi_rec<NT>(R.rb, nullptr, c0); }
+// ... of a stage's first conv A, with the 1x1 residual conv's bias br and inverse weight scales isr from the same record
+template <int NT>
+__device__ __forceinline__ Epi<NT> epi_a_res(const RtbPtrs& R, int tb_off, int c0, float (&br)[NT], float (&isr)[NT]) {
+  return epi_rec_res<NT>(R.ra, R.tb + tb_off, c0, br, isr);
+}
 
 // A weight pack in global memory as a wave reads it, n-tiles tile0 .. tile0 + NT - 1 (`frags` 1 KiB fragments [lane] x 16 B per n-tile): per
 // n-tile a WAVE-UNIFORM base (pack + tile offset: tile0 comes from the wave index, so the whole address is the same in every lane and lives in
@@ -1139,8 +1228,8 @@ __device__ __forceinline__ void chain_body_d0w(const ChainArgs& a, float* lds, i
   rw_zero_halo<GW>(slab, 64, lane, true);
   wave_lds_fence();
   f32x4 acc[4][2], res[4][2];
-  const Epi<2> e0a = epi_a<2>(a.r0, tb_off, c0);
-  const float br0[2] = {a.br[c0], a.br[c0 + 1]}, isr0[2] = {a.isr[c0], a.isr[c0 + 1]};
+  float br0[2], isr0[2];
+  const Epi<2> e0a = epi_a_res<2>(a.r0, tb_off, c0, br0, isr0);
   // ---- RTB 0 conv A (im2col chunk) + the 1x1 residual conv
   {
     u32x4 b[2][2], br[2][2];
@@ -1191,14 +1280,15 @@ __device__ __forceinline__ void chain_body_d0w(const ChainArgs& a, float* lds, i
     tile_scale(acc, ds.s);
     const WTiles<2> wt = w_tiles<2>(a.wt_bf0, GW::FRAGS3, 0, lane);
     u32x4 ring3[3][2][2];
-    const float bt[2] = {a.bt[c0], a.bt[c0 + 1]}, ist[2] = {a.ist0[c0] * ds.inv, a.ist0[c0 + 1] * ds.inv};
+    const TailRec<2, 1> tl = tail_rec<2, 1>(a.rt, c0);
+    const float ist[2] = {tl.is[0][0] * ds.inv, tl.is[0][1] * ds.inv};
     rd_ring_load<GW, 2, 3>(ring3, wt);
     rw_store2<GW, 4>(vs, acc);
     wave_lds_fence();
     // (outputs q = 16 mt + 4 g + r = the even positions 2 q: two M tiles read at stride 2)
     f32x4 y[2][2];
     rd_taps<Stride2<GW, 0, 2>, 2, 1, 3, true, false, 2, 3>(y, y, va + n * 16, wt, wt, ring3);
-    const float mo = tail_epilogue(y, ist, bt);
+    const float mo = tail_epilogue(y, ist, tl.bt);
     __syncthreads();                                         // every wave is done with its slab: the next stage's slab aliases them
     if (lane < MX_SLOTS) (lds + MX_OFF)[wave * MX_SLOTS + lane] = mo;
     char* const lb = reinterpret_cast<char*>(lds);
@@ -1236,8 +1326,8 @@ __device__ __forceinline__ void chain_body_d0s(const ChainArgs& a, float* lds, i
   d0_zero_xin_halo(xin, lane, hf == 0);
   rw_zero_halo<GW>(slab, 64, lane, hf == 0);
   f32x4 acc[2][2], res[2][2];
-  const Epi<2> e0a = epi_a<2>(a.r0, tb_off, c0);
-  const float br0[2] = {a.br[c0], a.br[c0 + 1]}, isr0[2] = {a.isr[c0], a.isr[c0 + 1]};
+  float br0[2], isr0[2];
+  const Epi<2> e0a = epi_a_res<2>(a.r0, tb_off, c0, br0, isr0);
   u32x4 b0[2][2], br[2][2];
   d0_load_wa(a, lane, b0, br);
   __syncthreads();
@@ -1291,14 +1381,15 @@ __device__ __forceinline__ void chain_body_d0s(const ChainArgs& a, float* lds, i
     const DynScale ds = dyn_scale(half_sample_max(mx, sp, hf, lane, rw_absmax(acc)));
     tile_scale(acc, ds.s);
     const WStaged<2> wt = w_staged<2>(wb1, GW::FRAGS3, lane);
-    const float bt[2] = {a.bt[c0], a.bt[c0 + 1]}, ist[2] = {a.ist0[c0] * ds.inv, a.ist0[c0 + 1] * ds.inv};
+    const TailRec<2, 1> tl = tail_rec<2, 1>(a.rt, c0);
+    const float ist[2] = {tl.is[0][0] * ds.inv, tl.is[0][1] * ds.inv};
     rw_store2<GW, 2>(vs, acc);
     staged_weights_landed();
     __syncthreads();
     f32x4 y[1][2];
     rd_ring_load<GW, 2, 2>(ring, wt);
     rd_taps<Stride2<GW, 0, 2>, 2, 1, 3, true, false, 1, 2>(y, y, va + n * 16, wt, wt, ring);
-    const float mo = tail_epilogue(y, ist, bt);
+    const float mo = tail_epilogue(y, ist, tl.bt);
     // (the barrier inside: every wave is done with its slab -- the next stage's slab aliases them -- and the sample's maxima
     // are published for the next stage's dynamic scale)
     const float so = dyn_scale(half_sample_max(mx, sp, hf, lane, mo)).s;
@@ -1372,8 +1463,8 @@ __device__ __forceinline__ void chain_body_d1d(const ChainArgs& a, float* lds, i
     u32x4 ring5[5][2][2];
     const WTiles<2> wpa = wt2(a.r0.wa_bf, GI::FRAGS5), wpr = wt2(a.wres_bf, 2 * GI::KC);
     rd_ring_load<GI, 2, 5>(ring5, wpa);
-    const Epi<2> e0a = epi_a<2>(a.r0, tb_off, c0);
-    const float br[2] = {a.br[c0], a.br[c0 + 1]}, isr[2] = {a.isr[c0], a.isr[c0 + 1]};
+    float br[2], isr[2];
+    const Epi<2> e0a = epi_a_res<2>(a.r0, tb_off, c0, br, isr);
     __syncthreads();                                         // downs.0's tail has written the input slab and its maxima
     TR(trb + 0);
     float inv_in[SW];
@@ -1418,7 +1509,7 @@ __device__ __forceinline__ void chain_body_d1d(const ChainArgs& a, float* lds, i
     float inv[SW];
     mx_scale_tile(mx, s0, acc, inv);
     const WTiles<2> wt = wt2(a.wt_bf0, GH::FRAGS3);
-    const float bt[2] = {a.bt[c0], a.bt[c0 + 1]}, ist[2] = {a.ist0[c0], a.ist0[c0 + 1]};
+    const TailRec<2, 1> tl = tail_rec<2, 1>(a.rt, c0);
     if constexpr (!PF) rd_ring_load<GH, 2, RD1>(ring, wt);
     store_tile();
     __syncthreads();
@@ -1429,8 +1520,8 @@ __device__ __forceinline__ void chain_body_d1d(const ChainArgs& a, float* lds, i
     float m2[2] = {0.f, 0.f};
 #pragma unroll
     for (int sl = 0; sl < SW; ++sl) {
-      const float is[2] = {ist[0] * inv[sl], ist[1] * inv[sl]};
-      m2[sl] = tail_epilogue(sub_tile<1>(y, sl), is, bt);
+      const float is[2] = {tl.is[0][0] * inv[sl], tl.is[0][1] * inv[sl]};
+      m2[sl] = tail_epilogue(sub_tile<1>(y, sl), is, tl.bt);
     }
     __syncthreads();                                         // every wave is done reading the slab the next stage's x slab aliases
     if (lane < 4 * SW) mx[(s0 + (lane >> 2)) * MX_SLOTS + np + 2 * (lane & 3)] = (lane >> 2) ? m2[1] : m2[0];
@@ -1523,8 +1614,8 @@ __device__ __forceinline__ void chain_body_d2d(const ChainArgs& a, float* lds, i
 #pragma unroll
   for (int sm = 0; sm < NS; ++sm) inv_in[sm] = dyn_scale(mx_read(mx, sm)).inv;
   rd_zero_halo<G64>(slab);
-  const Epi<2> e0a = epi_a<2>(a.r0, tb_off, c0);
-  const float br[2] = {a.br[c0], a.br[c0 + 1]}, isr[2] = {a.isr[c0], a.isr[c0 + 1]};
+  float br[2], isr[2];
+  const Epi<2> e0a = epi_a_res<2>(a.r0, tb_off, c0, br, isr);
   rowform_to_rd<D2::C0, D2::XSS, D2::XSTR, NS>(lds, slab, mx);
   __syncthreads();
   {
@@ -1624,8 +1715,8 @@ __device__ __forceinline__ void chain_body_u0d(const ChainArgs& a, float* lds, i
     tile_scale(sub_tile<1>(x0, sm), ds.s);
     tile_scale(sub_tile<1>(x1, sm), ds.s);
   }
-  const Epi<1> e0a = epi_a<1>(a.r0, tb_off, col);
-  const float br[1] = {a.br[col]}, isr[1] = {a.isr[col]};
+  float br[1], isr[1];
+  const Epi<1> e0a = epi_a_res<1>(a.r0, tb_off, col, br, isr);
   store2(x0);
   TR(160);
   __syncthreads();
@@ -1677,7 +1768,7 @@ __device__ __forceinline__ void chain_body_u0d(const ChainArgs& a, float* lds, i
     float inv[NS];
     mx_scale_tile(mx, 0, acc, inv);
     const WTiles<1> wt0 = wt1(a.wt_bf0, 2 * G64::KC * 2), wt1p = wt1(a.wt_bf1, 2 * G64::KC * 2);
-    const float bt[1] = {a.bt[col]}, is0 = a.ist0[col], is1 = a.ist1[col];
+    const TailRec<1, 2> tl = tail_rec<1, 2>(a.rt, col);
     if constexpr (!PF) rd_ring_load<G64, 1, RDC>(ring, wt0);
     rd_store1<G64>(vs64, acc, lane);
     __syncthreads();
@@ -1689,8 +1780,8 @@ __device__ __forceinline__ void chain_body_u0d(const ChainArgs& a, float* lds, i
     // per-sample maxima of the wave's 16 channels go to slot `wave` of mx region 0 (the caller's barrier publishes them)
 #pragma unroll
     for (int sm = 0; sm < NS; ++sm) {
-      const float s0[1] = {is0 * inv[sm]}, s1[1] = {is1 * inv[sm]};
-      const float m = tail_up_epilogue(sub_tile<1>(xe, sm), sub_tile<1>(xo, sm), s0, s1, bt);
+      const float s0[1] = {tl.is[0][0] * inv[sm]}, s1[1] = {tl.is[1][0] * inv[sm]};
+      const float m = tail_up_epilogue(sub_tile<1>(xe, sm), sub_tile<1>(xo, sm), s0, s1, tl.bt);
       if (lane == 0) mx[sm * MX_SLOTS + wave] = m;
     }
   }
@@ -1866,8 +1957,8 @@ __device__ __forceinline__ void chain_body_u1w(const ChainArgs& a, const FinalAr
   u1_store_chunk1(lb, wave, n, g, skip, sc.skip);
   __syncthreads();
   TR(trb + 10);
-  const Epi<2> e0a = epi_a<2>(a.r0, tb_off, c0);
-  const float br[2] = {a.br[c0], a.br[c0 + 1]}, isr[2] = {a.isr[c0], a.isr[c0 + 1]};
+  float br[2], isr[2];
+  const Epi<2> e0a = epi_a_res<2>(a.r0, tb_off, c0, br, isr);
   rd_taps<GA, 2, 0, 5, false, true, 2, RDA>(acc, res, vaA, wp1, wr1, ring);
   TR(trb + 11);
   // ---- from here on the wave is on its own: 32-channel slab
@@ -1922,8 +2013,8 @@ __device__ __forceinline__ void chain_body_u1w(const ChainArgs& a, const FinalAr
     tile_scale(acc, ds.s);
     const WTiles<2> wt0 = wt2(a.wt_bf0, 2 * GB::KC * 2), wt1 = wt2(a.wt_bf1, 2 * GB::KC * 2);
     u32x4 ring2[2][2][2];
-    const float bt[2] = {a.bt[c0], a.bt[c0 + 1]};
-    const float is0[2] = {a.ist0[c0] * ds.inv, a.ist0[c0 + 1] * ds.inv}, is1[2] = {a.ist1[c0] * ds.inv, a.ist1[c0 + 1] * ds.inv};
+    const TailRec<2, 2> tl = tail_rec<2, 2>(a.rt, c0);
+    const float is0[2] = {tl.is[0][0] * ds.inv, tl.is[0][1] * ds.inv}, is1[2] = {tl.is[1][0] * ds.inv, tl.is[1][1] * ds.inv};
     rd_ring_load<GB, 2, 2>(ring2, wt0);
     rw_store2<GB, 2>(vsB, acc);
     wave_lds_fence();
@@ -1931,7 +2022,7 @@ __device__ __forceinline__ void chain_body_u1w(const ChainArgs& a, const FinalAr
     rd_taps<GB, 2, 1, 2, true, false, 2, 2>(e, res, vaB, wt0, wt0, ring2);
     rd_ring_load<GB, 2, 2>(ring2, wt1);
     rd_taps<GB, 2, 2, 2, true, false, 2, 2>(o, res, vaB, wt1, wt1, ring2);
-    const DynScale df = dyn_scale(tail_up_epilogue(e, o, is0, is1, bt));
+    const DynScale df = dyn_scale(tail_up_epilogue(e, o, is0, is1, tl.bt));
     inv_f = df.inv;
     wave_lds_fence();                                        // the tail's reads are done: 64-row geometry
     rw_zero_halo<GF>(slab, 64, lane, true);
@@ -1945,8 +2036,9 @@ __device__ __forceinline__ void chain_body_u1w(const ChainArgs& a, const FinalAr
     const WTiles<1> w1 = w_tiles<1>(f.w1_bf, 2 * GF::KC, 0, lane);
     u32x4 ring1[1][1][2];
     rd_ring_load<GF, 1, 1>(ring1, w1);
-    const Epi<2> ef = epi_load<2>(f.bias, f.gamma, f.beta, nullptr, f.isc, c0);
-    const float b1 = f.w1_bias[n & 3], s1 = f.is1[n & 3];
+    const Epi<2> ef = epi_rec<2>(f.rec5, nullptr, c0);
+    const float2 o1 = *reinterpret_cast<const float2*>(f.rec1 + (n & 3) * 4);
+    const float b1 = o1.x, s1 = o1.y;
     wave_lds_fence();
     rd_taps<GF, 2, 0, 5, true, false, 4, 5>(y, y, vaF, wf, wf, ring5);
     rw_gn_mish_whole<4, 2, 2, 256, true>(y, ef.b, ef.g, ef.be, ef.is, inv_f, act_scale(f.act), [](int, int, int) { return 0.f; });
@@ -2017,8 +2109,8 @@ __device__ __forceinline__ void chain_body_u1s(const ChainArgs& a, const FinalAr
   u1_store_chunk1(lb, wave, n, g, skip, sc.skip);
   __syncthreads();
   TR(trb + 10);
-  const Epi<2> e0a = epi_a<2>(a.r0, tb_off, c0);
-  const float br[2] = {a.br[c0], a.br[c0 + 1]}, isr[2] = {a.isr[c0], a.isr[c0 + 1]};
+  float br[2], isr[2];
+  const Epi<2> e0a = epi_a_res<2>(a.r0, tb_off, c0, br, isr);
   rd_taps<GA, 2, 0, 5, false, true, 1, RDA>(acc, res, vaA, wp1, wr1, ring);
   TR(trb + 11);
   // ---- 32-channel slab of the sample, shared by its two waves
@@ -2073,8 +2165,8 @@ __device__ __forceinline__ void chain_body_u1s(const ChainArgs& a, const FinalAr
     const DynScale ds = dyn_scale(half_sample_max(mx, sp, hf, lane, rw_absmax(acc)));
     tile_scale(acc, ds.s);
     const WStaged<2> wt0 = w_staged<2>(wb1, TF / 2, lane), wt1 = w_staged<2>(wb1 + TF * 1024, TF / 2, lane);
-    const float bt[2] = {a.bt[c0], a.bt[c0 + 1]};
-    const float is0[2] = {a.ist0[c0] * ds.inv, a.ist0[c0 + 1] * ds.inv}, is1[2] = {a.ist1[c0] * ds.inv, a.ist1[c0 + 1] * ds.inv};
+    const TailRec<2, 2> tl = tail_rec<2, 2>(a.rt, c0);
+    const float is0[2] = {tl.is[0][0] * ds.inv, tl.is[0][1] * ds.inv}, is1[2] = {tl.is[1][0] * ds.inv, tl.is[1][1] * ds.inv};
     rw_store2<GB, 1>(vsB, acc);
     staged_weights_landed();
     __syncthreads();
@@ -2084,7 +2176,7 @@ __device__ __forceinline__ void chain_body_u1s(const ChainArgs& a, const FinalAr
     rd_taps<GB, 2, 1, 2, true, false, 1, 2>(e, res, vaB, wt0, wt0, ring2);
     rd_ring_load<GB, 2, 2>(ring2, wt1);
     rd_taps<GB, 2, 2, 2, true, false, 1, 2>(o, res, vaB, wt1, wt1, ring2);
-    const float m = tail_up_epilogue(e, o, is0, is1, bt);
+    const float m = tail_up_epilogue(e, o, is0, is1, tl.bt);
     const DynScale df = dyn_scale(half_sample_max(mx, sp, hf, lane, m));   // (its barrier: the tail's reads are done, 64-row geometry)
     inv_f = df.inv;
     rw_zero_halo<GF>(slab, 64, lane, hf == 0);
@@ -2097,8 +2189,9 @@ __device__ __forceinline__ void chain_body_u1s(const ChainArgs& a, const FinalAr
     const WTiles<1> w1 = w_tiles<1>(f.w1_bf, 2 * GF::KC, 0, lane);
     u32x4 ring1[1][1][2];
     rd_ring_load<GF, 1, 1>(ring1, w1);
-    const Epi<2> ef = epi_load<2>(f.bias, f.gamma, f.beta, nullptr, f.isc, c0);
-    const float b1 = f.w1_bias[n & 3], s1 = f.is1[n & 3];
+    const Epi<2> ef = epi_rec<2>(f.rec5, nullptr, c0);
+    const float2 o1 = *reinterpret_cast<const float2*>(f.rec1 + (n & 3) * 4);
+    const float b1 = o1.x, s1 = o1.y;
     staged_weights_landed();
     __syncthreads();                                         // the final block's input and weights are complete
     rd_ring_load<GF, 2, 2>(ring2, wf);

@@ -3,7 +3,7 @@
 # unet_kernel back to back, sampled with rocm-smi.  Usage (GPU box): bash tools/gpu_power.sh > gpurun_out/power.txt
 sample() { /opt/rocm/bin/rocm-smi --showclocks --showpower 2>&1 | awk '/sclk/{c=$NF} /Power \(W\)/{p=$NF} END{printf "sclk %s power %s W", c, p}'; }
 echo "idle: $(sample)"
-for cls in mfma16 mfma32 lds valu l2 idle; do
+for cls in ${POWER_CLASSES:-mfma16 mfma32 lds valu l2 l1 l2d l1d idle}; do
   ./build_tmp/power_probe $cls 5 > /tmp/pp_$cls.txt 2>&1 &
   PID=$!
   sleep 2.5; s1=$(sample); sleep 0.5; s2=$(sample); sleep 0.5; s3=$(sample)

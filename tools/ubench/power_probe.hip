@@ -3,7 +3,7 @@
 // SECONDS of wall time on every CU at the kernel's occupancy (two 4-wave workgroups per CU) with random operand bits, while the
 // calling script samples `rocm-smi --showclocks --showpower`; prints the sustained rate.  Classes: mfma16 (v_mfma_f32_16x16x32_f16),
 // mfma32 (v_mfma_f32_32x32x16_f16), lds (ds_read_b128, conflict free), valu (v_pk_fma_f32), l2 (global_load_dwordx4 of a 2 MB
-// buffer: L2 hits), l1 (the same over 16 KB: L1 hits), idle (s_sleep).
+// buffer: L2 hits), l1 (the same over 16 KB: L1 hits), l2d / l1d (global_load_dword over the same footprints: the narrow load), idle (s_sleep).
 // Build: hipcc --offload-arch=gfx950 -O3 tools/ubench/power_probe.hip -o power_probe;  run: power_probe <class> [seconds]
 #include <hip/hip_runtime.h>
 #include <chrono>
@@ -101,6 +101,23 @@ __global__ __launch_bounds__(256, 2) void k_l2(float* out, const u32x4* buf, int
   }
   out[blockIdx.x * 256 + threadIdx.x] = __builtin_bit_cast(float, acc.x ^ acc.y ^ acc.z ^ acc.w);
 }
+__global__ __launch_bounds__(256, 2) void k_l2d(float* out, const unsigned* buf, int iters, unsigned mask) {
+  // the narrow form of k_l2: a wave reads 256 B contiguous (global_load_dword), 8 loads in flight, walking (mask + 1) / 4 KB of the
+  // buffer: 2 MB = L2 hits, 16 KB = L1 hits -- a whole vector-memory instruction (64 addresses, one tag lookup per 128 B line) for a
+  // quarter of k_l2's bytes: the energy of the instruction itself
+  const int lane = threadIdx.x & 63, wid = blockIdx.x * 4 + (threadIdx.x >> 6);
+  unsigned acc = 0u;
+  unsigned pos = wid * 8;
+  for (int it = 0; it < iters; ++it) {
+    unsigned v[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) v[k] = buf[(((pos + k) & mask) << 6) + lane];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) acc ^= v[k];
+    pos += 8 * 37;
+  }
+  out[blockIdx.x * 256 + threadIdx.x] = __builtin_bit_cast(float, acc);
+}
 __global__ __launch_bounds__(256, 2) void k_idle(float* out, int iters) {
   for (int it = 0; it < iters; ++it) __builtin_amdgcn_s_sleep(127);
   out[blockIdx.x * 256 + threadIdx.x] = 0.f;
@@ -128,6 +145,8 @@ int main(int argc, char** argv) {
     else if (!strcmp(cls, "valu")) { hipLaunchKernelGGL(k_valu, dim3(nb), dim3(256), 0, 0, out, iters); unit = "v_pk_fma_f32"; }
     else if (!strcmp(cls, "l2")) { hipLaunchKernelGGL(k_l2, dim3(nb), dim3(256), 0, 0, out, buf, iters / 4, 2047u); unit = "global_load_dwordx4 (L2 hit)"; }
     else if (!strcmp(cls, "l1")) { hipLaunchKernelGGL(k_l2, dim3(nb), dim3(256), 0, 0, out, buf, iters / 4, 15u); unit = "global_load_dwordx4 (L1 hit)"; }
+    else if (!strcmp(cls, "l2d")) { hipLaunchKernelGGL(k_l2d, dim3(nb), dim3(256), 0, 0, out, reinterpret_cast<const unsigned*>(buf), iters / 4, 8191u); unit = "global_load_dword (L2 hit)"; }
+    else if (!strcmp(cls, "l1d")) { hipLaunchKernelGGL(k_l2d, dim3(nb), dim3(256), 0, 0, out, reinterpret_cast<const unsigned*>(buf), iters / 4, 63u); unit = "global_load_dword (L1 hit)"; }
     else { hipLaunchKernelGGL(k_idle, dim3(nb), dim3(256), 0, 0, out, iters / 16); unit = "s_sleep"; }
   };
   launch();
@@ -141,7 +160,7 @@ int main(int argc, char** argv) {
     launches += 4;
     el = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   } while (el < seconds);
-  const double it = !strcmp(cls, "l2") || !strcmp(cls, "l1") ? iters / 4 : !strcmp(cls, "mfma16") || !strcmp(cls, "mfma32") || !strcmp(cls, "lds") || !strcmp(cls, "valu") ? iters : iters / 16;
+  const double it = !strcmp(cls, "l2") || !strcmp(cls, "l1") || !strcmp(cls, "l2d") || !strcmp(cls, "l1d") ? iters / 4 : !strcmp(cls, "mfma16") || !strcmp(cls, "mfma32") || !strcmp(cls, "lds") || !strcmp(cls, "valu") ? iters : iters / 16;
   const double wave_instr = (double)launches * nb * 4 * it * per_iter;
   printf("%s: %.3f s, %ld launches, %.4g wave-instructions/s of %s (%.2f per CU per ns)\n", cls, el, launches, wave_instr / el, unit,
          wave_instr / el / 256 / 1e9);
